@@ -1,6 +1,6 @@
-// Stand-in for the reference's common/include/masks_visualization_kernels.hpp, used ONLY where the reference tree is absent
-// (the GPU box): just the declaration the HIP shim defines.  With /root/reference present the adapter check compiles against
-// the reference's own header instead (adapters/Makefile).
+// Stand-in for the reference's common/include/masks_visualization_kernels.hpp, used unless the adapter check is pointed at the
+// reference tree: just the declaration the HIP shim defines.  With REF_INC set the adapter check compiles against the
+// reference's own header instead (adapters/Makefile).
 #pragma once
 #include <cstdint>
 #include <opencv2/opencv.hpp>

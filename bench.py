@@ -27,9 +27,11 @@ resident in HBM and ``--streams`` frames in flight per GPU.  The same JSON line 
   gather_fps                 : the metric configuration with the per-frame RCCL all-gather enqueued (world 1): the N = 1 anchor of --gather
 p50 / p99 are taken over --latency-iters (default 1000) synchronised iterations after 50 warm-up ones: the reference's protocol
 (Models/data_utils/benchmark.py:17-47).
-Timing: with ``--steps K`` given (the driver's form) a timed region is EXACTLY K steps, fenced on both sides; the region is repeated until
-``--min-seconds`` (1 s) have been measured and the MEDIAN region is reported (``timed_regions`` in the line; a 20-step region is 37 ms, and one such
-sample moves by +-2 %).  Without ``--steps``: 300, raised until one region lasts ``--min-seconds``.
+Timing: with ``--steps K`` given (the driver's form) the timed region is EXACTLY K steps, fenced on both sides, after ``--warmup W`` untimed
+ones; ``ms_per_step`` is that region's wall time / K (a 20-step region is 37 ms, and one such sample moves by +-2 %: pick K from ms_per_step).
+Without ``--steps``: 300, raised until the region lasts ``--min-seconds``.
+``--dump-outputs DIR``: after the `value` leg's timed region, what its last step computed -- every network's fp32 logits and class map -- is
+written as DIR/<network>_{logits,mask}.npy (float32, a few MB); the weights and frames are seeded, so two builds can be compared output for output.
 
 Multi-GPU: the path shards by camera: rank r owns camera r, weights replicated, no data-path collective (the
 reference has none) -> "scaling": "weak".  ``--gather`` adds the per-frame RCCL all-gather of the per-camera masks through
@@ -209,9 +211,8 @@ def main():
     os.dup2(2, 1)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="timed steps K.  Given: EXACTLY K steps per timed region (the contract), repeated over several such "
-                    "regions until --min-seconds have been measured, `value` from the MEDIAN region (`timed_regions` in the line).  Absent: 300, raised so "
-                    "that one region lasts --min-seconds")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps K.  Given: EXACTLY K steps in the timed region (the contract).  Absent: 300, raised so "
+                    "that the region lasts --min-seconds")
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--workload", default="seg+3d", choices=sorted(WORKLOADS))
     ap.add_argument("--kind", default=None, help="deprecated alias: --workload <kind>")
@@ -221,7 +222,7 @@ def main():
     ap.add_argument("--streams", type=int, default=3,
                     help="frames in flight per GPU (independent engines / HIP streams, round-robin): the latency-bound "
                          "encoder of frame n+1 overlaps the MFMA-bound decoder of frame n")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="floor of every timed region")
+    ap.add_argument("--min-seconds", type=float, default=1.0, help="floor of every timed region when --steps is not given")
     ap.add_argument("--gather", action="store_true", help="all-gather per-camera masks every step (RCCL through the C ABI)")
     ap.add_argument("--no-fork", action="store_true", help="enqueue the base engine and its heads one after the other (vp_enqueue) "
                     "instead of one forked graph per frame (vp_enqueue_multi)")
@@ -230,6 +231,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the cpu_baseline leg (0 = all host cores, max 32)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the `value` leg's last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--latency-iters", type=int, default=1000, help="synchronised iterations behind p50 / p99 (benchmark.py:17-47: 50 warm-up + 1000)")
     ap.add_argument("--leg", default=None, choices=["three-heads-one-camera"], help="internal: one leg in a child process (see three_heads_note)")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=VALUE",
@@ -317,23 +319,20 @@ def main():
         return el
 
     def throughput(cams, steps, warmup, gather=False):
-        """(K, seconds of one K-step region).  --steps given: K = steps exactly, the region repeated (each one fenced on both sides, max over ranks) until
-        --min-seconds are covered, at most 40 times, and the MEDIAN region reported; otherwise K is raised until one region lasts --min-seconds."""
-        timed(cams, max(1, warmup), gather)
-        probe = timed(cams, min(max(steps, 1), 20), gather) / min(max(steps, 1), 20)
+        """(K, seconds of the K-step region).  `warmup` untimed steps first.  --steps given: K = steps exactly, ONE region fenced on both sides
+        (max over ranks); otherwise K is raised until the region lasts --min-seconds."""
+        if warmup > 0:
+            timed(cams, warmup, gather)
         if exact_steps:
             k = max(1, steps)
-            regions = max(1, min(40, int(math.ceil(args.min_seconds / max(probe * k, 1e-6)))))
         else:
-            k, regions = max(steps, int(math.ceil(1.15 * args.min_seconds / max(probe, 1e-6)))), 1
-        if dist is not None:  # every rank must run the same number of steps and regions
-            t = torch.tensor([k, regions], dtype=torch.int64, device="cuda")
+            probe = timed(cams, 20, gather) / 20
+            k = max(steps, int(math.ceil(1.15 * args.min_seconds / max(probe, 1e-6))))
+        if dist is not None:  # every rank must run the same number of steps
+            t = torch.tensor([k], dtype=torch.int64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            k, regions = int(t[0].item()), int(t[1].item())
-        els = sorted(timed(cams, k, gather) for _ in range(regions))
-        throughput.regions = regions
-        return k, els[len(els) // 2]
-    throughput.regions = 1
+            k = int(t[0].item())
+        return k, timed(cams, k, gather)
 
     def latency(cam, iters):
         lat = []
@@ -345,18 +344,26 @@ def main():
                 lat.append((time.perf_counter() - t1) * 1e3)
         return np.array(lat)
 
-    def three_figures(cams, steps, warmup, gather=False):
+    def dump_outputs(cam, out_dir):
+        """What a caller of the timed path receives for the frame `cam` ran last: every network's fp32 logits and u8 class map (as float32)."""
+        os.makedirs(out_dir, exist_ok=True)
+        for e in [cam.base] + cam.heads:
+            np.save(os.path.join(out_dir, f"{e.kind}_logits.npy"), e.logits().astype(np.float32))
+            np.save(os.path.join(out_dir, f"{e.kind}_mask.npy"), e.mask().astype(np.float32))
+
+    def three_figures(cams, steps, warmup, gather=False, dump_dir=None):
         # several cameras in flight: engines one after the other (the chip is full; forked heads only add contention);
         # one camera / one frame at a time: the backbone-only heads forked behind the shared encoder (vp_set_multi_fork)
         for c in cams:
             c.set_fork(False)
         k, el = throughput(cams, steps, warmup, gather)
-        main_regions = throughput.regions
+        if dump_dir is not None and rank == 0:
+            dump_outputs(cams[(k - 1) % len(cams)], dump_dir)  # the slot timed() enqueued last
         cams[0].set_fork(True)
         k1, el1 = throughput(cams[:1], max(steps // 3, 1), 3)
         lat = latency(cams[0], args.latency_iters)
         cams[0].set_fork(False)
-        return dict(steps=k, elapsed=el, regions=main_regions, fps=world * k / el, single=k1 / el1, latency_iters=len(lat),
+        return dict(steps=k, elapsed=el, fps=world * k / el, single=k1 / el1, latency_iters=len(lat),
                     p50=float(np.percentile(lat, 50)), p99=float(np.percentile(lat, 99)))
 
     def ego_engine():
@@ -408,7 +415,7 @@ def main():
 
     if args.gather:
         comms = make_comms()
-    main_fig = three_figures(cams, args.steps, args.warmup, args.gather)
+    main_fig = three_figures(cams, args.steps, args.warmup, args.gather, dump_dir=args.dump_outputs)
 
     # ---- the N = 1 anchor of the multi-camera exchange: the same throughput leg with the per-frame RCCL all-gather of the
     # class maps enqueued behind every frame (vp_gather, world 1), so the first 8-GPU `--gather` run has its reference point from this command
@@ -736,7 +743,7 @@ def main():
             "metric": f"frames/sec ({wl} {fw}x{fh}, one camera per GPU: preprocess + shared encoder + "
                       f"{len(kinds)} decoder(s) + decode per frame); p50 per-frame latency beside it",
             "value": round(main_fig["fps"], 2), "unit": "frames/s", "n_gpus": world, "steps": main_fig["steps"],
-            "steps_requested": args.steps, "timed_regions": main_fig["regions"], "warmup": args.warmup,
+            "steps_requested": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * main_fig["elapsed"] / main_fig["steps"], 4), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": prec_name, "data": "synthetic",
             "config": {"workload": f"BASELINE.json metric configuration: {wl} on one {fw}x{fh} camera per GPU, batch 1, "
