@@ -276,6 +276,17 @@ Act* Engine::add_upconv(const std::string& name, const Act* in, const Act* skip_
   }
   ns = std::max(1, std::min(ns, n_chunks));
   p.nsplit = ns;
+  // Compacted form (kernels_upconv.hip CPT) where runs of row-major pixels need fewer workgroups than the patches: the neck's 10x20 (one run of 256
+  // instead of two 16x16 patches, 39 % live) and 20x40 (7 runs of 128 instead of 9 8x16 patches, 69 % live) maps.  The K slices stay what the patch
+  // grid chose: another count would regroup the fp32 sums of upconv_finish_kernel (the results are bit-identical to the patch form's as it is), and
+  // the workgroups not launched go to the other cameras' work.  Parity engines only (the fp16 form is not instantiated compacted).
+  // VP_UPCONV_COMPACT (developer knob): 0 = the patch form everywhere, for A/B runs; 1 = the compacted form wherever it fits (tests).
+  {
+    const long long px = sh == 6 ? 256 : 128, runs = ((long long)in->H * in->W + px - 1) / px;
+    const char* e = dev_option("VP_UPCONV_COMPACT");
+    const bool want = e ? e[0] == '1' : runs < (sh == 6 ? t16 : t8);
+    p.compact = (!x1 && want && upconv_compact_fits(in->H, in->W, sh)) ? 1 : 0;
+  }
   p.partial = ns > 1 ? static_cast<float*>(dalloc((size_t)ns * 4 * in->H * in->W * coutw * sizeof(float), false)) : nullptr;
   if (!upconv_supported(p, sh)) throw std::invalid_argument("composed up-sampling stage: shape not covered: " + name);
   Op op;

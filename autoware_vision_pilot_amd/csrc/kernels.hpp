@@ -272,9 +272,12 @@ struct UpconvParams {
   int act;               // ACT_GELU | ACT_NONE
   int nsplit;            // K slices over the chunk list (> 1: fp32 partials + upconv_finish_kernel)
   float* partial;        // [nsplit][4 H W][CoutW]
+  int compact;           // 1: the compacted form (runs of row-major pixels instead of patches, kernels_upconv.hip); needs upconv_compact_fits
 };
 // shapes: 6 = 8 waves, 16x16 low-resolution pixels x 128 channels per phase (one workgroup per CU); 7 = 4 waves, 8x16 pixels x 128 channels (two per CU)
 bool upconv_supported(const UpconvParams& p, int shape);
+// whether the compacted form's halo windows of an H x W map fit the shape's LDS plan (maps up to 48 columns wide on shape 7, ~60 on shape 6)
+bool upconv_compact_fits(int H, int W, int shape);
 // The K axis of one output phase (py, px) is a list of 32-channel CHUNKS, each with its own tap list (a K "step" = one chunk x one tap = one weight
 // tile of CoutW x 32 and one shifted read of the chunk's halo image):
 //   chunks [0, Cin / 32): the low-resolution input, 4 taps (a, b) in {0, 1}^2 = low-resolution pixel (y + py - 1 + a, x + px - 1 + b);

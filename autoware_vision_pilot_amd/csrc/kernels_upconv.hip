@@ -22,6 +22,13 @@
 //     the step's barrier) and the registers are refilled with chunk c + 2 at once: a halo has as many steps to arrive as its predecessor has taps;
 //   * epilogue: fmaf(acc, 2^-prescale[phase][co], bias[row class][column class][co]), exact GELU, (hi, lo) split, pixel-shuffle store: every pixel's 128
 //     channels are 256 contiguous bytes per plane; split-K slices (the small maps of the neck) leave fp32 partials for upconv_finish_kernel.
+// COMPACTED form (CPT; the maps that the patches tile badly, engine_upconv.cpp): a workgroup owns a RUN of PX consecutive low-resolution pixels in
+// row-major order instead of a patch (10x20: one run of 256 instead of two 16x16 patches; 20x40: 7 runs of 128 instead of 9 8x16 patches).  The halo
+// image is the window of the map's 2-D grid (W + 2 columns, origin row yA - 1) between the first pixel a phase's taps read and the last: rows at a
+// pitch of 80 W + 256 bytes, so the LDS address of run pixel k is 80 k + 256 (row) == 80 k (mod 256) and a 16-lane group of 16 consecutive run pixels
+// stays on 16 distinct bank slots across a row wrap (the lane_to_px16 argument, conv_epilogue.hpp).  A tap is still an LDS address offset (a * pitch +
+// b * 80); each lane's fragment offsets are computed once; fragments past the run's end issue no reads and no MFMAs.  Same K order and operands per
+// output pixel as the patch form: bit-identical results.
 #include <algorithm>
 #include <cstdlib>
 
@@ -42,6 +49,23 @@ struct PixPhase {
     return (y < H && x < W) ? (2 * y + py) * (2 * W) + 2 * x + px : -1;
   }
 };
+// the same for the compacted form: fragment q >> 5 = run pixels [kA + 32 (q >> 5), + 32); lane_to_px16's 16-lane groups take 16 consecutive ones
+struct PixRun {
+  int kA, kE, W, py, px;   // run [kA, kE) of row-major low-resolution pixels, map width
+  __device__ __forceinline__ int operator()(int q) const {
+    int rowbit, c;
+    lane_to_px16(q & 31, rowbit, c);
+    const int k = kA + (q >> 5) * 32 + 16 * rowbit + c;
+    if (k >= kE) return -1;
+    const int y = k / W, x = k - y * W;
+    return (2 * y + py) * (2 * W) + 2 * x + px;
+  }
+};
+// bytes of one plane of a halo image: the patch form's (TH + 2) x 18 pixels; the compacted form of the 4-wave shape takes the whole staging capacity
+// (3 pieces per thread = 192 pixels: a 128-pixel run of a map up to 48 columns wide), 79 872 B of LDS in all: still two workgroups per CU
+constexpr int upconv_halo_bytes(int TH, bool CPT) { return (CPT && TH == 8) ? 192 * 80 : (TH + 2) * 18 * 80; }
+// halo pixels the staging moves: 3 pieces of 16 bytes per thread, 4 per pixel
+constexpr int upconv_halo_capacity(int nth) { return 3 * nth / 4; }
 // bias class of high-resolution pixel m (row-major, width W2, height H2): (first row ? 0 : last row ? 2 : 1) * 3 + the same for the column
 __device__ __forceinline__ int bias_class(int m, int H2, int W2) {
   const int Y = m / W2, X = m - Y * W2;
@@ -72,11 +96,12 @@ __device__ __forceinline__ int bias_class(int m, int H2, int W2) {
 // of that chunk is zeroed at the halo store and its weights are zero (half of those steps' MFMAs multiply zeros: up to 18 % of a stage's steps, accepted).
 // ABL (tools/upconv_ablate.hip only; 0 in the library): 1 = no halo loads / stores after the prologue, 2 = no MFMA, 16 = no epilogue (the accumulators stay
 // alive through a store no launch takes), 32 = epilogue arithmetic without the global stores, 128 = no weight DMA after the prologue
-template <int CO_TILE, int TH, int WCO, int WPX, bool HDB, int ACT, bool SPLITK, bool X1 = false, int ABL = 0>
+// CPT: the compacted form (header comment); the engine passes p.compact = 1 to launch_upconv
+template <int CO_TILE, int TH, int WCO, int WPX, bool HDB, int ACT, bool SPLITK, bool X1 = false, int ABL = 0, bool CPT = false>
 __global__ __launch_bounds__(64 * WCO * WPX, 2) void upconv_x3_kernel(const UpconvParams p) {
   constexpr int NTH = 64 * WCO * WPX;
   constexpr int TW = 16, ROWB = 80, HWD = TW + 2, HPX = (TH + 2) * HWD, PX = TH * TW;
-  constexpr int HALO_BYTES = HPX * ROWB, WROW = 64, W_BYTES = CO_TILE * WROW;
+  constexpr int HALO_BYTES = upconv_halo_bytes(TH, CPT), WROW = 64, W_BYTES = CO_TILE * WROW;
   constexpr int HCHUNKS = HPX * 4, HP = (HCHUNKS + NTH - 1) / NTH;
   constexpr int MT = CO_TILE / WCO / 32, NT = PX / WPX / 32;
   constexpr int NHB = HDB ? 2 : 1;
@@ -90,7 +115,7 @@ __global__ __launch_bounds__(64 * WCO * WPX, 2) void upconv_x3_kernel(const Upco
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wco = wave / WPX, wpx = wave % WPX;
   const int tiles_x = (p.W + TW - 1) / TW;
-  const int n_px_tiles = tiles_x * ((p.H + TH - 1) / TH);
+  const int n_px_tiles = CPT ? (p.H * p.W + PX - 1) / PX : tiles_x * ((p.H + TH - 1) / TH);
   const int n_co_tiles = p.CoutW / CO_TILE;
   int vid;  // XCD-aware workgroup -> tile map (see kernels_conv3x3.hip)
   {
@@ -114,7 +139,13 @@ __global__ __launch_bounds__(64 * WCO * WPX, 2) void upconv_x3_kernel(const Upco
   }
   const int py = phase >> 1, px = phase & 1;
   const int tyi = tile_px / tiles_x, txi = tile_px - tyi * tiles_x;
-  const int y0 = tyi * TH, x0 = txi * TW;
+  const int y0 = tyi * TH, x0 = txi * TW;   // (patch form)
+  // compacted form: run [kA, kE), first pixel (yA, xA), last (yE, xE)
+  const int kA = tile_px * PX, kE = min(kA + PX, p.H * p.W);
+  const int yA = kA / p.W, xA = kA - yA * p.W, yE = (kE - 1) / p.W, xE = (kE - 1) - yE * p.W;
+  // halo row pitch (bytes) and the part of a tap's offset that depends on the phase (the compacted window starts at the phase's first read pixel)
+  const int hrp = CPT ? p.W * ROWB + 256 : HWD * ROWB;
+  const int tpy = CPT ? 0 : py, tpx = CPT ? 0 : px;
   const int co0 = tile_co * CO_TILE;
   // channel counts the chunk list is built on: X1 chunks are 64 channels wide = two 32-channel halves
   const int CinV = X1 ? p.Cin >> 1 : p.Cin, CsV = X1 ? ((p.Cs + 63) >> 6) << 5 : p.Cs;
@@ -139,24 +170,50 @@ __global__ __launch_bounds__(64 * WCO * WPX, 2) void upconv_x3_kernel(const Upco
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
   // fragment addressing (same LDS image and lane maps as the halo kernel)
   int b_ofs0;  // pixel tile j of the wave sits two halo rows further: + j * 2 * HWD * ROWB
+  int b_ofs[NT];   // compacted form: per fragment (dead lanes read the run's first pixel)
+  int nlj = NT;    // compacted form: live fragments of this wave (wave-uniform)
   {
     int rowbit, c;
     lane_to_px16(lane & 31, rowbit, c);
     b_ofs0 = ((2 * (wpx * NT) + rowbit) * HWD + c) * ROWB + (lane >> 5) * 16;
+    if constexpr (CPT) {
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        int k = kA + (wpx * NT + j) * 32 + 16 * rowbit + c;
+        if (k >= kE) k = kA;
+        const int y = k / p.W, x = k - y * p.W;
+        b_ofs[j] = (y - yA) * hrp + (x - xA) * ROWB + (lane >> 5) * 16;
+      }
+      nlj = __builtin_amdgcn_readfirstlane(min(NT, max(0, (kE - kA + 31) / 32 - wpx * NT)));
+    }
   }
   const int a_swz = ((lane & 31) >> 2) & 3;
   const int a_ofs0 = (wco * 32 + (lane & 31)) * WROW + (((lane >> 5) ^ a_swz) << 4);  // K sub-step 1: chunk index ^ 2 -> ^ 32 bytes
 
   // ---- staging assignment: thread t moves 16-byte piece t + NTH * pc of a halo image (pieces of one thread sit NTH / 4 pixels apart).
   // Element offsets of the piece's pixel in the two sources (-1: outside the map, beyond the image, or a pixel this phase never reads)
-  int h_gx[HP], h_gs[HP];
+  // Compacted form: piece pixel hp = grid pixel lg0 + hp of the (W + 2)-column grid (origin: map pixel (yA - 1, -1)), from the phase's first read pixel
+  // (yA + py, xA + px) to the last (yE + py + 1, xE + px + 1): cnt pixels (<= the staging capacity, upconv_compact_fits); h_ls = its LDS offset or -1
+  int h_gx[HP], h_gs[HP], h_ls[HP];
 #pragma unroll
   for (int pc = 0; pc < HP; ++pc) {
     const int hidx = tid + NTH * pc;
     const int hp = hidx >> 2, ch = hidx & 3;
-    const int hy = hp / HWD, hx = hp - hy * HWD;
-    const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-    const bool ok = hidx < HCHUNKS && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W && hy >= py && hy <= py + TH && hx >= px && hx <= px + TW;
+    int gy, gx;
+    bool ok;
+    if constexpr (CPT) {
+      const int gw = p.W + 2, lg = py * gw + xA + px + hp, cnt = (yE - yA + 1) * gw + xE - xA + 2;
+      const int r = lg / gw, cc = lg - r * gw;
+      gy = yA - 1 + r;
+      gx = cc - 1;
+      ok = hp < cnt && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+      h_ls[pc] = hp < cnt ? (r - py) * hrp + (cc - xA - px) * ROWB + ch * 16 : -1;
+    } else {
+      const int hy = hp / HWD, hx = hp - hy * HWD;
+      gy = y0 - 1 + hy;
+      gx = x0 - 1 + hx;
+      ok = hidx < HCHUNKS && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W && hy >= py && hy <= py + TH && hx >= px && hx <= px + TW;
+    }
     h_gx[pc] = ok ? (gy * p.W + gx) * p.Cin + ch * 8 : -1;
     h_gs[pc] = ok ? (4 * gy * p.W + 2 * gx) * p.Cs + ch * 8 : -1;   // skip pixel (2 gy, 2 gx) of the 2H x 2W map; the class adds (qy * 2W + qx) * Cs
   }
@@ -209,8 +266,8 @@ __global__ __launch_bounds__(64 * WCO * WPX, 2) void upconv_x3_kernel(const Upco
 #define VP_STORE_H(BUF, DEAD1)                                                               \
   if (!(ABL & 1) || abl_prologue)                                                            \
   _Pragma("unroll") for (int pc = 0; pc < HP; ++pc) {                                        \
-    if (tid + NTH * pc < HCHUNKS) {                                                          \
-      char* dst_ = halo_base + (BUF) * PL * HSTRIDE + h_lds0 + pc * (NTH / 4) * ROWB;        \
+    if (CPT ? h_ls[pc] >= 0 : tid + NTH * pc < HCHUNKS) {                                    \
+      char* dst_ = halo_base + (BUF) * PL * HSTRIDE + (CPT ? h_ls[pc] : h_lds0 + pc * (NTH / 4) * ROWB); \
       *reinterpret_cast<u32x4*>(dst_) = h_gx[pc] >= 0 ? rh_hi[pc] : zero4;                   \
       *reinterpret_cast<u32x4*>(dst_ + HSTRIDE) = (h_gx[pc] >= 0 && !(DEAD1)) ? rh_lo[pc] : zero4; \
     }                                                                                        \
@@ -218,20 +275,31 @@ __global__ __launch_bounds__(64 * WCO * WPX, 2) void upconv_x3_kernel(const Upco
 #define VP_READ_FRAGS(SET, WPTR, HPTR, TAPOFS)                                               \
   {                                                                                          \
     const char* wsrc_ = (WPTR) + (a_ofs0 ^ ((SET) * 32));                                    \
+    if (!CPT || nlj > 0)                                                                     \
     _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                         \
       fa[SET][i] = *reinterpret_cast<const h8_t*>(wsrc_ + i * WCO * 32 * WROW);              \
       fal[SET][i] = *reinterpret_cast<const h8_t*>(wsrc_ + W_BYTES + i * WCO * 32 * WROW);   \
     }                                                                                        \
-    const char* hsrc_ = (HPTR) + b_ofs0 + (TAPOFS) + (SET) * 32;                             \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                         \
-      fb[SET][j] = *reinterpret_cast<const h8_t*>(hsrc_ + j * 2 * HWD * ROWB);               \
-      fbl[SET][j] = *reinterpret_cast<const h8_t*>(hsrc_ + HSTRIDE + j * 2 * HWD * ROWB);    \
+    if constexpr (CPT) {                                                                     \
+      const char* hsrc_ = (HPTR) + (TAPOFS) + (SET) * 32;                                    \
+      _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                       \
+        if (j >= nlj) continue;                                                              \
+        fb[SET][j] = *reinterpret_cast<const h8_t*>(hsrc_ + b_ofs[j]);                       \
+        fbl[SET][j] = *reinterpret_cast<const h8_t*>(hsrc_ + HSTRIDE + b_ofs[j]);            \
+      }                                                                                      \
+    } else {                                                                                 \
+      const char* hsrc_ = (HPTR) + b_ofs0 + (TAPOFS) + (SET) * 32;                           \
+      _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                       \
+        fb[SET][j] = *reinterpret_cast<const h8_t*>(hsrc_ + j * 2 * HWD * ROWB);             \
+        fbl[SET][j] = *reinterpret_cast<const h8_t*>(hsrc_ + HSTRIDE + j * 2 * HWD * ROWB);  \
+      }                                                                                      \
     }                                                                                        \
   }
   // accumulator tiles [Q0, Q1) of the wave (tile q = i * NT + j): hi*lo + lo*hi + hi*hi
 #define VP_MFMA_RANGE(SET, Q0, Q1)                                                           \
   _Pragma("unroll") for (int q_ = (Q0); q_ < (Q1); ++q_) {                                   \
     const int i = q_ / NT, j = q_ % NT;                                                      \
+    if constexpr (CPT) { if (j >= nlj) continue; }   /* a fragment past the run's end */     \
     if constexpr ((ABL & 2) != 0) { acc[i][j][0] += (float)fa[SET][i][0] + (float)fal[SET][i][1] + (float)fb[SET][j][2] + (float)fbl[SET][j][3]; continue; } \
     if constexpr (X1) { /* the planes are K halves: a0 . b0 + a1 . b1 */                     \
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[SET][i], fb[SET][j], acc[i][j], 0, 0, 0);   \
@@ -242,7 +310,7 @@ __global__ __launch_bounds__(64 * WCO * WPX, 2) void upconv_x3_kernel(const Upco
     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[SET][i], fbl[SET][j], acc[i][j], 0, 0, 0); \
     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[SET][i], fb[SET][j], acc[i][j], 0, 0, 0);  \
   }
-#define VP_TAP_OFS(D, K) ((((py + (D).a0 + ((D).nb == 2 ? ((K) >> 1) : (K))) * HWD) + px + (D).b0 + ((D).nb == 2 ? ((K) & 1) : 0)) * ROWB)
+#define VP_TAP_OFS(D, K) ((tpy + (D).a0 + ((D).nb == 2 ? ((K) >> 1) : (K))) * hrp + (tpx + (D).b0 + ((D).nb == 2 ? ((K) & 1) : 0)) * ROWB)
 
   // ---- prologue: halo(chunk cA) and weight tiles 0, 1 -> LDS; halo(chunk cA + 1) -> registers
   bool abl_prologue = true;   // (ablation hooks: the prologue always stages)
@@ -357,7 +425,10 @@ __global__ __launch_bounds__(64 * WCO * WPX, 2) void upconv_x3_kernel(const Upco
 #undef VP_LOAD_H
 #undef VP_DMA_W
 
-  const PixPhase pix{y0, x0, p.H, p.W, py, px};
+  const auto pix = [&] {
+    if constexpr (CPT) return PixRun{kA, kE, p.W, py, px};
+    else return PixPhase{y0, x0, p.H, p.W, py, px};
+  }();
   if constexpr ((ABL & 16) != 0) {   // ablation: keep the accumulators alive, skip the epilogue
     if (p.H == -12345) {
 #pragma unroll
@@ -483,8 +554,22 @@ __global__ __launch_bounds__(256) void upconv_finish_kernel(const UpconvParams p
   if (p.out_lo) *reinterpret_cast<h8_t*>(p.out_lo + o) = lo;   // (VP_FP16 engines: one plane)
 }
 
+bool upconv_compact_fits(int H, int W, int shape) {
+  if ((shape != 6 && shape != 7) || H < 1 || W < 1 || (long long)H * W >= (1 << 24)) return false;
+  const int PX = shape == 6 ? 256 : 128, nth = shape == 6 ? 512 : 256, th = shape == 6 ? 16 : 8;
+  // every run's window: staged pixels within the staging capacity, bytes within a halo plane (kernel: cnt, h_ls)
+  for (int kA = 0; kA < H * W; kA += PX) {
+    const int kE = std::min(kA + PX, H * W), yA = kA / W, xA = kA - yA * W, yE = (kE - 1) / W, xE = (kE - 1) - yE * W;
+    const long long cnt = (long long)(yE - yA + 1) * (W + 2) + xE - xA + 2;
+    const long long bytes = (long long)(yE - yA + 1) * (W * 80 + 256) + (xE - xA + 1) * 80 + 80;
+    if (cnt > upconv_halo_capacity(nth) || bytes > upconv_halo_bytes(th, true)) return false;
+  }
+  return true;
+}
+
 bool upconv_supported(const UpconvParams& p, int shape) {
   if (shape != 6 && shape != 7) return false;
+  if (p.compact && (p.in_lo == nullptr || !upconv_compact_fits(p.H, p.W, shape))) return false;   // (the fp16 engines keep the patch form)
   const bool x1 = p.in_lo == nullptr;   // VP_FP16 engines: one plane per tensor, 64-channel chunks (template parameter X1)
   if (!(p.in_hi && p.w_hi && p.w_lo && p.bias && p.wscale && p.out_hi && (x1 ? p.out_lo == nullptr : p.out_lo != nullptr))) return false;
   if (p.H < 1 || p.W < 1 || p.Cin < (x1 ? 64 : 32) || p.Cin % (x1 ? 64 : 32) != 0 || p.Cs % 32 != 0 || p.Cs < 0) return false;
@@ -498,18 +583,19 @@ bool upconv_supported(const UpconvParams& p, int shape) {
   return true;
 }
 
-template <int TH, int WPX, bool HDB, bool X1>
+template <int TH, int WPX, bool HDB, bool X1, bool CPT = false>
 static hipError_t launch_upconv_cfg(const UpconvParams& p, hipStream_t st) {
   constexpr int CO = 128;
-  constexpr int lds = (HDB ? 2 : 1) * 2 * ((TH + 2) * 18 * 80) + 6 * (CO * 64);
-  static_assert(lds <= 160 * 1024, "LDS budget");
+  constexpr int lds = (HDB ? 2 : 1) * 2 * upconv_halo_bytes(TH, CPT) + 6 * (CO * 64);
+  static_assert(lds <= (TH == 8 ? 80 : 160) * 1024, "LDS budget (the 4-wave shape: two workgroups per CU)");
   constexpr int GELU = X1 ? ACT_GELU_F16 : ACT_GELU;
   const bool gelu = p.act == GELU, sk = p.nsplit > 1;
-  auto k = sk ? upconv_x3_kernel<CO, TH, 2, WPX, HDB, ACT_NONE, true, X1>
-              : (gelu ? upconv_x3_kernel<CO, TH, 2, WPX, HDB, GELU, false, X1> : upconv_x3_kernel<CO, TH, 2, WPX, HDB, ACT_NONE, false, X1>);
+  auto k = sk ? upconv_x3_kernel<CO, TH, 2, WPX, HDB, ACT_NONE, true, X1, 0, CPT>
+              : (gelu ? upconv_x3_kernel<CO, TH, 2, WPX, HDB, GELU, false, X1, 0, CPT> : upconv_x3_kernel<CO, TH, 2, WPX, HDB, ACT_NONE, false, X1, 0, CPT>);
   static LdsAttrOnce attr_once[3];
   if (hipError_t e = set_max_dynamic_lds(attr_once[sk ? 2 : gelu], reinterpret_cast<const void*>(k), lds); e != hipSuccess) return e;
-  dim3 grid(((p.H + TH - 1) / TH) * ((p.W + 15) / 16) * 4 * (p.CoutW / CO) * p.nsplit);
+  const int n_px = CPT ? (p.H * p.W + TH * 16 - 1) / (TH * 16) : ((p.H + TH - 1) / TH) * ((p.W + 15) / 16);   // runs / patches
+  dim3 grid(n_px * 4 * (p.CoutW / CO) * p.nsplit);
   hipLaunchKernelGGL(k, grid, dim3(64 * 2 * WPX), lds, st, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !sk) return e;
@@ -523,6 +609,10 @@ hipError_t launch_upconv(const UpconvParams& p, int shape, hipStream_t st) {
   if (p.in_lo == nullptr) {   // VP_FP16 engines
     if (shape == 6) return launch_upconv_cfg<16, 4, true, true>(p, st);
     return launch_upconv_cfg<8, 2, false, true>(p, st);
+  }
+  if (p.compact) {
+    if (shape == 6) return launch_upconv_cfg<16, 4, true, false, true>(p, st);
+    return launch_upconv_cfg<8, 2, false, false, true>(p, st);
   }
   if (shape == 6) return launch_upconv_cfg<16, 4, true, false>(p, st);
   return launch_upconv_cfg<8, 2, false, false>(p, st);
