@@ -30,7 +30,7 @@ REWRITES = (
 
 def build(force=False):
     lib = os.path.join(OUT, "libvp_emul.so")
-    deps = [os.path.join(CSRC, f) for f in UNITS + HEADERS] + [os.path.join(HERE, f) for f in ("harness.cpp", "build.py", os.path.join("shim", "hip", "hip_runtime.h"))]
+    deps = [os.path.join(CSRC, f) for f in UNITS + HEADERS] + [os.path.join(HERE, f) for f in ("harness.cpp", "harness_entries.hpp", "build.py", os.path.join("shim", "hip", "hip_runtime.h"))]
     if not force and os.path.exists(lib) and all(os.path.getmtime(lib) >= os.path.getmtime(s) for s in deps):
         return lib
     os.makedirs(OUT, exist_ok=True)
@@ -64,7 +64,7 @@ def build_race_check(force=False):
     build(force)  # refreshes the rewritten sources under _build/
     out = os.path.join(OUT, "race")
     exe = os.path.join(out, "race_check")
-    deps = [os.path.join(CSRC, f) for f in UNITS + HEADERS] + [os.path.join(HERE, f) for f in ("harness.cpp", "race_check.cpp", "build.py", os.path.join("shim", "hip", "hip_runtime.h"))]
+    deps = [os.path.join(CSRC, f) for f in UNITS + HEADERS] + [os.path.join(HERE, f) for f in ("harness.cpp", "harness_entries.hpp", "race_check.cpp", "build.py", os.path.join("shim", "hip", "hip_runtime.h"))]
     if not force and os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(s) for s in deps):
         return exe
     os.makedirs(out, exist_ok=True)

@@ -155,6 +155,16 @@ int main(int argc, char** argv) {
       bad |= upconv(0, 128, 16, 128, 72, 5, 17, 7, 2);        // 96 skip channels: one full + one half-dead chunk per class, K slices
       bad |= upconv(1, 96, 16, 128, 0, 17, 19, 6, 1);
     }
+    // compacted form (runs of row-major pixels, parity form only), forced on: a halo window of whole map rows (80 W + 256 bytes apart), runs that
+    // wrap rows, fragments past a run's end
+    vp_set_option("VP_UPCONV_COMPACT", "1");
+    bad |= upconv(1, 64, 16, 128, 24, 7, 13, 7, 2);           // 4-wave shape: ragged map, skip tensor, K slices
+    if (!quick) {
+      bad |= upconv(1, 64, 16, 128, 40, 7, 13, 6, 3);         // 8-wave shape: two skip chunks, K slices
+      bad |= upconv(1, 64, 16, 128, 24, 10, 20, 6, 1);        // the neck's 10x20 on the 8-wave shape: one run
+      bad |= upconv(1, 96, 16, 128, 0, 1, 5, 7, 1);           // one short row, no skip tensor
+    }
+    vp_set_option("VP_UPCONV_COMPACT", nullptr);
   }
   if (!skip_conv) {  // heads' logits convolution: DMA halo + zero page, slab reduction through LDS (128 channels)
     bad |= conv_logits(1, 128, 3, quick ? 5 : 9, quick ? 17 : 33);
