@@ -13,7 +13,9 @@ frame: data = "synthetic".
 ``value`` is measured in the PARITY mode (fp16x3: every tensor a (hi, lo) fp16 pair, three fp16 MFMAs per product, fp32
 accumulate -- floats within 1e-3 of the fp32 oracle, class maps equal to the oracle's except tie flips inside that float tolerance
 (counted per pass in profiles/r06_parity_sweep.tsv; tests/test_gpu_networks.py, tests/test_gpu_parity_sweep.py), with the frame
-resident in HBM and ``--streams`` frames in flight per GPU.  The same JSON line also carries
+resident in HBM and ``--streams`` frames in flight per GPU.
+A plain run does only what `value` needs: it sets up, warms up, times the steps, writes ``--dump-outputs`` if asked and prints the line.
+With ``--full`` the same JSON line also carries
   single_stream_fps / p50_ms : one frame at a time (back-to-back / synchronised per frame), parity mode
   fp16_value ...             : the same three figures in plain fp16 (the reference's "fp16" configuration; NOT parity-grade)
   host_to_host_fps           : through the synchronous boundary call (vp_infer_multi: pageable host frame in, H2D, both
@@ -227,8 +229,10 @@ def main():
     ap.add_argument("--no-fork", action="store_true", help="enqueue the base engine and its heads one after the other (vp_enqueue) "
                     "instead of one forked graph per frame (vp_enqueue_multi)")
     ap.add_argument("--fork-all", action="store_true", help="experiment: forked graphs in the several-cameras legs too")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the fp16 and host-to-host legs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the `value` leg, also run every other leg (one camera, p50 / p99, other data and "
+                    "precisions, SceneSeg alone, AutoDrive, host-to-host, three heads, gather, roofline, cpu_baseline) and report them in the line")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: keep only the one-camera, p50 / p99, roofline and cpu_baseline legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the cpu_baseline leg (0 = all host cores, max 32)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the `value` leg's last timed step computed as DIR/<name>.npy (float32)")
@@ -245,6 +249,7 @@ def main():
         args.workload = args.kind
     Camera.fork = not args.no_fork
     Camera.fork_all = args.fork_all
+    secondary = args.full and not args.no_secondary
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: one rank per GPU, launched here (the driver's torch.distributed.run form sets the
@@ -351,7 +356,7 @@ def main():
             np.save(os.path.join(out_dir, f"{e.kind}_logits.npy"), e.logits().astype(np.float32))
             np.save(os.path.join(out_dir, f"{e.kind}_mask.npy"), e.mask().astype(np.float32))
 
-    def three_figures(cams, steps, warmup, gather=False, dump_dir=None):
+    def three_figures(cams, steps, warmup, gather=False, dump_dir=None, one_camera=True):
         # several cameras in flight: engines one after the other (the chip is full; forked heads only add contention);
         # one camera / one frame at a time: the backbone-only heads forked behind the shared encoder (vp_set_multi_fork)
         for c in cams:
@@ -359,6 +364,8 @@ def main():
         k, el = throughput(cams, steps, warmup, gather)
         if dump_dir is not None and rank == 0:
             dump_outputs(cams[(k - 1) % len(cams)], dump_dir)  # the slot timed() enqueued last
+        if not one_camera:    # a plain run: the throughput figure alone
+            return dict(steps=k, elapsed=el, fps=world * k / el)
         cams[0].set_fork(True)
         k1, el1 = throughput(cams[:1], max(steps // 3, 1), 3)
         lat = latency(cams[0], args.latency_iters)
@@ -415,12 +422,12 @@ def main():
 
     if args.gather:
         comms = make_comms()
-    main_fig = three_figures(cams, args.steps, args.warmup, args.gather, dump_dir=args.dump_outputs)
+    main_fig = three_figures(cams, args.steps, args.warmup, args.gather, dump_dir=args.dump_outputs, one_camera=args.full)
 
     # ---- the N = 1 anchor of the multi-camera exchange: the same throughput leg with the per-frame RCCL all-gather of the
     # class maps enqueued behind every frame (vp_gather, world 1), so the first 8-GPU `--gather` run has its reference point from this command
     gather_fig = None
-    if world == 1 and not args.gather and not args.no_secondary and args.leg is None:
+    if world == 1 and not args.gather and secondary and args.leg is None:
         try:
             comms = make_comms()
             for c in cams:
@@ -442,7 +449,7 @@ def main():
     # weight family of the parity sweep (synthetic.make_trained_like_state_dict: BatchNorm scales spread over 10^3 per layer, small variances, sparse
     # large weights) and a DIFFERENT synthetic frame in every in-flight slot (the default leg carries one frame in all of them).
     trained_fig = None
-    if world == 1 and not args.no_secondary and args.leg is None and args.workload == "seg+3d":
+    if world == 1 and secondary and args.leg is None and args.workload == "seg+3d":
         sds_t = [synthetic.make_trained_like_state_dict(kinds[0], SEEDS[kinds[0]])]
         for k in kinds[1:]:
             sds_t.append(synthetic.share_backbone(synthetic.make_trained_like_state_dict(k, SEEDS[k]), k, sds_t[0], kinds[0]))
@@ -506,7 +513,7 @@ def main():
                 st["out"].append(1e6 * (t3 - t2))
         return tuple(float(np.median(st[k])) for k in ("up", "net", "out"))
 
-    if rank == 0 and not args.no_secondary:
+    if rank == 0 and secondary:
         cam = cams[0]
         cam.set_fork(True)
         pre_kernel_us = 1e3 * float(cam.base.profile_layers(20)[0])          # launch 0 of the plan = the preprocess kernel (HIP events)
@@ -529,7 +536,7 @@ def main():
 
     # ---- host-to-host through the synchronous boundary call, one host thread per in-flight engine
     h2h = None
-    if not args.no_secondary:
+    if secondary:
         def host_loop(cam, seconds, out, idx):
             n, t0 = 0, time.perf_counter()
             while time.perf_counter() - t0 < seconds:
@@ -592,7 +599,7 @@ def main():
     # is fed RGB planes (onnxruntime_engine.cpp:80-100): a SECOND base engine with its own weights, stream and preprocess, not a head
     # grafted onto SceneSeg's encoder.  957.6 GFLOP per frame.  N = 1 only.
     three = None
-    if args.workload == "seg+3d" and not args.no_secondary and world == 1:
+    if args.workload == "seg+3d" and secondary and world == 1:
         egos = [ego_engine() for _ in range(nstreams)]
 
         def run3(slots, steps):
@@ -651,10 +658,16 @@ def main():
         for e in egos:
             e.close()
 
-    # ---- roofline of the dominant kernel family of the REPORTED precision: per-launch HIP events (eager replay, one stream)
     out = None
     if rank == 0:
         engs = [cams[0].base] + cams[0].heads
+        gflop = workload_gflop(kinds)
+        # what one frame EXECUTES on the matrix pipe (round 6: the composed up-sampling stages run 0.40-0.51x of the reference formulation's count)
+        exec_gflop = sum(fx for e in engs for fx in e.layer_flops_executed()) / 1e9
+
+    # ---- roofline of the dominant kernel family of the REPORTED precision: per-launch HIP events (eager replay, one stream)
+    roofline = None
+    if rank == 0 and args.full:
         rows = []
         for e in engs:
             ms = e.profile_layers(10)
@@ -670,8 +683,6 @@ def main():
             if t > f["worst"][1]:
                 f["worst"] = (name, t)
         tot_ms = sum(t for _, _, t, _ in rows)
-        # what one frame EXECUTES on the matrix pipe (round 6: the composed up-sampling stages run 0.40-0.51x of the reference formulation's count)
-        exec_gflop = sum(fx for _, _, _, fx in rows) / 1e9
         # The path is a dense contraction (bound = MFMA): the roofline kernel is the single instantiation
         # (= one rocprofv3 kernel name) with the largest total time among those carrying >= 5 % of the frame's FLOPs;
         # "+splitk" ops are two launches per timing interval and cannot give a per-kernel duration.
@@ -698,7 +709,6 @@ def main():
                             "algorithmic_mb_per_launch": round(fam[k]["bytes"] / fam[k]["n"] / 1e6, 2),
                             "traffic_mb_per_launch": round(trk["bytes"] / 1e6, 2) if trk else None,
                             **({"includes_finish_launch": True} if "+splitk" in k else {})})
-        gflop = workload_gflop(kinds)
         frame_tflops = gflop * (main_fig["fps"] / world) / 1e3
         if dom.startswith("conv") or dom.startswith("upconv"):
             achieved, peak, unit, bound = d["flops"] / (d["ms"] * 1e-3) / 1e12, PEAK_FP16_TFLOPS, "TFLOP/s", "mfma"
@@ -734,6 +744,7 @@ def main():
                     "stage computes its three reference operators with 0.40-0.51x the products (`*_executed`); fp16x3 issues 3 fp16 MFMAs per executed "
                     "product, `mfma_issue_frac` = issued MFMA FLOPs / peak",
         }
+    if rank == 0:
         prec_name = {"fp16": "fp16", "fp16x3": "fp16x3 (hi+lo fp16 pairs on the fp16 MFMA pipe, fp32 accumulate; fp32-class: floats within 1e-3 "
                                                "of the fp32 oracle, 0 class flips outside that float tolerance -- tie flips only, counted "
                                                "per pass in profiles/r06_parity_sweep.tsv)"}[args.precision]
@@ -752,14 +763,19 @@ def main():
                        "frames_in_flight_per_gpu": nstreams, "net_input": "1x3x320x640", "gather": bool(args.gather),
                        "gflop_per_frame": round(gflop, 1), "executed_gflop_per_frame": round(exec_gflop, 1), "timed_region_s": round(main_fig["elapsed"], 3)},
             "fps_per_gpu": round(main_fig["fps"] / world, 2),
-            "single_stream_fps": round(main_fig["single"], 2),
-            "p50_ms": round(main_fig["p50"], 4), "p99_ms": round(main_fig["p99"], 4), "latency_iters": main_fig["latency_iters"],
-            "modes_note": ("`value` / host_to_host_fps: several cameras in flight, every camera's engines enqueued one after the "
-                           "other (vp_set_multi_fork 0); single_stream_fps / p50_ms / p99_ms / host_to_host_p50_ms: ONE camera, one "
-                           "frame at a time, the backbone-only heads forked behind the shared encoder inside one graph "
-                           "(vp_enqueue_multi / vp_infer_multi, the default) -- same kernels, bit-identical results"
-                           + ("" if Camera.fork else "; --no-fork: forking disabled everywhere")),
-            "roofline": roofline,
+        }
+        if args.full:
+            out.update({
+                "single_stream_fps": round(main_fig["single"], 2),
+                "p50_ms": round(main_fig["p50"], 4), "p99_ms": round(main_fig["p99"], 4), "latency_iters": main_fig["latency_iters"],
+                "modes_note": ("`value` / host_to_host_fps: several cameras in flight, every camera's engines enqueued one after the "
+                               "other (vp_set_multi_fork 0); single_stream_fps / p50_ms / p99_ms / host_to_host_p50_ms: ONE camera, one "
+                               "frame at a time, the backbone-only heads forked behind the shared encoder inside one graph "
+                               "(vp_enqueue_multi / vp_infer_multi, the default) -- same kernels, bit-identical results"
+                               + ("" if Camera.fork else "; --no-fork: forking disabled everywhere")),
+                "roofline": roofline,
+            })
+        out.update({
             "rccl_world": world if (args.gather or world > 1) else 0,
             "rccl_use": ("per-frame all-gather of the class maps (vp_gather) + " if args.gather else "") + ("barrier / max-over-ranks timing" if world > 1 else ("none" if not args.gather else "world 1")),
             "library": lib.version(),
@@ -767,7 +783,7 @@ def main():
             "engine_create_note": "wall time of vp_create (SceneSeg) + vp_create_shared (Scene3D) from the in-memory VPW1 blobs: the packing a TensorRT-style "
                                   "engine cache would save (tensorrt_backend.cpp:40-54); median over the in-flight slots",
             "plan_hash": {e.kind: f"{e.plan_hash():016x}" for e in engs},
-        }
+        })
         if fps_timer is not None:
             out["fps_timer"] = fps_timer
         if three is not None:
@@ -793,7 +809,7 @@ def main():
             cm.close()
 
     # ---- the other precision beside it (fp16 when value is the parity mode, and vice versa)
-    if not args.no_secondary:
+    if secondary:
         other = "fp16" if args.precision == "fp16x3" else "fp16x3"
         cams2 = [Camera(lib, kinds, blobs, other, local_rank, frame) for _ in range(nstreams)]
         fig2 = three_figures(cams2, args.steps, max(3, args.warmup // 3))
@@ -809,7 +825,7 @@ def main():
 
     # ---- BASELINE configs[1]: SceneSeg ALONE on the 1280x720 camera, batch 1 -- "fp16" as BASELINE.json words it and the parity mode beside it;
     # same three figures, same protocol (N = 1 only: the other configurations are not part of the scaling curve)
-    if not args.no_secondary and world == 1 and args.workload == "seg+3d":
+    if secondary and world == 1 and args.workload == "seg+3d":
         sd1, blob1 = [sds[0]], [blobs[0]]
         for prec, tag in (("fp16", "sceneseg_fp16"), ("fp16x3", "sceneseg_fp16x3")):
             cs = [Camera(lib, ("sceneseg",), blob1, prec, local_rank, frame) for _ in range(nstreams)]
@@ -865,7 +881,7 @@ def main():
                                  f"mode on the same stored weights; fps with {nstreams} frames in flight, p50 / p99 one frame at a time; ~8.1 GFLOP per frame")
 
     # ---- CPU baseline: the oracle on the host cores, bounded sample (rank 0, N=1 only)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(kinds, sds, frame, args.cpu_seconds, args.cpu_threads)
     if dist is not None:
         dist.barrier()

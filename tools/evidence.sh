@@ -2,8 +2,8 @@
 # The round's measured evidence in one call, from the repo root ON the GPU box:   bash tools/evidence.sh r06 [quick]
 # Writes gpurun_out/<tag>_*; the files worth judging are then copied into profiles/ (tracked).  `quick` skips the GPU test suite.
 #   <tag>_pytest_gpu.log                      python -m pytest tests -q -m gpu
-#   <tag>_bench_default.json                  python bench.py   (the driver's N = 1 command)
-#   <tag>_rocprofv3_kernel_stats_bench.csv    rocprofv3 --kernel-trace --stats of bench.py --no-secondary --no-cpu-baseline --no-fork --steps 100
+#   <tag>_bench_default.json                  python bench.py --full   (the driver's N = 1 command with every leg)
+#   <tag>_rocprofv3_kernel_stats_bench.csv    rocprofv3 --kernel-trace --stats of bench.py --full --no-secondary --no-cpu-baseline --no-fork --steps 100
 #   <tag>_pmc_traffic.json                    separate --pmc FETCH_SIZE / WRITE_SIZE passes of tools/pmc_conv.py, calibrated in-run (tools/pmc_summarize.py)
 #   <tag>_pmc_sq_conv.tsv                     SQ counters per dispatch of the matrix kernels (tools/pmc_sq_summarize.py)
 #   <tag>_layers_<net>_<precision>.tsv        per-launch HIP-event tables (tools/layer_profile.py)
@@ -17,7 +17,7 @@ if [ "$2" != "quick" ]; then
   timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -30 > $O/${TAG}_pytest_gpu.log
   tail -3 $O/${TAG}_pytest_gpu.log
 fi
-timeout 900 python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_err.log
+timeout 900 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_err.log
 python - <<PY
 import json
 d = json.loads(open("$O/${TAG}_bench_default.json").read().strip().splitlines()[-1])
@@ -30,7 +30,7 @@ print(json.dumps(d.get("cpu_baseline")))
 PY
 # ---- rocprofv3 per-kernel statistics of the bench command (kernel trace only: no counters in this pass)
 rm -rf /tmp/prof_stats
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python $ROOT/bench.py --no-secondary --no-cpu-baseline --no-fork --steps 100 \
+(cd "$TMPDIR" && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$TMPDIR"/prof_stats -- python $ROOT/bench.py --full --no-secondary --no-cpu-baseline --no-fork --steps 100 \
   > $ROOT/$O/${TAG}_bench_under_rocprofv3.json 2> /tmp/prof_stats.err)
 f=$(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp "$f" $O/${TAG}_rocprofv3_kernel_stats_bench.csv && head -8 $O/${TAG}_rocprofv3_kernel_stats_bench.csv | cut -c1-200
