@@ -298,3 +298,90 @@ def test_fp8_weight_storage(emu_lib, precision):
         assert got.shape == ref.shape and err <= tol, (ks, cin, cout, err)
         plain = emu_lib.op_conv2d(x, wq, b, ks=ks, precision=precision, tile=tile, nsplit=nsplit)   # the same values as (hi, lo) fp16 planes
         assert float((np.abs(got - plain) / np.maximum(1.0, np.abs(plain))).max()) <= (2e-5 if precision == 1 else 2e-3)
+
+
+# ---- row spread and value edges (tests/decoder_checks.py): per-channel error against fp64 on the operands as stored; the same bodies run at
+# the production shapes on the device (tests/test_gpu_decoder_kernels.py)
+SPREAD = ["spread", "spread+dead"]
+EDGES = [2.0 ** -12, 2.0 ** 8]
+
+
+@pytest.mark.parametrize("rows", SPREAD)
+@pytest.mark.parametrize("precision", [0, 1], ids=["fp16", "fp16x3"])
+def test_halo_kernel_row_spread(emu_lib, precision, rows):
+    from decoder_checks import check_conv
+
+    for tile, nsplit in ((100, 1), (101, 2), (102, 1), (103, 3), (104, 1)):
+        check_conv(emu_lib, 48, 72, 11, 21, precision=precision, tile=tile, nsplit=nsplit, rows=rows, seed=tile)
+
+
+@pytest.mark.parametrize("rows", SPREAD)
+@pytest.mark.parametrize("precision", [0, 1], ids=["fp16", "fp16x3"])
+def test_x3_kernels_row_spread(emu_lib, precision, rows):
+    """halo tiles 6 - 9 (and their x1 forms) with split-K slices behind the finish kernel"""
+    from decoder_checks import check_conv
+
+    for tile, nsplit in ((106, 1), (107, 1), (108, 1), (109, 1), (107, 2), (108, 2)):
+        check_conv(emu_lib, 128, 128, 16, 32, precision=precision, tile=tile, nsplit=nsplit, rows=rows, seed=tile + nsplit)
+
+
+@pytest.mark.parametrize("rows", SPREAD)
+@pytest.mark.parametrize("precision", [0, 1], ids=["fp16", "fp16x3"])
+def test_map_kernel_row_spread(emu_lib, precision, rows):
+    """tile 11 on both geometries (20x40 and the context block's 10x20 with its mul-add residual); tile 12 (parity mode only)"""
+    from decoder_checks import check_conv
+
+    check_conv(emu_lib, 64, 72, 20, 40, precision=precision, tile=111, nsplit=2, rows=rows, seed=1)
+    check_conv(emu_lib, 64, 72, 10, 20, res_mode=2, precision=precision, tile=111, nsplit=2, rows=rows, seed=2)
+    if precision == 1:
+        check_conv(emu_lib, 64, 128, 20, 40, precision=1, tile=112, nsplit=2, rows=rows, seed=3)
+
+
+@pytest.mark.parametrize("rows", SPREAD)
+@pytest.mark.parametrize("precision", [0, 1], ids=["fp16", "fp16x3"])
+def test_head_and_gemm_row_spread(emu_lib, precision, rows):
+    """the logits kernel (mode 3: 64 channels -> 3, 128 -> 1); the generic kernel's 1x1 with residual add and mul-add"""
+    from decoder_checks import check_conv
+
+    check_conv(emu_lib, 64, 3, 19, 37, mode=3, act=0, precision=precision, rows=rows, seed=4)
+    check_conv(emu_lib, 128, 1, 10, 33, mode=3, act=0, precision=precision, rows=rows, seed=5)
+    check_conv(emu_lib, 96, 80, 7, 13, ks=1, act=2, res_mode=1, precision=precision, rows=rows, seed=6)
+    check_conv(emu_lib, 96, 80, 7, 13, ks=1, act=0, res_mode=2, precision=precision, tile=2, bk=64, nsplit=1, rows=rows, seed=7)
+
+
+@pytest.mark.parametrize("rows", SPREAD)
+@pytest.mark.parametrize("precision", [0, 1], ids=["fp16", "fp16x3"])
+def test_conv_transpose_row_spread(emu_lib, precision, rows, vp_opts):
+    """ConvTranspose2d(k2, s2): the register-stationary kernel (tile 5), the LDS-DMA GEMM (tile 6, split-K too), the fused skip link
+    (mode 2) with the skip weights spread on their own, through the LDS-DMA GEMM and the generic kernel"""
+    from decoder_checks import check_conv
+
+    check_conv(emu_lib, 128, 128, 32, 64, mode=1, act=0, precision=precision, tile=5, nsplit=1, rows=rows, seed=8)
+    vp_opts.setenv("VP_GEMM_DMA", "1")
+    check_conv(emu_lib, 256, 256, 9, 15, mode=1, act=0, precision=precision, tile=6, nsplit=1, rows=rows, seed=9)
+    check_conv(emu_lib, 320, 512, 8, 16, mode=1, act=0, precision=precision, tile=6, nsplit=3, rows=rows, seed=10)
+    check_conv(emu_lib, 256, 256, 10, 16, mode=2, cs=24, precision=precision, rows=rows, seed=11)
+    vp_opts.setenv("VP_GEMM_DMA", "0")
+    check_conv(emu_lib, 256, 256, 10, 16, mode=2, cs=24, precision=precision, rows=rows, seed=11)
+
+
+@pytest.mark.parametrize("scale", EDGES)
+@pytest.mark.parametrize("precision", [0, 1], ids=["fp16", "fp16x3"])
+def test_decoder_conv_kernels_value_edges(emu_lib, precision, scale, vp_opts):
+    """inputs, biases and residuals x 2^-12 (lo planes subnormal) and x 2^8, spread rows with a dead one: one case per kernel"""
+    from decoder_checks import check_conv
+
+    kw = dict(precision=precision, rows="spread+dead", scale=scale)
+    check_conv(emu_lib, 48, 72, 11, 21, tile=103, nsplit=2, seed=21, **kw)
+    check_conv(emu_lib, 128, 128, 16, 32, tile=106, nsplit=1, seed=22, **kw)
+    check_conv(emu_lib, 128, 128, 16, 32, tile=107, nsplit=2, seed=23, **kw)
+    check_conv(emu_lib, 64, 72, 10, 20, res_mode=2, tile=111, nsplit=2, seed=24, **kw)
+    check_conv(emu_lib, 64, 72, 20, 40, tile=111, nsplit=1, seed=25, **kw)
+    if precision == 1:
+        check_conv(emu_lib, 64, 128, 20, 40, tile=112, nsplit=2, seed=26, **kw)
+    check_conv(emu_lib, 64, 3, 19, 37, mode=3, act=0, seed=27, **kw)
+    check_conv(emu_lib, 96, 80, 7, 13, ks=1, act=2, res_mode=1, seed=28, **kw)
+    check_conv(emu_lib, 128, 128, 32, 64, mode=1, act=0, tile=5, nsplit=1, seed=29, **kw)
+    vp_opts.setenv("VP_GEMM_DMA", "1")
+    check_conv(emu_lib, 256, 256, 9, 15, mode=1, act=0, tile=6, nsplit=2, seed=30, **kw)
+    check_conv(emu_lib, 256, 256, 10, 16, mode=2, cs=24, seed=31, **kw)

@@ -130,3 +130,36 @@ def test_upconv_fp16_form_refuses_what_it_cannot_tile(emu_lib):
     t = make_stage(np.random.default_rng(15), 32, 32, 128, 0, 8, 16)   # 32 input channels pad to 32: not a multiple of the fp16 form's 64-channel chunk
     with pytest.raises(emu_lib.VpError, match="multiple of 64"):
         emu_lib.op_upconv(t["x"], t["wt"], t["bt"], t["w3"], t["b3"], precision="fp16")
+
+
+# ---- row spread and value edges (tests/decoder_checks.py): per-channel error against fp64 on the inputs as stored; the same body runs at the
+# production shapes on the device (tests/test_gpu_decoder_kernels.py)
+@pytest.mark.parametrize("rows", ["spread", "spread+dead", "spread_cm"])
+@pytest.mark.parametrize("precision", ["fp16", "fp16x3"])
+def test_upconv_kernel_row_spread(emu_lib, precision, rows):
+    """both shapes, with and without a skip tensor, one and two K slices"""
+    from decoder_checks import check_upconv
+
+    for shape, nsplit, cs in ((6, 1, 24), (7, 2, 24), (6, 2, 0), (7, 1, 0)):
+        check_upconv(emu_lib, 64, 48, 128, cs, 8, 16, shape=shape, nsplit=nsplit, precision=precision, rows=rows, seed=shape * 10 + nsplit + cs)
+
+
+@pytest.mark.parametrize("scale", [2.0 ** -12, 2.0 ** 8])
+@pytest.mark.parametrize("precision", ["fp16", "fp16x3"])
+def test_upconv_kernel_value_edges(emu_lib, precision, scale):
+    from decoder_checks import check_upconv
+
+    check_upconv(emu_lib, 64, 48, 128, 24, 8, 16, shape=7, nsplit=2, precision=precision, rows="spread+dead", scale=scale, seed=41)
+    check_upconv(emu_lib, 64, 48, 128, 24, 8, 16, shape=6, nsplit=1, precision=precision, rows="spread_cm", scale=scale, seed=42)
+
+
+@pytest.mark.parametrize("scale", [1.0, 2.0 ** -12])
+@pytest.mark.parametrize("rows", ["spread+dead", "spread_cm"])
+def test_upconv_compacted_form_row_spread(emu_lib, vp_opts, rows, scale):
+    """the compacted form (VP_UPCONV_COMPACT=1: runs of row-major pixels instead of patches) on the neck's 10x20 (shape 6) and 20x40 (shape 7)
+    geometries, with a skip tensor and K slices"""
+    from decoder_checks import check_upconv
+
+    vp_opts.setenv("VP_UPCONV_COMPACT", "1")
+    check_upconv(emu_lib, 64, 48, 128, 40, 10, 20, shape=6, nsplit=2, rows=rows, scale=scale, seed=43)
+    check_upconv(emu_lib, 64, 48, 128, 24, 20, 40, shape=7, nsplit=1, rows=rows, scale=scale, seed=44)
