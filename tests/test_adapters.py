@@ -49,6 +49,18 @@ def test_adapter_frame_matches_c_abi(tmp_path, state_dicts, vp_opts, mtype, kind
     lg = eng.logits()
     n = lg.size * 4
     assert np.array_equal(rest[:n].view(np.float32).reshape(lg.shape), lg)
+    # ... and against something that is not this library: the oracle's forward on the oracle's preprocess of the frame the binary dumped, at smoke()'s
+    # bar.  The one place where the drop-in itself, on the plan it creates by default, meets the oracle.
+    import torch
+
+    from oracle import nets
+
+    x = pre_post.preprocess(frame, input_is_bgr=True, planes_rgb=(kind == "egolanes"), norm_form="opencv")
+    ref = nets.forward(kind, nets.to_torch(state_dicts(kind)), torch.from_numpy(x))[0].numpy()
+    wrote = rest[:n].view(np.float32).reshape(lg.shape)
+    assert wrote.shape == ref.shape
+    rel = float((np.abs(wrote - ref) / np.maximum(1.0, np.abs(ref))).max())
+    assert rel <= 1e-3, f"{kind}: the adapter's logits vs the oracle, max rel err {rel:.3e}"
     tail = rest[n:]
     if kind == "sceneseg":
         assert np.array_equal(tail[:720 * 1280].reshape(720, 1280), pre_post.resize_nearest_u8(pre_post.seg_mask_u8(lg), 720, 1280))

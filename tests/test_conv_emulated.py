@@ -385,3 +385,34 @@ def test_decoder_conv_kernels_value_edges(emu_lib, precision, scale, vp_opts):
     vp_opts.setenv("VP_GEMM_DMA", "1")
     check_conv(emu_lib, 256, 256, 9, 15, mode=1, act=0, tile=6, nsplit=2, seed=30, **kw)
     check_conv(emu_lib, 256, 256, 10, 16, mode=2, cs=24, seed=31, **kw)
+
+
+@pytest.mark.parametrize("rows", SPREAD)
+@pytest.mark.parametrize("precision", [0, 1], ids=["fp16", "fp16x3"])
+def test_latency_plan_forms_row_spread(emu_lib, precision, rows):
+    """the tile / K-split combinations the latency plans use (tests/golden/kernel_plan_latency.json) that no case above reaches: the halo kernel's
+    64-channel tile with a long K in ONE slice (decode_layer_5 / 6: eight 32-channel chunks here; GELU, so the fp16 engines take the
+    register-epilogue instantiation), the same tile in four K slices of several chunks each (the fp16 engines' decode_layer_1; the cases above
+    clamp to two one-chunk slices), and the map kernel's 20x40-region geometry in ten slices (the parity mode's decode_layer_1)"""
+    from decoder_checks import check_conv
+
+    check_conv(emu_lib, 256, 64, 8, 16, precision=precision, tile=103, nsplit=1, rows=rows, seed=41)
+    check_conv(emu_lib, 320, 128, 10, 20, precision=precision, tile=103, nsplit=4, rows=rows, seed=42)      # 10 chunks in 4 slices, two channel tiles, ragged map
+    if precision == 1:
+        check_conv(emu_lib, 320, 40, 20, 40, precision=1, tile=111, nsplit=10, rows=rows, seed=43)           # 20 steps of 16 channels in 10 slices, ragged channel tile
+
+
+def test_latency_map_kernel_by_the_operator_rule(emu_lib, vp_opts):
+    """VP_PLAN_TARGET=latency with nothing forced: a 20x40 map with >= 256 input channels goes to the map kernel's 32-channel slabs on the
+    operator entry's own K split (256 slots / 2 channel tiles, at most one slice per two steps: 8) -- the bits of the forced (tile 111, 8 slices)
+    run, the split-K sum being deterministic.  (The default plan's 64-channel slabs, tile 112, keep the same K order: on an equal K split they give
+    these bits too, so what the equality pins is the K split and the K order; the halo kernel's tiles give other bits at every split.)"""
+    from decoder_checks import check_conv
+
+    kw = dict(precision=1, rows="spread+dead", seed=44)
+    forced = check_conv(emu_lib, 256, 64, 20, 40, tile=111, nsplit=8, **kw)["out"]
+    halo = check_conv(emu_lib, 256, 64, 20, 40, tile=103, nsplit=8, **kw)["out"]
+    vp_opts.setenv("VP_PLAN_TARGET", "latency")
+    by_rule = check_conv(emu_lib, 256, 64, 20, 40, tile=-1, nsplit=-1, **kw)["out"]
+    assert np.array_equal(by_rule.view(np.uint32), forced.view(np.uint32))
+    assert not np.array_equal(halo.view(np.uint32), forced.view(np.uint32))

@@ -357,3 +357,72 @@ def test_kernel_plan_is_the_committed_one(emu_lib, monkeypatch):
     assert h2 not in (h0, h1) and not any(k.startswith("conv3x3_map2<") for k in k2) and sum(1 for k in k2 if k.startswith("conv3x3_map<co32,px800")) == 2
     d5 = [k for n, k in zip(names, k2) if n.endswith("decode_layer_5")]
     assert d5 == ["conv3x3_halo<co64,px128,x3>"] and [k for n, k in zip(names, k0) if n.endswith("decode_layer_5")] == ["conv3x3_x3w8<co128,px256>"]
+
+
+# The launches whose (kernel tag, launch geometry) differ between a default-plan and a latency-plan engine: per precision, layer name suffix ->
+# ((default tag, launch), (latency tag, launch)).  Every network has the three neck layers; decode_layer_6 at 80x160 is EgoLanes' head alone
+# (the other heads' decode_layer_6 lives inside a composed up-sampling stage).  Written out, not derived: a rule change that moves another
+# layer, or moves one of these elsewhere, fails test_latency_plan_is_the_committed_one and gets reviewed.
+LATENCY_DIFFERENCE = {
+    "fp16x3": {"decode_layer_1": (("conv3x3_map2<co64,px800,x3>+splitk", "nsplit=10 wgs=120"), ("conv3x3_map<co32,px800,x3>+splitk", "nsplit=10")),
+               "decode_layer_3": (("conv3x3_map2<co64,px800,x3>+splitk", "nsplit=4 wgs=128"), ("conv3x3_map<co32,px800,x3>+splitk", "nsplit=3")),
+               "decode_layer_5": (("conv3x3_x3w8<co128,px256>", ""), ("conv3x3_halo<co64,px128,x3>", "")),
+               "decode_layer_6": (("conv3x3_x3w8<co128,px256>", ""), ("conv3x3_halo<co64,px128,x3>", ""))},
+    "fp16": {"decode_layer_1": (("conv3x3_x1w4<co128,px128,k64>+splitk", "nsplit=4"), ("conv3x3_halo<co64,px128,x1>+splitk", "nsplit=4")),
+             "decode_layer_3": (("conv3x3_x1w8<co128,px256,k64>", ""), ("conv3x3_halo<co64,px128,x1>+splitk", "nsplit=3")),
+             "decode_layer_5": (("conv3x3_x1w8<co128,px256,k64>", ""), ("conv3x3_halo<co64,px128,x1,regepi>", "")),
+             "decode_layer_6": (("conv3x3_x1w8<co128,px256,k64>", ""), ("conv3x3_halo<co64,px128,x1,regepi>", ""))},
+}
+LATENCY_DIFFERENCE_LAYERS = {"sceneseg": ("decode_layer_1", "decode_layer_3", "decode_layer_5"), "scene3d": ("decode_layer_1", "decode_layer_3", "decode_layer_5"),
+                             "domainseg": ("decode_layer_1", "decode_layer_3", "decode_layer_5"),
+                             "egolanes": ("decode_layer_1", "decode_layer_3", "decode_layer_5", "decode_layer_6")}
+
+
+def test_latency_plan_is_the_committed_one(emu_lib):
+    """The kernel plan of an engine created with VP_PLAN_LATENCY -- what adapters/hip_backend.hpp creates by default -- for the four scene networks
+    in both precisions against tests/golden/kernel_plan_latency.json, entry by entry: name, kernel tag AND launch geometry (vp_layer_launch; the
+    K split of this plan's map kernel is the engine's own rule, and tests/test_gpu_decoder_kernels.py takes it from that file).  Then what
+    include/vp_hip.h says of the two plans: the creation flag and the developer option select the same plan; the plan hash tells the plans apart;
+    and the difference between them is the written-out set above, nothing in the encoder, the context block or a composed up-sampling stage."""
+    import json
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    from dump_kernel_plan import NETWORKS
+
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kernel_plan_latency.json")))
+    assert sorted(want) == sorted(f"{kind}/{prec}" for kind, _ in NETWORKS for prec in ("fp16x3", "fp16"))
+
+    def plan(kind, seed, prec, **kw):
+        eng = emu_lib.Engine(kind, vw_blob(kind, seed), precision=prec, **kw)
+        try:
+            return [[n, k, l] for (n, _, _), k, l in zip(eng.layers(), eng.layer_kernels(), eng.layer_launches())], eng.plan_hash()
+        finally:
+            eng.close()
+
+    for kind, seed in NETWORKS:
+        for prec in ("fp16x3", "fp16"):
+            key = f"{kind}/{prec}"
+            rows_d, hash_d = plan(kind, seed, prec)
+            rows_l, hash_l = plan(kind, seed, prec, plan_latency=True)
+            diff = [(a, b) for a, b in zip(rows_l, want[key]) if list(a) != list(b)]
+            assert len(rows_l) == len(want[key]) and not diff, f"{key}: {diff[:6]}"
+            assert hash_l != hash_d and hash_l != 0, key
+            if key in ("sceneseg/fp16x3", "egolanes/fp16"):        # the flag and the option: the same plan, launch for launch, and the same hash
+                emu_lib.set_option("VP_PLAN_TARGET", "latency")
+                try:
+                    rows_o, hash_o = plan(kind, seed, prec)
+                    rows_both, hash_both = plan(kind, seed, prec, plan_latency=True)
+                finally:
+                    emu_lib.clear_options()
+                assert rows_o == rows_l and hash_o == hash_l, key
+                assert rows_both == rows_l and hash_both == hash_l, key
+            # the difference set, stated
+            assert [r[0] for r in rows_d] == [r[0] for r in rows_l], key
+            moved = {d[0]: ((d[1], d[2]), (l[1], l[2])) for d, l in zip(rows_d, rows_l) if d[1:] != l[1:]}
+            stated = LATENCY_DIFFERENCE[prec]
+            assert sorted(n.split(".")[-1] for n in moved) == sorted(LATENCY_DIFFERENCE_LAYERS[kind]), f"{key}: {moved}"
+            for name, pair in moved.items():
+                assert pair == stated[name.split(".")[-1]], f"{key} {name}: {pair}"
+                assert "encoder" not in name and "context" not in name and "upsample" not in name, name
+            first = min(i for i, (d, l) in enumerate(zip(rows_d, rows_l)) if d[1:] != l[1:])
+            assert all("decode_layer" in r[0] or r[0] in ("finite_probe", "lane_ring") for r in rows_l[first:]), key   # all behind the context block

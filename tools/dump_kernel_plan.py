@@ -2,7 +2,11 @@
 """Developer tool: (re)write tests/golden/kernel_plan.json -- the kernel tag the engine's dispatch rules give EVERY layer of every
 network in both precisions (vp_layer_kernel), taken from the CPU-emulated engine (tests/emul; the rules are host code and see the
 MI355X's 256 CUs there too).  tests/test_engine_emulated.py::test_kernel_plan_is_the_committed_one compares against it, so a predicate
-regression that silently picks another kernel fails the CPU suite.  Re-run after a DELIBERATE change of a rule and review the diff."""
+regression that silently picks another kernel fails the CPU suite.  Also writes tests/golden/kernel_plan_latency.json: the same eight
+engines created with VP_PLAN_LATENCY (the drop-in adapters' default), one entry per launch [name, kernel tag, launch] -- the launch string
+(vp_layer_launch: "nsplit=4", "groups=32", "") is recorded there because the latency plan's map-kernel K split is the engine's own rule and
+tests/test_gpu_decoder_kernels.py reproduces it (test_latency_plan_is_the_committed_one compares).  Re-run after a DELIBERATE change of a
+rule and review the diff."""
 import ctypes as ct
 import json
 import os
@@ -13,15 +17,20 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "emul"))
 
 
-def kernel_plan(lib):
+NETWORKS = (("sceneseg", 0), ("scene3d", 1), ("domainseg", 3), ("egolanes", 2))
+
+
+def kernel_plan(lib, latency=False):
+    """default plans: [name, tag] per launch (the committed format); latency plans: [name, tag, launch]"""
     from autoware_vision_pilot_amd import synthetic, weights as vw
 
     out = {}
-    for kind, seed in (("sceneseg", 0), ("scene3d", 1), ("domainseg", 3), ("egolanes", 2)):
+    for kind, seed in NETWORKS:
         blob = vw.pack_state_dict(synthetic.make_state_dict(kind, seed))
         for prec in ("fp16x3", "fp16"):
-            eng = lib.Engine(kind, blob, precision=prec)
-            out[f"{kind}/{prec}"] = [[n, k] for (n, _, _), k in zip(eng.layers(), eng.layer_kernels())]
+            eng = lib.Engine(kind, blob, precision=prec, plan_latency=latency)
+            rows = zip(eng.layers(), eng.layer_kernels(), eng.layer_launches())
+            out[f"{kind}/{prec}"] = [[n, k, l] if latency else [n, k] for (n, _, _), k, l in rows]
             eng.close()
     return out
 
@@ -36,7 +45,8 @@ if __name__ == "__main__":
         fn = getattr(so, name)
         fn.restype, fn.argtypes = res, args
     lib._lib = so
-    path = os.path.join(ROOT, "tests", "golden", "kernel_plan.json")
-    with open(path, "w") as f:
-        json.dump(kernel_plan(lib), f, indent=0)
-    print("written", path)
+    for fname, latency in (("kernel_plan.json", False), ("kernel_plan_latency.json", True)):
+        path = os.path.join(ROOT, "tests", "golden", fname)
+        with open(path, "w") as f:
+            json.dump(kernel_plan(lib, latency), f, indent=0)
+        print("written", path)
