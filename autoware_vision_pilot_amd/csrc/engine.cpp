@@ -165,6 +165,9 @@ Engine::Engine(int kind, const WeightBlob* blob, int precision, int gpu_id, Engi
   if (frames > 1 && (base || kind < 0 || kind > 3)) throw std::invalid_argument("a batched encoder is a base engine of a scene network kind");
   if (base && (frame_index < 0 || frame_index >= base->frames_)) throw std::invalid_argument("frame_index out of the base engine's range");
   if (!base && frame_index != 0) throw std::invalid_argument("frame_index needs a batched base engine");
+  if (kind == 5 && ((precision & 16) != 0 || base || frames > 1))
+    throw std::invalid_argument("VP_AUTOSPEED: VP_WEIGHTS_FP8, shared-prefix and batched creation are not supported for the detector network (VP_FP16 / VP_FP16X3, optionally | VP_PLAN_LATENCY)");
+  if (base && base->kind_ == 5) throw std::invalid_argument("VP_AUTOSPEED engines cannot be the base of a shared-prefix engine");
   if ((precision & 15) > 1 || (precision & ~(1 | 16 | 32)) != 0) throw std::invalid_argument("precision must be VP_FP16 or VP_FP16X3 (optionally | VP_WEIGHTS_FP8 | VP_PLAN_LATENCY)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -915,6 +918,10 @@ void Engine::build_model(const WeightBlob& blob) {
       {"DomainSegUpstream.pretrainedBackBone.encoder.", "DomainSegUpstream.pretrainedContext.", "DomainSegUpstream.pretrainedNeck.",
        "DomainSegHead."},
       {"BEVBackbone.encoder.", "AutoSteerContext.", "EgopathNeck.", "EgoLanesHead."}};
+  if (kind_ == 5) {
+    build_autospeed(blob);
+    return;
+  }
   if (kind_ == 4) {
     if (base_) throw std::invalid_argument("AutoDrive engines cannot be shared-prefix engines");
     build_autodrive(blob);
@@ -1003,52 +1010,44 @@ void Engine::build_model(const WeightBlob& blob) {
   decode_mode_ = kind_ == 3 ? 1 : 0;
 }
 
-// ------------------------------------------------------------------------------------------------ AutoDrive
-// autodrive_network.py:32-36, autodrive_backbone.py:8-48, autodrive_head.py:70-87, common_layers.py (Conv, CTX, SPPF,
-// C2PSA, PSABlock, Attention).  One plan: preprocess -> backbone (P5 256x16x32) -> [shift: previous frame's P5 to the
-// first half of the 512-channel head input] -> [place: this frame's P5 to the second half] -> head -> 3 scalars.
-void Engine::build_autodrive(const WeightBlob& blob) {
-  Act* head_cat = nullptr;
-  auto T = [&](const std::string& k) -> const HostTensor& { return blob.get(k); };
-  auto push = [&](const std::string& name, const char* kernel, std::function<hipError_t(hipStream_t)> fn, double flops = 0, double bytes = 0) {
-    Op op;
-    op.name = name;
-    op.kernel = kernel;
-    op.flops = flops;
-    op.bytes = bytes;
-    op.run = std::move(fn);
-    ops_.push_back(std::move(op));
-  };
-  d_input_ = static_cast<float*>(dalloc((size_t)3 * net_h() * net_w() * sizeof(float)));
-  plane_order_ = 1;  // RGB planes, ImageNet constants (visualizations/AutoDrive/video_visualization.py:29-33)
-  resize_mode_ = 1;  // ... behind PIL's antialiased Image.resize(..., Image.BILINEAR) (same lines)
-  push("preprocess", "preprocess", [this](hipStream_t st) {
-    PreprocessParams pp{};
-    pp.frame = d_frame_;
-    pp.stride = frame_stride_;
-    pp.xtab = d_xtab_;
-    pp.ytab = d_ytab_;
-    pp.out_h = net_h();
-    pp.out_w = net_w();
-    static const float mean_rgb[3] = {0.485f, 0.456f, 0.406f}, std_rgb[3] = {0.229f, 0.224f, 0.225f};
-    for (int c = 0; c < 3; ++c) {
-      const int colour = plane_order_ == 1 ? c : 2 - c;
-      pp.src_c[c] = pixel_format_ == 1 ? colour : 2 - colour;
-      pp.mean[c] = mean_rgb[colour];
-      pp.stdv[c] = std_rgb[colour];
-    }
-    pp.out = d_input_;
-    pp.norm_form = norm_form_;
-    if (resize_mode_ != 0) return launch_pil_resample(pil_params(pp), st);
-    return launch_preprocess(pp, st);
-  });
-  first_net_op_ = 1;
+// ---------------------------------------------------------------------------------- AutoDrive / AutoSpeed backbone
+// autodrive_backbone.py:8-48 == auto_speed_backbone.py:8-49 (the 'n' variant; the state-dict keys transfer 1-to-1 under the two prefixes): p1 .. p5.3.
+// One builder for both engines: same launches, names (under the prefix), kernel tags and geometry.  Reads d_input_ ([3][512][1024] fp32 planes).
+// p5_dest(c5, H, W) is called right before the last convolution (p5.3.cv2) and returns the tensor it stores into -- an alias view into a wider
+// tensor of the caller's (AutoDrive: the second half of head.cat; the detector: the P5 slice of the neck's last concatenation) -- or nullptr.
+Act* Engine::alias_slice(const std::string& name, Act* whole, int ch_off, int nch) {
+  if ((ch_off | nch) % 32 != 0 || ch_off + nch > whole->C) throw std::runtime_error("alias view: channel slices are multiples of 32 inside the tensor: " + name);
+  auto slice = std::make_unique<Act>();
+  slice->name = name;
+  slice->Creal = nch;
+  slice->C = whole->C;            // row pitch of the tensor it lives in
+  slice->H = whole->H;
+  slice->W = whole->W;
+  slice->hi = whole->hi + ch_off;
+  slice->lo = whole->lo ? whole->lo + ch_off : nullptr;
+  acts_.push_back(std::move(slice));
+  return acts_.back().get();
+}
 
+// one launch appended to the plan (the AutoDrive / AutoSpeed builders)
+void Engine::push_op(const std::string& name, const char* kernel, std::function<hipError_t(hipStream_t)> fn, double flops, double bytes) {
+  Op op;
+  op.name = name;
+  op.kernel = kernel;
+  op.flops = flops;
+  op.bytes = bytes;
+  op.run = std::move(fn);
+  ops_.push_back(std::move(op));
+}
+
+Engine::AdFeatures Engine::build_ad_backbone(const WeightBlob& blob, const std::string& P, const std::function<Act*(int, int, int)>& p5_dest) {
+  AdFeatures out;
+  auto T = [&](const std::string& k) -> const HostTensor& { return blob.get(k); };
   // ---- p1: Conv 3->16 k3 s2 + BN + SiLU on the fp32 planes (the stem kernel computes 32 output channels: 16 are padding)
   Act* x;
   {
-    Folded f = fold_conv_norm(blob, "backbone.p1");
-    if (f.cout > 32 || f.cin != 3 || f.k != 3) throw std::runtime_error("backbone.p1 shape mismatch");
+    Folded f = fold_conv_norm(blob, P + "p1");
+    if (f.cout > 32 || f.cin != 3 || f.k != 3) throw std::runtime_error(P + "p1 shape mismatch");
     std::vector<float> wk(27 * 32, 0.0f), bk(32, 0.0f);
     for (int co = 0; co < f.cout; ++co) {
       for (int k = 0; k < 27; ++k) wk[k * 32 + co] = f.w[co * 27 + k];
@@ -1060,9 +1059,9 @@ void Engine::build_autodrive(const WeightBlob& blob) {
     sp.W = net_w();
     sp.w = dupload(wk);
     sp.b = dupload(bk);
-    x = new_act("backbone.p1", f.cout, net_h() / 2, net_w() / 2);
+    x = new_act(P + "p1", f.cout, net_h() / 2, net_w() / 2);
     sp.out = x->view();
-    push("backbone.p1", "stem", [sp](hipStream_t st) { return launch_stem(sp, st); }, 2.0 * 27 * f.cout * x->H * x->W,
+    push_op(P + "p1", "stem", [sp](hipStream_t st) { return launch_stem(sp, st); }, 2.0 * 27 * f.cout * x->H * x->W,
          4.0 * 3 * net_h() * net_w() + 2.0 * x->elems());
   }
   auto conv_bn = [&](const std::string& name, const Act* in, int ks, int stride, int act) -> Act* {
@@ -1073,9 +1072,9 @@ void Engine::build_autodrive(const WeightBlob& blob) {
     return add_conv(name, in, f.w, f.b, f.cout, ks, o);
   };
   // ---- p2..p5: strided conv + CTX (common_layers.py:183-227)
-  const char* stage_names[4] = {"backbone.p2", "backbone.p3", "backbone.p4", "backbone.p5"};
+  const char* stage_names[4] = {"p2", "p3", "p4", "p5"};
   for (int si = 0; si < 4; ++si) {
-    const std::string sn = stage_names[si];
+    const std::string sn = P + stage_names[si];
     Act* a = conv_bn(sn + ".0", x, 3, 2, ACT_SILU);
     const std::string cp = sn + ".1";
     const int HW = a->H * a->W, C = a->Creal;
@@ -1086,7 +1085,7 @@ void Engine::build_autodrive(const WeightBlob& blob) {
     float* partial = static_cast<float*>(dalloc((size_t)nslab * a->C * sizeof(float)));
     {
       PoolParams pp{a->view(), partial, nslab};
-      push(cp + ".mean", "pool_partial", [pp](hipStream_t st) { return launch_pool_partial(pp, st); });
+      push_op(cp + ".mean", "pool_partial", [pp](hipStream_t st) { return launch_pool_partial(pp, st); });
     }
     // exp0: Conv1d(C -> H*W, k3, pad 1) on a length-1 sequence == the centre tap as a [H*W][C] matrix (:210), SiLU twice (:211-213)
     const HostTensor& ew = T(cp + ".exp0.weight");
@@ -1137,11 +1136,11 @@ void Engine::build_autodrive(const WeightBlob& blob) {
       // lanes per row: as few as keep every map row under a patch in one pass (16x16: 324 rows, one lane each in two passes; 8x8: 100 rows, two lanes each)
       CtxExpConv1Params q{fp, cpp, HW > 2048 ? 16 : 8, HW > 2048 ? 1 : 2};
       if (dev_option_is("VP_CTX_FUSE", '1') && ctx_exp_conv1_ok(q)) {
-        push(cp + ".exp0+ctx0", q.tile == 16 ? "ctx_exp_conv1<t16>" : "ctx_exp_conv1<t8>", [q](hipStream_t st) { return launch_ctx_exp_conv1(q, st); },
+        push_op(cp + ".exp0+ctx0", q.tile == 16 ? "ctx_exp_conv1<t16>" : "ctx_exp_conv1<t8>", [q](hipStream_t st) { return launch_ctx_exp_conv1(q, st); },
              2.0 * HW * C + 2.0 * 9 * c0n * HW, (fp.w8 ? 1.0 : 4.0) * HW * C);
       } else {
-        push(cp + ".exp0", fp.rows_kernel ? "fc<rows>" : "fc", [fp](hipStream_t st) { return launch_fc(fp, st); }, 2.0 * HW * C, (fp.w8 ? 1.0 : 4.0) * HW * C);
-        push(cp + ".ctx0", "ctx_conv1", [cpp](hipStream_t st) { return launch_ctx_conv1(cpp, st); }, 2.0 * 9 * c0n * HW);
+        push_op(cp + ".exp0", fp.rows_kernel ? "fc<rows>" : "fc", [fp](hipStream_t st) { return launch_fc(fp, st); }, 2.0 * HW * C, (fp.w8 ? 1.0 : 4.0) * HW * C);
+        push_op(cp + ".ctx0", "ctx_conv1", [cpp](hipStream_t st) { return launch_ctx_conv1(cpp, st); }, 2.0 * 9 * c0n * HW);
       }
     }
     // ctx1: conv3x3 C/2 -> C + SiLU, gate: c4*x + x, SiLU (:218-224)
@@ -1153,32 +1152,34 @@ void Engine::build_autodrive(const WeightBlob& blob) {
     Act* g = add_conv(cp + ".ctx1", c2, T(cp + ".ctx1.weight").data, T(cp + ".ctx1.bias").data, C, 3, o1);
     // ctx2: conv3x3 C -> Cout, no activation (:225)
     x = add_conv(cp + ".ctx2", g, T(cp + ".ctx2.weight").data, T(cp + ".ctx2.bias").data, T(cp + ".ctx2.weight").shape[0], 3, ConvOpts{});
+    if (si == 1) out.p3 = x;
+    if (si == 2) out.p4 = x;
   }
   // ---- SPPF (common_layers.py:230-243): cv1, three chained 5x5 max-pools, concat, cv2
   {
-    const std::string sp = "backbone.p5.2";
+    const std::string sp = P + "p5.2";
     Act* c1 = conv_bn(sp + ".cv1", x, 1, 1, ACT_SILU);
     const int c_ = c1->Creal;
     Act* cat = new_act(sp + ".cat", 4 * c_, x->H, x->W);
     const ActView cv = cat->view(), c1v = c1->view();
     // cat((x, mp5(x), mp5(mp5(x)), mp5^3(x))) in one launch (round 4: a slice copy + three chained max-pool launches before; kernels_autodrive.hip)
     if (sppf_pool_ok(c1v, cv, c_)) {
-      push(sp + ".pyramid", "sppf_pool", [=](hipStream_t st) { return launch_sppf_pool(c1v, cv, c_, st); });
+      push_op(sp + ".pyramid", "sppf_pool", [=](hipStream_t st) { return launch_sppf_pool(c1v, cv, c_, st); });
     } else {   // maps above 512 pixels (other input sizes): the slice copy and the three chained 5x5 max-pools
-      push(sp + ".cat0", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(c1v, 0, cv, 0, c_, st); });
+      push_op(sp + ".cat0", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(c1v, 0, cv, 0, c_, st); });
       for (int i = 0; i < 3; ++i)
-        push(sp + ".maxpool" + std::to_string(i), "maxpool5", [=](hipStream_t st) { return launch_maxpool5(cv, i * c_, cv, (i + 1) * c_, c_, st); });
+        push_op(sp + ".maxpool" + std::to_string(i), "maxpool5", [=](hipStream_t st) { return launch_maxpool5(cv, i * c_, cv, (i + 1) * c_, c_, st); });
     }
     x = conv_bn(sp + ".cv2", cat, 1, 1, ACT_SILU);
   }
   // ---- C2PSA (common_layers.py:246-257) with one PSABlock (:107-118) and its Attention (:78-104)
   {
-    const std::string cp = "backbone.p5.3", mb = cp + ".middle_block";
+    const std::string cp = P + "p5.3", mb = cp + ".middle_block";
     Act* t = conv_bn(cp + ".cv1", x, 1, 1, ACT_SILU);       // 2*c_ channels: [a | y]
     const int c_ = t->Creal / 2;
     Act* y = new_act(cp + ".y", c_, t->H, t->W);
     const ActView tv = t->view(), yv = y->view();
-    push(cp + ".split", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(tv, c_, yv, 0, c_, st); });
+    push_op(cp + ".split", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(tv, c_, yv, 0, c_, st); });
     const int heads = c_ / 64, dv = c_ / heads, dk = dv / 2;
     Act* qkv = conv_bn(mb + ".conv1.qkv", y, 1, 1, ACT_NONE);
     if (qkv->Creal != heads * (2 * dk + dv)) throw std::runtime_error("attention qkv width mismatch");
@@ -1197,7 +1198,7 @@ void Engine::build_autodrive(const WeightBlob& blob) {
       const char* ab = dev_option("VP_ATTN_BLOCK");
       ap.qblock = (attention_block_ok(ap) && !(ab && ab[0] == '0')) ? 4 : 0;
     }
-    push(mb + ".conv1.attention", ap.qblock ? "attention<q4>" : "attention", [ap](hipStream_t st) { return launch_attention(ap, st); },
+    push_op(mb + ".conv1.attention", ap.qblock ? "attention<q4>" : "attention", [ap](hipStream_t st) { return launch_attention(ap, st); },
          2.0 * heads * Tn * (double)Tn * (dk + dv));
     // + depthwise 3x3 positional conv of v (BN folded, identity activation)
     Act* pe = new_act(mb + ".conv1.pe", c_, t->H, t->W);
@@ -1214,7 +1215,7 @@ void Engine::build_autodrive(const WeightBlob& blob) {
       dp.out = pe->view();
       dp.w = dupload(wk);
       dp.b = dupload(bk);
-      push(mb + ".conv1.conv1", "dwconv_plain", [dp](hipStream_t st) { return launch_dwconv_plain(dp, st); }, 2.0 * 9 * c_ * Tn);
+      push_op(mb + ".conv1.conv1", "dwconv_plain", [dp](hipStream_t st) { return launch_dwconv_plain(dp, st); }, 2.0 * 9 * c_ * Tn);
     }
     // x = y + conv2(attn + pe)
     Act* y1;
@@ -1236,36 +1237,66 @@ void Engine::build_autodrive(const WeightBlob& blob) {
       y2 = add_conv(mb + ".conv2.1", h, f.w, f.b, f.cout, 1, o);
     }
     const ActView y2v = y2->view();
-    push(cp + ".cat", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(y2v, 0, tv, c_, c_, st); });  // cat((a, y), 1) in place
-    // ---- head input (autodrive_head.py:70-87): cat([prev, curr]).  Round 5: cv2 -- the backbone's last convolution -- stores this frame's P5 STRAIGHT into
-    // the second half of the 512-channel tensor (an alias view with the tensor's row pitch: the epilogues store at pixel * Cstore + channel), so the
-    // "place" copy launch is gone; the previous frame's features move to the first half right BEFORE it ("shift": the only copy a streaming pair needs).
+    push_op(cp + ".cat", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(y2v, 0, tv, c_, c_, st); });  // cat((a, y), 1) in place
+    // ---- last convolution: stored where the caller wants it (see above).  The alias store relies on the kernels' store guard `channel < Ncols` with
+    // Ncols = round_up(c5, 32) = c5 (checked here): a tile wider than c5 computes padding rows but never stores them into the neighbouring slice
+    // (tests/test_gpu_autodrive.py::test_autodrive_stream_of_four_frames)
     Folded f2 = fold_conv_norm(blob, cp + ".cv2");
     const int c5 = f2.cout;
-    if (c5 % 32 != 0) throw std::runtime_error("backbone.p5.3.cv2: output channels must be a multiple of 32");
-    head_cat = new_act("head.cat", 2 * c5, t->H, t->W);
-    {
-      const ActView cv = head_cat->view();
-      ad_shift_op_ = ops_.size();
-      push("head.shift_prev", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(cv, c5, cv, 0, c5, st); });
-    }
-    auto slice = std::make_unique<Act>();
-    slice->name = cp + ".cv2";
-    slice->Creal = c5;
-    slice->C = head_cat->C;            // row pitch of the tensor it lives in
-    slice->H = head_cat->H;
-    slice->W = head_cat->W;
-    slice->hi = head_cat->hi + c5;
-    slice->lo = head_cat->lo ? head_cat->lo + c5 : nullptr;
-    acts_.push_back(std::move(slice));
+    if (c5 % 32 != 0) throw std::runtime_error(cp + ".cv2: output channels must be a multiple of 32");
+    Act* dest = p5_dest ? p5_dest(c5, t->H, t->W) : nullptr;
     ConvOpts o2;
     o2.act = ACT_SILU;
-    ad_place_op_ = ops_.size();        // prime_previous() runs the plan up to and including this launch (minus the shift)
-    x = add_conv(cp + ".cv2", t, f2.w, f2.b, f2.cout, 1, o2, acts_.back().get());
-    if (ops_.size() != ad_place_op_ + 1) throw std::runtime_error("backbone.p5.3.cv2: expected ONE launch (no split-K finish) in front of the head");
-    // the alias store relies on the kernels' store guard `channel < Ncols` with Ncols = round_up(c5, 32) = c5 (checked above): a tile wider than c5 computes
-    // padding rows but never stores them into the neighbouring "previous frame" half (tests/test_gpu_autodrive.py::test_autodrive_stream_of_four_frames)
+    out.p5_op = ops_.size();
+    out.p5 = add_conv(cp + ".cv2", t, f2.w, f2.b, f2.cout, 1, o2, dest);
+    if (ops_.size() != out.p5_op + 1) throw std::runtime_error(cp + ".cv2: expected ONE launch (no split-K finish) behind the backbone");
   }
+  return out;
+}
+
+// ------------------------------------------------------------------------------------------------ AutoDrive
+// autodrive_network.py:32-36, autodrive_backbone.py:8-48, autodrive_head.py:70-87, common_layers.py (Conv, CTX, SPPF,
+// C2PSA, PSABlock, Attention).  One plan: preprocess -> backbone (P5 256x16x32) -> [shift: previous frame's P5 to the
+// first half of the 512-channel head input] -> [place: this frame's P5 to the second half] -> head -> 3 scalars.
+void Engine::build_autodrive(const WeightBlob& blob) {
+  Act* head_cat = nullptr;
+  auto T = [&](const std::string& k) -> const HostTensor& { return blob.get(k); };
+  d_input_ = static_cast<float*>(dalloc((size_t)3 * net_h() * net_w() * sizeof(float)));
+  plane_order_ = 1;  // RGB planes, ImageNet constants (visualizations/AutoDrive/video_visualization.py:29-33)
+  resize_mode_ = 1;  // ... behind PIL's antialiased Image.resize(..., Image.BILINEAR) (same lines)
+  push_op("preprocess", "preprocess", [this](hipStream_t st) {
+    PreprocessParams pp{};
+    pp.frame = d_frame_;
+    pp.stride = frame_stride_;
+    pp.xtab = d_xtab_;
+    pp.ytab = d_ytab_;
+    pp.out_h = net_h();
+    pp.out_w = net_w();
+    static const float mean_rgb[3] = {0.485f, 0.456f, 0.406f}, std_rgb[3] = {0.229f, 0.224f, 0.225f};
+    for (int c = 0; c < 3; ++c) {
+      const int colour = plane_order_ == 1 ? c : 2 - c;
+      pp.src_c[c] = pixel_format_ == 1 ? colour : 2 - colour;
+      pp.mean[c] = mean_rgb[colour];
+      pp.stdv[c] = std_rgb[colour];
+    }
+    pp.out = d_input_;
+    pp.norm_form = norm_form_;
+    if (resize_mode_ != 0) return launch_pil_resample(pil_params(pp), st);
+    return launch_preprocess(pp, st);
+  });
+  first_net_op_ = 1;
+
+  // ---- backbone; head input (autodrive_head.py:70-87): cat([prev, curr]).  Round 5: cv2 -- the backbone's last convolution -- stores this frame's P5
+  // STRAIGHT into the second half of the 512-channel tensor (an alias view with the tensor's row pitch: the epilogues store at pixel * Cstore + channel),
+  // so the "place" copy launch is gone; the previous frame's features move to the first half right BEFORE it ("shift": the only copy a streaming pair needs).
+  const AdFeatures feat = build_ad_backbone(blob, "backbone.", [&](int c5, int H, int W) -> Act* {
+    head_cat = new_act("head.cat", 2 * c5, H, W);
+    const ActView cv = head_cat->view();
+    ad_shift_op_ = ops_.size();
+    push_op("head.shift_prev", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(cv, c5, cv, 0, c5, st); });
+    return alias_slice("backbone.p5.3.cv2", head_cat, c5, c5);
+  });
+  ad_place_op_ = feat.p5_op;        // prime_previous() runs the plan up to and including this launch (minus the shift)
   // ---- head: 3 x (conv3x3 + SiLU) -> flatten (C-major) -> MLP
   Act* cat = head_cat;
   ConvOpts so;
@@ -1278,7 +1309,7 @@ void Engine::build_autodrive(const WeightBlob& blob) {
   {
     const ActView hv = h3->view();
     const int cr = h3->Creal;
-    push("head.flatten", "act_to_nchw", [=](hipStream_t st) { return launch_act_to_nchw(hv, cr, v0, st); });
+    push_op("head.flatten", "act_to_nchw", [=](hipStream_t st) { return launch_act_to_nchw(hv, cr, v0, st); });
   }
   out_c_ = 3;
   out_h_ = 1;
@@ -1297,7 +1328,7 @@ void Engine::build_autodrive(const WeightBlob& blob) {
     fp.K = K;
     fp.act = act;
     fp.out = out ? out : static_cast<float*>(dalloc((size_t)w.shape[0] * sizeof(float)));
-    push(name, "fc", [fp](hipStream_t st) { return launch_fc(fp, st); }, 2.0 * fp.N * K, (fp.w8 ? 1.0 : 4.0) * fp.N * K);
+    push_op(name, "fc", [fp](hipStream_t st) { return launch_fc(fp, st); }, 2.0 * fp.N * K, (fp.w8 ? 1.0 : 4.0) * fp.N * K);
     return fp.out;
   };
   const float* f1 = fc("head.fc1.0", v0, flat, ACT_SILU, nullptr);
@@ -1324,8 +1355,161 @@ void Engine::build_autodrive(const WeightBlob& blob) {
     fp.K = 512;
     fp.act = ACT_NONE;
     fp.out = d_logits_;
-    push("head.distance+curvature+flag", "fc", [fp](hipStream_t st) { return launch_fc(fp, st); }, 2.0 * 3 * 512, (fp.w8 ? 1.0 : 4.0) * 3 * 512);
+    push_op("head.distance+curvature+flag", "fc", [fp](hipStream_t st) { return launch_fc(fp, st); }, 2.0 * 3 * 512, (fp.w8 ? 1.0 : 4.0) * 3 * 512);
   }
+  decode_mode_ = 0;
+}
+
+// ------------------------------------------------------------------------------------------------ AutoSpeed
+// auto_speed_network.py:33-48 ('n' variant, 512 x 1024 input: :9-10 and the CTX map sizes): net (the backbone above under "net.") -> fpn
+// (auto_speed_neck.py:18-24) -> head (auto_speed_head.py:39-66).  Input: fp32 planes R, G, B in [0, 1] in d_input_ -- what the letterbox kernel of
+// vp_detect_preprocess leaves on the device; the engine has no frame preprocess of its own (entries: vp_infer_tensor, vp_detect_infer).
+// Output: fp32 [4 + nc][10752] (cx, cy, w, h in input pixels, class scores), the tensor vp_detect_postprocess(raw_on_device = 1) reads.
+//
+// Concatenations cost no launch where the producer can store through an alias view (alias_slice: the epilogues store at pixel * Cstore + channel):
+//   C3K2 (common_layers.py:166-180): conv1's two halves and the appended block output live in ONE 3c-channel tensor; a convolution's INPUT cannot be
+//   a slice (the kernels take the channel count as the row pitch), so the half that feeds the block is copied out once (chan_copy), and the Residual
+//   (:26-27) adds its input back from the slice in place: x + SiLU(conv2(..)) is the epilogues' RES_ADD, which is applied behind the activation.
+//   Neck: cat([up(A), B]) is one upsample2_cat launch (B comes from the backbone, which also feeds its next stage: it moves too); h3 / h5 and the
+//   tensors beside them (h1's output, the backbone's P5) are stored straight into the concatenated tensor.
+void Engine::build_autospeed(const WeightBlob& blob) {
+  auto T = [&](const std::string& k) -> const HostTensor& { return blob.get(k); };
+  const double esz = split() ? 4.0 : 2.0;
+  {  // DFL (common_layers.py:139-141): the 1x1 convolution is the constant 0..15 -- the decode kernel has it built in
+    const HostTensor& d = T("head.dfl.conv.weight");
+    bool ok = d.data.size() == 16;
+    for (int i = 0; ok && i < 16; ++i) ok = d.data[i] == (float)i;
+    if (!ok) throw std::runtime_error("weight blob: head.dfl.conv.weight is not the constant 0..15 of DFL (common_layers.py:140-141)");
+  }
+  const HostTensor& wc = T("head.cls.0.4.weight");
+  if (wc.shape.size() != 4 || wc.shape[0] < 1 || wc.shape[0] > 4092) throw std::runtime_error("weight blob: head.cls.0.4.weight: bad shape");
+  const int nc = wc.shape[0];
+  d_input_ = static_cast<float*>(dalloc((size_t)3 * net_h() * net_w() * sizeof(float)));
+  first_net_op_ = 0;         // no preprocess launch: the plan starts at the stem
+  input_is_tensor_ = true;
+
+  auto conv_bn = [&](const std::string& name, const Act* in, int ks, int stride, const Act* res = nullptr, Act* dst = nullptr) -> Act* {
+    Folded f = fold_conv_norm(blob, name);
+    ConvOpts o;
+    o.act = ACT_SILU;
+    o.stride = stride;
+    if (res) {
+      o.res_mode = RES_ADD;   // applied behind the activation (conv_epilogue.hpp): x + SiLU(conv(..))
+      o.res = res;
+    }
+    return add_conv(name, in, f.w, f.b, f.cout, ks, o, dst);
+  };
+  auto copy_slice = [&](const std::string& name, const Act* src, int src_off, const Act* dst, int dst_off, int nch) {
+    const ActView sv = src->view(), dv = dst->view();
+    push_op(name, "chan_copy", [=](hipStream_t st) { return launch_chan_copy(sv, src_off, dv, dst_off, nch, st); }, 0, 2.0 * esz * nch * src->H * src->W);
+  };
+  // Residual (common_layers.py:20-27); res: where the block's input is read back for the sum (same row pitch as dst)
+  auto residual = [&](const std::string& p, const Act* x, const Act* res, Act* dst) -> Act* {
+    return conv_bn(p + ".conv2", conv_bn(p + ".conv1", x, 3, 1), 3, 1, res, dst);
+  };
+  auto c3k2 = [&](const std::string& p, const Act* in, bool csp, Act* dst) -> Act* {
+    const int c = fold_conv_norm(blob, p + ".conv1").cout / 2;
+    if (c % 32 != 0) throw std::runtime_error(p + ": slice width must be a multiple of 32");
+    Act* cat = new_act(p + ".cat", 3 * c, in->H, in->W);
+    conv_bn(p + ".conv1", in, 1, 1, nullptr, alias_slice(p + ".conv1", cat, 0, 2 * c));
+    Act* y1 = new_act(p + ".y1", c, in->H, in->W);
+    copy_slice(p + ".split", cat, c, y1, 0, c);
+    Act* y2 = alias_slice(p + ".res_m.0", cat, 2 * c, c);
+    const std::string m = p + ".res_m.0";
+    if (!csp) {
+      residual(m, y1, alias_slice(p + ".y1@cat", cat, c, c), y2);
+    } else {   // C3K (common_layers.py:149-163): conv3(cat(res_m(conv1(x)), conv2(x)))
+      const int h = c / 2;
+      if (h % 32 != 0) throw std::runtime_error(m + ": slice width must be a multiple of 32");
+      Act* u = new_act(m + ".cat", c, in->H, in->W);
+      Act* r = conv_bn(m + ".conv1", y1, 1, 1);
+      conv_bn(m + ".conv2", y1, 1, 1, nullptr, alias_slice(m + ".conv2", u, h, h));
+      for (int i = 0; i < 2; ++i) r = residual(m + ".res_m." + std::to_string(i), r, r, nullptr);
+      copy_slice(m + ".cat0", r, 0, u, 0, h);
+      conv_bn(m + ".conv3", u, 1, 1, nullptr, y2);
+    }
+    return conv_bn(p + ".conv2", cat, 1, 1, nullptr, dst);
+  };
+  auto up_cat = [&](const std::string& name, const Act* a, const Act* b, Act* out) {
+    Upsample2CatParams q{};
+    q.a = a->view();
+    q.b = b->view();
+    q.out = out->view();
+    q.a_nch = a->Creal;
+    q.b_nch = b->Creal;
+    if (!upsample2_cat_ok(q)) throw std::runtime_error(name + ": unsupported shape for upsample2_cat");
+    push_op(name, "upsample2_cat", [q](hipStream_t st) { return launch_upsample2_cat(q, st); }, 0, 2.0 * esz * out->elems());
+  };
+
+  // ---- backbone: P5 goes straight into the neck's last concatenation cat([h5(p4), p5]) (auto_speed_neck.py:23)
+  const int c_h3 = T("fpn.h3.conv.weight").shape[0], c_h5 = T("fpn.h5.conv.weight").shape[0];
+  Act* cat4 = nullptr;
+  const AdFeatures f = build_ad_backbone(blob, "net.", [&](int c5, int H, int W) -> Act* {
+    cat4 = new_act("fpn.cat4", c_h5 + c5, H, W);
+    return alias_slice("net.p5.3.cv2", cat4, c_h5, c5);
+  });
+  if (!f.p3 || !f.p4 || !f.p5 || f.p4->H != 2 * f.p5->H || f.p3->H != 2 * f.p4->H) throw std::runtime_error("AutoSpeed backbone: unexpected pyramid");
+  // ---- neck (auto_speed_neck.py:18-24)
+  Act* cat1 = new_act("fpn.cat1", f.p5->Creal + f.p4->Creal, f.p4->H, f.p4->W);
+  up_cat("fpn.up5+p4", f.p5, f.p4, cat1);
+  const int c_h1 = fold_conv_norm(blob, "fpn.h1.conv2").cout;
+  Act* cat3 = new_act("fpn.cat3", c_h3 + c_h1, f.p4->H, f.p4->W);
+  Act* p4a = c3k2("fpn.h1", cat1, false, alias_slice("fpn.h1.conv2", cat3, c_h3, c_h1));
+  Act* cat2 = new_act("fpn.cat2", p4a->Creal + f.p3->Creal, f.p3->H, f.p3->W);
+  up_cat("fpn.up4+p3", p4a, f.p3, cat2);
+  Act* p3 = c3k2("fpn.h2", cat2, false, nullptr);
+  conv_bn("fpn.h3", p3, 3, 2, nullptr, alias_slice("fpn.h3", cat3, 0, c_h3));
+  Act* p4 = c3k2("fpn.h4", cat3, false, nullptr);
+  conv_bn("fpn.h5", p4, 3, 2, nullptr, alias_slice("fpn.h5", cat4, 0, c_h5));
+  Act* p5 = c3k2("fpn.h6", cat4, true, nullptr);
+
+  // ---- head (auto_speed_head.py:39-53), per level: box = 2 x (conv3x3 + SiLU) + 1x1 -> 64; cls = dw3x3, 1x1, dw3x3, 1x1 (all + SiLU) + 1x1 -> nc
+  auto dw = [&](const std::string& name, const Act* in) -> Act* {
+    Folded fd = fold_conv_norm(blob, name);
+    if (fd.cout != in->Creal || fd.cin != 1 || fd.k != 3) throw std::runtime_error("depthwise conv shape mismatch: " + name);
+    std::vector<float> wk((size_t)9 * in->C, 0.0f), bk(in->C, 0.0f);
+    for (int c = 0; c < fd.cout; ++c) {
+      for (int k = 0; k < 9; ++k) wk[(size_t)k * in->C + c] = fd.w[(size_t)c * 9 + k];
+      bk[c] = fd.b[c];
+    }
+    Act* out = new_act(name, fd.cout, in->H, in->W);
+    DwPlainParams dp{};
+    dp.in = in->view();
+    dp.out = out->view();
+    dp.w = dupload(wk);
+    dp.b = dupload(bk);
+    dp.act = ACT_SILU;
+    wbytes_[2] += 4 * wk.size();
+    push_op(name, "dwconv_plain<silu>", [dp](hipStream_t st) { return launch_dwconv_plain(dp, st); }, 2.0 * 9 * fd.cout * in->H * in->W, 2.0 * esz * in->elems());
+    return out;
+  };
+  auto plain1x1 = [&](const std::string& name, const Act* in) -> Act* {
+    const HostTensor& w = T(name + ".weight");
+    return add_conv(name, in, w.data, T(name + ".bias").data, w.shape[0], 1, ConvOpts{});
+  };
+  DetectHeadParams hp{};
+  const Act* feats[3] = {p3, p4, p5};
+  int first = 0;
+  for (int i = 0; i < 3; ++i) {
+    const std::string bp = "head.box." + std::to_string(i), cp = "head.cls." + std::to_string(i);
+    Act* box = plain1x1(bp + ".2", conv_bn(bp + ".1", conv_bn(bp + ".0", feats[i], 3, 1), 3, 1));
+    Act* cls = plain1x1(cp + ".4", conv_bn(cp + ".3", dw(cp + ".2", conv_bn(cp + ".1", dw(cp + ".0", feats[i]), 1, 1)), 1, 1));
+    if (box->Creal != 64 || cls->Creal != nc) throw std::runtime_error("weight blob: detector head widths (64 box channels, nc classes on every level): " + bp);
+    hp.lv[i].box = box->view();
+    hp.lv[i].cls = cls->view();
+    hp.lv[i].first = first;
+    hp.lv[i].stride = (float)net_h() / (float)feats[i]->H;   // auto_speed_network.py:41
+    first += feats[i]->H * feats[i]->W;
+  }
+  out_c_ = 4 + nc;
+  out_h_ = 1;
+  out_w_ = first;   // vp_logits / vp_output_shape: {1, 4 + nc, 1, 10752}
+  d_logits_ = static_cast<float*>(dalloc((size_t)out_c_ * first * sizeof(float)));
+  d_mask_ = static_cast<uint8_t*>(dalloc((size_t)first));   // no class map for a detector: stays zero
+  hp.nc = nc;
+  hp.total = first;
+  hp.out = d_logits_;
+  push_op("head.decode", "detect_head_decode", [hp](hipStream_t st) { return launch_detect_head_decode(hp, st); }, 0, esz * first * (64.0 + nc) + 4.0 * out_c_ * first);
   decode_mode_ = 0;
 }
 
@@ -1347,7 +1531,7 @@ void Engine::finish_plan() {
   if (d_logits_ && !h_logits_) {
     VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_logits_), (size_t)out_c_ * out_h_ * out_w_ * sizeof(float), hipHostMallocDefault));
     VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_mask_), (size_t)out_h_ * out_w_, hipHostMallocDefault));
-    if (kind_ != 4 && !decode_fused_) {  // AutoDrive returns three scalars: no mask to decode; else the logits conv already decoded
+    if (kind_ != 4 && kind_ != 5 && !decode_fused_) {  // AutoDrive returns three scalars, the detector boxes: no mask to decode; else the logits conv already decoded
       Op op;
       op.name = "decode";
       op.bytes = 4.0 * out_c_ * out_h_ * out_w_ + out_h_ * out_w_;

@@ -127,8 +127,13 @@ class Engine {
   // networks), 1 / 2 = Pillow's antialiased BILINEAR / BICUBIC (the Python scripts' Image.resize; 1 is AutoDrive's default)
   void set_resize_mode(int mode);
   int resize_mode() const { return resize_mode_; }
-  int net_h() const { return kind_ == 4 ? 512 : 320; }   // AutoDrive: autodrive_network.py:8-9
-  int net_w() const { return kind_ == 4 ? 1024 : 640; }
+  int net_h() const { return kind_ == 4 || kind_ == 5 ? 512 : 320; }   // AutoDrive: autodrive_network.py:8-9, AutoSpeed: auto_speed_network.py:9-10
+  int net_w() const { return kind_ == 4 || kind_ == 5 ? 1024 : 640; }
+  int kind() const { return kind_; }
+  // AutoSpeed (kind 5): the network input on the device ([3][512][1024] fp32 planes R, G, B in [0, 1]) for a producer on the same GPU (vp_detect_infer's
+  // letterbox kernel writes it), and the note that it now holds this frame's tensor
+  float* dev_input() const { return d_input_; }
+  void note_device_tensor();
   // AutoDrive (kind 4) pairs every frame with the previous one: infer_pair() runs the backbone on `prev` first
   // (features only), enqueue() then shifts the feature slots and runs backbone + head on the resident frame.
   void prime_previous();
@@ -141,6 +146,7 @@ class Engine {
   void sync();
   void fetch_outputs();      // enqueue_fetch() + sync
   void enqueue_fetch();      // async D2H of the selected outputs (set_outputs) into the pinned host buffers
+  void enqueue_status_fetch();  // async D2H of the range probe's verdict only
   // bit 0: logits, bit 1: mask.  De-selected outputs stay in HBM and are copied on first use (vp_logits / vp_mask_u8).
   void set_outputs(int mask) {
     if (mask < 0 || mask > 3) throw std::invalid_argument("outputs: bit 0 = logits, bit 1 = mask");
@@ -263,6 +269,17 @@ class Engine {
 
   void build_model(const WeightBlob& blob);
   void build_autodrive(const WeightBlob& blob);
+  void build_autospeed(const WeightBlob& blob);
+  // the backbone AutoDrive and AutoSpeed share (engine.cpp): P3 / P4 / P5 and the index of the launch that stores P5
+  struct AdFeatures {
+    Act* p3 = nullptr;
+    Act* p4 = nullptr;
+    Act* p5 = nullptr;
+    size_t p5_op = 0;
+  };
+  AdFeatures build_ad_backbone(const WeightBlob& blob, const std::string& prefix, const std::function<Act*(int, int, int)>& p5_dest);
+  void push_op(const std::string& name, const char* kernel, std::function<hipError_t(hipStream_t)> fn, double flops = 0, double bytes = 0);
+  Act* alias_slice(const std::string& name, Act* whole, int ch_off, int nch);  // view of channels [ch_off, ch_off + nch) with the tensor's row pitch (no allocation)
   std::vector<Act*> build_backbone(const WeightBlob& blob, const std::string& prefix);
   Act* build_context(const WeightBlob& blob, const std::string& p, const Act* deep, int cctx);
   Act* build_neck(const WeightBlob& blob, const std::string& p, const Act* ctx, const std::vector<Act*>& feats, int cctx);

@@ -235,6 +235,7 @@ bool frame_range_registered(const void* p, size_t bytes) {
 
 void Engine::upload_frame(const uint8_t* frame, int h, int w, int stride, int index) {
   if (base_) throw std::invalid_argument("shared engine: frames go to the base engine (vp_infer on the base, then vp_infer_shared)");
+  if (kind_ == 5) throw std::runtime_error("VP_AUTOSPEED engines have no frame preprocess of their own: attach the engine to a detector (vp_detect_attach) and call vp_detect_infer, or hand the letterboxed tensor to vp_infer_tensor");
   if (!frame || h < 2 || w < 2 || stride < 3 * w) throw std::invalid_argument("bad frame geometry");
   if (index < 0 || index >= frames_) throw std::invalid_argument("frame index out of range");
   VP_HIP_CHECK(hipSetDevice(gpu_));
@@ -297,6 +298,12 @@ void Engine::upload_tensor(const float* nchw) {
   if (!nchw) throw std::invalid_argument("null tensor");
   VP_HIP_CHECK(hipSetDevice(gpu_));
   VP_HIP_CHECK(hipMemcpyAsync(d_input_, nchw, (size_t)3 * net_h() * net_w() * sizeof(float), hipMemcpyHostToDevice, stream_));
+  if (!input_is_tensor_) { graph_valid_ = false; ++plan_epoch_; }
+  input_is_tensor_ = true;
+}
+
+void Engine::note_device_tensor() {
+  if (kind_ != 5) throw std::invalid_argument("note_device_tensor: VP_AUTOSPEED engines only");
   if (!input_is_tensor_) { graph_valid_ = false; ++plan_epoch_; }
   input_is_tensor_ = true;
 }
@@ -474,6 +481,14 @@ void Engine::enqueue_fetch() {
   if ((outputs_ & 2) && d_mask_) VP_HIP_CHECK(hipMemcpyAsync(h_mask_, d_mask_, (size_t)out_h_ * out_w_, hipMemcpyDeviceToHost, stream_));
   host_logits_valid_ = (outputs_ & 1) != 0;
   host_mask_valid_ = (outputs_ & 2) != 0;
+  if (finite_check_ && d_status_) {
+    VP_HIP_CHECK(hipMemcpyAsync(h_status_, d_status_, VP_PROBE_BLOCKS * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+    status_pending_ = true;
+  }
+}
+
+// The probe's verdict alone (vp_detect_infer: the network's output stays on the device; vp_logits fetches it lazily if asked)
+void Engine::enqueue_status_fetch() {
   if (finite_check_ && d_status_) {
     VP_HIP_CHECK(hipMemcpyAsync(h_status_, d_status_, VP_PROBE_BLOCKS * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
     status_pending_ = true;

@@ -381,11 +381,34 @@ struct AttnParams {
 bool attention_block_ok(const AttnParams& p);
 hipError_t launch_attention(const AttnParams& p, hipStream_t st);
 struct DwPlainParams {
-  ActView in, out;   // out = add + dwconv3x3(in) (BN folded, no activation), common_layers.py:103
-  ActView add;
+  ActView in, out;   // out = [add +] act(dwconv3x3(in)) (BN folded); Attention's positional conv (common_layers.py:103): no activation, add given
+  ActView add;       // add.hi == nullptr: no add (the detector head's class branch, auto_speed_head.py:45,47)
   const float* w;    // [9][C]
   const float* b;    // [C]
+  int act;           // ActFn applied before the add; 0 (ACT_NONE) = identity
 };
 hipError_t launch_dwconv_plain(const DwPlainParams& p, hipStream_t st);
+
+// ---- AutoSpeed detector network (neck: kernels_autodrive.hip; head decode: kernels_detect.hip)
+// out[:, 0 : a_nch] = nearest x2 of a[:, a_off : a_off + a_nch], out[:, a_nch : a_nch + b_nch] = b[:, b_off : b_off + b_nch]  (auto_speed_neck.py:20-22)
+struct Upsample2CatParams {
+  ActView a, b, out;   // a: H x W (C = row pitch), b and out: 2H x 2W
+  int a_off, a_nch, b_off, b_nch;   // multiples of 8
+};
+bool upsample2_cat_ok(const Upsample2CatParams& p);
+hipError_t launch_upsample2_cat(const Upsample2CatParams& p, hipStream_t st);
+// AutoSpeedHead.forward in eval mode behind the last convolutions (auto_speed_head.py:57-66) + DFL (common_layers.py:143-146), all levels in one launch
+struct DetectHeadLevel {
+  ActView box;   // [H][W][>= 64]: 4 sides x 16 bins, channel = side * 16 + bin
+  ActView cls;   // [H][W][>= nc] class logits
+  int first;     // index of the level's first anchor in the output rows
+  float stride;
+};
+struct DetectHeadParams {
+  DetectHeadLevel lv[3];
+  int nc, total;   // classes; anchors over all levels (10752 at 512 x 1024)
+  float* out;      // fp32 [4 + nc][total]: cx, cy, w, h in input pixels, then sigmoid class scores
+};
+hipError_t launch_detect_head_decode(const DetectHeadParams& p, hipStream_t st);
 
 }  // namespace vp

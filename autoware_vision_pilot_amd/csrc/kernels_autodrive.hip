@@ -300,7 +300,8 @@ __global__ __launch_bounds__(256) void attention_block_kernel(const AttnParams p
   }
 }
 
-// out = add + depthwise3x3(in) + b  (Attention: ... + self.conv1(v), common_layers.py:103; BN folded, identity activation)
+// out = [add +] act(depthwise3x3(in) + b), BN folded.  Attention (... + self.conv1(v), common_layers.py:103): identity activation, add given;
+// the detector head's class branch (Conv(x, x, SiLU, k=3, p=1, g=x), auto_speed_head.py:45,47): SiLU, no add.
 __global__ __launch_bounds__(256) void dwconv_plain_kernel(const DwPlainParams p) {
   const int CG = p.in.C >> 3;
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -320,11 +321,33 @@ __global__ __launch_bounds__(256) void dwconv_plain_kernel(const DwPlainParams p
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[i] = fmaf(v[i], wk[i], acc[i]);
     }
-  float a[8];
-  load8(p.add, (size_t)pix * p.add.C + cg * 8, a);
+  if (p.act != ACT_NONE) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] += a[i];
+    for (int i = 0; i < 8; ++i) acc[i] = apply_act(acc[i], p.act);
+  }
+  if (p.add.hi) {
+    float a[8];
+    load8(p.add, (size_t)pix * p.add.C + cg * 8, a);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] += a[i];
+  }
   store8(p.out, (size_t)pix * p.out.C + cg * 8, acc);
+}
+
+// cat([Upsample(scale_factor=2, nearest)(A), B], 1) of the detector neck (auto_speed_neck.py:20-22) in one launch: a thread moves one 16-byte channel
+// octet of one OUTPUT pixel, both planes -- octets [0, a_nch / 8) come from A's pixel (y / 2, x / 2), the ones behind them from B's pixel (y, x).
+// a_off / b_off: first channel of the slice inside A / B (A may be an alias view into a wider tensor: a.C is its row pitch).  Pure moves: bit-exact.
+__global__ __launch_bounds__(256) void upsample2_cat_kernel(const Upsample2CatParams p) {
+  const int CG = (p.a_nch + p.b_nch) >> 3, CA = p.a_nch >> 3;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)p.out.H * p.out.W * CG) return;
+  const int cg = (int)(t % CG), pix = (int)(t / CG);
+  const int y = pix / p.out.W, x = pix - y * p.out.W;
+  const ActView& src = cg < CA ? p.a : p.b;
+  const size_t so = cg < CA ? ((size_t)(y >> 1) * p.a.W + (x >> 1)) * p.a.C + p.a_off + cg * 8 : (size_t)pix * p.b.C + p.b_off + (cg - CA) * 8;
+  const size_t dso = (size_t)pix * p.out.C + cg * 8;
+  *reinterpret_cast<h8_t*>(p.out.hi + dso) = *reinterpret_cast<const h8_t*>(src.hi + so);
+  if (p.out.lo) *reinterpret_cast<h8_t*>(p.out.lo + dso) = *reinterpret_cast<const h8_t*>(src.lo + so);
 }
 
 hipError_t launch_chan_copy(const ActView& src, int src_off, const ActView& dst, int dst_off, int nch, hipStream_t st) {
@@ -355,6 +378,15 @@ hipError_t launch_attention(const AttnParams& p, hipStream_t st) {
   }
   if (p.qblock != 0) return hipErrorInvalidValue;
   VP_LAUNCH(attention_kernel, dim3(T, p.heads), dim3(256), (T + 256 + p.dk) * sizeof(float), st, p);
+}
+bool upsample2_cat_ok(const Upsample2CatParams& p) {
+  return p.a_nch > 0 && p.b_nch > 0 && !((p.a_nch | p.b_nch | p.a_off | p.b_off | p.a.C | p.b.C | p.out.C) & 7) && p.a_off + p.a_nch <= p.a.C && p.b_off + p.b_nch <= p.b.C &&
+         p.a_nch + p.b_nch <= p.out.C && p.out.H == 2 * p.a.H && p.out.W == 2 * p.a.W && p.out.H == p.b.H && p.out.W == p.b.W &&
+         (p.out.lo == nullptr) == (p.a.lo == nullptr) && (p.out.lo == nullptr) == (p.b.lo == nullptr);
+}
+hipError_t launch_upsample2_cat(const Upsample2CatParams& p, hipStream_t st) {
+  if (!upsample2_cat_ok(p)) return hipErrorInvalidValue;
+  VP_LAUNCH(upsample2_cat_kernel, dim3(nblk((long long)p.out.H * p.out.W * ((p.a_nch + p.b_nch) >> 3))), dim3(256), 0, st, p);
 }
 hipError_t launch_dwconv_plain(const DwPlainParams& p, hipStream_t st) {
   VP_LAUNCH(dwconv_plain_kernel, dim3(nblk((long long)p.in.H * p.in.W * (p.in.C >> 3))), dim3(256), 0, st, p);

@@ -185,4 +185,69 @@ hipError_t launch_detect_decode_nms(const DetectParams& p, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ detector head decode
+// AutoSpeedHead.forward in eval mode behind the per-level convolutions (auto_speed_head.py:57-66) with DFL (common_layers.py:143-146), the three
+// levels in one launch: a thread per anchor reads its 64 box channels and nc class channels as hi (+ lo) and writes one column of the fp32
+// [4 + nc][total] tensor (rows are contiguous over anchors: the stores of a wave coalesce; levels concatenated P3, P4, P5, row-major inside a level).
+// Arithmetic, all fp32, in this order:
+//   per side s (0 = left, 1 = top, 2 = right, 3 = bottom): m = max of the 16 bins; e_i = expf(x_i - m); S = e_0 + e_1 + ... + e_15 (bin order);
+//   d_s = 0 * (e_0 / S) + 1 * (e_1 / S) + ... + 15 * (e_15 / S) summed in bin order (DFL's conv weight is the constant 0..15: checked at load);
+//   anchor (ax, ay) = (x + 0.5, y + 0.5);  a = (ax - d_0, ay - d_1);  b = (ax + d_2, ay + d_3);
+//   cx, cy = (a + b) / 2 * stride;  w, h = (b - a) * stride;  score_c = 1 / (1 + expf(-logit_c)).
+__global__ __launch_bounds__(256) void detect_head_decode_kernel(const DetectHeadParams p) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= p.total) return;
+  const int li = n >= p.lv[2].first ? 2 : (n >= p.lv[1].first ? 1 : 0);
+  const DetectHeadLevel& L = p.lv[li];
+  const int pix = n - L.first;
+  const int y = pix / L.box.W, x = pix - y * L.box.W;
+  float d[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float v[16];
+    load8(L.box, (size_t)pix * L.box.C + s * 16, v);
+    load8(L.box, (size_t)pix * L.box.C + s * 16 + 8, v + 8);
+    float m = v[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) m = fmaxf(m, v[i]);
+    float S = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      v[i] = expf(v[i] - m);
+      S += v[i];
+    }
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc += (float)i * (v[i] / S);
+    d[s] = acc;
+  }
+  const float ax = (float)x + 0.5f, ay = (float)y + 0.5f;
+  const float a0 = ax - d[0], a1 = ay - d[1], b0 = ax + d[2], b1 = ay + d[3];
+  float* o = p.out + n;
+  o[0] = (a0 + b0) / 2.0f * L.stride;
+  o[(size_t)p.total] = (a1 + b1) / 2.0f * L.stride;
+  o[(size_t)2 * p.total] = (b0 - a0) * L.stride;
+  o[(size_t)3 * p.total] = (b1 - a1) * L.stride;
+  for (int c0 = 0; c0 < p.nc; c0 += 8) {
+    float v[8];
+    load8(L.cls, (size_t)pix * L.cls.C + c0, v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (c0 + i < p.nc) o[(size_t)(4 + c0 + i) * p.total] = sigmoid_f(v[i]);
+  }
+}
+
+hipError_t launch_detect_head_decode(const DetectHeadParams& p, hipStream_t st) {
+  int first = 0;
+  for (int i = 0; i < 3; ++i) {
+    const DetectHeadLevel& L = p.lv[i];
+    if (!L.box.hi || !L.cls.hi || L.box.C < 64 || (L.box.C & 7) || (L.cls.C & 7) || L.cls.C < ((p.nc + 7) & ~7) || L.box.H != L.cls.H || L.box.W != L.cls.W || L.first != first ||
+        L.box.H < 1 || L.box.W < 1)
+      return hipErrorInvalidValue;
+    first += L.box.H * L.box.W;
+  }
+  if (!p.out || p.nc < 1 || p.total != first) return hipErrorInvalidValue;
+  VP_LAUNCH(detect_head_decode_kernel, dim3(nblk(p.total)), dim3(256), 0, st, p);
+}
+
 }  // namespace vp

@@ -676,6 +676,124 @@ int vp_op_conv2d(int gpu_id, int precision, int mode, const float* in, int cin, 
   }
 }
 
+// ---- single-operator entries of the detector network's kernels (unit tests)
+}  // extern "C"
+namespace {
+// (hi, lo) planes of an activation, NHWC with padded channels on the device -> fp16 bit patterns [Creal][H][W] on the host
+void read_planes_chw(vp::Engine& g, const vp::Act* a, uint16_t* out_hi, uint16_t* out_lo) {
+  std::vector<uint16_t> buf(a->elems());
+  for (int plane = 0; plane < 2; ++plane) {
+    uint16_t* dst = plane ? out_lo : out_hi;
+    const vp::half_t* src = plane ? a->lo : a->hi;
+    if (!dst) continue;
+    if (!src) {
+      std::memset(dst, 0, (size_t)a->Creal * a->H * a->W * sizeof(uint16_t));
+      continue;
+    }
+    g.copy_d2h(buf.data(), src, buf.size() * sizeof(uint16_t));
+    for (int c = 0; c < a->Creal; ++c)
+      for (int i = 0; i < a->H * a->W; ++i) dst[(size_t)c * a->H * a->W + i] = buf[(size_t)i * a->C + c];
+  }
+}
+template <class F>
+int op_guarded(char* err, size_t err_len, F&& f) {
+  try {
+    f();
+    return VP_OK;
+  } catch (const std::invalid_argument& ex) {
+    set_err(err, err_len, ex.what());
+    return VP_ERR_ARG;
+  } catch (const std::exception& ex) {
+    set_err(err, err_len, ex.what());
+    return VP_ERR_HIP;
+  }
+}
+}  // namespace
+extern "C" {
+
+int vp_op_detect_head_decode(int gpu_id, int precision, const float* box, const float* cls, int nc, int h0, int w0, float* out, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!box || !cls || !out || nc < 1 || nc > 4092 || h0 < 4 || w0 < 4 || (h0 & 3) || (w0 & 3) || (long long)h0 * w0 > (1 << 22)) throw std::invalid_argument("bad argument");
+    vp::Engine g(-1, nullptr, precision, gpu_id);
+    vp::DetectHeadParams p{};
+    size_t off = 0;
+    int first = 0;
+    for (int l = 0; l < 3; ++l) {
+      const int h = h0 >> l, w = w0 >> l;
+      vp::Act* b = g.new_act("box", 64, h, w);
+      vp::Act* c = g.new_act("cls", nc, h, w);
+      g.upload_act(b, box + off * 64);
+      g.upload_act(c, cls + off * nc);
+      p.lv[l].box = b->view();
+      p.lv[l].cls = c->view();
+      p.lv[l].first = first;
+      p.lv[l].stride = (float)(8 << l);
+      off += (size_t)h * w;
+      first += h * w;
+    }
+    p.nc = nc;
+    p.total = first;
+    p.out = g.alloc_f32((size_t)(4 + nc) * first);
+    VP_HIP_CHECK(vp::launch_detect_head_decode(p, g.stream()));
+    g.copy_d2h(out, p.out, (size_t)(4 + nc) * first * sizeof(float));
+  });
+}
+
+int vp_op_upsample2_cat(int gpu_id, int precision, const float* a, int ca, const float* b, int cb, int h, int w, uint16_t* out_hi, uint16_t* out_lo,
+                        char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!a || !b || !out_hi || ca < 1 || cb < 1 || h < 1 || w < 1 || (ca & 31) || (long long)h * w > (1 << 20)) throw std::invalid_argument("bad argument (ca: a multiple of 32)");
+    vp::Engine g(-1, nullptr, precision, gpu_id);
+    vp::Act* ta = g.new_act("a", ca, h, w);
+    vp::Act* tb = g.new_act("b", cb, 2 * h, 2 * w);
+    vp::Act* to = g.new_act("out", ca + cb, 2 * h, 2 * w);
+    g.upload_act(ta, a);
+    g.upload_act(tb, b);
+    vp::Upsample2CatParams q{};
+    q.a = ta->view();
+    q.b = tb->view();
+    q.out = to->view();
+    q.a_nch = ca;
+    q.b_nch = tb->C;   // padded width: the pad channels are zero and land in the output's padding
+    if (ca + tb->C > to->C) q.b_nch = to->C - ca;
+    VP_HIP_CHECK(vp::launch_upsample2_cat(q, g.stream()));
+    read_planes_chw(g, to, out_hi, out_lo);
+  });
+}
+
+int vp_op_dwconv3x3(int gpu_id, int precision, const float* in, int c, int h, int w, const float* weight, const float* bias, int act, const float* add,
+                    uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!in || !weight || !bias || !out_hi || c < 1 || h < 1 || w < 1 || (long long)h * w > (1 << 20)) throw std::invalid_argument("bad argument");
+    vp::Engine g(-1, nullptr, precision, gpu_id);
+    vp::Act* ti = g.new_act("in", c, h, w);
+    vp::Act* to = g.new_act("out", c, h, w);
+    g.upload_act(ti, in);
+    std::vector<float> wk((size_t)9 * ti->C, 0.0f), bk(ti->C, 0.0f);
+    for (int ch = 0; ch < c; ++ch) {
+      for (int k = 0; k < 9; ++k) wk[(size_t)k * ti->C + ch] = weight[(size_t)ch * 9 + k];
+      bk[ch] = bias[ch];
+    }
+    float* dw = g.alloc_f32(wk.size());
+    float* db = g.alloc_f32(bk.size());
+    g.copy_h2d(dw, wk.data(), wk.size() * sizeof(float));
+    g.copy_h2d(db, bk.data(), bk.size() * sizeof(float));
+    vp::DwPlainParams dp{};
+    dp.in = ti->view();
+    dp.out = to->view();
+    dp.w = dw;
+    dp.b = db;
+    dp.act = act;
+    if (add) {
+      vp::Act* tadd = g.new_act("add", c, h, w);
+      g.upload_act(tadd, add);
+      dp.add = tadd->view();
+    }
+    VP_HIP_CHECK(vp::launch_dwconv_plain(dp, g.stream()));
+    read_planes_chw(g, to, out_hi, out_lo);
+  });
+}
+
 // ---- composed up-sampling stage (round 6): the load-time weight composition alone, and the whole stage as one operator
 int vp_compose_upconv(int gpu_id, const float* wt, const float* bt, const float* ws, const float* bs, const float* w3, const float* b3, int cin, int cm,
                       int cout, int cs, double* wx, double* wsk, double* bias, char* err, size_t err_len) {

@@ -1,6 +1,7 @@
 // vp_detect_*: the AutoSpeed detector's letterbox preprocess and decode + NMS on the device behind the C ABI (include/vp_hip.h; SURVEY.md N4;
-// VisionPilot/middleware_recipes/common/backends/autospeed/onnxruntime_engine.cpp:71-113, :170-290).  The detector network itself is not
-// part of this library: a host runs it with its own runtime between the two calls (or hands its output tensor over on the device).
+// VisionPilot/middleware_recipes/common/backends/autospeed/onnxruntime_engine.cpp:71-113, :170-290).  The detector network is a VP_AUTOSPEED
+// engine (engine.cpp build_autospeed) attached with vp_detect_attach: vp_detect_infer runs frame -> detections without leaving the device.  The
+// two-call form (a host's own runtime between vp_detect_preprocess and vp_detect_postprocess) stays as it was.
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
@@ -9,6 +10,7 @@
 
 #include "../../include/vp_hip.h"
 #include "engine.hpp"
+#include "vp_handle.hpp"
 #include "kernels.hpp"
 
 static_assert(sizeof(vp_detection) == sizeof(vp::Detection) && sizeof(vp_detection) == 24, "vp_detection is the reference's Detection");
@@ -35,6 +37,8 @@ struct vp_detect {
   float scale = 0.0f;
   int pad_x = 0, pad_y = 0, orig_w = 0, orig_h = 0;
   std::string err;
+  vp_engine* net = nullptr;        // borrowed VP_AUTOSPEED engine (vp_detect_attach)
+  hipEvent_t ev_in = nullptr, ev_out = nullptr;   // input tensor written (detector stream -> engine stream), network done (engine -> detector)
 
   ~vp_detect() {
     (void)hipSetDevice(gpu);
@@ -43,6 +47,8 @@ struct vp_detect {
       if (q) (void)hipFree(q);
     for (void* q : {(void*)h_frame, (void*)h_out, (void*)h_count})
       if (q) (void)hipHostFree(q);
+    if (ev_in) (void)hipEventDestroy(ev_in);
+    if (ev_out) (void)hipEventDestroy(ev_out);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -115,13 +121,18 @@ void vp_detect_destroy(vp_detect* d) { delete d; }
 
 const char* vp_detect_last_error(const vp_detect* d) { return d ? d->err.c_str() : "null handle"; }
 
-int vp_detect_preprocess(vp_detect* d, const uint8_t* bgr, int h, int w, int stride_bytes, float* dst_host_chw) {
-  return guarded(d, [&]() -> int {
-    if (!bgr || h < 1 || w < 1 || h > 16384 || w > 16384 || stride_bytes < 3 * w) throw std::invalid_argument("vp_detect_preprocess: bad frame geometry");
+}  // extern "C"
+
+namespace {
+// upload + letterbox of one frame into `dst` ([3][net_h][net_w] fp32) on the detector's stream; no synchronisation behind the launch.  `who`: the
+// entry point named in error texts.  Two waits on the detector's own stream, neither of which blocks in steady state: the one ahead of the staging
+// copy finds the stream drained (every entry returns synchronised), and the one behind the tap tables runs only when the frame size changes.
+void letterbox_frame(vp_detect* d, const char* who, const uint8_t* bgr, int h, int w, int stride_bytes, float* dst) {
+    if (!bgr || h < 1 || w < 1 || h > 16384 || w > 16384 || stride_bytes < 3 * w) throw std::invalid_argument(std::string(who) + ": bad frame geometry");
     // preprocessAutoSpeed :78-98 -- fp32 scale, truncated new size, centred paste
     const float scale = std::min((float)d->net_w / (float)w, (float)d->net_h / (float)h);
     const int new_w = (int)((float)w * scale), new_h = (int)((float)h * scale);
-    if (new_w < 1 || new_h < 1 || new_w > d->net_w || new_h > d->net_h) throw std::invalid_argument("vp_detect_preprocess: the frame collapses under the letterbox scale");
+    if (new_w < 1 || new_h < 1 || new_w > d->net_w || new_h > d->net_h) throw std::invalid_argument(std::string(who) + ": the frame collapses under the letterbox scale");
     const size_t bytes = (size_t)(h - 1) * stride_bytes + (size_t)3 * w;   // a strided view may END with its last pixel: never read a full last stride
     if (bytes > d->frame_cap) {
       if (d->d_frame) VP_HIP_CHECK(hipFree(d->d_frame));
@@ -137,7 +148,7 @@ int vp_detect_preprocess(vp_detect* d, const uint8_t* bgr, int h, int w, int str
       VP_HIP_CHECK(hipHostMalloc(&d->h_frame, bytes));
       d->h_frame_cap = bytes;
     }
-    VP_HIP_CHECK(hipStreamSynchronize(d->stream));  // the staging buffer and the tables may still be read by the previous call
+    VP_HIP_CHECK(hipStreamSynchronize(d->stream));  // the staging buffer and the tables must not be rewritten under a copy still in flight (a drained stream: no wait)
     std::memcpy(d->h_frame, bgr, bytes);
     VP_HIP_CHECK(hipMemcpyAsync(d->d_frame, d->h_frame, bytes, hipMemcpyHostToDevice, d->stream));
     if (d->tab_w != w || d->tab_h != h) {
@@ -174,13 +185,21 @@ int vp_detect_preprocess(vp_detect* d, const uint8_t* bgr, int h, int w, int str
     p.pad_y = (d->net_h - new_h) / 2;
     p.out_h = d->net_h;
     p.out_w = d->net_w;
-    p.out = d->d_input;
+    p.out = dst;
     VP_HIP_CHECK(vp::launch_letterbox(p, d->stream));
     d->scale = scale;
     d->pad_x = p.pad_x;
     d->pad_y = p.pad_y;
     d->orig_w = w;
     d->orig_h = h;
+}
+}  // namespace
+
+extern "C" {
+
+int vp_detect_preprocess(vp_detect* d, const uint8_t* bgr, int h, int w, int stride_bytes, float* dst_host_chw) {
+  return guarded(d, [&]() -> int {
+    letterbox_frame(d, "vp_detect_preprocess", bgr, h, w, stride_bytes, d->d_input);
     if (dst_host_chw) VP_HIP_CHECK(hipMemcpyAsync(dst_host_chw, d->d_input, (size_t)3 * d->net_h * d->net_w * sizeof(float), hipMemcpyDeviceToHost, d->stream));
     VP_HIP_CHECK(hipStreamSynchronize(d->stream));
     return VP_OK;
@@ -249,6 +268,86 @@ int vp_detect_postprocess(vp_detect* d, const float* raw, int raw_on_device, int
     }
     *count = kept;
     return VP_OK;
+  });
+}
+
+int vp_detect_attach(vp_detect* d, vp_engine* net) {
+  return guarded(d, [&]() -> int {
+    if (!net) {
+      d->net = nullptr;
+      return VP_OK;
+    }
+    if (!net->impl || net->impl->kind() != 5) throw std::invalid_argument("vp_detect_attach: the engine is not a VP_AUTOSPEED engine");
+    vp::Engine& g = *net->impl;
+    if (g.gpu() != d->gpu) throw std::invalid_argument("vp_detect_attach: the engine lives on GPU " + std::to_string(g.gpu()) + ", the detector on GPU " + std::to_string(d->gpu));
+    if (d->net_h != g.net_h() || d->net_w != g.net_w())
+      throw std::invalid_argument("vp_detect_attach: the detector was created for a " + std::to_string(d->net_h) + " x " + std::to_string(d->net_w) + " input, the network takes " +
+                                  std::to_string(g.net_h()) + " x " + std::to_string(g.net_w()));
+    if (d->max_boxes < g.out_w() || d->max_attrs < g.out_c())
+      throw std::invalid_argument("vp_detect_attach: the network's output is [" + std::to_string(g.out_c()) + "][" + std::to_string(g.out_w()) + "]: create the detector with max_attrs >= " +
+                                  std::to_string(g.out_c()) + " and max_boxes >= " + std::to_string(g.out_w()));
+    if (!d->ev_in) VP_HIP_CHECK(hipEventCreateWithFlags(&d->ev_in, hipEventDisableTiming));
+    if (!d->ev_out) VP_HIP_CHECK(hipEventCreateWithFlags(&d->ev_out, hipEventDisableTiming));
+    d->net = net;
+    return VP_OK;
+  });
+}
+
+int vp_detect_infer(vp_detect* d, const uint8_t* bgr, int h, int w, int stride_bytes, float conf_thresh, float iou_thresh, vp_detection* out, int out_cap,
+                    int* count) {
+  return guarded(d, [&]() -> int {
+    if (!d->net || !d->net->impl) throw std::invalid_argument("vp_detect_infer: no network attached (vp_detect_attach with a VP_AUTOSPEED engine first)");
+    if (!count || out_cap < 0 || (out_cap > 0 && !out)) throw std::invalid_argument("vp_detect_infer: bad output arguments");
+    vp::Engine& g = *d->net->impl;
+    try {
+     try {
+      // letterbox straight into the network's input tensor: every exit of this call, the failing ones included (see the handler below), leaves both
+      // streams drained, so nothing still reads it
+      letterbox_frame(d, "vp_detect_infer", bgr, h, w, stride_bytes, g.dev_input());
+      g.note_device_tensor();
+      VP_HIP_CHECK(hipEventRecord(d->ev_in, d->stream));
+      VP_HIP_CHECK(hipStreamWaitEvent(g.stream(), d->ev_in, 0));
+      g.enqueue();         // the replayed graph (first call: the eager warm-up pass)
+      g.enqueue_status_fetch();   // the range probe's verdict behind it; the output tensor itself stays on the device
+      VP_HIP_CHECK(hipEventRecord(d->ev_out, g.stream()));
+      VP_HIP_CHECK(hipStreamWaitEvent(d->stream, d->ev_out, 0));
+      vp::DetectParams p{};
+      p.raw = static_cast<const float*>(g.dev_logits());
+      p.num_attrs = g.out_c();
+      p.num_boxes = g.out_w();
+      p.conf_thresh = conf_thresh;
+      p.iou_thresh = iou_thresh;
+      p.scale = d->scale;
+      p.pad_x = d->pad_x;
+      p.pad_y = d->pad_y;
+      p.orig_w = d->orig_w;
+      p.orig_h = d->orig_h;
+      p.boxes = d->d_boxes;
+      p.cls = d->d_cls;
+      p.out = d->d_out;
+      p.out_cap = std::min(out_cap, d->max_boxes);
+      p.count = d->d_count;
+      VP_HIP_CHECK(vp::launch_detect_decode_nms(p, d->stream));
+      // count and (at most out_cap) detections come back together: this is the one host synchronisation of a call that has anything to wait for
+      VP_HIP_CHECK(hipMemcpyAsync(d->h_count, d->d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+      if (p.out_cap > 0) VP_HIP_CHECK(hipMemcpyAsync(d->h_out, d->d_out, (size_t)p.out_cap * sizeof(vp::Detection), hipMemcpyDeviceToHost, d->stream));
+      VP_HIP_CHECK(hipStreamSynchronize(d->stream));   // behind ev_out: the engine's stream has drained too
+      g.check_status();
+      const int kept = d->h_count[0], n = std::min(kept, p.out_cap);
+      if (n > 0) std::memcpy(out, d->h_out, (size_t)n * sizeof(vp::Detection));
+      *count = kept;
+      return VP_OK;
+     } catch (...) {
+      // a failure part-way (a launch error, the range probe's verdict): work may still be queued on either stream, and the next call rewrites the
+      // engine's input tensor and the staging buffer.  Drain both before the error leaves; the statuses are not looked at, the first error is the news.
+      (void)hipStreamSynchronize(g.stream());
+      (void)hipStreamSynchronize(d->stream);
+      throw;
+     }
+    } catch (const vp::RangeError& ex) {
+      d->err = ex.what();
+      return VP_ERR_RANGE;
+    }
   });
 }
 

@@ -15,14 +15,15 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvp_hip.so")
 
-VP_SCENESEG, VP_SCENE3D, VP_DOMAINSEG, VP_EGOLANES, VP_AUTODRIVE = 0, 1, 2, 3, 4
+VP_SCENESEG, VP_SCENE3D, VP_DOMAINSEG, VP_EGOLANES, VP_AUTODRIVE, VP_AUTOSPEED = 0, 1, 2, 3, 4, 5
 VP_WEIGHTS_FP8 = 16
 VP_PLAN_LATENCY = 32  # creation flag: this engine's kernel plan targets one network on one camera, one frame at a time (vp_hip.h)
 VP_FP16, VP_FP16X3 = 0, 1
 VP_BGR8, VP_RGB8 = 0, 1
 VP_PLANES_BGR, VP_PLANES_RGB = 0, 1
 VP_DECODE_SEG_MASK, VP_DECODE_LANE_LABEL, VP_DECODE_CLASS_INDEX = 0, 1, 2
-KINDS = {"sceneseg": VP_SCENESEG, "scene3d": VP_SCENE3D, "domainseg": VP_DOMAINSEG, "egolanes": VP_EGOLANES, "autodrive": VP_AUTODRIVE}
+KINDS = {"sceneseg": VP_SCENESEG, "scene3d": VP_SCENE3D, "domainseg": VP_DOMAINSEG, "egolanes": VP_EGOLANES, "autodrive": VP_AUTODRIVE,
+         "autospeed": VP_AUTOSPEED}
 PRECISIONS = {"fp16": VP_FP16, "fp16x3": VP_FP16X3, "fp32": VP_FP16X3}
 
 # every symbol include/vp_hip.h declares: name -> (restype, argtypes)
@@ -105,6 +106,11 @@ _SIGS = {
     "vp_detect_letterbox": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vp_detect_set_letterbox": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vp_detect_postprocess": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
+    "vp_detect_attach": (C.c_int, [_P, _P]),
+    "vp_detect_infer": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
+    "vp_op_detect_head_decode": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_char_p, C.c_size_t]),
+    "vp_op_upsample2_cat": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_char_p, C.c_size_t]),
+    "vp_op_dwconv3x3": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "vp_version": (C.c_char_p, []),
     "vp_set_lane_ring": (C.c_int, [_P, C.c_int]),
     "vp_lane_ring_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int)]),
@@ -722,6 +728,55 @@ def op_upconv(x, wt, bt, w3, b3, skip=None, ws=None, bs=None, act=1, shape=-1, n
     return out
 
 
+def _op_rc(rc, err, what):
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"{what} failed ({rc}): {err.value.decode(errors='replace')}")
+
+
+def op_detect_head_decode(box, cls, h0, w0, precision="fp16x3", gpu_id=0):
+    """vp_op_detect_head_decode: box [64][sum h_l w_l] / cls [nc][sum h_l w_l] logits of the three levels one after the other (level l: (h0 >> l) x
+    (w0 >> l), stride 8 << l) -> [4 + nc][sum h_l w_l] fp32 as AutoSpeedHead.forward gives in eval mode."""
+    box, cls = _f32(box), _f32(cls)
+    nc, total = cls.shape[0], cls.shape[1]
+    sizes = [(h0 >> l) * (w0 >> l) for l in range(3)]
+    assert box.shape == (64, total) and sum(sizes) == total
+    offs = np.cumsum([0] + sizes)
+    bl = np.concatenate([box[:, offs[l]:offs[l + 1]].ravel() for l in range(3)])   # per level CHW, levels one after the other
+    cl = np.concatenate([cls[:, offs[l]:offs[l + 1]].ravel() for l in range(3)])
+    out = np.empty((4 + nc, total), np.float32)
+    err = C.create_string_buffer(512)
+    pr = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    _op_rc(load().vp_op_detect_head_decode(gpu_id, pr, _ptr(bl), _ptr(cl), nc, h0, w0, _ptr(out), err, len(err)), err, "vp_op_detect_head_decode")
+    return out
+
+
+def op_upsample2_cat(a, b, precision="fp16x3", gpu_id=0):
+    """vp_op_upsample2_cat: a [ca][h][w], b [cb][2h][2w] -> (hi, lo) float16 planes [ca + cb][2h][2w] of cat(nearest x2 of a, b) as the kernel stores them."""
+    a, b = _f32(a), _f32(b)
+    ca, h, w = a.shape
+    cb = b.shape[0]
+    hi = np.empty((ca + cb, 2 * h, 2 * w), np.float16)
+    lo = np.empty_like(hi)
+    err = C.create_string_buffer(512)
+    pr = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    _op_rc(load().vp_op_upsample2_cat(gpu_id, pr, _ptr(a), ca, _ptr(b), cb, h, w, _ptr(hi), _ptr(lo), err, len(err)), err, "vp_op_upsample2_cat")
+    return hi, lo
+
+
+def op_dwconv3x3(x, weight, bias, act=0, add=None, precision="fp16x3", gpu_id=0):
+    """vp_op_dwconv3x3: depthwise 3x3 (pad 1) + bias + activation (0 none, 2 SiLU) [+ add] -> (hi, lo) float16 planes [c][h][w]."""
+    x, weight, bias = _f32(x), _f32(weight), _f32(bias)
+    c, h, w = x.shape
+    add = None if add is None else _f32(add)
+    hi = np.empty((c, h, w), np.float16)
+    lo = np.empty_like(hi)
+    err = C.create_string_buffer(512)
+    pr = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    _op_rc(load().vp_op_dwconv3x3(gpu_id, pr, _ptr(x), c, h, w, _ptr(weight), _ptr(bias), int(act), None if add is None else _ptr(add), _ptr(hi), _ptr(lo), err,
+                                  len(err)), err, "vp_op_dwconv3x3")
+    return hi, lo
+
+
 def autosteer_angle(logits):
     """vp_autosteer_angle: AutoSteerOnnxEngine::postProcess -- first arg-max over the head's logits (61 classes) minus 30 degrees (host only)."""
     a = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1)
@@ -742,7 +797,9 @@ def resample_coeffs(in_size, out_size, mode):
 class Detector:
     """AutoSpeed detector pre / post-processing on the device (vp_detect_*): the Python twin of AutoSpeedOnnxEngine's preprocessAutoSpeed and
     postProcess (VisionPilot/middleware_recipes/common/backends/autospeed/onnxruntime_engine.cpp:71-113, :170-290).  The detector network
-    itself is the caller's: `preprocess(frame)` -> its input tensor, `postprocess(raw, conf, iou)` -> the kept detections."""
+    is either the caller's -- `preprocess(frame)` -> its input tensor, `postprocess(raw, conf, iou)` -> the kept detections -- or an
+    Engine("autospeed", ...) of this library: `attach(engine)` once, then `infer(frame, conf, iou)` per frame (vp_detect_infer: nothing leaves the device).
+    The network's input is 512 x 1024 with 10752 boxes: Detector(512, 1024, max_boxes=10752, max_attrs=4 + classes)."""
 
     def __init__(self, net_h=640, net_w=640, max_boxes=8400, max_attrs=84, gpu_id=0):
         self._lib = load()
@@ -758,6 +815,32 @@ class Detector:
         if getattr(self, "_h", None):
             self._lib.vp_detect_destroy(self._h)
             self._h = None
+        self._net = None
+
+    def attach(self, engine):
+        """vp_detect_attach: borrow an Engine("autospeed", ...) as this detector's network (None detaches); ValueError if it does not fit."""
+        rc = self._lib.vp_detect_attach(self._h, None if engine is None else engine._h)
+        if rc == -1:
+            raise ValueError(f"vp_detect_attach failed ({rc}): {self._lib.vp_detect_last_error(self._h).decode(errors='replace')}")
+        self._check(rc, "vp_detect_attach")
+        self._net = engine   # keeps the engine alive while it is attached
+
+    def infer(self, frame_bgr_u8, conf_thresh, iou_thresh, cap=None):
+        """vp_detect_infer: HxWx3 BGR uint8 frame -> ([n][6] float32 rows x1, y1, x2, y2, confidence, class_id; total kept) through the attached network."""
+        f = frame_bgr_u8
+        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.strides[2] != 1 or f.strides[1] != 3:
+            f = np.ascontiguousarray(f, dtype=np.uint8)
+        cap = 1024 if cap is None else cap
+        out = np.zeros((max(cap, 1), 6), np.float32)
+        n = C.c_int()
+        rc = self._lib.vp_detect_infer(self._h, _ptr(f), f.shape[0], f.shape[1], f.strides[0], float(conf_thresh), float(iou_thresh), _ptr(out), cap, C.byref(n))
+        if rc == -5:
+            raise VpRangeError(f"vp_detect_infer failed ({rc}): {self._lib.vp_detect_last_error(self._h).decode(errors='replace')}")
+        self._check(rc, "vp_detect_infer")
+        k = min(n.value, cap)
+        det = out[:k].copy()
+        det[:, 5] = out[:k, 5].view(np.int32).astype(np.float32)
+        return det, n.value
 
     __del__ = close
 

@@ -245,6 +245,79 @@ def autodrive_param_count():
     return sum(int(np.prod(s)) for _, s, _ in autodrive_spec())
 
 
+# ------------------------------------------------------------------------------------------------ AutoSpeed detector network
+AS_NET_H, AS_NET_W = 512, 1024        # auto_speed_network.py:9-10
+AS_NUM_CLASSES = 4
+AS_STRIDES = (8, 16, 32)
+AS_NUM_ANCHORS = sum((AS_NET_H // s) * (AS_NET_W // s) for s in AS_STRIDES)   # 10752
+
+
+def _as_c3k2(p, cin, cout, csp, r=2):
+    """common_layers.py:166-180 C3K2 with n = 1: conv1, conv2, then res_m.0 = Residual (:20-27) or C3K (:149-163)."""
+    c = cout // r
+    s = _ad_conv_bn(p + ".conv1", 2 * c, cin, 1) + _ad_conv_bn(p + ".conv2", cout, 3 * c, 1)
+    m = p + ".res_m.0"
+    if not csp:
+        return s + _ad_conv_bn(m + ".conv1", c // 2, c, 3) + _ad_conv_bn(m + ".conv2", c, c // 2, 3)
+    s += _ad_conv_bn(m + ".conv1", c // 2, c, 1) + _ad_conv_bn(m + ".conv2", c // 2, c, 1) + _ad_conv_bn(m + ".conv3", c, c, 1)
+    for i in range(2):   # Residual(c / 2, e = 1.0)
+        s += _ad_conv_bn(f"{m}.res_m.{i}.conv1", c // 2, c // 2, 3) + _ad_conv_bn(f"{m}.res_m.{i}.conv2", c // 2, c // 2, 3)
+    return s
+
+
+def autospeed_spec(num_classes=AS_NUM_CLASSES):
+    """(key, shape, init kind) of AutoSpeedNetwork().build_model('n', num_classes) in the reference ``state_dict`` order, num_batches_tracked
+    omitted (auto_speed_network.py:33-43, auto_speed_backbone.py:8-49, auto_speed_neck.py:8-16, auto_speed_head.py:24-49).  The backbone under
+    ``net.`` is AutoDrive's under ``backbone.``, key for key."""
+    s = [("net." + k[len("backbone."):], shape, kind) for k, shape, kind in autodrive_spec() if k.startswith("backbone.")]
+    s += _as_c3k2("fpn.h1", 128 + 256, 128, False) + _as_c3k2("fpn.h2", 128 + 128, 64, False) + _ad_conv_bn("fpn.h3", 64, 64, 3)
+    s += _as_c3k2("fpn.h4", 64 + 128, 128, False) + _ad_conv_bn("fpn.h5", 128, 128, 3) + _as_c3k2("fpn.h6", 128 + 256, 256, True)
+    filters = (64, 128, 256)
+    box, cls = max(64, filters[0] // 4), max(80, filters[0], num_classes)
+    s += [("head.dfl.conv.weight", (1, 16, 1, 1), "dfl")]
+    for i, x in enumerate(filters):
+        s += _ad_conv_bn(f"head.box.{i}.0", box, x, 3) + _ad_conv_bn(f"head.box.{i}.1", box, box, 3)
+        s += [(f"head.box.{i}.2.weight", (64, box, 1, 1), "conv"), (f"head.box.{i}.2.bias", (64,), "bias")]
+    for i, x in enumerate(filters):
+        s += _ad_conv_bn(f"head.cls.{i}.0", x, x, 3, groups=x) + _ad_conv_bn(f"head.cls.{i}.1", cls, x, 1)
+        s += _ad_conv_bn(f"head.cls.{i}.2", cls, cls, 3, groups=cls) + _ad_conv_bn(f"head.cls.{i}.3", cls, cls, 1)
+        s += [(f"head.cls.{i}.4.weight", (num_classes, cls, 1, 1), "conv"), (f"head.cls.{i}.4.bias", (num_classes,), "bias")]
+    return s
+
+
+AS_CLS_LOGIT_GAIN, AS_CLS_LOGIT_BIAS = 3.0, -4.0
+AS_BOX_LOGIT_GAIN = 3.0
+
+
+def make_autospeed_state_dict(seed, num_classes=AS_NUM_CLASSES):
+    """Seeded init of the detector network: the backbone as make_autodrive_state_dict tunes it (exp0 / ctx2 gains), DFL's constant 0..15.
+    The module's own initialisation (auto_speed_head.py:68-80) gives class scores of at most 0.0024 -- no detection at any useful threshold -- so
+    the last class convolution gets gain AS_CLS_LOGIT_GAIN and bias AS_CLS_LOGIT_BIAS (scores spread over (0, 1) with a few per cent of the anchors
+    above 0.25) and the last box convolution gain AS_BOX_LOGIT_GAIN (peaked bin distributions: boxes of many sizes, so NMS has work to do)."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for k, shape, kind in autospeed_spec(num_classes):
+        if kind == "dfl":
+            out[k] = np.arange(16, dtype=np.float32).reshape(shape)
+        elif kind == "conv1d":   # net.pN.1.exp0.weight of the backbone's CTX blocks (_ad_ctx): gain 0.5, as make_autodrive_state_dict
+            out[k] = (rng.standard_normal(shape, dtype=np.float32) * np.float32(0.5 * np.sqrt(2.0 / shape[1]))).astype(np.float32)
+        else:
+            out[k] = _init(rng, shape, kind)
+        if k.endswith("ctx2.weight"):
+            out[k] = out[k] * np.float32(0.5)
+        if k.startswith("head.cls.") and k.endswith(".4.weight"):
+            out[k] = out[k] * np.float32(AS_CLS_LOGIT_GAIN)
+        if k.startswith("head.cls.") and k.endswith(".4.bias"):
+            out[k] = out[k] + np.float32(AS_CLS_LOGIT_BIAS)
+        if k.startswith("head.box.") and k.endswith(".2.weight"):
+            out[k] = out[k] * np.float32(AS_BOX_LOGIT_GAIN)
+    return out
+
+
+def autospeed_param_count(num_classes=AS_NUM_CLASSES):
+    return sum(int(np.prod(s)) for k, s, _ in autospeed_spec(num_classes) if not k.endswith(("running_mean", "running_var")))
+
+
 # ------------------------------------------------------------------------------------------------ frames
 def synthetic_frame(h, w, seed, smooth=True):
     """Seeded u8 HxWx3 frame.  ``smooth`` mixes low-frequency sinusoids with noise so argmax regions are

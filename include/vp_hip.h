@@ -54,7 +54,14 @@ enum vp_status { VP_OK = 0, VP_ERR_ARG = -1, VP_ERR_WEIGHTS = -2, VP_ERR_HIP = -
 /* VP_AUTODRIVE (BASELINE configs[4]): Models/model_components/autodrive/autodrive_network.py:32-36 --
  * shared backbone on the previous and the current frame (network input 1x3x512x1024, RGB planes), head -> three scalars
  * returned through vp_logits as shape {1,3,1,1} = (d_norm, curvature, flag_logit); no mask. */
-enum vp_model_kind { VP_SCENESEG = 0, VP_SCENE3D = 1, VP_DOMAINSEG = 2, VP_EGOLANES = 3, VP_AUTODRIVE = 4 };
+/* VP_AUTOSPEED: the detector network, Models/model_components/auto_speed/auto_speed_network.py:33-48, version 'n' (the number of
+ * classes is read from the weights; 4 in the reference's checkpoints).  Input: 1x3x512x1024 fp32 planes R, G, B in [0, 1], no mean / std -- what
+ * vp_detect_preprocess leaves on the device; the engine has NO frame preprocess of its own: its entries are vp_infer_tensor (host tensor) and
+ * vp_detect_infer (below); vp_infer / vp_upload_frame return VP_ERR_STATE.  Output through vp_logits: shape {1, 4 + nc, 1, 10752} = the head's
+ * eval-mode tensor [4 + nc][10752] (cx, cy, w, h in input pixels, then sigmoid class scores; levels of stride 8, 16, 32 one after the other), the
+ * tensor vp_detect_postprocess reads; no mask.  VP_FP16 / VP_FP16X3 (| VP_PLAN_LATENCY); VP_WEIGHTS_FP8, vp_create_shared* and
+ * vp_create_batched* are refused with VP_ERR_ARG. */
+enum vp_model_kind { VP_SCENESEG = 0, VP_SCENE3D = 1, VP_DOMAINSEG = 2, VP_EGOLANES = 3, VP_AUTODRIVE = 4, VP_AUTOSPEED = 5 };
 
 /* VP_FP16  : fp16 tensors, fp16 MFMA, fp32 accumulate (the reference's "fp16" configuration).
  * VP_FP16X3: fp32-class accuracy on the fp16 matrix pipe: every tensor is a (hi, lo) fp16 pair and every
@@ -323,8 +330,11 @@ int vp_tensor_read(vp_engine* e, int i, float* dst_chw);                       /
 /* ---- AutoSpeed detector: letterbox preprocess and decode + NMS on the device ------------------------------------
  * Replaces AutoSpeedOnnxEngine::preprocessAutoSpeed (VisionPilot/middleware_recipes/common/backends/autospeed/
  * onnxruntime_engine.cpp:71-113) and ::postProcess / ::computeIoU / ::applyNMS (:170-290); the TensorRT engine (tensorrt_engine.cpp)
- * holds the same two stages.  The detector network is NOT part of this library: the host runs it between the two calls and hands its
- * output tensor [num_attrs][num_boxes] (cx, cy, w, h in letterbox pixels, then the class scores) to vp_detect_postprocess.
+ * holds the same two stages.  Two forms:
+ *   one call : a VP_AUTOSPEED engine (the detector network on the device, see vp_model_kind) attached with vp_detect_attach, then
+ *              vp_detect_infer per frame: letterbox -> network (the engine's replayed graph) -> decode + NMS, no tensor leaves the device;
+ *   two calls: the host runs a detector of its own between vp_detect_preprocess and vp_detect_postprocess and hands its output tensor
+ *              [num_attrs][num_boxes] (cx, cy, w, h in letterbox pixels, then the class scores) to the latter.
  * vp_detection is the reference's `Detection` (autospeed/detection.hpp:8-12), field for field.  A handle owns its stream and buffers and is
  * not thread-safe (one handle per calling thread, as the reference has one engine object per thread); every call returns synchronised.
  * With raw_on_device the caller's producer must have finished writing the tensor (the call does not wait on foreign streams). */
@@ -351,6 +361,31 @@ int vp_detect_set_letterbox(vp_detect* d, float scale, int pad_x, int pad_y, int
  * kept; min(*count, out_cap) of them are written, in the reference's output order. */
 int vp_detect_postprocess(vp_detect* d, const float* raw, int raw_on_device, int num_attrs, int num_boxes, float conf_thresh, float iou_thresh,
                           vp_detection* out, int out_cap, int* count);
+/* One-call form.  vp_detect_attach: `net` is BORROWED (it must outlive the attachment; NULL detaches).  VP_ERR_ARG unless it is a VP_AUTOSPEED
+ * engine on the detector's GPU, the detector was created with net_h x net_w = 512 x 1024, max_boxes >= 10752 and max_attrs >= 4 + nc.
+ * vp_detect_infer: frame -> detections, arguments as vp_detect_preprocess + vp_detect_postprocess.  The letterbox kernel writes the engine's input
+ * tensor, the engine's graph runs on the engine's stream, decode + NMS read the engine's output tensor in place; the two streams are ordered by
+ * events and the call waits for the device ONCE, at its end (the wait ahead of the frame's staging copy finds the detector's stream drained, since every
+ * call -- a failing one included -- returns with both streams drained; a frame of a new size uploads its tap tables and waits for them, once per size;
+ * a handle's first call also runs the engine's eager warm-up pass).  A
+ * non-finite network output (vp_set_finite_check on the engine, default on) returns VP_ERR_RANGE.  The raw tensor of the frame stays readable
+ * through vp_logits(net). */
+int vp_detect_attach(vp_detect* d, vp_engine* net);
+int vp_detect_infer(vp_detect* d, const uint8_t* bgr, int h, int w, int stride_bytes, float conf_thresh, float iou_thresh, vp_detection* out,
+                    int out_cap, int* count);
+
+/* ---- single-operator entries of the detector network's kernels (unit tests; not used by callers) -----------
+ * vp_op_detect_head_decode: box [3 levels one after the other][64][h_l][w_l] and cls [..][nc][h_l][w_l] fp32 CHW logits, level l of size
+ *   (h0 >> l) x (w0 >> l), stride 8 << l -> out [4 + nc][sum h_l w_l] (AutoSpeedHead.forward in eval mode behind the convolutions).
+ * vp_op_upsample2_cat: a [ca][h][w], b [cb][2h][2w] -> out [ca + cb][2h][2w] = cat(nearest x2 of a, b); the (hi, lo) planes the kernel moves are
+ *   returned as they are: out_hi / out_lo are uint16 fp16 bit patterns [ca + cb][2h][2w] (out_lo all zero for VP_FP16).
+ * vp_op_dwconv3x3: depthwise 3x3 (pad 1) + bias + activation (ActFn code: 0 none, 2 SiLU) [+ add]: in [c][h][w], weight [c][3][3], add NULL or
+ *   [c][h][w] -> out_hi / out_lo as above. */
+int vp_op_detect_head_decode(int gpu_id, int precision, const float* box, const float* cls, int nc, int h0, int w0, float* out, char* err, size_t err_len);
+int vp_op_upsample2_cat(int gpu_id, int precision, const float* a, int ca, const float* b, int cb, int h, int w, uint16_t* out_hi, uint16_t* out_lo,
+                        char* err, size_t err_len);
+int vp_op_dwconv3x3(int gpu_id, int precision, const float* in, int c, int h, int w, const float* weight, const float* bias, int act, const float* add,
+                    uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len);
 
 /* ---- single-operator entry (unit parity tests of the MFMA conv kernel; not used by callers) -------------- */
 /* mode 0: Conv2d k=ks stride 1 pad ks/2, weight [Cout][Cin][ks][ks]; mode 1: ConvTranspose2d k2 s2, weight

@@ -6,7 +6,11 @@ regression that silently picks another kernel fails the CPU suite.  Also writes 
 engines created with VP_PLAN_LATENCY (the drop-in adapters' default), one entry per launch [name, kernel tag, launch] -- the launch string
 (vp_layer_launch: "nsplit=4", "groups=32", "") is recorded there because the latency plan's map-kernel K split is the engine's own rule and
 tests/test_gpu_decoder_kernels.py reproduces it (test_latency_plan_is_the_committed_one compares).  Re-run after a DELIBERATE change of a
-rule and review the diff."""
+rule and review the diff.
+
+`dump_kernel_plan.py autospeed` writes tests/golden/kernel_plan_autospeed.json instead: the detector network (VP_AUTOSPEED) in both precisions, default
+and latency plan, and AutoDrive's plan beside it -- [name, tag, launch] per launch; the two share their backbone launches (Engine::build_ad_backbone),
+which tests/test_autospeed_net_emulated.py checks entry by entry.  Without an argument only the two scene-network files are written."""
 import ctypes as ct
 import json
 import os
@@ -35,6 +39,21 @@ def kernel_plan(lib, latency=False):
     return out
 
 
+def autospeed_plan(lib):
+    """{"autospeed/<precision>[/latency]": [[name, tag, launch], ...], "autodrive/<precision>": [...]}"""
+    from autoware_vision_pilot_amd import synthetic, weights as vw
+
+    out = {}
+    for kind, blob in (("autospeed", vw.pack_state_dict(synthetic.make_autospeed_state_dict(0))), ("autodrive", vw.pack_state_dict(synthetic.make_autodrive_state_dict(0)))):
+        for prec in ("fp16x3", "fp16"):
+            for latency in ((False, True) if kind == "autospeed" else (False,)):
+                eng = lib.Engine(kind, blob, precision=prec, plan_latency=latency)
+                rows = zip(eng.layers(), eng.layer_kernels(), eng.layer_launches())
+                out[f"{kind}/{prec}" + ("/latency" if latency else "")] = [[n, k, l] for (n, _, _), k, l in rows]
+                eng.close()
+    return out
+
+
 if __name__ == "__main__":
     import build as eb
 
@@ -45,6 +64,12 @@ if __name__ == "__main__":
         fn = getattr(so, name)
         fn.restype, fn.argtypes = res, args
     lib._lib = so
+    if sys.argv[1:] == ["autospeed"]:
+        path = os.path.join(ROOT, "tests", "golden", "kernel_plan_autospeed.json")
+        with open(path, "w") as f:
+            json.dump(autospeed_plan(lib), f, indent=0)
+        print("written", path)
+        sys.exit(0)
     for fname, latency in (("kernel_plan.json", False), ("kernel_plan_latency.json", True)):
         path = os.path.join(ROOT, "tests", "golden", fname)
         with open(path, "w") as f:
