@@ -168,6 +168,9 @@ Engine::Engine(int kind, const WeightBlob* blob, int precision, int gpu_id, Engi
   if (kind == 5 && ((precision & 16) != 0 || base || frames > 1))
     throw std::invalid_argument("VP_AUTOSPEED: VP_WEIGHTS_FP8, shared-prefix and batched creation are not supported for the detector network (VP_FP16 / VP_FP16X3, optionally | VP_PLAN_LATENCY)");
   if (base && base->kind_ == 5) throw std::invalid_argument("VP_AUTOSPEED engines cannot be the base of a shared-prefix engine");
+  if (kind == 6 && ((precision & 16) != 0 || base || frames > 1))
+    throw std::invalid_argument("VP_AUTOSTEER: VP_WEIGHTS_FP8, shared-prefix and batched creation are not supported for the lane-perception network (VP_FP16 / VP_FP16X3, optionally | VP_PLAN_LATENCY)");
+  if (base && base->kind_ == 6) throw std::invalid_argument("VP_AUTOSTEER engines cannot be the base of a shared-prefix engine");
   if ((precision & 15) > 1 || (precision & ~(1 | 16 | 32)) != 0) throw std::invalid_argument("precision must be VP_FP16 or VP_FP16X3 (optionally | VP_WEIGHTS_FP8 | VP_PLAN_LATENCY)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -918,6 +921,10 @@ void Engine::build_model(const WeightBlob& blob) {
       {"DomainSegUpstream.pretrainedBackBone.encoder.", "DomainSegUpstream.pretrainedContext.", "DomainSegUpstream.pretrainedNeck.",
        "DomainSegHead."},
       {"BEVBackbone.encoder.", "AutoSteerContext.", "EgopathNeck.", "EgoLanesHead."}};
+  if (kind_ == 6) {
+    build_autosteer(blob);
+    return;
+  }
   if (kind_ == 5) {
     build_autospeed(blob);
     return;
@@ -1152,6 +1159,7 @@ Engine::AdFeatures Engine::build_ad_backbone(const WeightBlob& blob, const std::
     Act* g = add_conv(cp + ".ctx1", c2, T(cp + ".ctx1.weight").data, T(cp + ".ctx1.bias").data, C, 3, o1);
     // ctx2: conv3x3 C -> Cout, no activation (:225)
     x = add_conv(cp + ".ctx2", g, T(cp + ".ctx2.weight").data, T(cp + ".ctx2.bias").data, T(cp + ".ctx2.weight").shape[0], 3, ConvOpts{});
+    if (si == 0) out.p2 = x;
     if (si == 1) out.p3 = x;
     if (si == 2) out.p4 = x;
   }
@@ -1360,6 +1368,61 @@ void Engine::build_autodrive(const WeightBlob& blob) {
   decode_mode_ = 0;
 }
 
+// ---- blocks of the AutoSpeed / AutoSteer necks (the comment in front of build_autospeed says where a concatenation costs no launch)
+Act* Engine::neck_conv_bn(const WeightBlob& blob, const std::string& name, const Act* in, int ks, int stride, const Act* res, Act* dst) {
+  Folded f = fold_conv_norm(blob, name);
+  ConvOpts o;
+  o.act = ACT_SILU;
+  o.stride = stride;
+  if (res) {
+    o.res_mode = RES_ADD;   // applied behind the activation (conv_epilogue.hpp): x + SiLU(conv(..))
+    o.res = res;
+  }
+  return add_conv(name, in, f.w, f.b, f.cout, ks, o, dst);
+}
+void Engine::neck_copy_slice(const std::string& name, const Act* src, int src_off, const Act* dst, int dst_off, int nch) {
+  const ActView sv = src->view(), dv = dst->view();
+  push_op(name, "chan_copy", [=](hipStream_t st) { return launch_chan_copy(sv, src_off, dv, dst_off, nch, st); }, 0,
+          2.0 * (split() ? 4.0 : 2.0) * nch * src->H * src->W);
+}
+Act* Engine::neck_c3k2(const WeightBlob& blob, const std::string& p, const Act* in, bool csp, Act* dst) {
+  // Residual (common_layers.py:20-27); res: where the block's input is read back for the sum (same row pitch as dst)
+  auto residual = [&](const std::string& q, const Act* x, const Act* res, Act* d) -> Act* {
+    return neck_conv_bn(blob, q + ".conv2", neck_conv_bn(blob, q + ".conv1", x, 3, 1), 3, 1, res, d);
+  };
+  const int c = fold_conv_norm(blob, p + ".conv1").cout / 2;
+  if (c % 32 != 0) throw std::runtime_error(p + ": slice width must be a multiple of 32");
+  Act* cat = new_act(p + ".cat", 3 * c, in->H, in->W);
+  neck_conv_bn(blob, p + ".conv1", in, 1, 1, nullptr, alias_slice(p + ".conv1", cat, 0, 2 * c));
+  Act* y1 = new_act(p + ".y1", c, in->H, in->W);
+  neck_copy_slice(p + ".split", cat, c, y1, 0, c);
+  Act* y2 = alias_slice(p + ".res_m.0", cat, 2 * c, c);
+  const std::string m = p + ".res_m.0";
+  if (!csp) {
+    residual(m, y1, alias_slice(p + ".y1@cat", cat, c, c), y2);
+  } else {   // C3K (common_layers.py:149-163): conv3(cat(res_m(conv1(x)), conv2(x)))
+    const int h = c / 2;
+    if (h % 32 != 0) throw std::runtime_error(m + ": slice width must be a multiple of 32");
+    Act* u = new_act(m + ".cat", c, in->H, in->W);
+    Act* r = neck_conv_bn(blob, m + ".conv1", y1, 1, 1);
+    neck_conv_bn(blob, m + ".conv2", y1, 1, 1, nullptr, alias_slice(m + ".conv2", u, h, h));
+    for (int i = 0; i < 2; ++i) r = residual(m + ".res_m." + std::to_string(i), r, r, nullptr);
+    neck_copy_slice(m + ".cat0", r, 0, u, 0, h);
+    neck_conv_bn(blob, m + ".conv3", u, 1, 1, nullptr, y2);
+  }
+  return neck_conv_bn(blob, p + ".conv2", cat, 1, 1, nullptr, dst);
+}
+void Engine::neck_up_cat(const std::string& name, const Act* a, const Act* b, Act* out) {
+  Upsample2CatParams q{};
+  q.a = a->view();
+  q.b = b->view();
+  q.out = out->view();
+  q.a_nch = a->Creal;
+  q.b_nch = b->Creal;
+  if (!upsample2_cat_ok(q)) throw std::runtime_error(name + ": unsupported shape for upsample2_cat");
+  push_op(name, "upsample2_cat", [q](hipStream_t st) { return launch_upsample2_cat(q, st); }, 0, 2.0 * (split() ? 4.0 : 2.0) * out->elems());
+}
+
 // ------------------------------------------------------------------------------------------------ AutoSpeed
 // auto_speed_network.py:33-48 ('n' variant, 512 x 1024 input: :9-10 and the CTX map sizes): net (the backbone above under "net.") -> fpn
 // (auto_speed_neck.py:18-24) -> head (auto_speed_head.py:39-66).  Input: fp32 planes R, G, B in [0, 1] in d_input_ -- what the letterbox kernel of
@@ -1389,57 +1452,10 @@ void Engine::build_autospeed(const WeightBlob& blob) {
   input_is_tensor_ = true;
 
   auto conv_bn = [&](const std::string& name, const Act* in, int ks, int stride, const Act* res = nullptr, Act* dst = nullptr) -> Act* {
-    Folded f = fold_conv_norm(blob, name);
-    ConvOpts o;
-    o.act = ACT_SILU;
-    o.stride = stride;
-    if (res) {
-      o.res_mode = RES_ADD;   // applied behind the activation (conv_epilogue.hpp): x + SiLU(conv(..))
-      o.res = res;
-    }
-    return add_conv(name, in, f.w, f.b, f.cout, ks, o, dst);
+    return neck_conv_bn(blob, name, in, ks, stride, res, dst);
   };
-  auto copy_slice = [&](const std::string& name, const Act* src, int src_off, const Act* dst, int dst_off, int nch) {
-    const ActView sv = src->view(), dv = dst->view();
-    push_op(name, "chan_copy", [=](hipStream_t st) { return launch_chan_copy(sv, src_off, dv, dst_off, nch, st); }, 0, 2.0 * esz * nch * src->H * src->W);
-  };
-  // Residual (common_layers.py:20-27); res: where the block's input is read back for the sum (same row pitch as dst)
-  auto residual = [&](const std::string& p, const Act* x, const Act* res, Act* dst) -> Act* {
-    return conv_bn(p + ".conv2", conv_bn(p + ".conv1", x, 3, 1), 3, 1, res, dst);
-  };
-  auto c3k2 = [&](const std::string& p, const Act* in, bool csp, Act* dst) -> Act* {
-    const int c = fold_conv_norm(blob, p + ".conv1").cout / 2;
-    if (c % 32 != 0) throw std::runtime_error(p + ": slice width must be a multiple of 32");
-    Act* cat = new_act(p + ".cat", 3 * c, in->H, in->W);
-    conv_bn(p + ".conv1", in, 1, 1, nullptr, alias_slice(p + ".conv1", cat, 0, 2 * c));
-    Act* y1 = new_act(p + ".y1", c, in->H, in->W);
-    copy_slice(p + ".split", cat, c, y1, 0, c);
-    Act* y2 = alias_slice(p + ".res_m.0", cat, 2 * c, c);
-    const std::string m = p + ".res_m.0";
-    if (!csp) {
-      residual(m, y1, alias_slice(p + ".y1@cat", cat, c, c), y2);
-    } else {   // C3K (common_layers.py:149-163): conv3(cat(res_m(conv1(x)), conv2(x)))
-      const int h = c / 2;
-      if (h % 32 != 0) throw std::runtime_error(m + ": slice width must be a multiple of 32");
-      Act* u = new_act(m + ".cat", c, in->H, in->W);
-      Act* r = conv_bn(m + ".conv1", y1, 1, 1);
-      conv_bn(m + ".conv2", y1, 1, 1, nullptr, alias_slice(m + ".conv2", u, h, h));
-      for (int i = 0; i < 2; ++i) r = residual(m + ".res_m." + std::to_string(i), r, r, nullptr);
-      copy_slice(m + ".cat0", r, 0, u, 0, h);
-      conv_bn(m + ".conv3", u, 1, 1, nullptr, y2);
-    }
-    return conv_bn(p + ".conv2", cat, 1, 1, nullptr, dst);
-  };
-  auto up_cat = [&](const std::string& name, const Act* a, const Act* b, Act* out) {
-    Upsample2CatParams q{};
-    q.a = a->view();
-    q.b = b->view();
-    q.out = out->view();
-    q.a_nch = a->Creal;
-    q.b_nch = b->Creal;
-    if (!upsample2_cat_ok(q)) throw std::runtime_error(name + ": unsupported shape for upsample2_cat");
-    push_op(name, "upsample2_cat", [q](hipStream_t st) { return launch_upsample2_cat(q, st); }, 0, 2.0 * esz * out->elems());
-  };
+  auto c3k2 = [&](const std::string& p, const Act* in, bool csp, Act* dst) -> Act* { return neck_c3k2(blob, p, in, csp, dst); };
+  auto up_cat = [&](const std::string& name, const Act* a, const Act* b, Act* out) { neck_up_cat(name, a, b, out); };
 
   // ---- backbone: P5 goes straight into the neck's last concatenation cat([h5(p4), p5]) (auto_speed_neck.py:23)
   const int c_h3 = T("fpn.h3.conv.weight").shape[0], c_h5 = T("fpn.h5.conv.weight").shape[0];
@@ -1513,6 +1529,131 @@ void Engine::build_autospeed(const WeightBlob& blob) {
   decode_mode_ = 0;
 }
 
+// ------------------------------------------------------------------------------------------------ AutoSteer (2.0 perception network)
+// auto_steer_network.py:39-43 ('n' variant, 512 x 1024 input: :9-10): net (the shared backbone under "net.", auto_steer_backbone.py:8-49, which hands
+// P2 on as well) -> fpn (auto_steer_neck.py:8-19: the top-down half of the detector's neck, h1 and h2) -> head (auto_steer_percept_head.py:29-68).
+// Input: the 512 x 1024 frame as R, G, B planes of u8 / 255, no mean / std, no resize (auto_steer_infer.py:19-23,41-45): the preprocess kernel at
+// identity geometry (taps (x, x, 2048, 0): the integer bilinear returns the byte) with mean 0 and std 1 ((t - 0) / 1 == t in IEEE arithmetic).
+// Output: fp32 {1, 2, 64, 1}: plane 0 = xp (ego-lane column / W per feature row), plane 1 = h_vector.
+// Head, three launches: v2 and v1 (Conv2d (2,1) stride (2,1) + bias + SiLU: rowpair_conv) store straight into the two halves of the 64-channel
+// `features` tensor -- v2 replicated 2 x 2 on store, which IS cat([up(v2), v1]) -- and lane_rows_head does everything behind it, one workgroup per row.
+void Engine::build_autosteer(const WeightBlob& blob) {
+  auto T = [&](const std::string& k) -> const HostTensor& { return blob.get(k); };
+  auto want_shape = [&](const std::string& key, std::initializer_list<int> shape) -> const HostTensor& {
+    const HostTensor& t = T(key);
+    if (t.shape != std::vector<int>(shape)) {
+      std::string s;
+      for (int d : shape) s += (s.empty() ? "" : ", ") + std::to_string(d);
+      throw std::runtime_error("weight blob: " + key + ": expected shape [" + s + "] (the 'n' AutoSteer head, auto_steer_percept_head.py:29-43)");
+    }
+    return t;
+  };
+  const HostTensor& v1w = want_shape("head.v1.weight", {32, 64, 2, 1});
+  const HostTensor& v2w = want_shape("head.v2.weight", {32, 64, 2, 1});
+  want_shape("head.v1.bias", {32});
+  want_shape("head.v2.bias", {32});
+  want_shape("head.c1.conv.weight", {1, 64, 3, 3});
+  want_shape("head.c2.conv.weight", {1, 64, 3, 3});
+  const HostTensor& h1w = want_shape("head.h1.weight", {1, 1, 1, 16});
+  const HostTensor& h2w = want_shape("head.h2.weight", {1, 1, 1, 16});
+  want_shape("head.h1.bias", {1});
+  want_shape("head.h2.bias", {1});
+
+  d_input_ = static_cast<float*>(dalloc((size_t)3 * net_h() * net_w() * sizeof(float)));
+  plane_order_ = 1;   // RGB planes (auto_steer_infer.py:20)
+  push_op("preprocess", "preprocess", [this](hipStream_t st) {
+    PreprocessParams pp{};
+    pp.frame = d_frame_;
+    pp.stride = frame_stride_;
+    pp.xtab = d_xtab_;
+    pp.ytab = d_ytab_;
+    pp.out_h = net_h();
+    pp.out_w = net_w();
+    for (int c = 0; c < 3; ++c) {
+      const int colour = plane_order_ == 1 ? c : 2 - c;
+      pp.src_c[c] = pixel_format_ == 1 ? colour : 2 - colour;
+      pp.mean[c] = 0.0f;
+      pp.stdv[c] = 1.0f;
+    }
+    pp.out = d_input_;
+    pp.norm_form = norm_form_;
+    return launch_preprocess(pp, st);
+  });
+  first_net_op_ = 1;
+
+  const AdFeatures f = build_ad_backbone(blob, "net.", nullptr);
+  if (!f.p2 || !f.p3 || !f.p4 || !f.p5 || f.p4->H != 2 * f.p5->H || f.p3->H != 2 * f.p4->H || f.p2->H != 2 * f.p3->H)
+    throw std::runtime_error("AutoSteer backbone: unexpected pyramid");
+  // ---- neck (auto_steer_neck.py:15-19)
+  Act* cat1 = new_act("fpn.cat1", f.p5->Creal + f.p4->Creal, f.p4->H, f.p4->W);
+  neck_up_cat("fpn.up5+p4", f.p5, f.p4, cat1);
+  Act* p4a = neck_c3k2(blob, "fpn.h1", cat1, false, nullptr);
+  Act* cat2 = new_act("fpn.cat2", p4a->Creal + f.p3->Creal, f.p3->H, f.p3->W);
+  neck_up_cat("fpn.up4+p3", p4a, f.p3, cat2);
+  Act* p3a = neck_c3k2(blob, "fpn.h2", cat2, false, nullptr);
+  if (f.p2->Creal != 64) throw std::runtime_error("weight blob: net.p2.1.ctx2.weight: the head's P2 tap has 64 channels in the 'n' network");
+  if (p3a->Creal != 64) throw std::runtime_error("weight blob: fpn.h2.conv2.conv.weight: the head's P3 tap has 64 channels in the 'n' network");
+
+  // ---- head
+  const double esz = split() ? 4.0 : 2.0;
+  Act* feat = new_act("features", 64, f.p2->H / 2, f.p2->W);
+  if (feat->W != 256 || feat->H != p3a->H || feat->W != 2 * p3a->W) throw std::runtime_error("AutoSteer head: the feature map is 64 x 256 (W = 256) at 512 x 1024");
+  auto rowpair = [&](const std::string& name, const HostTensor& w, const Act* in, int ch_off, int replicate) {
+    const int cin = w.shape[1], cout = w.shape[0];
+    std::vector<float> wk((size_t)2 * cin * cout);   // [ky * cin + ci][co]
+    for (int co = 0; co < cout; ++co)
+      for (int ci = 0; ci < cin; ++ci)
+        for (int ky = 0; ky < 2; ++ky) wk[((size_t)ky * cin + ci) * cout + co] = w.data[((size_t)co * cin + ci) * 2 + ky];
+    RowpairConvParams q{};
+    q.in = in->view();
+    q.cin = cin;
+    q.w = dupload(wk);
+    q.b = dupload(T(name + ".bias").data);
+    q.out = alias_slice(name, feat, ch_off, cout)->view();
+    q.replicate = replicate;
+    wbytes_[2] += 4 * wk.size();
+    if (!rowpair_conv_ok(q)) throw std::runtime_error(name + ": unsupported shape for rowpair_conv");
+    push_op(name, replicate ? "rowpair_conv<up2>" : "rowpair_conv", [q](hipStream_t st) { return launch_rowpair_conv(q, st); },
+            2.0 * 2 * cin * cout * (in->H / 2) * in->W, esz * in->elems() + esz * cout * feat->H * feat->W);
+  };
+  rowpair("head.v2", v2w, p3a, 0, 1);          // features[:, 0:32] = up(SiLU(v2(p3')))
+  rowpair("head.v1", v1w, f.p2, 32, 0);        // features[:, 32:64] = SiLU(v1(p2))
+  out_c_ = 2;
+  out_h_ = feat->H;
+  out_w_ = 1;   // vp_logits / vp_output_shape: {1, 2, 64, 1}
+  d_logits_ = static_cast<float*>(dalloc((size_t)out_c_ * out_h_ * sizeof(float)));
+  d_mask_ = static_cast<uint8_t*>(dalloc((size_t)out_h_));   // no class map: stays zero
+  {
+    const Folded c1 = fold_conv_norm(blob, "head.c1"), c2 = fold_conv_norm(blob, "head.c2");
+    std::vector<float> wk((size_t)9 * 64 * 2);   // [tap][ci][output]
+    for (int t = 0; t < 9; ++t)
+      for (int ci = 0; ci < 64; ++ci) {
+        wk[((size_t)t * 64 + ci) * 2 + 0] = c1.w[(size_t)ci * 9 + t];
+        wk[((size_t)t * 64 + ci) * 2 + 1] = c2.w[(size_t)ci * 9 + t];
+      }
+    std::vector<float> hk(36);   // h1 weights, h2 weights, then c1, c2, h1, h2 biases
+    for (int i = 0; i < 16; ++i) {
+      hk[i] = h1w.data[i];
+      hk[16 + i] = h2w.data[i];
+    }
+    hk[32] = c1.b[0];
+    hk[33] = c2.b[0];
+    hk[34] = T("head.h1.bias").data[0];
+    hk[35] = T("head.h2.bias").data[0];
+    LaneRowsHeadParams q{};
+    q.features = feat->view();
+    q.cin = 64;
+    q.w = dupload(wk);
+    q.hw = dupload(hk);
+    q.out = d_logits_;
+    wbytes_[2] += 4 * (wk.size() + hk.size());
+    if (!lane_rows_head_ok(q)) throw std::runtime_error("head.c1+c2: unsupported shape for lane_rows_head");
+    push_op("head.lanes+height", "lane_rows_head", [q](hipStream_t st) { return launch_lane_rows_head(q, st); }, 2.0 * 2 * 9 * 64 * feat->H * feat->W,
+            3.0 * esz * feat->elems());
+  }
+  decode_mode_ = 0;
+}
+
 // Runs preprocess + backbone on the resident frame and parks its P5 features in the "current" slot, WITHOUT the head:
 // the next enqueue() shifts them to "previous".  Eager launches (twice per stream at most: vp_infer_pair / first frame).
 void Engine::prime_previous() {
@@ -1531,7 +1672,7 @@ void Engine::finish_plan() {
   if (d_logits_ && !h_logits_) {
     VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_logits_), (size_t)out_c_ * out_h_ * out_w_ * sizeof(float), hipHostMallocDefault));
     VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_mask_), (size_t)out_h_ * out_w_, hipHostMallocDefault));
-    if (kind_ != 4 && kind_ != 5 && !decode_fused_) {  // AutoDrive returns three scalars, the detector boxes: no mask to decode; else the logits conv already decoded
+    if (kind_ != 4 && kind_ != 5 && kind_ != 6 && !decode_fused_) {  // AutoDrive returns three scalars, the detector boxes, AutoSteer lane rows: no mask to decode; else the logits conv already decoded
       Op op;
       op.name = "decode";
       op.bytes = 4.0 * out_c_ * out_h_ * out_w_ + out_h_ * out_w_;

@@ -127,8 +127,8 @@ class Engine {
   // networks), 1 / 2 = Pillow's antialiased BILINEAR / BICUBIC (the Python scripts' Image.resize; 1 is AutoDrive's default)
   void set_resize_mode(int mode);
   int resize_mode() const { return resize_mode_; }
-  int net_h() const { return kind_ == 4 || kind_ == 5 ? 512 : 320; }   // AutoDrive: autodrive_network.py:8-9, AutoSpeed: auto_speed_network.py:9-10
-  int net_w() const { return kind_ == 4 || kind_ == 5 ? 1024 : 640; }
+  int net_h() const { return kind_ >= 4 && kind_ <= 6 ? 512 : 320; }   // AutoDrive: autodrive_network.py:8-9, AutoSpeed: auto_speed_network.py:9-10, AutoSteer: auto_steer_network.py:9-10
+  int net_w() const { return kind_ >= 4 && kind_ <= 6 ? 1024 : 640; }
   int kind() const { return kind_; }
   // AutoSpeed (kind 5): the network input on the device ([3][512][1024] fp32 planes R, G, B in [0, 1]) for a producer on the same GPU (vp_detect_infer's
   // letterbox kernel writes it), and the note that it now holds this frame's tensor
@@ -270,8 +270,10 @@ class Engine {
   void build_model(const WeightBlob& blob);
   void build_autodrive(const WeightBlob& blob);
   void build_autospeed(const WeightBlob& blob);
-  // the backbone AutoDrive and AutoSpeed share (engine.cpp): P3 / P4 / P5 and the index of the launch that stores P5
+  void build_autosteer(const WeightBlob& blob);
+  // the backbone AutoDrive, AutoSpeed and AutoSteer share (engine.cpp): P2 / P3 / P4 / P5 and the index of the launch that stores P5
   struct AdFeatures {
+    Act* p2 = nullptr;
     Act* p3 = nullptr;
     Act* p4 = nullptr;
     Act* p5 = nullptr;
@@ -280,6 +282,12 @@ class Engine {
   AdFeatures build_ad_backbone(const WeightBlob& blob, const std::string& prefix, const std::function<Act*(int, int, int)>& p5_dest);
   void push_op(const std::string& name, const char* kernel, std::function<hipError_t(hipStream_t)> fn, double flops = 0, double bytes = 0);
   Act* alias_slice(const std::string& name, Act* whole, int ch_off, int nch);  // view of channels [ch_off, ch_off + nch) with the tensor's row pitch (no allocation)
+  // blocks of the AutoSpeed / AutoSteer necks (engine.cpp, in front of build_autospeed): Conv + BN + SiLU [+ residual behind the activation], a channel
+  // slice copy, C3K2 (common_layers.py:166-180) and cat([up(a), b]) as one launch
+  Act* neck_conv_bn(const WeightBlob& blob, const std::string& name, const Act* in, int ks, int stride, const Act* res = nullptr, Act* dst = nullptr);
+  void neck_copy_slice(const std::string& name, const Act* src, int src_off, const Act* dst, int dst_off, int nch);
+  Act* neck_c3k2(const WeightBlob& blob, const std::string& p, const Act* in, bool csp, Act* dst);
+  void neck_up_cat(const std::string& name, const Act* a, const Act* b, Act* out);
   std::vector<Act*> build_backbone(const WeightBlob& blob, const std::string& prefix);
   Act* build_context(const WeightBlob& blob, const std::string& p, const Act* deep, int cctx);
   Act* build_neck(const WeightBlob& blob, const std::string& p, const Act* ctx, const std::vector<Act*>& feats, int cctx);

@@ -145,6 +145,7 @@ PilResampleParams Engine::pil_params(const PreprocessParams& pp) const {
 void Engine::set_resize_mode(int mode) {
   if (mode < 0 || mode > 2) throw std::invalid_argument("resize mode: 0 = cv::resize INTER_LINEAR model, 1 = PIL BILINEAR, 2 = PIL BICUBIC");
   if (base_) throw std::invalid_argument("shared engine: the base engine owns the frame path");
+  if (kind_ == 6 && mode != 0) throw std::invalid_argument("VP_AUTOSTEER: the network takes the 512 x 1024 frame as it is (no resize)");
   if (mode != resize_mode_) {
     resize_mode_ = mode;
     tab_h_ = tab_w_ = 0;
@@ -237,6 +238,8 @@ void Engine::upload_frame(const uint8_t* frame, int h, int w, int stride, int in
   if (base_) throw std::invalid_argument("shared engine: frames go to the base engine (vp_infer on the base, then vp_infer_shared)");
   if (kind_ == 5) throw std::runtime_error("VP_AUTOSPEED engines have no frame preprocess of their own: attach the engine to a detector (vp_detect_attach) and call vp_detect_infer, or hand the letterboxed tensor to vp_infer_tensor");
   if (!frame || h < 2 || w < 2 || stride < 3 * w) throw std::invalid_argument("bad frame geometry");
+  if (kind_ == 6 && (h != net_h() || w != net_w()))   // auto_steer_infer.py:37-39 raises ValueError: this network has no resize in front of it
+    throw std::invalid_argument("VP_AUTOSTEER: the input frame must be 512 x 1024 (height x width), got " + std::to_string(h) + " x " + std::to_string(w));
   if (index < 0 || index >= frames_) throw std::invalid_argument("frame index out of range");
   VP_HIP_CHECK(hipSetDevice(gpu_));
   const size_t need = (size_t)h * stride;

@@ -411,4 +411,31 @@ struct DetectHeadParams {
 };
 hipError_t launch_detect_head_decode(const DetectHeadParams& p, hipStream_t st);
 
+// ---- AutoSteer lane-perception head (auto_steer_percept_head.py:45-68; rowpair_conv: kernels_autodrive.hip, lane_rows_head: kernels_detect.hip)
+// Conv2d(cin -> 32, kernel (2,1), stride (2,1), bias) + SiLU: out(y, x, co) = SiLU(b[co] + sum_{ky, ci} w[ky * cin + ci][co] * in(2y + ky, x, ci)), fp32 FMAs
+// in that k order.  `out` may be an alias slice of a wider tensor (out.C = its row pitch).  replicate: every result is stored to the four pixels
+// (2y + dy, 2x + dx) of an `out` of twice the size -- Upsample(scale_factor=2, nearest) of the result (:55).
+struct RowpairConvParams {
+  ActView in;        // H x W x >= cin (an odd last row is ignored, as Conv2d does)
+  int cin;           // multiple of 8, <= 64
+  const float* w;    // [2 * cin][32]
+  const float* b;    // [32]
+  ActView out;       // (H / 2) x W, or H x 2W with replicate; 32 channels are stored at out.hi / out.lo
+  int replicate;
+};
+bool rowpair_conv_ok(const RowpairConvParams& p);
+hipError_t launch_rowpair_conv(const RowpairConvParams& p, hipStream_t st);
+// Everything behind `features` (:58-85), one workgroup per row, one thread per column (W = 256): c1 and c2 as ONE 2-output 3x3 convolution (BN folded,
+// taps outside the map skipped); lanes: SiLU, SiLU, softmax over the row, expectation of the column index / W; height: SiLU, SiLU, h1 over 16 groups of
+// 16 columns + SiLU, h2 over the 16 results + SiLU.
+struct LaneRowsHeadParams {
+  ActView features;  // H x 256 x cin
+  int cin;           // multiple of 8, <= 64
+  const float* w;    // [9 taps (ky * 3 + kx)][cin][2 outputs (c1, c2)]
+  const float* hw;   // [16] h1 weights, [16] h2 weights, then the biases of c1, c2, h1, h2
+  float* out;        // fp32 [2][H]: xp, h_vector
+};
+bool lane_rows_head_ok(const LaneRowsHeadParams& p);
+hipError_t launch_lane_rows_head(const LaneRowsHeadParams& p, hipStream_t st);
+
 }  // namespace vp

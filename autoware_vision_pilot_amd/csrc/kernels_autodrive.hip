@@ -350,6 +350,46 @@ __global__ __launch_bounds__(256) void upsample2_cat_kernel(const Upsample2CatPa
   if (p.out.lo) *reinterpret_cast<h8_t*>(p.out.lo + dso) = *reinterpret_cast<const h8_t*>(src.lo + so);
 }
 
+// Conv2d(cin -> 32, kernel (2,1), stride (2,1)) + bias + SiLU of the AutoSteer head (auto_steer_percept_head.py:38-39,48-51): per output pixel a
+// K = 2 * cin dot product over input rows 2y and 2y + 1 for 32 outputs.  134 MFLOP on the larger of the two maps against 8 MB of activations read
+// once: the launch is bound by the latency of its loads, not by arithmetic, so it is plain fp32 FMAs on hi + lo (exact sums of the pair) against
+// fp32 weights -- no operand split, no MFMA tile to pad at N = 32.  A thread owns 8 output channels of one pixel (4 threads per pixel: their
+// input loads hit the same lines); the weights sit in LDS as [k][32], read as broadcasts.  k runs ky-major, channel-minor, from the bias: a fixed order.
+__global__ __launch_bounds__(256) void rowpair_conv_kernel(const RowpairConvParams p) {
+  __shared__ float sw[2 * 64 * 32];
+  const int K = 2 * p.cin;
+  for (int i = threadIdx.x; i < K * 32; i += 256) sw[i] = p.w[i];
+  __syncthreads();
+  const int Ho = p.in.H >> 1, W = p.in.W;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int og = t & 3, pix = t >> 2;
+  if (pix >= Ho * W) return;
+  const int y = pix / W, x = pix - y * W;
+  float acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = p.b[og * 8 + i];
+  for (int ky = 0; ky < 2; ++ky) {
+    const size_t base = ((size_t)(2 * y + ky) * W + x) * p.in.C;
+    for (int c0 = 0; c0 < p.cin; c0 += 8) {
+      float v[8];
+      load8(p.in, base + c0, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float* wr = sw + (ky * p.cin + c0 + j) * 32 + og * 8;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = fmaf(v[j], wr[i], acc[i]);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = silu_f(acc[i]);
+  if (!p.replicate) {
+    store8(p.out, (size_t)pix * p.out.C + og * 8, acc);
+  } else {
+    for (int d = 0; d < 4; ++d) store8(p.out, ((size_t)(2 * y + (d >> 1)) * p.out.W + 2 * x + (d & 1)) * p.out.C + og * 8, acc);
+  }
+}
+
 hipError_t launch_chan_copy(const ActView& src, int src_off, const ActView& dst, int dst_off, int nch, hipStream_t st) {
   VP_LAUNCH(chan_copy_kernel, dim3(nblk((long long)src.H * src.W * (nch >> 3))), dim3(256), 0, st, src, src_off, dst, dst_off, nch);
 }
@@ -387,6 +427,15 @@ bool upsample2_cat_ok(const Upsample2CatParams& p) {
 hipError_t launch_upsample2_cat(const Upsample2CatParams& p, hipStream_t st) {
   if (!upsample2_cat_ok(p)) return hipErrorInvalidValue;
   VP_LAUNCH(upsample2_cat_kernel, dim3(nblk((long long)p.out.H * p.out.W * ((p.a_nch + p.b_nch) >> 3))), dim3(256), 0, st, p);
+}
+bool rowpair_conv_ok(const RowpairConvParams& p) {
+  const int Ho = p.in.H >> 1, f = p.replicate ? 2 : 1;
+  return p.in.hi && p.out.hi && p.w && p.b && p.cin >= 8 && p.cin <= 64 && !(p.cin & 7) && p.cin <= p.in.C && !((p.in.C | p.out.C) & 7) && p.out.C >= 32 && Ho >= 1 &&
+         p.in.W >= 1 && p.out.H == f * Ho && p.out.W == f * p.in.W && (p.out.lo == nullptr) == (p.in.lo == nullptr) && (long long)Ho * p.in.W <= (1 << 26);
+}
+hipError_t launch_rowpair_conv(const RowpairConvParams& p, hipStream_t st) {
+  if (!rowpair_conv_ok(p)) return hipErrorInvalidValue;
+  VP_LAUNCH(rowpair_conv_kernel, dim3(nblk((long long)(p.in.H >> 1) * p.in.W * 4)), dim3(256), 0, st, p);
 }
 hipError_t launch_dwconv_plain(const DwPlainParams& p, hipStream_t st) {
   VP_LAUNCH(dwconv_plain_kernel, dim3(nblk((long long)p.in.H * p.in.W * (p.in.C >> 3))), dim3(256), 0, st, p);

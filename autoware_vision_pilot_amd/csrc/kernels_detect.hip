@@ -250,4 +250,85 @@ hipError_t launch_detect_head_decode(const DetectHeadParams& p, hipStream_t st) 
   VP_LAUNCH(detect_head_decode_kernel, dim3(nblk(p.total)), dim3(256), 0, st, p);
 }
 
+// ------------------------------------------------------------------------------------------------ AutoSteer lane rows head
+// AutoSteerPerceptHead.forward behind `features` (auto_steer_percept_head.py:58-85), one workgroup per feature row y, one thread per column x (W = 256).
+//   conv : (a0, a1) = (c1, c2) biases (BN folded at load); for the taps (ky, kx) in row-major order that lie inside the map, for ci = 0 .. cin - 1:
+//          a_o = fmaf(features(y + ky - 1, x + kx - 1, ci) as hi (+ lo), w[tap][ci][o], a_o).  Weights are uniform: LDS, read as broadcasts.
+//   lanes: v = SiLU(SiLU(a0)) (Conv's own activation, then :60); m = row maximum; e = expf(v - m); S = sum e, N = sum e * x, both by the same
+//          binary tree over the 256 columns in LDS (element t adds element t + s, s = 128, 64, .., 1): xp = N / S / W  (:61-69).
+//   height: g = SiLU(SiLU(a1)) (Conv's own activation, then :73); u_j = SiLU(h1_b + g[16 j] * h1_w[0] + .. + g[16 j + 15] * h1_w[15]) for the 16 groups j, each summed in column order by one
+//          thread; h = SiLU(h2_b + u_0 * h2_w[0] + .. + u_15 * h2_w[15]) by thread 0  (:72-77).
+// No atomics, one fixed order: replays are bit-stable.  The kernel reads 3 x 256 x cin pairs per row (each pixel by three neighbouring threads and
+// three rows: L1 / L2 hits) for 2 x 9 x cin FMAs per thread -- 64 workgroups bound by the latency of the loads and of the ten barriers behind them.
+__global__ __launch_bounds__(256) void lane_rows_head_kernel(const LaneRowsHeadParams p) {
+  __shared__ float sw[9 * 64 * 2];
+  __shared__ float red0[256], red1[256], sg[256], su[16];
+  const int tid = threadIdx.x, y = blockIdx.x;
+  const int H = p.features.H, W = p.features.W, C = p.features.C;
+  for (int i = tid; i < 9 * p.cin * 2; i += 256) sw[i] = p.w[i];
+  __syncthreads();
+  float a0 = p.hw[32], a1 = p.hw[33];
+  for (int ky = 0; ky < 3; ++ky) {
+    const int yy = y + ky - 1;
+    if (yy < 0 || yy >= H) continue;
+    for (int kx = 0; kx < 3; ++kx) {
+      const int xx = tid + kx - 1;
+      if (xx < 0 || xx >= W) continue;
+      const size_t base = ((size_t)yy * W + xx) * C;
+      const float* wt = sw + (ky * 3 + kx) * p.cin * 2;
+      for (int c0 = 0; c0 < p.cin; c0 += 8) {
+        float v[8];
+        load8(p.features, base + c0, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          a0 = fmaf(v[j], wt[(c0 + j) * 2], a0);
+          a1 = fmaf(v[j], wt[(c0 + j) * 2 + 1], a1);
+        }
+      }
+    }
+  }
+  const float lane = silu_f(silu_f(a0));
+  sg[tid] = silu_f(silu_f(a1));
+  red0[tid] = lane;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red0[tid] = fmaxf(red0[tid], red0[tid + s]);
+    __syncthreads();
+  }
+  const float m = red0[0];
+  __syncthreads();
+  const float e = expf(lane - m);
+  red0[tid] = e;
+  red1[tid] = e * (float)tid;
+  if (tid < 16) {   // height branch, first stage: group tid
+    float u = p.hw[34];
+    for (int i = 0; i < 16; ++i) u = fmaf(sg[tid * 16 + i], p.hw[i], u);
+    su[tid] = silu_f(u);
+  }
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) {
+      red0[tid] += red0[tid + s];
+      red1[tid] += red1[tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    // NaN anywhere in the row: fmaxf drops it from m, but expf(NaN - m) carries it into both sums -- the range probe sees it
+    p.out[y] = red1[0] / red0[0] / (float)W;
+    float h = p.hw[35];
+    for (int j = 0; j < 16; ++j) h = fmaf(su[j], p.hw[16 + j], h);
+    p.out[H + y] = silu_f(h);
+  }
+}
+
+bool lane_rows_head_ok(const LaneRowsHeadParams& p) {
+  return p.features.hi && p.w && p.hw && p.out && p.features.W == 256 && p.features.H >= 1 && p.features.H <= 65535 && p.cin >= 8 && p.cin <= 64 && !(p.cin & 7) &&
+         p.cin <= p.features.C && !(p.features.C & 7);
+}
+hipError_t launch_lane_rows_head(const LaneRowsHeadParams& p, hipStream_t st) {
+  if (!lane_rows_head_ok(p)) return hipErrorInvalidValue;
+  VP_LAUNCH(lane_rows_head_kernel, dim3(p.features.H), dim3(256), 0, st, p);
+}
+
 }  // namespace vp

@@ -794,6 +794,78 @@ int vp_op_dwconv3x3(int gpu_id, int precision, const float* in, int c, int h, in
   });
 }
 
+// ---- single-operator entries of the AutoSteer head's kernels (unit tests)
+int vp_op_rowpair_conv(int gpu_id, int precision, const float* in, int cin, int h, int w, const float* weight, const float* bias, int replicate,
+                       int dst_c, int dst_off, const float* dst_init, uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!in || !weight || !bias || !out_hi || cin < 8 || cin > 64 || (cin & 7) || h < 2 || w < 1 || (long long)h * w > (1 << 20) || dst_c < 32 || (dst_c & 31) || dst_off < 0 ||
+        (dst_off & 31) || dst_off + 32 > dst_c)
+      throw std::invalid_argument("bad argument (cin: a multiple of 8 up to 64; dst_c, dst_off: multiples of 32 with dst_off + 32 <= dst_c)");
+    vp::Engine g(-1, nullptr, precision, gpu_id);
+    const int f = replicate ? 2 : 1, ho = (h / 2) * f, wo = w * f;
+    vp::Act* ti = g.new_act("in", cin, h, w);
+    vp::Act* to = g.new_act("out", dst_c, ho, wo);
+    g.upload_act(ti, in);
+    if (dst_init) g.upload_act(to, dst_init);
+    std::vector<float> wk((size_t)2 * cin * 32);
+    for (int co = 0; co < 32; ++co)
+      for (int ci = 0; ci < cin; ++ci)
+        for (int ky = 0; ky < 2; ++ky) wk[((size_t)ky * cin + ci) * 32 + co] = weight[((size_t)co * cin + ci) * 2 + ky];
+    float* dw = g.alloc_f32(wk.size());
+    float* db = g.alloc_f32(32);
+    g.copy_h2d(dw, wk.data(), wk.size() * sizeof(float));
+    g.copy_h2d(db, bias, 32 * sizeof(float));
+    vp::RowpairConvParams q{};
+    q.in = ti->view();
+    q.cin = cin;
+    q.w = dw;
+    q.b = db;
+    q.out = to->view();
+    q.out.hi += dst_off;   // the alias-slice convention: pixel * Cstore + channel
+    if (q.out.lo) q.out.lo += dst_off;
+    q.replicate = replicate ? 1 : 0;
+    VP_HIP_CHECK(vp::launch_rowpair_conv(q, g.stream()));
+    read_planes_chw(g, to, out_hi, out_lo);
+  });
+}
+
+int vp_op_lane_rows_head(int gpu_id, int precision, const float* features, int cin, int h, int w, const float* c1_w, float c1_b, const float* c2_w,
+                         float c2_b, const float* h1_w, float h1_b, const float* h2_w, float h2_b, float* out_2xh, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!features || !c1_w || !c2_w || !h1_w || !h2_w || !out_2xh || cin < 8 || cin > 64 || (cin & 7) || h < 1 || h > 4096 || w != 256)
+      throw std::invalid_argument("bad argument (cin: a multiple of 8 up to 64; w = 256)");
+    vp::Engine g(-1, nullptr, precision, gpu_id);
+    vp::Act* tf = g.new_act("features", cin, h, w);
+    g.upload_act(tf, features);
+    std::vector<float> wk((size_t)9 * cin * 2), hk(36);
+    for (int t = 0; t < 9; ++t)
+      for (int ci = 0; ci < cin; ++ci) {
+        wk[((size_t)t * cin + ci) * 2 + 0] = c1_w[(size_t)ci * 9 + t];
+        wk[((size_t)t * cin + ci) * 2 + 1] = c2_w[(size_t)ci * 9 + t];
+      }
+    for (int i = 0; i < 16; ++i) {
+      hk[i] = h1_w[i];
+      hk[16 + i] = h2_w[i];
+    }
+    hk[32] = c1_b;
+    hk[33] = c2_b;
+    hk[34] = h1_b;
+    hk[35] = h2_b;
+    float* dw = g.alloc_f32(wk.size());
+    float* dh = g.alloc_f32(hk.size());
+    g.copy_h2d(dw, wk.data(), wk.size() * sizeof(float));
+    g.copy_h2d(dh, hk.data(), hk.size() * sizeof(float));
+    vp::LaneRowsHeadParams q{};
+    q.features = tf->view();
+    q.cin = cin;
+    q.w = dw;
+    q.hw = dh;
+    q.out = g.alloc_f32((size_t)2 * h);
+    VP_HIP_CHECK(vp::launch_lane_rows_head(q, g.stream()));
+    g.copy_d2h(out_2xh, q.out, (size_t)2 * h * sizeof(float));
+  });
+}
+
 // ---- composed up-sampling stage (round 6): the load-time weight composition alone, and the whole stage as one operator
 int vp_compose_upconv(int gpu_id, const float* wt, const float* bt, const float* ws, const float* bs, const float* w3, const float* b3, int cin, int cm,
                       int cout, int cs, double* wx, double* wsk, double* bias, char* err, size_t err_len) {

@@ -15,7 +15,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvp_hip.so")
 
-VP_SCENESEG, VP_SCENE3D, VP_DOMAINSEG, VP_EGOLANES, VP_AUTODRIVE, VP_AUTOSPEED = 0, 1, 2, 3, 4, 5
+VP_SCENESEG, VP_SCENE3D, VP_DOMAINSEG, VP_EGOLANES, VP_AUTODRIVE, VP_AUTOSPEED, VP_AUTOSTEER = 0, 1, 2, 3, 4, 5, 6
 VP_WEIGHTS_FP8 = 16
 VP_PLAN_LATENCY = 32  # creation flag: this engine's kernel plan targets one network on one camera, one frame at a time (vp_hip.h)
 VP_FP16, VP_FP16X3 = 0, 1
@@ -23,7 +23,7 @@ VP_BGR8, VP_RGB8 = 0, 1
 VP_PLANES_BGR, VP_PLANES_RGB = 0, 1
 VP_DECODE_SEG_MASK, VP_DECODE_LANE_LABEL, VP_DECODE_CLASS_INDEX = 0, 1, 2
 KINDS = {"sceneseg": VP_SCENESEG, "scene3d": VP_SCENE3D, "domainseg": VP_DOMAINSEG, "egolanes": VP_EGOLANES, "autodrive": VP_AUTODRIVE,
-         "autospeed": VP_AUTOSPEED}
+         "autospeed": VP_AUTOSPEED, "autosteer": VP_AUTOSTEER}
 PRECISIONS = {"fp16": VP_FP16, "fp16x3": VP_FP16X3, "fp32": VP_FP16X3}
 
 # every symbol include/vp_hip.h declares: name -> (restype, argtypes)
@@ -111,6 +111,9 @@ _SIGS = {
     "vp_op_detect_head_decode": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_char_p, C.c_size_t]),
     "vp_op_upsample2_cat": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_char_p, C.c_size_t]),
     "vp_op_dwconv3x3": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "vp_op_rowpair_conv": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "vp_op_lane_rows_head": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_char_p,
+                                       C.c_size_t]),
     "vp_version": (C.c_char_p, []),
     "vp_set_lane_ring": (C.c_int, [_P, C.c_int]),
     "vp_lane_ring_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int)]),
@@ -775,6 +778,41 @@ def op_dwconv3x3(x, weight, bias, act=0, add=None, precision="fp16x3", gpu_id=0)
     _op_rc(load().vp_op_dwconv3x3(gpu_id, pr, _ptr(x), c, h, w, _ptr(weight), _ptr(bias), int(act), None if add is None else _ptr(add), _ptr(hi), _ptr(lo), err,
                                   len(err)), err, "vp_op_dwconv3x3")
     return hi, lo
+
+
+def op_rowpair_conv(x, weight, bias, replicate=False, dst=None, dst_off=0, precision="fp16x3", gpu_id=0):
+    """vp_op_rowpair_conv: Conv2d(cin -> 32, kernel (2,1), stride (2,1)) + bias + SiLU of x [cin][h][w] (weight [32][cin][2][1]); with `replicate` every
+    result pixel is stored 2 x 2.  dst: the destination's initial content [dst_c][h'][w'] (None: 32 channels of zeros); the result lands in its channels
+    [dst_off, dst_off + 32).  Returns the whole destination as (hi, lo) float16 planes."""
+    x, weight, bias = _f32(x), _f32(weight), _f32(bias)
+    cin, h, w = x.shape
+    assert weight.shape == (32, cin, 2, 1) and bias.shape == (32,)
+    f = 2 if replicate else 1
+    ho, wo = (h // 2) * f, w * f
+    dst = None if dst is None else _f32(dst)
+    dst_c = 32 if dst is None else dst.shape[0]
+    assert dst is None or dst.shape == (dst_c, ho, wo)
+    hi = np.empty((dst_c, ho, wo), np.float16)
+    lo = np.empty_like(hi)
+    err = C.create_string_buffer(512)
+    pr = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    _op_rc(load().vp_op_rowpair_conv(gpu_id, pr, _ptr(x), cin, h, w, _ptr(weight), _ptr(bias), int(bool(replicate)), dst_c, int(dst_off),
+                                     None if dst is None else _ptr(dst), _ptr(hi), _ptr(lo), err, len(err)), err, "vp_op_rowpair_conv")
+    return hi, lo
+
+
+def op_lane_rows_head(features, c1_w, c1_b, c2_w, c2_b, h1_w, h1_b, h2_w, h2_b, precision="fp16x3", gpu_id=0):
+    """vp_op_lane_rows_head: features [cin][h][256] -> [2][h] fp32 (xp, h_vector) as AutoSteerPerceptHead.forward gives behind `features`; c1 / c2 are the
+    3x3 convolutions [cin][3][3] with their BatchNorm folded in, h1 / h2 the 16-tap row convolutions."""
+    features, c1_w, c2_w, h1_w, h2_w = _f32(features), _f32(c1_w).reshape(-1), _f32(c2_w).reshape(-1), _f32(h1_w).reshape(-1), _f32(h2_w).reshape(-1)
+    cin, h, w = features.shape
+    assert c1_w.size == cin * 9 and c2_w.size == cin * 9 and h1_w.size == 16 and h2_w.size == 16
+    out = np.empty((2, h), np.float32)
+    err = C.create_string_buffer(512)
+    pr = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    _op_rc(load().vp_op_lane_rows_head(gpu_id, pr, _ptr(features), cin, h, w, _ptr(c1_w), float(c1_b), _ptr(c2_w), float(c2_b), _ptr(h1_w), float(h1_b),
+                                       _ptr(h2_w), float(h2_b), _ptr(out), err, len(err)), err, "vp_op_lane_rows_head")
+    return out
 
 
 def autosteer_angle(logits):

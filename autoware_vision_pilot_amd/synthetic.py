@@ -318,6 +318,58 @@ def autospeed_param_count(num_classes=AS_NUM_CLASSES):
     return sum(int(np.prod(s)) for k, s, _ in autospeed_spec(num_classes) if not k.endswith(("running_mean", "running_var")))
 
 
+# ------------------------------------------------------------------------------------------------ AutoSteer 2.0 lane-perception network
+AST_ROWS, AST_COLS = 64, 256          # the head's feature map at 512 x 1024
+
+
+def autosteer_spec():
+    """(key, shape, init kind) of AutoSteerNetwork().build_model('n') in the reference ``state_dict`` order, num_batches_tracked omitted
+    (auto_steer_network.py:33-43, auto_steer_backbone.py:8-40, auto_steer_neck.py:8-13, auto_steer_percept_head.py:29-43).  The backbone under ``net.`` is
+    AutoDrive's under ``backbone.``, key for key; ``fpn.h1`` / ``fpn.h2`` are the detector neck's."""
+    s = [("net." + k[len("backbone."):], shape, kind) for k, shape, kind in autodrive_spec() if k.startswith("backbone.")]
+    s += _as_c3k2("fpn.h1", 128 + 256, 128, False) + _as_c3k2("fpn.h2", 128 + 128, 64, False)
+    s += _ad_conv_bn("head.c1", 1, 64, 3) + _ad_conv_bn("head.c2", 1, 64, 3)
+    for v in ("v1", "v2"):
+        s += [(f"head.{v}.weight", (32, 64, 2, 1), "conv"), (f"head.{v}.bias", (32,), "bias")]
+    for h in ("h1", "h2"):
+        s += [(f"head.{h}.weight", (1, 1, 1, 16), "conv"), (f"head.{h}.bias", (1,), "bias")]
+    return s
+
+
+# With plain random head weights the row softmax is nearly uniform (every xp ~ 0.498) and h_vector sits on one side of 0.5: every test of the
+# outputs would be vacuous.  Chosen over a small grid by tools/pin_autosteer_net.py so that the conditions it asserts hold on its fixture frames:
+AST_C1_NORM_GAIN = 12.0                # head.c1.norm.weight: a peaked row softmax, xp spread over the rows
+AST_C2_NORM_GAIN = 2.0                 # head.c2.norm.weight
+AST_H1_GAIN, AST_H1_BIAS = 2.0, 0.0    # head.h1.weight / bias
+AST_H2_GAIN, AST_H2_BIAS = 4.0, -0.5   # head.h2.weight / bias: h_vector on both sides of 0.5
+
+
+def make_autosteer_state_dict(seed, gains=None):
+    """Seeded init of the lane-perception network: the backbone as make_autodrive_state_dict tunes it (exp0 / ctx2 gains), the head with the gains
+    above (``gains``: a dict overriding them by name, c1 / c2 / h1 / h1_bias / h2 / h2_bias -- the pin tool's grid search)."""
+    g = {"c1": AST_C1_NORM_GAIN, "c2": AST_C2_NORM_GAIN, "h1": AST_H1_GAIN, "h1_bias": AST_H1_BIAS, "h2": AST_H2_GAIN, "h2_bias": AST_H2_BIAS}
+    g.update(gains or {})
+    rng = np.random.default_rng(seed)
+    out = {}
+    for k, shape, kind in autosteer_spec():
+        if kind == "conv1d":   # net.pN.1.exp0.weight of the backbone's CTX blocks (_ad_ctx): gain 0.5, as make_autodrive_state_dict
+            out[k] = (rng.standard_normal(shape, dtype=np.float32) * np.float32(0.5 * np.sqrt(2.0 / shape[1]))).astype(np.float32)
+        else:
+            out[k] = _init(rng, shape, kind)
+        if k.endswith("ctx2.weight"):
+            out[k] = out[k] * np.float32(0.5)
+    out["head.c1.norm.weight"] = out["head.c1.norm.weight"] * np.float32(g["c1"])
+    out["head.c2.norm.weight"] = out["head.c2.norm.weight"] * np.float32(g["c2"])
+    for h in ("h1", "h2"):
+        out[f"head.{h}.weight"] = out[f"head.{h}.weight"] * np.float32(g[h])
+        out[f"head.{h}.bias"] = out[f"head.{h}.bias"] + np.float32(g[h + "_bias"])
+    return out
+
+
+def autosteer_param_count():
+    return sum(int(np.prod(s)) for k, s, _ in autosteer_spec() if not k.endswith(("running_mean", "running_var")))
+
+
 # ------------------------------------------------------------------------------------------------ frames
 def synthetic_frame(h, w, seed, smooth=True):
     """Seeded u8 HxWx3 frame.  ``smooth`` mixes low-frequency sinusoids with noise so argmax regions are

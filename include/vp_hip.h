@@ -61,7 +61,15 @@ enum vp_status { VP_OK = 0, VP_ERR_ARG = -1, VP_ERR_WEIGHTS = -2, VP_ERR_HIP = -
  * eval-mode tensor [4 + nc][10752] (cx, cy, w, h in input pixels, then sigmoid class scores; levels of stride 8, 16, 32 one after the other), the
  * tensor vp_detect_postprocess reads; no mask.  VP_FP16 / VP_FP16X3 (| VP_PLAN_LATENCY); VP_WEIGHTS_FP8, vp_create_shared* and
  * vp_create_batched* are refused with VP_ERR_ARG. */
-enum vp_model_kind { VP_SCENESEG = 0, VP_SCENE3D = 1, VP_DOMAINSEG = 2, VP_EGOLANES = 3, VP_AUTODRIVE = 4, VP_AUTOSPEED = 5 };
+/* VP_AUTOSTEER: the AutoSteer 2.0 lane-perception network, Models/model_components/auto_steer/auto_steer_network.py:39-43, version 'n' (what
+ * Models/inference/auto_steer_infer.py AutoSteerNetworkInfer runs).  Input: a 512 x 1024 frame taken as it is -- R, G, B planes of u8 / 255, no mean / std,
+ * no resize (auto_steer_infer.py:19-23,41-45): vp_infer / vp_upload_frame return VP_ERR_ARG for any other geometry (the reference raises ValueError),
+ * vp_set_input_format picks BGR8 (default) or RGB8 bytes, vp_infer_tensor takes the [3][512][1024] planes.  Output through vp_logits: shape
+ * {1, 2, 64, 1}: plane 0 = xp (ego-lane position per feature row, in [0, 1)), plane 1 = h_vector (per-row validity; the visualisation draws a row when
+ * it is >= 0.5); no mask.  VP_FP16 / VP_FP16X3 (| VP_PLAN_LATENCY); VP_WEIGHTS_FP8, vp_create_shared* and vp_create_batched* are refused with
+ * VP_ERR_ARG; a blob whose head is not the 'n' head is refused with VP_ERR_WEIGHTS naming the key.  (The v1 temporal AutoSteer head fed by EgoLanes
+ * logits is another model and not part of this library: vp_set_lane_ring hands its input over.) */
+enum vp_model_kind { VP_SCENESEG = 0, VP_SCENE3D = 1, VP_DOMAINSEG = 2, VP_EGOLANES = 3, VP_AUTODRIVE = 4, VP_AUTOSPEED = 5, VP_AUTOSTEER = 6 };
 
 /* VP_FP16  : fp16 tensors, fp16 MFMA, fp32 accumulate (the reference's "fp16" configuration).
  * VP_FP16X3: fp32-class accuracy on the fp16 matrix pipe: every tensor is a (hi, lo) fp16 pair and every
@@ -386,6 +394,16 @@ int vp_op_upsample2_cat(int gpu_id, int precision, const float* a, int ca, const
                         char* err, size_t err_len);
 int vp_op_dwconv3x3(int gpu_id, int precision, const float* in, int c, int h, int w, const float* weight, const float* bias, int act, const float* add,
                     uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len);
+/* ---- single-operator entries of the AutoSteer head's kernels (unit tests; not used by callers) ------------
+ * vp_op_rowpair_conv: Conv2d(cin -> 32, kernel (2,1), stride (2,1)) + bias + SiLU: in [cin][h][w], weight [32][cin][2][1], bias [32].  The result,
+ *   (h / 2) x w -- with replicate every pixel stored 2 x 2: h' x 2w, h' = 2 (h / 2) -- lands in channels [dst_off, dst_off + 32) of a destination of dst_c channels
+ *   (multiples of 32) that starts as dst_init ([dst_c][h'][w'] or NULL = zeros); out_hi / out_lo: the whole destination as fp16 bit patterns.
+ * vp_op_lane_rows_head: features [cin][h][256] -> out [2][h] (xp, h_vector): c1_w / c2_w [cin][3][3] and c1_b / c2_b with the BatchNorm folded in,
+ *   h1_w / h2_w [16]. */
+int vp_op_rowpair_conv(int gpu_id, int precision, const float* in, int cin, int h, int w, const float* weight, const float* bias, int replicate,
+                       int dst_c, int dst_off, const float* dst_init, uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len);
+int vp_op_lane_rows_head(int gpu_id, int precision, const float* features, int cin, int h, int w, const float* c1_w, float c1_b, const float* c2_w,
+                         float c2_b, const float* h1_w, float h1_b, const float* h2_w, float h2_b, float* out_2xh, char* err, size_t err_len);
 
 /* ---- single-operator entry (unit parity tests of the MFMA conv kernel; not used by callers) -------------- */
 /* mode 0: Conv2d k=ks stride 1 pad ks/2, weight [Cout][Cin][ks][ks]; mode 1: ConvTranspose2d k2 s2, weight

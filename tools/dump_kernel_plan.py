@@ -10,7 +10,9 @@ rule and review the diff.
 
 `dump_kernel_plan.py autospeed` writes tests/golden/kernel_plan_autospeed.json instead: the detector network (VP_AUTOSPEED) in both precisions, default
 and latency plan, and AutoDrive's plan beside it -- [name, tag, launch] per launch; the two share their backbone launches (Engine::build_ad_backbone),
-which tests/test_autospeed_net_emulated.py checks entry by entry.  Without an argument only the two scene-network files are written."""
+which tests/test_autospeed_net_emulated.py checks entry by entry.  `dump_kernel_plan.py autosteer` writes tests/golden/kernel_plan_autosteer.json:
+the AutoSteer 2.0 lane-perception network (VP_AUTOSTEER) in the same four forms (tests/test_autosteer_net_emulated.py compares, and checks its
+backbone launches against AutoDrive's).  Without an argument only the two scene-network files are written."""
 import ctypes as ct
 import json
 import os
@@ -54,6 +56,21 @@ def autospeed_plan(lib):
     return out
 
 
+def autosteer_plan(lib):
+    """{"autosteer/<precision>[/latency]": [[name, tag, launch], ...]}"""
+    from autoware_vision_pilot_amd import synthetic, weights as vw
+
+    out = {}
+    blob = vw.pack_state_dict(synthetic.make_autosteer_state_dict(0))
+    for prec in ("fp16x3", "fp16"):
+        for latency in (False, True):
+            eng = lib.Engine("autosteer", blob, precision=prec, plan_latency=latency)
+            rows = zip(eng.layers(), eng.layer_kernels(), eng.layer_launches())
+            out[f"autosteer/{prec}" + ("/latency" if latency else "")] = [[n, k, l] for (n, _, _), k, l in rows]
+            eng.close()
+    return out
+
+
 if __name__ == "__main__":
     import build as eb
 
@@ -68,6 +85,12 @@ if __name__ == "__main__":
         path = os.path.join(ROOT, "tests", "golden", "kernel_plan_autospeed.json")
         with open(path, "w") as f:
             json.dump(autospeed_plan(lib), f, indent=0)
+        print("written", path)
+        sys.exit(0)
+    if sys.argv[1:] == ["autosteer"]:
+        path = os.path.join(ROOT, "tests", "golden", "kernel_plan_autosteer.json")
+        with open(path, "w") as f:
+            json.dump(autosteer_plan(lib), f, indent=0)
         print("written", path)
         sys.exit(0)
     for fname, latency in (("kernel_plan.json", False), ("kernel_plan_latency.json", True)):
