@@ -81,6 +81,12 @@ struct ConvGemmParams {
   // convt_rs_kernel: cap on the persistent pixel-tile groups, resolved when the PLAN is built (developer option VP_CONVT_RS_GROUPS; 0 = no cap).
   // It used to be read at launch / capture time: an option set later changed existing engines behind their plan hash
   int rs_groups;
+  // VP_ACT_SCALE (per-tensor power-of-two activation scale): the tensors of a flagged engine are stored as x * 2^-s_t.  scaled != 0
+  // routes the launch to the all-runtime epilogue (conv_epilogue.hpp), which then evaluates fmaf(acc, wscale[co] * in_mul, bias[co]) (in_mul = 2^s_in: the
+  // product of two powers of two, exact -- the input exponent folded into the row scale), reads the residual as res * res_mul (2^s_res) and stores
+  // v * out_mul (2^-s_out) behind activation, residual and post-activation.  scaled == 0: the three floats are not read (zero-initialised blocks stay valid).
+  int scaled;
+  float in_mul, res_mul, out_mul;
 };
 
 // nn.GELU() (exact erf form, scene_neck.py:8).  ~300 M activations per frame: libm's erff (~45 VALU ops, branchy)

@@ -48,10 +48,19 @@ __device__ __forceinline__ void epilogue_store8(const ConvGemmParams& p, int M, 
   const int act = ACT >= 0 ? ACT : p.act;
   const int res_mode = RES >= 0 ? RES : p.res_mode;
   const int store_mode = STORE >= 0 ? STORE : p.store_mode;
+  const bool scaled = STORE < 0 && p.scaled != 0;   // VP_ACT_SCALE: like post_act, only the all-runtime instantiation carries it (the engine routes such launches there)
+  f32x4_t t0 = s0, t1 = s1;
+  if (scaled) {   // the input exponent folds into the row scale: a power of two times the row's scale, exact
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      t0[r] *= p.in_mul;
+      t1[r] *= p.in_mul;
+    }
+  }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    v[r] = apply_act(fmaf(v[r], s0[r], b0[r]), act);   // s = 2^-prescale of the weight row (ConvGemmParams::wscale): exact
-    v[4 + r] = apply_act(fmaf(v[4 + r], s1[r], b1[r]), act);
+    v[r] = apply_act(fmaf(v[r], t0[r], b0[r]), act);   // s = 2^-prescale of the weight row (ConvGemmParams::wscale): exact
+    v[4 + r] = apply_act(fmaf(v[4 + r], t1[r], b1[r]), act);
   }
   if (store_mode == STORE_NCHW_F32) {
 #pragma unroll
@@ -83,12 +92,20 @@ __device__ __forceinline__ void epilogue_store8(const ConvGemmParams& p, int M, 
 #pragma unroll
       for (int r = 0; r < 8; ++r) r8[r] += (float)rl[r];
     }
+    if (scaled) {   // true residual values: RES_MULADD (v * r + r) is not homogeneous
+#pragma unroll
+      for (int r = 0; r < 8; ++r) r8[r] *= p.res_mul;
+    }
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = (res_mode == RES_ADD) ? (v[r] + r8[r]) : (v[r] * r8[r] + r8[r]);
   }
   if (STORE < 0 && p.post_act != ACT_NONE) {  // only the all-runtime instantiation carries it (the engine routes such ops there)
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = apply_act(v[r], p.post_act);
+  }
+  if (scaled) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) v[r] *= p.out_mul;
   }
   h8_t hi;
 #pragma unroll
@@ -212,7 +229,7 @@ __device__ __forceinline__ void epilogue_pass(const ConvGemmParams& p, char* sta
         *reinterpret_cast<f32x4_t*>(dst + 4) = *reinterpret_cast<const f32x4_t*>(stage + r * PITCH + c8 * 32 + 16);
       }
     } else {
-      const int key = p.post_act != ACT_NONE ? -1 : p.store_mode * 100 + p.res_mode * 10 + p.act;
+      const int key = (p.post_act != ACT_NONE || p.scaled != 0) ? -1 : p.store_mode * 100 + p.res_mode * 10 + p.act;
 #define VP_ROWS(S, R, A) epilogue_rows<S, R, A, PXT, RPI, PITCH>(p, stage, r0, c8, co, pix, M)
       switch (key) {
         case STORE_NHWC * 100 + RES_NONE * 10 + ACT_GELU: VP_ROWS(STORE_NHWC, RES_NONE, ACT_GELU); break;   // decoder 3x3
@@ -314,7 +331,7 @@ __device__ __forceinline__ void epilogue_regs_fp16(const ConvGemmParams& p, char
 }
 // which (activation, store) combinations have a register-epilogue instantiation; 0 = none, else a small case id
 __host__ __device__ inline int regepi_case(const ConvGemmParams& p, int co_tile, bool split) {
-  if (split || p.out_lo || p.res_mode != RES_NONE || p.nsplit != 1 || p.post_act != ACT_NONE) return 0;
+  if (split || p.out_lo || p.res_mode != RES_NONE || p.nsplit != 1 || p.post_act != ACT_NONE || p.scaled != 0) return 0;
   if (p.store_mode == STORE_NHWC) {
     if (p.act == ACT_GELU_F16) return 1;
     if (p.act == ACT_SILU_F16) return 2;

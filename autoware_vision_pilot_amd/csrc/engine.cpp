@@ -161,6 +161,11 @@ RowScale row_prescale(const float* w, size_t rows, size_t per, size_t rows_alloc
 // ==================================================================================================== Engine
 Engine::Engine(int kind, const WeightBlob* blob, int precision, int gpu_id, Engine* base, int frames, int frame_index)
     : kind_(kind), precision_(precision), gpu_(gpu_id), frames_(frames), frame_index_(frame_index), base_(base) {
+  if ((precision & 64) != 0) {
+    if (kind >= 0 && kind != 4) throw std::invalid_argument("VP_ACT_SCALE: the per-tensor activation scale is built for VP_AUTODRIVE engines only");
+    if ((precision & 15) != 1) throw std::invalid_argument("VP_ACT_SCALE needs VP_FP16X3 (the parity mode)");
+    if (base || frames != 1) throw std::invalid_argument("VP_ACT_SCALE: shared-prefix and batched creation are not supported");
+  }
   if (frames < 1 || frames > 16) throw std::invalid_argument("frames must be 1..16");
   if (frames > 1 && (base || kind < 0 || kind > 3)) throw std::invalid_argument("a batched encoder is a base engine of a scene network kind");
   if (base && (frame_index < 0 || frame_index >= base->frames_)) throw std::invalid_argument("frame_index out of the base engine's range");
@@ -171,7 +176,7 @@ Engine::Engine(int kind, const WeightBlob* blob, int precision, int gpu_id, Engi
   if (kind == 6 && ((precision & 16) != 0 || base || frames > 1))
     throw std::invalid_argument("VP_AUTOSTEER: VP_WEIGHTS_FP8, shared-prefix and batched creation are not supported for the lane-perception network (VP_FP16 / VP_FP16X3, optionally | VP_PLAN_LATENCY)");
   if (base && base->kind_ == 6) throw std::invalid_argument("VP_AUTOSTEER engines cannot be the base of a shared-prefix engine");
-  if ((precision & 15) > 1 || (precision & ~(1 | 16 | 32)) != 0) throw std::invalid_argument("precision must be VP_FP16 or VP_FP16X3 (optionally | VP_WEIGHTS_FP8 | VP_PLAN_LATENCY)");
+  if ((precision & 15) > 1 || (precision & ~(1 | 16 | 32 | 64)) != 0) throw std::invalid_argument("precision must be VP_FP16 or VP_FP16X3 (optionally | VP_WEIGHTS_FP8 | VP_PLAN_LATENCY | VP_ACT_SCALE)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     throw std::runtime_error("libvp_hip: no HIP device visible (this library has no CPU fallback)");
@@ -388,6 +393,11 @@ Act* Engine::frame_view(const Act* a, int f) {
 Act* Engine::new_act(const std::string& name, int creal, int h, int w) {
   auto a = std::make_unique<Act>();
   a->name = name;
+  if (act_scale()) {
+    a->tie = (int)act_exp_.size();
+    act_exp_.push_back(0);
+    act_exp_seen_.push_back(0);
+  }
   a->Creal = creal;
   a->C = round_up(creal, 32);
   a->H = h;
@@ -1032,6 +1042,7 @@ Act* Engine::alias_slice(const std::string& name, Act* whole, int ch_off, int nc
   slice->W = whole->W;
   slice->hi = whole->hi + ch_off;
   slice->lo = whole->lo ? whole->lo + ch_off : nullptr;
+  slice->tie = whole->tie;
   acts_.push_back(std::move(slice));
   return acts_.back().get();
 }
@@ -1068,8 +1079,15 @@ Engine::AdFeatures Engine::build_ad_backbone(const WeightBlob& blob, const std::
     sp.b = dupload(bk);
     x = new_act(P + "p1", f.cout, net_h() / 2, net_w() / 2);
     sp.out = x->view();
-    push_op(P + "p1", "stem", [sp](hipStream_t st) { return launch_stem(sp, st); }, 2.0 * 27 * f.cout * x->H * x->W,
-         4.0 * 3 * net_h() * net_w() + 2.0 * x->elems());
+    // (VP_ACT_SCALE, here and below: a launch reads its tensors' exponents when it RUNS; for an unflagged engine they are 0, `scaled` is 0 and every
+    // multiplier 1.0f, so the parameter block is the one built above)
+    push_op(P + "p1", "stem", [this, sp, x](hipStream_t st) {
+      StemParams q = sp;
+      q.scaled = act_exp(x) != 0;
+      q.out_mul = act_mul(x, -1);
+      return launch_stem(q, st);
+    }, 2.0 * 27 * f.cout * x->H * x->W, 4.0 * 3 * net_h() * net_w() + 2.0 * x->elems());
+    ops_.back().writes = {x};
   }
   auto conv_bn = [&](const std::string& name, const Act* in, int ks, int stride, int act) -> Act* {
     Folded f = fold_conv_norm(blob, name);
@@ -1092,7 +1110,7 @@ Engine::AdFeatures Engine::build_ad_backbone(const WeightBlob& blob, const std::
     float* partial = static_cast<float*>(dalloc((size_t)nslab * a->C * sizeof(float)));
     {
       PoolParams pp{a->view(), partial, nslab};
-      push_op(cp + ".mean", "pool_partial", [pp](hipStream_t st) { return launch_pool_partial(pp, st); });
+      push_op(cp + ".mean", "pool_partial", [pp](hipStream_t st) { return launch_pool_partial(pp, st); });   // (VP_ACT_SCALE: sums of STORED values; exp0 scales the mean)
     }
     // exp0: Conv1d(C -> H*W, k3, pad 1) on a length-1 sequence == the centre tap as a [H*W][C] matrix (:210), SiLU twice (:211-213)
     const HostTensor& ew = T(cp + ".exp0.weight");
@@ -1142,12 +1160,24 @@ Engine::AdFeatures Engine::build_ad_backbone(const WeightBlob& blob, const std::
       // Selected only by VP_CTX_FUSE=1; the scene networks' context_layer_2 + 3 (200 rows, 2x2 patches, 50 workgroups) keep the fused form (21 -> 17 us).
       // lanes per row: as few as keep every map row under a patch in one pass (16x16: 324 rows, one lane each in two passes; 8x8: 100 rows, two lanes each)
       CtxExpConv1Params q{fp, cpp, HW > 2048 ? 16 : 8, HW > 2048 ? 1 : 2};
-      if (dev_option_is("VP_CTX_FUSE", '1') && ctx_exp_conv1_ok(q)) {
+      if (dev_option_is("VP_CTX_FUSE", '1') && ctx_exp_conv1_ok(q) && !act_scale()) {
         push_op(cp + ".exp0+ctx0", q.tile == 16 ? "ctx_exp_conv1<t16>" : "ctx_exp_conv1<t8>", [q](hipStream_t st) { return launch_ctx_exp_conv1(q, st); },
              2.0 * HW * C + 2.0 * 9 * c0n * HW, (fp.w8 ? 1.0 : 4.0) * HW * C);
       } else {
-        push_op(cp + ".exp0", fp.rows_kernel ? "fc<rows>" : "fc", [fp](hipStream_t st) { return launch_fc(fp, st); }, 2.0 * HW * C, (fp.w8 ? 1.0 : 4.0) * HW * C);
-        push_op(cp + ".ctx0", "ctx_conv1", [cpp](hipStream_t st) { return launch_ctx_conv1(cpp, st); }, 2.0 * 9 * c0n * HW);
+        // exp0 reads the mean of the stored tensor: 2^s_a folds into 1 / (H W) (a power of two times a float: exact); its fp32 map holds true values.
+        // ctx0 stores its result times 2^-s_out.  Both read the exponents when they launch (vp_calibrate_range changes them; the graph is re-captured).
+        push_op(cp + ".exp0", fp.rows_kernel ? "fc<rows>" : "fc", [this, fp, a](hipStream_t st) {
+          FcParams q2 = fp;
+          q2.inv_hw = fp.inv_hw * act_mul(a);
+          return launch_fc(q2, st);
+        }, 2.0 * HW * C, (fp.w8 ? 1.0 : 4.0) * HW * C);
+        push_op(cp + ".ctx0", "ctx_conv1", [this, cpp, c2](hipStream_t st) {
+          CtxConv1Params q2 = cpp;
+          q2.scaled = act_exp(c2) != 0;
+          q2.out_mul = act_mul(c2, -1);
+          return launch_ctx_conv1(q2, st);
+        }, 2.0 * 9 * c0n * HW);
+        ops_.back().writes = {c2};
       }
     }
     // ctx1: conv3x3 C/2 -> C + SiLU, gate: c4*x + x, SiLU (:218-224)
@@ -1171,12 +1201,17 @@ Engine::AdFeatures Engine::build_ad_backbone(const WeightBlob& blob, const std::
     Act* cat = new_act(sp + ".cat", 4 * c_, x->H, x->W);
     const ActView cv = cat->view(), c1v = c1->view();
     // cat((x, mp5(x), mp5(mp5(x)), mp5^3(x))) in one launch (round 4: a slice copy + three chained max-pool launches before; kernels_autodrive.hip)
+    tie_acts(c1, cat);   // copies and max-pools commute with a positive scale: s_out == s_in
     if (sppf_pool_ok(c1v, cv, c_)) {
       push_op(sp + ".pyramid", "sppf_pool", [=](hipStream_t st) { return launch_sppf_pool(c1v, cv, c_, st); });
+      ops_.back().writes = {cat};
     } else {   // maps above 512 pixels (other input sizes): the slice copy and the three chained 5x5 max-pools
       push_op(sp + ".cat0", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(c1v, 0, cv, 0, c_, st); });
-      for (int i = 0; i < 3; ++i)
+      ops_.back().writes = {cat};
+      for (int i = 0; i < 3; ++i) {
         push_op(sp + ".maxpool" + std::to_string(i), "maxpool5", [=](hipStream_t st) { return launch_maxpool5(cv, i * c_, cv, (i + 1) * c_, c_, st); });
+        ops_.back().writes = {cat};
+      }
     }
     x = conv_bn(sp + ".cv2", cat, 1, 1, ACT_SILU);
   }
@@ -1187,7 +1222,9 @@ Engine::AdFeatures Engine::build_ad_backbone(const WeightBlob& blob, const std::
     const int c_ = t->Creal / 2;
     Act* y = new_act(cp + ".y", c_, t->H, t->W);
     const ActView tv = t->view(), yv = y->view();
+    tie_acts(t, y);
     push_op(cp + ".split", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(tv, c_, yv, 0, c_, st); });
+    ops_.back().writes = {y};
     const int heads = c_ / 64, dv = c_ / heads, dk = dv / 2;
     Act* qkv = conv_bn(mb + ".conv1.qkv", y, 1, 1, ACT_NONE);
     if (qkv->Creal != heads * (2 * dk + dv)) throw std::runtime_error("attention qkv width mismatch");
@@ -1206,8 +1243,14 @@ Engine::AdFeatures Engine::build_ad_backbone(const WeightBlob& blob, const std::
       const char* ab = dev_option("VP_ATTN_BLOCK");
       ap.qblock = (attention_block_ok(ap) && !(ab && ab[0] == '0')) ? 4 : 0;
     }
-    push_op(mb + ".conv1.attention", ap.qblock ? "attention<q4>" : "attention", [ap](hipStream_t st) { return launch_attention(ap, st); },
-         2.0 * heads * Tn * (double)Tn * (dk + dv));
+    tie_acts(qkv, att);   // out is a convex combination of v rows, vout a copy of v: both keep qkv's exponent (AttnParams)
+    tie_acts(qkv, vv);
+    push_op(mb + ".conv1.attention", ap.qblock ? "attention<q4>" : "attention", [this, ap, qkv](hipStream_t st) {
+      AttnParams q2 = ap;
+      q2.scale = ap.scale * act_mul(qkv) * act_mul(qkv);   // logits from true q and k: 2^(s_q + s_k), exact
+      return launch_attention(q2, st);
+    }, 2.0 * heads * Tn * (double)Tn * (dk + dv));
+    ops_.back().writes = {att, vv};
     // + depthwise 3x3 positional conv of v (BN folded, identity activation)
     Act* pe = new_act(mb + ".conv1.pe", c_, t->H, t->W);
     {
@@ -1223,7 +1266,15 @@ Engine::AdFeatures Engine::build_ad_backbone(const WeightBlob& blob, const std::
       dp.out = pe->view();
       dp.w = dupload(wk);
       dp.b = dupload(bk);
-      push_op(mb + ".conv1.conv1", "dwconv_plain", [dp](hipStream_t st) { return launch_dwconv_plain(dp, st); }, 2.0 * 9 * c_ * Tn);
+      push_op(mb + ".conv1.conv1", "dwconv_plain", [this, dp, vv, att, pe](hipStream_t st) {
+        DwPlainParams q2 = dp;
+        q2.scaled = (act_exp(vv) | act_exp(att) | act_exp(pe)) != 0;
+        q2.in_mul = act_mul(vv);
+        q2.add_mul = act_mul(att);
+        q2.out_mul = act_mul(pe, -1);
+        return launch_dwconv_plain(q2, st);
+      }, 2.0 * 9 * c_ * Tn);
+      ops_.back().writes = {pe};
     }
     // x = y + conv2(attn + pe)
     Act* y1;
@@ -1245,7 +1296,9 @@ Engine::AdFeatures Engine::build_ad_backbone(const WeightBlob& blob, const std::
       y2 = add_conv(mb + ".conv2.1", h, f.w, f.b, f.cout, 1, o);
     }
     const ActView y2v = y2->view();
+    tie_acts(t, y2);
     push_op(cp + ".cat", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(y2v, 0, tv, c_, c_, st); });  // cat((a, y), 1) in place
+    ops_.back().writes = {t};
     // ---- last convolution: stored where the caller wants it (see above).  The alias store relies on the kernels' store guard `channel < Ncols` with
     // Ncols = round_up(c5, 32) = c5 (checked here): a tile wider than c5 computes padding rows but never stores them into the neighbouring slice
     // (tests/test_gpu_autodrive.py::test_autodrive_stream_of_four_frames)
@@ -1301,7 +1354,7 @@ void Engine::build_autodrive(const WeightBlob& blob) {
     head_cat = new_act("head.cat", 2 * c5, H, W);
     const ActView cv = head_cat->view();
     ad_shift_op_ = ops_.size();
-    push_op("head.shift_prev", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(cv, c5, cv, 0, c5, st); });
+    push_op("head.shift_prev", "chan_copy", [=](hipStream_t st) { return launch_chan_copy(cv, c5, cv, 0, c5, st); });   // (VP_ACT_SCALE: both halves share head.cat's exponent)
     return alias_slice("backbone.p5.3.cv2", head_cat, c5, c5);
   });
   ad_place_op_ = feat.p5_op;        // prime_previous() runs the plan up to and including this launch (minus the shift)
@@ -1317,7 +1370,8 @@ void Engine::build_autodrive(const WeightBlob& blob) {
   {
     const ActView hv = h3->view();
     const int cr = h3->Creal;
-    push_op("head.flatten", "act_to_nchw", [=](hipStream_t st) { return launch_act_to_nchw(hv, cr, v0, st); });
+    // the MLP reads fp32 TRUE values: a scaled tensor is multiplied back here (1.0f otherwise)
+    push_op("head.flatten", "act_to_nchw", [this, hv, cr, v0, h3](hipStream_t st) { return launch_act_to_nchw(hv, cr, v0, st, act_mul(h3)); });
   }
   out_c_ = 3;
   out_h_ = 1;

@@ -1,6 +1,7 @@
 // Host-side engine of libvp_hip: weight blob -> folded/packed device weights -> static per-model launch plan
 // (one HIP stream, replayed as a hipGraph) behind the C ABI of include/vp_hip.h.
 #pragma once
+#include <cmath>
 #include <functional>
 #include <map>
 #include <memory>
@@ -57,6 +58,7 @@ struct Act {
   int frames = 1;  // batched encoder: `frames` camera frames stacked along H (H = frames * per-frame height)
   half_t* hi = nullptr;
   half_t* lo = nullptr;
+  int tie = -1;    // VP_ACT_SCALE engines: index of the exponent this tensor is stored with (Engine::act_exp_); tensors that share storage or a copy share it
   ActView view() const { return ActView{hi, lo, H, W, C}; }
   size_t elems() const { return (size_t)H * W * C; }
 };
@@ -70,6 +72,7 @@ struct Op {
   // SURVEY.md 8d's three-op count so whole-frame figures stay comparable across rounds); 0 = same as flops
   double flops_executed = 0;
   std::function<hipError_t(hipStream_t)> run;
+  std::vector<const Act*> writes;  // VP_ACT_SCALE engines: the tensors this launch stores (what vp_calibrate_range measures behind it)
 };
 
 // ConvTranspose2d(k2, s2) [+ 1x1 skip link] -> Conv3x3 multiplied out at load (engine_upconv.cpp): fp64, real (un-padded) channel counts
@@ -219,6 +222,17 @@ class Engine {
   bool host_logits_current() const { return host_logits_valid_; }  // the pinned host logits belong to the LAST pass
   bool split() const { return (precision_ & 15) == 1; }
   bool fp8_weights() const { return (precision_ & 16) != 0; }
+  // VP_ACT_SCALE (creation flag, AutoDrive in the parity mode and the operator entry): every activation tensor t is stored as x * 2^-s_t
+  bool act_scale() const { return (precision_ & 64) != 0; }
+  int act_exp(const Act* a) const { return (a && a->tie >= 0) ? act_exp_[a->tie] : 0; }
+  float act_mul(const Act* a, int sign = 1) const { return std::ldexp(1.0f, sign * act_exp(a)); }   // 2^(sign * s_a)
+  void tie_acts(const Act* a, const Act* b);   // plan time: b's tensors take a's exponent (copies, max-pools, alias slices: s_out == s_in)
+  void set_act_exp(const Act* a, int e);       // operator entry / tests
+  void calibrate_range(int target_log2);
+  void reset_range();
+  std::vector<int> act_scales() const;                  // one per acts() entry
+  void set_act_scales(const int* exps, int n);
+  void stash_previous_frame();                          // AutoDrive: keeps the frame vp_infer_pair primes with, so that a calibration can run the pair again
   // kernel plan target of THIS engine (round 6: a creation flag, VP_PLAN_LATENCY; the process-wide developer option VP_PLAN_TARGET still selects it for
   // every engine created while it is set): the round-4 choices for the CU-time rules of engine_dispatch.cpp
   bool plan_latency() const;
@@ -305,6 +319,14 @@ class Engine {
   unsigned long long hash_bb_ = 0, hash_ctx_ = 0, hash_neck_ = 0;
   std::vector<Act*> feats_;   // backbone taps f0..f4 (kept for shared-prefix engines)
   Act* neck_out_ = nullptr;
+  std::vector<int> act_exp_;        // VP_ACT_SCALE: exponent per tie group (Act::tie)
+  std::vector<char> act_exp_seen_;  // ... measured since the last reset: a later measurement only raises it
+  unsigned* d_absmax_ = nullptr;
+  uint8_t* d_prev_frame_ = nullptr;
+  size_t prev_frame_cap_ = 0;
+  bool prev_frame_stashed_ = false;  // stash_previous_frame() ran and no frame was uploaded since
+  bool prev_frame_valid_ = false;    // the stash is the frame the pair's previous half came from: true only while the upload right behind the stash is the resident frame
+  void exps_changed() { graph_valid_ = false; ++plan_epoch_; }
   size_t ad_shift_op_ = 0, ad_place_op_ = 0;  // AutoDrive: ops_[shift] moves curr->prev features, ops_[place] stores the new ones
   bool ad_primed_ = false;
   std::vector<void*> allocs_;

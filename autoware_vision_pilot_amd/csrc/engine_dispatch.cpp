@@ -130,6 +130,23 @@ void Engine::push_conv_op(const std::string& name, const Act* in, const PackedCo
   const bool sp = split();
   Op op;
   op.name = name;
+  // VP_ACT_SCALE: the launch reads its tensors' exponents when it RUNS (vp_calibrate_range / vp_set_act_scales change them and invalidate the graph).  With
+  // every exponent 0 the block is the unflagged engine's, bit for bit; otherwise `scaled` sends it to the all-runtime epilogue (conv_epilogue.hpp).
+  const Act* res_act = o.res;
+  auto with_exps = [this, in, res_act, out](ConvGemmParams q) {
+    const int si = act_exp(in), sr = act_exp(res_act), so = act_exp(out);
+    q.scaled = (si | sr | so) != 0;
+    q.in_mul = std::ldexp(1.0f, si);
+    q.res_mul = std::ldexp(1.0f, sr);
+    q.out_mul = std::ldexp(1.0f, -so);
+    return q;
+  };
+  if (act_scale()) {
+    const bool halo_plain = tile >= 100 && tile - 100 <= 5 && !(tile == 104 && o.tile < 0 && head_conv_supported(p));
+    if (!(halo_plain || tile < 5) || store_mode != STORE_NHWC || o.in2 || fuse_decode || !out || (o.tile < 0 && tile < 100 && convt_rs_supported(p, sp)))
+      throw std::invalid_argument("VP_ACT_SCALE: only the generic GEMM kernel and the halo kernel's tiles 0 - 5 (NHWC store) carry the activation scale: " + name);
+    op.writes = {out};
+  }
   if (pc.nsplit > 1) op.launch = "nsplit=" + std::to_string(pc.nsplit);   // the tag only says "+splitk"
   op.flops = 2.0 * M * (double)cout_real * (store_mode == STORE_SHUFFLE2 ? 4 : 1) * in->Creal * ks * ks;
   const double esz = sp ? 4.0 : 2.0;
@@ -226,6 +243,8 @@ void Engine::push_conv_op(const std::string& name, const Act* in, const PackedCo
         q.decode_mode = decode_mode_;  // vp_set_decode_mode may change it between frames (it invalidates the graph)
         return launch_conv3x3_halo(q, ht, sp, st);
       };
+    } else if (act_scale()) {
+      op.run = [p, ht, sp, with_exps](hipStream_t st) { return launch_conv3x3_halo(with_exps(p), ht, sp, st); };
     } else {
       op.run = [p, ht, sp](hipStream_t st) { return launch_conv3x3_halo(p, ht, sp, st); };
     }
@@ -260,6 +279,8 @@ void Engine::push_conv_op(const std::string& name, const Act* in, const PackedCo
         q.decode_mode = decode_mode_;
         return launch_conv_gemm(q, tile, bk, sp, st);
       };
+    } else if (act_scale()) {
+      op.run = [p, tile, bk, sp, with_exps](hipStream_t st) { return launch_conv_gemm(with_exps(p), tile, bk, sp, st); };
     } else {
       op.run = [p, tile, bk, sp](hipStream_t st) { return launch_conv_gemm(p, tile, bk, sp, st); };
     }

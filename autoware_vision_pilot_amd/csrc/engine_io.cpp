@@ -2,6 +2,7 @@
 // capture and replay (single engine and base + shared heads), output fetch and the range probe's verdict, resizes, visualisation, timers.
 #include "engine_internal.hpp"
 
+#include <climits>
 #include <cstdint>
 #include <mutex>
 #include <utility>
@@ -242,6 +243,8 @@ void Engine::upload_frame(const uint8_t* frame, int h, int w, int stride, int in
     throw std::invalid_argument("VP_AUTOSTEER: the input frame must be 512 x 1024 (height x width), got " + std::to_string(h) + " x " + std::to_string(w));
   if (index < 0 || index >= frames_) throw std::invalid_argument("frame index out of range");
   VP_HIP_CHECK(hipSetDevice(gpu_));
+  prev_frame_valid_ = prev_frame_stashed_;   // VP_ACT_SCALE: a stashed previous frame belongs to the upload right behind it only
+  prev_frame_stashed_ = false;
   const size_t need = (size_t)h * stride;
   if ((h != frame_h_ || w != frame_w_ || stride != frame_stride_) && frames_ > 1 && index != 0 && frame_h_ != 0)
     throw std::invalid_argument("batched encoder: all frames of a pass share one geometry (upload slot 0 first to change it)");
@@ -737,12 +740,170 @@ void Engine::read_act(int i, float* dst) {
   float* d = nullptr;
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
   VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d), n * sizeof(float)));
-  hipError_t e = launch_act_to_nchw(a.view(), a.Creal, d, stream_);
+  hipError_t e = launch_act_to_nchw(a.view(), a.Creal, d, stream_, act_mul(&a));   // true values (VP_ACT_SCALE: times 2^s of the tensor)
   if (e == hipSuccess) e = hipStreamSynchronize(stream_);
   if (e == hipSuccess) e = hipMemcpyAsync(dst, d, n * sizeof(float), hipMemcpyDeviceToHost, stream_);   // (not the legacy stream: engine.hpp copy_h2d)
   if (e == hipSuccess) e = hipStreamSynchronize(stream_);
   hipFree(d);
   VP_HIP_CHECK(e);
+}
+
+// ------------------------------------------------------------------------------------------------ VP_ACT_SCALE
+// Per-tensor power-of-two activation scale (DESIGN.md section 4 "Range").  A flagged engine stores tensor t as x * 2^-s_t; the exponents live in
+// act_exp_ (one per TIE GROUP: tensors that share storage or are copies / max-pools of each other), every launch reads them when it runs.
+void Engine::tie_acts(const Act* a, const Act* b) {
+  if (!act_scale() || !a || !b || a->tie == b->tie) return;
+  const int from = b->tie, to = a->tie;
+  if (act_exp_[from] != act_exp_[to]) throw std::invalid_argument("tied tensors carry different exponents: " + a->name + ", " + b->name);
+  for (auto& t : acts_)
+    if (t->tie == from) t->tie = to;
+}
+
+void Engine::set_act_exp(const Act* a, int e) {
+  if (!act_scale() || !a || a->tie < 0) throw std::invalid_argument("VP_ACT_SCALE: not a tensor of a flagged engine");
+  if (e < -60 || e > 60) throw std::invalid_argument("VP_ACT_SCALE: exponent out of range (-60 .. 60)");
+  act_exp_[a->tie] = e;
+  exps_changed();
+}
+
+std::vector<int> Engine::act_scales() const {
+  std::vector<int> v(acts_.size(), 0);
+  for (size_t i = 0; i < acts_.size(); ++i) v[i] = act_exp(acts_[i].get());
+  return v;
+}
+
+void Engine::set_act_scales(const int* exps, int n) {
+  if (!act_scale()) throw std::invalid_argument("vp_set_act_scales: the engine was not created with VP_ACT_SCALE");
+  if (!exps || n != (int)acts_.size()) throw std::invalid_argument("vp_set_act_scales: the table needs one exponent per tensor (" + std::to_string(acts_.size()) + ")");
+  std::vector<int> grp(act_exp_.size(), INT_MIN);
+  for (int i = 0; i < n; ++i) {
+    const Act& a = *acts_[i];
+    if (exps[i] < -60 || exps[i] > 60) throw std::invalid_argument("vp_set_act_scales: exponent out of range (-60 .. 60): " + a.name);
+    if (grp[a.tie] != INT_MIN && grp[a.tie] != exps[i]) throw std::invalid_argument("vp_set_act_scales: tied tensors disagree at '" + a.name + "' (tensors that share storage share one exponent)");
+    grp[a.tie] = exps[i];
+  }
+  for (size_t g = 0; g < grp.size(); ++g)
+    if (grp[g] != INT_MIN) {
+      act_exp_[g] = grp[g];
+      act_exp_seen_[g] = 1;   // an installed exponent counts as measured: a later calibration only raises it
+    }
+  ad_primed_ = false;   // features parked under the old exponents are not carried over
+  exps_changed();
+}
+
+void Engine::reset_range() {
+  if (!act_scale()) throw std::invalid_argument("vp_reset_range: the engine was not created with VP_ACT_SCALE");
+  std::fill(act_exp_.begin(), act_exp_.end(), 0);
+  std::fill(act_exp_seen_.begin(), act_exp_seen_.end(), 0);
+  ad_primed_ = false;
+  exps_changed();
+}
+
+void Engine::stash_previous_frame() {
+  if (!act_scale() || !d_frame_ || input_is_tensor_) return;
+  const size_t need = (size_t)frame_h_ * frame_stride_;
+  if (need > prev_frame_cap_) {
+    VP_HIP_CHECK(hipStreamSynchronize(stream_));
+    if (d_prev_frame_) dfree(d_prev_frame_);
+    d_prev_frame_ = static_cast<uint8_t*>(dalloc(std::max(need, frame_cap_), false));
+    prev_frame_cap_ = std::max(need, frame_cap_);
+  }
+  VP_HIP_CHECK(hipMemcpyAsync(d_prev_frame_, d_frame_, need, hipMemcpyDeviceToDevice, stream_));
+  prev_frame_stashed_ = true;   // upload_frame turns it into prev_frame_valid_ for the ONE frame uploaded next (the pair's current half)
+}
+
+// Runs the plan eagerly, launch by launch, on the resident frame (AutoDrive: on the frame vp_infer_pair primed with first, then on the current one), measures
+// every tensor a launch stores (act_absmax_kernel) and moves its exponent so that the stored abs-max lies in [2^(target - 1), 2^target).  The first
+// measurement of a tensor since vp_reset_range sets the exponent, later ones only raise it: calibrating on several frames gives the per-tensor maximum.
+void Engine::calibrate_range(int target_log2) {
+  if (!act_scale() || kind_ != 4) throw std::invalid_argument("vp_calibrate_range: engines created with VP_ACT_SCALE only");
+  if (target_log2 == 0) target_log2 = 12;
+  if (target_log2 < 1 || target_log2 > 15) throw std::invalid_argument("vp_calibrate_range: target_log2 is 1 .. 15 (0 = the default, 12)");
+  if (!input_is_tensor_ && !d_frame_) throw std::runtime_error("no frame resident: call vp_upload_frame / vp_infer_pair first");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  if (!d_absmax_) d_absmax_ = static_cast<unsigned*>(dalloc(2 * sizeof(unsigned)));
+  const size_t first = input_is_tensor_ ? first_net_op_ : 0;
+  const int head_tie = ops_[ad_place_op_].writes.empty() ? -1 : ops_[ad_place_op_].writes[0]->tie;
+  std::vector<int> raises(act_exp_.size(), 0), lower(act_exp_.size(), INT_MIN);
+  for (size_t g = 0; g < lower.size(); ++g)
+    if (act_exp_seen_[g]) lower[g] = act_exp_[g];
+  auto launch = [&](size_t i) {
+    const hipError_t e = ops_[i].run(stream_);
+    if (e != hipSuccess) throw std::runtime_error("launch failed in layer '" + ops_[i].name + "': " + hipGetErrorString(e));
+  };
+  // false: the exponent of the tensor that carries the previous frame's features (head.cat) moved behind the shift -- the round starts over
+  auto pass = [&](size_t begin, size_t end, bool prime) -> bool {
+    for (size_t i = begin; i < end; ++i) {
+      if (prime && i == ad_shift_op_) continue;
+      launch(i);
+      for (const Act* a : ops_[i].writes) {
+        const int g = a->tie;
+        if (g < 0) continue;
+        bool restart = false;
+        for (;;) {
+          unsigned r[2] = {0u, 0u};
+          fill_zero(d_absmax_, sizeof(r));
+          VP_HIP_CHECK(launch_act_absmax(a->hi, a->lo, a->Creal, a->H, a->W, a->C, d_absmax_, stream_));
+          copy_d2h(r, d_absmax_, sizeof(r));
+          float amax;
+          std::memcpy(&amax, &r[0], sizeof(float));
+          const bool bad = r[1] != 0u;
+          int want = act_exp_[g];
+          if (bad) {
+            if (++raises[g] > 3) throw RangeError("vp_calibrate_range: tensor '" + a->name + "' still holds non-finite values after its exponent was raised 3 times by 16");
+            want += 16;
+          } else if (amax == 0.0f) {
+            break;   // an all-zero tensor keeps its exponent
+          } else {
+            int e2 = 0;
+            std::frexp(amax, &e2);   // stored abs-max in [2^(e2 - 1), 2^e2)
+            want = std::max(lower[g], act_exp_[g] + e2 - target_log2);
+            lower[g] = want;
+            act_exp_seen_[g] = 1;
+          }
+          if (want == act_exp_[g]) break;
+          act_exp_[g] = want;
+          // head.cat also holds the PREVIOUS frame's features, stored under the old exponent: settle the exponent on this frame first (so that the
+          // previous frame's smaller values cannot take it back), then start the round over
+          if (!prime && g == head_tie && i >= ad_shift_op_) restart = true;
+          for (size_t j = begin; j <= i; ++j) {   // every launch so far that writes the tensor stores it again
+            if (j == ad_shift_op_) continue;
+            bool writes = false;
+            for (const Act* w : ops_[j].writes) writes |= w->tie == g;
+            if (writes) launch(j);
+          }
+          if (!bad) break;
+        }
+        if (restart) return false;
+      }
+    }
+    return true;
+  };
+  const bool pair = prev_frame_valid_ && !input_is_tensor_ && prev_frame_cap_ >= (size_t)frame_h_ * frame_stride_;
+  bool done = false;
+  try {
+    for (int round = 0; round < 16 && !done; ++round) {
+      if (pair) std::swap(d_frame_, d_prev_frame_);
+      try {
+        pass(first, ad_place_op_ + 1, true);   // the previous frame (or the resident one again): features only
+      } catch (...) {
+        if (pair) std::swap(d_frame_, d_prev_frame_);
+        throw;
+      }
+      if (pair) std::swap(d_frame_, d_prev_frame_);
+      done = pass(first, ops_.size(), false);
+    }
+  } catch (...) {
+    hipStreamSynchronize(stream_);
+    ad_primed_ = false;
+    exps_changed();
+    throw;
+  }
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  ad_primed_ = done;   // the current frame's features sit in the "current" slot under the final exponents
+  exps_changed();
+  if (!done) throw RangeError("vp_calibrate_range: the exponents did not settle");
 }
 
 }  // namespace vp

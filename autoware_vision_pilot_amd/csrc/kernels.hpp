@@ -49,6 +49,8 @@ struct StemParams {
   ActView out;      // C = 32
   unsigned long long* zero;  // optional: the squeeze-excite accumulators of the frame, zeroed here (every block's pool comes later)
   size_t zero_n;
+  int scaled;        // VP_ACT_SCALE: != 0 -> the result is stored times out_mul (2^-s_out); 0: out_mul is not read
+  float out_mul;
 };
 
 struct DwParams {
@@ -184,6 +186,8 @@ struct CtxConv1Params {
   const float* b;    // [C]
   ActView out;
   int act;           // ACT_GELU (scene_context.py:46-47) or ACT_SILU (CTX.ctx0, common_layers.py:216-217)
+  int scaled;        // VP_ACT_SCALE: != 0 -> the result is stored times out_mul (2^-s_out); 0: out_mul is not read
+  float out_mul;
 };
 
 // Round 5: the matvec that BUILDS the one-channel map and the 3x3 convolution that reads it, in one launch (ctx_exp_conv1_kernel):
@@ -360,7 +364,11 @@ hipError_t launch_depth_colorize(const float* src, size_t n, const unsigned* mm,
 hipError_t launch_viz_blend(const uint8_t* mask, int mw, const int* ytab, const int* xtab, const uint8_t* frame, int stride, int oh, int ow,
                             const uint8_t* lut, int frame_is_rgb, uint8_t* dst, hipStream_t st);
 hipError_t launch_nchw_to_act(const float* src, int Creal, const ActView& a, hipStream_t st);
-hipError_t launch_act_to_nchw(const ActView& a, int Creal, float* dst, hipStream_t st);
+hipError_t launch_act_to_nchw(const ActView& a, int Creal, float* dst, hipStream_t st, float mul = 1.0f);  // dst = (hi + lo) * mul (VP_ACT_SCALE: 2^s of the tensor)
+// VP_ACT_SCALE calibration (kernels_misc.hip act_absmax_kernel): result[0] = bit pattern of max |hi + lo| (fp32, non-finite elements left out) over the
+// c real channels of an h x w tensor with channel pitch c_pitch (c_pitch and the plane pointers multiples of 8 elements), result[1] = count of
+// non-finite elements.  Integer max / add only: the same bits whatever order the workgroups finish in.  The caller zeroes result[0..2) first.
+hipError_t launch_act_absmax(const half_t* hi, const half_t* lo, int c, int h, int w, int c_pitch, unsigned* result, hipStream_t st);
 
 // ---- AutoDrive blocks (kernels_autodrive.hip)
 // channel-slice copy: dst[pix][dst_off + c] = src[pix][src_off + c], c < nch (torch.cat / split / chunk along C)
@@ -377,6 +385,8 @@ struct AttnParams {
   int heads, dk, dv;
   float scale;
   int qblock;    // 4: four query tokens per workgroup (attention_block_kernel: dk = 32, dv = 64, <= 1760 tokens); 0: one workgroup per query token
+  // VP_ACT_SCALE: qkv, out and vout carry ONE exponent s (tied at plan time): v -> vout is a copy and out a convex combination of v rows, so both are
+  // homogeneous in v; the logits need true q . k, which the engine folds into `scale` (scale * 2^(2 s), exact) when it launches -- no device change
 };
 bool attention_block_ok(const AttnParams& p);
 hipError_t launch_attention(const AttnParams& p, hipStream_t st);
@@ -386,6 +396,9 @@ struct DwPlainParams {
   const float* w;    // [9][C]
   const float* b;    // [C]
   int act;           // ActFn applied before the add; 0 (ACT_NONE) = identity
+  // VP_ACT_SCALE: scaled != 0 -> in is read times in_mul (2^s_in), add times add_mul (2^s_add), the result stored times out_mul (2^-s_out); 0: not read
+  int scaled;
+  float in_mul, add_mul, out_mul;
 };
 hipError_t launch_dwconv_plain(const DwPlainParams& p, hipStream_t st);
 

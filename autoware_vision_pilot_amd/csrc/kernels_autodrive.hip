@@ -317,6 +317,10 @@ __global__ __launch_bounds__(256) void dwconv_plain_kernel(const DwPlainParams p
       if ((unsigned)iy >= (unsigned)p.in.H || (unsigned)ix >= (unsigned)p.in.W) continue;
       float v[8];
       load8(p.in, ((size_t)iy * p.in.W + ix) * p.in.C + cg * 8, v);
+      if (p.scaled) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] *= p.in_mul;
+      }
       const float* wk = p.w + (size_t)(ky * 3 + kx) * p.in.C + cg * 8;
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[i] = fmaf(v[i], wk[i], acc[i]);
@@ -328,8 +332,16 @@ __global__ __launch_bounds__(256) void dwconv_plain_kernel(const DwPlainParams p
   if (p.add.hi) {
     float a[8];
     load8(p.add, (size_t)pix * p.add.C + cg * 8, a);
+    if (p.scaled) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) a[i] *= p.add_mul;
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] += a[i];
+  }
+  if (p.scaled) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] *= p.out_mul;
   }
   store8(p.out, (size_t)pix * p.out.C + cg * 8, acc);
 }

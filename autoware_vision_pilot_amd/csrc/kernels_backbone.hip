@@ -55,6 +55,10 @@ __global__ __launch_bounds__(256) void stem_kernel(const StemParams p) {
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = silu_f16(acc[i]);  // x * rcp(1 + exp2(-x log2 e)) in fp32 (v_exp_f32 / v_rcp_f32, |error| <= 3e-7 |silu|): every mode since round 3 -- libm's expf + IEEE division cost 3-9 us per launch (tools/mbf_check.hip)
+  if (p.scaled) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] *= p.out_mul;
+  }
   store8(p.out, (size_t)pix * 32 + g * 8, acc);
 }
 

@@ -101,6 +101,10 @@ __global__ __launch_bounds__(256) void ctx_conv1_kernel(const CtxConv1Params p) 
     }
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = p.act == ACT_GELU ? gelu_exact(acc[i]) : apply_act(acc[i], p.act);
+  if (p.scaled) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] *= p.out_mul;
+  }
   store8(p.out, (size_t)pix * p.out.C + cg * 8, acc);
 }
 
@@ -438,7 +442,7 @@ __global__ __launch_bounds__(256) void nchw_to_act_kernel(const float* src, int 
   a.hi[t] = h;
   if (a.lo) a.lo[t] = (half_t)(v - (float)h);
 }
-__global__ __launch_bounds__(256) void act_to_nchw_kernel(ActView a, int Creal, float* dst) {
+__global__ __launch_bounds__(256) void act_to_nchw_kernel(ActView a, int Creal, float* dst, float mul) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   const int HW = a.H * a.W;
   if (t >= (long long)HW * Creal) return;
@@ -446,7 +450,39 @@ __global__ __launch_bounds__(256) void act_to_nchw_kernel(ActView a, int Creal, 
   const size_t off = (size_t)pix * a.C + c;
   float v = (float)a.hi[off];
   if (a.lo) v += (float)a.lo[off];
-  dst[t] = v;
+  dst[t] = v * mul;   // mul = 1 (exact) unless the tensor is stored scaled (VP_ACT_SCALE)
+}
+
+// VP_ACT_SCALE calibration: max |hi + lo| and the count of non-finite elements of one tensor.  A thread reads one 16-byte octet per plane; octets that
+// straddle the real-channel count are masked per element (the padding of an alias slice belongs to its neighbour).  |x| >= 0 as fp32 orders like its bit
+// pattern, so the maximum is an INTEGER max (wave shuffle, then one atomicMax per wave) and the count an integer add: order-independent, no float atomics.
+__global__ __launch_bounds__(256) void act_absmax_kernel(const half_t* hi, const half_t* lo, int c, long long npix, int c_pitch, unsigned* result) {
+  const int CG = (c + 7) >> 3;
+  unsigned best = 0u, bad = 0u;
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < npix * CG; t += (long long)gridDim.x * 256) {
+    const int cg = (int)(t % CG);
+    const size_t off = (size_t)(t / CG) * c_pitch + cg * 8;
+    const h8_t h = *reinterpret_cast<const h8_t*>(hi + off);
+    h8_t l = {};
+    if (lo) l = *reinterpret_cast<const h8_t*>(lo + off);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (cg * 8 + i >= c) continue;
+      const unsigned u = __float_as_uint((float)h[i] + (float)l[i]) & 0x7FFFFFFFu;
+      if (u >= 0x7F800000u) ++bad;
+      else best = u > best ? u : best;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned b2 = __shfl_xor(best, o);
+    best = b2 > best ? b2 : best;
+    bad += __shfl_xor(bad, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (best) atomicMax(result, best);
+    if (bad) atomicAdd(result + 1, bad);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------- launchers
@@ -525,8 +561,15 @@ hipError_t launch_resize_bilinear_f32(const float* src, int sw, const int* yi, c
 hipError_t launch_nchw_to_act(const float* src, int Creal, const ActView& a, hipStream_t st) {
   VP_LAUNCH(nchw_to_act_kernel, dim3(nblk((long long)a.H * a.W * a.C)), dim3(256), 0, st, src, Creal, a);
 }
-hipError_t launch_act_to_nchw(const ActView& a, int Creal, float* dst, hipStream_t st) {
-  VP_LAUNCH(act_to_nchw_kernel, dim3(nblk((long long)a.H * a.W * Creal)), dim3(256), 0, st, a, Creal, dst);
+hipError_t launch_act_absmax(const half_t* hi, const half_t* lo, int c, int h, int w, int c_pitch, unsigned* result, hipStream_t st) {
+  if (!hi || !result || c < 1 || h < 1 || w < 1 || c_pitch < ((c + 7) & ~7) || (c_pitch & 7) || ((reinterpret_cast<uintptr_t>(hi) | reinterpret_cast<uintptr_t>(lo)) & 15))
+    return hipErrorInvalidValue;
+  const long long n = (long long)h * w * ((c + 7) >> 3);
+  const unsigned blocks = n > 1024ll * 256 ? 1024u : (unsigned)((n + 255) / 256);
+  VP_LAUNCH(act_absmax_kernel, dim3(blocks), dim3(256), 0, st, hi, lo, c, (long long)h * w, c_pitch, result);
+}
+hipError_t launch_act_to_nchw(const ActView& a, int Creal, float* dst, hipStream_t st, float mul) {
+  VP_LAUNCH(act_to_nchw_kernel, dim3(nblk((long long)a.H * a.W * Creal)), dim3(256), 0, st, a, Creal, dst, mul);
 }
 
 }  // namespace vp

@@ -392,6 +392,7 @@ int vp_set_multi_fork(vp_engine* base, int enable) {
 int vp_infer_pair(vp_engine* e, const uint8_t* prev, const uint8_t* curr, int h, int w, int stride_bytes) {
   return guarded(e, [&](vp::Engine& g) {
     g.upload_frame(prev, h, w, stride_bytes);
+    g.stash_previous_frame();   // VP_ACT_SCALE engines keep it for vp_calibrate_range; a no-op otherwise
     g.prime_previous();
     g.upload_frame(curr, h, w, stride_bytes);
     g.enqueue();
@@ -604,6 +605,23 @@ int vp_tensor_read(vp_engine* e, int i, float* dst) {
   return guarded(e, [&](vp::Engine& g) { g.read_act(i, dst); });
 }
 
+// ---- VP_ACT_SCALE: per-tensor power-of-two activation scale (engine_io.cpp)
+int vp_calibrate_range(vp_engine* e, int target_log2) {
+  return guarded(e, [&](vp::Engine& g) { g.calibrate_range(target_log2); });
+}
+int vp_reset_range(vp_engine* e) {
+  return guarded(e, [&](vp::Engine& g) { g.reset_range(); });
+}
+int vp_act_scales(const vp_engine* e, int* exps, int cap) {
+  if (!e || !e->impl || (cap > 0 && !exps)) return VP_ERR_ARG;
+  const std::vector<int> v = e->impl->act_scales();
+  for (int i = 0; i < cap && i < (int)v.size(); ++i) exps[i] = v[i];
+  return (int)v.size();
+}
+int vp_set_act_scales(vp_engine* e, const int* exps, int n) {
+  return guarded(e, [&](vp::Engine& g) { g.set_act_scales(exps, n); });
+}
+
 int vp_op_conv2d(int gpu_id, int precision, int mode, const float* in, int cin, int h, int w, const float* weight, const float* bias,
                  int cout, int ks, int act, int res_mode, const float* res, int tile, int bk, int nsplit, float* out, char* err,
                  size_t err_len) {
@@ -791,6 +809,64 @@ int vp_op_dwconv3x3(int gpu_id, int precision, const float* in, int c, int h, in
     }
     VP_HIP_CHECK(vp::launch_dwconv_plain(dp, g.stream()));
     read_planes_chw(g, to, out_hi, out_lo);
+  });
+}
+
+// ---- single-operator entries of the VP_ACT_SCALE mechanism (unit tests)
+int vp_op_absmax(int gpu_id, const uint16_t* hi, const uint16_t* lo, int c, int h, int w, int c_pitch, float* absmax, unsigned* nonfinite, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!hi || !absmax || !nonfinite || c < 1 || h < 1 || w < 1 || c_pitch < ((c + 7) & ~7) || (c_pitch & 7) || (long long)h * w * c_pitch > (1ll << 28))
+      throw std::invalid_argument("bad argument (c_pitch: a multiple of 8, at least c rounded up to 8)");
+    vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
+    const size_t n = (size_t)h * w * c_pitch;
+    vp::half_t* dh = reinterpret_cast<vp::half_t*>(g.alloc_f32((n + 1) / 2));
+    vp::half_t* dl = lo ? reinterpret_cast<vp::half_t*>(g.alloc_f32((n + 1) / 2)) : nullptr;
+    unsigned* dr = reinterpret_cast<unsigned*>(g.alloc_f32(2));   // zeroed
+    g.copy_h2d(dh, hi, n * sizeof(uint16_t));
+    if (lo) g.copy_h2d(dl, lo, n * sizeof(uint16_t));
+    VP_HIP_CHECK(vp::launch_act_absmax(dh, dl, c, h, w, c_pitch, dr, g.stream()));
+    unsigned r[2];
+    g.copy_d2h(r, dr, sizeof(r));
+    std::memcpy(absmax, &r[0], sizeof(float));
+    *nonfinite = r[1];
+  });
+}
+
+int vp_op_conv2d_scaled(int gpu_id, int precision, int mode, const float* in, int cin, int h, int w, const float* weight, const float* bias, int cout, int ks,
+                        int act, int res_mode, const float* res, int tile, int bk, int nsplit, int in_exp, int res_exp, int out_exp, uint16_t* out_hi,
+                        uint16_t* out_lo, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!in || !weight || !bias || !out_hi || cin < 1 || cout < 1 || h < 1 || w < 1 || (long long)h * w > (1 << 20)) throw std::invalid_argument("bad argument");
+    if (mode != 0) throw std::invalid_argument("vp_op_conv2d_scaled: mode 0 (Conv2d) only");
+    vp::Engine g(-1, nullptr, precision | VP_ACT_SCALE, gpu_id);
+    // the planes hold x * 2^-s: the host scales the true-valued arguments (exact) before they are split
+    auto scaled_copy = [](const float* src, size_t n, int e) {
+      std::vector<float> v(src, src + n);
+      for (float& x : v) x = std::ldexp(x, -e);
+      return v;
+    };
+    vp::Act* a = g.new_act("in", cin, h, w);
+    g.upload_act(a, scaled_copy(in, (size_t)cin * h * w, in_exp).data());
+    g.set_act_exp(a, in_exp);
+    vp::ConvOpts o;
+    o.act = act;
+    o.tile = tile;
+    o.bk = bk;
+    o.nsplit = nsplit;
+    if (res_mode != 0) {
+      if (!res) throw std::invalid_argument("res_mode set but res is null");
+      vp::Act* r = g.new_act("res", cout, h, w);
+      g.upload_act(r, scaled_copy(res, (size_t)cout * h * w, res_exp).data());
+      g.set_act_exp(r, res_exp);
+      o.res_mode = res_mode;
+      o.res = r;
+    }
+    const size_t wn = (size_t)cin * cout * ks * ks;
+    vp::Act* y = g.add_conv("op", a, std::vector<float>(weight, weight + wn), std::vector<float>(bias, bias + cout), cout, ks, o);
+    g.set_act_exp(y, out_exp);
+    g.run_eager();
+    g.sync();
+    read_planes_chw(g, y, out_hi, out_lo);
   });
 }
 

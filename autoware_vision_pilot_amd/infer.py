@@ -177,22 +177,46 @@ class AutoDriveInfer:
     Image.resize((1024, 512), Image.BILINEAR), bit-exact against Pillow, RGB planes, to_tensor + ImageNet normalisation,
     video_visualization.py:29-33) -> (d_norm, curvature, flag_logit);
     ``step(frame)`` is the streaming form (pairs each frame with the previous one).  ``frames_are_bgr`` matches
-    OpenCV captures.  ``weights_fp8`` selects the per-channel e4m3 weight format of BASELINE configs[4]."""
+    OpenCV captures.  ``weights_fp8`` selects the per-channel e4m3 weight format of BASELINE configs[4].  ``act_scale`` (parity mode only) stores every
+    activation tensor with a power-of-two scale of its own and calibrates the scales on the first pair it sees (vp_hip.h VP_ACT_SCALE) -- the first
+    ``forward``, or the second ``step`` (the first frame of a stream has no pair yet and runs uncalibrated): a frame whose activations leave the fp16
+    range then gets an answer instead of VpRangeError."""
 
     D_MAX_M = 150.0
 
-    def __init__(self, checkpoint_path="", precision="fp16", gpu_id=0, weights_fp8=False, frames_are_bgr=True):
+    def __init__(self, checkpoint_path="", precision="fp16", gpu_id=0, weights_fp8=False, frames_are_bgr=True, act_scale=False):
         if checkpoint_path is None or len(checkpoint_path) == 0:
             raise ValueError("No path to checkpiont file provided in class initialization")
-        self.model = _lib.Engine("autodrive", checkpoint_path, precision=precision, gpu_id=gpu_id, weights_fp8=weights_fp8)
+        self.model = _lib.Engine("autodrive", checkpoint_path, precision=precision, gpu_id=gpu_id, weights_fp8=weights_fp8, act_scale=act_scale)
         self.model.set_input_format(_lib.VP_BGR8 if frames_are_bgr else _lib.VP_RGB8, _lib.VP_PLANES_RGB)
+        self._calibrate = bool(act_scale)
+        self._first = None
+
+    def _calibrate_on(self, image_prev, image_curr):
+        """first pair: run it (the uncalibrated pass may be refused), calibrate on it; the caller then answers it"""
+        self._calibrate = False
+        self._first = None
+        try:
+            self.model.infer_pair(np.asarray(image_prev), np.asarray(image_curr))
+        except _lib.VpRangeError:
+            pass
+        self.model.calibrate_range()
 
     def forward(self, image_prev, image_curr):
+        if self._calibrate:
+            self._calibrate_on(image_prev, image_curr)
         self.model.infer_pair(np.asarray(image_prev), np.asarray(image_curr))
         d, c, f = self.model.logits().reshape(3)
         return float(d), float(c), float(f)
 
     def step(self, image):
+        if self._calibrate:
+            if self._first is None:
+                self._first = np.array(image, copy=True)   # no pair yet: this frame runs uncalibrated (paired with itself, as every first frame)
+            else:
+                prev = self._first
+                self._calibrate_on(prev, image)
+                return self.forward(prev, image)            # the stream goes on behind it: the next step pairs with this frame
         self.model.infer(np.asarray(image))
         d, c, f = self.model.logits().reshape(3)
         return float(d), float(c), float(f)

@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libvp_hip.so")
 VP_SCENESEG, VP_SCENE3D, VP_DOMAINSEG, VP_EGOLANES, VP_AUTODRIVE, VP_AUTOSPEED, VP_AUTOSTEER = 0, 1, 2, 3, 4, 5, 6
 VP_WEIGHTS_FP8 = 16
 VP_PLAN_LATENCY = 32  # creation flag: this engine's kernel plan targets one network on one camera, one frame at a time (vp_hip.h)
+VP_ACT_SCALE = 64  # creation flag: per-tensor power-of-two activation scale (AutoDrive, parity mode; vp_hip.h)
 VP_FP16, VP_FP16X3 = 0, 1
 VP_BGR8, VP_RGB8 = 0, 1
 VP_PLANES_BGR, VP_PLANES_RGB = 0, 1
@@ -93,6 +94,13 @@ _SIGS = {
     "vp_tensor_count": (C.c_int, [_P]),
     "vp_tensor_info": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vp_tensor_read": (C.c_int, [_P, C.c_int, _P]),
+    "vp_calibrate_range": (C.c_int, [_P, C.c_int]),
+    "vp_reset_range": (C.c_int, [_P]),
+    "vp_act_scales": (C.c_int, [_P, _P, C.c_int]),
+    "vp_set_act_scales": (C.c_int, [_P, _P, C.c_int]),
+    "vp_op_absmax": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint), C.c_char_p, C.c_size_t]),
+    "vp_op_conv2d_scaled": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_char_p, C.c_size_t]),
     "vp_op_conv2d": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P,
                                C.c_int, C.c_int, C.c_int, _P, C.c_char_p, C.c_size_t]),
     "vp_compose_upconv": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_char_p, C.c_size_t]),
@@ -273,7 +281,7 @@ def convert_onnx(onnx_path, vpw_path):
 class Engine:
     """Thin RAII wrapper over a vp_engine handle."""
 
-    def __init__(self, kind, weights, precision="fp16", gpu_id=0, base=None, weights_fp8=False, frames=1, frame_index=None, plan_latency=False):
+    def __init__(self, kind, weights, precision="fp16", gpu_id=0, base=None, weights_fp8=False, frames=1, frame_index=None, plan_latency=False, act_scale=False):
         """base: another Engine -> shared-prefix engine (vp_create_shared): reuses the base engine's backbone (and
         context + neck when their parameters are identical) on the frame the base last processed.
         frames > 1: batched encoder (vp_create_batched) -- preprocess + backbone of `frames` cameras per pass, no head;
@@ -288,6 +296,8 @@ class Engine:
             pr |= VP_WEIGHTS_FP8
         if plan_latency:
             pr |= VP_PLAN_LATENCY
+        if act_scale:
+            pr |= VP_ACT_SCALE
         self._base = base  # keeps the base engine alive as long as this one
         path = None if isinstance(weights, (bytes, bytearray, memoryview, np.ndarray)) else (os.fsencode(weights) if weights else b"")
         if frames != 1 or frame_index is not None:
@@ -397,6 +407,25 @@ class Engine:
         if a.shape != b.shape or a.ndim != 3 or a.shape[2] != 3:
             raise ValueError("frames must be two HxWx3 uint8 arrays of the same shape")
         self._ck(self._lib.vp_infer_pair(self._h, _ptr(a), _ptr(b), a.shape[0], a.shape[1], a.strides[0]))
+
+    # ---- per-tensor activation scale (engines created with act_scale=True)
+    def calibrate_range(self, target_log2=0):
+        """vp_calibrate_range over the resident frame(s): the pair of the last infer_pair (whether or not it raised VpRangeError), or the uploaded frame."""
+        self._ck(self._lib.vp_calibrate_range(self._h, int(target_log2)))
+
+    def reset_range(self):
+        self._ck(self._lib.vp_reset_range(self._h))
+
+    def act_scales(self):
+        """One exponent per tensors() entry: tensor t is stored as x * 2^-s_t."""
+        n = self._ck(self._lib.vp_tensor_count(self._h))
+        out = np.zeros(n, dtype=np.int32)
+        self._ck(self._lib.vp_act_scales(self._h, _ptr(out), n))
+        return out
+
+    def set_act_scales(self, exps):
+        e = np.ascontiguousarray(exps, dtype=np.int32)
+        self._ck(self._lib.vp_set_act_scales(self._h, _ptr(e), int(e.size)))
 
     def infer_shared(self):
         """Run this shared-prefix engine's own layers on the frame its base engine processed last."""
@@ -692,6 +721,36 @@ def op_conv2d(x, weight, bias, ks=3, mode=0, act=0, res=None, res_mode=0, precis
 
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def op_absmax(hi, lo, c, gpu_id=0):
+    """vp_op_absmax: hi / lo float16 planes [h][w][c_pitch] (lo may be None) -> (max |hi + lo| over channels [0, c) as float32, count of non-finite elements)."""
+    hi = np.ascontiguousarray(hi, dtype=np.float16)
+    lo = None if lo is None else np.ascontiguousarray(lo, dtype=np.float16)
+    h, w, pitch = hi.shape
+    amax, bad = C.c_float(), C.c_uint()
+    err = C.create_string_buffer(512)
+    rc = load().vp_op_absmax(gpu_id, _ptr(hi), None if lo is None else _ptr(lo), int(c), h, w, pitch, C.byref(amax), C.byref(bad), err, len(err))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_op_absmax failed ({rc}): {err.value.decode(errors='replace')}")
+    return np.float32(amax.value), int(bad.value)
+
+
+def op_conv2d_scaled(x, weight, bias, ks=3, act=0, res=None, res_mode=0, in_exp=0, res_exp=0, out_exp=0, precision=VP_FP16X3, tile=-1, bk=-1, nsplit=-1, gpu_id=0):
+    """vp_op_conv2d_scaled: op_conv2d with the input stored as x * 2^-in_exp, the residual as res * 2^-res_exp, the result as y * 2^-out_exp.
+    x / res are true values; returns the STORED (hi, lo) float16 planes [cout][h][w]."""
+    x, weight, bias = _f32(x), _f32(weight), _f32(bias)
+    cin, h, w = x.shape
+    cout = weight.shape[0]
+    r = _f32(res)
+    hi = np.empty((cout, h, w), np.float16)
+    lo = np.empty_like(hi)
+    err = C.create_string_buffer(512)
+    rc = load().vp_op_conv2d_scaled(gpu_id, int(precision), 0, _ptr(x), cin, h, w, _ptr(weight), _ptr(bias), cout, ks, act, res_mode, None if r is None else _ptr(r),
+                                    tile, bk, nsplit, int(in_exp), int(res_exp), int(out_exp), _ptr(hi), _ptr(lo), err, len(err))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_op_conv2d_scaled failed ({rc}): {err.value.decode(errors='replace')}")
+    return hi, lo
 
 
 def compose_upconv(wt, bt, w3, b3, ws=None, bs=None, gpu_id=0):

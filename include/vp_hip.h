@@ -91,7 +91,12 @@ enum vp_precision { VP_FP16 = 0, VP_FP16X3 = 1,
                      * process that holds several engines (VisionPilot/production_release/main.cpp:505-535: EgoLanes beside AutoSpeed / AutoSteer)
                      * chooses for each; results differ from the default plan's only in fp32 summation order; vp_plan_hash() tells the plans apart.
                      * A shared-prefix engine may choose differently from its base. */
-                    VP_PLAN_LATENCY = 32 };
+                    VP_PLAN_LATENCY = 32,
+                    /* OR-able flag: per-tensor power-of-two ACTIVATION SCALE (see RANGE GUARD below).  VP_AUTODRIVE with VP_FP16X3 only, alone or with
+                     * VP_WEIGHTS_FP8 and / or VP_PLAN_LATENCY; any other model kind, VP_FP16, vp_create_shared* and vp_create_batched* return
+                     * VP_ERR_ARG.  Every activation tensor t is stored as x * 2^-s_t; all s_t start at 0, and with all of them 0 the engine's
+                     * launches and bits are the unflagged engine's.  vp_calibrate_range chooses them, vp_set_act_scales installs a shipped table. */
+                    VP_ACT_SCALE = 64 };
 
 enum vp_pixel_format { VP_BGR8 = 0, VP_RGB8 = 1 };
 /* Plane order of the network input: BGR planes = middleware "common" backends (onnx_runtime_backend.cpp:47-57),
@@ -212,6 +217,21 @@ int vp_unregister_frames(const void* pool);
 /* {1, C, H, W} of the output tensor WITHOUT touching the device: vp_logits also returns the shape but fetches a de-selected tensor
  * (vp_set_outputs) on the way.  Same state rule as vp_logits: VP_ERR_STATE before the first inference (onnx_runtime_backend.cpp:86-91). */
 int vp_output_shape(const vp_engine* e, int64_t shape[4]);
+/* ACTIVATION SCALE (engines created with VP_ACT_SCALE; closes the RANGE GUARD's per-frame case below for AutoDrive).
+ * vp_calibrate_range: runs the plan eagerly, launch by launch, over the RESIDENT frame -- after vp_infer_pair (whatever it returned) over that pair,
+ *   after vp_upload_frame over that frame as both halves of the pair -- measures every tensor a launch stores and moves its exponent so that the
+ *   stored abs-max lies in [2^(target_log2 - 1), 2^target_log2); target_log2 1 .. 15, 0 = 12 (16x headroom below 65504).  A tensor that holds inf / NaN
+ *   gets +16, at most 3 times, else VP_ERR_RANGE names it.  Later calls only RAISE exponents (calibrate over several frames: the per-tensor maximum);
+ *   vp_reset_range puts all back to 0.  The stream continues behind a calibration: the current frame's features stay parked, so the next vp_infer pairs
+ *   with it; behind vp_set_act_scales and vp_reset_range the next vp_infer is the first frame of a stream.  A vp_upload_frame or vp_infer after the
+ *   pair drops the pair's previous frame.
+ * vp_act_scales / vp_set_act_scales: the table, one exponent per vp_tensor_count() entry, so a host calibrates once and ships it: engines with equal
+ *   tables give equal bits.  VP_ERR_ARG if n differs or if tensors that share storage (alias slices, copies, max-pools) disagree.  An installed exponent counts as measured: a later calibration only raises it.  vp_plan_hash does not change: exponents are data, not plan.
+ * vp_tensor_read and vp_logits return true values.  The range probe stays on: a frame beyond the calibrated headroom still returns VP_ERR_RANGE. */
+int vp_calibrate_range(vp_engine* e, int target_log2);
+int vp_reset_range(vp_engine* e);
+int vp_act_scales(const vp_engine* e, int* exps, int cap);   /* returns the tensor count */
+int vp_set_act_scales(vp_engine* e, const int* exps, int n);
 /* RANGE GUARD.  Both precision modes compute on fp16 planes: VP_FP16X3 has fp32-class SIGNIFICAND (hi + lo) but fp16 EXPONENT range.
  *   - at load: a BN-folded weight with |w| > 65504 (or non-finite) fails vp_create* with VP_ERR_RANGE instead of loading as inf;
  *   - per frame: an activation beyond 65504 becomes inf and reaches the logits as inf / NaN; a probe kernel over the logits at the end
@@ -394,6 +414,16 @@ int vp_op_upsample2_cat(int gpu_id, int precision, const float* a, int ca, const
                         char* err, size_t err_len);
 int vp_op_dwconv3x3(int gpu_id, int precision, const float* in, int c, int h, int w, const float* weight, const float* bias, int act, const float* add,
                     uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len);
+/* ---- single-operator entries of the activation-scale mechanism (unit tests; not used by callers) ------------
+ * vp_op_absmax: act_absmax_kernel on (hi, lo) fp16 bit patterns laid out [h][w][c_pitch] (lo may be NULL): max |hi + lo| over the channels [0, c) of
+ *   every pixel, non-finite elements left out and counted in *nonfinite.
+ * vp_op_conv2d_scaled: vp_op_conv2d (mode 0) with the input stored as in * 2^-in_exp, the residual as res * 2^-res_exp and the result as
+ *   y * 2^-out_exp; in / res are TRUE values (scaled on the host); out_hi / out_lo are the STORED planes, fp16 bit patterns [cout][h][w]. */
+int vp_op_absmax(int gpu_id, const uint16_t* hi, const uint16_t* lo, int c, int h, int w, int c_pitch, float* absmax, unsigned* nonfinite, char* err,
+                 size_t err_len);
+int vp_op_conv2d_scaled(int gpu_id, int precision, int mode, const float* in, int cin, int h, int w, const float* weight, const float* bias, int cout,
+                        int ks, int act, int res_mode, const float* res, int tile, int bk, int nsplit, int in_exp, int res_exp, int out_exp,
+                        uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len);
 /* ---- single-operator entries of the AutoSteer head's kernels (unit tests; not used by callers) ------------
  * vp_op_rowpair_conv: Conv2d(cin -> 32, kernel (2,1), stride (2,1)) + bias + SiLU: in [cin][h][w], weight [32][cin][2][1], bias [32].  The result,
  *   (h / 2) x w -- with replicate every pixel stored 2 x 2: h' x 2w, h' = 2 (h / 2) -- lands in channels [dst_off, dst_off + 32) of a destination of dst_c channels
