@@ -3,6 +3,8 @@
 // engine_io.cpp (frames in, graph replay, outputs out).
 #include "engine_internal.hpp"
 
+#include <array>
+
 namespace vp {
 
 // ================================================================================================ WeightBlob
@@ -162,7 +164,8 @@ RowScale row_prescale(const float* w, size_t rows, size_t per, size_t rows_alloc
 Engine::Engine(int kind, const WeightBlob* blob, int precision, int gpu_id, Engine* base, int frames, int frame_index)
     : kind_(kind), precision_(precision), gpu_(gpu_id), frames_(frames), frame_index_(frame_index), base_(base) {
   if ((precision & 64) != 0) {
-    if (kind >= 0 && kind != 4) throw std::invalid_argument("VP_ACT_SCALE: the per-tensor activation scale is built for VP_AUTODRIVE engines only");
+    if (kind >= 0 && kind != 4 && kind != 5 && kind != 6)
+      throw std::invalid_argument("VP_ACT_SCALE: the per-tensor activation scale is built for VP_AUTODRIVE, VP_AUTOSPEED and VP_AUTOSTEER engines (not for the scene networks)");
     if ((precision & 15) != 1) throw std::invalid_argument("VP_ACT_SCALE needs VP_FP16X3 (the parity mode)");
     if (base || frames != 1) throw std::invalid_argument("VP_ACT_SCALE: shared-prefix and batched creation are not supported");
   }
@@ -1436,8 +1439,10 @@ Act* Engine::neck_conv_bn(const WeightBlob& blob, const std::string& name, const
 }
 void Engine::neck_copy_slice(const std::string& name, const Act* src, int src_off, const Act* dst, int dst_off, int nch) {
   const ActView sv = src->view(), dv = dst->view();
+  tie_acts(src, dst);   // VP_ACT_SCALE: a copy keeps the exponent
   push_op(name, "chan_copy", [=](hipStream_t st) { return launch_chan_copy(sv, src_off, dv, dst_off, nch, st); }, 0,
           2.0 * (split() ? 4.0 : 2.0) * nch * src->H * src->W);
+  ops_.back().writes = {dst};
 }
 Act* Engine::neck_c3k2(const WeightBlob& blob, const std::string& p, const Act* in, bool csp, Act* dst) {
   // Residual (common_layers.py:20-27); res: where the block's input is read back for the sum (same row pitch as dst)
@@ -1466,15 +1471,20 @@ Act* Engine::neck_c3k2(const WeightBlob& blob, const std::string& p, const Act* 
   }
   return neck_conv_bn(blob, p + ".conv2", cat, 1, 1, nullptr, dst);
 }
-void Engine::neck_up_cat(const std::string& name, const Act* a, const Act* b, Act* out) {
+void Engine::neck_up_cat(const std::string& name, const Act* a, const Act* b, Act* out, int a_off, int a_nch, int b_off, int b_nch) {
   Upsample2CatParams q{};
   q.a = a->view();
   q.b = b->view();
   q.out = out->view();
-  q.a_nch = a->Creal;
-  q.b_nch = b->Creal;
+  q.a_off = a_off;
+  q.b_off = b_off;
+  q.a_nch = a_nch > 0 ? a_nch : a->Creal;
+  q.b_nch = b_nch > 0 ? b_nch : b->Creal;
   if (!upsample2_cat_ok(q)) throw std::runtime_error(name + ": unsupported shape for upsample2_cat");
+  tie_acts(out, a);   // VP_ACT_SCALE: a mover -- both sources and the result carry one exponent (like head.cat / SPPF's cat)
+  tie_acts(out, b);
   push_op(name, "upsample2_cat", [q](hipStream_t st) { return launch_upsample2_cat(q, st); }, 0, 2.0 * (split() ? 4.0 : 2.0) * out->elems());
+  ops_.back().writes = {out};
 }
 
 // ------------------------------------------------------------------------------------------------ AutoSpeed
@@ -1550,7 +1560,16 @@ void Engine::build_autospeed(const WeightBlob& blob) {
     dp.b = dupload(bk);
     dp.act = ACT_SILU;
     wbytes_[2] += 4 * wk.size();
-    push_op(name, "dwconv_plain<silu>", [dp](hipStream_t st) { return launch_dwconv_plain(dp, st); }, 2.0 * 9 * fd.cout * in->H * in->W, 2.0 * esz * in->elems());
+    // (VP_ACT_SCALE, here and below: the exponents are read when the launch RUNS; all 0 -> `scaled` 0, the block built above)
+    push_op(name, "dwconv_plain<silu>", [this, dp, in, out](hipStream_t st) {
+      DwPlainParams q2 = dp;
+      q2.scaled = (act_exp(in) | act_exp(out)) != 0;
+      q2.in_mul = act_mul(in);
+      q2.add_mul = 1.0f;
+      q2.out_mul = act_mul(out, -1);
+      return launch_dwconv_plain(q2, st);
+    }, 2.0 * 9 * fd.cout * in->H * in->W, 2.0 * esz * in->elems());
+    ops_.back().writes = {out};
     return out;
   };
   auto plain1x1 = [&](const std::string& name, const Act* in) -> Act* {
@@ -1559,6 +1578,7 @@ void Engine::build_autospeed(const WeightBlob& blob) {
   };
   DetectHeadParams hp{};
   const Act* feats[3] = {p3, p4, p5};
+  std::array<const Act*, 6> head_in{};   // box and cls of the three levels: the decode reads their exponents
   int first = 0;
   for (int i = 0; i < 3; ++i) {
     const std::string bp = "head.box." + std::to_string(i), cp = "head.cls." + std::to_string(i);
@@ -1567,6 +1587,8 @@ void Engine::build_autospeed(const WeightBlob& blob) {
     if (box->Creal != 64 || cls->Creal != nc) throw std::runtime_error("weight blob: detector head widths (64 box channels, nc classes on every level): " + bp);
     hp.lv[i].box = box->view();
     hp.lv[i].cls = cls->view();
+    head_in[2 * i] = box;
+    head_in[2 * i + 1] = cls;
     hp.lv[i].first = first;
     hp.lv[i].stride = (float)net_h() / (float)feats[i]->H;   // auto_speed_network.py:41
     first += feats[i]->H * feats[i]->W;
@@ -1579,7 +1601,15 @@ void Engine::build_autospeed(const WeightBlob& blob) {
   hp.nc = nc;
   hp.total = first;
   hp.out = d_logits_;
-  push_op("head.decode", "detect_head_decode", [hp](hipStream_t st) { return launch_detect_head_decode(hp, st); }, 0, esz * first * (64.0 + nc) + 4.0 * out_c_ * first);
+  push_op("head.decode", "detect_head_decode", [this, hp, head_in](hipStream_t st) {
+    DetectHeadParams q2 = hp;   // the softmax, the sigmoid and the box arithmetic see TRUE values: 2^s of the six inputs
+    for (int i = 0; i < 3; ++i) {
+      q2.scaled |= (act_exp(head_in[2 * i]) | act_exp(head_in[2 * i + 1])) != 0;
+      q2.lv[i].box_mul = act_mul(head_in[2 * i]);
+      q2.lv[i].cls_mul = act_mul(head_in[2 * i + 1]);
+    }
+    return launch_detect_head_decode(q2, st);
+  }, 0, esz * first * (64.0 + nc) + 4.0 * out_c_ * first);
   decode_mode_ = 0;
 }
 
@@ -1663,12 +1693,19 @@ void Engine::build_autosteer(const WeightBlob& blob) {
     q.cin = cin;
     q.w = dupload(wk);
     q.b = dupload(T(name + ".bias").data);
-    q.out = alias_slice(name, feat, ch_off, cout)->view();
+    const Act* dst = alias_slice(name, feat, ch_off, cout);   // (VP_ACT_SCALE: both halves are stored under `features`' exponent)
+    q.out = dst->view();
     q.replicate = replicate;
     wbytes_[2] += 4 * wk.size();
     if (!rowpair_conv_ok(q)) throw std::runtime_error(name + ": unsupported shape for rowpair_conv");
-    push_op(name, replicate ? "rowpair_conv<up2>" : "rowpair_conv", [q](hipStream_t st) { return launch_rowpair_conv(q, st); },
-            2.0 * 2 * cin * cout * (in->H / 2) * in->W, esz * in->elems() + esz * cout * feat->H * feat->W);
+    push_op(name, replicate ? "rowpair_conv<up2>" : "rowpair_conv", [this, q, in, dst](hipStream_t st) {
+      RowpairConvParams q2 = q;
+      q2.scaled = (act_exp(in) | act_exp(dst)) != 0;
+      q2.in_mul = act_mul(in);
+      q2.out_mul = act_mul(dst, -1);
+      return launch_rowpair_conv(q2, st);
+    }, 2.0 * 2 * cin * cout * (in->H / 2) * in->W, esz * in->elems() + esz * cout * feat->H * feat->W);
+    ops_.back().writes = {dst};
   };
   rowpair("head.v2", v2w, p3a, 0, 1);          // features[:, 0:32] = up(SiLU(v2(p3')))
   rowpair("head.v1", v1w, f.p2, 32, 0);        // features[:, 32:64] = SiLU(v1(p2))
@@ -1702,7 +1739,12 @@ void Engine::build_autosteer(const WeightBlob& blob) {
     q.out = d_logits_;
     wbytes_[2] += 4 * (wk.size() + hk.size());
     if (!lane_rows_head_ok(q)) throw std::runtime_error("head.c1+c2: unsupported shape for lane_rows_head");
-    push_op("head.lanes+height", "lane_rows_head", [q](hipStream_t st) { return launch_lane_rows_head(q, st); }, 2.0 * 2 * 9 * 64 * feat->H * feat->W,
+    push_op("head.lanes+height", "lane_rows_head", [this, q, feat](hipStream_t st) {
+      LaneRowsHeadParams q2 = q;   // xp / h_vector from TRUE feature values
+      q2.scaled = act_exp(feat) != 0;
+      q2.in_mul = act_mul(feat);
+      return launch_lane_rows_head(q2, st);
+    }, 2.0 * 2 * 9 * 64 * feat->H * feat->W,
             3.0 * esz * feat->elems());
   }
   decode_mode_ = 0;

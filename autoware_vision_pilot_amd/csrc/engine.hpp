@@ -222,12 +222,16 @@ class Engine {
   bool host_logits_current() const { return host_logits_valid_; }  // the pinned host logits belong to the LAST pass
   bool split() const { return (precision_ & 15) == 1; }
   bool fp8_weights() const { return (precision_ & 16) != 0; }
-  // VP_ACT_SCALE (creation flag, AutoDrive in the parity mode and the operator entry): every activation tensor t is stored as x * 2^-s_t
+  // VP_ACT_SCALE (creation flag, AutoDrive / AutoSpeed / AutoSteer in the parity mode and the operator entries): every activation tensor t is stored as x * 2^-s_t
   bool act_scale() const { return (precision_ & 64) != 0; }
   int act_exp(const Act* a) const { return (a && a->tie >= 0) ? act_exp_[a->tie] : 0; }
   float act_mul(const Act* a, int sign = 1) const { return std::ldexp(1.0f, sign * act_exp(a)); }   // 2^(sign * s_a)
   void tie_acts(const Act* a, const Act* b);   // plan time: b's tensors take a's exponent (copies, max-pools, alias slices: s_out == s_in)
   void set_act_exp(const Act* a, int e);       // operator entry / tests
+  // operator entry / tests: cat([up(a), b]) the way the necks build it, the tie of a, b and out included
+  void add_up_cat(const std::string& name, const Act* a, const Act* b, Act* out, int a_off, int a_nch, int b_off, int b_nch) {
+    neck_up_cat(name, a, b, out, a_off, a_nch, b_off, b_nch);
+  }
   void calibrate_range(int target_log2);
   void reset_range();
   std::vector<int> act_scales() const;                  // one per acts() entry
@@ -301,7 +305,8 @@ class Engine {
   Act* neck_conv_bn(const WeightBlob& blob, const std::string& name, const Act* in, int ks, int stride, const Act* res = nullptr, Act* dst = nullptr);
   void neck_copy_slice(const std::string& name, const Act* src, int src_off, const Act* dst, int dst_off, int nch);
   Act* neck_c3k2(const WeightBlob& blob, const std::string& p, const Act* in, bool csp, Act* dst);
-  void neck_up_cat(const std::string& name, const Act* a, const Act* b, Act* out);
+  // channels [a_off, a_off + a_nch) of a and [b_off, b_off + b_nch) of b; a_nch / b_nch 0 = the whole tensor
+  void neck_up_cat(const std::string& name, const Act* a, const Act* b, Act* out, int a_off = 0, int a_nch = 0, int b_off = 0, int b_nch = 0);
   std::vector<Act*> build_backbone(const WeightBlob& blob, const std::string& prefix);
   Act* build_context(const WeightBlob& blob, const std::string& p, const Act* deep, int cctx);
   Act* build_neck(const WeightBlob& blob, const std::string& p, const Act* ctx, const std::vector<Act*>& feats, int cctx);

@@ -816,7 +816,7 @@ void Engine::stash_previous_frame() {
 // every tensor a launch stores (act_absmax_kernel) and moves its exponent so that the stored abs-max lies in [2^(target - 1), 2^target).  The first
 // measurement of a tensor since vp_reset_range sets the exponent, later ones only raise it: calibrating on several frames gives the per-tensor maximum.
 void Engine::calibrate_range(int target_log2) {
-  if (!act_scale() || kind_ != 4) throw std::invalid_argument("vp_calibrate_range: engines created with VP_ACT_SCALE only");
+  if (!act_scale() || (kind_ != 4 && kind_ != 5 && kind_ != 6)) throw std::invalid_argument("vp_calibrate_range: engines created with VP_ACT_SCALE only");
   if (target_log2 == 0) target_log2 = 12;
   if (target_log2 < 1 || target_log2 > 15) throw std::invalid_argument("vp_calibrate_range: target_log2 is 1 .. 15 (0 = the default, 12)");
   if (!input_is_tensor_ && !d_frame_) throw std::runtime_error("no frame resident: call vp_upload_frame / vp_infer_pair first");
@@ -824,7 +824,11 @@ void Engine::calibrate_range(int target_log2) {
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
   if (!d_absmax_) d_absmax_ = static_cast<unsigned*>(dalloc(2 * sizeof(unsigned)));
   const size_t first = input_is_tensor_ ? first_net_op_ : 0;
-  const int head_tie = ops_[ad_place_op_].writes.empty() ? -1 : ops_[ad_place_op_].writes[0]->tie;
+  // AutoDrive pairs the resident frame with the previous one (head.cat carries both); the detector and the lane network are single-frame plans: one
+  // pass over whatever input is resident, and the AutoDrive-only launch indices stay out of it
+  const bool ad = kind_ == 4;
+  const size_t shift_op = ad ? ad_shift_op_ : SIZE_MAX;
+  const int head_tie = (!ad || ops_[ad_place_op_].writes.empty()) ? -1 : ops_[ad_place_op_].writes[0]->tie;
   std::vector<int> raises(act_exp_.size(), 0), lower(act_exp_.size(), INT_MIN);
   for (size_t g = 0; g < lower.size(); ++g)
     if (act_exp_seen_[g]) lower[g] = act_exp_[g];
@@ -835,7 +839,7 @@ void Engine::calibrate_range(int target_log2) {
   // false: the exponent of the tensor that carries the previous frame's features (head.cat) moved behind the shift -- the round starts over
   auto pass = [&](size_t begin, size_t end, bool prime) -> bool {
     for (size_t i = begin; i < end; ++i) {
-      if (prime && i == ad_shift_op_) continue;
+      if (prime && i == shift_op) continue;
       launch(i);
       for (const Act* a : ops_[i].writes) {
         const int g = a->tie;
@@ -866,9 +870,9 @@ void Engine::calibrate_range(int target_log2) {
           act_exp_[g] = want;
           // head.cat also holds the PREVIOUS frame's features, stored under the old exponent: settle the exponent on this frame first (so that the
           // previous frame's smaller values cannot take it back), then start the round over
-          if (!prime && g == head_tie && i >= ad_shift_op_) restart = true;
+          if (ad && !prime && g == head_tie && i >= shift_op) restart = true;
           for (size_t j = begin; j <= i; ++j) {   // every launch so far that writes the tensor stores it again
-            if (j == ad_shift_op_) continue;
+            if (j == shift_op) continue;
             bool writes = false;
             for (const Act* w : ops_[j].writes) writes |= w->tie == g;
             if (writes) launch(j);
@@ -880,9 +884,10 @@ void Engine::calibrate_range(int target_log2) {
     }
     return true;
   };
-  const bool pair = prev_frame_valid_ && !input_is_tensor_ && prev_frame_cap_ >= (size_t)frame_h_ * frame_stride_;
+  const bool pair = ad && prev_frame_valid_ && !input_is_tensor_ && prev_frame_cap_ >= (size_t)frame_h_ * frame_stride_;
   bool done = false;
   try {
+    if (!ad) done = pass(first, ops_.size(), false);
     for (int round = 0; round < 16 && !done; ++round) {
       if (pair) std::swap(d_frame_, d_prev_frame_);
       try {
@@ -901,7 +906,7 @@ void Engine::calibrate_range(int target_log2) {
     throw;
   }
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
-  ad_primed_ = done;   // the current frame's features sit in the "current" slot under the final exponents
+  ad_primed_ = ad && done;   // the current frame's features sit in the "current" slot under the final exponents
   exps_changed();
   if (!done) throw RangeError("vp_calibrate_range: the exponents did not settle");
 }

@@ -416,11 +416,15 @@ struct DetectHeadLevel {
   ActView cls;   // [H][W][>= nc] class logits
   int first;     // index of the level's first anchor in the output rows
   float stride;
+  // VP_ACT_SCALE: DetectHeadParams::scaled != 0 -> box is read times box_mul (2^s_box), cls times cls_mul (2^s_cls): the softmax, the sigmoid and the box
+  // arithmetic see true values, the fp32 output is true-valued; 0: not read
+  float box_mul, cls_mul;
 };
 struct DetectHeadParams {
   DetectHeadLevel lv[3];
   int nc, total;   // classes; anchors over all levels (10752 at 512 x 1024)
   float* out;      // fp32 [4 + nc][total]: cx, cy, w, h in input pixels, then sigmoid class scores
+  int scaled;      // VP_ACT_SCALE: != 0 -> the levels' box_mul / cls_mul apply
 };
 hipError_t launch_detect_head_decode(const DetectHeadParams& p, hipStream_t st);
 
@@ -435,6 +439,9 @@ struct RowpairConvParams {
   const float* b;    // [32]
   ActView out;       // (H / 2) x W, or H x 2W with replicate; 32 channels are stored at out.hi / out.lo
   int replicate;
+  // VP_ACT_SCALE: scaled != 0 -> in is read times in_mul (2^s_in), the result stored times out_mul (2^-s_out) behind SiLU (plain and replicated store); 0: not read
+  int scaled;
+  float in_mul, out_mul;
 };
 bool rowpair_conv_ok(const RowpairConvParams& p);
 hipError_t launch_rowpair_conv(const RowpairConvParams& p, hipStream_t st);
@@ -447,6 +454,9 @@ struct LaneRowsHeadParams {
   const float* w;    // [9 taps (ky * 3 + kx)][cin][2 outputs (c1, c2)]
   const float* hw;   // [16] h1 weights, [16] h2 weights, then the biases of c1, c2, h1, h2
   float* out;        // fp32 [2][H]: xp, h_vector
+  // VP_ACT_SCALE: scaled != 0 -> features is read times in_mul (2^s_features); xp / h_vector are true-valued either way; 0: not read
+  int scaled;
+  float in_mul;
 };
 bool lane_rows_head_ok(const LaneRowsHeadParams& p);
 hipError_t launch_lane_rows_head(const LaneRowsHeadParams& p, hipStream_t st);

@@ -385,6 +385,10 @@ __global__ __launch_bounds__(256) void rowpair_conv_kernel(const RowpairConvPara
     for (int c0 = 0; c0 < p.cin; c0 += 8) {
       float v[8];
       load8(p.in, base + c0, v);
+      if (p.scaled) {   // VP_ACT_SCALE: true input values (a power of two times the recombined hi + lo: exact)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] *= p.in_mul;
+      }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float* wr = sw + (ky * p.cin + c0 + j) * 32 + og * 8;
@@ -395,6 +399,10 @@ __global__ __launch_bounds__(256) void rowpair_conv_kernel(const RowpairConvPara
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = silu_f(acc[i]);
+  if (p.scaled) {   // behind SiLU, in front of the split of either store
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] *= p.out_mul;
+  }
   if (!p.replicate) {
     store8(p.out, (size_t)pix * p.out.C + og * 8, acc);
   } else {

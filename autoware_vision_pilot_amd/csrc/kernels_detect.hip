@@ -207,6 +207,10 @@ __global__ __launch_bounds__(256) void detect_head_decode_kernel(const DetectHea
     float v[16];
     load8(L.box, (size_t)pix * L.box.C + s * 16, v);
     load8(L.box, (size_t)pix * L.box.C + s * 16 + 8, v + 8);
+    if (p.scaled) {   // VP_ACT_SCALE: true logits (a power of two times the recombined hi + lo: exact)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] *= L.box_mul;
+    }
     float m = v[0];
 #pragma unroll
     for (int i = 1; i < 16; ++i) m = fmaxf(m, v[i]);
@@ -231,6 +235,10 @@ __global__ __launch_bounds__(256) void detect_head_decode_kernel(const DetectHea
   for (int c0 = 0; c0 < p.nc; c0 += 8) {
     float v[8];
     load8(L.cls, (size_t)pix * L.cls.C + c0, v);
+    if (p.scaled) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] *= L.cls_mul;
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i)
       if (c0 + i < p.nc) o[(size_t)(4 + c0 + i) * p.total] = sigmoid_f(v[i]);
@@ -279,6 +287,10 @@ __global__ __launch_bounds__(256) void lane_rows_head_kernel(const LaneRowsHeadP
       for (int c0 = 0; c0 < p.cin; c0 += 8) {
         float v[8];
         load8(p.features, base + c0, v);
+        if (p.scaled) {   // VP_ACT_SCALE: true feature values (a power of two times the recombined hi + lo: exact)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] *= p.in_mul;
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           a0 = fmaf(v[j], wt[(c0 + j) * 2], a0);

@@ -726,35 +726,123 @@ int op_guarded(char* err, size_t err_len, F&& f) {
     return VP_ERR_HIP;
   }
 }
+// VP_ACT_SCALE operator entries: the planes hold x * 2^-s -- the host scales the TRUE-valued argument (exact) before it is split; e = 0: the argument itself
+void upload_act_scaled(vp::Engine& g, vp::Act* a, const float* chw, int e) {
+  if (e == 0) return g.upload_act(a, chw);
+  if (e < -60 || e > 60) throw std::invalid_argument("exponent out of range (-60 .. 60)");
+  std::vector<float> v(chw, chw + (size_t)a->Creal * a->H * a->W);
+  for (float& x : v) x = std::ldexp(x, -e);
+  g.upload_act(a, v.data());
+}
+
+// exps: null = the unflagged launch (vp_op_detect_head_decode); else [3][2] exponents of (box, cls) per level
+void op_detect_head_decode(int gpu_id, int precision, const float* box, const float* cls, int nc, int h0, int w0, const int* exps, float* out) {
+  if (!box || !cls || !out || nc < 1 || nc > 4092 || h0 < 4 || w0 < 4 || (h0 & 3) || (w0 & 3) || (long long)h0 * w0 > (1 << 22)) throw std::invalid_argument("bad argument");
+  vp::Engine g(-1, nullptr, precision, gpu_id);
+  vp::DetectHeadParams p{};
+  size_t off = 0;
+  int first = 0;
+  for (int l = 0; l < 3; ++l) {
+    const int h = h0 >> l, w = w0 >> l;
+    vp::Act* b = g.new_act("box", 64, h, w);
+    vp::Act* c = g.new_act("cls", nc, h, w);
+    const int eb = exps ? exps[2 * l] : 0, ec = exps ? exps[2 * l + 1] : 0;
+    upload_act_scaled(g, b, box + off * 64, eb);
+    upload_act_scaled(g, c, cls + off * nc, ec);
+    p.scaled |= (eb | ec) != 0;   // all 0: the unflagged parameter block
+    p.lv[l].box_mul = std::ldexp(1.0f, eb);
+    p.lv[l].cls_mul = std::ldexp(1.0f, ec);
+    p.lv[l].box = b->view();
+    p.lv[l].cls = c->view();
+    p.lv[l].first = first;
+    p.lv[l].stride = (float)(8 << l);
+    off += (size_t)h * w;
+    first += h * w;
+  }
+  p.nc = nc;
+  p.total = first;
+  p.out = g.alloc_f32((size_t)(4 + nc) * first);
+  VP_HIP_CHECK(vp::launch_detect_head_decode(p, g.stream()));
+  g.copy_d2h(out, p.out, (size_t)(4 + nc) * first * sizeof(float));
+}
+
+// the AutoSteer head's two kernels; exponents 0: the unflagged launches (vp_op_rowpair_conv / vp_op_lane_rows_head)
+void op_rowpair_conv(int gpu_id, int precision, const float* in, int cin, int h, int w, const float* weight, const float* bias, int replicate,
+                     int dst_c, int dst_off, const float* dst_init, int in_exp, int out_exp, uint16_t* out_hi, uint16_t* out_lo) {
+  if (!in || !weight || !bias || !out_hi || cin < 8 || cin > 64 || (cin & 7) || h < 2 || w < 1 || (long long)h * w > (1 << 20) || dst_c < 32 || (dst_c & 31) || dst_off < 0 ||
+      (dst_off & 31) || dst_off + 32 > dst_c)
+    throw std::invalid_argument("bad argument (cin: a multiple of 8 up to 64; dst_c, dst_off: multiples of 32 with dst_off + 32 <= dst_c)");
+  vp::Engine g(-1, nullptr, precision, gpu_id);
+  const int f = replicate ? 2 : 1, ho = (h / 2) * f, wo = w * f;
+  vp::Act* ti = g.new_act("in", cin, h, w);
+  vp::Act* to = g.new_act("out", dst_c, ho, wo);
+  upload_act_scaled(g, ti, in, in_exp);
+  if (dst_init) upload_act_scaled(g, to, dst_init, out_exp);   // the whole destination carries one exponent (an alias slice shares its tensor's)
+  std::vector<float> wk((size_t)2 * cin * 32);
+  for (int co = 0; co < 32; ++co)
+    for (int ci = 0; ci < cin; ++ci)
+      for (int ky = 0; ky < 2; ++ky) wk[((size_t)ky * cin + ci) * 32 + co] = weight[((size_t)co * cin + ci) * 2 + ky];
+  float* dw = g.alloc_f32(wk.size());
+  float* db = g.alloc_f32(32);
+  g.copy_h2d(dw, wk.data(), wk.size() * sizeof(float));
+  g.copy_h2d(db, bias, 32 * sizeof(float));
+  vp::RowpairConvParams q{};
+  q.in = ti->view();
+  q.cin = cin;
+  q.w = dw;
+  q.b = db;
+  q.out = to->view();
+  q.out.hi += dst_off;   // the alias-slice convention: pixel * Cstore + channel
+  if (q.out.lo) q.out.lo += dst_off;
+  q.replicate = replicate ? 1 : 0;
+  q.scaled = (in_exp | out_exp) != 0;   // both 0: the unflagged parameter block
+  q.in_mul = std::ldexp(1.0f, in_exp);
+  q.out_mul = std::ldexp(1.0f, -out_exp);
+  VP_HIP_CHECK(vp::launch_rowpair_conv(q, g.stream()));
+  read_planes_chw(g, to, out_hi, out_lo);
+}
+
+void op_lane_rows_head(int gpu_id, int precision, const float* features, int cin, int h, int w, const float* c1_w, float c1_b, const float* c2_w,
+                       float c2_b, const float* h1_w, float h1_b, const float* h2_w, float h2_b, int in_exp, float* out_2xh) {
+  if (!features || !c1_w || !c2_w || !h1_w || !h2_w || !out_2xh || cin < 8 || cin > 64 || (cin & 7) || h < 1 || h > 4096 || w != 256)
+    throw std::invalid_argument("bad argument (cin: a multiple of 8 up to 64; w = 256)");
+  vp::Engine g(-1, nullptr, precision, gpu_id);
+  vp::Act* tf = g.new_act("features", cin, h, w);
+  upload_act_scaled(g, tf, features, in_exp);
+  std::vector<float> wk((size_t)9 * cin * 2), hk(36);
+  for (int t = 0; t < 9; ++t)
+    for (int ci = 0; ci < cin; ++ci) {
+      wk[((size_t)t * cin + ci) * 2 + 0] = c1_w[(size_t)ci * 9 + t];
+      wk[((size_t)t * cin + ci) * 2 + 1] = c2_w[(size_t)ci * 9 + t];
+    }
+  for (int i = 0; i < 16; ++i) {
+    hk[i] = h1_w[i];
+    hk[16 + i] = h2_w[i];
+  }
+  hk[32] = c1_b;
+  hk[33] = c2_b;
+  hk[34] = h1_b;
+  hk[35] = h2_b;
+  float* dw = g.alloc_f32(wk.size());
+  float* dh = g.alloc_f32(hk.size());
+  g.copy_h2d(dw, wk.data(), wk.size() * sizeof(float));
+  g.copy_h2d(dh, hk.data(), hk.size() * sizeof(float));
+  vp::LaneRowsHeadParams q{};
+  q.features = tf->view();
+  q.cin = cin;
+  q.w = dw;
+  q.hw = dh;
+  q.out = g.alloc_f32((size_t)2 * h);
+  q.scaled = in_exp != 0;   // 0: the unflagged parameter block
+  q.in_mul = std::ldexp(1.0f, in_exp);
+  VP_HIP_CHECK(vp::launch_lane_rows_head(q, g.stream()));
+  g.copy_d2h(out_2xh, q.out, (size_t)2 * h * sizeof(float));
+}
 }  // namespace
 extern "C" {
 
 int vp_op_detect_head_decode(int gpu_id, int precision, const float* box, const float* cls, int nc, int h0, int w0, float* out, char* err, size_t err_len) {
-  return op_guarded(err, err_len, [&] {
-    if (!box || !cls || !out || nc < 1 || nc > 4092 || h0 < 4 || w0 < 4 || (h0 & 3) || (w0 & 3) || (long long)h0 * w0 > (1 << 22)) throw std::invalid_argument("bad argument");
-    vp::Engine g(-1, nullptr, precision, gpu_id);
-    vp::DetectHeadParams p{};
-    size_t off = 0;
-    int first = 0;
-    for (int l = 0; l < 3; ++l) {
-      const int h = h0 >> l, w = w0 >> l;
-      vp::Act* b = g.new_act("box", 64, h, w);
-      vp::Act* c = g.new_act("cls", nc, h, w);
-      g.upload_act(b, box + off * 64);
-      g.upload_act(c, cls + off * nc);
-      p.lv[l].box = b->view();
-      p.lv[l].cls = c->view();
-      p.lv[l].first = first;
-      p.lv[l].stride = (float)(8 << l);
-      off += (size_t)h * w;
-      first += h * w;
-    }
-    p.nc = nc;
-    p.total = first;
-    p.out = g.alloc_f32((size_t)(4 + nc) * first);
-    VP_HIP_CHECK(vp::launch_detect_head_decode(p, g.stream()));
-    g.copy_d2h(out, p.out, (size_t)(4 + nc) * first * sizeof(float));
-  });
+  return op_guarded(err, err_len, [&] { op_detect_head_decode(gpu_id, precision, box, cls, nc, h0, w0, nullptr, out); });
 }
 
 int vp_op_upsample2_cat(int gpu_id, int precision, const float* a, int ca, const float* b, int cb, int h, int w, uint16_t* out_hi, uint16_t* out_lo,
@@ -873,72 +961,55 @@ int vp_op_conv2d_scaled(int gpu_id, int precision, int mode, const float* in, in
 // ---- single-operator entries of the AutoSteer head's kernels (unit tests)
 int vp_op_rowpair_conv(int gpu_id, int precision, const float* in, int cin, int h, int w, const float* weight, const float* bias, int replicate,
                        int dst_c, int dst_off, const float* dst_init, uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len) {
-  return op_guarded(err, err_len, [&] {
-    if (!in || !weight || !bias || !out_hi || cin < 8 || cin > 64 || (cin & 7) || h < 2 || w < 1 || (long long)h * w > (1 << 20) || dst_c < 32 || (dst_c & 31) || dst_off < 0 ||
-        (dst_off & 31) || dst_off + 32 > dst_c)
-      throw std::invalid_argument("bad argument (cin: a multiple of 8 up to 64; dst_c, dst_off: multiples of 32 with dst_off + 32 <= dst_c)");
-    vp::Engine g(-1, nullptr, precision, gpu_id);
-    const int f = replicate ? 2 : 1, ho = (h / 2) * f, wo = w * f;
-    vp::Act* ti = g.new_act("in", cin, h, w);
-    vp::Act* to = g.new_act("out", dst_c, ho, wo);
-    g.upload_act(ti, in);
-    if (dst_init) g.upload_act(to, dst_init);
-    std::vector<float> wk((size_t)2 * cin * 32);
-    for (int co = 0; co < 32; ++co)
-      for (int ci = 0; ci < cin; ++ci)
-        for (int ky = 0; ky < 2; ++ky) wk[((size_t)ky * cin + ci) * 32 + co] = weight[((size_t)co * cin + ci) * 2 + ky];
-    float* dw = g.alloc_f32(wk.size());
-    float* db = g.alloc_f32(32);
-    g.copy_h2d(dw, wk.data(), wk.size() * sizeof(float));
-    g.copy_h2d(db, bias, 32 * sizeof(float));
-    vp::RowpairConvParams q{};
-    q.in = ti->view();
-    q.cin = cin;
-    q.w = dw;
-    q.b = db;
-    q.out = to->view();
-    q.out.hi += dst_off;   // the alias-slice convention: pixel * Cstore + channel
-    if (q.out.lo) q.out.lo += dst_off;
-    q.replicate = replicate ? 1 : 0;
-    VP_HIP_CHECK(vp::launch_rowpair_conv(q, g.stream()));
-    read_planes_chw(g, to, out_hi, out_lo);
-  });
+  return op_guarded(err, err_len, [&] { op_rowpair_conv(gpu_id, precision, in, cin, h, w, weight, bias, replicate, dst_c, dst_off, dst_init, 0, 0, out_hi, out_lo); });
 }
 
 int vp_op_lane_rows_head(int gpu_id, int precision, const float* features, int cin, int h, int w, const float* c1_w, float c1_b, const float* c2_w,
                          float c2_b, const float* h1_w, float h1_b, const float* h2_w, float h2_b, float* out_2xh, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] { op_lane_rows_head(gpu_id, precision, features, cin, h, w, c1_w, c1_b, c2_w, c2_b, h1_w, h1_b, h2_w, h2_b, 0, out_2xh); });
+}
+
+// ---- the detector's and the lane network's own kernels under VP_ACT_SCALE (unit tests): arguments are TRUE values, stored as x * 2^-exp
+int vp_op_upsample2_cat_scaled(int gpu_id, int precision, const float* a, int ca, int a_off, int a_nch, const float* b, int cb, int b_off, int b_nch, int h, int w,
+                               int exp, uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len) {
   return op_guarded(err, err_len, [&] {
-    if (!features || !c1_w || !c2_w || !h1_w || !h2_w || !out_2xh || cin < 8 || cin > 64 || (cin & 7) || h < 1 || h > 4096 || w != 256)
-      throw std::invalid_argument("bad argument (cin: a multiple of 8 up to 64; w = 256)");
-    vp::Engine g(-1, nullptr, precision, gpu_id);
-    vp::Act* tf = g.new_act("features", cin, h, w);
-    g.upload_act(tf, features);
-    std::vector<float> wk((size_t)9 * cin * 2), hk(36);
-    for (int t = 0; t < 9; ++t)
-      for (int ci = 0; ci < cin; ++ci) {
-        wk[((size_t)t * cin + ci) * 2 + 0] = c1_w[(size_t)ci * 9 + t];
-        wk[((size_t)t * cin + ci) * 2 + 1] = c2_w[(size_t)ci * 9 + t];
-      }
-    for (int i = 0; i < 16; ++i) {
-      hk[i] = h1_w[i];
-      hk[16 + i] = h2_w[i];
-    }
-    hk[32] = c1_b;
-    hk[33] = c2_b;
-    hk[34] = h1_b;
-    hk[35] = h2_b;
-    float* dw = g.alloc_f32(wk.size());
-    float* dh = g.alloc_f32(hk.size());
-    g.copy_h2d(dw, wk.data(), wk.size() * sizeof(float));
-    g.copy_h2d(dh, hk.data(), hk.size() * sizeof(float));
-    vp::LaneRowsHeadParams q{};
-    q.features = tf->view();
-    q.cin = cin;
-    q.w = dw;
-    q.hw = dh;
-    q.out = g.alloc_f32((size_t)2 * h);
-    VP_HIP_CHECK(vp::launch_lane_rows_head(q, g.stream()));
-    g.copy_d2h(out_2xh, q.out, (size_t)2 * h * sizeof(float));
+    if (!a || !b || !out_hi || ca < 1 || cb < 1 || h < 1 || w < 1 || (long long)h * w > (1 << 20) || a_nch < 8 || b_nch < 8 || ((a_off | a_nch | b_off | b_nch) & 7) || a_off < 0 ||
+        b_off < 0 || a_off + a_nch > ca || b_off + b_nch > cb)
+      throw std::invalid_argument("bad argument (offsets and widths: multiples of 8 inside the sources)");
+    vp::Engine g(-1, nullptr, precision | VP_ACT_SCALE, gpu_id);
+    vp::Act* ta = g.new_act("a", ca, h, w);
+    vp::Act* tb = g.new_act("b", cb, 2 * h, 2 * w);
+    vp::Act* to = g.new_act("out", a_nch + b_nch, 2 * h, 2 * w);
+    upload_act_scaled(g, ta, a, exp);
+    upload_act_scaled(g, tb, b, exp);
+    g.add_up_cat("op", ta, tb, to, a_off, a_nch, b_off, b_nch);   // ties a, b and out: a mover keeps the exponent
+    g.set_act_exp(to, exp);
+    if (g.act_exp(ta) != exp || g.act_exp(tb) != exp) throw std::runtime_error("upsample2_cat: the sources do not carry the result's exponent");
+    g.run_eager();
+    g.sync();
+    read_planes_chw(g, to, out_hi, out_lo);
+  });
+}
+
+int vp_op_detect_head_decode_scaled(int gpu_id, int precision, const float* box, const float* cls, int nc, int h0, int w0, const int* exps, float* out, char* err,
+                                    size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!exps) throw std::invalid_argument("bad argument (exps: six exponents, box and cls of the three levels)");
+    op_detect_head_decode(gpu_id, precision, box, cls, nc, h0, w0, exps, out);
+  });
+}
+
+int vp_op_rowpair_conv_scaled(int gpu_id, int precision, const float* in, int cin, int h, int w, const float* weight, const float* bias, int replicate, int dst_c,
+                              int dst_off, const float* dst_init, int in_exp, int out_exp, uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    op_rowpair_conv(gpu_id, precision, in, cin, h, w, weight, bias, replicate, dst_c, dst_off, dst_init, in_exp, out_exp, out_hi, out_lo);
+  });
+}
+
+int vp_op_lane_rows_head_scaled(int gpu_id, int precision, const float* features, int cin, int h, int w, const float* c1_w, float c1_b, const float* c2_w,
+                                float c2_b, const float* h1_w, float h1_b, const float* h2_w, float h2_b, int in_exp, float* out_2xh, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    op_lane_rows_head(gpu_id, precision, features, cin, h, w, c1_w, c1_b, c2_w, c2_b, h1_w, h1_b, h2_w, h2_b, in_exp, out_2xh);
   });
 }
 

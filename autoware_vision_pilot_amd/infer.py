@@ -232,18 +232,27 @@ class AutoSteerNetworkInfer:
     """Models/inference/auto_steer_infer.py AutoSteerNetworkInfer behind the engine (the AutoSteer 2.0 lane-perception network, version 'n'):
     ``inference(image)`` on a 512 x 1024 x 3 uint8 BGR frame -> (xp [64], h_vector [64]): the ego-lane position per feature row in [0, 1) and the
     per-row validity the visualisation thresholds at 0.5.  The network takes the frame as it is (RGB planes of u8 / 255); any other size raises
-    ValueError as the reference does (:37-39)."""
+    ValueError as the reference does (:37-39).  ``act_scale`` (parity mode only) stores every activation tensor with a power-of-two scale of its own and
+    calibrates the scales on the first frame it sees (vp_hip.h VP_ACT_SCALE), as AutoDriveInfer does on its first pair."""
 
-    def __init__(self, autosteer_checkpoint_path="", precision="fp16", gpu_id=0):
+    def __init__(self, autosteer_checkpoint_path="", precision="fp16", gpu_id=0, act_scale=False):
         if autosteer_checkpoint_path is None or len(autosteer_checkpoint_path) == 0:
             raise ValueError("No path to checkpiont file provided in class initialization")
-        self.model = _lib.Engine("autosteer", autosteer_checkpoint_path, precision=precision, gpu_id=gpu_id)
+        self.model = _lib.Engine("autosteer", autosteer_checkpoint_path, precision=precision, gpu_id=gpu_id, act_scale=act_scale)
         self.model.set_input_format(_lib.VP_BGR8, _lib.VP_PLANES_RGB)
+        self._calibrate = bool(act_scale)
 
     def inference(self, image):
         image = np.asarray(image)
         if image.ndim != 3 or image.shape[0] != 512 or image.shape[1] != 1024:
             raise ValueError("Incorrect input size - input image must have height of 512px and width of 1024px")
+        if self._calibrate:   # first frame: run it (the uncalibrated pass may be refused), calibrate on it, then answer it
+            self._calibrate = False
+            try:
+                self.model.infer(image)
+            except _lib.VpRangeError:
+                pass
+            self.model.calibrate_range()
         self.model.infer(image)
         out = self.model.logits().reshape(2, 64)
         return out[0].copy(), out[1].copy()

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libvp_hip.so")
 VP_SCENESEG, VP_SCENE3D, VP_DOMAINSEG, VP_EGOLANES, VP_AUTODRIVE, VP_AUTOSPEED, VP_AUTOSTEER = 0, 1, 2, 3, 4, 5, 6
 VP_WEIGHTS_FP8 = 16
 VP_PLAN_LATENCY = 32  # creation flag: this engine's kernel plan targets one network on one camera, one frame at a time (vp_hip.h)
-VP_ACT_SCALE = 64  # creation flag: per-tensor power-of-two activation scale (AutoDrive, parity mode; vp_hip.h)
+VP_ACT_SCALE = 64  # creation flag: per-tensor power-of-two activation scale (AutoDrive, AutoSpeed, AutoSteer; parity mode; vp_hip.h)
 VP_FP16, VP_FP16X3 = 0, 1
 VP_BGR8, VP_RGB8 = 0, 1
 VP_PLANES_BGR, VP_PLANES_RGB = 0, 1
@@ -122,6 +122,13 @@ _SIGS = {
     "vp_op_rowpair_conv": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "vp_op_lane_rows_head": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_char_p,
                                        C.c_size_t]),
+    "vp_op_upsample2_cat_scaled": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
+                                             C.c_char_p, C.c_size_t]),
+    "vp_op_detect_head_decode_scaled": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_char_p, C.c_size_t]),
+    "vp_op_rowpair_conv_scaled": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P,
+                                            C.c_char_p, C.c_size_t]),
+    "vp_op_lane_rows_head_scaled": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, C.c_int,
+                                              _P, C.c_char_p, C.c_size_t]),
     "vp_version": (C.c_char_p, []),
     "vp_set_lane_ring": (C.c_int, [_P, C.c_int]),
     "vp_lane_ring_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int)]),
@@ -795,9 +802,10 @@ def _op_rc(rc, err, what):
         raise (ValueError if rc == -1 else VpError)(f"{what} failed ({rc}): {err.value.decode(errors='replace')}")
 
 
-def op_detect_head_decode(box, cls, h0, w0, precision="fp16x3", gpu_id=0):
+def op_detect_head_decode(box, cls, h0, w0, precision="fp16x3", gpu_id=0, exps=None):
     """vp_op_detect_head_decode: box [64][sum h_l w_l] / cls [nc][sum h_l w_l] logits of the three levels one after the other (level l: (h0 >> l) x
-    (w0 >> l), stride 8 << l) -> [4 + nc][sum h_l w_l] fp32 as AutoSpeedHead.forward gives in eval mode."""
+    (w0 >> l), stride 8 << l) -> [4 + nc][sum h_l w_l] fp32 as AutoSpeedHead.forward gives in eval mode.  exps (vp_op_detect_head_decode_scaled): six
+    exponents, (box, cls) per level -- the true-valued inputs are stored as x * 2^-exp and the kernel multiplies back."""
     box, cls = _f32(box), _f32(cls)
     nc, total = cls.shape[0], cls.shape[1]
     sizes = [(h0 >> l) * (w0 >> l) for l in range(3)]
@@ -808,6 +816,11 @@ def op_detect_head_decode(box, cls, h0, w0, precision="fp16x3", gpu_id=0):
     out = np.empty((4 + nc, total), np.float32)
     err = C.create_string_buffer(512)
     pr = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    if exps is not None:
+        e = np.ascontiguousarray(exps, dtype=np.int32).reshape(6)
+        _op_rc(load().vp_op_detect_head_decode_scaled(gpu_id, pr, _ptr(bl), _ptr(cl), nc, h0, w0, _ptr(e), _ptr(out), err, len(err)), err,
+               "vp_op_detect_head_decode_scaled")
+        return out
     _op_rc(load().vp_op_detect_head_decode(gpu_id, pr, _ptr(bl), _ptr(cl), nc, h0, w0, _ptr(out), err, len(err)), err, "vp_op_detect_head_decode")
     return out
 
@@ -825,6 +838,23 @@ def op_upsample2_cat(a, b, precision="fp16x3", gpu_id=0):
     return hi, lo
 
 
+def op_upsample2_cat_scaled(a, b, a_off=0, a_nch=None, b_off=0, b_nch=None, exp=0, precision="fp16x3", gpu_id=0):
+    """vp_op_upsample2_cat_scaled: channels [a_off, a_off + a_nch) of a [ca][h][w] and [b_off, b_off + b_nch) of b [cb][2h][2w], true values stored as
+    x * 2^-exp in a flagged engine that ties a, b and the result -> the STORED (hi, lo) float16 planes [a_nch + b_nch][2h][2w]."""
+    a, b = _f32(a), _f32(b)
+    ca, h, w = a.shape
+    cb = b.shape[0]
+    a_nch = ca - a_off if a_nch is None else int(a_nch)
+    b_nch = cb - b_off if b_nch is None else int(b_nch)
+    hi = np.empty((a_nch + b_nch, 2 * h, 2 * w), np.float16)
+    lo = np.empty_like(hi)
+    err = C.create_string_buffer(512)
+    pr = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    _op_rc(load().vp_op_upsample2_cat_scaled(gpu_id, pr, _ptr(a), ca, int(a_off), a_nch, _ptr(b), cb, int(b_off), b_nch, h, w, int(exp), _ptr(hi), _ptr(lo), err,
+                                             len(err)), err, "vp_op_upsample2_cat_scaled")
+    return hi, lo
+
+
 def op_dwconv3x3(x, weight, bias, act=0, add=None, precision="fp16x3", gpu_id=0):
     """vp_op_dwconv3x3: depthwise 3x3 (pad 1) + bias + activation (0 none, 2 SiLU) [+ add] -> (hi, lo) float16 planes [c][h][w]."""
     x, weight, bias = _f32(x), _f32(weight), _f32(bias)
@@ -839,10 +869,11 @@ def op_dwconv3x3(x, weight, bias, act=0, add=None, precision="fp16x3", gpu_id=0)
     return hi, lo
 
 
-def op_rowpair_conv(x, weight, bias, replicate=False, dst=None, dst_off=0, precision="fp16x3", gpu_id=0):
+def op_rowpair_conv(x, weight, bias, replicate=False, dst=None, dst_off=0, precision="fp16x3", gpu_id=0, in_exp=None, out_exp=None):
     """vp_op_rowpair_conv: Conv2d(cin -> 32, kernel (2,1), stride (2,1)) + bias + SiLU of x [cin][h][w] (weight [32][cin][2][1]); with `replicate` every
     result pixel is stored 2 x 2.  dst: the destination's initial content [dst_c][h'][w'] (None: 32 channels of zeros); the result lands in its channels
-    [dst_off, dst_off + 32).  Returns the whole destination as (hi, lo) float16 planes."""
+    [dst_off, dst_off + 32).  Returns the whole destination as (hi, lo) float16 planes.  in_exp / out_exp (vp_op_rowpair_conv_scaled): x and dst are
+    true values stored as x * 2^-in_exp / dst * 2^-out_exp, the planes returned are the STORED ones (true value = (hi + lo) * 2^out_exp)."""
     x, weight, bias = _f32(x), _f32(weight), _f32(bias)
     cin, h, w = x.shape
     assert weight.shape == (32, cin, 2, 1) and bias.shape == (32,)
@@ -855,20 +886,31 @@ def op_rowpair_conv(x, weight, bias, replicate=False, dst=None, dst_off=0, preci
     lo = np.empty_like(hi)
     err = C.create_string_buffer(512)
     pr = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    if in_exp is not None or out_exp is not None:
+        _op_rc(load().vp_op_rowpair_conv_scaled(gpu_id, pr, _ptr(x), cin, h, w, _ptr(weight), _ptr(bias), int(bool(replicate)), dst_c, int(dst_off),
+                                                None if dst is None else _ptr(dst), int(in_exp or 0), int(out_exp or 0), _ptr(hi), _ptr(lo), err, len(err)),
+               err, "vp_op_rowpair_conv_scaled")
+        return hi, lo
     _op_rc(load().vp_op_rowpair_conv(gpu_id, pr, _ptr(x), cin, h, w, _ptr(weight), _ptr(bias), int(bool(replicate)), dst_c, int(dst_off),
                                      None if dst is None else _ptr(dst), _ptr(hi), _ptr(lo), err, len(err)), err, "vp_op_rowpair_conv")
     return hi, lo
 
 
-def op_lane_rows_head(features, c1_w, c1_b, c2_w, c2_b, h1_w, h1_b, h2_w, h2_b, precision="fp16x3", gpu_id=0):
+def op_lane_rows_head(features, c1_w, c1_b, c2_w, c2_b, h1_w, h1_b, h2_w, h2_b, precision="fp16x3", gpu_id=0, in_exp=None):
     """vp_op_lane_rows_head: features [cin][h][256] -> [2][h] fp32 (xp, h_vector) as AutoSteerPerceptHead.forward gives behind `features`; c1 / c2 are the
-    3x3 convolutions [cin][3][3] with their BatchNorm folded in, h1 / h2 the 16-tap row convolutions."""
+    3x3 convolutions [cin][3][3] with their BatchNorm folded in, h1 / h2 the 16-tap row convolutions.  in_exp (vp_op_lane_rows_head_scaled): the
+    true-valued features are stored as x * 2^-in_exp and the kernel multiplies back."""
     features, c1_w, c2_w, h1_w, h2_w = _f32(features), _f32(c1_w).reshape(-1), _f32(c2_w).reshape(-1), _f32(h1_w).reshape(-1), _f32(h2_w).reshape(-1)
     cin, h, w = features.shape
     assert c1_w.size == cin * 9 and c2_w.size == cin * 9 and h1_w.size == 16 and h2_w.size == 16
     out = np.empty((2, h), np.float32)
     err = C.create_string_buffer(512)
     pr = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    if in_exp is not None:
+        _op_rc(load().vp_op_lane_rows_head_scaled(gpu_id, pr, _ptr(features), cin, h, w, _ptr(c1_w), float(c1_b), _ptr(c2_w), float(c2_b), _ptr(h1_w),
+                                                  float(h1_b), _ptr(h2_w), float(h2_b), int(in_exp), _ptr(out), err, len(err)), err,
+               "vp_op_lane_rows_head_scaled")
+        return out
     _op_rc(load().vp_op_lane_rows_head(gpu_id, pr, _ptr(features), cin, h, w, _ptr(c1_w), float(c1_b), _ptr(c2_w), float(c2_b), _ptr(h1_w), float(h1_b),
                                        _ptr(h2_w), float(h2_b), _ptr(out), err, len(err)), err, "vp_op_lane_rows_head")
     return out

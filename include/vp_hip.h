@@ -59,16 +59,18 @@ enum vp_status { VP_OK = 0, VP_ERR_ARG = -1, VP_ERR_WEIGHTS = -2, VP_ERR_HIP = -
  * vp_detect_preprocess leaves on the device; the engine has NO frame preprocess of its own: its entries are vp_infer_tensor (host tensor) and
  * vp_detect_infer (below); vp_infer / vp_upload_frame return VP_ERR_STATE.  Output through vp_logits: shape {1, 4 + nc, 1, 10752} = the head's
  * eval-mode tensor [4 + nc][10752] (cx, cy, w, h in input pixels, then sigmoid class scores; levels of stride 8, 16, 32 one after the other), the
- * tensor vp_detect_postprocess reads; no mask.  VP_FP16 / VP_FP16X3 (| VP_PLAN_LATENCY); VP_WEIGHTS_FP8, vp_create_shared* and
- * vp_create_batched* are refused with VP_ERR_ARG. */
+ * tensor vp_detect_postprocess reads; no mask.  VP_FP16 / VP_FP16X3 (| VP_PLAN_LATENCY; VP_FP16X3 also | VP_ACT_SCALE: vp_calibrate_range then runs on
+ * the tensor of the last vp_infer_tensor / vp_detect_infer, and vp_detect_infer works unchanged on the calibrated engine); VP_WEIGHTS_FP8,
+ * vp_create_shared* and vp_create_batched* are refused with VP_ERR_ARG. */
 /* VP_AUTOSTEER: the AutoSteer 2.0 lane-perception network, Models/model_components/auto_steer/auto_steer_network.py:39-43, version 'n' (what
  * Models/inference/auto_steer_infer.py AutoSteerNetworkInfer runs).  Input: a 512 x 1024 frame taken as it is -- R, G, B planes of u8 / 255, no mean / std,
  * no resize (auto_steer_infer.py:19-23,41-45): vp_infer / vp_upload_frame return VP_ERR_ARG for any other geometry (the reference raises ValueError),
  * vp_set_input_format picks BGR8 (default) or RGB8 bytes, vp_infer_tensor takes the [3][512][1024] planes.  Output through vp_logits: shape
  * {1, 2, 64, 1}: plane 0 = xp (ego-lane position per feature row, in [0, 1)), plane 1 = h_vector (per-row validity; the visualisation draws a row when
- * it is >= 0.5); no mask.  VP_FP16 / VP_FP16X3 (| VP_PLAN_LATENCY); VP_WEIGHTS_FP8, vp_create_shared* and vp_create_batched* are refused with
- * VP_ERR_ARG; a blob whose head is not the 'n' head is refused with VP_ERR_WEIGHTS naming the key.  (The v1 temporal AutoSteer head fed by EgoLanes
- * logits is another model and not part of this library: vp_set_lane_ring hands its input over.) */
+ * it is >= 0.5); no mask.  VP_FP16 / VP_FP16X3 (| VP_PLAN_LATENCY; VP_FP16X3 also | VP_ACT_SCALE: vp_calibrate_range then runs on the resident
+ * frame); VP_WEIGHTS_FP8, vp_create_shared* and vp_create_batched* are refused with VP_ERR_ARG; a blob whose head is not the 'n' head is refused with
+ * VP_ERR_WEIGHTS naming the key.  (The v1 temporal AutoSteer head fed by EgoLanes logits is another model and not part of this library:
+ * vp_set_lane_ring hands its input over.) */
 enum vp_model_kind { VP_SCENESEG = 0, VP_SCENE3D = 1, VP_DOMAINSEG = 2, VP_EGOLANES = 3, VP_AUTODRIVE = 4, VP_AUTOSPEED = 5, VP_AUTOSTEER = 6 };
 
 /* VP_FP16  : fp16 tensors, fp16 MFMA, fp32 accumulate (the reference's "fp16" configuration).
@@ -92,10 +94,11 @@ enum vp_precision { VP_FP16 = 0, VP_FP16X3 = 1,
                      * chooses for each; results differ from the default plan's only in fp32 summation order; vp_plan_hash() tells the plans apart.
                      * A shared-prefix engine may choose differently from its base. */
                     VP_PLAN_LATENCY = 32,
-                    /* OR-able flag: per-tensor power-of-two ACTIVATION SCALE (see RANGE GUARD below).  VP_AUTODRIVE with VP_FP16X3 only, alone or with
-                     * VP_WEIGHTS_FP8 and / or VP_PLAN_LATENCY; any other model kind, VP_FP16, vp_create_shared* and vp_create_batched* return
-                     * VP_ERR_ARG.  Every activation tensor t is stored as x * 2^-s_t; all s_t start at 0, and with all of them 0 the engine's
-                     * launches and bits are the unflagged engine's.  vp_calibrate_range chooses them, vp_set_act_scales installs a shipped table. */
+                    /* OR-able flag: per-tensor power-of-two ACTIVATION SCALE (see RANGE GUARD below).  VP_AUTODRIVE, VP_AUTOSPEED and VP_AUTOSTEER
+                     * (the YOLO-block family) with VP_FP16X3 only, alone or with VP_PLAN_LATENCY (VP_AUTODRIVE also with VP_WEIGHTS_FP8); the scene
+                     * network kinds, VP_FP16, vp_create_shared* and vp_create_batched* return VP_ERR_ARG.  Every activation tensor t is stored as
+                     * x * 2^-s_t; all s_t start at 0, and with all of them 0 the engine's launches and bits are the unflagged engine's.
+                     * vp_calibrate_range chooses them, vp_set_act_scales installs a shipped table. */
                     VP_ACT_SCALE = 64 };
 
 enum vp_pixel_format { VP_BGR8 = 0, VP_RGB8 = 1 };
@@ -217,14 +220,16 @@ int vp_unregister_frames(const void* pool);
 /* {1, C, H, W} of the output tensor WITHOUT touching the device: vp_logits also returns the shape but fetches a de-selected tensor
  * (vp_set_outputs) on the way.  Same state rule as vp_logits: VP_ERR_STATE before the first inference (onnx_runtime_backend.cpp:86-91). */
 int vp_output_shape(const vp_engine* e, int64_t shape[4]);
-/* ACTIVATION SCALE (engines created with VP_ACT_SCALE; closes the RANGE GUARD's per-frame case below for AutoDrive).
- * vp_calibrate_range: runs the plan eagerly, launch by launch, over the RESIDENT frame -- after vp_infer_pair (whatever it returned) over that pair,
- *   after vp_upload_frame over that frame as both halves of the pair -- measures every tensor a launch stores and moves its exponent so that the
- *   stored abs-max lies in [2^(target_log2 - 1), 2^target_log2); target_log2 1 .. 15, 0 = 12 (16x headroom below 65504).  A tensor that holds inf / NaN
- *   gets +16, at most 3 times, else VP_ERR_RANGE names it.  Later calls only RAISE exponents (calibrate over several frames: the per-tensor maximum);
- *   vp_reset_range puts all back to 0.  The stream continues behind a calibration: the current frame's features stay parked, so the next vp_infer pairs
- *   with it; behind vp_set_act_scales and vp_reset_range the next vp_infer is the first frame of a stream.  A vp_upload_frame or vp_infer after the
- *   pair drops the pair's previous frame.
+/* ACTIVATION SCALE (engines created with VP_ACT_SCALE; closes the RANGE GUARD's per-frame case below for AutoDrive, AutoSpeed and AutoSteer).
+ * vp_calibrate_range: runs the plan eagerly, launch by launch, over the RESIDENT frame -- AutoDrive: after vp_infer_pair (whatever it returned) over that
+ *   pair, after vp_upload_frame over that frame as both halves of the pair; AutoSteer: over the frame of the last vp_upload_frame / vp_infer; AutoSpeed:
+ *   over the input tensor of the last vp_infer_tensor / vp_detect_infer (single-frame plans: one pass, nothing parked) -- measures every tensor a launch
+ *   stores and moves its exponent so that the stored abs-max lies in [2^(target_log2 - 1), 2^target_log2); target_log2 1 .. 15, 0 = 12 (16x headroom
+ *   below 65504).  A tensor that holds inf / NaN gets +16, at most 3 times, else VP_ERR_RANGE names it.  Later calls only RAISE exponents (calibrate
+ *   over several frames: the per-tensor maximum); vp_reset_range puts all back to 0.  AutoDrive only (the other two kinds keep nothing from one frame
+ *   to the next): the stream continues behind a calibration -- the current frame's features stay parked, so the next vp_infer pairs with it; behind
+ *   vp_set_act_scales and vp_reset_range the next vp_infer is the first frame of a stream; a vp_upload_frame or vp_infer after the pair drops the
+ *   pair's previous frame.
  * vp_act_scales / vp_set_act_scales: the table, one exponent per vp_tensor_count() entry, so a host calibrates once and ships it: engines with equal
  *   tables give equal bits.  VP_ERR_ARG if n differs or if tensors that share storage (alias slices, copies, max-pools) disagree.  An installed exponent counts as measured: a later calibration only raises it.  vp_plan_hash does not change: exponents are data, not plan.
  * vp_tensor_read and vp_logits return true values.  The range probe stays on: a frame beyond the calibrated headroom still returns VP_ERR_RANGE. */
@@ -434,6 +439,24 @@ int vp_op_rowpair_conv(int gpu_id, int precision, const float* in, int cin, int 
                        int dst_c, int dst_off, const float* dst_init, uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len);
 int vp_op_lane_rows_head(int gpu_id, int precision, const float* features, int cin, int h, int w, const float* c1_w, float c1_b, const float* c2_w,
                          float c2_b, const float* h1_w, float h1_b, const float* h2_w, float h2_b, float* out_2xh, char* err, size_t err_len);
+/* ---- the detector's and the lane network's own kernels under the activation scale (unit tests; not used by callers) ------------
+ * The float arguments are TRUE values; the entry stores them as x * 2^-exp (scaled on the host: exact) and hands the exponents to the launch.  With every
+ * exponent 0 a launch is the one of the entry without the suffix: same parameter block, same bits.
+ * vp_op_upsample2_cat_scaled: channels [a_off, a_off + a_nch) of a [ca][h][w] and [b_off, b_off + b_nch) of b [cb][2h][2w] (multiples of 8) in an engine
+ *   created with VP_ACT_SCALE, which ties a, b and the result to ONE exponent; out_hi / out_lo: the STORED planes [a_nch + b_nch][2h][2w].
+ * vp_op_detect_head_decode_scaled: exps[6] = (box, cls) exponents of the three levels; out is true-valued like vp_op_detect_head_decode's.
+ * vp_op_rowpair_conv_scaled: in stored under in_exp, the whole destination (dst_init included) under out_exp; out_hi / out_lo: the STORED planes.
+ * vp_op_lane_rows_head_scaled: features stored under in_exp; out_2xh is true-valued. */
+int vp_op_upsample2_cat_scaled(int gpu_id, int precision, const float* a, int ca, int a_off, int a_nch, const float* b, int cb, int b_off, int b_nch, int h,
+                               int w, int exp, uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len);
+int vp_op_detect_head_decode_scaled(int gpu_id, int precision, const float* box, const float* cls, int nc, int h0, int w0, const int* exps, float* out,
+                                    char* err, size_t err_len);
+int vp_op_rowpair_conv_scaled(int gpu_id, int precision, const float* in, int cin, int h, int w, const float* weight, const float* bias, int replicate,
+                              int dst_c, int dst_off, const float* dst_init, int in_exp, int out_exp, uint16_t* out_hi, uint16_t* out_lo, char* err,
+                              size_t err_len);
+int vp_op_lane_rows_head_scaled(int gpu_id, int precision, const float* features, int cin, int h, int w, const float* c1_w, float c1_b, const float* c2_w,
+                                float c2_b, const float* h1_w, float h1_b, const float* h2_w, float h2_b, int in_exp, float* out_2xh, char* err,
+                                size_t err_len);
 
 /* ---- single-operator entry (unit parity tests of the MFMA conv kernel; not used by callers) -------------- */
 /* mode 0: Conv2d k=ks stride 1 pad ks/2, weight [Cout][Cin][ks][ks]; mode 1: ConvTranspose2d k2 s2, weight
