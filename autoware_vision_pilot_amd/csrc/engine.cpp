@@ -92,11 +92,9 @@ Folded fold_conv_bn(const WeightBlob& blob, const std::string& p) { return fold_
 // common_layers.py:5-14 Conv: `conv` (no bias) + `norm` (BatchNorm2d eps 1e-3)
 Folded fold_conv_norm(const WeightBlob& blob, const std::string& p) { return fold_conv(blob, p + ".conv", p + ".norm", 1e-3f); }
 
-// Experiment knob VP_WLO_KEEP_BITS (round 6; read once per engine in Engine::construct): explicit mantissa bits the LOW planes of
-// the weights keep (10 = all; fewer toggling bits through a power-limited matrix pipe: profiles/r06_mfma_power_lo_trunc.txt).  Default: untouched.
-std::atomic<int> g_wlo_keep{10};
-half_t truncate_lo(half_t lo) {
-  const int keep = g_wlo_keep.load(std::memory_order_relaxed);
+// Experiment knob VP_WLO_KEEP_BITS (round 6; read once per engine in Engine::construct into wlo_keep_): explicit mantissa bits the LOW
+// planes of the weights keep (10 = all; fewer toggling bits through a power-limited matrix pipe: profiles/r06_mfma_power_lo_trunc.txt).  Default: untouched.
+half_t truncate_lo(half_t lo, int keep) {
   if (keep >= 10) return lo;
   unsigned short bits;
   std::memcpy(&bits, &lo, 2);
@@ -105,14 +103,14 @@ half_t truncate_lo(half_t lo) {
   return lo;
 }
 
-void split_half(float v, float pre, half_t* hi, half_t* lo) {
+void split_half(float v, float pre, half_t* hi, half_t* lo, int keep_bits) {
   // Both precision modes carry weights on fp16 planes: a folded weight beyond the fp16 range (or non-finite) is refused at load (the
   // prescale could carry it, the activations it produces would not survive).  Small weights: see prescale_exp (engine_internal.hpp).
   if (!(std::fabs(v) <= 65504.0f)) throw RangeError("weight " + std::to_string(v) + " is outside the fp16 range the matrix pipe carries (|w| <= 65504): re-scale the checkpoint");
   const float x = v * pre;
   const half_t h = (half_t)x;
   *hi = h;
-  *lo = truncate_lo((half_t)(x - (float)h));
+  *lo = truncate_lo((half_t)(x - (float)h), keep_bits);
 }
 
 uint8_t e4m3_encode(float q) {
@@ -200,7 +198,7 @@ void Engine::construct(int kind, const WeightBlob* blob, int precision, int gpu_
   }
   {
     const char* e = dev_option("VP_WLO_KEEP_BITS");
-    g_wlo_keep.store(e ? std::atoi(e) : 10, std::memory_order_relaxed);
+    wlo_keep_ = e ? std::atoi(e) : 10;
   }
   if (base) {
     if (kind < 0 || base->kind_ < 0) throw std::invalid_argument("shared engines need model kinds on both sides");
@@ -540,7 +538,7 @@ std::vector<Act*> Engine::build_backbone(const WeightBlob& blob, const std::stri
           std::vector<float> be(z->C, 0.0f);
           const RowScale rs = row_prescale(f_exp.w.data(), cexp, cin, z->C);
           for (int co = 0; co < cexp; ++co) {
-            for (int ci = 0; ci < cin; ++ci) split_half(f_exp.w[(size_t)co * cin + ci], rs.pre[co], &wh[(size_t)co * x->C + ci], &wlo[(size_t)co * x->C + ci]);
+            for (int ci = 0; ci < cin; ++ci) split_half(f_exp.w[(size_t)co * cin + ci], rs.pre[co], &wh[(size_t)co * x->C + ci], &wlo[(size_t)co * x->C + ci], wlo_keep_);
             be[co] = f_exp.b[co];
           }
           MbFrontParams mp{};
@@ -681,8 +679,7 @@ std::vector<Act*> Engine::build_backbone(const WeightBlob& blob, const std::stri
           o.res_mode = RES_ADD;
           o.res = x;
         }
-        PackedConv pc;
-        choose_conv_cfg(HWz, ncols, z->C, 1, o, &pc);  // per frame: every frame has its own gate, hence its own scaled weights
+        PackedConv pc(choose_gemm_cfg(HWz, ncols, z->C, 1, o.tile, o.bk, o.nsplit));  // per frame: every frame has its own gate, hence its own scaled weights
         std::vector<float> wf((size_t)pc.CoutW * z->C, 0.0f), bias(pc.CoutW, 0.0f);
         const RowScale rs = row_prescale(f.w.data(), S.cout, cexp, pc.CoutW);   // se_gate_scale multiplies by the gate (0, 1) and splits on the device
         for (int co = 0; co < S.cout; ++co) {

@@ -100,6 +100,9 @@ int register_frame_range(const void* pool, size_t bytes);
 int unregister_frame_range(const void* pool);
 bool frame_range_registered(const void* p, size_t bytes);
 
+struct ConvChoice;   // engine_internal.hpp: what the dispatch rules of engine_dispatch.cpp give one convolution
+struct HostWeights;  // engine_internal.hpp: a layer's packed weights on the host
+
 class Engine {
  public:
   // base != nullptr builds a SHARED-PREFIX engine (vp_create_shared): sub-networks whose parameters equal the base
@@ -257,6 +260,8 @@ class Engine {
     float* wscale = nullptr;  // [CoutW] 2^-prescale of the weight rows (engine_internal.hpp prescale_exp), or the fp8 row scales
     uint8_t* w8 = nullptr;    // VP_WEIGHTS_FP8 on a kernel that stages weights through registers: e4m3 codes in that kernel's layout (w_hi / w_lo null)
     int CoutW = 0, tile = 0, bk = 32, nsplit = 1;
+    PackedConv() = default;
+    explicit PackedConv(const ConvChoice& c);
   };
   void construct(int kind, const WeightBlob* blob, int precision, int gpu_id, Engine* base);
   void release();  // frees every device / host resource; idempotent (destructor and failed construction)
@@ -279,9 +284,7 @@ class Engine {
   // FC matrix [N][K] -> fp32 rows, or (VP_WEIGHTS_FP8) e4m3 codes + row scales.  row_amax: per-row maximum the quantiser saw when it is not the
   // maximum of the K values handed in (AutoDrive's exp0: a row's three Conv1d taps share one scale, only the centre tap is used), else null
   void upload_fc_weights(FcParams* fp, const std::vector<float>& w, int N, int K, const std::vector<float>* row_amax = nullptr);
-  int gemm_dma_nsplit(int M, int ncols, int kw) const;
-  bool gemm_dma_wanted(int H, int W, int ncols, int cin_pad, int cin2_pad, int cstore) const;
-  void choose_conv_cfg(int M, int ncols, int cin_pad, int ks, const ConvOpts& o, PackedConv* pc);
+  void upload_packed(PackedConv* pc, const HostWeights& hw);  // hi, lo | codes, then bias, then the row scales
   void push_conv_op(const std::string& name, const Act* in, const PackedConv& pc, int ks, int ncols, const ConvOpts& o, Act* out,
                     int store_mode, int cout_real);
 
@@ -317,6 +320,7 @@ class Engine {
 
   Act* frame_view(const Act* a, int f);  // per-frame window of a stacked activation (no allocation)
   int kind_, precision_, gpu_;
+  int wlo_keep_ = 10;  // experiment knob VP_WLO_KEEP_BITS, read once in construct(): mantissa bits this engine's low weight planes keep (10 = all)
   int frames_ = 1, frame_index_ = 0;
   hipStream_t stream_ = nullptr;
   Engine* base_ = nullptr;

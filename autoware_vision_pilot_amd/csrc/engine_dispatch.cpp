@@ -1,6 +1,8 @@
-// libvp_hip engine, part 2 of 3: the DISPATCH RULES -- which kernel, tile and split factor every convolution of a plan gets, and the
-// weight packing that kernel expects.  Every rule here is a measured choice (the comment at the rule names the profile); the outcome for
-// every layer of every network is pinned by tests/golden/kernel_plan.json (tests/test_engine_emulated.py).
+// libvp_hip engine, part 2 of 3: the DISPATCH RULES -- which kernel, tile and split factor every convolution of a plan gets (choose_conv and its
+// family: free functions of the layer's shape and the developer options, callable without an engine), the weight packing that kernel expects
+// (pack_index / pack_weight_rows) and the emission of the launch (Engine::push_conv_op).  Every rule here is a measured choice (the comment at the rule
+// names the profile); the outcome for every layer of every network is pinned by tests/golden/kernel_plan*.json, and under every developer option by
+// tests/golden/plan_options.json (tests/test_engine_emulated.py).
 #include "engine_internal.hpp"
 
 namespace vp {
@@ -41,11 +43,23 @@ bool plan_override(const std::string& name, int* tile, int* nsplit) {
 }
 
 // ------------------------------------------------------------------------------------------- conv planning
-void Engine::choose_conv_cfg(int M, int ncols, int cin_pad, int ks, const ConvOpts& o, PackedConv* pc) {
-  auto cdiv = [](long long a, long long b) { return (a + b - 1) / b; };
+namespace {
+
+long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+// conv + bias + {GELU, none}: the epilogue the pipelined kernels carry without split-K
+bool plain_epilogue(const ConvQuery& q) { return (q.act == ACT_GELU || q.act == ACT_NONE) && q.res_mode == RES_NONE && q.post_act == ACT_NONE; }
+int option_int(const char* key, int dflt) {
+  const char* e = dev_option(key);
+  return e ? std::atoi(e) : dflt;
+}
+
+}  // namespace
+
+ConvChoice choose_gemm_cfg(int M, int ncols, int cin_pad, int ks, int forced_tile, int forced_bk, int forced_nsplit) {
+  ConvChoice c;
   int tile;
-  if (o.tile >= 0) {
-    tile = o.tile;
+  if (forced_tile >= 0) {
+    tile = forced_tile;
   } else if (ncols <= 32) {
     tile = 3;
   } else if (ncols % 128 == 0 && (cdiv(M, 128) * (ncols / 128) >= 192 || (M <= 256 && ncols >= 2048))) {
@@ -55,15 +69,16 @@ void Engine::choose_conv_cfg(int M, int ncols, int cin_pad, int ks, const ConvOp
   } else {
     tile = 2;
   }
-  pc->tile = tile;
-  pc->bk = o.bk > 0 ? o.bk : 64;  // 128-byte rows per load, half the K steps of BK=32
-  if (cin_pad % pc->bk != 0) pc->bk = 32;
-  pc->CoutW = round_up(ncols, conv_tile_co(tile));
-  const long long blocks = cdiv(M, conv_tile_px(tile)) * (pc->CoutW / conv_tile_co(tile));
-  const int S = ks * ks * (cin_pad / pc->bk);
+  c.tile = tile;
+  c.layout = tile == 6 ? GEMM_DMA : GEMM_ROWS;
+  c.bk = forced_bk > 0 ? forced_bk : 64;  // 128-byte rows per load, half the K steps of BK=32
+  if (cin_pad % c.bk != 0) c.bk = 32;
+  c.CoutW = round_up(ncols, conv_tile_co(tile));
+  const long long blocks = cdiv(M, conv_tile_px(tile)) * (c.CoutW / conv_tile_co(tile));
+  const int S = ks * ks * (cin_pad / c.bk);
   int ns = 1;
-  if (o.nsplit > 0) {
-    ns = o.nsplit;
+  if (forced_nsplit > 0) {
+    ns = forced_nsplit;
   } else if (blocks < 128 && S >= 32) {  // split-K pays only for long K loops: it costs a second (finish) launch
     ns = (int)std::min<long long>(cdiv(384, blocks), std::max(1, S / 8));
     ns = std::max(1, std::min(ns, 32));
@@ -72,12 +87,434 @@ void Engine::choose_conv_cfg(int M, int ncols, int cin_pad, int ks, const ConvOp
     // walking 8-18 dependent staging steps): slices of >= 3 steps up to ~128 workgroups.  Measured (parity mode, per launch incl.
     // the finish kernel): 25 -> 15 us on stages 6 / 7, 20 -> 15 on stage 5, SceneSeg single stream 2.076 -> 2.015 ms.
     // VP_PROJ_SPLIT = minimum steps per slice (0 = never split).
-    const char* e = dev_option("VP_PROJ_SPLIT");
-    const int min_steps = e ? std::atoi(e) : 3;
+    const int min_steps = option_int("VP_PROJ_SPLIT", 3);
     if (min_steps > 0 && S >= 2 * min_steps) ns = std::max(1, std::min<int>(S / min_steps, (int)cdiv(128, blocks)));
   }
-  pc->nsplit = std::min(ns, std::max(1, S));
+  c.nsplit = std::min(ns, std::max(1, S));
+  return c;
 }
+
+namespace {
+
+// ---- the halo tile of a 3x3 stride-1 convolution, step by step (choose_conv runs them in this order)
+
+// step 1, the base halo rule: LDS-resident halo kernel (kernels_conv3x3.hip) unless overridden (tile >= 100 selects a halo tile); -1 = the generic kernel
+int base_halo_tile(const ConvQuery& q, int ncols) {
+  int halo = -1;
+  const char* env = dev_option("VP_CONV3X3");
+  const bool force_v1 = (env && std::strcmp(env, "v1") == 0) || (q.tile >= 0 && q.tile < 100);
+  if (q.tile >= 100) {
+    halo = q.tile - 100;
+  } else if (!force_v1) {
+    const long long t256 = cdiv(q.H, 16) * cdiv(q.W, 16), t128 = cdiv(q.H, 8) * cdiv(q.W, 16);
+    if (ncols <= 32) {
+      halo = (dev_option("VP_HEAD_TILE5") && t256 >= 400) ? 5 : 4;
+    } else if (ncols % 128 != 0) {
+      halo = (!q.split && t256 * cdiv(ncols, 64) >= 400) ? 2 : 3;
+    } else {
+      halo = (!q.split && t256 * (ncols / 128) >= 400) ? 0 : 1;
+      // fewer 128-channel tiles than CUs: 64-channel tiles double the workgroup count, so the layer needs no split-K
+      // (decode_layer_5: 46 us vs 57 us with a 3-way split) or half the split factor and half the fp32 partial
+      // traffic (neck layers at 20x40 / 40x80: -1..-5 us each; profiles/r01_splitk_ablation.txt)
+      if (halo == 1 && t128 * (ncols / 128) < 256) halo = 3;
+    }
+  }
+  if (halo >= 0 && q.split && (halo == 0 || halo == 2)) halo += 1;
+  return halo;
+}
+
+// step 2, the pipelined shapes.  *rule_nsplit: the K slices a rule picks TOGETHER with its tile (0 = none)
+// parity mode, 128-channel tiles: the pipelined kernels of kernels_conv3x3_x3.hip -- halo tile 7 (8x16 patches, two
+// independent workgroups per CU; also the split-K shape of the small-map layers) or 6 (16x16 patches, one 8-wave workgroup)
+int pipelined_tile(const ConvQuery& q, int ncols, int halo, int* rule_nsplit) {
+  const char* envx = dev_option("VP_X3_TILE");  // developer knob: 0 = halo kernel, 6 / 7 = force that shape
+  const long long wgs16 = cdiv(q.H, 16) * cdiv(q.W, 16) * (ncols / 128);
+  // measured per layer (profiles/r02_layers_*): the 4-wave shape wins where the K loop is short (Cin <= 128: prologue and
+  // epilogue weigh most and two independent workgroups per CU overlap them), the 8-wave shape elsewhere (half the weight
+  // staging per MFMA)
+  const int want = envx ? std::atoi(envx) : (q.cin_pad <= 128 ? 7 : 6);
+  const bool plain = plain_epilogue(q);
+  // round 4: the VP_FP16 engines take the same shapes on 64-channel chunks (X1: the planes are the chunk's halves) for their big layers --
+  // the halo kernel's lone-wave schedule left them at 0.29-0.31 of peak.  VP_F16_BIG=0 (developer knob, A/B timing): the halo kernel.
+  const char* envf = dev_option("VP_F16_BIG");
+  if (!q.split && !q.fp8_storage && q.tile < 0 && !(envf && envf[0] == '0') && halo >= 0 && halo <= 3 && ncols % 128 == 0 && q.cin_pad % 64 == 0 && !q.logits_out &&
+      !q.in2 && plain && wgs16 >= option_int("VP_F16_MIN_WGS", q.plan_latency ? 160 : 36)) {
+    // measured per layer (profiles/r04_layers_sceneseg_fp16_big_ab.tsv): the 8-wave shape wins where ONE round of its workgroups covers the
+    // map and the K loop is long (decode_layer_4: 79.6 -> 68.9 us, decode_layer_7: 45.6 -> 40.9); with two rounds (decode_layer_6: 75.6 ->
+    // 77.2) or two chunks per workgroup (decode_layer_8: 85.8 -> 95.6 / 83.7 on the 4-wave shape) the halo kernel's two workgroups per CU
+    // do as well or better.  VP_F16_BIG=6 / 7 forces a shape on every eligible layer.
+    // Round 6, throughput plan: the in-frame search (tools/plan_search.py --precision fp16, profiles/r06_plan_search_fp16.tsv) moves the smaller layers
+    // onto the pipelined shapes as well, as round 5 did for the parity mode -- fewer, fatter workgroups leave CUs to the other cameras: decode_layer_5
+    // (100 tiles of 16x16 x 128 channels) and decode_layer_3 (60) on the 8-wave shape (+0.5 % / +1.1 % frames/s on the metric pair), decode_layer_1
+    // (20x40 map, 36 tiles) on the 4-wave shape in four K slices (+0.6 %); together 1040 -> 1067 frames/s.  The latency plan keeps the 160-tile floor.
+    if (envf) halo = std::atoi(envf) == 6 ? 6 : 7;
+    else if (wgs16 <= 256 && q.cin_pad >= 256 && wgs16 >= 60) halo = 6;
+    else if (wgs16 < 60 && q.cin_pad >= 256 && q.H * q.W <= 800 && q.nsplit <= 0) {
+      halo = 7;
+      *rule_nsplit = 4;
+    }
+  }
+  if (q.split && q.tile < 0 && want != 0 && (halo == 1 || halo == 3) && ncols % 128 == 0 && !q.logits_out && !q.in2) {
+    // Smaller layers stay on the halo kernel's 64-channel tiles (two workgroups per CU, twice the workgroup count): measured
+    // on MI355X, the 4-wave shape without split-K took 139 vs 100 us on decode_layer_5 (200 patches) and its split-K form
+    // (kernel support kept, tile 107 + nsplit) 63 vs 47 / 79 vs 70 us on decode_layer_1 / 3 (profiles/r02_splitk_x3w4.txt)
+    // Round 5: the floor is 100 tiles of 16x16 x 128 channels (it was 160): decode_layer_5 (512 -> 256 on 80x160: exactly 100) moves from the halo kernel's
+    // 400 64-channel workgroups to 100 8-wave workgroups of the pipelined shape.  ALONE the layer is slower (101 -> 138 us: 100 CUs), per occupied CU
+    // it runs at 2.2 TFLOP/s against 1.16 -- 100 CUs do not pull the package to its power limit -- and with the other head or the other cameras on
+    // the remaining CUs the frame rate gains 1.5-3 % at an unchanged one-camera p50 (profiles/r05_dec5_x3w8_ab.txt).  Below 100 (the 40x80 / 20x40
+    // maps: 60 / 36 workgroups) the same move LOSES 2 % / 11 %: their launches get 2-4x longer than the rest of the frame can cover.
+    // VP_X3_MIN_WGS: developer knob, fewest 16x16 workgroups for the pipelined shapes
+    if (plain && wgs16 >= option_int("VP_X3_MIN_WGS", q.plan_latency ? 160 : 100)) halo = want == 6 ? 6 : 7;
+  }
+  return halo;
+}
+
+// step 3, the map kernels.  forced_nsplit is what the caller forced or, as the rules stand, what step 2 picked (see choose_conv)
+// parity mode, small maps of the neck (20x40 / 40x80 pixels, long K): one workgroup = a 32-channel weight slab x a K slice x ALL pixels
+// of a 20x40 region (kernels_conv3x3_map.hip, halo tile 11): the 8x16 tiles re-stream the weights once per pixel tile and are bound by
+// that traffic.  Any epilogue (it always ends in the finish kernel).  VP_MAP3X3=0 (developer knob, A/B timing): the tiled kernels.
+int map_tile(const ConvQuery& q, int ncols, int M, int halo) {
+  const bool on = !dev_option_is("VP_MAP3X3", '0');
+  // round 4: the context block's 10x20 maps take the kernel's 10x20-region geometry (four waves, two workgroups per CU; VP_CTX3=0: the
+  // halo kernel's 8x16 tiles + split-K as before) -- context_layer_4 has 128 input channels, so the channel floor is per geometry
+  const int geom = conv3x3_map_geometry(q.H, q.W);
+  const bool geom_on = geom == 1 ? q.cin_pad >= 256 : (geom == 2 && q.cin_pad >= 128 && !dev_option_is("VP_CTX3", '0'));
+  // round 4: the VP_FP16 engines take the kernel too (X1: steps of 32 channels, the halves in the two planes; VP_F16_MAP=0: the halo kernel's
+  // 64-channel tiles + split-K as before)
+  const char* envf = dev_option("VP_F16_MAP");
+  // measured per layer (profiles/r04_layers_sceneseg_fp16_map_ab.tsv, halo kernel + split-K -> map kernel, us): context_layer_4..6 20.5 / 16.5 / 22.7 ->
+  // 18.5 / 14.3 / 19.9, decode_layer_0 (1280 channels on 20x40) 40.4 -> 35.5; decode_layer_1..3 28.2 / 43.7 / 37.1 -> 29.9 / 45.5 / 37.8: the kernel
+  // where it wins (the 10x20 geometry, >= 1024 input channels on a single region); VP_F16_MAP=1 everywhere it fits
+  const bool f16_rule = (envf && envf[0] == '1') || geom == 2 || (q.cin_pad >= 1024 && M <= 800);
+  const bool prec_on = q.split || (!q.fp8_storage && q.cin_pad % 32 == 0 && !(envf && envf[0] == '0') && f16_rule);
+  const int map_max_m = option_int("VP_MAP_MAX_M", 3200);   // developer knob: largest map (pixels) the map kernels take
+  if (q.tile == 111 || (on && prec_on && q.tile < 0 && halo >= 0 && ncols > 32 && !q.logits_out && !q.in2 && M <= map_max_m && geom_on &&
+                        conv3x3_map_shape_ok(q.H, q.W, q.cin_pad, round_up(ncols, 32))))
+    halo = 11;
+  // round 5: 64-channel slabs (two M tiles per wave, kernels_conv3x3_map.hip "map2") where the geometry is the neck's and the output channels pad to 64
+  // without waste: parity mode only.  VP_MAP2=0 (developer knob, A/B timing): tile 11 everywhere.
+  const int min_regions = option_int("VP_MAP2_MIN_REGIONS", 1);   // developer knob: 4 = the 40x80 maps only
+  if (halo == 11 && q.tile < 0 && q.split && geom == 1 && !dev_option_is("VP_MAP2", '0') && !(q.plan_latency && !dev_option_is("VP_MAP2", '1')) &&
+      round_up(ncols, 64) == round_up(ncols, 32) &&
+      (q.H / 20) * (q.W / 40) >= min_regions && conv3x3_map2_shape_ok(q.H, q.W, q.cin_pad, round_up(ncols, 64)))
+    halo = 12;
+  if (q.tile == 112) halo = 12;
+  return halo;
+}
+
+// step 6, the split factor (and K block) for the chosen tile; forced: the caller's factor (<= 0 = the rule's)
+void halo_split(const ConvQuery& q, int M, int halo, int forced, ConvChoice* c) {
+  const double slice_mb = (double)M * c->CoutW * 4.0 / 1e6;
+  if (halo == 12) {  // 64-channel slabs: a workgroup is twice the work of tile 11's, so the SAME K split gives half the workgroups (see the kernel's header)
+    const int regions = (q.H / 20) * (q.W / 40), n_co = c->CoutW / 64, KS = q.cin_pad / 16;
+    const int slots = std::max(1, option_int("VP_MAP2_SLOTS", 128));   // developer knob: workgroups a layer aims at
+    int ns = forced > 0 ? forced : std::max(1, slots / (regions * n_co));
+    double cap_mb = 27.0;   // 40x80 maps: four K slices (26.2 MB of slabs) -- measured 124 -> 103 / 91 -> 76 us per layer and +1.1 % frames/s against three (gpurun r5c04)
+    if (const char* e = dev_option("VP_MAP2_CAP_MB")) cap_mb = std::atof(e);   // developer knob: ceiling of the fp32 slabs a layer may write
+    while (forced <= 0 && ns > 2 && ns * slice_mb > cap_mb) --ns;
+    c->bk = 16;
+    c->nsplit = std::max(1, std::min(ns, std::max(1, KS / 2)));
+    return;
+  }
+  if (halo == 11) {  // map kernel: K slices until ~one round of workgroups (one per CU at 20x40 regions, two at 10x20), fp32 slabs <= 24 MB
+    const int geom = conv3x3_map_geometry(q.H, q.W);
+    const int regions = geom == 1 ? (q.H / 20) * (q.W / 40) : (q.H / 10) * (q.W / 20), n_co = c->CoutW / 32, KS = q.cin_pad / (q.split ? 16 : 32);
+    const int slots = geom == 1 ? 256 : 512;   // 155 KB of LDS = one workgroup per CU (a 257th waits a whole round); 74 KB = two
+    int ns = forced > 0 ? forced : std::max(1, slots / (regions * n_co));
+    while (forced <= 0 && ns > 2 && ns * slice_mb > 26.0) --ns;
+    if (const char* e = dev_option("VP_MAP_NSPLIT_PCT")) {   // developer knob (K-slice sweeps of the map kernel): percentage of the rule's factor
+      if (forced <= 0 && ns > 1) ns = std::max(1, (int)(ns * std::atoi(e) / 100.0 + 0.5));
+    }
+    c->bk = q.split ? 16 : 32;
+    c->nsplit = std::max(1, std::min(ns, std::max(1, KS / 2)));
+    return;
+  }
+  const int KC = q.cin_pad / 32;
+  const long long blocks = cdiv(q.H, halo_tile_th(halo)) * cdiv(q.W, 16) * (c->CoutW / halo_tile_co(halo));
+  // split-K: aim at ONE machine-wide wave of workgroups (256); go towards two only while the K loop per slice stays
+  // long (> 6 chunks = 54 tap steps), and keep the fp32 partials (written + re-read by the finish kernel at
+  // ~4.5 TB/s) under ~24 MB.  Measured per layer in profiles/r01_splitk_ablation.txt.
+  int ns = 1;
+  if (forced > 0) {
+    ns = forced;
+  } else if (halo == 4 && q.logits_out && q.cout <= 4 && (q.cin_pad == 64 || q.cin_pad == 128) && q.res_mode == RES_NONE && q.act == ACT_NONE &&
+             std::max(1, q.stride) == 1 && !(dev_option_is("VP_HEAD_CONV", '0'))) {
+    ns = 1;  // a head's logits convolution goes to kernels_head.hip (persistent workgroups: needs no split on any map size)
+  } else if (blocks < 256 && q.split) {
+    // parity mode (measured per layer with VP_NSPLIT_FORCE = 1..16, profiles/r02_splitk_sweep_fp16x3.txt): ONE full round of
+    // workgroups at two per CU -- ns = floor(512 / blocks), at most one slice per input chunk.  A little past 512 (the fp16
+    // rule gave 540 / 600 workgroups on the 20x40 / 40x80 layers) a second, nearly empty round costs 10-20 % of the layer.
+    ns = (int)std::max<long long>(1, 512 / blocks);
+    while (ns > 2 && ns * slice_mb > 24.0) --ns;
+  } else if (blocks < 256) {
+    ns = (int)((256 + blocks - 1) / blocks);
+    while (KC / ns > 6 && blocks * ns < 512) ++ns;
+    while (ns > 2 && ns * slice_mb > 24.0) --ns;
+    ns = std::min(ns, std::max(1, KC / 2));
+  }
+  if (const char* e = dev_option("VP_NSPLIT_PCT")) {  // developer knob (split-K sweeps): percentage applied to the heuristic's factor
+    if (forced <= 0 && ns > 1) ns = std::max(1, (int)(ns * std::atoi(e) / 100.0 + 0.5));
+  }
+  if (const char* e = dev_option("VP_NSPLIT_FORCE")) {  // developer knob: one factor for every layer the heuristic splits
+    if (forced <= 0 && ns > 1) ns = std::max(1, std::atoi(e));
+  }
+  c->nsplit = std::max(1, std::min(ns, KC));
+  if (halo == 6) c->nsplit = 1;  // one 8-wave workgroup per CU, >= 160 tiles: no split-K shape
+}
+
+// step 7, the late moves onto the pipelined 64-channel shapes (halo tiles 8 / 9), which look at the split factor step 6 chose
+// 64-channel tiles of the parity mode: the pipelined kernel's 64-channel shape (halo tile 8: same tiles, same split factor as
+// halo tile 3, three workgroups per CU).  Measured on MI355X (SceneSeg, us, halo tile 3 -> tile 8): decode_layer_0..3 70.5 /
+// 48.1 / 82.6 / 60.2 -> 77.9 / 54.6 / 90.2 / 65.6, decode_layer_5 98.6 -> 106.5, decode_layer_9 (128 -> 64 channels on
+// 320x640) 108.0 -> 102.2; 389 -> 381 frames/s with it everywhere.  So: only the short-K big-map case (as for tile 7);
+// VP_X3_C64=1 wherever the epilogue fits (plain, or anything behind split-K), =0 nowhere.
+int late_c64_tile(const ConvQuery& q, int ncols, int M, int halo, ConvChoice* c) {
+  const bool stride1 = std::max(1, q.stride) == 1, plain = plain_epilogue(q);
+  if ((halo == 3 || halo == 2) && !q.split && !q.fp8_storage && q.tile < 0 && q.cin_pad % 64 == 0 && ncols == 64 && !q.logits_out && !q.in2 && stride1) {
+    // fp16 engines, 64-channel outputs on the big maps (decode_layer_9: 128 -> 64 channels on 320x640): the pipelined 64-channel shape
+    const char* e8 = dev_option("VP_F16_BIG");
+    if (plain && e8 && e8[0] != '0' && M >= 65536) {   // measured level with the halo kernel (decode_layer_9: 52.2 -> 52.0 us): only when forced
+      halo = 8;
+      c->nsplit = 1;
+    }
+  }
+  if (halo == 3 && q.split && q.tile < 0 && q.cin_pad % 32 == 0 && !q.logits_out && !q.in2 && stride1) {
+    const char* e8 = dev_option("VP_X3_C64");
+    const bool fits = plain || c->nsplit > 1;
+    const bool want8 = e8 ? e8[0] == '1' : (c->nsplit == 1 && q.cin_pad <= 128 && M >= 65536);
+    if (fits && want8) halo = 8;
+  }
+  // round 5: 64-channel tiles of the parity mode on 16x16 pixels with the four waves side by side (halo tile 9: every wave 64 channels x 64 pixels, 8
+  // fragment reads per 12 MFMAs instead of 6 per 6).  Built for the 64-channel-output layers without split-K on VERDICT round 4's reading that they are
+  // fragment-read-bound; MEASURED SLOWER (profiles/r05_x3_t16_ab.txt): decode_layer_5 99.2 -> 135.1 us (200 workgroups of four waves = one wave per
+  // SIMD on 200 CUs), decode_layer_9 103.9 -> 110.6 us (800 tiles on 512 slots: two rounds), frames/s level (412.8 against 412.7).  Kept as a shape
+  // (tile 109, tests), selected only by VP_X3_T16=1.
+  if ((halo == 3 || halo == 8) && q.split && q.tile < 0 && c->nsplit == 1 && q.cin_pad % 32 == 0 && !q.logits_out && !q.in2 && stride1 && plain &&
+      dev_option_is("VP_X3_T16", '1') && M >= 12800)
+    halo = 9;
+  return halo;
+}
+
+}  // namespace
+
+ConvChoice choose_conv(const std::string& name, const ConvQuery& q) {
+  const int cstride = std::max(1, q.stride);
+  if (cstride > 1 && (q.ks != 3 || q.H % cstride || q.W % cstride)) throw std::invalid_argument("strided conv: 3x3 on even maps only: " + name);
+  const int M = (q.H / cstride) * (q.W / cstride), ncols = round_up(q.cout, 32);
+  int halo = -1, rule_nsplit = 0;
+  if (q.ks == 3 && cstride == 1 && q.H >= 8 && q.W >= 16) {
+    halo = base_halo_tile(q, ncols);
+    halo = pipelined_tile(q, ncols, halo, &rule_nsplit);
+    halo = map_tile(q, ncols, M, halo);
+    // steps 4 and 5, the fp8 clamp and the shape validity throws (in the order the messages have always come in)
+    if (halo == 12 && (!q.split || q.fp8_storage || !conv3x3_map2_shape_ok(q.H, q.W, q.cin_pad, round_up(ncols, 64))))
+      throw std::invalid_argument("halo tile 12 (map kernel, 64-channel slabs): parity mode, maps that tile into 20x40 regions, >= 32 input channels: " + name);
+    // VP_WEIGHTS_FP8 as storage (AutoDrive engines and the operator entry): the halo kernel's 8x16-pixel tiles of 64 / 32 channels are the ones
+    // instantiated with the byte-weight staging path (kernels_conv3x3.hip W8)
+    if (q.fp8_storage && q.tile < 0 && halo >= 0) halo = ncols <= 32 ? 4 : 3;
+    if (halo == 11 && (q.fp8_storage || (!q.split && q.cin_pad % 32 != 0) || !conv3x3_map_shape_ok(q.H, q.W, q.cin_pad, round_up(ncols, 32))))
+      throw std::invalid_argument("halo tile 11 (map kernel): maps that tile into 20x40 or 10x20 regions, >= 32 input channels (a multiple of 32 in the fp16 engines): " + name);
+    if (halo >= 6 && halo <= 9 && !q.split && q.cin_pad % 64 != 0) throw std::invalid_argument("halo tiles 6 - 9 in the fp16 engines: input channels a multiple of 64: " + name);
+  }
+  ConvChoice c;
+  if (halo >= 0) {
+    // The fp16 rule of step 2 picks four K slices WITH halo tile 7, and a later step may still replace the tile: the factor then reaches the new tile's
+    // kernel as if the caller had forced it (SceneNeck.decode_layer_0 of the three-op fp16 plan runs the map kernel on 4 slices instead of its own ~10:
+    // ADVICE.md, round 6).  Reproduced as it is -- tests/golden/plan_options.json pins it; applying rule_nsplit only while the tile is still 7 is a
+    // behaviour change of its own.
+    const int forced = q.nsplit > 0 ? q.nsplit : rule_nsplit;
+    c.bk = 32;
+    c.CoutW = round_up(ncols, halo_tile_co(halo));
+    halo_split(q, M, halo, forced, &c);
+    if (halo < 11) halo = late_c64_tile(q, ncols, M, halo, &c);
+    c.tile = 100 + halo;
+    c.layout = halo == 12 ? MAP2 : halo == 11 ? (q.split ? MAP : MAP_K32) : (halo >= 6 && halo <= 9) ? (q.split ? X3_SWIZZLED : X1_K64) : HALO32;
+  } else {
+    // fp8 storage: the generic kernel's 64 x 64 tile carries the byte-weight staging path (kernels_conv.hip W8)
+    c = choose_gemm_cfg(M, ncols, q.cin_pad, q.ks, (q.fp8_storage && q.tile < 0) ? 2 : q.tile, q.bk, q.nsplit);
+    c.layout = GEMM_ROWS;   // the LDS-DMA layout is add_convT*'s alone
+  }
+  // VP_WEIGHTS_FP8: real e4m3 storage where the layer's kernel stages its weights through registers (the generic GEMM kernel and the halo
+  // kernel's tiles 0-5: every matrix layer of AutoDrive); the LDS-DMA / register-stationary kernels copy weight images verbatim and keep
+  // de-quantised fp16 planes
+  c.w8 = q.fp8_storage && ((halo < 0 && c.tile == 2) || halo == 3 || halo == 4);
+  return c;
+}
+
+// The small-map up-sampling GEMMs go to the LDS-DMA pipelined kernel (kernels_gemm_dma.hip; tile 6).  Measured per layer on
+// MI355X (SceneSeg neck, us, old -> new): parity mode 42.1 / 41.0 / 42.2 -> 37.9 / 37.7 / 37.7 and +2.8 % frames/s with three
+// frames in flight (fewer workgroups at a higher rate leave CUs to the other frames); fp16 30.4 / 23.4 / 25.4 -> 26.8 / 26.8 /
+// 21.7: the fp16 engines take it from 2048 pixels up only.  VP_GEMM_DMA=1: wherever the shape fits, =0: never.
+bool gemm_dma_wanted(int H, int W, int ncols, int cin_pad, int cin2_pad, int cstore, bool split) {
+  const int M = H * W;
+  const char* e = dev_option("VP_GEMM_DMA");
+  if (e && e[0] == '0') return false;
+  if (!split && M < 2048 && !(e && e[0] == '1')) return false;
+  // the register-stationary kernel's shapes are its own (and keep the plain weight layout)
+  if (!dev_option_is("VP_CONVT_RS", '0') && convt_rs_shape_case(H, W, cin_pad, cin2_pad, ncols, cstore) != 0) return false;
+  return gemm_dma_shape_ok(M, ncols, cin_pad, cin2_pad, cstore);
+}
+
+// split-K factor of that kernel: towards ~160 workgroups while a slice keeps >= 8 K steps (VP_GEMM_DMA_NSPLIT: developer knob)
+int gemm_dma_nsplit(int M, int ncols, int kw) {
+  if (const char* e = dev_option("VP_GEMM_DMA_NSPLIT")) return std::max(1, std::atoi(e));
+  const int tiles = ((M + 127) / 128) * (ncols / 256), steps = kw / 32;
+  int ns = 1;
+  while (tiles * ns < 128 && steps / (ns + 1) >= 8) ++ns;
+  return ns;
+}
+
+// ------------------------------------------------------------------------------------------- weight packing
+size_t pack_index(WeightLayout layout, int co, int ci, int tap, int cin_pad, int CoutW) {
+  // the pipelined kernels copy weight tiles to LDS by LDS-DMA, a LINEAR copy: the tile is stored in its LDS image order, i.e. with the 16-byte
+  // chunks of a row XOR-swizzled by (row >> 2) & 3
+  const int ci_sw = (((ci & 31) >> 3) ^ ((co >> 2) & 3)) << 3 | (ci & 7);
+  switch (layout) {
+    case GEMM_ROWS: return ((size_t)tap * CoutW + co) * cin_pad + ci;
+    case HALO32: return (((size_t)(ci >> 5) * 9 + tap) * CoutW + co) * 32 + (ci & 31);
+    case X3_SWIZZLED: return (((size_t)(ci >> 5) * 9 + tap) * CoutW + co) * 32 + ci_sw;
+    case X1_K64: return (((size_t)(ci >> 6) * 9 + tap) * CoutW + co) * 32 + ci_sw;
+    case MAP: return conv3x3_map_pack_index(co, ci, tap, cin_pad);
+    case MAP_K32: return conv3x3_map_pack_index_k32(co, ci, tap, cin_pad);
+    case MAP2: return conv3x3_map2_pack_index(co, ci, tap, cin_pad);
+    case GEMM_DMA: return gemm_dma_pack_index(co, ci, cin_pad);
+  }
+  return 0;
+}
+
+namespace {
+
+// [rows][K] weights -> {hi, lo | codes, bias, post} of `layout`: per row the power-of-two prescale over its K values (fp8 storage: the row's
+// quantisation scale instead -- e4m3 values need no prescale, |q| in [2^-9, 448] are normal fp16 numbers), then every value split into its planes.
+// w(r, k): the weight; bias(r): its bias; out_row(r): the row's place in the packed matrix (< rows_alloc); at(out_row, k) -> {index, plane} there.
+template <class W, class B, class R, class At>
+HostWeights pack_weight_rows(int rows, int K, int rows_alloc, size_t elems, WeightLayout layout, bool split, bool w8, int keep_bits, W&& w, B&& bias,
+                             R&& out_row, At&& at) {
+  const bool halves = layout == X1_K64 || layout == MAP_K32;   // one fp16 value per weight, spread over the two plane arrays
+  HostWeights hw;
+  hw.hi.assign(w8 ? 0 : elems / (halves ? 2 : 1), (half_t)0.0f);
+  hw.lo.assign(((split || halves) && !w8) ? hw.hi.size() : 0, (half_t)0.0f);
+  hw.codes.assign(w8 ? elems : 0, (uint8_t)0);
+  hw.bias.assign(rows_alloc, 0.0f);
+  hw.post.assign(rows_alloc, 1.0f);
+  parallel_rows(rows, [&](int r_begin, int r_end) {
+    for (int r = r_begin; r < r_end; ++r) {
+      const int n = out_row(r);
+      hw.bias[n] = bias(r);
+      float amax = 0.0f;
+      for (int k = 0; k < K; ++k) {
+        const float a = std::fabs(w(r, k));
+        if (a > amax) amax = a;   // NaN compares false: split_half reports it
+      }
+      const int sexp = prescale_exp(amax);
+      const float pre = w8 ? 1.0f : std::ldexp(1.0f, sexp);
+      hw.post[n] = w8 ? fp8_row_scale(amax) : std::ldexp(1.0f, -sexp);
+      for (int k = 0; k < K; ++k) {
+        const float v = w(r, k);
+        const std::pair<size_t, int> d = at(n, k);
+        if (w8) {
+          if (!(std::fabs(v) <= 65504.0f)) throw RangeError("weight " + std::to_string(v) + " is outside the fp16 range the matrix pipe carries (|w| <= 65504): re-scale the checkpoint");
+          hw.codes[d.first] = e4m3_encode(v / hw.post[n]);   // v / S is on the e4m3 grid up to the fold's float rounding: the nearest code IS the quantiser's
+          continue;
+        }
+        half_t h, l;
+        split_half(v, pre, &h, &l, keep_bits);
+        (d.second ? hw.lo : hw.hi)[d.first] = h;
+        if (split && !halves) hw.lo[d.first] = l;
+      }
+    }
+  });
+  return hw;
+}
+
+}  // namespace
+
+Engine::PackedConv::PackedConv(const ConvChoice& c) : CoutW(c.CoutW), tile(c.tile), bk(c.bk), nsplit(c.nsplit) {}
+
+void Engine::upload_packed(PackedConv* pc, const HostWeights& hw) {
+  if (!hw.codes.empty()) {
+    pc->w8 = dupload(hw.codes);
+    wbytes_[0] += hw.codes.size();
+  } else {
+    pc->w_hi = dupload(hw.hi);
+    pc->w_lo = hw.lo.empty() ? nullptr : dupload(hw.lo);
+    wbytes_[1] += 2 * (hw.hi.size() + hw.lo.size());
+  }
+  pc->bias = dupload(hw.bias);
+  pc->wscale = dupload(hw.post);
+}
+
+// ------------------------------------------------------------------------------------------- emission
+namespace {
+
+enum ConvKernel { K_MAP, K_MAP2, K_X3, K_HEAD, K_HALO, K_GEMM_DMA, K_CONVT_RS, K_GEMM };
+
+// the kernel instantiation tag of a launch; v = the halo tile (K_X3, K_HALO) or the generic tile (K_GEMM)
+std::string conv_kernel_tag(ConvKernel k, const ConvGemmParams& p, int v, int bk, bool sp, bool fuse_decode) {
+  const char* splitk = p.nsplit > 1 ? "+splitk" : "";
+  const char* decode = fuse_decode ? "+decode" : "";
+  switch (k) {
+    case K_MAP: return std::string("conv3x3_map<co32,") + (conv3x3_map_geometry(p.H, p.W) == 1 ? "px800," : "px200,") + (sp ? "x3>" : "x1,k32>") + "+splitk";
+    case K_MAP2: return "conv3x3_map2<co64,px800,x3>+splitk";
+    case K_X3:
+      // fp16 engines ("x1"): the same schedule on 64-channel chunks, the chunk's two halves in the two LDS planes (kernels_conv3x3_x3.hip X1)
+      return std::string(sp ? "conv3x3_x3" : "conv3x3_x1") + (v == 6 ? "w8<co128,px256" : (v == 7 ? "w4<co128,px128" : (v == 8 ? "w4<co64,px128" : "w4<co64,px256"))) + (sp ? ">" : ",k64>") + splitk;
+    case K_HEAD: return std::string("head_conv3x3<c") + std::to_string(p.Cin) + (sp ? ",x3>" : ",x1>") + decode;
+    case K_HALO: {
+      // ",regepi": the register-GELU single-pass epilogue instantiation (same condition as launch_halo_cfg)
+      const bool regepi = !sp && p.act == ACT_GELU_F16 && p.res_mode == RES_NONE && p.store_mode == STORE_NHWC && p.nsplit == 1 && !p.w8;
+      return "conv3x3_halo<co" + std::to_string(halo_tile_co(v)) + ",px" + std::to_string(halo_tile_px(v)) + (sp ? ",x3" : ",x1") + (p.w8 ? ",w8" : "") +
+             (regepi ? ",regepi>" : ">") + splitk + decode;
+    }
+    case K_GEMM_DMA: return std::string("gemm_dma<co256,px128,") + (sp ? "x3>" : "x1>") + splitk;
+    case K_CONVT_RS: return "convt_rs<k" + std::to_string(p.Cin + p.Cin2) + (sp ? ",x3>" : ",x1>");
+    case K_GEMM: {
+      const int epi = (p.ks == 1 && !sp && !p.w8) ? regepi_case(p, conv_tile_co(v), sp) : 0;  // same rule as launch_cfg (kernels_conv.hip)
+      return "conv_gemm<bk" + std::to_string(bk) + ",co" + std::to_string(conv_tile_co(v)) + ",px" + std::to_string(conv_tile_px(v)) + (sp ? ",x3" : ",x1") +
+             (p.w8 ? ",w8" : "") + (epi ? ",regepi" + std::to_string(epi) + ">" : ">") + splitk + decode;
+    }
+  }
+  return std::string();
+}
+
+// ---- optional per-layer tile autotune (VP_AUTOTUNE=1 enables; measured +-1 % on the frames-in-flight bench, so
+// the static heuristic is the default): time the tile shapes that share this weight packing and keep the fastest.  The K order per output is identical for every tile, so the choice never changes a result bit.
+int autotune_halo_tile(const ConvGemmParams& p, int ht, bool sp, hipStream_t stream) {
+  std::vector<int> cand;
+  for (int c : {0, 1, 2, 3, 4}) {
+    if (sp && (c == 0 || c == 2)) continue;
+    if (p.CoutW % halo_tile_co(c) != 0) continue;
+    if (halo_tile_co(c) > p.CoutW) continue;
+    if (p.Ncols <= 32 && c != 4) continue;
+    if (p.Ncols > 32 && c == 4) continue;
+    cand.push_back(c);
+  }
+  // Cost = wall time of 6 launches spread over 3 streams: the engine is meant to run with several frames in
+  // flight, so what counts is the CU-time a tile shape consumes under contention, not its latency alone.
+  hipStream_t ts[3] = {stream, nullptr, nullptr};
+  VP_HIP_CHECK(hipStreamCreateWithFlags(&ts[1], hipStreamNonBlocking));
+  VP_HIP_CHECK(hipStreamCreateWithFlags(&ts[2], hipStreamNonBlocking));
+  double best = 1e30;
+  int best_c = ht;
+  for (int c : cand) {
+    hipError_t e = launch_conv3x3_halo(p, c, sp, stream);  // warm-up (also sets the LDS attribute)
+    if (e != hipSuccess) continue;
+    VP_HIP_CHECK(hipStreamSynchronize(stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int r = 0; r < 6 && e == hipSuccess; ++r) e = launch_conv3x3_halo(p, c, sp, ts[r % 3]);
+    for (hipStream_t s : ts) VP_HIP_CHECK(hipStreamSynchronize(s));
+    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    if (e == hipSuccess && us < best) {
+      best = us;
+      best_c = c;
+    }
+  }
+  hipStreamDestroy(ts[1]);
+  hipStreamDestroy(ts[2]);
+  return best_c;
+}
+
+}  // namespace
 
 void Engine::push_conv_op(const std::string& name, const Act* in, const PackedConv& pc, int ks, int ncols, const ConvOpts& o, Act* out,
                           int store_mode, int cout_real) {
@@ -141,6 +578,18 @@ void Engine::push_conv_op(const std::string& name, const Act* in, const PackedCo
     q.out_mul = std::ldexp(1.0f, -so);
     return q;
   };
+  // a launch with the patches it takes when it RUNS: the decode mode of a fused decode (vp_set_decode_mode may change it between frames; it
+  // invalidates the graph), the exponents of a VP_ACT_SCALE engine; an unflagged engine passes its parameter block untouched
+  auto patched = [&](auto launch) -> std::function<hipError_t(hipStream_t)> {
+    if (fuse_decode)
+      return [this, p, launch](hipStream_t st) {
+        ConvGemmParams q = p;
+        q.decode_mode = decode_mode_;
+        return launch(q, st);
+      };
+    if (act_scale()) return [p, launch, with_exps](hipStream_t st) { return launch(with_exps(p), st); };
+    return [p, launch](hipStream_t st) { return launch(p, st); };
+  };
   if (act_scale()) {
     const bool halo_plain = tile >= 100 && tile - 100 <= 5 && !(tile == 104 && o.tile < 0 && head_conv_supported(p));
     if (!(halo_plain || tile < 5) || store_mode != STORE_NHWC || o.in2 || fuse_decode || !out || (o.tile < 0 && tile < 100 && convt_rs_supported(p, sp)))
@@ -156,107 +605,40 @@ void Engine::push_conv_op(const std::string& name, const Act* in, const PackedCo
     op.flops += 2.0 * M * 4.0 * cout_real * o.in2->Creal;
     op.bytes += esz * ((double)M * 4.0 * o.in2->Creal + (double)cout_real * o.in2->Creal);
   }
-  if (tile >= 100) {
-    int ht = tile - 100;
-    // ---- optional per-layer tile autotune (VP_AUTOTUNE=1 enables; measured +-1 % on the frames-in-flight bench, so
-    // the static heuristic is the default): time the tile shapes that share this weight packing and keep the fastest.  The K order per output is identical for every tile, so the choice never changes a result bit.
-    const char* at_env = dev_option("VP_AUTOTUNE");
-    const bool explicit_tile = o.tile >= 100;
-    if (!explicit_tile && at_env && at_env[0] == '1' && kind_ >= 0) {
-      std::vector<int> cand;
-      for (int c : {0, 1, 2, 3, 4}) {
-        if (sp && (c == 0 || c == 2)) continue;
-        if (pc.CoutW % halo_tile_co(c) != 0) continue;
-        if (halo_tile_co(c) > pc.CoutW) continue;
-        if (ncols <= 32 && c != 4) continue;
-        if (ncols > 32 && c == 4) continue;
-        cand.push_back(c);
-      }
-      // Cost = wall time of 6 launches spread over 3 streams: the engine is meant to run with several frames in
-      // flight, so what counts is the CU-time a tile shape consumes under contention, not its latency alone.
-      hipStream_t ts[3] = {stream_, nullptr, nullptr};
-      VP_HIP_CHECK(hipStreamCreateWithFlags(&ts[1], hipStreamNonBlocking));
-      VP_HIP_CHECK(hipStreamCreateWithFlags(&ts[2], hipStreamNonBlocking));
-      double best = 1e30;
-      int best_c = ht;
-      for (int c : cand) {
-        hipError_t e = launch_conv3x3_halo(p, c, sp, stream_);  // warm-up (also sets the LDS attribute)
-        if (e != hipSuccess) continue;
-        VP_HIP_CHECK(hipStreamSynchronize(stream_));
-        const auto t0 = std::chrono::steady_clock::now();
-        for (int r = 0; r < 6 && e == hipSuccess; ++r) e = launch_conv3x3_halo(p, c, sp, ts[r % 3]);
-        for (hipStream_t s : ts) VP_HIP_CHECK(hipStreamSynchronize(s));
-        const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-        if (e == hipSuccess && us < best) {
-          best = us;
-          best_c = c;
-        }
-      }
-      hipStreamDestroy(ts[1]);
-      hipStreamDestroy(ts[2]);
-      ht = best_c;
-    }
-    if (ht == 11) {
-      if (!conv3x3_map_supported(p)) throw std::invalid_argument("halo tile 11 (map kernel): 3x3 stride 1, 20x40 or 10x20 regions: " + name);
-      op.kernel = std::string("conv3x3_map<co32,") + (conv3x3_map_geometry(p.H, p.W) == 1 ? "px800," : "px200,") + (sp ? "x3>" : "x1,k32>") + "+splitk";
-      op.run = [p](hipStream_t st) { return launch_conv3x3_map(p, st); };
-      ops_.push_back(std::move(op));
-      return;
-    }
-    if (ht == 12) {
-      if (!conv3x3_map2_supported(p)) throw std::invalid_argument("halo tile 12 (map kernel, 64-channel slabs): parity mode, 3x3 stride 1, 20x40 regions, output channels padded to 64: " + name);
-      op.kernel = "conv3x3_map2<co64,px800,x3>+splitk";
-      op.launch += " wgs=" + std::to_string((p.H / 20) * (p.W / 40) * (p.CoutW / 64) * p.nsplit);
-      op.run = [p](hipStream_t st) { return launch_conv3x3_map2(p, st); };
-      ops_.push_back(std::move(op));
-      return;
-    }
-    if (ht >= 6 && ht <= 9) {
-      if (!conv3x3_x3_supported(p, ht)) throw std::invalid_argument("halo tiles 6 - 9 (pipelined kernels): conv + bias + {GELU, none}, NHWC, 128- (64-) channel tiles, fp16: input channels a multiple of 64; any epilogue with split-K (7 / 8): " + name);
-      // fp16 engines ("x1"): the same schedule on 64-channel chunks, the chunk's two halves in the two LDS planes (kernels_conv3x3_x3.hip X1)
-      op.kernel = std::string(sp ? "conv3x3_x3" : "conv3x3_x1") + (ht == 6 ? "w8<co128,px256" : (ht == 7 ? "w4<co128,px128" : (ht == 8 ? "w4<co64,px128" : "w4<co64,px256"))) + (sp ? ">" : ",k64>") + (pc.nsplit > 1 ? "+splitk" : "");
-      op.run = [p, ht](hipStream_t st) { return launch_conv3x3_x3(p, ht, st); };
-      ops_.push_back(std::move(op));
-      return;
-    }
-    // the heads' logits convolution: weights stationary in registers, 16x16x32 MFMA, LDS-DMA halo (kernels_head.hip); same weight
-    // packing as halo tile 4.  VP_HEAD_CONV=0 keeps the halo kernel.
-    if (ht == 4 && o.tile < 0 && head_conv_supported(p) && !(dev_option_is("VP_HEAD_CONV", '0'))) {
-      const void* zeros = zero_page();
-      op.kernel = std::string("head_conv3x3<c") + std::to_string(p.Cin) + (sp ? ",x3>" : ",x1>") + (fuse_decode ? "+decode" : "");
-      op.run = [this, p, zeros, fuse_decode](hipStream_t st) {
-        ConvGemmParams q = p;
-        if (fuse_decode) q.decode_mode = decode_mode_;  // vp_set_decode_mode may change it between frames (it invalidates the graph)
-        return launch_head_conv(q, zeros, st);
-      };
-      ops_.push_back(std::move(op));
-      return;
-    }
-    // ",regepi": the register-GELU single-pass epilogue instantiation (same condition as launch_halo_cfg)
-    const bool regepi = !sp && p.act == ACT_GELU_F16 && p.res_mode == RES_NONE && p.store_mode == STORE_NHWC && p.nsplit == 1 && !p.w8;
-    op.kernel = "conv3x3_halo<co" + std::to_string(halo_tile_co(ht)) + ",px" + std::to_string(halo_tile_px(ht)) + (sp ? ",x3" : ",x1") +
-                (p.w8 ? ",w8" : "") + (regepi ? ",regepi>" : ">") + (pc.nsplit > 1 ? "+splitk" : "");
-    if (fuse_decode) {
-      op.kernel += "+decode";
-      op.run = [this, p, ht, sp](hipStream_t st) {
-        ConvGemmParams q = p;
-        q.decode_mode = decode_mode_;  // vp_set_decode_mode may change it between frames (it invalidates the graph)
-        return launch_conv3x3_halo(q, ht, sp, st);
-      };
-    } else if (act_scale()) {
-      op.run = [p, ht, sp, with_exps](hipStream_t st) { return launch_conv3x3_halo(with_exps(p), ht, sp, st); };
-    } else {
-      op.run = [p, ht, sp](hipStream_t st) { return launch_conv3x3_halo(p, ht, sp, st); };
-    }
+  int ht = tile - 100;
+  if (tile >= 100 && o.tile < 100 && dev_option_is("VP_AUTOTUNE", '1') && kind_ >= 0) ht = autotune_halo_tile(p, ht, sp, stream_);
+  // the heads' logits convolution: weights stationary in registers, 16x16x32 MFMA, LDS-DMA halo (kernels_head.hip); same weight
+  // packing as halo tile 4.  VP_HEAD_CONV=0 keeps the halo kernel.
+  const bool head = tile >= 100 && ht == 4 && o.tile < 0 && head_conv_supported(p) && !(dev_option_is("VP_HEAD_CONV", '0'));
+  if (tile >= 100 && ht == 11) {
+    if (!conv3x3_map_supported(p)) throw std::invalid_argument("halo tile 11 (map kernel): 3x3 stride 1, 20x40 or 10x20 regions: " + name);
+    op.kernel = conv_kernel_tag(K_MAP, p, ht, bk, sp, fuse_decode);
+    op.run = [p](hipStream_t st) { return launch_conv3x3_map(p, st); };
+  } else if (tile >= 100 && ht == 12) {
+    if (!conv3x3_map2_supported(p)) throw std::invalid_argument("halo tile 12 (map kernel, 64-channel slabs): parity mode, 3x3 stride 1, 20x40 regions, output channels padded to 64: " + name);
+    op.kernel = conv_kernel_tag(K_MAP2, p, ht, bk, sp, fuse_decode);
+    op.launch += " wgs=" + std::to_string((p.H / 20) * (p.W / 40) * (p.CoutW / 64) * p.nsplit);
+    op.run = [p](hipStream_t st) { return launch_conv3x3_map2(p, st); };
+  } else if (tile >= 100 && ht >= 6 && ht <= 9) {
+    if (!conv3x3_x3_supported(p, ht)) throw std::invalid_argument("halo tiles 6 - 9 (pipelined kernels): conv + bias + {GELU, none}, NHWC, 128- (64-) channel tiles, fp16: input channels a multiple of 64; any epilogue with split-K (7 / 8): " + name);
+    op.kernel = conv_kernel_tag(K_X3, p, ht, bk, sp, fuse_decode);
+    op.run = [p, ht](hipStream_t st) { return launch_conv3x3_x3(p, ht, st); };
+  } else if (head) {
+    const void* zeros = zero_page();
+    op.kernel = conv_kernel_tag(K_HEAD, p, ht, bk, sp, fuse_decode);
+    op.run = patched([zeros](const ConvGemmParams& q, hipStream_t st) { return launch_head_conv(q, zeros, st); });
+  } else if (tile >= 100) {
+    op.kernel = conv_kernel_tag(K_HALO, p, ht, bk, sp, fuse_decode);
+    op.run = patched([ht, sp](const ConvGemmParams& q, hipStream_t st) { return launch_conv3x3_halo(q, ht, sp, st); });
   } else if (tile == 6) {  // its weights are packed in its own layout (add_convT*): no other kernel may take this launch
     if (!gemm_dma_supported(p, sp))
       throw std::invalid_argument("LDS-DMA GEMM kernel (tile 6): ConvTranspose k2 s2 (+ skip link) + bias, 4 * Cout and Cout multiples of 256, K >= 256, >= 128 pixels: " + name);
-    op.kernel = std::string("gemm_dma<co256,px128,") + (sp ? "x3>" : "x1>") + (pc.nsplit > 1 ? "+splitk" : "");
+    op.kernel = conv_kernel_tag(K_GEMM_DMA, p, tile, bk, sp, fuse_decode);
     op.run = [p](hipStream_t st) { return launch_gemm_dma(p, st); };
   } else if (tile == 5 || (!(dev_option_is("VP_CONVT_RS", '0')) && convt_rs_supported(p, sp))) {
     if (!convt_rs_supported(p, sp))
       throw std::invalid_argument("register-stationary ConvTranspose kernel (tile 5): k2 s2 + bias, K = 128 or 256 + 32 (skip link), map width a multiple of 32, >= 2048 pixels: " + name);
-    op.kernel = "convt_rs<k" + std::to_string(p.Cin + p.Cin2) + (sp ? ",x3>" : ",x1>");
+    op.kernel = conv_kernel_tag(K_CONVT_RS, p, tile, bk, sp, fuse_decode);
     // Round 5: the K = 256 + 32 case (ConvTranspose + skip link 80x160 -> 160x320: four quadrant slices per pixel range) runs on 32 pixel-tile groups per
     // slice = 128 persistent workgroups instead of 256.  An HBM-side byte mover does not need every CU to pull its bytes: ALONE the launch is slower
     // (37.8 -> 52.7 us), with the other head or other cameras on the freed CUs the frame gains 1.2-1.3 % on two boxes and one camera's p50 is level or
@@ -268,22 +650,8 @@ void Engine::push_conv_op(const std::string& name, const Act* in, const PackedCo
     if (p.rs_groups > 0) op.launch += "groups=" + std::to_string(p.rs_groups);
     op.run = [p](hipStream_t st) { return launch_convt_rs(p, st); };
   } else {
-    const int epi = (ks == 1 && !sp && !p.w8) ? regepi_case(p, conv_tile_co(tile), sp) : 0;  // same rule as launch_cfg (kernels_conv.hip)
-    op.kernel = "conv_gemm<bk" + std::to_string(bk) + ",co" + std::to_string(conv_tile_co(tile)) + ",px" +
-                std::to_string(conv_tile_px(tile)) + (sp ? ",x3" : ",x1") + (p.w8 ? ",w8" : "") + (epi ? ",regepi" + std::to_string(epi) + ">" : ">") +
-                (pc.nsplit > 1 ? "+splitk" : "");
-    if (fuse_decode) {
-      op.kernel += "+decode";
-      op.run = [this, p, tile, bk, sp](hipStream_t st) {
-        ConvGemmParams q = p;
-        q.decode_mode = decode_mode_;
-        return launch_conv_gemm(q, tile, bk, sp, st);
-      };
-    } else if (act_scale()) {
-      op.run = [p, tile, bk, sp, with_exps](hipStream_t st) { return launch_conv_gemm(with_exps(p), tile, bk, sp, st); };
-    } else {
-      op.run = [p, tile, bk, sp](hipStream_t st) { return launch_conv_gemm(p, tile, bk, sp, st); };
-    }
+    op.kernel = conv_kernel_tag(K_GEMM, p, tile, bk, sp, fuse_decode);
+    op.run = patched([tile, bk, sp](const ConvGemmParams& q, hipStream_t st) { return launch_conv_gemm(q, tile, bk, sp, st); });
   }
   ops_.push_back(std::move(op));
 }
@@ -299,291 +667,23 @@ Act* Engine::add_conv(const std::string& name, const Act* in, const std::vector<
       if (on > 0) o.nsplit = on;
     }
   }
-  const int cin = in->Creal, cin_pad = in->C;
-  if (w.size() != (size_t)cout * cin * ks * ks) throw std::runtime_error("conv weight size mismatch: " + name);
+  const int cin = in->Creal, cin_pad = in->C, taps = ks * ks;
+  if (w.size() != (size_t)cout * cin * taps) throw std::runtime_error("conv weight size mismatch: " + name);
+  ConvQuery q;
+  q.H = in->H, q.W = in->W, q.stride = o.stride;
+  q.cin = cin, q.cin_pad = cin_pad, q.cout = cout, q.ks = ks;
+  q.act = o.act, q.res_mode = o.res_mode, q.post_act = o.post_act;
+  q.logits_out = o.logits_out != nullptr, q.in2 = o.in2 != nullptr;
+  q.tile = o.tile, q.bk = o.bk, q.nsplit = o.nsplit;
+  q.split = split(), q.fp8_storage = fp8_storage(), q.plan_latency = plan_latency();
+  const ConvChoice c = choose_conv(name, q);
+  PackedConv pc(c);
+  const HostWeights hw = pack_weight_rows(
+      cout, cin * taps, c.CoutW, (size_t)taps * c.CoutW * cin_pad, c.layout, split(), c.w8, wlo_keep_,
+      [&](int co, int k) { return w[(size_t)co * cin * taps + k]; }, [&](int co) { return b[co]; }, [](int co) { return co; },
+      [&](int co, int k) { return std::pair<size_t, int>(pack_index(c.layout, co, k / taps, k % taps, cin_pad, c.CoutW), pack_plane(c.layout, k / taps)); });
+  upload_packed(&pc, hw);
   const int cstride = std::max(1, o.stride);
-  if (cstride > 1 && (ks != 3 || in->H % cstride || in->W % cstride)) throw std::invalid_argument("strided conv: 3x3 on even maps only: " + name);
-  const int M = (in->H / cstride) * (in->W / cstride);
-  const int ncols = round_up(cout, 32);
-  PackedConv pc;
-  const int taps = ks * ks;
-  // ---- 3x3: LDS-resident halo kernel (kernels_conv3x3.hip) unless overridden (tile >= 100 selects a halo tile)
-  int halo = -1;
-  if (ks == 3 && cstride == 1 && in->H >= 8 && in->W >= 16) {
-    const char* env = dev_option("VP_CONV3X3");
-    const bool force_v1 = (env && std::strcmp(env, "v1") == 0) || (o.tile >= 0 && o.tile < 100);
-    if (o.tile >= 100) {
-      halo = o.tile - 100;
-    } else if (!force_v1) {
-      auto cdiv = [](long long a, long long b) { return (a + b - 1) / b; };
-      const long long t256 = cdiv(in->H, 16) * cdiv(in->W, 16), t128 = cdiv(in->H, 8) * cdiv(in->W, 16);
-      if (ncols <= 32) {
-        halo = (dev_option("VP_HEAD_TILE5") && t256 >= 400) ? 5 : 4;
-      } else if (ncols % 128 != 0) {
-        halo = (!split() && t256 * cdiv(ncols, 64) >= 400) ? 2 : 3;
-      } else {
-        halo = (!split() && t256 * (ncols / 128) >= 400) ? 0 : 1;
-        // fewer 128-channel tiles than CUs: 64-channel tiles double the workgroup count, so the layer needs no split-K
-        // (decode_layer_5: 46 us vs 57 us with a 3-way split) or half the split factor and half the fp32 partial
-        // traffic (neck layers at 20x40 / 40x80: -1..-5 us each; profiles/r01_splitk_ablation.txt)
-        if (halo == 1 && t128 * (ncols / 128) < 256) halo = 3;
-      }
-    }
-    if (halo >= 0 && split() && (halo == 0 || halo == 2)) halo += 1;
-    // parity mode, 128-channel tiles: the pipelined kernels of kernels_conv3x3_x3.hip -- halo tile 7 (8x16 patches, two
-    // independent workgroups per CU; also the split-K shape of the small-map layers) or 6 (16x16 patches, one 8-wave workgroup)
-    {
-      const char* envx = dev_option("VP_X3_TILE");  // developer knob: 0 = halo kernel, 6 / 7 = force that shape
-      auto cdiv = [](long long a, long long b) { return (a + b - 1) / b; };
-      const long long wgs16 = cdiv(in->H, 16) * cdiv(in->W, 16) * (ncols / 128), wgs8 = cdiv(in->H, 8) * cdiv(in->W, 16) * (ncols / 128);
-      // measured per layer (profiles/r02_layers_*): the 4-wave shape wins where the K loop is short (Cin <= 128: prologue and
-      // epilogue weigh most and two independent workgroups per CU overlap them), the 8-wave shape elsewhere (half the weight
-      // staging per MFMA)
-      const int want = envx ? std::atoi(envx) : (cin_pad <= 128 ? 7 : 6);
-      const bool plain = (o.act == ACT_GELU || o.act == ACT_NONE) && o.res_mode == RES_NONE && o.post_act == ACT_NONE;
-      // round 4: the VP_FP16 engines take the same shapes on 64-channel chunks (X1: the planes are the chunk's halves) for their big layers --
-      // the halo kernel's lone-wave schedule left them at 0.29-0.31 of peak.  VP_F16_BIG=0 (developer knob, A/B timing): the halo kernel.
-      const char* envf = dev_option("VP_F16_BIG");
-      if (!split() && !fp8_storage() && o.tile < 0 && !(envf && envf[0] == '0') && halo >= 0 && halo <= 3 && ncols % 128 == 0 && cin_pad % 64 == 0 && !o.logits_out &&
-          !o.in2 && plain && wgs16 >= [this] { const char* e = dev_option("VP_F16_MIN_WGS"); return e ? std::atoi(e) : (plan_latency() ? 160 : 36); }()) {
-        // measured per layer (profiles/r04_layers_sceneseg_fp16_big_ab.tsv): the 8-wave shape wins where ONE round of its workgroups covers the
-        // map and the K loop is long (decode_layer_4: 79.6 -> 68.9 us, decode_layer_7: 45.6 -> 40.9); with two rounds (decode_layer_6: 75.6 ->
-        // 77.2) or two chunks per workgroup (decode_layer_8: 85.8 -> 95.6 / 83.7 on the 4-wave shape) the halo kernel's two workgroups per CU
-        // do as well or better.  VP_F16_BIG=6 / 7 forces a shape on every eligible layer.
-        // Round 6, throughput plan: the in-frame search (tools/plan_search.py --precision fp16, profiles/r06_plan_search_fp16.tsv) moves the smaller layers
-        // onto the pipelined shapes as well, as round 5 did for the parity mode -- fewer, fatter workgroups leave CUs to the other cameras: decode_layer_5
-        // (100 tiles of 16x16 x 128 channels) and decode_layer_3 (60) on the 8-wave shape (+0.5 % / +1.1 % frames/s on the metric pair), decode_layer_1
-        // (20x40 map, 36 tiles) on the 4-wave shape in four K slices (+0.6 %); together 1040 -> 1067 frames/s.  The latency plan keeps the 160-tile floor.
-        if (envf) halo = std::atoi(envf) == 6 ? 6 : 7;
-        else if (wgs16 <= 256 && cin_pad >= 256 && wgs16 >= 60) halo = 6;
-        else if (wgs16 < 60 && cin_pad >= 256 && in->H * in->W <= 800 && o.nsplit <= 0) {
-          halo = 7;
-          o.nsplit = 4;
-        }
-      }
-      if (split() && o.tile < 0 && want != 0 && (halo == 1 || halo == 3) && ncols % 128 == 0 && !o.logits_out && !o.in2) {
-        // Smaller layers stay on the halo kernel's 64-channel tiles (two workgroups per CU, twice the workgroup count): measured
-        // on MI355X, the 4-wave shape without split-K took 139 vs 100 us on decode_layer_5 (200 patches) and its split-K form
-        // (kernel support kept, tile 107 + nsplit) 63 vs 47 / 79 vs 70 us on decode_layer_1 / 3 (profiles/r02_splitk_x3w4.txt)
-        // Round 5: the floor is 100 tiles of 16x16 x 128 channels (it was 160): decode_layer_5 (512 -> 256 on 80x160: exactly 100) moves from the halo kernel's
-        // 400 64-channel workgroups to 100 8-wave workgroups of the pipelined shape.  ALONE the layer is slower (101 -> 138 us: 100 CUs), per occupied CU
-        // it runs at 2.2 TFLOP/s against 1.16 -- 100 CUs do not pull the package to its power limit -- and with the other head or the other cameras on
-        // the remaining CUs the frame rate gains 1.5-3 % at an unchanged one-camera p50 (profiles/r05_dec5_x3w8_ab.txt).  Below 100 (the 40x80 / 20x40
-        // maps: 60 / 36 workgroups) the same move LOSES 2 % / 11 %: their launches get 2-4x longer than the rest of the frame can cover.
-        const char* envw = dev_option("VP_X3_MIN_WGS");  // developer knob: fewest 16x16 workgroups for the pipelined shapes
-        if (plain && wgs16 >= (envw ? std::atoi(envw) : (plan_latency() ? 160 : 100))) halo = want == 6 ? 6 : 7;
-        (void)wgs8;
-      }
-    }
-    // parity mode, small maps of the neck (20x40 / 40x80 pixels, long K): one workgroup = a 32-channel weight slab x a K slice x ALL pixels
-    // of a 20x40 region (kernels_conv3x3_map.hip, halo tile 11): the 8x16 tiles re-stream the weights once per pixel tile and are bound by
-    // that traffic.  Any epilogue (it always ends in the finish kernel).  VP_MAP3X3=0 (developer knob, A/B timing): the tiled kernels.
-    {
-      const char* envm = dev_option("VP_MAP3X3");
-      const bool on = !(envm && envm[0] == '0');
-      // round 4: the context block's 10x20 maps take the kernel's 10x20-region geometry (four waves, two workgroups per CU; VP_CTX3=0: the
-      // halo kernel's 8x16 tiles + split-K as before) -- context_layer_4 has 128 input channels, so the channel floor is per geometry
-      const char* envc = dev_option("VP_CTX3");
-      const int geom = conv3x3_map_geometry(in->H, in->W);
-      const bool geom_on = geom == 1 ? cin_pad >= 256 : (geom == 2 && cin_pad >= 128 && !(envc && envc[0] == '0'));
-      // round 4: the VP_FP16 engines take the kernel too (X1: steps of 32 channels, the halves in the two planes; VP_F16_MAP=0: the halo kernel's
-      // 64-channel tiles + split-K as before)
-      const char* envf = dev_option("VP_F16_MAP");
-      // measured per layer (profiles/r04_layers_sceneseg_fp16_map_ab.tsv, halo kernel + split-K -> map kernel, us): context_layer_4..6 20.5 / 16.5 / 22.7 ->
-      // 18.5 / 14.3 / 19.9, decode_layer_0 (1280 channels on 20x40) 40.4 -> 35.5; decode_layer_1..3 28.2 / 43.7 / 37.1 -> 29.9 / 45.5 / 37.8: the kernel
-      // where it wins (the 10x20 geometry, >= 1024 input channels on a single region); VP_F16_MAP=1 everywhere it fits
-      const bool f16_rule = (envf && envf[0] == '1') || geom == 2 || (cin_pad >= 1024 && M <= 800);
-      const bool prec_on = split() || (!fp8_storage() && cin_pad % 32 == 0 && !(envf && envf[0] == '0') && f16_rule);
-      int map_max_m = 3200;
-      if (const char* e = dev_option("VP_MAP_MAX_M")) map_max_m = std::atoi(e);   // developer knob: largest map (pixels) the map kernels take
-      if (o.tile == 111 || (on && prec_on && o.tile < 0 && halo >= 0 && ncols > 32 && !o.logits_out && !o.in2 && M <= map_max_m && geom_on &&
-                            conv3x3_map_shape_ok(in->H, in->W, cin_pad, round_up(ncols, 32))))
-        halo = 11;
-      // round 5: 64-channel slabs (two M tiles per wave, kernels_conv3x3_map.hip "map2") where the geometry is the neck's and the output channels pad to 64
-      // without waste: parity mode only.  VP_MAP2=0 (developer knob, A/B timing): tile 11 everywhere.
-      int min_regions = 1;
-      if (const char* e = dev_option("VP_MAP2_MIN_REGIONS")) min_regions = std::atoi(e);   // developer knob: 4 = the 40x80 maps only
-      if (halo == 11 && o.tile < 0 && split() && geom == 1 && !dev_option_is("VP_MAP2", '0') && !(plan_latency() && !dev_option_is("VP_MAP2", '1')) &&
-          round_up(ncols, 64) == round_up(ncols, 32) &&
-          (in->H / 20) * (in->W / 40) >= min_regions && conv3x3_map2_shape_ok(in->H, in->W, cin_pad, round_up(ncols, 64)))
-        halo = 12;
-    }
-    if (o.tile == 112) halo = 12;
-    if (halo == 12 && (!split() || fp8_storage() || !conv3x3_map2_shape_ok(in->H, in->W, cin_pad, round_up(ncols, 64))))
-      throw std::invalid_argument("halo tile 12 (map kernel, 64-channel slabs): parity mode, maps that tile into 20x40 regions, >= 32 input channels: " + name);
-    // VP_WEIGHTS_FP8 as storage (AutoDrive engines and the operator entry): the halo kernel's 8x16-pixel tiles of 64 / 32 channels are the ones
-    // instantiated with the byte-weight staging path (kernels_conv3x3.hip W8)
-    if (fp8_storage() && o.tile < 0 && halo >= 0) halo = ncols <= 32 ? 4 : 3;
-    if (halo == 11 && (fp8_storage() || (!split() && cin_pad % 32 != 0) || !conv3x3_map_shape_ok(in->H, in->W, cin_pad, round_up(ncols, 32))))
-      throw std::invalid_argument("halo tile 11 (map kernel): maps that tile into 20x40 or 10x20 regions, >= 32 input channels (a multiple of 32 in the fp16 engines): " + name);
-    if (halo >= 6 && halo <= 9 && !split() && cin_pad % 64 != 0) throw std::invalid_argument("halo tiles 6 - 9 in the fp16 engines: input channels a multiple of 64: " + name);
-  }
-  if (halo >= 0) {
-    pc.tile = 100 + halo;
-    pc.bk = 32;
-    pc.CoutW = round_up(ncols, halo_tile_co(halo));
-    if (halo == 12) {  // 64-channel slabs: a workgroup is twice the work of tile 11's, so the SAME K split gives half the workgroups (see the kernel's header)
-      const int regions = (in->H / 20) * (in->W / 40), n_co = pc.CoutW / 64, KS = cin_pad / 16;
-      int slots = 128;
-      if (const char* e = dev_option("VP_MAP2_SLOTS")) slots = std::max(1, std::atoi(e));   // developer knob: workgroups a layer aims at
-      int ns = o.nsplit > 0 ? o.nsplit : std::max(1, slots / (regions * n_co));
-      const double slice_mb = (double)M * pc.CoutW * 4.0 / 1e6;
-      double cap_mb = 27.0;   // 40x80 maps: four K slices (26.2 MB of slabs) -- measured 124 -> 103 / 91 -> 76 us per layer and +1.1 % frames/s against three (gpurun r5c04)
-      if (const char* e = dev_option("VP_MAP2_CAP_MB")) cap_mb = std::atof(e);   // developer knob: ceiling of the fp32 slabs a layer may write
-      while (o.nsplit <= 0 && ns > 2 && ns * slice_mb > cap_mb) --ns;
-      pc.bk = 16;
-      pc.nsplit = std::max(1, std::min(ns, std::max(1, KS / 2)));
-    } else if (halo == 11) {  // map kernel: K slices until ~one round of workgroups (one per CU at 20x40 regions, two at 10x20), fp32 slabs <= 24 MB
-      const int geom = conv3x3_map_geometry(in->H, in->W);
-      const int regions = geom == 1 ? (in->H / 20) * (in->W / 40) : (in->H / 10) * (in->W / 20), n_co = pc.CoutW / 32, KS = cin_pad / (split() ? 16 : 32);
-      const int slots = geom == 1 ? 256 : 512;   // 155 KB of LDS = one workgroup per CU (a 257th waits a whole round); 74 KB = two
-      int ns = o.nsplit > 0 ? o.nsplit : std::max(1, slots / (regions * n_co));
-      const double slice_mb = (double)M * pc.CoutW * 4.0 / 1e6;
-      while (o.nsplit <= 0 && ns > 2 && ns * slice_mb > 26.0) --ns;
-      if (const char* e = dev_option("VP_MAP_NSPLIT_PCT")) {   // developer knob (K-slice sweeps of the map kernel): percentage of the rule's factor
-        if (o.nsplit <= 0 && ns > 1) ns = std::max(1, (int)(ns * std::atoi(e) / 100.0 + 0.5));
-      }
-      pc.bk = split() ? 16 : 32;
-      pc.nsplit = std::max(1, std::min(ns, std::max(1, KS / 2)));
-    } else {
-    const int KC = cin_pad / 32;
-    const long long blocks = (long long)((in->H + halo_tile_th(halo) - 1) / halo_tile_th(halo)) * ((in->W + 15) / 16) *
-                             (pc.CoutW / halo_tile_co(halo));
-    // split-K: aim at ONE machine-wide wave of workgroups (256); go towards two only while the K loop per slice stays
-    // long (> 6 chunks = 54 tap steps), and keep the fp32 partials (written + re-read by the finish kernel at
-    // ~4.5 TB/s) under ~24 MB.  Measured per layer in profiles/r01_splitk_ablation.txt.
-    int ns = 1;
-    if (o.nsplit > 0) {
-      ns = o.nsplit;
-    } else if (halo == 4 && o.logits_out && cout <= 4 && (cin_pad == 64 || cin_pad == 128) && o.res_mode == RES_NONE && o.act == ACT_NONE &&
-               cstride == 1 && !(dev_option_is("VP_HEAD_CONV", '0'))) {
-      ns = 1;  // a head's logits convolution goes to kernels_head.hip (persistent workgroups: needs no split on any map size)
-    } else if (blocks < 256 && split()) {
-      // parity mode (measured per layer with VP_NSPLIT_FORCE = 1..16, profiles/r02_splitk_sweep_fp16x3.txt): ONE full round of
-      // workgroups at two per CU -- ns = floor(512 / blocks), at most one slice per input chunk.  A little past 512 (the fp16
-      // rule gave 540 / 600 workgroups on the 20x40 / 40x80 layers) a second, nearly empty round costs 10-20 % of the layer.
-      ns = (int)std::max<long long>(1, 512 / blocks);
-      const double slice_mb = (double)M * pc.CoutW * 4.0 / 1e6;
-      while (ns > 2 && ns * slice_mb > 24.0) --ns;
-    } else if (blocks < 256) {
-      ns = (int)((256 + blocks - 1) / blocks);
-      while (KC / ns > 6 && blocks * ns < 512) ++ns;
-      const double slice_mb = (double)M * pc.CoutW * 4.0 / 1e6;
-      while (ns > 2 && ns * slice_mb > 24.0) --ns;
-      ns = std::min(ns, std::max(1, KC / 2));
-    }
-    if (const char* e = dev_option("VP_NSPLIT_PCT")) {  // developer knob (split-K sweeps): percentage applied to the heuristic's factor
-      if (o.nsplit <= 0 && ns > 1) ns = std::max(1, (int)(ns * std::atoi(e) / 100.0 + 0.5));
-    }
-    if (const char* e = dev_option("VP_NSPLIT_FORCE")) {  // developer knob: one factor for every layer the heuristic splits
-      if (o.nsplit <= 0 && ns > 1) ns = std::max(1, std::atoi(e));
-    }
-    pc.nsplit = std::max(1, std::min(ns, KC));
-    if (halo == 6) pc.nsplit = 1;  // one 8-wave workgroup per CU, >= 160 tiles: no split-K shape
-    // 64-channel tiles of the parity mode: the pipelined kernel's 64-channel shape (halo tile 8: same tiles, same split factor as
-    // halo tile 3, three workgroups per CU).  Measured on MI355X (SceneSeg, us, halo tile 3 -> tile 8): decode_layer_0..3 70.5 /
-    // 48.1 / 82.6 / 60.2 -> 77.9 / 54.6 / 90.2 / 65.6, decode_layer_5 98.6 -> 106.5, decode_layer_9 (128 -> 64 channels on
-    // 320x640) 108.0 -> 102.2; 389 -> 381 frames/s with it everywhere.  So: only the short-K big-map case (as for tile 7);
-    // VP_X3_C64=1 wherever the epilogue fits (plain, or anything behind split-K), =0 nowhere.
-    if ((halo == 3 || halo == 2) && !split() && !fp8_storage() && o.tile < 0 && cin_pad % 64 == 0 && ncols == 64 && !o.logits_out && !o.in2 && cstride == 1) {
-      // fp16 engines, 64-channel outputs on the big maps (decode_layer_9: 128 -> 64 channels on 320x640): the pipelined 64-channel shape
-      const char* e8 = dev_option("VP_F16_BIG");
-      const bool plain8 = (o.act == ACT_GELU || o.act == ACT_NONE) && o.res_mode == RES_NONE && o.post_act == ACT_NONE;
-      if (plain8 && e8 && e8[0] != '0' && M >= 65536) {   // measured level with the halo kernel (decode_layer_9: 52.2 -> 52.0 us): only when forced
-        halo = 8;
-        pc.tile = 108;
-        pc.nsplit = 1;
-      }
-    }
-    if (halo == 3 && split() && o.tile < 0 && cin_pad % 32 == 0 && !o.logits_out && !o.in2 && cstride == 1) {
-      const char* e8 = dev_option("VP_X3_C64");
-      const bool plain8 = (o.act == ACT_GELU || o.act == ACT_NONE) && o.res_mode == RES_NONE && o.post_act == ACT_NONE;
-      const bool fits = plain8 || pc.nsplit > 1;
-      const bool want8 = e8 ? e8[0] == '1' : (pc.nsplit == 1 && cin_pad <= 128 && M >= 65536);
-      if (fits && want8) {
-        halo = 8;
-        pc.tile = 108;
-      }
-    }
-    // round 5: 64-channel tiles of the parity mode on 16x16 pixels with the four waves side by side (halo tile 9: every wave 64 channels x 64 pixels, 8
-    // fragment reads per 12 MFMAs instead of 6 per 6).  Built for the 64-channel-output layers without split-K on VERDICT round 4's reading that they are
-    // fragment-read-bound; MEASURED SLOWER (profiles/r05_x3_t16_ab.txt): decode_layer_5 99.2 -> 135.1 us (200 workgroups of four waves = one wave per
-    // SIMD on 200 CUs), decode_layer_9 103.9 -> 110.6 us (800 tiles on 512 slots: two rounds), frames/s level (412.8 against 412.7).  Kept as a shape
-    // (tile 109, tests), selected only by VP_X3_T16=1.
-    if ((halo == 3 || halo == 8) && split() && o.tile < 0 && pc.nsplit == 1 && cin_pad % 32 == 0 && !o.logits_out && !o.in2 && cstride == 1 &&
-        (o.act == ACT_GELU || o.act == ACT_NONE) && o.res_mode == RES_NONE && o.post_act == ACT_NONE && dev_option_is("VP_X3_T16", '1') && M >= 12800) {
-      halo = 9;
-      pc.tile = 109;
-    }
-    }
-  } else {
-    ConvOpts og = o;
-    if (fp8_storage() && og.tile < 0) og.tile = 2;   // the generic kernel's 64 x 64 tile carries the byte-weight staging path (kernels_conv.hip W8)
-    choose_conv_cfg(M, ncols, cin_pad, ks, og, &pc);
-  }
-  // VP_WEIGHTS_FP8: real e4m3 storage where the layer's kernel stages its weights through registers (the generic GEMM kernel and the halo
-  // kernel's tiles 0-5: every matrix layer of AutoDrive); the LDS-DMA / register-stationary kernels copy weight images verbatim and keep
-  // de-quantised fp16 planes
-  const bool w8 = fp8_storage() && ((halo < 0 && pc.tile == 2) || halo == 3 || halo == 4);
-  // fp16 engines on the pipelined kernels (halo tiles 6 - 8 without the lo plane): 64-channel chunks, the chunk's halves in two plane arrays
-  const bool k64 = halo >= 6 && halo <= 9 && !split();
-  const bool k32map = halo == 11 && !split();   // map kernel in the fp16 engines: 32-channel steps, the step's halves in the two plane arrays
-  std::vector<half_t> hi(w8 ? 0 : (size_t)taps * pc.CoutW * cin_pad / ((k64 || k32map) ? 2 : 1), (half_t)0.0f), lo(((split() || k64 || k32map) && !w8) ? hi.size() : 0, (half_t)0.0f);
-  std::vector<uint8_t> codes(w8 ? (size_t)taps * pc.CoutW * cin_pad : 0, (uint8_t)0);
-  RowScale rs = row_prescale(w.data(), cout, (size_t)cin * taps, pc.CoutW);
-  if (w8)   // the rows' quantisation scales instead of the power-of-two prescale (e4m3 values need none: |q| in [2^-9, 448] are normal fp16 numbers)
-    for (int co = 0; co < cout; ++co) {
-      float amax = 0.0f;
-      for (size_t i = 0; i < (size_t)cin * taps; ++i) amax = std::max(amax, std::fabs(w[(size_t)co * cin * taps + i]));
-      rs.post[co] = fp8_row_scale(amax);
-      rs.pre[co] = 1.0f / rs.post[co];
-    }
-  parallel_rows(cout, [&](int co_begin, int co_end) {
-  for (int co = co_begin; co < co_end; ++co)
-    for (int ci = 0; ci < cin; ++ci)
-      for (int t = 0; t < taps; ++t) {
-        const float v = w[((size_t)co * cin + ci) * taps + t];
-        // generic kernel: [tap][CoutW][Cin] ; halo kernel: [cin/32][tap][CoutW][32] (contiguous per-tap tiles)
-        // halo tiles 6 / 7 (kernels_conv3x3_x3.hip) copy weight tiles to LDS by LDS-DMA, a LINEAR copy: the tile is stored
-        // in its LDS image order, i.e. with the 16-byte chunks of a row XOR-swizzled by (row >> 2) & 3
-        const int ci_sw = (halo >= 6 && halo <= 9) ? ((((ci & 31) >> 3) ^ ((co >> 2) & 3)) << 3 | (ci & 7)) : (ci & 31);
-        const size_t d = k32map ? conv3x3_map_pack_index_k32(co, ci, t, cin_pad)
-                         : halo == 12 ? conv3x3_map2_pack_index(co, ci, t, cin_pad)
-                         : halo == 11 ? conv3x3_map_pack_index(co, ci, t, cin_pad)
-                         : k64     ? ((((size_t)(ci >> 6) * 9 + t) * pc.CoutW + co) * 32 + ci_sw)
-                         : halo >= 0 ? ((((size_t)(ci >> 5) * 9 + t) * pc.CoutW + co) * 32 + ci_sw)
-                                   : (((size_t)t * pc.CoutW + co) * cin_pad + ci);
-        if (w8) {
-          if (!(std::fabs(v) <= 65504.0f)) throw RangeError("weight " + std::to_string(v) + " is outside the fp16 range the matrix pipe carries (|w| <= 65504): re-scale the checkpoint");
-          codes[d] = e4m3_encode(v / rs.post[co]);   // v / S is on the e4m3 grid up to the fold's float rounding: the nearest code IS the quantiser's
-          continue;
-        }
-        half_t h, l;
-        split_half(v, rs.pre[co], &h, &l);
-        if (k64) {
-          ((ci >> 5) & 1 ? lo : hi)[d] = h;
-          continue;
-        }
-        if (k32map) {
-          ((ci >> 4) & 1 ? lo : hi)[d] = h;
-          continue;
-        }
-        hi[d] = h;
-        if (split()) lo[d] = l;
-      }
-  });
-  std::vector<float> bias(pc.CoutW, 0.0f);
-  for (int co = 0; co < cout; ++co) bias[co] = b[co];
-  if (w8) {
-    pc.w8 = dupload(codes);
-    wbytes_[0] += codes.size();
-  } else {
-    pc.w_hi = dupload(hi);
-    pc.w_lo = (split() || k64 || k32map) ? dupload(lo) : nullptr;
-    wbytes_[1] += 2 * (hi.size() + lo.size());
-  }
-  pc.bias = dupload(bias);
-  pc.wscale = dupload(rs.post);
   Act* out = nullptr;
   int store = STORE_NHWC;
   if (o.logits_out) {
@@ -591,32 +691,26 @@ Act* Engine::add_conv(const std::string& name, const Act* in, const std::vector<
   } else {
     out = out_override ? out_override : new_act(name, cout, in->H / cstride, in->W / cstride);
   }
-  push_conv_op(name, in, pc, ks, ncols, o, out, store, cout);
+  push_conv_op(name, in, pc, ks, round_up(cout, 32), o, out, store, cout);
   return out;
 }
 
-// The small-map up-sampling GEMMs go to the LDS-DMA pipelined kernel (kernels_gemm_dma.hip; tile 6).  Measured per layer on
-// MI355X (SceneSeg neck, us, old -> new): parity mode 42.1 / 41.0 / 42.2 -> 37.9 / 37.7 / 37.7 and +2.8 % frames/s with three
-// frames in flight (fewer workgroups at a higher rate leave CUs to the other frames); fp16 30.4 / 23.4 / 25.4 -> 26.8 / 26.8 /
-// 21.7: the fp16 engines take it from 2048 pixels up only.  VP_GEMM_DMA=1: wherever the shape fits, =0: never.
-bool Engine::gemm_dma_wanted(int H, int W, int ncols, int cin_pad, int cin2_pad, int cstore) const {
-  const int M = H * W;
-  const char* e = dev_option("VP_GEMM_DMA");
-  if (e && e[0] == '0') return false;
-  if (!split() && M < 2048 && !(e && e[0] == '1')) return false;
-  const char* rs = dev_option("VP_CONVT_RS");  // the register-stationary kernel's shapes are its own (and keep the plain weight layout)
-  if (!(rs && rs[0] == '0') && convt_rs_shape_case(H, W, cin_pad, cin2_pad, ncols, cstore) != 0) return false;
-  return gemm_dma_shape_ok(M, ncols, cin_pad, cin2_pad, cstore);
+// ConvTranspose2d(k2,s2) [+ the 1x1 skip link as a K extension, cs >= 0 channels behind cin_pad]: wt [cin][cout][2][2], ws [cout][cs] -> GEMM rows
+// n = (dy*2+dx)*cpad + co over input pixels, the prescale per GEMM row over BOTH weight sets of its K axis, the biases summed
+static HostWeights pack_convT_rows(const std::vector<float>& wt, const std::vector<float>& bt, const float* ws, const float* bs, int cin, int cin_pad,
+                                   int cs, int cs_pad, int cout, int cpad, const ConvChoice& c, bool split, int keep_bits) {
+  const int kw = cin_pad + cs_pad;
+  auto weight = [&](int r, int k) {  // wt: [ci][co][dy][dx], q = dy*2+dx
+    const int q = r / cout, co = r - q * cout;
+    return k < cin ? wt[((size_t)k * cout + co) * 4 + q] : ws[(size_t)co * cs + (k - cin)];
+  };
+  return pack_weight_rows(
+      4 * cout, cin + cs, c.CoutW, (size_t)c.CoutW * kw, c.layout, split, false, keep_bits, weight, [&](int r) { return bs ? bt[r % cout] + bs[r % cout] : bt[r % cout]; },
+      [&](int r) { return (r / cout) * cpad + r % cout; },
+      [&](int n, int k) { return std::pair<size_t, int>(pack_index(c.layout, n, k < cin ? k : cin_pad + (k - cin), 0, kw, c.CoutW), 0); });
 }
 
-// split-K factor of that kernel: towards ~160 workgroups while a slice keeps >= 8 K steps (VP_GEMM_DMA_NSPLIT: developer knob)
-int Engine::gemm_dma_nsplit(int M, int ncols, int kw) const {
-  if (const char* e = dev_option("VP_GEMM_DMA_NSPLIT")) return std::max(1, std::atoi(e));
-  const int tiles = ((M + 127) / 128) * (ncols / 256), steps = kw / 32;
-  int ns = 1;
-  while (tiles * ns < 128 && steps / (ns + 1) >= 8) ++ns;
-  return ns;
-}
+static const char* const kGemmDmaShape = "LDS-DMA GEMM kernel (tile 6): ConvTranspose k2 s2 (+ skip link) + bias, 4 * Cout and Cout multiples of 256, K >= 256, >= 128 pixels: ";
 
 // ConvTranspose2d(k2,s2): w [cin][cout][2][2] -> GEMM rows n = (dy*2+dx)*Cout_pad + co over input pixels.
 Act* Engine::add_convT(const std::string& name, const Act* in, const std::vector<float>& w, const std::vector<float>& b, int cout,
@@ -626,7 +720,6 @@ Act* Engine::add_convT(const std::string& name, const Act* in, const std::vector
   Act* out = new_act(name, cout, in->H * 2, in->W * 2);
   const int cpad = out->C;
   const int ncols = 4 * cpad;
-  PackedConv pc;
   ConvOpts oo = o;
   oo.pixel_shuffle = true;
   // parity mode: 128-channel tiles with 32-channel K blocks (measured with VP_CONVT_TILE / VP_CONVT_BK over all tiles:
@@ -635,42 +728,17 @@ Act* Engine::add_convT(const std::string& name, const Act* in, const std::vector
     oo.tile = 0;
     if (oo.bk < 0) oo.bk = 32;
   }
-  if (gemm_dma_wanted(in->H, in->W, ncols, cin_pad, 0, cpad) && o.tile < 0) {
+  if (gemm_dma_wanted(in->H, in->W, ncols, cin_pad, 0, cpad, split()) && o.tile < 0) {
     oo.tile = 6;
     oo.nsplit = gemm_dma_nsplit(in->H * in->W, ncols, cin_pad);
   }
-  if (const char* e = dev_option("VP_CONVT_TILE")) oo.tile = std::atoi(e);  // developer knobs (tile / BK sweeps)
-  if (const char* e = dev_option("VP_CONVT_BK")) oo.bk = std::atoi(e);
-  choose_conv_cfg(in->H * in->W, ncols, cin_pad, 1, oo, &pc);
-  if (pc.tile == 6 && !(gemm_dma_shape_ok(in->H * in->W, ncols, cin_pad, 0, cpad) && pc.CoutW == ncols))  // before the weights are packed in its layout
-    throw std::invalid_argument("LDS-DMA GEMM kernel (tile 6): ConvTranspose k2 s2 (+ skip link) + bias, 4 * Cout and Cout multiples of 256, K >= 256, >= 128 pixels: " + name);
-  std::vector<half_t> hi((size_t)pc.CoutW * cin_pad, (half_t)0.0f), lo(split() ? hi.size() : 0, (half_t)0.0f);
-  std::vector<float> bias(pc.CoutW, 0.0f), post(pc.CoutW, 1.0f);
-  parallel_rows(4 * cout, [&](int r_begin, int r_end) {
-    for (int r = r_begin; r < r_end; ++r) {
-      const int q = r / cout, co = r - q * cout;
-      const int n = q * cpad + co;
-      bias[n] = b[co];
-      float amax = 0.0f;   // prescale per GEMM row n = (quadrant, output channel)
-      for (int ci = 0; ci < cin; ++ci) amax = std::max(amax, std::fabs(w[((size_t)ci * cout + co) * 4 + q]));
-      const int sexp = prescale_exp(amax);
-      const float pre = std::ldexp(1.0f, sexp);
-      post[n] = std::ldexp(1.0f, -sexp);
-      for (int ci = 0; ci < cin; ++ci) {
-        const float v = w[((size_t)ci * cout + co) * 4 + q];  // [ci][co][dy][dx], q = dy*2+dx
-        half_t h, l;
-        split_half(v, pre, &h, &l);
-        const size_t d = pc.tile == 6 ? gemm_dma_pack_index(n, ci, cin_pad) : (size_t)n * cin_pad + ci;
-        hi[d] = h;
-        if (split()) lo[d] = l;
-      }
-    }
-  });
-  pc.w_hi = dupload(hi);
-  pc.w_lo = split() ? dupload(lo) : nullptr;
-  wbytes_[1] += 2 * (hi.size() + lo.size());
-  pc.bias = dupload(bias);
-  pc.wscale = dupload(post);
+  oo.tile = option_int("VP_CONVT_TILE", oo.tile);  // developer knobs (tile / BK sweeps)
+  oo.bk = option_int("VP_CONVT_BK", oo.bk);
+  const ConvChoice c = choose_gemm_cfg(in->H * in->W, ncols, cin_pad, 1, oo.tile, oo.bk, oo.nsplit);
+  if (c.tile == 6 && !(gemm_dma_shape_ok(in->H * in->W, ncols, cin_pad, 0, cpad) && c.CoutW == ncols))  // before the weights are packed in its layout
+    throw std::invalid_argument(kGemmDmaShape + name);
+  PackedConv pc(c);
+  upload_packed(&pc, pack_convT_rows(w, b, nullptr, nullptr, cin, cin_pad, 0, 0, cout, cpad, c, split(), wlo_keep_));
   push_conv_op(name, in, pc, 1, ncols, o, out, STORE_SHUFFLE2, cout);
   return out;
 }
@@ -687,7 +755,6 @@ Act* Engine::add_convT_skip(const std::string& up_name, const std::string& skip_
   if (wt.size() != (size_t)cin * cout * 4) throw std::runtime_error("convT weight size mismatch: " + up_name);
   if (ws.size() != (size_t)cout * cs) throw std::runtime_error("skip conv weight size mismatch: " + skip_name);
   if (skip_in->H != in->H * 2 || skip_in->W != in->W * 2) throw std::runtime_error("skip tensor size mismatch: " + skip_name);
-  const char* env = dev_option("VP_FUSE_SKIP");
   const int cpad = round_up(cout, 32);
   const int ncols = 4 * cpad;
   ConvOpts o;
@@ -697,16 +764,15 @@ Act* Engine::add_convT_skip(const std::string& up_name, const std::string& skip_
     o.tile = 0;
     o.bk = 32;
   }
-  if (gemm_dma_wanted(in->H, in->W, ncols, cin_pad, cs_pad, cpad)) {
+  if (gemm_dma_wanted(in->H, in->W, ncols, cin_pad, cs_pad, cpad, split())) {
     o.tile = 6;
     o.nsplit = gemm_dma_nsplit(in->H * in->W, ncols, cin_pad + cs_pad);
   }
-  if (const char* e = dev_option("VP_CONVT_TILE")) o.tile = std::atoi(e);
-  PackedConv pc;
-  choose_conv_cfg(in->H * in->W, ncols, cin_pad + cs_pad, 1, o, &pc);
-  if (pc.tile == 6 && !(gemm_dma_shape_ok(in->H * in->W, ncols, cin_pad, cs_pad, cpad) && pc.CoutW == ncols))
+  o.tile = option_int("VP_CONVT_TILE", o.tile);
+  const ConvChoice c = choose_gemm_cfg(in->H * in->W, ncols, cin_pad + cs_pad, 1, o.tile, o.bk, o.nsplit);
+  if (c.tile == 6 && !(gemm_dma_shape_ok(in->H * in->W, ncols, cin_pad, cs_pad, cpad) && c.CoutW == ncols))
     throw std::invalid_argument("LDS-DMA GEMM kernel (tile 6): shape not covered: " + up_name);
-  const bool fusable = (cpad % conv_tile_co(pc.tile) == 0 && !(env && env[0] == '0')) || pc.tile == 6;
+  const bool fusable = (cpad % conv_tile_co(c.tile) == 0 && !dev_option_is("VP_FUSE_SKIP", '0')) || c.tile == 6;
   if (!fusable) {
     Act* u = add_convT(up_name, in, wt, bt, cout, ConvOpts{});
     ConvOpts so;
@@ -716,35 +782,8 @@ Act* Engine::add_convT_skip(const std::string& up_name, const std::string& skip_
     return u;
   }
   Act* out = new_act(up_name, cout, in->H * 2, in->W * 2);
-  const int kw = cin_pad + cs_pad;
-  std::vector<half_t> hi((size_t)pc.CoutW * kw, (half_t)0.0f), lo(split() ? hi.size() : 0, (half_t)0.0f);
-  std::vector<float> bias(pc.CoutW, 0.0f), post(pc.CoutW, 1.0f);
-  parallel_rows(4 * cout, [&](int r_begin, int r_end) {
-    for (int r = r_begin; r < r_end; ++r) {
-      const int q = r / cout, co = r - q * cout;
-      const int n = q * cpad + co;
-      bias[n] = bt[co] + bs[co];
-      float amax = 0.0f;   // prescale per GEMM row over BOTH weight sets of its K axis
-      for (int k = 0; k < cin + cs; ++k) amax = std::max(amax, std::fabs(k < cin ? wt[((size_t)k * cout + co) * 4 + q] : ws[(size_t)co * cs + (k - cin)]));
-      const int sexp = prescale_exp(amax);
-      const float pre = std::ldexp(1.0f, sexp);
-      post[n] = std::ldexp(1.0f, -sexp);
-      for (int k = 0; k < cin + cs; ++k) {
-        const float v = k < cin ? wt[((size_t)k * cout + co) * 4 + q] : ws[(size_t)co * cs + (k - cin)];
-        const size_t col = k < cin ? k : cin_pad + (k - cin);
-        half_t h, l;
-        split_half(v, pre, &h, &l);
-        const size_t d = pc.tile == 6 ? gemm_dma_pack_index(n, (int)col, kw) : (size_t)n * kw + col;
-        hi[d] = h;
-        if (split()) lo[d] = l;
-      }
-    }
-  });
-  pc.w_hi = dupload(hi);
-  pc.w_lo = split() ? dupload(lo) : nullptr;
-  wbytes_[1] += 2 * (hi.size() + lo.size());
-  pc.bias = dupload(bias);
-  pc.wscale = dupload(post);
+  PackedConv pc(c);
+  upload_packed(&pc, pack_convT_rows(wt, bt, ws.data(), bs.data(), cin, cin_pad, cs, cs_pad, cout, cpad, c, split(), wlo_keep_));
   push_conv_op(up_name + "+" + skip_name.substr(skip_name.rfind('.') == std::string::npos ? 0 : skip_name.rfind('.') + 1), in, pc, 1, ncols, o,
                out, STORE_SHUFFLE2, cout);
   return out;

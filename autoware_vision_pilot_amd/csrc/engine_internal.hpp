@@ -1,5 +1,6 @@
-// Internal to the engine's translation units (engine.cpp = weights + plan, engine_dispatch.cpp = per-layer kernel selection and weight
-// packing, engine_io.cpp = frame path, graph replay, outputs, visualisation).  Not part of the library's interface.
+// Internal to the engine's translation units (engine.cpp = weights + plan; engine_dispatch.cpp = choose_conv, the pure per-layer kernel choice, the one
+// weight packer and the emission of a convolution's launch; engine_upconv.cpp = the composed up-sampling stages; engine_io.cpp = frame path, graph replay,
+// outputs, visualisation).  Not part of the library's interface.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -20,6 +21,45 @@ static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // VP_PLAN_OVERRIDE (engine_dispatch.cpp): one layer's kernel choice forced by name -- the in-frame tuner's lever (tools/plan_search.py)
 bool plan_override(const std::string& name, int* tile, int* nsplit);
 
+// ---- the dispatch rules (engine_dispatch.cpp): free functions of the layer's shape that read dev_option() and nothing else -- no engine, no device
+enum WeightLayout {
+  GEMM_ROWS,     // generic GEMM kernel: [tap][CoutW][K]
+  HALO32,        // halo kernel: [K / 32][tap][CoutW][32] (contiguous per-tap tiles)
+  X3_SWIZZLED,   // pipelined kernels, parity mode: HALO32 with the 16-byte chunks of a row XOR-swizzled (the LDS image, copied linearly by LDS-DMA)
+  X1_K64,        // pipelined kernels, fp16 engines: 64-channel chunks, the chunk's halves in the two plane arrays
+  MAP,           // map kernel (halo tile 11), parity mode
+  MAP_K32,       // map kernel in the fp16 engines: 32-channel steps, the step's halves in the two plane arrays
+  MAP2,          // map kernel, 64-channel slabs (halo tile 12)
+  GEMM_DMA       // LDS-DMA GEMM kernel (tile 6)
+};
+struct ConvQuery {
+  int H = 0, W = 0, stride = 1;          // INPUT map, convolution stride
+  int cin = 0, cin_pad = 0, cout = 0, ks = 1;
+  int act = ACT_NONE, res_mode = RES_NONE, post_act = ACT_NONE;
+  bool logits_out = false, in2 = false;
+  int tile = -1, bk = -1, nsplit = -1;   // caller-forced (ConvOpts, VP_PLAN_OVERRIDE); < 0 / <= 0 = the rule's
+  bool split = false, fp8_storage = false, plan_latency = false;
+};
+struct ConvChoice {
+  int tile = 0;                          // 0 - 6: generic GEMM / LDS-DMA GEMM tile, 100 + halo tile: the 3x3 kernels
+  int bk = 32, CoutW = 0, nsplit = 1;
+  WeightLayout layout = GEMM_ROWS;
+  bool w8 = false;                       // VP_WEIGHTS_FP8 as storage: e4m3 codes in that layout
+};
+ConvChoice choose_conv(const std::string& name, const ConvQuery& q);
+// the generic GEMM kernel's tile, K block and split factor for an M x ncols x (ks * ks * cin_pad) problem; tile / bk / nsplit: forced, < 0 / <= 0 = the rule's
+ConvChoice choose_gemm_cfg(int M, int ncols, int cin_pad, int ks, int tile, int bk, int nsplit);
+bool gemm_dma_wanted(int H, int W, int ncols, int cin_pad, int cin2_pad, int cstore, bool split);
+int gemm_dma_nsplit(int M, int ncols, int kw);
+// element (co, ci, tap) of a layer's weights in `layout`; pack_plane: 1 = the value lives in the SECOND plane array (layouts that carry one fp16 value per weight)
+size_t pack_index(WeightLayout layout, int co, int ci, int tap, int cin_pad, int CoutW);
+inline int pack_plane(WeightLayout layout, int ci) { return layout == X1_K64 ? (ci >> 5) & 1 : (layout == MAP_K32 ? (ci >> 4) & 1 : 0); }
+struct HostWeights {
+  std::vector<half_t> hi, lo;    // fp16 planes (lo: parity mode, or the second half of X1_K64 / MAP_K32) ...
+  std::vector<uint8_t> codes;    // ... or e4m3 codes
+  std::vector<float> bias, post; // [rows_alloc]: bias, 2^-prescale (fp8 row scale) of the rows; 0 / 1 in the padding
+};
+
 constexpr float kBnEps = 1e-5f;  // torchvision efficientnet_b0 BatchNorm2d default
 
 struct Folded {
@@ -30,9 +70,9 @@ Folded fold_conv(const WeightBlob& blob, const std::string& conv, const std::str
 Folded fold_conv_bn(const WeightBlob& blob, const std::string& p);    // torchvision Conv2dNormActivation: `.0` conv, `.1` norm
 Folded fold_conv_norm(const WeightBlob& blob, const std::string& p);  // common_layers.py:5-14 Conv: `.conv`, `.norm`
 // (hi, lo) fp16 planes of v * pre, pre = the weight row's power-of-two prescale (an exact product); throws RangeError when v itself is
-// beyond the fp16 range or not finite
-void split_half(float v, float pre, half_t* hi, half_t* lo);
-half_t truncate_lo(half_t lo);   // experiment knob VP_WLO_KEEP_BITS (engine.cpp); identity by default
+// beyond the fp16 range or not finite.  keep_bits: explicit mantissa bits the low plane keeps (experiment knob VP_WLO_KEEP_BITS, Engine::wlo_keep_; 10 = all)
+void split_half(float v, float pre, half_t* hi, half_t* lo, int keep_bits = 10);
+half_t truncate_lo(half_t lo, int keep_bits);
 // Per-output-row power-of-two PRESCALE of a weight matrix (round 4).  Unscaled, lo = fp16(w - fp16(w)) of a typical decoder weight is an fp16
 // SUBNORMAL (kaiming std 0.013 at K = 11520: |lo| <= 4e-6, spacing 6e-8) and the pair carries ~17 bits instead of 22.  With s such that the
 // row maximum lands in [2^13, 2^14) every weight within 2^-10 of the row maximum keeps both planes normal, and any smaller one is still exact

@@ -23,12 +23,12 @@ inline void tap_of(int q, int tt, int* a, int* d) {
 }
 
 // (hi, lo) fp16 planes of v * pre from a double (the composed weights are carried in fp64 until here)
-inline void split_half_d(double v, double pre, half_t* hi, half_t* lo) {
+inline void split_half_d(double v, double pre, half_t* hi, half_t* lo, int keep_bits) {
   const double x = v * pre;
   if (!(std::fabs(x) <= 65504.0)) throw RangeError("composed up-sampling weight " + std::to_string(v) + " is outside the fp16 range the matrix pipe carries: re-scale the checkpoint");
   const half_t h = (half_t)x;
   *hi = h;
-  *lo = truncate_lo((half_t)(x - (double)h));
+  *lo = truncate_lo((half_t)(x - (double)h), keep_bits);
 }
 
 }  // namespace
@@ -211,10 +211,10 @@ Act* Engine::add_upconv(const std::string& name, const Act* in, const Act* skip_
             const size_t dst = upconv_pack_index(phase, d.step0 + k, co, i & 31, S, coutw);
             if (x1) {   // one fp16 value per weight; plane = which half of the 64-channel chunk
               half_t h, l;
-              split_half_d(row[chm * d.ch0 + i], pre, &h, &l);
+              split_half_d(row[chm * d.ch0 + i], pre, &h, &l, wlo_keep_);
               (i >> 5 ? lo : hi)[dst] = h;
             } else {
-              split_half_d(row[d.ch0 + i], pre, &hi[dst], &lo[dst]);
+              split_half_d(row[d.ch0 + i], pre, &hi[dst], &lo[dst], wlo_keep_);
             }
           }
         }

@@ -507,7 +507,6 @@ int vp_layer_kernel(const vp_engine* e, int i, const char** kernel) {
   *kernel = e->impl->ops()[i].kernel.c_str();
   return VP_OK;
 }
-// launch geometry beyond the tag ("nsplit=4", "groups=32", "nsplit=2 wgs=128"; "" when the tag says it all): what vp_plan_hash mixes in third
 // AutoSteerOnnxEngine::postProcess (production_release/src/inference/autosteer_engine.cpp:160-185): first maximum wins, angle = class - 30
 float vp_autosteer_angle(const float* logits, int classes) {
   if (!logits || classes < 1) return 0.0f;
@@ -520,6 +519,7 @@ float vp_autosteer_angle(const float* logits, int classes) {
     }
   return static_cast<float>(best - 30);
 }
+// launch geometry beyond the tag ("nsplit=4", "groups=32", "nsplit=2 wgs=128"; "" when the tag says it all): what vp_plan_hash mixes in third
 int vp_layer_launch(const vp_engine* e, int i, const char** launch) {
   if (!e || !e->impl || !launch || i < 0 || i >= (int)e->impl->ops().size()) return VP_ERR_ARG;
   *launch = e->impl->ops()[i].launch.c_str();

@@ -287,7 +287,7 @@ def vw_blob(kind, seed):
 
 def test_kernel_plan_is_the_committed_one(emu_lib, monkeypatch):
     """WHICH kernel every layer of every network gets (vp_layer_kernel), both precisions, against tests/golden/kernel_plan.json: the
-    dispatch rules of engine.cpp (tile shapes, split-K, the pipelined / register-stationary / LDS-DMA kernels, fused decode) are host
+    dispatch rules of csrc/engine_dispatch.cpp (choose_conv: tile shapes, split-K, the pipelined / register-stationary / LDS-DMA kernels, fused decode) are host
     code and untested as rules otherwise -- a wrong predicate silently picks a slower kernel.  Deliberate rule changes regenerate the file
     with tools/dump_kernel_plan.py and show up as a reviewable diff."""
     import json
@@ -426,3 +426,33 @@ def test_latency_plan_is_the_committed_one(emu_lib):
                 assert "encoder" not in name and "context" not in name and "upsample" not in name, name
             first = min(i for i, (d, l) in enumerate(zip(rows_d, rows_l)) if d[1:] != l[1:])
             assert all("decode_layer" in r[0] or r[0] in ("finite_probe", "lane_ring") for r in rows_l[first:]), key   # all behind the context block
+
+
+def test_plan_under_every_option_is_the_committed_one(emu_lib):
+    """The plan hash (every launch's name, kernel tag and launch string) under every developer option the rules of csrc/engine_dispatch.cpp read, one
+    setting at a time, against tests/golden/plan_options.json (tools/dump_plan_options.py: the settings, the engines and why SceneSeg takes them on top
+    of VP_UPCONV=0) -- the branches tools/plan_search.py and the A/B profiles run through, which the default-option plan files cannot see.  A setting
+    under which creation throws must throw the same message.  On a mismatch: the launches that differ from the engine's base plan under that setting."""
+    import json
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import dump_plan_options as dpo
+
+    want = json.load(open(dpo.GOLDEN))
+    engines = dpo.engines()
+    assert sorted(want) == sorted(e[0] for e in engines)
+    bad = []
+    for key, kind, prec, kw, blob in engines:
+        settings = dpo.settings_of(kind, prec)
+        assert sorted(want[key]) == sorted(dpo.setting_key(o) for o in settings), key
+        for o in settings:
+            got = dpo.plan_under(emu_lib, kind, blob(kind), prec, kw, o)
+            if got != want[key][dpo.setting_key(o)]:
+                base = dpo.plan_under(emu_lib, kind, blob(kind), prec, kw, settings[0], rows=True)
+                rows = dpo.plan_under(emu_lib, kind, blob(kind), prec, kw, o, rows=True)
+                moved = [r for r in rows or [] if r not in base]
+                bad.append((key, dpo.setting_key(o), got, want[key][dpo.setting_key(o)]))
+                print(f"{key} {dpo.setting_key(o)}: {got} != {want[key][dpo.setting_key(o)]}; launches that differ from {dpo.setting_key(settings[0])}:")
+                for r in moved:
+                    print("   ", r)
+    assert not bad, bad

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: (re)write tests/golden/kernel_plan.json -- the kernel tag the engine's dispatch rules give EVERY layer of every
+"""Developer tool: (re)write tests/golden/kernel_plan.json -- the kernel tag the engine's dispatch rules (csrc/engine_dispatch.cpp choose_conv, csrc/engine_upconv.cpp) give EVERY layer of every
 network in both precisions (vp_layer_kernel), taken from the CPU-emulated engine (tests/emul; the rules are host code and see the
 MI355X's 256 CUs there too).  tests/test_engine_emulated.py::test_kernel_plan_is_the_committed_one compares against it, so a predicate
 regression that silently picks another kernel fails the CPU suite.  Also writes tests/golden/kernel_plan_latency.json: the same eight
