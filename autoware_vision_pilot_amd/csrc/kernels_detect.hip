@@ -185,6 +185,166 @@ hipError_t launch_detect_decode_nms(const DetectParams& p, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------- the Python wrapper's letterbox and decode
+// Models/inference/auto_speed_infer.py decodes differently from the C++ engine above: Pillow's resize, a second sigmoid, NMS in letterbox pixels
+// whatever the classes, back-mapping only of what is kept.  tests/autospeed_py_ref.py is the restatement these two kernels are held to.
+//
+// resize_letterbox + ToTensor (:24-42): Image.new("RGB", size, (114, 114, 114)), paste at (pad_x, pad_y).  The resized planes come from
+// launch_pil_resample as u8 / 255 (one IEEE division: torchvision's ToTensor), so the paste is a copy; the grey is the same division of 114.
+__global__ __launch_bounds__(256) void letterbox_paste_kernel(const LetterboxPasteParams p) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= p.out_w) return;
+  const int rx = x - p.pad_x, ry = y - p.pad_y;
+  const bool inside = (unsigned)rx < (unsigned)p.new_w && (unsigned)ry < (unsigned)p.new_h;
+  const float grey = __fdiv_rn(114.0f, 255.0f);
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    p.out[((size_t)c * p.out_h + y) * p.out_w + x] = inside ? p.src[((size_t)c * p.new_h + ry) * p.new_w + rx] : grey;
+}
+
+hipError_t launch_letterbox_paste(const LetterboxPasteParams& p, hipStream_t st) {
+  if (!p.src || !p.out || p.new_w < 1 || p.new_h < 1 || p.pad_x < 0 || p.pad_y < 0 || p.pad_x + p.new_w > p.out_w || p.pad_y + p.new_h > p.out_h)
+    return hipErrorInvalidValue;
+  VP_LAUNCH(letterbox_paste_kernel, dim3((p.out_w + 255) / 256, p.out_h), dim3(256), 0, st, p);
+}
+
+// post_process_predictions + nms + the back-mapping of inference() (:63-83, :100-106), one workgroup with the phases of detect_decode_nms_kernel:
+//   A  score = max_c sigmoid(raw score) (the head's scores are sigmoids already; the wrapper applies a second one, :69), class = first maximum
+//      (torch.max), `score > conf` kept (:70).  Scores are > 0, so the key order is the float order; ~index keeps equal scores in box order.
+//   B  the same descending bitonic sort.
+//   C  corners cx -+ w / 2 (xywh2xyxy :45-52) in LETTERBOX pixels -> scratch.
+//   D  greedy suppression whatever the classes: IoU = inter / (area_i + area_j - inter) > iou (torchvision.ops.nms: no +1; a 0 / 0 is NaN and
+//      suppresses nothing).
+//   E  compaction in order; a kept box goes (x - pad) / scale and is clamped to [0, orig] (:101-106) as it is written, six floats a row.
+__device__ __forceinline__ float agnostic_iou(const f32x4_t a, const f32x4_t b) {
+  const float iw = fmaxf(0.0f, __fsub_rn(fminf(a[2], b[2]), fmaxf(a[0], b[0])));
+  const float ih = fmaxf(0.0f, __fsub_rn(fminf(a[3], b[3]), fmaxf(a[1], b[1])));
+  const float inter = __fmul_rn(iw, ih);
+  const float area_a = __fmul_rn(__fsub_rn(a[2], a[0]), __fsub_rn(a[3], a[1]));
+  const float area_b = __fmul_rn(__fsub_rn(b[2], b[0]), __fsub_rn(b[3], b[1]));
+  return __fdiv_rn(inter, __fsub_rn(__fadd_rn(area_a, area_b), inter));
+}
+
+__global__ __launch_bounds__(kDetThreads) void detect_agnostic_nms_kernel(const DetectAgnosticParams p, const int P_max) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char det_smem[];
+  unsigned long long* const keys = reinterpret_cast<unsigned long long*>(det_smem);      // [P_max]
+  unsigned char* const flags = det_smem + (size_t)P_max * 8;                              // [P_max] 1 = suppressed
+  __shared__ int n_cand;
+  __shared__ int scan[kDetThreads];
+  const int tid = threadIdx.x, nb = p.num_boxes;
+  if (tid == 0) n_cand = 0;
+  __syncthreads();
+  // ---- A
+  for (int i = tid; i < nb; i += kDetThreads) {
+    float best = sigmoid_f(p.raw[(size_t)4 * nb + i]);
+    int cls = 0;
+    for (int c = 5; c < p.num_attrs; ++c) {
+      const float s = sigmoid_f(p.raw[(size_t)c * nb + i]);
+      if (s > best || (s != s && best == best)) {   // torch.max: the first maximum; a NaN wins and stays (the box is then dropped below)
+        best = s;
+        cls = c - 4;
+      }
+    }
+    if (!(best > p.conf_thresh)) continue;
+    const int slot = atomicAdd(&n_cand, 1);
+    keys[slot] = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
+    p.cls[i] = cls;
+  }
+  __syncthreads();
+  const int n = n_cand;
+  int P = 1;
+  while (P < n) P <<= 1;
+  for (int t = n + tid; t < P; t += kDetThreads) keys[t] = 0ull;
+  __syncthreads();
+  // ---- B
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < P; t += kDetThreads) {
+        const int u = t ^ j;
+        if (u > t) {
+          const unsigned long long a = keys[t], b = keys[u];
+          if (((t & k) == 0) ? a < b : a > b) {
+            keys[t] = b;
+            keys[u] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  // ---- C
+  for (int r = tid; r < n; r += kDetThreads) {
+    const int i = (int)(0xFFFFFFFFu - (unsigned)(keys[r] & 0xFFFFFFFFull));
+    const float cx = p.raw[i], cy = p.raw[(size_t)nb + i], w = p.raw[(size_t)2 * nb + i], h = p.raw[(size_t)3 * nb + i];
+    const float hw = __fdiv_rn(w, 2.0f), hh = __fdiv_rn(h, 2.0f);
+    f32x4_t b;
+    b[0] = __fsub_rn(cx, hw);
+    b[1] = __fsub_rn(cy, hh);
+    b[2] = __fadd_rn(cx, hw);
+    b[3] = __fadd_rn(cy, hh);
+    *reinterpret_cast<f32x4_t*>(p.boxes + (size_t)r * 4) = b;
+    flags[r] = 0;
+  }
+  __threadfence_block();
+  __syncthreads();
+  // ---- D
+  for (int i = 0; i < n; ++i) {
+    if (flags[i]) continue;  // uniform: nothing was written since the last barrier
+    const f32x4_t bi = *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)i * 4);
+    for (int j = i + 1 + tid; j < n; j += kDetThreads) {
+      if (flags[j]) continue;
+      if (agnostic_iou(bi, *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)j * 4)) > p.iou_thresh) flags[j] = 1;
+    }
+    __syncthreads();
+  }
+  // ---- E
+  const int per = (n + kDetThreads - 1) / kDetThreads, r0 = min(n, tid * per), r1 = min(n, r0 + per);
+  int mine = 0;
+  for (int r = r0; r < r1; ++r) mine += flags[r] ? 0 : 1;
+  scan[tid] = mine;
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int t = 0; t < kDetThreads; ++t) {
+      const int v = scan[t];
+      scan[t] = run;
+      run += v;
+    }
+    p.count[0] = run;
+    p.count[1] = n;
+  }
+  __syncthreads();
+  const float px = (float)p.pad_x, py = (float)p.pad_y, ow = (float)p.orig_w, oh = (float)p.orig_h;
+  int pos = scan[tid];
+  for (int r = r0; r < r1; ++r) {
+    if (flags[r]) continue;
+    if (pos < p.out_cap) {
+      const f32x4_t b = *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)r * 4);
+      const int i = (int)(0xFFFFFFFFu - (unsigned)(keys[r] & 0xFFFFFFFFull));
+      float* o = p.out + (size_t)pos * 6;
+      o[0] = fminf(fmaxf(__fdiv_rn(__fsub_rn(b[0], px), p.scale), 0.0f), ow);
+      o[1] = fminf(fmaxf(__fdiv_rn(__fsub_rn(b[1], py), p.scale), 0.0f), oh);
+      o[2] = fminf(fmaxf(__fdiv_rn(__fsub_rn(b[2], px), p.scale), 0.0f), ow);
+      o[3] = fminf(fmaxf(__fdiv_rn(__fsub_rn(b[3], py), p.scale), 0.0f), oh);
+      o[4] = __uint_as_float((unsigned)(keys[r] >> 32));
+      o[5] = (float)p.cls[i];
+    }
+    ++pos;
+  }
+}
+
+hipError_t launch_detect_agnostic_nms(const DetectAgnosticParams& p, hipStream_t st) {
+  if (!p.raw || !p.boxes || !p.cls || !p.count || (p.out_cap > 0 && !p.out) || p.num_attrs < 5 || p.num_boxes < 1 || p.num_boxes > kDetectMaxBoxes || p.out_cap < 0 ||
+      !(p.scale > 0.0f))
+    return hipErrorInvalidValue;
+  int P = 1;
+  while (P < p.num_boxes) P <<= 1;
+  const size_t lds = (size_t)P * 9;
+  static LdsAttrOnce once;
+  if (hipError_t e = set_max_dynamic_lds(once, reinterpret_cast<const void*>(detect_agnostic_nms_kernel), 9 * kDetectMaxBoxes); e != hipSuccess) return e;
+  hipLaunchKernelGGL(detect_agnostic_nms_kernel, dim3(1), dim3(kDetThreads), lds, st, p, P);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ detector head decode
 // AutoSpeedHead.forward in eval mode behind the per-level convolutions (auto_speed_head.py:57-66) with DFL (common_layers.py:143-146), the three
 // levels in one launch: a thread per anchor reads its 64 box channels and nc class channels as hi (+ lo) and writes one column of the fp32

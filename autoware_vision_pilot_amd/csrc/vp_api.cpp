@@ -332,6 +332,15 @@ int vp_unregister_frames(const void* pool) {
     return VP_ERR_HIP;
   }
 }
+// the same four numbers from creation on: the plan fixes them (vp_output_shape answers only after an inference, as the reference backend does)
+int vp_output_dims(const vp_engine* e, int64_t shape[4]) {
+  if (!e || !e->impl || !shape) return VP_ERR_ARG;
+  shape[0] = 1;
+  shape[1] = e->impl->out_c();
+  shape[2] = e->impl->out_h();
+  shape[3] = e->impl->out_w();
+  return VP_OK;
+}
 int vp_output_shape(const vp_engine* e, int64_t shape[4]) {
   if (!e || !e->impl || !shape) return VP_ERR_ARG;
   if (!e->impl->have_outputs()) {

@@ -5,6 +5,7 @@
     Scene3DNetworkInfer(checkpoint_path).inference(image)            -> fp32   [320,640,1] scene_3d_infer.py:12-58
     DomainSegNetworkInfer(checkpoint_path).inference(image)          -> fp32   [320,640,1] (0/1) domain_seg_infer.py:12-60
     EgoLanesNetworkInfer(checkpoint_path).inference(image)           -> fp32   [3,80,160]  ego_lanes_infer.py:8-62
+    AutoSpeedNetworkInfer(checkpoint_path).inference(PIL any size)   -> list of [x1, y1, x2, y2, score, class]  auto_speed_infer.py:5-108
 
 ``checkpoint_path`` is a VPW1 blob (``weights.export_checkpoint`` converts the reference ``.pth``), or blob bytes.
 ``image`` is anything with ``.size == (640, 320)`` convertible by ``numpy.asarray`` to HxWx3 uint8 RGB (a PIL image),
@@ -256,3 +257,49 @@ class AutoSteerNetworkInfer:
         self.model.infer(image)
         out = self.model.logits().reshape(2, 64)
         return out[0].copy(), out[1].copy()
+
+
+class AutoSpeedNetworkInfer:
+    """Models/inference/auto_speed_infer.py AutoSpeedNetworkInfer behind the engine (the AutoSpeed detector network, version 'n'):
+    ``inference(image)`` on a PIL RGB image of any size (anything ``numpy.asarray`` turns into HxWx3 uint8 RGB) -> a list of
+    ``[x1, y1, x2, y2, score, class]`` lists in the image's own coordinates, ``[]`` when nothing is kept.  The wrapper's own arithmetic, all of it on
+    the device (vp_hip.h vp_detect_infer_pil): Pillow's ``Image.BILINEAR`` letterbox into (1024, 512) on grey 114 and ``ToTensor`` bit for bit
+    (:24-42), a sigmoid over the head's already-sigmoid class scores, ``score > 0.6``, class-agnostic NMS at 0.45 in letterbox pixels (:63-83),
+    the kept boxes mapped back and clamped (:100-106).  These are NOT the results of the C++ AutoSpeedOnnxEngine (``lib.Detector.infer``), which
+    decodes differently.  The reference casts the input to fp16 (``.half()``) because it runs a half model on CUDA; here the fp32 tensor feeds
+    whichever precision the engine was created with.  ``checkpoint_path`` is a VPW1 blob (path or bytes).  ``act_scale`` (parity mode only) stores
+    every activation tensor with a power-of-two scale of its own and calibrates the scales on the first image it sees (vp_hip.h VP_ACT_SCALE)."""
+
+    def __init__(self, checkpoint_path="", precision="fp16", gpu_id=0, act_scale=False):
+        if checkpoint_path is None or len(checkpoint_path) == 0:
+            raise ValueError("No path to checkpiont file provided in class initialization")
+        self.train_size = (1024, 512)  # target width, height
+        self.conf_thres, self.iou_thres = 0.6, 0.45   # post_process_predictions' defaults (:63)
+        self.device = f"hip:{gpu_id}"
+        self.model = _lib.Engine("autospeed", checkpoint_path, precision=precision, gpu_id=gpu_id, act_scale=act_scale)
+        _, attrs, _, boxes = self.model.output_dims()   # before any inference: output_shape() answers only after one
+        self._detector = _lib.Detector(self.train_size[1], self.train_size[0], max_boxes=boxes, max_attrs=attrs, gpu_id=gpu_id)
+        self._detector.attach(self.model)
+        self._calibrate = bool(act_scale)
+
+    def resize_letterbox(self, img):
+        """(scale, pad_x, pad_y) of the letterbox of ``img`` (:24-34; the padded image itself stays on the device)."""
+        orig_w, orig_h = img.size
+        scale, _, _, pad_x, pad_y = _lib.detect_geometry_pil(self.train_size[1], self.train_size[0], orig_h, orig_w)
+        return scale, pad_x, pad_y
+
+    def inference(self, image):
+        a = np.asarray(image)
+        if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+            raise ValueError("image must be HxWx3 uint8 RGB")
+        if self._calibrate:   # first image: run it (the uncalibrated pass may be refused), calibrate on it, then answer it
+            self._calibrate = False
+            try:
+                self._detector.infer_pil(a, self.conf_thres, self.iou_thres, cap=0)
+            except _lib.VpRangeError:
+                pass
+            self.model.calibrate_range()
+        rows, n = self._detector.infer_pil(a, self.conf_thres, self.iou_thres)
+        if n > len(rows):   # more kept than the first buffer holds: once more with room for all of them
+            rows, n = self._detector.infer_pil(a, self.conf_thres, self.iou_thres, cap=n)
+        return rows.tolist()

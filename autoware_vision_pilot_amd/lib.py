@@ -69,6 +69,7 @@ _SIGS = {
     "vp_register_frames": (C.c_int, [C.c_void_p, C.c_size_t]),
     "vp_unregister_frames": (C.c_int, [C.c_void_p]),
     "vp_output_shape": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "vp_output_dims": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "vp_set_finite_check": (C.c_int, [_P, C.c_int]),
     "vp_infer_multi": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int, C.c_int]),
     "vp_enqueue_multi": (C.c_int, [_P, C.POINTER(_P), C.c_int]),
@@ -116,6 +117,11 @@ _SIGS = {
     "vp_detect_postprocess": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
     "vp_detect_attach": (C.c_int, [_P, _P]),
     "vp_detect_infer": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
+    "vp_detect_geometry_pil": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int)]),
+    "vp_detect_preprocess_pil": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "vp_detect_postprocess_agnostic": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
+    "vp_detect_infer_pil": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
     "vp_op_detect_head_decode": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_char_p, C.c_size_t]),
     "vp_op_upsample2_cat": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_char_p, C.c_size_t]),
     "vp_op_dwconv3x3": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_char_p, C.c_size_t]),
@@ -501,6 +507,12 @@ class Engine:
         """(1, C, H, W) of the output tensor without fetching it (vp_output_shape)."""
         sh = (C.c_int64 * 4)()
         self._ck(self._lib.vp_output_shape(self._h, sh))
+        return tuple(int(v) for v in sh)
+
+    def output_dims(self):
+        """(1, C, H, W) of the output tensor as the plan fixes it: answered before the first inference too (vp_output_dims)."""
+        sh = (C.c_int64 * 4)()
+        self._ck(self._lib.vp_output_dims(self._h, sh))
         return tuple(int(v) for v in sh)
 
     def set_pinned_staging(self, on):
@@ -1016,3 +1028,52 @@ class Detector:
         det = out[:k].copy()
         det[:, 5] = out[:k, 5].view(np.int32).astype(np.float32)   # class_id is an int in the struct
         return det, n.value
+
+    # ---- the Python wrapper's arithmetic (Models/inference/auto_speed_infer.py; vp_hip.h vp_detect_*_pil / _agnostic)
+    @staticmethod
+    def _frame(frame_u8):
+        f = np.asarray(frame_u8)
+        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.strides[2] != 1 or f.strides[1] != 3:
+            f = np.ascontiguousarray(f, dtype=np.uint8)
+        return f
+
+    def preprocess_pil(self, frame_u8, pixel_format=VP_RGB8):
+        """vp_detect_preprocess_pil: HxWx3 uint8 frame (RGB as a PIL image gives it, or VP_BGR8) -> ([3][net_h][net_w] float32 planes R, G, B, (scale, pad_x, pad_y)),
+        Pillow's BILINEAR letterbox + ToTensor bit for bit."""
+        f = self._frame(frame_u8)
+        out = np.empty((3, self.net_h, self.net_w), np.float32)
+        self._check(self._lib.vp_detect_preprocess_pil(self._h, _ptr(f), f.shape[0], f.shape[1], f.strides[0], int(pixel_format), _ptr(out)), "vp_detect_preprocess_pil")
+        return out, self.letterbox()
+
+    def postprocess_agnostic(self, raw, conf_thresh, iou_thresh, cap=None):
+        """vp_detect_postprocess_agnostic: raw [num_attrs][num_boxes] float32 -> ([n][6] float32 rows x1, y1, x2, y2, score, class; total kept)."""
+        raw = np.ascontiguousarray(raw, dtype=np.float32)
+        cap = raw.shape[1] if cap is None else cap
+        out = np.zeros((max(cap, 1), 6), np.float32)
+        n = C.c_int()
+        self._check(self._lib.vp_detect_postprocess_agnostic(self._h, _ptr(raw), 0, raw.shape[0], raw.shape[1], float(conf_thresh), float(iou_thresh), _ptr(out), cap,
+                                                             C.byref(n)), "vp_detect_postprocess_agnostic")
+        return out[:min(n.value, cap)].copy(), n.value
+
+    def infer_pil(self, frame_u8, conf_thresh, iou_thresh, cap=None, pixel_format=VP_RGB8):
+        """vp_detect_infer_pil: frame -> ([n][6] float32 rows x1, y1, x2, y2, score, class; total kept) through the attached network."""
+        f = self._frame(frame_u8)
+        cap = 1024 if cap is None else cap
+        out = np.zeros((max(cap, 1), 6), np.float32)
+        n = C.c_int()
+        rc = self._lib.vp_detect_infer_pil(self._h, _ptr(f), f.shape[0], f.shape[1], f.strides[0], int(pixel_format), float(conf_thresh), float(iou_thresh), _ptr(out),
+                                           cap, C.byref(n))
+        if rc == -5:
+            raise VpRangeError(f"vp_detect_infer_pil failed ({rc}): {self._lib.vp_detect_last_error(self._h).decode(errors='replace')}")
+        self._check(rc, "vp_detect_infer_pil")
+        return out[:min(n.value, cap)].copy(), n.value
+
+
+def detect_geometry_pil(net_h, net_w, h, w):
+    """vp_detect_geometry_pil: (scale, new_w, new_h, pad_x, pad_y) of the Python wrapper's resize_letterbox for an h x w frame (host only)."""
+    s = C.c_double()
+    v = [C.c_int() for _ in range(4)]
+    rc = load().vp_detect_geometry_pil(net_h, net_w, h, w, C.byref(s), *[C.byref(x) for x in v])
+    if rc != 0:
+        raise ValueError(f"vp_detect_geometry_pil: a {h} x {w} frame has no letterbox in {net_h} x {net_w}")
+    return (s.value,) + tuple(x.value for x in v)

@@ -220,6 +220,7 @@ int vp_unregister_frames(const void* pool);
 /* {1, C, H, W} of the output tensor WITHOUT touching the device: vp_logits also returns the shape but fetches a de-selected tensor
  * (vp_set_outputs) on the way.  Same state rule as vp_logits: VP_ERR_STATE before the first inference (onnx_runtime_backend.cpp:86-91). */
 int vp_output_shape(const vp_engine* e, int64_t shape[4]);
+int vp_output_dims(const vp_engine* e, int64_t shape[4]);  /* the same shape, answered from creation on (vp_output_shape: VP_ERR_STATE before the first inference) */
 /* ACTIVATION SCALE (engines created with VP_ACT_SCALE; closes the RANGE GUARD's per-frame case below for AutoDrive, AutoSpeed and AutoSteer).
  * vp_calibrate_range: runs the plan eagerly, launch by launch, over the RESIDENT frame -- AutoDrive: after vp_infer_pair (whatever it returned) over that
  *   pair, after vp_upload_frame over that frame as both halves of the pair; AutoSteer: over the frame of the last vp_upload_frame / vp_infer; AutoSpeed:
@@ -406,6 +407,25 @@ int vp_detect_postprocess(vp_detect* d, const float* raw, int raw_on_device, int
 int vp_detect_attach(vp_detect* d, vp_engine* net);
 int vp_detect_infer(vp_detect* d, const uint8_t* bgr, int h, int w, int stride_bytes, float conf_thresh, float iou_thresh, vp_detection* out,
                     int out_cap, int* count);
+/* The same stages in the arithmetic of the PYTHON wrapper, Models/inference/auto_speed_infer.py AutoSpeedNetworkInfer, which no thresholds of the
+ * entries above reproduce (infer.AutoSpeedNetworkInfer is built on these; they share the handle, its buffers and its stored geometry with them):
+ *   vp_detect_preprocess_pil  resize_letterbox + ToTensor (:24-42): scale = min(net_w / w, net_h / h) in double, new size int(w * scale), Pillow's
+ *       antialiased Image.BILINEAR resize bit for bit (the tables of vp_resample_coeffs, u8 between the horizontal and the vertical pass), pasted at
+ *       pad = (net - new) / 2 on a canvas of 114s, planes R, G, B of u8 / 255 (one fp32 division).  pixel_format: VP_RGB8 (a PIL image) or VP_BGR8.
+ *       The geometry is stored for the decode and reported by vp_detect_letterbox (scale rounded to float).
+ *   vp_detect_postprocess_agnostic  post_process_predictions + the back-mapping (:63-83, :100-106): score = max over the classes of
+ *       sigmoid(raw score), class = the first maximum, `score > conf_thresh` kept; corners cx -+ w / 2; greedy suppression by descending score
+ *       (equal scores in box order) at IoU > iou_thresh WHATEVER the classes, IoU = inter / (a + b - inter) in letterbox pixels (the
+ *       torchvision.ops.nms rule); kept boxes -> (x - pad) / scale, clamped to the frame.  out_rows6: [out_cap][6] floats x1, y1, x2, y2, score,
+ *       class; *count and out_cap as vp_detect_postprocess.
+ *   vp_detect_infer_pil  both around the attached network: the streams, events and the one wait of vp_detect_infer; VP_ERR_RANGE likewise.
+ * vp_detect_geometry_pil (host only): the letterbox geometry alone; VP_ERR_ARG when the resized image would be empty. */
+int vp_detect_geometry_pil(int net_h, int net_w, int h, int w, double* scale, int* new_w, int* new_h, int* pad_x, int* pad_y);
+int vp_detect_preprocess_pil(vp_detect* d, const uint8_t* frame, int h, int w, int stride_bytes, int pixel_format, float* dst_host_chw);
+int vp_detect_postprocess_agnostic(vp_detect* d, const float* raw, int raw_on_device, int num_attrs, int num_boxes, float conf_thresh, float iou_thresh,
+                                   float* out_rows6, int out_cap, int* count);
+int vp_detect_infer_pil(vp_detect* d, const uint8_t* frame, int h, int w, int stride_bytes, int pixel_format, float conf_thresh, float iou_thresh,
+                        float* out_rows6, int out_cap, int* count);
 
 /* ---- single-operator entries of the detector network's kernels (unit tests; not used by callers) -----------
  * vp_op_detect_head_decode: box [3 levels one after the other][64][h_l][w_l] and cls [..][nc][h_l][w_l] fp32 CHW logits, level l of size

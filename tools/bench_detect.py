@@ -5,7 +5,9 @@
 python tools/bench_detect.py
 python tools/bench_detect.py --network   the detector NETWORK as an engine of this library (VP_AUTOSPEED) instead: the per-launch table
     (vp_profile_layers), in-graph time per frame, vp_detect_infer host-to-host p50 / p99 over 1000 calls on a 1280 x 720 frame and, in the same run for
-    scale, the AutoDrive engine's p50 and the two stages around a host-run network (512 x 1024 letterbox; decode + NMS of the network's own tensor)."""
+    scale, the AutoDrive engine's p50 and the two stages around a host-run network (512 x 1024 letterbox; decode + NMS of the network's own tensor).
+python tools/bench_detect.py --python-wrapper   the Python wrapper's twin on a 1280 x 720 frame: infer.AutoSpeedNetworkInfer.inference p50, vp_detect_infer_pil
+    and vp_detect_infer host-to-host p50 / p99 on the same handle and frame, the network's in-graph time, and the two letterboxes and decodes alone."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -71,6 +73,48 @@ def network():
     print(json.dumps(out))
 
 
+def python_wrapper():
+    from PIL import Image
+
+    from autoware_vision_pilot_amd import infer, synthetic, weights as vw
+
+    bgr = synthetic.synthetic_frame(720, 1280, 21)
+    rgb = np.ascontiguousarray(bgr[:, :, ::-1])
+    image = Image.fromarray(rgb)
+    out = {"library": lib.version()}
+
+    def p(fn, n, warm=30):
+        for _ in range(warm):
+            fn()
+        t = []
+        for _ in range(n):
+            t0 = time.perf_counter(); fn(); t.append((time.perf_counter() - t0) * 1e6)
+        return round(float(np.percentile(t, 50)), 1), round(float(np.percentile(t, 99)), 1)
+
+    for prec in ("fp16x3", "fp16"):
+        twin = infer.AutoSpeedNetworkInfer(vw.pack_state_dict(synthetic.make_autospeed_state_dict(5)), precision=prec)
+        det, eng = twin._detector, twin.model
+        out[f"{prec}_rows_kept"] = len(twin.inference(image))
+        out[f"{prec}_inference_1280x720_p50_us"], out[f"{prec}_inference_1280x720_p99_us"] = p(lambda: twin.inference(image), 1000)
+        out[f"{prec}_detect_infer_pil_1280x720_p50_us"], out[f"{prec}_detect_infer_pil_1280x720_p99_us"] = p(lambda: det.infer_pil(rgb, 0.6, 0.45, cap=300), 1000)
+        out[f"{prec}_detect_infer_1280x720_p50_us"], out[f"{prec}_detect_infer_1280x720_p99_us"] = p(lambda: det.infer(bgr, 0.6, 0.45, cap=300), 1000)
+        g = []
+        for _ in range(200):
+            eng.timer_begin(); eng.enqueue(); g.append(eng.timer_end() * 1e3)
+        out[f"{prec}_network_in_graph_p50_us"] = round(float(np.percentile(g, 50)), 1)
+        raw = eng.logits().reshape(8, 10752).copy()
+        out[f"{prec}_letterbox_pil_p50_us"] = p(lambda: det.preprocess_pil(rgb), 200, 20)[0]
+        out[f"{prec}_letterbox_p50_us"] = p(lambda: det.preprocess(bgr), 200, 20)[0]
+        out[f"{prec}_postprocess_agnostic_own_raw_p50_us"] = p(lambda: det.postprocess_agnostic(raw, 0.6, 0.45), 200, 20)[0]
+        out[f"{prec}_postprocess_own_raw_p50_us"] = p(lambda: det.postprocess(raw, 0.6, 0.45), 200, 20)[0]
+        det.close()
+        eng.close()
+    print(json.dumps(out))
+
+
+if "--python-wrapper" in sys.argv[1:]:
+    python_wrapper()
+    sys.exit(0)
 if "--network" in sys.argv[1:]:
     network()
     sys.exit(0)

@@ -42,17 +42,15 @@ def check_conditions(raw, geom, hw):
     return n, gap
 
 
-def main(reference_root):
+def reference_module(reference_root, sd):
+    """the reference's own AutoSpeedNetwork ('n', the synthetic class count) with the state dict `sd` loaded strictly, in eval mode"""
     import torch
 
-    import autospeed_net_ref as ref
     from autoware_vision_pilot_amd import synthetic
-    from oracle import autospeed
 
     sys.path.insert(0, reference_root)
     from Models.model_components.auto_speed.auto_speed_network import AutoSpeedNetwork
 
-    sd = synthetic.make_autospeed_state_dict(WEIGHT_SEED)
     model = AutoSpeedNetwork().build_model("n", synthetic.AS_NUM_CLASSES)
     want_keys = [k for k in model.state_dict() if not k.endswith("num_batches_tracked")]
     assert want_keys == list(sd), "key list / order differs from the reference module's"
@@ -63,6 +61,18 @@ def main(reference_root):
             full[k] = torch.zeros_like(v)
     model.load_state_dict(full, strict=True)
     model.eval()
+    return model
+
+
+def main(reference_root):
+    import torch
+
+    import autospeed_net_ref as ref
+    from autoware_vision_pilot_amd import synthetic
+    from oracle import autospeed
+
+    sd = synthetic.make_autospeed_state_dict(WEIGHT_SEED)
+    model = reference_module(reference_root, sd)
     taps = {}
     model.fpn.register_forward_hook(lambda m, i, o: taps.update(fpn=[t.detach().clone() for t in o]))
     out = {"weight_seed": WEIGHT_SEED, "frames": np.array(FRAMES), "conf": np.float32(CONF), "iou": np.float32(IOU), "box_step": BOX_STEP, "tap_step": TAP_STEP}
