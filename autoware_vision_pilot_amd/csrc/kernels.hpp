@@ -145,6 +145,11 @@ struct Detection {       // == autoware_pov::vision::autospeed::Detection (detec
   int class_id;
 };
 
+// Decode + NMS, one kernel with two rules (kernels_detect.hip detect_nms_kernel).  kDetectPerClass: the C++ engines' postProcess + applyNMS.
+// kDetectAgnostic: the Python wrapper's (Models/inference/auto_speed_infer.py:63-83, :100-106; vp_detect_postprocess_agnostic / _infer_pil):
+// score = max over the classes of sigmoid(raw score), class = the first maximum, `score > conf` kept, greedy suppression at IoU > iou whatever the
+// classes on the corner boxes in LETTERBOX pixels (the torchvision.ops.nms rule); only the kept boxes go (x - pad) / scale and are clamped to the frame.
+enum DetectRule { kDetectPerClass = 0, kDetectAgnostic = 1 };
 struct DetectParams {
   const float* raw;      // [num_attrs][num_boxes]: cx, cy, w, h (letterbox pixels), then the class scores
   int num_attrs, num_boxes;
@@ -153,35 +158,20 @@ struct DetectParams {
   int pad_x, pad_y, orig_w, orig_h;
   float* boxes;          // scratch [num_boxes][4]: candidate boxes in sorted order
   int* cls;              // scratch [num_boxes]
-  Detection* out;        // [out_cap]
+  Detection* out;        // [out_cap] rows of 24 bytes: a Detection; under kDetectAgnostic six floats (class_id holds the class as a float's bits)
   int out_cap;
   int* count;            // [2]: detections kept (may exceed out_cap: only out_cap are written), candidates above the threshold
 };
 constexpr int kDetectMaxBoxes = 16384;
 
-// The Python wrapper's form of the same two stages (Models/inference/auto_speed_infer.py:15-43, :63-83, :100-106; vp_detect_*_pil / _agnostic).
-// Letterbox: Pillow's BILINEAR resize is launch_pil_resample (mean 0, std 1, norm_form 0: its planes are u8 / 255, one IEEE division) into `src`;
-// this kernel pastes those planes into the canvas of 114 / 255.
+// The Python wrapper's letterbox (Models/inference/auto_speed_infer.py:15-43; vp_detect_preprocess_pil): Pillow's BILINEAR resize is
+// launch_pil_resample (mean 0, std 1, norm_form 0: its planes are u8 / 255, one IEEE division) into `src`; this kernel pastes those planes into the
+// canvas of 114 / 255.
 struct LetterboxPasteParams {
   const float* src;      // [3][new_h][new_w] planes R, G, B of the resized image
   int new_w, new_h, pad_x, pad_y;
   int out_h, out_w;
   float* out;            // [3][out_h][out_w]
-};
-// Decode + NMS: score = max over the classes of sigmoid(raw score), class = the first maximum, `score > conf` kept, corners cx -+ w / 2, greedy
-// suppression in descending score order (equal scores in box order) at IoU > iou whatever the classes, IoU = inter / (a + b - inter) on the corner boxes
-// in LETTERBOX pixels (the torchvision.ops.nms rule); the kept boxes then go (x - pad) / scale and are clamped to the frame.
-struct DetectAgnosticParams {
-  const float* raw;      // [num_attrs][num_boxes] as DetectParams
-  int num_attrs, num_boxes;
-  float conf_thresh, iou_thresh;
-  float scale;
-  int pad_x, pad_y, orig_w, orig_h;
-  float* boxes;          // scratch [num_boxes][4]: candidate corners in letterbox pixels, sorted order
-  int* cls;              // scratch [num_boxes]
-  float* out;            // [out_cap][6]: x1, y1, x2, y2, score, class (as a float)
-  int out_cap;
-  int* count;            // [2] as DetectParams
 };
 
 struct FcParams {
@@ -364,9 +354,9 @@ hipError_t launch_dwconv(const DwParams& p, hipStream_t st);
 bool mbconv_front_supported(const MbFrontParams& p);
 hipError_t launch_mbconv_front(const MbFrontParams& p, hipStream_t st);
 hipError_t launch_letterbox(const LetterboxParams& p, hipStream_t st);
-hipError_t launch_detect_decode_nms(const DetectParams& p, hipStream_t st);
+hipError_t launch_detect_nms(const DetectParams& p, DetectRule rule, hipStream_t st);
+inline hipError_t launch_detect_decode_nms(const DetectParams& p, hipStream_t st) { return launch_detect_nms(p, kDetectPerClass, st); }  // the earlier name: callers built against it keep compiling
 hipError_t launch_letterbox_paste(const LetterboxPasteParams& p, hipStream_t st);
-hipError_t launch_detect_agnostic_nms(const DetectAgnosticParams& p, hipStream_t st);
 bool mbconv_back_supported(const MbBackParams& p);
 hipError_t launch_mbconv_back(const MbBackParams& p, hipStream_t st);
 hipError_t launch_pool_partial(const PoolParams& p, hipStream_t st);

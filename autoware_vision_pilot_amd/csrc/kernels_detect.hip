@@ -2,8 +2,9 @@
 // different model family and not part of this library; these are the two stages the reference's engines wrap around it on the CPU
 // (VisionPilot/middleware_recipes/common/backends/autospeed/onnxruntime_engine.cpp; tensorrt_engine.cpp holds the same code):
 //   letterbox_kernel           preprocessAutoSpeed (:71-113): resize (aspect kept) into a 114-grey canvas, / 255, planes R, G, B
-//   detect_decode_nms_kernel   postProcess + applyNMS (:170-290): strict-'>' class argmax from 0, confidence threshold, xywh -> xyxy, letterbox
+//   detect_nms_kernel<false>   postProcess + applyNMS (:170-290): strict-'>' class argmax from 0, confidence threshold, xywh -> xyxy, letterbox
 //                              space -> image, clamp, sort by confidence, greedy same-class IoU suppression
+// and the same two stages as the Python wrapper computes them (letterbox_paste_kernel, detect_nms_kernel<true>).
 // Integer / index work is bit-exact against oracle/autospeed.py; the fp32 arithmetic is the reference's, expression for expression, with
 // IEEE division and without contraction (__f*_rn), so the kept set and its coordinates are bit-identical too.
 #include "act_io.hpp"
@@ -41,28 +42,76 @@ hipError_t launch_letterbox(const LetterboxParams& p, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------------------- decode + NMS
-// One workgroup of 1024 threads: the stage is a few thousand boxes of 8 floats and inherently sequential at its end (greedy NMS).
-//   A  candidates: per box the class argmax and the threshold; survivors get a 64-bit key (confidence bits << 32 | ~box index) in LDS.
-//      Confidences are >= +0 (the argmax starts from 0), so their bit patterns order like the floats; ~index makes equal confidences
-//      keep the box order (the reference's std::sort leaves ties unspecified).
+// One kernel, two rules.  AGNOSTIC = false is the C++ engines' postProcess + applyNMS (onnxruntime_engine.cpp:170-290); AGNOSTIC = true is the Python
+// wrapper's post_process_predictions + nms + the back-mapping of inference() (Models/inference/auto_speed_infer.py:63-83, :100-106), which
+// tests/autospeed_py_ref.py restates.  One workgroup of 1024 threads: the stage is a few thousand boxes of 8 floats and inherently sequential at its
+// end (greedy NMS).  The rules differ in four places (det_best_class, det_to_image in C or in E, det_iou and the class test in D, the sixth word of a
+// row) and share everything else:
+//   A  candidates: per box the best class and the threshold (det_best_class); survivors get a 64-bit key (score bits << 32 | ~box index) in LDS.
+//      Scores are >= +0 under either rule, so their bit patterns order like the floats; ~index makes equal scores keep the box order (the
+//      reference's std::sort leaves ties unspecified; torchvision's nms is stable).
 //   B  bitonic sort of the keys in LDS, descending (<= 16384 keys = 128 KB).
-//   C  the sorted candidates' boxes in image coordinates -> scratch.
-//   D  greedy suppression: a kept box i suppresses later same-class boxes with IoU > threshold, all threads striding over j; boxes that
-//      are already suppressed cost nothing (the flag is uniform after the last barrier), so the barriers number the KEPT boxes.
-//   E  compaction in order (per-thread chunks, scan in LDS).
+//   C  the sorted candidates' corners cx -+ w / 2 -> scratch: mapped to the image and clamped here under the C++ rule (postProcess :198-222), left
+//      in LETTERBOX pixels under the agnostic one (xywh2xyxy :45-52).
+//   D  greedy suppression: a kept box i suppresses later boxes with IoU > threshold -- of its own class only (applyNMS :257-290) or whatever the
+//      classes (torchvision.ops.nms) -- all threads striding over j; boxes that are already suppressed cost nothing (the flag is uniform after the
+//      last barrier), so the barriers number the KEPT boxes.
+//   E  compaction in order (per-thread chunks, scan in LDS).  The agnostic rule maps and clamps a kept box only now, as its row is written
+//      (:101-106); its class is written as a float, the C++ rule's as the int of Detection.
 constexpr int kDetThreads = 1024;
 
-__device__ __forceinline__ float det_iou(const f32x4_t a, const f32x4_t b) {  // computeIoU, onnxruntime_engine.cpp:239-255
+// the best class score of box i and its class.  C++ rule: strict '>' over the raw scores starting from 0 (class -1 when none is positive).  Agnostic
+// rule: a sigmoid over every score (the head's scores are sigmoids already; the wrapper applies a second one, :69), the first maximum as torch.max
+// finds it -- a NaN wins and stays (the box is then dropped by the threshold).
+template <bool AGNOSTIC>
+__device__ __forceinline__ float det_best_class(const DetectParams& p, const int i, int* cls_out) {
+  const int nb = p.num_boxes;
+  float best = 0.0f;
+  int cls = -1, c = 4;
+  if constexpr (AGNOSTIC) {
+    best = sigmoid_f(p.raw[(size_t)4 * nb + i]);
+    cls = 0;
+    c = 5;
+  }
+  for (; c < p.num_attrs; ++c) {
+    float s = p.raw[(size_t)c * nb + i];
+    if constexpr (AGNOSTIC) s = sigmoid_f(s);
+    if (s > best || (AGNOSTIC && s != s && best == best)) {
+      best = s;
+      cls = c - 4;
+    }
+  }
+  *cls_out = cls;
+  return best;
+}
+
+// corners in letterbox pixels -> image, (x - pad) / scale clamped to [0, orig]; the two sources nest their min and max differently
+template <bool AGNOSTIC>
+__device__ __forceinline__ f32x4_t det_to_image(const f32x4_t b, const DetectParams& p) {
+  const auto one = [&](const float v, const int pad, const int orig) {
+    const float q = __fdiv_rn(__fsub_rn(v, (float)pad), p.scale), lim = (float)orig;
+    return AGNOSTIC ? fminf(fmaxf(q, 0.0f), lim) : fmaxf(0.0f, fminf(lim, q));
+  };
+  return f32x4_t{one(b[0], p.pad_x, p.orig_w), one(b[1], p.pad_y, p.orig_h), one(b[2], p.pad_x, p.orig_w), one(b[3], p.pad_y, p.orig_h)};
+}
+
+// computeIoU (onnxruntime_engine.cpp:239-255) / torchvision.ops.nms (no +1): the same expression; only the C++ code guards the division, so under
+// the agnostic rule a 0 / 0 is NaN and suppresses nothing
+template <bool AGNOSTIC>
+__device__ __forceinline__ float det_iou(const f32x4_t a, const f32x4_t b) {
   const float iw = fmaxf(0.0f, __fsub_rn(fminf(a[2], b[2]), fmaxf(a[0], b[0])));
   const float ih = fmaxf(0.0f, __fsub_rn(fminf(a[3], b[3]), fmaxf(a[1], b[1])));
   const float inter = __fmul_rn(iw, ih);
   const float area_a = __fmul_rn(__fsub_rn(a[2], a[0]), __fsub_rn(a[3], a[1]));
   const float area_b = __fmul_rn(__fsub_rn(b[2], b[0]), __fsub_rn(b[3], b[1]));
   const float uni = __fsub_rn(__fadd_rn(area_a, area_b), inter);
-  return uni > 0.0f ? __fdiv_rn(inter, uni) : 0.0f;
+  return AGNOSTIC || uni > 0.0f ? __fdiv_rn(inter, uni) : 0.0f;
 }
 
-__global__ __launch_bounds__(kDetThreads) void detect_decode_nms_kernel(const DetectParams p, const int P_max) {
+__device__ __forceinline__ int det_box_of(const unsigned long long key) { return (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull)); }
+
+template <bool AGNOSTIC>
+__global__ __launch_bounds__(kDetThreads) void detect_nms_kernel(const DetectParams p, const int P_max) {
   extern __shared__ __attribute__((aligned(16))) unsigned char det_smem[];
   unsigned long long* const keys = reinterpret_cast<unsigned long long*>(det_smem);      // [P_max]
   unsigned char* const flags = det_smem + (size_t)P_max * 8;                              // [P_max] 1 = suppressed
@@ -73,16 +122,9 @@ __global__ __launch_bounds__(kDetThreads) void detect_decode_nms_kernel(const De
   __syncthreads();
   // ---- A
   for (int i = tid; i < nb; i += kDetThreads) {
-    float best = 0.0f;
-    int cls = -1;
-    for (int c = 4; c < p.num_attrs; ++c) {
-      const float s = p.raw[(size_t)c * nb + i];
-      if (s > best) {
-        best = s;
-        cls = c - 4;
-      }
-    }
-    if (best < p.conf_thresh) continue;
+    int cls;
+    const float best = det_best_class<AGNOSTIC>(p, i, &cls);
+    if (AGNOSTIC ? !(best > p.conf_thresh) : best < p.conf_thresh) continue;
     const int slot = atomicAdd(&n_cand, 1);
     keys[slot] = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
     p.cls[i] = cls;
@@ -108,31 +150,28 @@ __global__ __launch_bounds__(kDetThreads) void detect_decode_nms_kernel(const De
       }
       __syncthreads();
     }
-  // ---- C: boxes of the sorted candidates (postProcess :198-222)
-  const float px = (float)p.pad_x, py = (float)p.pad_y, ow = (float)p.orig_w, oh = (float)p.orig_h;
+  // ---- C: corners of the sorted candidates
   for (int r = tid; r < n; r += kDetThreads) {
-    const int i = (int)(0xFFFFFFFFu - (unsigned)(keys[r] & 0xFFFFFFFFull));
+    const int i = det_box_of(keys[r]);
     const float cx = p.raw[i], cy = p.raw[(size_t)nb + i], w = p.raw[(size_t)2 * nb + i], h = p.raw[(size_t)3 * nb + i];
     const float hw = __fdiv_rn(w, 2.0f), hh = __fdiv_rn(h, 2.0f);
-    f32x4_t b;
-    b[0] = fmaxf(0.0f, fminf(ow, __fdiv_rn(__fsub_rn(__fsub_rn(cx, hw), px), p.scale)));
-    b[1] = fmaxf(0.0f, fminf(oh, __fdiv_rn(__fsub_rn(__fsub_rn(cy, hh), py), p.scale)));
-    b[2] = fmaxf(0.0f, fminf(ow, __fdiv_rn(__fsub_rn(__fadd_rn(cx, hw), px), p.scale)));
-    b[3] = fmaxf(0.0f, fminf(oh, __fdiv_rn(__fsub_rn(__fadd_rn(cy, hh), py), p.scale)));
+    f32x4_t b = {__fsub_rn(cx, hw), __fsub_rn(cy, hh), __fadd_rn(cx, hw), __fadd_rn(cy, hh)};
+    if constexpr (!AGNOSTIC) b = det_to_image<false>(b, p);
     *reinterpret_cast<f32x4_t*>(p.boxes + (size_t)r * 4) = b;
     flags[r] = 0;
   }
   __threadfence_block();
   __syncthreads();
-  // ---- D: greedy same-class suppression (applyNMS :257-290)
+  // ---- D: greedy suppression
   for (int i = 0; i < n; ++i) {
     if (flags[i]) continue;  // uniform: nothing was written since the last barrier
     const f32x4_t bi = *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)i * 4);
-    const int ci = p.cls[(int)(0xFFFFFFFFu - (unsigned)(keys[i] & 0xFFFFFFFFull))];
+    const int ci = AGNOSTIC ? 0 : p.cls[det_box_of(keys[i])];
     for (int j = i + 1 + tid; j < n; j += kDetThreads) {
       if (flags[j]) continue;
-      if (p.cls[(int)(0xFFFFFFFFu - (unsigned)(keys[j] & 0xFFFFFFFFull))] != ci) continue;
-      if (det_iou(bi, *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)j * 4)) > p.iou_thresh) flags[j] = 1;
+      if constexpr (!AGNOSTIC)
+        if (p.cls[det_box_of(keys[j])] != ci) continue;
+      if (det_iou<AGNOSTIC>(bi, *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)j * 4)) > p.iou_thresh) flags[j] = 1;
     }
     __syncthreads();
   }
@@ -157,38 +196,41 @@ __global__ __launch_bounds__(kDetThreads) void detect_decode_nms_kernel(const De
   for (int r = r0; r < r1; ++r) {
     if (flags[r]) continue;
     if (pos < p.out_cap) {
-      const f32x4_t b = *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)r * 4);
-      const int i = (int)(0xFFFFFFFFu - (unsigned)(keys[r] & 0xFFFFFFFFull));
+      f32x4_t b = *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)r * 4);
+      if constexpr (AGNOSTIC) b = det_to_image<true>(b, p);
+      const int cls = p.cls[det_box_of(keys[r])];
       Detection d;
       d.x1 = b[0];
       d.y1 = b[1];
       d.x2 = b[2];
       d.y2 = b[3];
       d.confidence = __uint_as_float((unsigned)(keys[r] >> 32));
-      d.class_id = p.cls[i];
+      d.class_id = AGNOSTIC ? (int)__float_as_uint((float)cls) : cls;
       p.out[pos] = d;
     }
     ++pos;
   }
 }
 
-hipError_t launch_detect_decode_nms(const DetectParams& p, hipStream_t st) {
-  if (!p.raw || !p.boxes || !p.cls || !p.out || !p.count || p.num_attrs < 5 || p.num_boxes < 1 || p.num_boxes > kDetectMaxBoxes || p.out_cap < 0 ||
+template <bool AGNOSTIC>
+static hipError_t launch_detect_nms_rule(const DetectParams& p, const int P, hipStream_t st) {
+  static LdsAttrOnce once;
+  if (hipError_t e = set_max_dynamic_lds(once, reinterpret_cast<const void*>(detect_nms_kernel<AGNOSTIC>), 9 * kDetectMaxBoxes); e != hipSuccess) return e;
+  hipLaunchKernelGGL(detect_nms_kernel<AGNOSTIC>, dim3(1), dim3(kDetThreads), (size_t)P * 9, st, p, P);
+  return hipGetLastError();
+}
+
+hipError_t launch_detect_nms(const DetectParams& p, DetectRule rule, hipStream_t st) {
+  if (!p.raw || !p.boxes || !p.cls || !p.count || (p.out_cap > 0 && !p.out) || p.num_attrs < 5 || p.num_boxes < 1 || p.num_boxes > kDetectMaxBoxes || p.out_cap < 0 ||
       !(p.scale > 0.0f))
     return hipErrorInvalidValue;
   int P = 1;
   while (P < p.num_boxes) P <<= 1;
-  const size_t lds = (size_t)P * 9;
-  static LdsAttrOnce once;
-  if (hipError_t e = set_max_dynamic_lds(once, reinterpret_cast<const void*>(detect_decode_nms_kernel), 9 * kDetectMaxBoxes); e != hipSuccess) return e;
-  hipLaunchKernelGGL(detect_decode_nms_kernel, dim3(1), dim3(kDetThreads), lds, st, p, P);
-  return hipGetLastError();
+  return rule == kDetectAgnostic ? launch_detect_nms_rule<true>(p, P, st) : launch_detect_nms_rule<false>(p, P, st);
 }
 
-// ------------------------------------------------------------------------------------- the Python wrapper's letterbox and decode
-// Models/inference/auto_speed_infer.py decodes differently from the C++ engine above: Pillow's resize, a second sigmoid, NMS in letterbox pixels
-// whatever the classes, back-mapping only of what is kept.  tests/autospeed_py_ref.py is the restatement these two kernels are held to.
-//
+// ---------------------------------------------------------------------------------------------- the Python wrapper's letterbox
+// Models/inference/auto_speed_infer.py letterboxes with Pillow; tests/autospeed_py_ref.py is the restatement this kernel is held to.
 // resize_letterbox + ToTensor (:24-42): Image.new("RGB", size, (114, 114, 114)), paste at (pad_x, pad_y).  The resized planes come from
 // launch_pil_resample as u8 / 255 (one IEEE division: torchvision's ToTensor), so the paste is a copy; the grey is the same division of 114.
 __global__ __launch_bounds__(256) void letterbox_paste_kernel(const LetterboxPasteParams p) {
@@ -206,143 +248,6 @@ hipError_t launch_letterbox_paste(const LetterboxPasteParams& p, hipStream_t st)
   if (!p.src || !p.out || p.new_w < 1 || p.new_h < 1 || p.pad_x < 0 || p.pad_y < 0 || p.pad_x + p.new_w > p.out_w || p.pad_y + p.new_h > p.out_h)
     return hipErrorInvalidValue;
   VP_LAUNCH(letterbox_paste_kernel, dim3((p.out_w + 255) / 256, p.out_h), dim3(256), 0, st, p);
-}
-
-// post_process_predictions + nms + the back-mapping of inference() (:63-83, :100-106), one workgroup with the phases of detect_decode_nms_kernel:
-//   A  score = max_c sigmoid(raw score) (the head's scores are sigmoids already; the wrapper applies a second one, :69), class = first maximum
-//      (torch.max), `score > conf` kept (:70).  Scores are > 0, so the key order is the float order; ~index keeps equal scores in box order.
-//   B  the same descending bitonic sort.
-//   C  corners cx -+ w / 2 (xywh2xyxy :45-52) in LETTERBOX pixels -> scratch.
-//   D  greedy suppression whatever the classes: IoU = inter / (area_i + area_j - inter) > iou (torchvision.ops.nms: no +1; a 0 / 0 is NaN and
-//      suppresses nothing).
-//   E  compaction in order; a kept box goes (x - pad) / scale and is clamped to [0, orig] (:101-106) as it is written, six floats a row.
-__device__ __forceinline__ float agnostic_iou(const f32x4_t a, const f32x4_t b) {
-  const float iw = fmaxf(0.0f, __fsub_rn(fminf(a[2], b[2]), fmaxf(a[0], b[0])));
-  const float ih = fmaxf(0.0f, __fsub_rn(fminf(a[3], b[3]), fmaxf(a[1], b[1])));
-  const float inter = __fmul_rn(iw, ih);
-  const float area_a = __fmul_rn(__fsub_rn(a[2], a[0]), __fsub_rn(a[3], a[1]));
-  const float area_b = __fmul_rn(__fsub_rn(b[2], b[0]), __fsub_rn(b[3], b[1]));
-  return __fdiv_rn(inter, __fsub_rn(__fadd_rn(area_a, area_b), inter));
-}
-
-__global__ __launch_bounds__(kDetThreads) void detect_agnostic_nms_kernel(const DetectAgnosticParams p, const int P_max) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char det_smem[];
-  unsigned long long* const keys = reinterpret_cast<unsigned long long*>(det_smem);      // [P_max]
-  unsigned char* const flags = det_smem + (size_t)P_max * 8;                              // [P_max] 1 = suppressed
-  __shared__ int n_cand;
-  __shared__ int scan[kDetThreads];
-  const int tid = threadIdx.x, nb = p.num_boxes;
-  if (tid == 0) n_cand = 0;
-  __syncthreads();
-  // ---- A
-  for (int i = tid; i < nb; i += kDetThreads) {
-    float best = sigmoid_f(p.raw[(size_t)4 * nb + i]);
-    int cls = 0;
-    for (int c = 5; c < p.num_attrs; ++c) {
-      const float s = sigmoid_f(p.raw[(size_t)c * nb + i]);
-      if (s > best || (s != s && best == best)) {   // torch.max: the first maximum; a NaN wins and stays (the box is then dropped below)
-        best = s;
-        cls = c - 4;
-      }
-    }
-    if (!(best > p.conf_thresh)) continue;
-    const int slot = atomicAdd(&n_cand, 1);
-    keys[slot] = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
-    p.cls[i] = cls;
-  }
-  __syncthreads();
-  const int n = n_cand;
-  int P = 1;
-  while (P < n) P <<= 1;
-  for (int t = n + tid; t < P; t += kDetThreads) keys[t] = 0ull;
-  __syncthreads();
-  // ---- B
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < P; t += kDetThreads) {
-        const int u = t ^ j;
-        if (u > t) {
-          const unsigned long long a = keys[t], b = keys[u];
-          if (((t & k) == 0) ? a < b : a > b) {
-            keys[t] = b;
-            keys[u] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  // ---- C
-  for (int r = tid; r < n; r += kDetThreads) {
-    const int i = (int)(0xFFFFFFFFu - (unsigned)(keys[r] & 0xFFFFFFFFull));
-    const float cx = p.raw[i], cy = p.raw[(size_t)nb + i], w = p.raw[(size_t)2 * nb + i], h = p.raw[(size_t)3 * nb + i];
-    const float hw = __fdiv_rn(w, 2.0f), hh = __fdiv_rn(h, 2.0f);
-    f32x4_t b;
-    b[0] = __fsub_rn(cx, hw);
-    b[1] = __fsub_rn(cy, hh);
-    b[2] = __fadd_rn(cx, hw);
-    b[3] = __fadd_rn(cy, hh);
-    *reinterpret_cast<f32x4_t*>(p.boxes + (size_t)r * 4) = b;
-    flags[r] = 0;
-  }
-  __threadfence_block();
-  __syncthreads();
-  // ---- D
-  for (int i = 0; i < n; ++i) {
-    if (flags[i]) continue;  // uniform: nothing was written since the last barrier
-    const f32x4_t bi = *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)i * 4);
-    for (int j = i + 1 + tid; j < n; j += kDetThreads) {
-      if (flags[j]) continue;
-      if (agnostic_iou(bi, *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)j * 4)) > p.iou_thresh) flags[j] = 1;
-    }
-    __syncthreads();
-  }
-  // ---- E
-  const int per = (n + kDetThreads - 1) / kDetThreads, r0 = min(n, tid * per), r1 = min(n, r0 + per);
-  int mine = 0;
-  for (int r = r0; r < r1; ++r) mine += flags[r] ? 0 : 1;
-  scan[tid] = mine;
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int t = 0; t < kDetThreads; ++t) {
-      const int v = scan[t];
-      scan[t] = run;
-      run += v;
-    }
-    p.count[0] = run;
-    p.count[1] = n;
-  }
-  __syncthreads();
-  const float px = (float)p.pad_x, py = (float)p.pad_y, ow = (float)p.orig_w, oh = (float)p.orig_h;
-  int pos = scan[tid];
-  for (int r = r0; r < r1; ++r) {
-    if (flags[r]) continue;
-    if (pos < p.out_cap) {
-      const f32x4_t b = *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)r * 4);
-      const int i = (int)(0xFFFFFFFFu - (unsigned)(keys[r] & 0xFFFFFFFFull));
-      float* o = p.out + (size_t)pos * 6;
-      o[0] = fminf(fmaxf(__fdiv_rn(__fsub_rn(b[0], px), p.scale), 0.0f), ow);
-      o[1] = fminf(fmaxf(__fdiv_rn(__fsub_rn(b[1], py), p.scale), 0.0f), oh);
-      o[2] = fminf(fmaxf(__fdiv_rn(__fsub_rn(b[2], px), p.scale), 0.0f), ow);
-      o[3] = fminf(fmaxf(__fdiv_rn(__fsub_rn(b[3], py), p.scale), 0.0f), oh);
-      o[4] = __uint_as_float((unsigned)(keys[r] >> 32));
-      o[5] = (float)p.cls[i];
-    }
-    ++pos;
-  }
-}
-
-hipError_t launch_detect_agnostic_nms(const DetectAgnosticParams& p, hipStream_t st) {
-  if (!p.raw || !p.boxes || !p.cls || !p.count || (p.out_cap > 0 && !p.out) || p.num_attrs < 5 || p.num_boxes < 1 || p.num_boxes > kDetectMaxBoxes || p.out_cap < 0 ||
-      !(p.scale > 0.0f))
-    return hipErrorInvalidValue;
-  int P = 1;
-  while (P < p.num_boxes) P <<= 1;
-  const size_t lds = (size_t)P * 9;
-  static LdsAttrOnce once;
-  if (hipError_t e = set_max_dynamic_lds(once, reinterpret_cast<const void*>(detect_agnostic_nms_kernel), 9 * kDetectMaxBoxes); e != hipSuccess) return e;
-  hipLaunchKernelGGL(detect_agnostic_nms_kernel, dim3(1), dim3(kDetThreads), lds, st, p, P);
-  return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------ detector head decode

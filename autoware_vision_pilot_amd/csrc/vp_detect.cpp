@@ -3,7 +3,8 @@
 // engine (engine.cpp build_autospeed) attached with vp_detect_attach: vp_detect_infer runs frame -> detections without leaving the device.  The
 // two-call form (a host's own runtime between vp_detect_preprocess and vp_detect_postprocess) stays as it was.
 // vp_detect_preprocess_pil / _postprocess_agnostic / _infer_pil: the same three entries in the arithmetic of the Python wrapper
-// (Models/inference/auto_speed_infer.py), which letterboxes with Pillow and decodes differently; they share the handle, its buffers and its stored geometry.
+// (Models/inference/auto_speed_infer.py), which letterboxes with Pillow and decodes differently; they share the handle, its buffers and its stored geometry.  Each pair of entries is one
+// implementation taking the decode rule (postprocess_rows, infer_rows below; vp::DetectRule, kernels.hpp).
 #include <cmath>
 #include <algorithm>
 #include <cstring>
@@ -18,46 +19,66 @@
 
 static_assert(sizeof(vp_detection) == sizeof(vp::Detection) && sizeof(vp_detection) == 24, "vp_detection is the reference's Detection");
 
+namespace {
+// an owning buffer of device (hipMalloc) or pinned host (hipHostMalloc) memory, grown on demand: the contents do not survive a growth
+template <class T, bool PINNED>
+struct Buf {
+  T* p = nullptr;
+  size_t cap = 0;   // elements
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() { release(); }
+  void release() {
+    if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+  }
+  void reserve(size_t n) {
+    if (n <= cap) return;
+    release();
+    VP_HIP_CHECK(PINNED ? hipHostMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)) : hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)));
+    cap = n;
+  }
+  operator T*() const { return p; }
+};
+template <class T>
+using DevBuf = Buf<T, false>;
+template <class T>
+using PinBuf = Buf<T, true>;
+}  // namespace
+
 struct vp_detect {
   int gpu = 0, net_h = 0, net_w = 0, max_boxes = 0, max_attrs = 0;
   hipStream_t stream = nullptr;
-  uint8_t* d_frame = nullptr;
-  size_t frame_cap = 0;
-  uint8_t* h_frame = nullptr;  // pinned staging
-  size_t h_frame_cap = 0;
-  int* d_xtab = nullptr;
-  int* d_ytab = nullptr;
-  int tab_w = 0, tab_h = 0, tab_cap_w = 0, tab_cap_h = 0;
-  float* d_input = nullptr;  // [3][net_h][net_w]
-  float* d_raw = nullptr;    // [max_attrs][max_boxes]
-  float* d_boxes = nullptr;
-  int* d_cls = nullptr;
-  vp::Detection* d_out = nullptr;
-  int* d_count = nullptr;
-  vp::Detection* h_out = nullptr;  // pinned [max_boxes]
-  int* h_count = nullptr;          // pinned [2]
+  DevBuf<uint8_t> d_frame;
+  PinBuf<uint8_t> h_frame;         // staging
+  DevBuf<int> d_xtab, d_ytab;      // [net_w][4], [net_h][4]
+  int tab_w = 0, tab_h = 0;
+  DevBuf<float> d_input;           // [3][net_h][net_w]
+  DevBuf<float> d_raw;             // [max_attrs][max_boxes]
+  DevBuf<float> d_boxes;
+  DevBuf<int> d_cls;
+  DevBuf<vp::Detection> d_out;     // [max_boxes] rows of 24 bytes under either rule (vp::DetectParams::out)
+  DevBuf<int> d_count;
+  PinBuf<vp::Detection> h_out;     // [max_boxes]
+  PinBuf<int> h_count;             // [2]
   // letterbox geometry of the last preprocessed frame (scale_, pad_x_, pad_y_, orig_width_, orig_height_ of the reference engine)
   float scale = 0.0f;
   int pad_x = 0, pad_y = 0, orig_w = 0, orig_h = 0;
   // Pillow letterbox (vp_detect_preprocess_pil): the tables of vp_resample_coeffs for the last frame size, Pillow's u8 image between its two passes,
   // the resized fp32 planes the paste kernel reads
-  int* d_pil_tab[4] = {nullptr, nullptr, nullptr, nullptr};   // hb, hk, vb, vk
+  DevBuf<int> d_pil_tab[4];        // hb, hk, vb, vk
   int pil_hks = 0, pil_vks = 0, pil_w = 0, pil_h = 0;
-  uint8_t* d_pil_tmp = nullptr;
-  size_t pil_tmp_cap = 0;
-  float* d_pil_planes = nullptr;   // [3][new_h][new_w], room for [3][net_h][net_w]
+  DevBuf<uint8_t> d_pil_tmp;
+  DevBuf<float> d_pil_planes;      // [3][new_h][new_w], room for [3][net_h][net_w]
   std::string err;
   vp_engine* net = nullptr;        // borrowed VP_AUTOSPEED engine (vp_detect_attach)
   hipEvent_t ev_in = nullptr, ev_out = nullptr;   // input tensor written (detector stream -> engine stream), network done (engine -> detector)
 
-  ~vp_detect() {
+  ~vp_detect() {   // the buffers free themselves behind this body
     (void)hipSetDevice(gpu);
     if (stream) (void)hipStreamSynchronize(stream);
-    for (void* q : {(void*)d_frame, (void*)d_xtab, (void*)d_ytab, (void*)d_input, (void*)d_raw, (void*)d_boxes, (void*)d_cls, (void*)d_out, (void*)d_count,
-                    (void*)d_pil_tab[0], (void*)d_pil_tab[1], (void*)d_pil_tab[2], (void*)d_pil_tab[3], (void*)d_pil_tmp, (void*)d_pil_planes})
-      if (q) (void)hipFree(q);
-    for (void* q : {(void*)h_frame, (void*)h_out, (void*)h_count})
-      if (q) (void)hipHostFree(q);
     if (ev_in) (void)hipEventDestroy(ev_in);
     if (ev_out) (void)hipEventDestroy(ev_out);
     if (stream) (void)hipStreamDestroy(stream);
@@ -109,14 +130,14 @@ int vp_detect_create(vp_detect** out, int gpu_id, int net_h, int net_w, int max_
     d->max_attrs = max_attrs;
     VP_HIP_CHECK(hipSetDevice(gpu_id));
     VP_HIP_CHECK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    VP_HIP_CHECK(hipMalloc(&d->d_input, (size_t)3 * net_h * net_w * sizeof(float)));
-    VP_HIP_CHECK(hipMalloc(&d->d_raw, (size_t)max_attrs * max_boxes * sizeof(float)));
-    VP_HIP_CHECK(hipMalloc(&d->d_boxes, (size_t)max_boxes * 4 * sizeof(float)));
-    VP_HIP_CHECK(hipMalloc(&d->d_cls, (size_t)max_boxes * sizeof(int)));
-    VP_HIP_CHECK(hipMalloc(&d->d_out, (size_t)max_boxes * sizeof(vp::Detection)));
-    VP_HIP_CHECK(hipMalloc(&d->d_count, 2 * sizeof(int)));
-    VP_HIP_CHECK(hipHostMalloc(&d->h_out, (size_t)max_boxes * sizeof(vp::Detection)));
-    VP_HIP_CHECK(hipHostMalloc(&d->h_count, 2 * sizeof(int)));
+    d->d_input.reserve((size_t)3 * net_h * net_w);
+    d->d_raw.reserve((size_t)max_attrs * max_boxes);
+    d->d_boxes.reserve((size_t)max_boxes * 4);
+    d->d_cls.reserve(max_boxes);
+    d->d_out.reserve(max_boxes);
+    d->d_count.reserve(2);
+    d->h_out.reserve(max_boxes);
+    d->h_count.reserve(2);
     *out = d.release();
     return VP_OK;
   } catch (const std::invalid_argument& ex) {
@@ -135,79 +156,65 @@ const char* vp_detect_last_error(const vp_detect* d) { return d ? d->err.c_str()
 }  // extern "C"
 
 namespace {
+void check_frame(const char* who, const uint8_t* frame, int h, int w, int stride_bytes) {
+  if (!frame || h < 1 || w < 1 || h > 16384 || w > 16384 || stride_bytes < 3 * w) throw std::invalid_argument(std::string(who) + ": bad frame geometry");
+}
+
+void store_geometry(vp_detect* d, float scale, int pad_x, int pad_y, int orig_w, int orig_h) {
+  d->scale = scale;
+  d->pad_x = pad_x;
+  d->pad_y = pad_y;
+  d->orig_w = orig_w;
+  d->orig_h = orig_h;
+}
+
 // the frame's bytes into d->d_frame through the pinned staging buffer, on the detector's stream (both grown on demand)
 void upload_frame(vp_detect* d, const uint8_t* bgr, int h, int w, int stride_bytes) {
-    const size_t bytes = (size_t)(h - 1) * stride_bytes + (size_t)3 * w;   // a strided view may END with its last pixel: never read a full last stride
-    if (bytes > d->frame_cap) {
-      if (d->d_frame) VP_HIP_CHECK(hipFree(d->d_frame));
-      d->d_frame = nullptr;
-      d->frame_cap = 0;
-      VP_HIP_CHECK(hipMalloc(&d->d_frame, bytes));
-      d->frame_cap = bytes;
-    }
-    if (bytes > d->h_frame_cap) {
-      if (d->h_frame) VP_HIP_CHECK(hipHostFree(d->h_frame));
-      d->h_frame = nullptr;
-      d->h_frame_cap = 0;
-      VP_HIP_CHECK(hipHostMalloc(&d->h_frame, bytes));
-      d->h_frame_cap = bytes;
-    }
-    VP_HIP_CHECK(hipStreamSynchronize(d->stream));  // the staging buffer and the tables must not be rewritten under a copy still in flight (a drained stream: no wait)
-    std::memcpy(d->h_frame, bgr, bytes);
-    VP_HIP_CHECK(hipMemcpyAsync(d->d_frame, d->h_frame, bytes, hipMemcpyHostToDevice, d->stream));
+  const size_t bytes = (size_t)(h - 1) * stride_bytes + (size_t)3 * w;   // a strided view may END with its last pixel: never read a full last stride
+  d->d_frame.reserve(bytes);
+  d->h_frame.reserve(bytes);
+  VP_HIP_CHECK(hipStreamSynchronize(d->stream));  // the staging buffer and the tables must not be rewritten under a copy still in flight (a drained stream: no wait)
+  std::memcpy(d->h_frame, bgr, bytes);
+  VP_HIP_CHECK(hipMemcpyAsync(d->d_frame, d->h_frame, bytes, hipMemcpyHostToDevice, d->stream));
 }
 
 // upload + letterbox of one frame into `dst` ([3][net_h][net_w] fp32) on the detector's stream; no synchronisation behind the launch.  `who`: the
 // entry point named in error texts.  Two waits on the detector's own stream, neither of which blocks in steady state: the one ahead of the staging
 // copy finds the stream drained (every entry returns synchronised), and the one behind the tap tables runs only when the frame size changes.
 void letterbox_frame(vp_detect* d, const char* who, const uint8_t* bgr, int h, int w, int stride_bytes, float* dst) {
-    if (!bgr || h < 1 || w < 1 || h > 16384 || w > 16384 || stride_bytes < 3 * w) throw std::invalid_argument(std::string(who) + ": bad frame geometry");
-    // preprocessAutoSpeed :78-98 -- fp32 scale, truncated new size, centred paste
-    const float scale = std::min((float)d->net_w / (float)w, (float)d->net_h / (float)h);
-    const int new_w = (int)((float)w * scale), new_h = (int)((float)h * scale);
-    if (new_w < 1 || new_h < 1 || new_w > d->net_w || new_h > d->net_h) throw std::invalid_argument(std::string(who) + ": the frame collapses under the letterbox scale");
-    upload_frame(d, bgr, h, w, stride_bytes);
-    if (d->tab_w != w || d->tab_h != h) {
-      std::vector<int> xt, yt;
-      vp::linear_taps_u8(w, new_w, &xt);
-      vp::linear_taps_u8(h, new_h, &yt);
-      if (new_w > d->tab_cap_w) {
-        if (d->d_xtab) VP_HIP_CHECK(hipFree(d->d_xtab));
-        d->d_xtab = nullptr;
-        VP_HIP_CHECK(hipMalloc(&d->d_xtab, (size_t)d->net_w * 4 * sizeof(int)));
-        d->tab_cap_w = d->net_w;
-      }
-      if (new_h > d->tab_cap_h) {
-        if (d->d_ytab) VP_HIP_CHECK(hipFree(d->d_ytab));
-        d->d_ytab = nullptr;
-        VP_HIP_CHECK(hipMalloc(&d->d_ytab, (size_t)d->net_h * 4 * sizeof(int)));
-        d->tab_cap_h = d->net_h;
-      }
-      // on the detector's own stream, then waited for: hipMemcpy would use the legacy stream, which the runtime refuses while any thread captures a graph
-      VP_HIP_CHECK(hipMemcpyAsync(d->d_xtab, xt.data(), xt.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
-      VP_HIP_CHECK(hipMemcpyAsync(d->d_ytab, yt.data(), yt.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
-      VP_HIP_CHECK(hipStreamSynchronize(d->stream));
-      d->tab_w = w;
-      d->tab_h = h;
-    }
-    vp::LetterboxParams p{};
-    p.frame = d->d_frame;
-    p.stride = stride_bytes;
-    p.xtab = d->d_xtab;
-    p.ytab = d->d_ytab;
-    p.new_w = new_w;
-    p.new_h = new_h;
-    p.pad_x = (d->net_w - new_w) / 2;
-    p.pad_y = (d->net_h - new_h) / 2;
-    p.out_h = d->net_h;
-    p.out_w = d->net_w;
-    p.out = dst;
-    VP_HIP_CHECK(vp::launch_letterbox(p, d->stream));
-    d->scale = scale;
-    d->pad_x = p.pad_x;
-    d->pad_y = p.pad_y;
-    d->orig_w = w;
-    d->orig_h = h;
+  check_frame(who, bgr, h, w, stride_bytes);
+  // preprocessAutoSpeed :78-98 -- fp32 scale, truncated new size, centred paste
+  const float scale = std::min((float)d->net_w / (float)w, (float)d->net_h / (float)h);
+  const int new_w = (int)((float)w * scale), new_h = (int)((float)h * scale);
+  if (new_w < 1 || new_h < 1 || new_w > d->net_w || new_h > d->net_h) throw std::invalid_argument(std::string(who) + ": the frame collapses under the letterbox scale");
+  upload_frame(d, bgr, h, w, stride_bytes);
+  if (d->tab_w != w || d->tab_h != h) {
+    std::vector<int> xt, yt;
+    vp::linear_taps_u8(w, new_w, &xt);
+    vp::linear_taps_u8(h, new_h, &yt);
+    d->d_xtab.reserve((size_t)d->net_w * 4);   // new_w <= net_w: room for every frame size
+    d->d_ytab.reserve((size_t)d->net_h * 4);
+    // on the detector's own stream, then waited for: hipMemcpy would use the legacy stream, which the runtime refuses while any thread captures a graph
+    VP_HIP_CHECK(hipMemcpyAsync(d->d_xtab, xt.data(), xt.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    VP_HIP_CHECK(hipMemcpyAsync(d->d_ytab, yt.data(), yt.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    VP_HIP_CHECK(hipStreamSynchronize(d->stream));
+    d->tab_w = w;
+    d->tab_h = h;
+  }
+  vp::LetterboxParams p{};
+  p.frame = d->d_frame;
+  p.stride = stride_bytes;
+  p.xtab = d->d_xtab;
+  p.ytab = d->d_ytab;
+  p.new_w = new_w;
+  p.new_h = new_h;
+  p.pad_x = (d->net_w - new_w) / 2;
+  p.pad_y = (d->net_h - new_h) / 2;
+  p.out_h = d->net_h;
+  p.out_w = d->net_w;
+  p.out = dst;
+  VP_HIP_CHECK(vp::launch_letterbox(p, d->stream));
+  store_geometry(d, scale, p.pad_x, p.pad_y, w, h);
 }
 
 // resize_letterbox of the Python wrapper (auto_speed_infer.py:24-34) in the doubles Python computes it in: scale = min(tw / ow, th / oh),
@@ -228,32 +235,23 @@ bool pil_geometry(int net_h, int net_w, int h, int w, double* scale, int* new_w,
 // upload + Pillow letterbox of one frame into `dst` ([3][net_h][net_w] fp32) on the detector's stream, no synchronisation behind the launches: Pillow's
 // two passes (launch_pil_resample on the tables of vp_resample_coeffs, BILINEAR) into d_pil_planes, then the paste.  Waits as letterbox_frame.
 void letterbox_pil_frame(vp_detect* d, const char* who, const uint8_t* frame, int h, int w, int stride_bytes, int pixel_format, float* dst) {
-  if (!frame || h < 1 || w < 1 || h > 16384 || w > 16384 || stride_bytes < 3 * w) throw std::invalid_argument(std::string(who) + ": bad frame geometry");
+  check_frame(who, frame, h, w, stride_bytes);
   if (pixel_format != VP_BGR8 && pixel_format != VP_RGB8) throw std::invalid_argument(std::string(who) + ": pixel_format is VP_BGR8 or VP_RGB8");
   double scale = 0.0;
   int new_w = 0, new_h = 0, pad_x = 0, pad_y = 0;
   if (!pil_geometry(d->net_h, d->net_w, h, w, &scale, &new_w, &new_h, &pad_x, &pad_y))
     throw std::invalid_argument(std::string(who) + ": the frame collapses under the letterbox scale");
   upload_frame(d, frame, h, w, stride_bytes);
-  if (!d->d_pil_planes) VP_HIP_CHECK(hipMalloc(&d->d_pil_planes, (size_t)3 * d->net_h * d->net_w * sizeof(float)));
+  d->d_pil_planes.reserve((size_t)3 * d->net_h * d->net_w);
   if (d->pil_w != w || d->pil_h != h) {
     std::vector<int> tab[4];
     const int hks = vp::pil_coeffs(w, new_w, 1, &tab[0], &tab[1]), vks = vp::pil_coeffs(h, new_h, 1, &tab[2], &tab[3]);
     d->pil_w = d->pil_h = 0;
-    for (int i = 0; i < 4; ++i) {   // once per frame size: the tap count follows the size, so the tables are simply made anew
-      if (d->d_pil_tab[i]) VP_HIP_CHECK(hipFree(d->d_pil_tab[i]));
-      d->d_pil_tab[i] = nullptr;
-      VP_HIP_CHECK(hipMalloc(&d->d_pil_tab[i], tab[i].size() * sizeof(int)));
+    for (int i = 0; i < 4; ++i) {   // once per frame size: the tap count follows the size
+      d->d_pil_tab[i].reserve(tab[i].size());
       VP_HIP_CHECK(hipMemcpyAsync(d->d_pil_tab[i], tab[i].data(), tab[i].size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
     }
-    const size_t tmp_bytes = (size_t)h * new_w * 3;
-    if (tmp_bytes > d->pil_tmp_cap) {
-      if (d->d_pil_tmp) VP_HIP_CHECK(hipFree(d->d_pil_tmp));
-      d->d_pil_tmp = nullptr;
-      d->pil_tmp_cap = 0;
-      VP_HIP_CHECK(hipMalloc(&d->d_pil_tmp, tmp_bytes));
-      d->pil_tmp_cap = tmp_bytes;
-    }
+    d->d_pil_tmp.reserve((size_t)h * new_w * 3);
     VP_HIP_CHECK(hipStreamSynchronize(d->stream));   // the host vectors leave scope
     d->pil_hks = hks;
     d->pil_vks = vks;
@@ -292,15 +290,12 @@ void letterbox_pil_frame(vp_detect* d, const char* who, const uint8_t* frame, in
   p.out_w = d->net_w;
   p.out = dst;
   VP_HIP_CHECK(vp::launch_letterbox_paste(p, d->stream));
-  d->scale = (float)scale;
-  d->pad_x = pad_x;
-  d->pad_y = pad_y;
-  d->orig_w = w;
-  d->orig_h = h;
+  store_geometry(d, (float)scale, pad_x, pad_y, w, h);
 }
 
-vp::DetectAgnosticParams agnostic_params(vp_detect* d, const float* raw, int num_attrs, int num_boxes, float conf_thresh, float iou_thresh, int out_cap) {
-  vp::DetectAgnosticParams p{};
+// the decode + NMS launch on the detector's stream: `raw` on the device, the handle's scratch, rows and counts, its stored geometry
+vp::DetectParams launch_decode(vp_detect* d, vp::DetectRule rule, const float* raw, int num_attrs, int num_boxes, float conf_thresh, float iou_thresh, int out_cap) {
+  vp::DetectParams p{};
   p.raw = raw;
   p.num_attrs = num_attrs;
   p.num_boxes = num_boxes;
@@ -313,10 +308,87 @@ vp::DetectAgnosticParams agnostic_params(vp_detect* d, const float* raw, int num
   p.orig_h = d->orig_h;
   p.boxes = d->d_boxes;
   p.cls = d->d_cls;
-  p.out = reinterpret_cast<float*>(d->d_out);   // [max_boxes] rows of 24 bytes either way
+  p.out = d->d_out;
   p.out_cap = std::min(out_cap, d->max_boxes);
   p.count = d->d_count;
+  VP_HIP_CHECK(vp::launch_detect_nms(p, rule, d->stream));
   return p;
+}
+
+constexpr size_t kRow = sizeof(vp::Detection);   // 24 bytes under either rule: a vp_detection, or six floats
+
+// vp_detect_postprocess / _postprocess_agnostic: raw tensor in, rows out.  The count comes back first, then exactly the rows there are.
+int postprocess_rows(vp_detect* d, vp::DetectRule rule, const float* raw, int raw_on_device, int num_attrs, int num_boxes, float conf_thresh, float iou_thresh,
+                     void* out, int out_cap, int* count) {
+  const bool agnostic = rule == vp::kDetectAgnostic;
+  const char* who = agnostic ? "vp_detect_postprocess_agnostic" : "vp_detect_postprocess";
+  return guarded(d, [&]() -> int {
+    if (!raw || !count || out_cap < 0 || (out_cap > 0 && !out) || num_attrs < 5 || num_attrs > d->max_attrs || num_boxes < 1 || num_boxes > d->max_boxes)
+      throw std::invalid_argument(std::string(who) + ": bad argument (num_attrs / num_boxes within the sizes given to vp_detect_create)");
+    if (d->orig_w == 0)
+      throw std::invalid_argument(std::string(who) + ": no letterbox geometry yet (" + (agnostic ? "vp_detect_preprocess_pil" : "vp_detect_preprocess") + " or vp_detect_set_letterbox first)");
+    const float* src = raw;
+    if (!raw_on_device) {
+      VP_HIP_CHECK(hipMemcpyAsync(d->d_raw, raw, (size_t)num_attrs * num_boxes * sizeof(float), hipMemcpyHostToDevice, d->stream));
+      src = d->d_raw;
+    }
+    const vp::DetectParams p = launch_decode(d, rule, src, num_attrs, num_boxes, conf_thresh, iou_thresh, out_cap);
+    VP_HIP_CHECK(hipMemcpyAsync(d->h_count, d->d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    VP_HIP_CHECK(hipStreamSynchronize(d->stream));
+    const int kept = d->h_count[0], n = std::min(kept, p.out_cap);
+    if (n > 0) {
+      VP_HIP_CHECK(hipMemcpyAsync(d->h_out, d->d_out, (size_t)n * kRow, hipMemcpyDeviceToHost, d->stream));
+      VP_HIP_CHECK(hipStreamSynchronize(d->stream));
+      std::memcpy(out, d->h_out, (size_t)n * kRow);
+    }
+    *count = kept;
+    return VP_OK;
+  });
+}
+
+// vp_detect_infer / _infer_pil: frame in, rows out through the attached engine without leaving the device.  `letterbox(who, dst)` uploads the frame
+// and writes the network's input tensor on the detector's stream.
+template <class Letterbox>
+int infer_rows(vp_detect* d, vp::DetectRule rule, Letterbox&& letterbox, float conf_thresh, float iou_thresh, void* out, int out_cap, int* count) {
+  const char* who = rule == vp::kDetectAgnostic ? "vp_detect_infer_pil" : "vp_detect_infer";
+  return guarded(d, [&]() -> int {
+    if (!d->net || !d->net->impl) throw std::invalid_argument(std::string(who) + ": no network attached (vp_detect_attach with a VP_AUTOSPEED engine first)");
+    if (!count || out_cap < 0 || (out_cap > 0 && !out)) throw std::invalid_argument(std::string(who) + ": bad output arguments");
+    vp::Engine& g = *d->net->impl;
+    try {
+     try {
+      // letterbox straight into the network's input tensor: every exit of this call, the failing ones included (see the handler below), leaves both
+      // streams drained, so nothing still reads it
+      letterbox(who, g.dev_input());
+      g.note_device_tensor();
+      VP_HIP_CHECK(hipEventRecord(d->ev_in, d->stream));
+      VP_HIP_CHECK(hipStreamWaitEvent(g.stream(), d->ev_in, 0));
+      g.enqueue();         // the replayed graph (first call: the eager warm-up pass)
+      g.enqueue_status_fetch();   // the range probe's verdict behind it; the output tensor itself stays on the device
+      VP_HIP_CHECK(hipEventRecord(d->ev_out, g.stream()));
+      VP_HIP_CHECK(hipStreamWaitEvent(d->stream, d->ev_out, 0));
+      const vp::DetectParams p = launch_decode(d, rule, static_cast<const float*>(g.dev_logits()), g.out_c(), g.out_w(), conf_thresh, iou_thresh, out_cap);
+      // count and (at most out_cap) detections come back together: this is the one host synchronisation of a call that has anything to wait for
+      VP_HIP_CHECK(hipMemcpyAsync(d->h_count, d->d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+      if (p.out_cap > 0) VP_HIP_CHECK(hipMemcpyAsync(d->h_out, d->d_out, (size_t)p.out_cap * kRow, hipMemcpyDeviceToHost, d->stream));
+      VP_HIP_CHECK(hipStreamSynchronize(d->stream));   // behind ev_out: the engine's stream has drained too
+      g.check_status();
+      const int kept = d->h_count[0], n = std::min(kept, p.out_cap);
+      if (n > 0) std::memcpy(out, d->h_out, (size_t)n * kRow);
+      *count = kept;
+      return VP_OK;
+     } catch (...) {
+      // a failure part-way (a launch error, the range probe's verdict): work may still be queued on either stream, and the next call rewrites the
+      // engine's input tensor and the staging buffer.  Drain both before the error leaves; the statuses are not looked at, the first error is the news.
+      (void)hipStreamSynchronize(g.stream());
+      (void)hipStreamSynchronize(d->stream);
+      throw;
+     }
+    } catch (const vp::RangeError& ex) {
+      d->err = ex.what();
+      return VP_ERR_RANGE;
+    }
+  });
 }
 }  // namespace
 
@@ -347,53 +419,13 @@ int vp_detect_letterbox(const vp_detect* d, float* scale, int* pad_x, int* pad_y
 
 int vp_detect_set_letterbox(vp_detect* d, float scale, int pad_x, int pad_y, int orig_w, int orig_h) {
   if (!d || !(scale > 0.0f) || orig_w < 1 || orig_h < 1) return VP_ERR_ARG;
-  d->scale = scale;
-  d->pad_x = pad_x;
-  d->pad_y = pad_y;
-  d->orig_w = orig_w;
-  d->orig_h = orig_h;
+  store_geometry(d, scale, pad_x, pad_y, orig_w, orig_h);
   return VP_OK;
 }
 
 int vp_detect_postprocess(vp_detect* d, const float* raw, int raw_on_device, int num_attrs, int num_boxes, float conf_thresh, float iou_thresh,
                           vp_detection* out, int out_cap, int* count) {
-  return guarded(d, [&]() -> int {
-    if (!raw || !count || out_cap < 0 || (out_cap > 0 && !out) || num_attrs < 5 || num_attrs > d->max_attrs || num_boxes < 1 || num_boxes > d->max_boxes)
-      throw std::invalid_argument("vp_detect_postprocess: bad argument (num_attrs / num_boxes within the sizes given to vp_detect_create)");
-    if (d->orig_w == 0) throw std::invalid_argument("vp_detect_postprocess: no letterbox geometry yet (vp_detect_preprocess or vp_detect_set_letterbox first)");
-    const float* src = raw;
-    if (!raw_on_device) {
-      VP_HIP_CHECK(hipMemcpyAsync(d->d_raw, raw, (size_t)num_attrs * num_boxes * sizeof(float), hipMemcpyHostToDevice, d->stream));
-      src = d->d_raw;
-    }
-    vp::DetectParams p{};
-    p.raw = src;
-    p.num_attrs = num_attrs;
-    p.num_boxes = num_boxes;
-    p.conf_thresh = conf_thresh;
-    p.iou_thresh = iou_thresh;
-    p.scale = d->scale;
-    p.pad_x = d->pad_x;
-    p.pad_y = d->pad_y;
-    p.orig_w = d->orig_w;
-    p.orig_h = d->orig_h;
-    p.boxes = d->d_boxes;
-    p.cls = d->d_cls;
-    p.out = d->d_out;
-    p.out_cap = std::min(out_cap, d->max_boxes);
-    p.count = d->d_count;
-    VP_HIP_CHECK(vp::launch_detect_decode_nms(p, d->stream));
-    VP_HIP_CHECK(hipMemcpyAsync(d->h_count, d->d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-    VP_HIP_CHECK(hipStreamSynchronize(d->stream));
-    const int kept = d->h_count[0], n = std::min(kept, p.out_cap);
-    if (n > 0) {
-      VP_HIP_CHECK(hipMemcpyAsync(d->h_out, d->d_out, (size_t)n * sizeof(vp::Detection), hipMemcpyDeviceToHost, d->stream));
-      VP_HIP_CHECK(hipStreamSynchronize(d->stream));
-      std::memcpy(out, d->h_out, (size_t)n * sizeof(vp::Detection));
-    }
-    *count = kept;
-    return VP_OK;
-  });
+  return postprocess_rows(d, vp::kDetectPerClass, raw, raw_on_device, num_attrs, num_boxes, conf_thresh, iou_thresh, out, out_cap, count);
 }
 
 int vp_detect_attach(vp_detect* d, vp_engine* net) {
@@ -420,60 +452,8 @@ int vp_detect_attach(vp_detect* d, vp_engine* net) {
 
 int vp_detect_infer(vp_detect* d, const uint8_t* bgr, int h, int w, int stride_bytes, float conf_thresh, float iou_thresh, vp_detection* out, int out_cap,
                     int* count) {
-  return guarded(d, [&]() -> int {
-    if (!d->net || !d->net->impl) throw std::invalid_argument("vp_detect_infer: no network attached (vp_detect_attach with a VP_AUTOSPEED engine first)");
-    if (!count || out_cap < 0 || (out_cap > 0 && !out)) throw std::invalid_argument("vp_detect_infer: bad output arguments");
-    vp::Engine& g = *d->net->impl;
-    try {
-     try {
-      // letterbox straight into the network's input tensor: every exit of this call, the failing ones included (see the handler below), leaves both
-      // streams drained, so nothing still reads it
-      letterbox_frame(d, "vp_detect_infer", bgr, h, w, stride_bytes, g.dev_input());
-      g.note_device_tensor();
-      VP_HIP_CHECK(hipEventRecord(d->ev_in, d->stream));
-      VP_HIP_CHECK(hipStreamWaitEvent(g.stream(), d->ev_in, 0));
-      g.enqueue();         // the replayed graph (first call: the eager warm-up pass)
-      g.enqueue_status_fetch();   // the range probe's verdict behind it; the output tensor itself stays on the device
-      VP_HIP_CHECK(hipEventRecord(d->ev_out, g.stream()));
-      VP_HIP_CHECK(hipStreamWaitEvent(d->stream, d->ev_out, 0));
-      vp::DetectParams p{};
-      p.raw = static_cast<const float*>(g.dev_logits());
-      p.num_attrs = g.out_c();
-      p.num_boxes = g.out_w();
-      p.conf_thresh = conf_thresh;
-      p.iou_thresh = iou_thresh;
-      p.scale = d->scale;
-      p.pad_x = d->pad_x;
-      p.pad_y = d->pad_y;
-      p.orig_w = d->orig_w;
-      p.orig_h = d->orig_h;
-      p.boxes = d->d_boxes;
-      p.cls = d->d_cls;
-      p.out = d->d_out;
-      p.out_cap = std::min(out_cap, d->max_boxes);
-      p.count = d->d_count;
-      VP_HIP_CHECK(vp::launch_detect_decode_nms(p, d->stream));
-      // count and (at most out_cap) detections come back together: this is the one host synchronisation of a call that has anything to wait for
-      VP_HIP_CHECK(hipMemcpyAsync(d->h_count, d->d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-      if (p.out_cap > 0) VP_HIP_CHECK(hipMemcpyAsync(d->h_out, d->d_out, (size_t)p.out_cap * sizeof(vp::Detection), hipMemcpyDeviceToHost, d->stream));
-      VP_HIP_CHECK(hipStreamSynchronize(d->stream));   // behind ev_out: the engine's stream has drained too
-      g.check_status();
-      const int kept = d->h_count[0], n = std::min(kept, p.out_cap);
-      if (n > 0) std::memcpy(out, d->h_out, (size_t)n * sizeof(vp::Detection));
-      *count = kept;
-      return VP_OK;
-     } catch (...) {
-      // a failure part-way (a launch error, the range probe's verdict): work may still be queued on either stream, and the next call rewrites the
-      // engine's input tensor and the staging buffer.  Drain both before the error leaves; the statuses are not looked at, the first error is the news.
-      (void)hipStreamSynchronize(g.stream());
-      (void)hipStreamSynchronize(d->stream);
-      throw;
-     }
-    } catch (const vp::RangeError& ex) {
-      d->err = ex.what();
-      return VP_ERR_RANGE;
-    }
-  });
+  return infer_rows(d, vp::kDetectPerClass, [&](const char* who, float* dst) { letterbox_frame(d, who, bgr, h, w, stride_bytes, dst); }, conf_thresh, iou_thresh, out, out_cap,
+                    count);
 }
 
 int vp_detect_geometry_pil(int net_h, int net_w, int h, int w, double* scale, int* new_w, int* new_h, int* pad_x, int* pad_y) {
@@ -492,68 +472,13 @@ int vp_detect_preprocess_pil(vp_detect* d, const uint8_t* frame, int h, int w, i
 
 int vp_detect_postprocess_agnostic(vp_detect* d, const float* raw, int raw_on_device, int num_attrs, int num_boxes, float conf_thresh, float iou_thresh,
                                    float* out_rows6, int out_cap, int* count) {
-  return guarded(d, [&]() -> int {
-    if (!raw || !count || out_cap < 0 || (out_cap > 0 && !out_rows6) || num_attrs < 5 || num_attrs > d->max_attrs || num_boxes < 1 || num_boxes > d->max_boxes)
-      throw std::invalid_argument("vp_detect_postprocess_agnostic: bad argument (num_attrs / num_boxes within the sizes given to vp_detect_create)");
-    if (d->orig_w == 0)
-      throw std::invalid_argument("vp_detect_postprocess_agnostic: no letterbox geometry yet (vp_detect_preprocess_pil or vp_detect_set_letterbox first)");
-    const float* src = raw;
-    if (!raw_on_device) {
-      VP_HIP_CHECK(hipMemcpyAsync(d->d_raw, raw, (size_t)num_attrs * num_boxes * sizeof(float), hipMemcpyHostToDevice, d->stream));
-      src = d->d_raw;
-    }
-    const vp::DetectAgnosticParams p = agnostic_params(d, src, num_attrs, num_boxes, conf_thresh, iou_thresh, out_cap);
-    VP_HIP_CHECK(vp::launch_detect_agnostic_nms(p, d->stream));
-    VP_HIP_CHECK(hipMemcpyAsync(d->h_count, d->d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-    VP_HIP_CHECK(hipStreamSynchronize(d->stream));
-    const int kept = d->h_count[0], n = std::min(kept, p.out_cap);
-    if (n > 0) {
-      VP_HIP_CHECK(hipMemcpyAsync(d->h_out, d->d_out, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-      VP_HIP_CHECK(hipStreamSynchronize(d->stream));
-      std::memcpy(out_rows6, d->h_out, (size_t)n * 6 * sizeof(float));
-    }
-    *count = kept;
-    return VP_OK;
-  });
+  return postprocess_rows(d, vp::kDetectAgnostic, raw, raw_on_device, num_attrs, num_boxes, conf_thresh, iou_thresh, out_rows6, out_cap, count);
 }
 
 int vp_detect_infer_pil(vp_detect* d, const uint8_t* frame, int h, int w, int stride_bytes, int pixel_format, float conf_thresh, float iou_thresh,
                         float* out_rows6, int out_cap, int* count) {
-  return guarded(d, [&]() -> int {
-    if (!d->net || !d->net->impl) throw std::invalid_argument("vp_detect_infer_pil: no network attached (vp_detect_attach with a VP_AUTOSPEED engine first)");
-    if (!count || out_cap < 0 || (out_cap > 0 && !out_rows6)) throw std::invalid_argument("vp_detect_infer_pil: bad output arguments");
-    vp::Engine& g = *d->net->impl;
-    try {
-     try {
-      // the event order of vp_detect_infer, stage for stage
-      letterbox_pil_frame(d, "vp_detect_infer_pil", frame, h, w, stride_bytes, pixel_format, g.dev_input());
-      g.note_device_tensor();
-      VP_HIP_CHECK(hipEventRecord(d->ev_in, d->stream));
-      VP_HIP_CHECK(hipStreamWaitEvent(g.stream(), d->ev_in, 0));
-      g.enqueue();
-      g.enqueue_status_fetch();
-      VP_HIP_CHECK(hipEventRecord(d->ev_out, g.stream()));
-      VP_HIP_CHECK(hipStreamWaitEvent(d->stream, d->ev_out, 0));
-      const vp::DetectAgnosticParams p = agnostic_params(d, static_cast<const float*>(g.dev_logits()), g.out_c(), g.out_w(), conf_thresh, iou_thresh, out_cap);
-      VP_HIP_CHECK(vp::launch_detect_agnostic_nms(p, d->stream));
-      VP_HIP_CHECK(hipMemcpyAsync(d->h_count, d->d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-      if (p.out_cap > 0) VP_HIP_CHECK(hipMemcpyAsync(d->h_out, d->d_out, (size_t)p.out_cap * 6 * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-      VP_HIP_CHECK(hipStreamSynchronize(d->stream));
-      g.check_status();
-      const int kept = d->h_count[0], n = std::min(kept, p.out_cap);
-      if (n > 0) std::memcpy(out_rows6, d->h_out, (size_t)n * 6 * sizeof(float));
-      *count = kept;
-      return VP_OK;
-     } catch (...) {
-      (void)hipStreamSynchronize(g.stream());   // as vp_detect_infer: both streams drained before the error leaves
-      (void)hipStreamSynchronize(d->stream);
-      throw;
-     }
-    } catch (const vp::RangeError& ex) {
-      d->err = ex.what();
-      return VP_ERR_RANGE;
-    }
-  });
+  return infer_rows(d, vp::kDetectAgnostic, [&](const char* who, float* dst) { letterbox_pil_frame(d, who, frame, h, w, stride_bytes, pixel_format, dst); }, conf_thresh,
+                    iou_thresh, out_rows6, out_cap, count);
 }
 
 }  // extern "C"

@@ -978,20 +978,8 @@ class Detector:
 
     def infer(self, frame_bgr_u8, conf_thresh, iou_thresh, cap=None):
         """vp_detect_infer: HxWx3 BGR uint8 frame -> ([n][6] float32 rows x1, y1, x2, y2, confidence, class_id; total kept) through the attached network."""
-        f = frame_bgr_u8
-        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.strides[2] != 1 or f.strides[1] != 3:
-            f = np.ascontiguousarray(f, dtype=np.uint8)
-        cap = 1024 if cap is None else cap
-        out = np.zeros((max(cap, 1), 6), np.float32)
-        n = C.c_int()
-        rc = self._lib.vp_detect_infer(self._h, _ptr(f), f.shape[0], f.shape[1], f.strides[0], float(conf_thresh), float(iou_thresh), _ptr(out), cap, C.byref(n))
-        if rc == -5:
-            raise VpRangeError(f"vp_detect_infer failed ({rc}): {self._lib.vp_detect_last_error(self._h).decode(errors='replace')}")
-        self._check(rc, "vp_detect_infer")
-        k = min(n.value, cap)
-        det = out[:k].copy()
-        det[:, 5] = out[:k, 5].view(np.int32).astype(np.float32)
-        return det, n.value
+        f = self._frame(frame_bgr_u8)
+        return self._rows("vp_detect_infer", (_ptr(f), f.shape[0], f.shape[1], f.strides[0]), conf_thresh, iou_thresh, 1024 if cap is None else cap, True, True)
 
     __del__ = close
 
@@ -999,11 +987,30 @@ class Detector:
         if rc != 0:
             raise VpError(f"{what} failed ({rc}): {self._lib.vp_detect_last_error(self._h).decode(errors='replace')}")
 
-    def preprocess(self, frame_bgr_u8):
-        """HxWx3 BGR uint8 -> ([3][net_h][net_w] float32 planes R, G, B in [0, 1], (scale, pad_x, pad_y))."""
-        f = frame_bgr_u8
+    @staticmethod
+    def _frame(frame_u8):
+        f = np.asarray(frame_u8)
         if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.strides[2] != 1 or f.strides[1] != 3:
             f = np.ascontiguousarray(f, dtype=np.uint8)
+        return f
+
+    def _rows(self, entry, head, conf_thresh, iou_thresh, cap, int_class, range_error=False):
+        """allocate `cap` rows, call `entry`(handle, *head, conf, iou, rows, cap, &count), slice: ([min(count, cap)][6] float32, count).  `int_class`: the
+        entry writes vp_detection records, whose class_id is an int."""
+        out = np.zeros((max(cap, 1), 6), np.float32)
+        n = C.c_int()
+        rc = getattr(self._lib, entry)(self._h, *head, float(conf_thresh), float(iou_thresh), _ptr(out), cap, C.byref(n))
+        if range_error and rc == -5:
+            raise VpRangeError(f"{entry} failed ({rc}): {self._lib.vp_detect_last_error(self._h).decode(errors='replace')}")
+        self._check(rc, entry)
+        rows = out[:min(n.value, cap)].copy()
+        if int_class:
+            rows[:, 5] = rows[:, 5].view(np.int32).astype(np.float32)
+        return rows, n.value
+
+    def preprocess(self, frame_bgr_u8):
+        """HxWx3 BGR uint8 -> ([3][net_h][net_w] float32 planes R, G, B in [0, 1], (scale, pad_x, pad_y))."""
+        f = self._frame(frame_bgr_u8)
         out = np.empty((3, self.net_h, self.net_w), np.float32)
         self._check(self._lib.vp_detect_preprocess(self._h, _ptr(f), f.shape[0], f.shape[1], f.strides[0], _ptr(out)), "vp_detect_preprocess")
         return out, self.letterbox()
@@ -1019,24 +1026,9 @@ class Detector:
     def postprocess(self, raw, conf_thresh, iou_thresh, cap=None):
         """raw [num_attrs][num_boxes] float32 -> ([n][6] float32 rows x1, y1, x2, y2, confidence, class_id; total kept)."""
         raw = np.ascontiguousarray(raw, dtype=np.float32)
-        cap = raw.shape[1] if cap is None else cap
-        out = np.zeros((max(cap, 1), 6), np.float32)
-        n = C.c_int()
-        self._check(self._lib.vp_detect_postprocess(self._h, _ptr(raw), 0, raw.shape[0], raw.shape[1], float(conf_thresh), float(iou_thresh), _ptr(out), cap,
-                                                    C.byref(n)), "vp_detect_postprocess")
-        k = min(n.value, cap)
-        det = out[:k].copy()
-        det[:, 5] = out[:k, 5].view(np.int32).astype(np.float32)   # class_id is an int in the struct
-        return det, n.value
+        return self._rows("vp_detect_postprocess", (_ptr(raw), 0, raw.shape[0], raw.shape[1]), conf_thresh, iou_thresh, raw.shape[1] if cap is None else cap, True)
 
     # ---- the Python wrapper's arithmetic (Models/inference/auto_speed_infer.py; vp_hip.h vp_detect_*_pil / _agnostic)
-    @staticmethod
-    def _frame(frame_u8):
-        f = np.asarray(frame_u8)
-        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.strides[2] != 1 or f.strides[1] != 3:
-            f = np.ascontiguousarray(f, dtype=np.uint8)
-        return f
-
     def preprocess_pil(self, frame_u8, pixel_format=VP_RGB8):
         """vp_detect_preprocess_pil: HxWx3 uint8 frame (RGB as a PIL image gives it, or VP_BGR8) -> ([3][net_h][net_w] float32 planes R, G, B, (scale, pad_x, pad_y)),
         Pillow's BILINEAR letterbox + ToTensor bit for bit."""
@@ -1048,25 +1040,13 @@ class Detector:
     def postprocess_agnostic(self, raw, conf_thresh, iou_thresh, cap=None):
         """vp_detect_postprocess_agnostic: raw [num_attrs][num_boxes] float32 -> ([n][6] float32 rows x1, y1, x2, y2, score, class; total kept)."""
         raw = np.ascontiguousarray(raw, dtype=np.float32)
-        cap = raw.shape[1] if cap is None else cap
-        out = np.zeros((max(cap, 1), 6), np.float32)
-        n = C.c_int()
-        self._check(self._lib.vp_detect_postprocess_agnostic(self._h, _ptr(raw), 0, raw.shape[0], raw.shape[1], float(conf_thresh), float(iou_thresh), _ptr(out), cap,
-                                                             C.byref(n)), "vp_detect_postprocess_agnostic")
-        return out[:min(n.value, cap)].copy(), n.value
+        return self._rows("vp_detect_postprocess_agnostic", (_ptr(raw), 0, raw.shape[0], raw.shape[1]), conf_thresh, iou_thresh, raw.shape[1] if cap is None else cap, False)
 
     def infer_pil(self, frame_u8, conf_thresh, iou_thresh, cap=None, pixel_format=VP_RGB8):
         """vp_detect_infer_pil: frame -> ([n][6] float32 rows x1, y1, x2, y2, score, class; total kept) through the attached network."""
         f = self._frame(frame_u8)
-        cap = 1024 if cap is None else cap
-        out = np.zeros((max(cap, 1), 6), np.float32)
-        n = C.c_int()
-        rc = self._lib.vp_detect_infer_pil(self._h, _ptr(f), f.shape[0], f.shape[1], f.strides[0], int(pixel_format), float(conf_thresh), float(iou_thresh), _ptr(out),
-                                           cap, C.byref(n))
-        if rc == -5:
-            raise VpRangeError(f"vp_detect_infer_pil failed ({rc}): {self._lib.vp_detect_last_error(self._h).decode(errors='replace')}")
-        self._check(rc, "vp_detect_infer_pil")
-        return out[:min(n.value, cap)].copy(), n.value
+        return self._rows("vp_detect_infer_pil", (_ptr(f), f.shape[0], f.shape[1], f.strides[0], int(pixel_format)), conf_thresh, iou_thresh, 1024 if cap is None else cap,
+                          False, True)
 
 
 def detect_geometry_pil(net_h, net_w, h, w):

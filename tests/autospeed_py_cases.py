@@ -80,6 +80,27 @@ def decode_cases():
     return cases
 
 
+LARGE_BOXES = 2100
+
+
+def large_case(boxes=LARGE_BOXES):
+    """(raw [8][boxes], conf, iou, geometry, orig_w, orig_h): more than 1024 candidates, so the sort holds several keys per thread and the compaction
+    several rows per thread.  10 x 10 boxes on a 15-pixel grid of 68 columns, every one a candidate; every odd k with (k // 2) % 5 == 0 sits 3 pixels
+    right of box k - 1 instead (IoU 7/13 = 0.54 against the 0.45 threshold: one of the two goes, a tenth of all boxes), every other pair is disjoint.
+    Raw scores 3.0 - 0.001 * ((k * 997) % 2100) in class k % 4 are all different (997 is prime): their sigmoids are 4.5e-5 apart or more, about
+    750 fp32 ulps, and 0.11 or more above conf."""
+    k = np.arange(boxes)
+    raw = np.full((8, boxes), -6.0, np.float32)
+    raw[0] = 6 + (k % 68) * 15
+    raw[1] = 6 + (k // 68) * 15
+    near = (k % 2 == 1) & ((k // 2) % 5 == 0)
+    raw[0, near] = raw[0, k[near] - 1] + 3
+    raw[1, near] = raw[1, k[near] - 1]
+    raw[2:4] = 10.0
+    raw[4 + k % 4, k] = (3.0 - 0.001 * ((k * 997) % 2100)).astype(np.float32)
+    return raw, 0.6, 0.45, (0.5, 10, 4), 2028, 1016
+
+
 def fixture_cases():
     """the fixture's candidate columns (the reference module's raw near or above the threshold) with the fixture's geometry: the kept rows are the
     reference wrapper's own"""
@@ -89,6 +110,39 @@ def fixture_cases():
         geom = (float(g[f"geom_{fi}"][0]), int(g[f"geom_{fi}"][1]), int(g[f"geom_{fi}"][2]))
         out.append((g[f"cand_raw_{fi}"], float(g["conf"]), float(g["iou"]), geom, int(w), int(h), g[f"rows_{fi}"]))
     return out
+
+
+def pin_cases(large_boxes=(LARGE_BOXES, 1100)):
+    """{key: (raw, conf, iou, geometry, orig_w, orig_h)} of everything tests/golden/detect_agnostic_parent.npz holds (tools/pin_detect_agnostic.py)"""
+    out = {"decode_%d" % i: c[1:7] for i, c in enumerate(decode_cases())}
+    out.update({"fixture_%d" % i: c[:6] for i, c in enumerate(fixture_cases())})
+    out.update({"large_%d" % n: large_case(n) for n in large_boxes})
+    return out
+
+
+def pin_record(det, raw, conf, iou, geom, ow, oh):
+    """what the pin holds of one case: the rows of a call with room for every box, and the two counts -- that call's and the one a buffer of PIN_CAP
+    rows gets (whose rows must be the first PIN_CAP of the full call's)"""
+    det.set_letterbox(np.float32(geom[0]), geom[1], geom[2], ow, oh)
+    rows, n = det.postprocess_agnostic(raw, conf, iou)
+    head, n_cap = det.postprocess_agnostic(raw, conf, iou, cap=PIN_CAP)
+    assert np.array_equal(head.view(np.uint32), rows[:PIN_CAP].view(np.uint32))
+    return rows, np.array([n, n_cap], np.int32)
+
+
+PIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "detect_agnostic_parent.npz")
+PIN_CAP = 5
+PIN_EXACT_COLUMNS = [0, 1, 2, 3, 5]      # plain fp32 + - / : independent of expf.  Column 4 is a sigmoid and keeps the 1e-3 bar of check_decode
+
+
+def check_parent_pin(det, key):
+    """the case `key` against the rows the two-kernel library before the fold gave: counts, row order, corners and class bit-identical"""
+    pin = np.load(PIN)
+    rows, counts = pin_record(det, *pin_cases()[key])
+    want = pin[key + "_rows"]
+    assert np.array_equal(counts, pin[key + "_counts"]), (counts, pin[key + "_counts"])
+    assert rows.shape == want.shape
+    assert np.array_equal(rows[:, PIN_EXACT_COLUMNS].view(np.uint32), want[:, PIN_EXACT_COLUMNS].view(np.uint32))
 
 
 def rel(got, want):

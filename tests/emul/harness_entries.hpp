@@ -111,12 +111,12 @@ int emu_se_gate_scale(const unsigned long long* sums, int replicas, int C, int C
   q.sq = sq; q.Creal = Creal; q.frames = frames;
   return harness_done(launch_se_gate_scale(p, q, nullptr));
 }
-int emu_detect(const float* raw, int num_attrs, int num_boxes, float conf, float iou, float scale, int pad_x, int pad_y, int orig_w, int orig_h, float* boxes, int* cls,
-               void* out, int out_cap, int* count) {
+int emu_detect(int rule, const float* raw, int num_attrs, int num_boxes, float conf, float iou, float scale, int pad_x, int pad_y, int orig_w, int orig_h, float* boxes,
+               int* cls, void* out, int out_cap, int* count) {
   DetectParams p{};
   p.raw = raw; p.num_attrs = num_attrs; p.num_boxes = num_boxes; p.conf_thresh = conf; p.iou_thresh = iou; p.scale = scale; p.pad_x = pad_x; p.pad_y = pad_y;
   p.orig_w = orig_w; p.orig_h = orig_h; p.boxes = boxes; p.cls = cls; p.out = static_cast<Detection*>(out); p.out_cap = out_cap; p.count = count;
-  return harness_done(launch_detect_decode_nms(p, nullptr));
+  return harness_done(launch_detect_nms(p, rule ? kDetectAgnostic : kDetectPerClass, nullptr));
 }
 int emu_fc(const float* x, const float* w, const float* b, float* out, int N, int K, int act) {
   FcParams p{};

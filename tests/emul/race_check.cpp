@@ -26,7 +26,7 @@ int emu_mbconv_front(void*, void*, int, int, int, const void*, const void*, cons
 int emu_mbconv_back(void*, void*, int, int, int, int, const unsigned long long*, int, int, const float*, const float*, const float*, const float*, int, const float*, const float*,
                     void*, void*, void*, void*, int, const unsigned long long*);
 int emu_fc(const float*, const float*, const float*, float*, int, int, int);
-int emu_detect(const float*, int, int, float, float, float, int, int, int, int, float*, int*, void*, int, int*);
+int emu_detect(int, const float*, int, int, float, float, float, int, int, int, int, float*, int*, void*, int, int*);
 int emu_pool_partial(void*, void*, int, int, int, float*, int);
 int emu_attention(void*, void*, int, int, int, int, int, float, void*, void*, void*, void*, int);
 int emu_sppf_pool(void*, void*, int, int, int, void*, void*, int, int);
@@ -211,7 +211,7 @@ int main(int argc, char** argv) {
       bad |= emu_mbconv_back(ih.data(), il.data(), h, ww, C, C, sums.data(), 8, sq, w1.data(), b1.data(), w2q.data(), b2.data(), sqp, pw.data(), pb.data(), rh.data(), rl.data(),
                              oh_.data(), ol_.data(), cout, cfg ? sums.data() : nullptr);
     }
-    {  // detector decode + NMS (kernels_detect.hip): LDS candidate list, bitonic sort, suppression flags written between barriers
+    {  // detector decode + NMS (kernels_detect.hip), both rules: LDS candidate list, bitonic sort, suppression flags written between barriers
       const int nb = 600, na = 7;
       std::vector<float> raw = rnd((size_t)na * nb, 0.5f);
       for (int i = 0; i < nb; ++i) {
@@ -223,7 +223,9 @@ int main(int argc, char** argv) {
       std::vector<float> boxes((size_t)nb * 4);
       std::vector<int> cls(nb), count(2);
       std::vector<float> out((size_t)nb * 6);
-      bad |= emu_detect(raw.data(), na, nb, 0.1f, 0.4f, 0.5f, 0, 140, 1280, 720, boxes.data(), cls.data(), out.data(), nb, count.data());
+      bad |= emu_detect(0, raw.data(), na, nb, 0.1f, 0.4f, 0.5f, 0, 140, 1280, 720, boxes.data(), cls.data(), out.data(), nb, count.data());
+      // the agnostic rule's scores are sigmoids: the best of three N(0, 0.5) classes passes 0.5 for seven boxes in eight
+      bad |= emu_detect(1, raw.data(), na, nb, 0.5f, 0.4f, 0.5f, 0, 140, 1280, 720, boxes.data(), cls.data(), out.data(), nb, count.data());
     }
     std::vector<float> fx = rnd(200), fw = rnd(37 * 200, 0.1f), fb = rnd(37), fo(37);
     bad |= emu_fc(fx.data(), fw.data(), fb.data(), fo.data(), 37, 200, 1);

@@ -1,4 +1,4 @@
-"""The two kernels of the Python AutoSpeed wrapper's stages (kernels_detect.hip letterbox_paste_kernel, detect_agnostic_nms_kernel) and their C ABI
+"""The two kernels of the Python AutoSpeed wrapper's stages (kernels_detect.hip letterbox_paste_kernel, detect_nms_kernel<true>) and their C ABI
 (vp_detect_preprocess_pil, vp_detect_postprocess_agnostic; csrc/vp_detect.cpp) executed through the HIP-on-CPU emulation against
 tests/autospeed_py_ref.py, at the shapes of tests/test_gpu_autospeed_py.py."""
 import ctypes as ct
@@ -11,6 +11,7 @@ import pytest
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emul"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import autospeed_py_cases as cases  # noqa: E402
+import autospeed_py_ref as ref  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -34,6 +35,13 @@ def emu_lib():
 @pytest.fixture(scope="module")
 def det(emu_lib):
     d = emu_lib.Detector(cases.NET_H, cases.NET_W, max_boxes=128, max_attrs=8)
+    yield d
+    d.close()
+
+
+@pytest.fixture(scope="module")
+def big_det(emu_lib):
+    d = emu_lib.Detector(cases.NET_H, cases.NET_W, max_boxes=cases.LARGE_BOXES, max_attrs=8)
     yield d
     d.close()
 
@@ -83,6 +91,21 @@ def test_agnostic_decode_hand_built(det, case):
 def test_agnostic_decode_fixture_columns(det):
     for raw, conf, iou, geom, ow, oh, want in cases.fixture_cases():
         cases.check_decode(det, raw, conf, iou, geom, ow, oh, want=want)
+
+
+def test_agnostic_decode_more_than_1024_candidates(big_det):
+    """2100 boxes, every one a candidate: the sort runs on 4096 keys (four per thread), the compaction on three rows per thread"""
+    raw, conf, iou, geom, ow, oh = cases.large_case()
+    score_gap, iou_gap, n_cand = ref.candidate_iou_gap(raw, conf, iou)
+    assert n_cand == raw.shape[1] == 2100 and iou_gap >= 0.05 and score_gap >= 0.1
+    _, n, _ = cases.check_decode(big_det, raw, conf, iou, geom, ow, oh)
+    assert n == 1890
+    cases.check_decode(big_det, raw, conf, iou, geom, ow, oh, cap=5)
+
+
+@pytest.mark.parametrize("key", sorted(cases.pin_cases()))
+def test_agnostic_decode_keeps_the_two_kernel_library_s_bits(big_det, key):
+    cases.check_parent_pin(big_det, key)
 
 
 def test_existing_stages_keep_their_bits_around_the_new_ones(emu_lib, det):

@@ -37,6 +37,13 @@ def det(lib):
 
 
 @pytest.fixture(scope="module")
+def big_det(lib):
+    d = lib.Detector(cases.NET_H, cases.NET_W, max_boxes=cases.LARGE_BOXES, max_attrs=8)
+    yield d
+    d.close()
+
+
+@pytest.fixture(scope="module")
 def blob():
     from autoware_vision_pilot_amd import synthetic, weights as vw
 
@@ -103,6 +110,24 @@ def test_agnostic_decode_fixture_columns(det):
     for raw, conf, iou, geom, ow, oh, want in cases.fixture_cases():
         _, n, err = cases.check_decode(det, raw, conf, iou, geom, ow, oh, want=want)
         print(f"fixture columns: {n} kept, floats against the reference wrapper's rows {err:.2e}")
+
+
+def test_agnostic_decode_more_than_1024_candidates(big_det):
+    """2100 boxes, every one a candidate: the sort runs on 4096 keys (four per thread), the compaction on three rows per thread"""
+    raw, conf, iou, geom, ow, oh = cases.large_case()
+    score_gap, iou_gap, n_cand = ref.candidate_iou_gap(raw, conf, iou)
+    print(f"{n_cand} candidates of {raw.shape[1]} boxes, IoU gap {iou_gap:.3f}, score gap {score_gap:.3f}")
+    assert n_cand == raw.shape[1] == 2100 and iou_gap >= 0.05 and score_gap >= 0.1
+    _, n, err = cases.check_decode(big_det, raw, conf, iou, geom, ow, oh)
+    print(f"{n} kept, floats against the restatement {err:.2e}")
+    assert n == 1890
+    cases.check_decode(big_det, raw, conf, iou, geom, ow, oh, cap=5)
+
+
+@pytest.mark.parametrize("key", sorted(cases.pin_cases()))
+def test_agnostic_decode_keeps_the_two_kernel_library_s_bits(big_det, key):
+    """tests/golden/detect_agnostic_parent.npz: counts, row order, corners and class of the library before the two kernels became one, bit for bit"""
+    cases.check_parent_pin(big_det, key)
 
 
 # --------------------------------------------------------------------------------------------------------------- whole path
