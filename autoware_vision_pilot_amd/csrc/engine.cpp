@@ -460,9 +460,11 @@ std::vector<Act*> Engine::build_backbone(const WeightBlob& blob, const std::stri
     x->frames = N;
     for (int fi = 0; fi < N; ++fi) {
       sp.in = d_input_ + (size_t)fi * 3 * net_h() * net_w();
-      sp.out = frame_view(x, fi)->view();
+      Act* xf = frame_view(x, fi);
+      sp.out = xf->view();
       Op op;
       op.name = P + "0";
+      op.writes = {xf};
       op.flops = 2.0 * 27 * 32 * (x->H / N) * x->W;
       op.bytes = 4.0 * 3 * net_h() * net_w() + 2.0 * x->elems() / N;
       op.run = [sp](hipStream_t st) { return launch_stem(sp, st); };
@@ -566,6 +568,7 @@ std::vector<Act*> Engine::build_backbone(const WeightBlob& blob, const std::stri
           op.bytes = (split() ? 4.0 : 2.0) * (x->elems() + z->elems());
           op.kernel = std::string("mbconv_front<k") + std::to_string(S.k) + ",s" + std::to_string(stride) + (split() ? ">" : ",x1>");
           op.run = [mp](hipStream_t st) { return launch_mbconv_front(mp, st); };
+          op.writes = {z};
           ops_.push_back(std::move(op));
           ++j;
         } else {
@@ -586,6 +589,7 @@ std::vector<Act*> Engine::build_backbone(const WeightBlob& blob, const std::stri
         op.kernel = S.k == 3 ? "dwconv_pool<3>" : "dwconv_pool<5>";
         if (N > 1) op.kernel += ",batch";
         op.run = [dp](hipStream_t st) { return launch_dwconv(dp, st); };
+        op.writes = {z};
         ops_.push_back(std::move(op));
         ++j;
         }
@@ -668,6 +672,7 @@ std::vector<Act*> Engine::build_backbone(const WeightBlob& blob, const std::stri
         op.bytes = (split() ? 4.0 : 2.0) * (z->elems() + out->elems() + (residual ? x->elems() : 0)) + 4.0 * wf.size();
         op.kernel = std::string("mbconv_back<wm") + (z->H * z->W >= 12800 ? "4" : "1") + (split() ? ">" : ",x1>");
         op.run = [mb](hipStream_t st) { return launch_mbconv_back(mb, st); };
+        op.writes = {out};
         ops_.push_back(std::move(op));
         x = out;
       } else {
@@ -829,6 +834,7 @@ Act* Engine::build_context(const WeightBlob& blob, const std::string& p, const A
       op.name = p + "context_layer_3";
       op.run = [cp](hipStream_t st) { return launch_ctx_conv1(cp, st); };
     }
+    op.writes = {c};
     ops_.push_back(std::move(op));
   }
   const int couts[3] = {256, 512, cctx};
@@ -1012,6 +1018,7 @@ void Engine::build_model(const WeightBlob& blob) {
     op.name = "BackboneFeatureFusion";
     op.kernel = fp.octets ? "fusion<octets>" : "fusion";
     op.run = [fp](hipStream_t st) { return launch_fusion(fp, st); };
+    op.writes = {fused};
     ops_.push_back(std::move(op));
     deep = fused;
   }

@@ -72,7 +72,7 @@ struct Op {
   // SURVEY.md 8d's three-op count so whole-frame figures stay comparable across rounds); 0 = same as flops
   double flops_executed = 0;
   std::function<hipError_t(hipStream_t)> run;
-  std::vector<const Act*> writes;  // VP_ACT_SCALE engines: the tensors this launch stores (what vp_calibrate_range measures behind it)
+  std::vector<const Act*> writes;  // the tensors this launch stores in HBM: what vp_calibrate_range and vp_range_survey measure behind it (host bookkeeping only)
 };
 
 // ConvTranspose2d(k2, s2) [+ 1x1 skip link] -> Conv3x3 multiplied out at load (engine_upconv.cpp): fp64, real (un-padded) channel counts
@@ -236,6 +236,13 @@ class Engine {
     neck_up_cat(name, a, b, out, a_off, a_nch, b_off, b_nch);
   }
   void calibrate_range(int target_log2);
+  // vp_range_survey (include/vp_hip.h): one entry per acts() entry, count == 0 where the plan never stores the tensor
+  struct RangeStats {
+    float absmax = 0.0f;
+    int exp = 0;
+    unsigned long long count = 0, nonfinite = 0, zeros = 0, bins[VP_HIST_BINS] = {};
+  };
+  std::vector<RangeStats> range_survey();
   void reset_range();
   std::vector<int> act_scales() const;                  // one per acts() entry
   void set_act_scales(const int* exps, int n);
@@ -331,6 +338,12 @@ class Engine {
   std::vector<int> act_exp_;        // VP_ACT_SCALE: exponent per tie group (Act::tie)
   std::vector<char> act_exp_seen_;  // ... measured since the last reset: a later measurement only raises it
   unsigned* d_absmax_ = nullptr;
+  unsigned long long* d_survey_ = nullptr;   // range_survey: per tensor {abs-max bits | non-finite count << 32 as two words, VP_HIST_WORDS counters}
+  // The eager launch-by-launch walk calibrate_range and range_survey share (engine_io.cpp): visit(i, a, begin, prime) runs behind launch i for every
+  // tensor a it stores; `begin` is the first launch of the pass, `prime` marks AutoDrive's features-only pass over the previous frame.  visit returns
+  // false to start the round over; walk_stored returns whether a round ran to its end.
+  using StoredVisitor = std::function<bool(size_t i, const Act* a, size_t begin, bool prime)>;
+  bool walk_stored(const StoredVisitor& visit);
   uint8_t* d_prev_frame_ = nullptr;
   size_t prev_frame_cap_ = 0;
   bool prev_frame_stashed_ = false;  // stash_previous_frame() ran and no frame was uploaded since

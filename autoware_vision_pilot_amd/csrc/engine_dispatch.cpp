@@ -594,8 +594,8 @@ void Engine::push_conv_op(const std::string& name, const Act* in, const PackedCo
     const bool halo_plain = tile >= 100 && tile - 100 <= 5 && !(tile == 104 && o.tile < 0 && head_conv_supported(p));
     if (!(halo_plain || tile < 5) || store_mode != STORE_NHWC || o.in2 || fuse_decode || !out || (o.tile < 0 && tile < 100 && convt_rs_supported(p, sp)))
       throw std::invalid_argument("VP_ACT_SCALE: only the generic GEMM kernel and the halo kernel's tiles 0 - 5 (NHWC store) carry the activation scale: " + name);
-    op.writes = {out};
   }
+  if (out) op.writes = {out};
   if (pc.nsplit > 1) op.launch = "nsplit=" + std::to_string(pc.nsplit);   // the tag only says "+splitk"
   op.flops = 2.0 * M * (double)cout_real * (store_mode == STORE_SHUFFLE2 ? 4 : 1) * in->Creal * ks * ks;
   const double esz = sp ? 4.0 : 2.0;

@@ -812,9 +812,45 @@ void Engine::stash_previous_frame() {
   prev_frame_stashed_ = true;   // upload_frame turns it into prev_frame_valid_ for the ONE frame uploaded next (the pair's current half)
 }
 
-// Runs the plan eagerly, launch by launch, on the resident frame (AutoDrive: on the frame vp_infer_pair primed with first, then on the current one), measures
-// every tensor a launch stores (act_absmax_kernel) and moves its exponent so that the stored abs-max lies in [2^(target - 1), 2^target).  The first
-// measurement of a tensor since vp_reset_range sets the exponent, later ones only raise it: calibrating on several frames gives the per-tensor maximum.
+// The eager walk of the plan that calibration and the range survey share: launch by launch on the resident input (the uploaded frame, or the tensor
+// vp_infer_tensor / vp_detect_infer left), `visit` behind every launch for every tensor the launch stores (Op::writes).  AutoDrive pairs the resident frame
+// with the previous one (head.cat carries both): a round is a features-only pass over the previous frame (`prime`: up to the launch that parks P5, the
+// shift left out) -- the stashed frame of vp_infer_pair where the engine keeps one, else the resident frame again -- and then the whole plan on the current
+// one.  The detector and the lane network are single-frame plans like the scene networks: one pass, and the AutoDrive-only launch indices stay out of it.
+// A visitor that returns false starts the round over (at most 16 rounds).
+bool Engine::walk_stored(const StoredVisitor& visit) {
+  const size_t first = input_is_tensor_ ? first_net_op_ : 0;
+  const bool ad = kind_ == 4;
+  const size_t shift_op = ad ? ad_shift_op_ : SIZE_MAX;
+  auto pass = [&](size_t begin, size_t end, bool prime) -> bool {
+    for (size_t i = begin; i < end; ++i) {
+      if (prime && i == shift_op) continue;
+      run_ops(stream_, i, i + 1);
+      for (const Act* a : ops_[i].writes)
+        if (!visit(i, a, begin, prime)) return false;
+    }
+    return true;
+  };
+  if (!ad) return pass(first, ops_.size(), false);
+  const bool pair = prev_frame_valid_ && !input_is_tensor_ && prev_frame_cap_ >= (size_t)frame_h_ * frame_stride_;
+  bool done = false;
+  for (int round = 0; round < 16 && !done; ++round) {
+    if (pair) std::swap(d_frame_, d_prev_frame_);
+    try {
+      pass(first, ad_place_op_ + 1, true);   // the previous frame (or the resident one again): features only
+    } catch (...) {
+      if (pair) std::swap(d_frame_, d_prev_frame_);
+      throw;
+    }
+    if (pair) std::swap(d_frame_, d_prev_frame_);
+    done = pass(first, ops_.size(), false);
+  }
+  return done;
+}
+
+// Runs the plan eagerly (walk_stored), measures every tensor a launch stores (act_absmax_kernel) and moves its exponent so that the stored abs-max lies in
+// [2^(target - 1), 2^target).  The first measurement of a tensor since vp_reset_range sets the exponent, later ones only raise it: calibrating on several
+// frames gives the per-tensor maximum.
 void Engine::calibrate_range(int target_log2) {
   if (!act_scale() || (kind_ != 4 && kind_ != 5 && kind_ != 6)) throw std::invalid_argument("vp_calibrate_range: engines created with VP_ACT_SCALE only");
   if (target_log2 == 0) target_log2 = 12;
@@ -823,82 +859,56 @@ void Engine::calibrate_range(int target_log2) {
   VP_HIP_CHECK(hipSetDevice(gpu_));
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
   if (!d_absmax_) d_absmax_ = static_cast<unsigned*>(dalloc(2 * sizeof(unsigned)));
-  const size_t first = input_is_tensor_ ? first_net_op_ : 0;
-  // AutoDrive pairs the resident frame with the previous one (head.cat carries both); the detector and the lane network are single-frame plans: one
-  // pass over whatever input is resident, and the AutoDrive-only launch indices stay out of it
   const bool ad = kind_ == 4;
   const size_t shift_op = ad ? ad_shift_op_ : SIZE_MAX;
   const int head_tie = (!ad || ops_[ad_place_op_].writes.empty()) ? -1 : ops_[ad_place_op_].writes[0]->tie;
   std::vector<int> raises(act_exp_.size(), 0), lower(act_exp_.size(), INT_MIN);
   for (size_t g = 0; g < lower.size(); ++g)
     if (act_exp_seen_[g]) lower[g] = act_exp_[g];
-  auto launch = [&](size_t i) {
-    const hipError_t e = ops_[i].run(stream_);
-    if (e != hipSuccess) throw std::runtime_error("launch failed in layer '" + ops_[i].name + "': " + hipGetErrorString(e));
-  };
   // false: the exponent of the tensor that carries the previous frame's features (head.cat) moved behind the shift -- the round starts over
-  auto pass = [&](size_t begin, size_t end, bool prime) -> bool {
-    for (size_t i = begin; i < end; ++i) {
-      if (prime && i == shift_op) continue;
-      launch(i);
-      for (const Act* a : ops_[i].writes) {
-        const int g = a->tie;
-        if (g < 0) continue;
-        bool restart = false;
-        for (;;) {
-          unsigned r[2] = {0u, 0u};
-          fill_zero(d_absmax_, sizeof(r));
-          VP_HIP_CHECK(launch_act_absmax(a->hi, a->lo, a->Creal, a->H, a->W, a->C, d_absmax_, stream_));
-          copy_d2h(r, d_absmax_, sizeof(r));
-          float amax;
-          std::memcpy(&amax, &r[0], sizeof(float));
-          const bool bad = r[1] != 0u;
-          int want = act_exp_[g];
-          if (bad) {
-            if (++raises[g] > 3) throw RangeError("vp_calibrate_range: tensor '" + a->name + "' still holds non-finite values after its exponent was raised 3 times by 16");
-            want += 16;
-          } else if (amax == 0.0f) {
-            break;   // an all-zero tensor keeps its exponent
-          } else {
-            int e2 = 0;
-            std::frexp(amax, &e2);   // stored abs-max in [2^(e2 - 1), 2^e2)
-            want = std::max(lower[g], act_exp_[g] + e2 - target_log2);
-            lower[g] = want;
-            act_exp_seen_[g] = 1;
-          }
-          if (want == act_exp_[g]) break;
-          act_exp_[g] = want;
-          // head.cat also holds the PREVIOUS frame's features, stored under the old exponent: settle the exponent on this frame first (so that the
-          // previous frame's smaller values cannot take it back), then start the round over
-          if (ad && !prime && g == head_tie && i >= shift_op) restart = true;
-          for (size_t j = begin; j <= i; ++j) {   // every launch so far that writes the tensor stores it again
-            if (j == shift_op) continue;
-            bool writes = false;
-            for (const Act* w : ops_[j].writes) writes |= w->tie == g;
-            if (writes) launch(j);
-          }
-          if (!bad) break;
-        }
-        if (restart) return false;
+  auto settle = [&](size_t i, const Act* a, size_t begin, bool prime) -> bool {
+    const int g = a->tie;
+    if (g < 0) return true;
+    bool restart = false;
+    for (;;) {
+      unsigned r[2] = {0u, 0u};
+      fill_zero(d_absmax_, sizeof(r));
+      VP_HIP_CHECK(launch_act_absmax(a->hi, a->lo, a->Creal, a->H, a->W, a->C, d_absmax_, stream_));
+      copy_d2h(r, d_absmax_, sizeof(r));
+      float amax;
+      std::memcpy(&amax, &r[0], sizeof(float));
+      const bool bad = r[1] != 0u;
+      int want = act_exp_[g];
+      if (bad) {
+        if (++raises[g] > 3) throw RangeError("vp_calibrate_range: tensor '" + a->name + "' still holds non-finite values after its exponent was raised 3 times by 16");
+        want += 16;
+      } else if (amax == 0.0f) {
+        break;   // an all-zero tensor keeps its exponent
+      } else {
+        int e2 = 0;
+        std::frexp(amax, &e2);   // stored abs-max in [2^(e2 - 1), 2^e2)
+        want = std::max(lower[g], act_exp_[g] + e2 - target_log2);
+        lower[g] = want;
+        act_exp_seen_[g] = 1;
       }
+      if (want == act_exp_[g]) break;
+      act_exp_[g] = want;
+      // head.cat also holds the PREVIOUS frame's features, stored under the old exponent: settle the exponent on this frame first (so that the
+      // previous frame's smaller values cannot take it back), then start the round over
+      if (ad && !prime && g == head_tie && i >= shift_op) restart = true;
+      for (size_t j = begin; j <= i; ++j) {   // every launch so far that writes the tensor stores it again
+        if (j == shift_op) continue;
+        bool writes = false;
+        for (const Act* w : ops_[j].writes) writes |= w->tie == g;
+        if (writes) run_ops(stream_, j, j + 1);
+      }
+      if (!bad) break;
     }
-    return true;
+    return !restart;
   };
-  const bool pair = ad && prev_frame_valid_ && !input_is_tensor_ && prev_frame_cap_ >= (size_t)frame_h_ * frame_stride_;
   bool done = false;
   try {
-    if (!ad) done = pass(first, ops_.size(), false);
-    for (int round = 0; round < 16 && !done; ++round) {
-      if (pair) std::swap(d_frame_, d_prev_frame_);
-      try {
-        pass(first, ad_place_op_ + 1, true);   // the previous frame (or the resident one again): features only
-      } catch (...) {
-        if (pair) std::swap(d_frame_, d_prev_frame_);
-        throw;
-      }
-      if (pair) std::swap(d_frame_, d_prev_frame_);
-      done = pass(first, ops_.size(), false);
-    }
+    done = walk_stored(settle);
   } catch (...) {
     hipStreamSynchronize(stream_);
     ad_primed_ = false;
@@ -909,6 +919,62 @@ void Engine::calibrate_range(int target_log2) {
   ad_primed_ = ad && done;   // the current frame's features sit in the "current" slot under the final exponents
   exps_changed();
   if (!done) throw RangeError("vp_calibrate_range: the exponents did not settle");
+}
+
+// vp_range_survey: the same walk with a visitor that only measures.  Behind the LAST launch that stores a tensor (alias slices of a concatenation, in-place
+// copies: one measurement of the finished tensor) it queues act_absmax_kernel and act_exp_hist_kernel on the stored planes; nothing is read back until the
+// pass has ended, so the survey costs one synchronisation.  No exponent, launch or graph changes: the engine is left as a plain pass over the same input
+// leaves it, outputs on the device included.  Non-finite values are what the survey reports, never an error of its own.
+std::vector<Engine::RangeStats> Engine::range_survey() {
+  if (base_ || frames_ != 1) throw std::invalid_argument("vp_range_survey: the engine must own its whole network (not a shared-prefix head, not a batched encoder)");
+  if (!input_is_tensor_ && !d_frame_) throw std::runtime_error("no frame resident: call vp_upload_frame / vp_infer first");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  constexpr size_t kWords = VP_HIST_WORDS + 1;   // word 0: {abs-max bits, non-finite count} as launch_act_absmax writes them, then the histogram's words
+  const size_t n = acts_.size();
+  if (!d_survey_) d_survey_ = static_cast<unsigned long long*>(dalloc(n * kWords * sizeof(unsigned long long)));
+  fill_zero(d_survey_, n * kWords * sizeof(unsigned long long));
+  std::map<const Act*, size_t> index, last;
+  for (size_t t = 0; t < n; ++t) index[acts_[t].get()] = t;
+  for (size_t i = input_is_tensor_ ? first_net_op_ : 0; i < ops_.size(); ++i)
+    for (const Act* a : ops_[i].writes) last[a] = i;
+  std::vector<char> measured(n, 0);
+  auto measure = [&](size_t i, const Act* a, size_t, bool prime) -> bool {
+    const auto it = index.find(a);
+    if (prime || it == index.end() || last[a] != i || measured[it->second]) return true;
+    unsigned long long* d = d_survey_ + it->second * kWords;
+    VP_HIP_CHECK(launch_act_absmax(a->hi, a->lo, a->Creal, a->H, a->W, a->C, reinterpret_cast<unsigned*>(d), stream_));
+    VP_HIP_CHECK(launch_act_exp_hist(a->hi, a->lo, a->Creal, a->H, a->W, a->C, d + 1, stream_));
+    measured[it->second] = 1;
+    return true;
+  };
+  try {
+    walk_stored(measure);
+  } catch (...) {
+    hipStreamSynchronize(stream_);
+    ad_primed_ = false;
+    throw;
+  }
+  std::vector<unsigned long long> host(n * kWords);
+  copy_d2h(host.data(), d_survey_, host.size() * sizeof(unsigned long long));
+  ad_primed_ = kind_ == 4;   // the current frame's features sit in the "current" slot, as behind any pass
+  have_outputs_ = true;
+  host_logits_valid_ = host_mask_valid_ = false;
+  note_pass();
+  std::vector<RangeStats> out(n);
+  for (size_t t = 0; t < n; ++t) {
+    RangeStats& r = out[t];
+    r.exp = act_exp(acts_[t].get());
+    if (!measured[t]) continue;
+    const unsigned long long* w = host.data() + t * kWords;
+    const unsigned amax_bits = (unsigned)(w[0] & 0xFFFFFFFFull);
+    std::memcpy(&r.absmax, &amax_bits, sizeof(float));
+    r.nonfinite = w[0] >> 32;
+    for (int k = 0; k < VP_HIST_BINS; ++k) r.bins[k] = w[1 + k];
+    r.zeros = w[1 + VP_HIST_BINS];
+    r.count = w[2 + VP_HIST_BINS];
+  }
+  return out;
 }
 
 }  // namespace vp

@@ -300,6 +300,7 @@ Act* Engine::add_upconv(const std::string& name, const Act* in, const Act* skip_
   op.flops_executed = 2.0 * M2 * cout * (4.0 * cin + 9.0 * cs);
   op.bytes = (x1 ? 2.0 : 4.0) * ((M2 / 4 * cin + M2 * cs + M2 * cout) + cout * (16.0 * cin + 9.0 * cs));
   op.run = [p, sh](hipStream_t st) { return launch_upconv(p, sh, st); };
+  op.writes = {out};
   ops_.push_back(std::move(op));
   return out;
 }

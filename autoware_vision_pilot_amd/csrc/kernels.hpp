@@ -386,6 +386,11 @@ hipError_t launch_act_to_nchw(const ActView& a, int Creal, float* dst, hipStream
 // c real channels of an h x w tensor with channel pitch c_pitch (c_pitch and the plane pointers multiples of 8 elements), result[1] = count of
 // non-finite elements.  Integer max / add only: the same bits whatever order the workgroups finish in.  The caller zeroes result[0..2) first.
 hipError_t launch_act_absmax(const half_t* hi, const half_t* lo, int c, int h, int w, int c_pitch, unsigned* result, hipStream_t st);
+// Range survey (kernels_misc.hip act_exp_hist_kernel), arguments as launch_act_absmax: result[k] += elements with floor(log2 |hi + lo|) == VP_HIST_EXP_MIN + k
+// (k < VP_HIST_BINS), result[VP_HIST_BINS] += exact zeros, result[VP_HIST_BINS + 1] += real elements visited; non-finite elements in neither a bin nor the
+// zeros.  Integer adds only.  The caller zeroes the VP_HIST_WORDS words first.
+constexpr int VP_HIST_BINS = 40, VP_HIST_EXP_MIN = -24, VP_HIST_WORDS = VP_HIST_BINS + 2;   // == VP_RANGE_BINS / VP_RANGE_EXP_MIN of vp_hip.h (vp_api.cpp checks)
+hipError_t launch_act_exp_hist(const half_t* hi, const half_t* lo, int c, int h, int w, int c_pitch, unsigned long long* result, hipStream_t st);
 
 // ---- AutoDrive blocks (kernels_autodrive.hip)
 // channel-slice copy: dst[pix][dst_off + c] = src[pix][src_off + c], c < nch (torch.cat / split / chunk along C)

@@ -485,6 +485,63 @@ __global__ __launch_bounds__(256) void act_absmax_kernel(const half_t* hi, const
   }
 }
 
+// Range survey (vp_range_survey): counts the stored values x = (float)hi + (float)lo of one tensor per binary exponent.  result[k], k < VP_HIST_BINS:
+// elements with floor(log2 |x|) == VP_HIST_EXP_MIN + k; result[VP_HIST_BINS]: exact zeros (+0 and -0); result[VP_HIST_BINS + 1]: real elements visited.
+// Non-finite elements are counted in neither a bin nor the zeros (act_absmax_kernel counts them); pad channels are left out by that kernel's rule, and
+// the loads are its loads: one 16-byte octet per plane and thread.  The exponent is read off the fp32 bits: a non-zero sum of two fp16 values is a
+// multiple of 2^-24, hence a normal fp32 number.  A finite sum of 2^16 or more -- no (hi, lo) pair an engine stores reaches it, only arbitrary planes
+// handed to the operator entry can -- is counted in the top bin, so that bins + zeros + non-finite always add up to the element count.
+// In a real tensor almost all values fall into three or four adjacent bins, so a shared histogram would serialise a wave on one address.  Here every
+// LANE owns a sub-histogram in LDS, laid out [wave][counter pair][lane]: the word of (pair, lane) lies in bank `lane` whatever the bin, so one
+// ds_add_u32 per element is conflict-free for every value distribution, and nobody else touches a lane's words (no barrier until the end).  Two
+// 16-bit counters share a word (the add is 1 or 1 << 16): 21 words per lane, 21.5 KB per workgroup instead of 42, which is what lets seven
+// workgroups share a CU and keep act_absmax_kernel's number of loads in flight.  A 16-bit counter holds a lane's share as long as the lane visits
+// fewer than 2^16 elements; the launcher sizes the grid for that (kHistOctetsPerThread).  At the end a wave sums its 64 sub-histograms by shuffles,
+// the block's four waves meet in LDS, and one thread per counter adds the block's sum to global memory with an ordinary vector atomic on the 64-bit
+// word (at most 42 per block).  All sums are integer: the result does not depend on the order, two runs give equal words.
+constexpr long long kHistOctetsPerThread = 8191;   // 8 elements each: 65528 < 2^16
+__global__ __launch_bounds__(256) void act_exp_hist_kernel(const half_t* hi, const half_t* lo, int c, long long npix, int c_pitch, unsigned long long* result) {
+  constexpr int NB = VP_HIST_BINS + 1;   // the bins, then the zeros
+  constexpr int NW = (NB + 1) / 2;       // words per lane: counter b is the (b & 1) half of word b >> 1
+  __shared__ unsigned hist[4][NW][64];
+  __shared__ unsigned long long wsum[4][NB + 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned(*mine)[64] = hist[wave];
+#pragma unroll
+  for (int b = 0; b < NW; ++b) mine[b][lane] = 0u;
+  const int CG = (c + 7) >> 3;
+  unsigned seen = 0u;
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < npix * CG; t += (long long)gridDim.x * 256) {
+    const int cg = (int)(t % CG);
+    const size_t off = (size_t)(t / CG) * c_pitch + cg * 8;
+    const h8_t h = *reinterpret_cast<const h8_t*>(hi + off);
+    h8_t l = {};
+    if (lo) l = *reinterpret_cast<const h8_t*>(lo + off);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (cg * 8 + i >= c) continue;
+      ++seen;
+      const unsigned u = __float_as_uint((float)h[i] + (float)l[i]) & 0x7FFFFFFFu;
+      if (u >= 0x7F800000u) continue;
+      int b = (int)(u >> 23) - (127 + VP_HIST_EXP_MIN);
+      b = u == 0u ? VP_HIST_BINS : (b > VP_HIST_BINS - 1 ? VP_HIST_BINS - 1 : (b < 0 ? 0 : b));
+      atomicAdd(&mine[b >> 1][lane], 1u << ((b & 1) << 4));   // the lane's own word: one ds_add_u32, no return value
+    }
+  }
+#pragma unroll 1
+  for (int b = 0; b <= NB; ++b) {
+    unsigned long long v = b < NB ? ((mine[b >> 1][lane] >> ((b & 1) << 4)) & 0xFFFFu) : seen;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0) wsum[wave][b] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x <= NB) {
+    const unsigned long long v = wsum[0][threadIdx.x] + wsum[1][threadIdx.x] + wsum[2][threadIdx.x] + wsum[3][threadIdx.x];
+    if (v) atomicAdd(result + threadIdx.x, v);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- launchers
 hipError_t launch_preprocess(const PreprocessParams& p, hipStream_t st) {
   VP_LAUNCH(preprocess_kernel, dim3(nblk(p.out_w), p.out_h), dim3(256), 0, st, p);
@@ -567,6 +624,16 @@ hipError_t launch_act_absmax(const half_t* hi, const half_t* lo, int c, int h, i
   const long long n = (long long)h * w * ((c + 7) >> 3);
   const unsigned blocks = n > 1024ll * 256 ? 1024u : (unsigned)((n + 255) / 256);
   VP_LAUNCH(act_absmax_kernel, dim3(blocks), dim3(256), 0, st, hi, lo, c, (long long)h * w, c_pitch, result);
+}
+hipError_t launch_act_exp_hist(const half_t* hi, const half_t* lo, int c, int h, int w, int c_pitch, unsigned long long* result, hipStream_t st) {
+  if (!hi || !result || c < 1 || h < 1 || w < 1 || c_pitch < ((c + 7) & ~7) || (c_pitch & 7) || ((reinterpret_cast<uintptr_t>(hi) | reinterpret_cast<uintptr_t>(lo)) & 15))
+    return hipErrorInvalidValue;
+  const long long n = (long long)h * w * ((c + 7) >> 3);   // the grid of launch_act_absmax: the same octets per thread, the same bytes read ...
+  long long blocks = n > 1024ll * 256 ? 1024 : (n + 255) / 256;
+  const long long need = (n + 256 * kHistOctetsPerThread - 1) / (256 * kHistOctetsPerThread);   // ... unless a lane's 16-bit counters would not hold its share (beyond 2^34 elements)
+  if (need > blocks) blocks = need;
+  if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
+  VP_LAUNCH(act_exp_hist_kernel, dim3((unsigned)blocks), dim3(256), 0, st, hi, lo, c, (long long)h * w, c_pitch, result);
 }
 hipError_t launch_act_to_nchw(const ActView& a, int Creal, float* dst, hipStream_t st, float mul) {
   VP_LAUNCH(act_to_nchw_kernel, dim3(nblk((long long)a.H * a.W * Creal)), dim3(256), 0, st, a, Creal, dst, mul);

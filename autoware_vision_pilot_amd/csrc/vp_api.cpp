@@ -631,6 +631,27 @@ int vp_set_act_scales(vp_engine* e, const int* exps, int n) {
   return guarded(e, [&](vp::Engine& g) { g.set_act_scales(exps, n); });
 }
 
+// ---- range survey (engine_io.cpp Engine::range_survey)
+static_assert(VP_RANGE_BINS == vp::VP_HIST_BINS && VP_RANGE_EXP_MIN == vp::VP_HIST_EXP_MIN, "vp_hip.h and kernels.hpp describe one histogram");
+int vp_range_survey(vp_engine* e, vp_range_stats* out, int cap) {
+  if (cap < 0 || (cap > 0 && !out)) return VP_ERR_ARG;
+  int n = 0;
+  const int rc = guarded(e, [&](vp::Engine& g) {
+    const std::vector<vp::Engine::RangeStats> v = g.range_survey();
+    n = (int)v.size();
+    for (int i = 0; i < cap && i < n; ++i) {
+      vp_range_stats& o = out[i];
+      o.absmax = v[i].absmax;
+      o.exp = v[i].exp;
+      o.count = v[i].count;
+      o.nonfinite = v[i].nonfinite;
+      o.zeros = v[i].zeros;
+      std::memcpy(o.bins, v[i].bins, sizeof(o.bins));
+    }
+  });
+  return rc == VP_OK ? n : rc;
+}
+
 int vp_op_conv2d(int gpu_id, int precision, int mode, const float* in, int cin, int h, int w, const float* weight, const float* bias,
                  int cout, int ks, int act, int res_mode, const float* res, int tile, int bk, int nsplit, float* out, char* err,
                  size_t err_len) {
@@ -926,6 +947,27 @@ int vp_op_absmax(int gpu_id, const uint16_t* hi, const uint16_t* lo, int c, int 
     g.copy_d2h(r, dr, sizeof(r));
     std::memcpy(absmax, &r[0], sizeof(float));
     *nonfinite = r[1];
+  });
+}
+
+int vp_op_exp_hist(int gpu_id, const uint16_t* hi, const uint16_t* lo, int c, int h, int w, int c_pitch, unsigned long long* bins, unsigned long long* zeros,
+                   unsigned long long* count, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!hi || !bins || !zeros || !count || c < 1 || h < 1 || w < 1 || c_pitch < ((c + 7) & ~7) || (c_pitch & 7) || (long long)h * w * c_pitch > (1ll << 28))
+      throw std::invalid_argument("bad argument (c_pitch: a multiple of 8, at least c rounded up to 8)");
+    vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
+    const size_t n = (size_t)h * w * c_pitch;
+    vp::half_t* dh = reinterpret_cast<vp::half_t*>(g.alloc_f32((n + 1) / 2));
+    vp::half_t* dl = lo ? reinterpret_cast<vp::half_t*>(g.alloc_f32((n + 1) / 2)) : nullptr;
+    unsigned long long* dr = reinterpret_cast<unsigned long long*>(g.alloc_f32(2 * vp::VP_HIST_WORDS));   // zeroed
+    g.copy_h2d(dh, hi, n * sizeof(uint16_t));
+    if (lo) g.copy_h2d(dl, lo, n * sizeof(uint16_t));
+    VP_HIP_CHECK(vp::launch_act_exp_hist(dh, dl, c, h, w, c_pitch, dr, g.stream()));
+    unsigned long long r[vp::VP_HIST_WORDS];
+    g.copy_d2h(r, dr, sizeof(r));
+    std::memcpy(bins, r, VP_RANGE_BINS * sizeof(unsigned long long));
+    *zeros = r[VP_RANGE_BINS];
+    *count = r[VP_RANGE_BINS + 1];
   });
 }
 

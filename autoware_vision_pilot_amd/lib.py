@@ -99,6 +99,8 @@ _SIGS = {
     "vp_reset_range": (C.c_int, [_P]),
     "vp_act_scales": (C.c_int, [_P, _P, C.c_int]),
     "vp_set_act_scales": (C.c_int, [_P, _P, C.c_int]),
+    "vp_range_survey": (C.c_int, [_P, _P, C.c_int]),
+    "vp_op_exp_hist": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_char_p, C.c_size_t]),
     "vp_op_absmax": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint), C.c_char_p, C.c_size_t]),
     "vp_op_conv2d_scaled": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P,
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_char_p, C.c_size_t]),
@@ -168,6 +170,15 @@ VP_NORM_TORCHVISION, VP_NORM_OPENCV = 0, 1
 VP_RESIZE_CV_LINEAR, VP_RESIZE_PIL_BILINEAR, VP_RESIZE_PIL_BICUBIC = 0, 1, 2
 VP_GATHER_MASK, VP_GATHER_LOGITS = 0, 1
 VP_COMM_ID_BYTES = 128
+
+VP_RANGE_BINS, VP_RANGE_EXP_MIN = 40, -24
+
+
+class RangeStats(C.Structure):
+    """vp_range_stats (include/vp_hip.h)"""
+    _fields_ = [("absmax", C.c_float), ("exp", C.c_int), ("count", C.c_ulonglong), ("nonfinite", C.c_ulonglong), ("zeros", C.c_ulonglong),
+                ("bins", C.c_ulonglong * VP_RANGE_BINS)]
+
 
 _lib = None
 
@@ -640,6 +651,18 @@ class Engine:
         self._ck(self._lib.vp_tensor_read(self._h, i, _ptr(out)))
         return out
 
+    def range_survey(self):
+        """vp_range_survey over the resident input: one record per tensors() entry -- name, c, h, w, exp, absmax, count, nonfinite, zeros, bins (int64
+        [VP_RANGE_BINS], bins[k] = stored values with floor(log2 |x|) == VP_RANGE_EXP_MIN + k).  count == 0: the plan never stores that tensor.  Values
+        are STORED ones (tensor_read(i) * 2^-exp on an act_scale engine).  range_summary() derives headroom and the subnormal shares from a record."""
+        info = self.tensors()
+        buf = (RangeStats * max(1, len(info)))()
+        n = self._ck(self._lib.vp_range_survey(self._h, C.cast(buf, C.c_void_p), len(info)))
+        if n != len(info):
+            raise VpError(f"vp_range_survey answered {n} tensors, vp_tensor_count {len(info)}")
+        return [{"name": name, "c": c, "h": h, "w": w, "exp": int(r.exp), "absmax": np.float32(r.absmax), "count": int(r.count), "nonfinite": int(r.nonfinite),
+                 "zeros": int(r.zeros), "bins": np.array(r.bins[:], dtype=np.int64)} for (name, c, h, w), r in zip(info, buf)]
+
 
 def decode_logits_host(logits_chw, decode_mode=VP_DECODE_SEG_MASK, gpu_id=0):
     """createMaskFromTensorHIP twin (vp_decode_logits_host): host CxHxW fp32 logits -> HxW u8 mask."""
@@ -753,6 +776,31 @@ def op_absmax(hi, lo, c, gpu_id=0):
     if rc != 0:
         raise (ValueError if rc == -1 else VpError)(f"vp_op_absmax failed ({rc}): {err.value.decode(errors='replace')}")
     return np.float32(amax.value), int(bad.value)
+
+
+def op_exp_hist(hi, lo, c, gpu_id=0):
+    """vp_op_exp_hist: hi / lo float16 planes [h][w][c_pitch] (lo may be None) -> (bins int64 [VP_RANGE_BINS], zeros, count) over channels [0, c)."""
+    hi = np.ascontiguousarray(hi, dtype=np.float16)
+    lo = None if lo is None else np.ascontiguousarray(lo, dtype=np.float16)
+    h, w, pitch = hi.shape
+    bins = np.zeros(VP_RANGE_BINS, dtype=np.uint64)
+    zeros, count = C.c_ulonglong(), C.c_ulonglong()
+    err = C.create_string_buffer(512)
+    rc = load().vp_op_exp_hist(gpu_id, _ptr(hi), None if lo is None else _ptr(lo), int(c), h, w, pitch, _ptr(bins), C.byref(zeros), C.byref(count), err, len(err))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_op_exp_hist failed ({rc}): {err.value.decode(errors='replace')}")
+    return bins.astype(np.int64), int(zeros.value), int(count.value)
+
+
+def range_summary(rec):
+    """What a range_survey() record says about the fp16 exponent range: `headroom` = 15 - floor(log2 absmax), the binades left below the top one (None for
+    an all-zero tensor), `below_lo_normal` = share of the non-zero finite values below 0.125 = 2^-3, where the quantum of the LOW plane (2^-11 of the
+    value) is an fp16 subnormal (meaningful for two-plane engines), `below_hi_normal` = share below 2^-14, where the high plane itself is subnormal."""
+    bins = np.asarray(rec["bins"], dtype=np.int64)
+    nz = int(bins.sum())
+    amax = float(rec["absmax"])
+    share = lambda e: (float(bins[: e - VP_RANGE_EXP_MIN].sum()) / nz) if nz else 0.0
+    return {"headroom": None if not amax > 0.0 else 15 - int(np.frexp(np.float32(amax))[1] - 1), "below_lo_normal": share(-3), "below_hi_normal": share(-14)}
 
 
 def op_conv2d_scaled(x, weight, bias, ks=3, act=0, res=None, res_mode=0, in_exp=0, res_exp=0, out_exp=0, precision=VP_FP16X3, tile=-1, bk=-1, nsplit=-1, gpu_id=0):

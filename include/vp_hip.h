@@ -238,6 +238,29 @@ int vp_calibrate_range(vp_engine* e, int target_log2);
 int vp_reset_range(vp_engine* e);
 int vp_act_scales(const vp_engine* e, int* exps, int cap);   /* returns the tensor count */
 int vp_set_act_scales(vp_engine* e, const int* exps, int n);
+/* RANGE SURVEY (any engine that owns its whole network: all seven kinds, VP_FP16 and VP_FP16X3, with or without VP_WEIGHTS_FP8 / VP_PLAN_LATENCY /
+ * VP_ACT_SCALE).  vp_range_survey runs the plan eagerly, launch by launch, over the RESIDENT input -- the frame of the last vp_upload_frame / vp_infer,
+ * the tensor of the last vp_infer_tensor / vp_detect_infer; AutoDrive: the pair vp_calibrate_range would run (an engine without VP_ACT_SCALE keeps no
+ * previous frame: the resident frame is both halves) -- and, right behind the last launch that writes it, measures every tensor the plan stores in
+ * HBM: abs-max and non-finite count of the stored value x = (float)hi + (float)lo (what vp_tensor_read returns; on a VP_ACT_SCALE engine
+ * vp_tensor_read's value times 2^-exp), and a histogram of floor(log2 |x|) over the fp16 exponent range, 2^-24 (the smallest fp16 magnitude) up to
+ * the top binade 2^15.  Exact zeros are counted apart, non-finite elements in neither; pad channels are not visited: count == c * h * w and
+ * sum(bins) + zeros + nonfinite == count.  All counters are integer sums: two surveys of one input give equal words.
+ *   out[i], i < min(cap, tensor count), belongs to tensor i of vp_tensor_info; tensors the plan never stores (views that only name a slice) keep
+ *   count == 0 (exp is filled in for them too).  Returns the tensor count.  VP_ERR_ARG for a shared-prefix head or a batched encoder, VP_ERR_STATE when nothing is resident.  Never
+ *   VP_ERR_RANGE: non-finite values are what it reports -- the first tensor in plan order with nonfinite > 0 is where a frame left the range.
+ *   The engine is left as a plain pass over the same input leaves it (outputs on the device, fetched by vp_logits / vp_mask_u8 on use); no launch,
+ *   exponent or graph changes, the next vp_infer replays the graph it replayed before.
+ *   NOT seen: values that only live on chip -- the expanded tensor inside the fused MBConv kernels, the up-sampled tensor of a composed stage. */
+#define VP_RANGE_BINS 40
+#define VP_RANGE_EXP_MIN (-24)
+typedef struct vp_range_stats {
+  float absmax;                 /* of the stored value hi + lo, non-finite elements left out */
+  int exp;                      /* VP_ACT_SCALE exponent of the tensor (true value = stored * 2^exp); 0 otherwise */
+  unsigned long long count, nonfinite, zeros;
+  unsigned long long bins[VP_RANGE_BINS];   /* bins[k]: floor(log2 |x|) == VP_RANGE_EXP_MIN + k */
+} vp_range_stats;
+int vp_range_survey(vp_engine* e, vp_range_stats* out, int cap);
 /* RANGE GUARD.  Both precision modes compute on fp16 planes: VP_FP16X3 has fp32-class SIGNIFICAND (hi + lo) but fp16 EXPONENT range.
  *   - at load: a BN-folded weight with |w| > 65504 (or non-finite) fails vp_create* with VP_ERR_RANGE instead of loading as inf;
  *   - per frame: an activation beyond 65504 becomes inf and reaches the logits as inf / NaN; a probe kernel over the logits at the end
@@ -449,6 +472,10 @@ int vp_op_absmax(int gpu_id, const uint16_t* hi, const uint16_t* lo, int c, int 
 int vp_op_conv2d_scaled(int gpu_id, int precision, int mode, const float* in, int cin, int h, int w, const float* weight, const float* bias, int cout,
                         int ks, int act, int res_mode, const float* res, int tile, int bk, int nsplit, int in_exp, int res_exp, int out_exp,
                         uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len);
+/* vp_op_exp_hist: act_exp_hist_kernel (the range survey's histogram) on planes laid out as for vp_op_absmax: bins[VP_RANGE_BINS], *zeros and *count as
+ *   in vp_range_stats.  A finite |hi + lo| of 2^16 or more (no pair an engine stores) is counted in the top bin. */
+int vp_op_exp_hist(int gpu_id, const uint16_t* hi, const uint16_t* lo, int c, int h, int w, int c_pitch, unsigned long long* bins,
+                   unsigned long long* zeros, unsigned long long* count, char* err, size_t err_len);
 /* ---- single-operator entries of the AutoSteer head's kernels (unit tests; not used by callers) ------------
  * vp_op_rowpair_conv: Conv2d(cin -> 32, kernel (2,1), stride (2,1)) + bias + SiLU: in [cin][h][w], weight [32][cin][2][1], bias [32].  The result,
  *   (h / 2) x w -- with replicate every pixel stored 2 x 2: h' x 2w, h' = 2 (h / 2) -- lands in channels [dst_off, dst_off + 32) of a destination of dst_c channels
