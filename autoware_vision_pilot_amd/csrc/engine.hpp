@@ -100,6 +100,16 @@ int register_frame_range(const void* pool, size_t bytes);
 int unregister_frame_range(const void* pool);
 bool frame_range_registered(const void* p, size_t bytes);
 
+// What a consumer sees of a device-resident camera frame (vp_frame, vp_handle.hpp): packed BGR8 rows `pitch` bytes apart on GPU `gpu`, complete on the
+// device once `ready` has fired.  bgr == nullptr: nothing was uploaded yet.
+struct FrameView {
+  const uint8_t* bgr = nullptr;
+  int h = 0, w = 0, pitch = 0, gpu = 0;
+  hipEvent_t ready = nullptr;
+};
+// the region (x0, y0, w, h) of a frame as a consumer takes it (w == h == 0: the whole frame); throws std::invalid_argument / std::runtime_error
+void resolve_frame_region(const FrameView& f, int x0, int y0, int* w, int* h);
+
 struct ConvChoice;   // engine_internal.hpp: what the dispatch rules of engine_dispatch.cpp give one convolution
 struct HostWeights;  // engine_internal.hpp: a layer's packed weights on the host
 
@@ -146,6 +156,10 @@ class Engine {
 
   // frame path
   void upload_frame(const uint8_t* frame, int h, int w, int stride, int index = 0);  // index: slot of a batched encoder
+  // the asynchronous twin for a device-resident camera frame (vp_frame): this engine's stream waits for the frame's content, then copies the region
+  // (x0, y0, w, h; w == h == 0: the whole frame) device to device into the engine's own frame buffer, rows packed.  The caller records the "consumer
+  // done" event behind it (vp_api.cpp).
+  void upload_from_frame(const FrameView& f, int x0, int y0, int w, int h);
   int frames() const { return frames_; }
   void upload_tensor(const float* nchw);
   void enqueue();
@@ -323,6 +337,11 @@ class Engine {
   void build_head(const WeightBlob& blob, const std::string& p, const Act* neck, const std::vector<Act*>& feats);
   void finish_plan();
   void ensure_tables(int h, int w);
+  // the two halves of a frame upload: "accept this geometry" (refusals, buffer, tap tables, graph invalidation; returns where the bytes go) and, behind
+  // the copy each path queues itself, "a frame is the input now"
+  void refuse_frame_input() const;
+  uint8_t* accept_frame_geometry(bool have_bytes, int h, int w, int stride, int index);
+  void note_frame_input();
   void capture_graph();
 
   Act* frame_view(const Act* a, int f);  // per-frame window of a stacked activation (no allocation)

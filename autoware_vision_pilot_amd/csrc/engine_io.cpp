@@ -235,10 +235,16 @@ bool frame_range_registered(const void* p, size_t bytes) {
   return false;
 }
 
-void Engine::upload_frame(const uint8_t* frame, int h, int w, int stride, int index) {
+void Engine::refuse_frame_input() const {
   if (base_) throw std::invalid_argument("shared engine: frames go to the base engine (vp_infer on the base, then vp_infer_shared)");
   if (kind_ == 5) throw std::runtime_error("VP_AUTOSPEED engines have no frame preprocess of their own: attach the engine to a detector (vp_detect_attach) and call vp_detect_infer, or hand the letterboxed tensor to vp_infer_tensor");
-  if (!frame || h < 2 || w < 2 || stride < 3 * w) throw std::invalid_argument("bad frame geometry");
+}
+
+// First half of every frame upload (host bytes: upload_frame; a device-resident vp_frame: upload_from_frame): the refusals, the frame buffer, the tap
+// tables and the graph invalidation a new geometry brings.  Returns where slot `index`'s bytes go.
+uint8_t* Engine::accept_frame_geometry(bool have_bytes, int h, int w, int stride, int index) {
+  refuse_frame_input();
+  if (!have_bytes || h < 2 || w < 2 || stride < 3 * w) throw std::invalid_argument("bad frame geometry");
   if (kind_ == 6 && (h != net_h() || w != net_w()))   // auto_steer_infer.py:37-39 raises ValueError: this network has no resize in front of it
     throw std::invalid_argument("VP_AUTOSTEER: the input frame must be 512 x 1024 (height x width), got " + std::to_string(h) + " x " + std::to_string(w));
   if (index < 0 || index >= frames_) throw std::invalid_argument("frame index out of range");
@@ -260,11 +266,44 @@ void Engine::upload_frame(const uint8_t* frame, int h, int w, int stride, int in
   frame_h_ = h;
   frame_w_ = w;
   frame_stride_ = stride;
+  return d_frame_ + (size_t)index * need;
+}
+
+void Engine::note_frame_input() {
+  if (input_is_tensor_) { graph_valid_ = false; ++plan_epoch_; }
+  input_is_tensor_ = false;
+}
+
+void resolve_frame_region(const FrameView& f, int x0, int y0, int* w, int* h) {
+  if (!f.bgr) throw std::runtime_error("the frame was never uploaded (vp_frame_upload / vp_frame_upload_device first)");
+  if (*w == 0 && *h == 0 && x0 == 0 && y0 == 0) {
+    *w = f.w;
+    *h = f.h;
+  }
+  if (x0 < 0 || y0 < 0 || *w < 2 || *h < 2 || (long long)x0 + *w > f.w || (long long)y0 + *h > f.h)
+    throw std::invalid_argument("frame region (x0 " + std::to_string(x0) + ", y0 " + std::to_string(y0) + ", " + std::to_string(*w) + " x " + std::to_string(*h) +
+                                ") must be at least 2 x 2 and lie inside the " + std::to_string(f.w) + " x " + std::to_string(f.h) + " frame");
+}
+
+void Engine::upload_from_frame(const FrameView& f, int x0, int y0, int w, int h) {
+  refuse_frame_input();
+  if (frames_ > 1) throw std::invalid_argument("batched encoder: frames from a vp_frame are not supported (vp_upload_frame_n takes host frames)");
+  if (pixel_format_ != 0) throw std::invalid_argument("vp_frame holds BGR8: the engine's input pixel format must be VP_BGR8 (vp_set_input_format)");
+  if (f.gpu != gpu_) throw std::invalid_argument("the frame lives on GPU " + std::to_string(f.gpu) + ", the engine on GPU " + std::to_string(gpu_));
+  resolve_frame_region(f, x0, y0, &w, &h);
+  uint8_t* dst = accept_frame_geometry(true, h, w, 3 * w, 0);
+  VP_HIP_CHECK(hipStreamWaitEvent(stream_, f.ready, 0));   // never a host wait: the copy runs once the frame's content is complete
+  VP_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)3 * w, f.bgr + (size_t)y0 * f.pitch + (size_t)3 * x0, f.pitch, (size_t)3 * w, h, hipMemcpyDeviceToDevice, stream_));
+  note_frame_input();
+}
+
+void Engine::upload_frame(const uint8_t* frame, int h, int w, int stride, int index) {
+  uint8_t* dst = accept_frame_geometry(frame != nullptr, h, w, stride, index);
+  const size_t need = (size_t)h * stride;
   // A strided view (cv::Mat ROI, numpy slice) guarantees only (h-1)*stride + 3*w readable bytes: the tail of the last row
   // belongs to the parent image or to nobody.  Packed frames go as one copy, views row by row (hipMemcpy2D).
   // The caller's buffer is pageable (cv::Mat); the copy is staged through this engine's pinned buffer so the transfer
   // itself is one DMA that overlaps other engines' kernels (the reference does the same H2D: tensorrt_backend.cpp:184-186).
-  uint8_t* dst = d_frame_ + (size_t)index * need;
   const size_t packed = (size_t)(h - 1) * stride + (size_t)3 * w;
   // a frame inside a pool the host registered (vp_register_frames) is page-locked already: one DMA straight from the caller's memory
   const bool staged = pinned_staging_ && !frame_range_registered(frame, packed);
@@ -294,8 +333,7 @@ void Engine::upload_frame(const uint8_t* frame, int h, int w, int stride, int in
   } else {
     VP_HIP_CHECK(hipMemcpy2DAsync(dst, stride, frame, stride, (size_t)3 * w, h, hipMemcpyHostToDevice, stream_));
   }
-  if (input_is_tensor_) { graph_valid_ = false; ++plan_epoch_; }
-  input_is_tensor_ = false;
+  note_frame_input();
 }
 
 void Engine::upload_tensor(const float* nchw) {

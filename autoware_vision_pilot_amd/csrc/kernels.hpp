@@ -41,6 +41,23 @@ struct PilResampleParams {
   int norm_form;         // as PreprocessParams
 };
 
+// vp_frame (include/vp_hip.h): a camera frame in its native format -> packed BGR8 on the device, once, behind the upload.  kernels_misc.hip
+// frame_to_bgr8_kernel.  format: the vp_frame_format code.  p0 / s0: the single plane (NV12: the Y plane) and its row stride in bytes; p1 / s1: NV12's
+// interleaved UV plane.  dst rows are dst_pitch = 12 * ceil(w / 4) bytes apart (== 3 * w when w is a multiple of 4): one work-item stores the three
+// words of four pixels, bytes behind the last pixel of a row are written as 0.
+constexpr int kFrameFormats = 8;   // BGR8, RGB8, BGRA8, RGBA8, GRAY8, NV12, YUY2, UYVY
+inline int frame_bgr_pitch(int w) { return 12 * ((w + 3) / 4); }
+struct FrameToBgrParams {
+  const uint8_t* p0;
+  const uint8_t* p1;
+  int s0, s1;
+  int h, w;
+  int format;
+  uint8_t* dst;
+  int dst_pitch;
+};
+hipError_t launch_frame_to_bgr8(const FrameToBgrParams& p, hipStream_t st);
+
 struct StemParams {
   const float* in;  // [3][H][W]
   int H, W;         // input size (output is H/2 x W/2)

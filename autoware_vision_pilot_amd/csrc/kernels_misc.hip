@@ -36,6 +36,86 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreprocessParams 
   }
 }
 
+// ------------------------------------------------------------------------------------------ vp_frame: native camera formats -> BGR8
+// One work-item produces four pixels of a row (NV12: of two rows, i.e. two whole 2x2 chroma groups; YUY2 / UYVY: two 2x1 groups), so every chroma
+// sample is read once, and stores them as three aligned 32-bit words per row (kernels.hpp FrameToBgrParams: rows are 12 * ceil(w / 4) bytes apart).
+// Pixels beyond the row's end are written as zero bytes.  Source planes are read byte by byte: a decoder surface or a caller's view promises no alignment.
+// The YUV formats use the integer BT.601 limited-range form documented for OpenCV's cvtColor(COLOR_YUV2BGR_NV12 / _YUY2 / _UYVY) -- 20 fractional
+// bits, no chroma interpolation -- which include/vp_hip.h states as the DEFINITION (parity with OpenCV itself is not pinned):
+//   y = 1220542 * max(0, Y - 16), u = U - 128, v = V - 128
+//   R = sat8((y + 1673527 v + 2^19) >> 20), G = sat8((y - 852492 v - 409993 u + 2^19) >> 20), B = sat8((y + 2116026 u + 2^19) >> 20)
+struct ChromaTerms {
+  int r, g, b;   // the chroma part of each channel, rounding constant included
+};
+__device__ __forceinline__ ChromaTerms chroma_terms(int U, int V) {
+  const int u = U - 128, v = V - 128;
+  return {1673527 * v + (1 << 19), -852492 * v - 409993 * u + (1 << 19), 2116026 * u + (1 << 19)};
+}
+__device__ __forceinline__ unsigned sat8(int x) { return (unsigned)min(max(x, 0), 255); }
+// one pixel as b | g << 8 | r << 16
+__device__ __forceinline__ unsigned yuv_pixel(int Y, const ChromaTerms& c) {
+  const int y = 1220542 * max(0, Y - 16);
+  return sat8((y + c.b) >> 20) | (sat8((y + c.g) >> 20) << 8) | (sat8((y + c.r) >> 20) << 16);
+}
+__device__ __forceinline__ void store_bgr4(uint8_t* row, int j, const unsigned px[4]) {
+  uint32_t* d = reinterpret_cast<uint32_t*>(row + 12 * (size_t)j);
+  d[0] = px[0] | (px[1] << 24);
+  d[1] = (px[1] >> 8) | (px[2] << 16);
+  d[2] = (px[2] >> 16) | (px[3] << 8);
+}
+__global__ __launch_bounds__(256) void frame_to_bgr8_kernel(const FrameToBgrParams p) {
+  const int bpr = (p.w + 3) >> 2;                          // four-pixel blocks per row
+  const int rows = p.format == 5 ? p.h >> 1 : p.h;         // NV12: row pairs
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)rows * bpr) return;
+  const int r = (int)(t / bpr), j = (int)(t - (long long)r * bpr), x0 = 4 * j;
+  unsigned px[4] = {0u, 0u, 0u, 0u};
+  if (p.format == 5) {   // NV12: Y rows 2r, 2r + 1; one (U, V) per 2x2 block
+    const uint8_t* y0 = p.p0 + (size_t)(2 * r) * p.s0 + x0;
+    const uint8_t* y1 = y0 + p.s0;
+    const uint8_t* uv = p.p1 + (size_t)r * p.s1 + x0;
+    unsigned px1[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      if (x0 + 2 * g >= p.w) break;                        // w is even: a group is whole or absent
+      const ChromaTerms c = chroma_terms(uv[2 * g], uv[2 * g + 1]);
+      px[2 * g] = yuv_pixel(y0[2 * g], c);
+      px[2 * g + 1] = yuv_pixel(y0[2 * g + 1], c);
+      px1[2 * g] = yuv_pixel(y1[2 * g], c);
+      px1[2 * g + 1] = yuv_pixel(y1[2 * g + 1], c);
+    }
+    store_bgr4(p.dst + (size_t)(2 * r) * p.dst_pitch, j, px);
+    store_bgr4(p.dst + (size_t)(2 * r + 1) * p.dst_pitch, j, px1);
+    return;
+  }
+  const uint8_t* row = p.p0 + (size_t)r * p.s0;
+  if (p.format >= 6) {   // YUY2: Y0 U Y1 V; UYVY: U Y0 V Y1 -- one (U, V) per horizontal pixel pair
+    const int yo = p.format == 6 ? 0 : 1, co = 1 - yo;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      if (x0 + 2 * g >= p.w) break;
+      const uint8_t* s = row + 2 * (size_t)(x0 + 2 * g);
+      const ChromaTerms c = chroma_terms(s[co], s[co + 2]);
+      px[2 * g] = yuv_pixel(s[yo], c);
+      px[2 * g + 1] = yuv_pixel(s[yo + 2], c);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int x = x0 + i;
+      if (x >= p.w) break;
+      if (p.format == 4) {          // GRAY8 replicated
+        px[i] = 0x010101u * row[x];
+      } else {
+        const uint8_t* s = row + (size_t)x * (p.format <= 1 ? 3 : 4);
+        const bool rgb = p.format == 1 || p.format == 3;   // RGB8 / RGBA8: R first; BGR8 / BGRA8: B first; alpha dropped
+        px[i] = (unsigned)s[rgb ? 2 : 0] | ((unsigned)s[1] << 8) | ((unsigned)s[rgb ? 0 : 2] << 16);
+      }
+    }
+  }
+  store_bgr4(p.dst + (size_t)r * p.dst_pitch, j, px);
+}
+
 // Pillow's 8-bit resample passes (kernels.hpp PilResampleParams): int32 accumulation from 1 << 21 of u8 x 22-bit coefficients,
 // `>> 22`, clip to u8 (Resample.c clip8) -- integer work, bit-exact by construction.
 __device__ __forceinline__ int pil_clip8(int acc) { return min(max(acc >> 22, 0), 255); }
@@ -545,6 +625,14 @@ __global__ __launch_bounds__(256) void act_exp_hist_kernel(const half_t* hi, con
 // ---------------------------------------------------------------------------------------------- launchers
 hipError_t launch_preprocess(const PreprocessParams& p, hipStream_t st) {
   VP_LAUNCH(preprocess_kernel, dim3(nblk(p.out_w), p.out_h), dim3(256), 0, st, p);
+}
+hipError_t launch_frame_to_bgr8(const FrameToBgrParams& p, hipStream_t st) {
+  const bool pairs = p.format >= 5;   // 4:2:x: whole chroma groups only
+  if (!p.p0 || !p.dst || p.format < 0 || p.format >= kFrameFormats || p.h < 2 || p.w < 2 || (pairs && (p.w & 1)) || (p.format == 5 && (!p.p1 || (p.h & 1))) ||
+      p.dst_pitch < frame_bgr_pitch(p.w) || (p.dst_pitch & 3) || (reinterpret_cast<uintptr_t>(p.dst) & 3))
+    return hipErrorInvalidValue;
+  const long long n = (long long)(p.format == 5 ? p.h / 2 : p.h) * ((p.w + 3) / 4);
+  VP_LAUNCH(frame_to_bgr8_kernel, dim3(nblk(n)), dim3(256), 0, st, p);
 }
 hipError_t launch_pil_resample(const PilResampleParams& p, hipStream_t st) {
   hipLaunchKernelGGL(pil_resample_h_kernel, dim3(nblk(p.out_w), p.in_h), dim3(256), 0, st, p);

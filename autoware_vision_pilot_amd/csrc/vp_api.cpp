@@ -471,6 +471,289 @@ int vp_upload_frame(vp_engine* e, const uint8_t* frame, int h, int w, int stride
 int vp_enqueue(vp_engine* e) {
   return guarded(e, [&](vp::Engine& g) { g.enqueue(); });
 }
+
+// ---- vp_frame: a device-resident camera frame (include/vp_hip.h; handle: vp_handle.hpp; kernel: kernels_misc.hip frame_to_bgr8_kernel)
+}  // extern "C"
+
+vp_frame::~vp_frame() {
+  (void)hipSetDevice(gpu);
+  if (stream) (void)hipStreamSynchronize(stream);
+  for (Consumer& c : consumers) {
+    (void)hipEventSynchronize(c.done);   // a consumer's copy may still read the image
+    (void)hipEventDestroy(c.done);
+  }
+  for (hipEvent_t ev : {stage_ev[0], stage_ev[1], ready, producer})
+    if (ev) (void)hipEventDestroy(ev);
+  if (d_bgr) (void)hipFree(d_bgr);
+  if (d_src) (void)hipFree(d_src);
+  if (h_stage) (void)hipHostFree(h_stage);
+  if (stream) (void)hipStreamDestroy(stream);
+}
+
+vp::FrameView vp_frame::view() const {
+  vp::FrameView v;
+  v.bgr = uploaded ? d_bgr : nullptr;
+  v.h = h;
+  v.w = w;
+  v.pitch = pitch;
+  v.gpu = gpu;
+  v.ready = ready;
+  return v;
+}
+
+void vp_frame::note_consumer(hipStream_t s) {
+  std::lock_guard<std::mutex> lk(mu);
+  Consumer* c = nullptr;
+  for (Consumer& k : consumers)
+    if (k.stream == s) c = &k;
+  if (!c) {
+    hipEvent_t ev = nullptr;
+    VP_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    consumers.push_back({s, ev, false});
+    c = &consumers.back();
+  }
+  VP_HIP_CHECK(hipEventRecord(c->done, s));
+  c->pending = true;
+}
+
+void vp_frame::wait_for_consumers() {
+  std::lock_guard<std::mutex> lk(mu);
+  for (Consumer& c : consumers)
+    if (c.pending) {
+      VP_HIP_CHECK(hipStreamWaitEvent(stream, c.done, 0));
+      c.pending = false;
+    }
+}
+
+namespace {
+
+template <class F>
+int frame_guarded(vp_frame* f, F&& fn) {
+  if (!f) return VP_ERR_ARG;
+  try {
+    VP_HIP_CHECK(hipSetDevice(f->gpu));
+    fn();
+    return VP_OK;
+  } catch (const std::invalid_argument& ex) {
+    f->err = ex.what();
+    return VP_ERR_ARG;
+  } catch (const std::exception& ex) {
+    f->err = ex.what();
+    return std::strncmp(ex.what(), "HIP error", 9) == 0 ? VP_ERR_HIP : VP_ERR_STATE;
+  }
+}
+
+struct FramePlanes {
+  int n = 1;
+  size_t row_bytes[2] = {0, 0};
+  int rows[2] = {0, 0};
+};
+
+// the refusals of vp_frame_upload*, and the planes the format has
+FramePlanes check_frame_planes(const char* who, int format, const void* const* planes, const int* strides, int n_planes, int h, int w) {
+  static const char* const names[vp::kFrameFormats] = {"BGR8", "RGB8", "BGRA8", "RGBA8", "GRAY8", "NV12", "YUY2", "UYVY"};
+  static const int px_bytes[vp::kFrameFormats] = {3, 3, 4, 4, 1, 1, 2, 2};
+  const std::string me(who);
+  if (format < 0 || format >= vp::kFrameFormats) throw std::invalid_argument(me + ": unknown format " + std::to_string(format));
+  const std::string fmt = names[format];
+  FramePlanes fp;
+  fp.n = format == VP_FRAME_NV12 ? 2 : 1;
+  if (n_planes != fp.n) throw std::invalid_argument(me + ": " + fmt + " has " + std::to_string(fp.n) + " plane(s), got n_planes = " + std::to_string(n_planes));
+  if (!planes || !strides) throw std::invalid_argument(me + ": null planes / strides");
+  if (h < 2 || w < 2 || h > 16384 || w > 16384) throw std::invalid_argument(me + ": frame size " + std::to_string(w) + " x " + std::to_string(h) + " (2 .. 16384 each way)");
+  if (format >= VP_FRAME_NV12 && (w & 1)) throw std::invalid_argument(me + ": " + fmt + " needs an even width (one chroma pair per two pixels), got " + std::to_string(w));
+  if (format == VP_FRAME_NV12 && (h & 1)) throw std::invalid_argument(me + ": NV12 needs an even height (one chroma pair per 2x2 block), got " + std::to_string(h));
+  fp.row_bytes[0] = (size_t)px_bytes[format] * w;
+  fp.rows[0] = h;
+  if (fp.n == 2) {
+    fp.row_bytes[1] = (size_t)w;   // w / 2 interleaved (U, V) pairs
+    fp.rows[1] = h / 2;
+  }
+  for (int i = 0; i < fp.n; ++i) {
+    if (!planes[i]) throw std::invalid_argument(me + ": plane " + std::to_string(i) + " is null");
+    if (strides[i] < 0 || (size_t)strides[i] < fp.row_bytes[i])
+      throw std::invalid_argument(me + ": stride " + std::to_string(strides[i]) + " of plane " + std::to_string(i) + " is below the row's " + std::to_string(fp.row_bytes[i]) + " bytes");
+  }
+  return fp;
+}
+
+template <class T>
+void grow(T*& p, size_t& cap, size_t need, bool pinned) {
+  if (need <= cap) return;
+  if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+  p = nullptr;
+  cap = 0;
+  const size_t n = (need + 255) & ~(size_t)255;
+  VP_HIP_CHECK(pinned ? hipHostMalloc(reinterpret_cast<void**>(&p), n, hipHostMallocDefault) : hipMalloc(reinterpret_cast<void**>(&p), n));
+  cap = n;
+}
+
+// ahead of every upload: the image is about to be overwritten, so the frame's stream falls in behind every consumer copy queued so far; a buffer that
+// has to grow is freed only once those copies and the frame's own work have run (the one host wait of this path, once per geometry)
+void begin_upload(vp_frame* f, int h, int w, size_t src_bytes, size_t stage_bytes) {
+  f->wait_for_consumers();
+  const int pitch = vp::frame_bgr_pitch(w);
+  if ((size_t)h * pitch > f->bgr_cap || src_bytes > f->src_cap || stage_bytes > f->stage_cap) {
+    VP_HIP_CHECK(hipStreamSynchronize(f->stream));
+    grow(f->d_bgr, f->bgr_cap, (size_t)h * pitch, false);
+    grow(f->d_src, f->src_cap, src_bytes, false);
+    if (stage_bytes > f->stage_cap) {
+      if (f->h_stage) (void)hipHostFree(f->h_stage);
+      f->h_stage = nullptr;
+      f->stage_cap = 0;
+      const size_t n = (stage_bytes + 255) & ~(size_t)255;
+      VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&f->h_stage), 2 * n, hipHostMallocDefault));   // two slots: frame n + 1 is staged while n flies
+      f->stage_cap = n;
+    }
+  }
+}
+
+void end_upload(vp_frame* f, int h, int w) {
+  VP_HIP_CHECK(hipEventRecord(f->ready, f->stream));
+  f->h = h;
+  f->w = w;
+  f->pitch = vp::frame_bgr_pitch(w);
+  f->uploaded = true;
+}
+
+void convert_planes(vp_frame* f, int format, const uint8_t* p0, int s0, const uint8_t* p1, int s1, int h, int w) {
+  vp::FrameToBgrParams q{};
+  q.p0 = p0;
+  q.p1 = p1;
+  q.s0 = s0;
+  q.s1 = s1;
+  q.h = h;
+  q.w = w;
+  q.format = format;
+  q.dst = f->d_bgr;
+  q.dst_pitch = vp::frame_bgr_pitch(w);
+  VP_HIP_CHECK(vp::launch_frame_to_bgr8(q, f->stream));
+}
+
+}  // namespace
+
+extern "C" {
+
+int vp_frame_create(vp_frame** out, int gpu_id, char* err, size_t err_len) {
+  if (!out) return VP_ERR_ARG;
+  *out = nullptr;
+  try {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) throw std::runtime_error("HIP error: no HIP device visible: a vp_frame lives on the device");
+    if (gpu_id < 0 || gpu_id >= n) throw std::invalid_argument("gpu_id out of range");
+    auto f = std::make_unique<vp_frame>();
+    f->gpu = gpu_id;
+    VP_HIP_CHECK(hipSetDevice(gpu_id));
+    VP_HIP_CHECK(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    VP_HIP_CHECK(hipEventCreateWithFlags(&f->ready, hipEventDisableTiming));
+    VP_HIP_CHECK(hipEventCreateWithFlags(&f->producer, hipEventDisableTiming));
+    for (hipEvent_t& ev : f->stage_ev) VP_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    *out = f.release();
+    return VP_OK;
+  } catch (const std::invalid_argument& ex) {
+    set_err(err, err_len, ex.what());
+    return VP_ERR_ARG;
+  } catch (const std::exception& ex) {
+    set_err(err, err_len, ex.what());
+    return VP_ERR_HIP;
+  }
+}
+
+void vp_frame_destroy(vp_frame* f) { delete f; }
+
+const char* vp_frame_last_error(const vp_frame* f) { return f ? f->err.c_str() : "null frame"; }
+
+int vp_frame_upload(vp_frame* f, int format, const uint8_t* const* planes, const int* strides, int n_planes, int h, int w) {
+  return frame_guarded(f, [&] {
+    const FramePlanes fp = check_frame_planes("vp_frame_upload", format, reinterpret_cast<const void* const*>(planes), strides, n_planes, h, w);
+    size_t total = 0;
+    bool registered = true;   // every plane inside a vp_register_frames range: one DMA per plane straight from the caller's memory
+    for (int i = 0; i < fp.n; ++i) {
+      total += fp.row_bytes[i] * fp.rows[i];
+      registered = registered && vp::frame_range_registered(planes[i], (size_t)(fp.rows[i] - 1) * strides[i] + fp.row_bytes[i]);
+    }
+    const bool bgr = format == VP_FRAME_BGR8;
+    begin_upload(f, h, w, bgr ? 0 : total, registered ? 0 : total);
+    const int pitch = vp::frame_bgr_pitch(w);
+    if (registered) {
+      size_t off = 0;
+      for (int i = 0; i < fp.n; ++i) {
+        uint8_t* dst = bgr ? f->d_bgr : f->d_src + off;
+        VP_HIP_CHECK(hipMemcpy2DAsync(dst, bgr ? (size_t)pitch : fp.row_bytes[i], planes[i], strides[i], fp.row_bytes[i], fp.rows[i], hipMemcpyHostToDevice, f->stream));
+        off += fp.row_bytes[i] * fp.rows[i];
+      }
+    } else {
+      f->stage_slot ^= 1;
+      uint8_t* slot = f->h_stage + (size_t)f->stage_slot * f->stage_cap;
+      // the H2D that last read this slot (two uploads ago) may still be queued: its event orders this host write behind it
+      VP_HIP_CHECK(hipEventSynchronize(f->stage_ev[f->stage_slot]));
+      uint8_t* o = slot;
+      for (int i = 0; i < fp.n; ++i)
+        for (int y = 0; y < fp.rows[i]; ++y, o += fp.row_bytes[i]) std::memcpy(o, planes[i] + (size_t)y * strides[i], fp.row_bytes[i]);
+      if (bgr) VP_HIP_CHECK(hipMemcpy2DAsync(f->d_bgr, pitch, slot, fp.row_bytes[0], fp.row_bytes[0], h, hipMemcpyHostToDevice, f->stream));
+      else VP_HIP_CHECK(hipMemcpyAsync(f->d_src, slot, total, hipMemcpyHostToDevice, f->stream));
+      VP_HIP_CHECK(hipEventRecord(f->stage_ev[f->stage_slot], f->stream));
+    }
+    if (!bgr) convert_planes(f, format, f->d_src, (int)fp.row_bytes[0], fp.n == 2 ? f->d_src + fp.row_bytes[0] * fp.rows[0] : nullptr, (int)fp.row_bytes[1], h, w);
+    end_upload(f, h, w);
+  });
+}
+
+int vp_frame_upload_device(vp_frame* f, int format, const void* const* dev_planes, const int* strides, int n_planes, int h, int w, void* producer_stream) {
+  return frame_guarded(f, [&] {
+    const FramePlanes fp = check_frame_planes("vp_frame_upload_device", format, dev_planes, strides, n_planes, h, w);
+    begin_upload(f, h, w, 0, 0);
+    if (producer_stream) {   // the planes are complete once the work queued on the producer's stream so far has run
+      VP_HIP_CHECK(hipEventRecord(f->producer, static_cast<hipStream_t>(producer_stream)));
+      VP_HIP_CHECK(hipStreamWaitEvent(f->stream, f->producer, 0));
+    }
+    if (format == VP_FRAME_BGR8)
+      VP_HIP_CHECK(hipMemcpy2DAsync(f->d_bgr, vp::frame_bgr_pitch(w), dev_planes[0], strides[0], fp.row_bytes[0], h, hipMemcpyDeviceToDevice, f->stream));
+    else
+      convert_planes(f, format, static_cast<const uint8_t*>(dev_planes[0]), strides[0], fp.n == 2 ? static_cast<const uint8_t*>(dev_planes[1]) : nullptr,
+                     fp.n == 2 ? strides[1] : 0, h, w);
+    end_upload(f, h, w);
+  });
+}
+
+int vp_frame_sync(vp_frame* f) {
+  return frame_guarded(f, [&] { VP_HIP_CHECK(hipStreamSynchronize(f->stream)); });
+}
+
+int vp_frame_dims(const vp_frame* f, int* h, int* w) {
+  if (!f || !h || !w) return VP_ERR_ARG;
+  if (!f->uploaded) return VP_ERR_STATE;
+  *h = f->h;
+  *w = f->w;
+  return VP_OK;
+}
+
+int vp_frame_fetch_bgr8(vp_frame* f, uint8_t* dst, int dst_stride) {
+  return frame_guarded(f, [&] {
+    if (!f->uploaded) throw std::runtime_error("the frame was never uploaded (vp_frame_upload / vp_frame_upload_device first)");
+    if (!dst || dst_stride < 3 * f->w) throw std::invalid_argument("vp_frame_fetch_bgr8: null destination or a stride below 3 * width");
+    VP_HIP_CHECK(hipMemcpy2DAsync(dst, dst_stride, f->d_bgr, f->pitch, (size_t)3 * f->w, f->h, hipMemcpyDeviceToHost, f->stream));
+    VP_HIP_CHECK(hipStreamSynchronize(f->stream));
+  });
+}
+
+int vp_upload_from_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h) {
+  return guarded(e, [&](vp::Engine& g) {
+    if (!f) throw std::invalid_argument("null frame");
+    g.upload_from_frame(f->view(), x0, y0, w, h);
+    f->note_consumer(g.stream());   // the next upload into the frame waits for this copy, on the device
+  });
+}
+
+int vp_infer_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h) {
+  return guarded(e, [&](vp::Engine& g) {
+    if (!f) throw std::invalid_argument("null frame");
+    g.upload_from_frame(f->view(), x0, y0, w, h);
+    f->note_consumer(g.stream());
+    g.enqueue();
+    g.fetch_outputs();
+  });
+}
 int vp_sync(vp_engine* e) {
   return guarded(e, [&](vp::Engine& g) { g.sync(); });
 }

@@ -181,13 +181,15 @@ void upload_frame(vp_detect* d, const uint8_t* bgr, int h, int w, int stride_byt
 // upload + letterbox of one frame into `dst` ([3][net_h][net_w] fp32) on the detector's stream; no synchronisation behind the launch.  `who`: the
 // entry point named in error texts.  Two waits on the detector's own stream, neither of which blocks in steady state: the one ahead of the staging
 // copy finds the stream drained (every entry returns synchronised), and the one behind the tap tables runs only when the frame size changes.
-void letterbox_frame(vp_detect* d, const char* who, const uint8_t* bgr, int h, int w, int stride_bytes, float* dst) {
-  check_frame(who, bgr, h, w, stride_bytes);
+// `bring()` puts the frame's bytes into d->d_frame, rows stride_bytes apart, on the detector's stream: the host path's staged upload, or the region copy
+// out of a device-resident vp_frame.
+template <class Bring>
+void letterbox_resident(vp_detect* d, const char* who, Bring&& bring, int h, int w, int stride_bytes, float* dst) {
   // preprocessAutoSpeed :78-98 -- fp32 scale, truncated new size, centred paste
   const float scale = std::min((float)d->net_w / (float)w, (float)d->net_h / (float)h);
   const int new_w = (int)((float)w * scale), new_h = (int)((float)h * scale);
   if (new_w < 1 || new_h < 1 || new_w > d->net_w || new_h > d->net_h) throw std::invalid_argument(std::string(who) + ": the frame collapses under the letterbox scale");
-  upload_frame(d, bgr, h, w, stride_bytes);
+  bring();
   if (d->tab_w != w || d->tab_h != h) {
     std::vector<int> xt, yt;
     vp::linear_taps_u8(w, new_w, &xt);
@@ -215,6 +217,25 @@ void letterbox_frame(vp_detect* d, const char* who, const uint8_t* bgr, int h, i
   p.out = dst;
   VP_HIP_CHECK(vp::launch_letterbox(p, d->stream));
   store_geometry(d, scale, p.pad_x, p.pad_y, w, h);
+}
+
+void letterbox_frame(vp_detect* d, const char* who, const uint8_t* bgr, int h, int w, int stride_bytes, float* dst) {
+  check_frame(who, bgr, h, w, stride_bytes);
+  letterbox_resident(d, who, [&] { upload_frame(d, bgr, h, w, stride_bytes); }, h, w, stride_bytes, dst);
+}
+
+// the same from a region of a device-resident vp_frame: the detector's stream waits for the frame's content, copies the region device to device (rows
+// packed) and tells the frame that a consumer's copy is queued; the letterbox launch behind it is the host path's
+void letterbox_from_frame(vp_detect* d, const char* who, vp_frame* f, int x0, int y0, int w, int h, float* dst) {
+  const vp::FrameView v = f->view();
+  if (v.gpu != d->gpu) throw std::invalid_argument(std::string(who) + ": the frame lives on GPU " + std::to_string(v.gpu) + ", the detector on GPU " + std::to_string(d->gpu));
+  vp::resolve_frame_region(v, x0, y0, &w, &h);
+  letterbox_resident(d, who, [&] {
+    d->d_frame.reserve((size_t)h * 3 * w);   // a growth frees the old buffer: every entry returns with the stream drained, nothing reads it
+    VP_HIP_CHECK(hipStreamWaitEvent(d->stream, v.ready, 0));
+    VP_HIP_CHECK(hipMemcpy2DAsync(d->d_frame, (size_t)3 * w, v.bgr + (size_t)y0 * v.pitch + (size_t)3 * x0, v.pitch, (size_t)3 * w, h, hipMemcpyDeviceToDevice, d->stream));
+    f->note_consumer(d->stream);
+  }, h, w, 3 * w, dst);
 }
 
 // resize_letterbox of the Python wrapper (auto_speed_infer.py:24-34) in the doubles Python computes it in: scale = min(tw / ow, th / oh),
@@ -454,6 +475,21 @@ int vp_detect_infer(vp_detect* d, const uint8_t* bgr, int h, int w, int stride_b
                     int* count) {
   return infer_rows(d, vp::kDetectPerClass, [&](const char* who, float* dst) { letterbox_frame(d, who, bgr, h, w, stride_bytes, dst); }, conf_thresh, iou_thresh, out, out_cap,
                     count);
+}
+
+int vp_detect_infer_frame(vp_detect* d, vp_frame* f, int x0, int y0, int w, int h, float conf_thresh, float iou_thresh, vp_detection* out, int out_cap,
+                          int* count) {
+  if (!d) return VP_ERR_ARG;
+  if (!f) {
+    d->err = "vp_detect_infer_frame: null frame";
+    return VP_ERR_ARG;
+  }
+  if (!f->uploaded) {
+    d->err = "vp_detect_infer_frame: the frame was never uploaded (vp_frame_upload / vp_frame_upload_device first)";
+    return VP_ERR_STATE;
+  }
+  return infer_rows(d, vp::kDetectPerClass, [&](const char*, float* dst) { letterbox_from_frame(d, "vp_detect_infer_frame", f, x0, y0, w, h, dst); }, conf_thresh,
+                    iou_thresh, out, out_cap, count);
 }
 
 int vp_detect_geometry_pil(int net_h, int net_w, int h, int w, double* scale, int* new_w, int* new_h, int* pad_x, int* pad_y) {

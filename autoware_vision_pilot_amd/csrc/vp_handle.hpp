@@ -1,7 +1,9 @@
-// The opaque handle behind include/vp_hip.h (shared by vp_api.cpp and vp_comm.cpp).
+// The opaque handles behind include/vp_hip.h (shared by vp_api.cpp, vp_detect.cpp and vp_comm.cpp).
 #pragma once
 #include <memory>
+#include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/vp_hip.h"
 #include "engine.hpp"
@@ -9,4 +11,41 @@
 struct vp_engine {
   std::unique_ptr<vp::Engine> impl;
   std::string err;
+};
+
+// vp_frame: one camera frame, uploaded once in its native format and kept as packed BGR8 on the device for any number of consumers (engines, the
+// detector).  Owns its stream and buffers; the member functions are defined in vp_api.cpp.
+// Ordering, all of it on the device: an upload ends with `ready` recorded on the frame's stream, and every consumer's stream waits for that event
+// ahead of its region copy; a consumer records its own event behind the copy (note_consumer), and the next upload makes the frame's stream wait for
+// every such event before it overwrites the image (wait_for_consumers).  `consumers` is the only state two threads touch: consumers on different
+// engines may run concurrently, so it sits behind `mu`.  One event per consumer stream is enough: a later record on the same stream lies behind the
+// earlier copy too.
+struct vp_frame {
+  int gpu = 0;
+  hipStream_t stream = nullptr;
+  uint8_t* d_bgr = nullptr;      // [h][pitch], pitch = vp::frame_bgr_pitch(w)
+  size_t bgr_cap = 0;
+  uint8_t* d_src = nullptr;      // the native planes of a host upload, rows packed, plane after plane (what the conversion kernel reads)
+  size_t src_cap = 0;
+  uint8_t* h_stage = nullptr;    // pinned staging of a pageable host frame: two slots, as the engines' (engine_io.cpp upload_frame)
+  size_t stage_cap = 0;          // bytes per slot
+  int stage_slot = 0;
+  hipEvent_t stage_ev[2] = {nullptr, nullptr};
+  int h = 0, w = 0, pitch = 0;
+  bool uploaded = false;
+  hipEvent_t ready = nullptr;     // content complete
+  hipEvent_t producer = nullptr;  // vp_frame_upload_device: recorded on the caller's producer stream
+  struct Consumer {
+    hipStream_t stream;
+    hipEvent_t done;
+    bool pending;
+  };
+  std::mutex mu;
+  std::vector<Consumer> consumers;
+  std::string err;
+
+  ~vp_frame();
+  vp::FrameView view() const;
+  void note_consumer(hipStream_t s);   // behind a consumer's copy, on the consumer's stream
+  void wait_for_consumers();           // ahead of an upload, on the frame's stream
 };

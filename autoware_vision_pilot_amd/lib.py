@@ -151,6 +151,17 @@ _SIGS = {
     "vp_split_weight_rows": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     "vp_fp8_encode_rows": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "vp_convert_onnx": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]),
+    "vp_frame_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_size_t]),
+    "vp_frame_destroy": (None, [_P]),
+    "vp_frame_last_error": (C.c_char_p, [_P]),
+    "vp_frame_upload": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]),
+    "vp_frame_upload_device": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, _P]),
+    "vp_frame_sync": (C.c_int, [_P]),
+    "vp_frame_dims": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vp_frame_fetch_bgr8": (C.c_int, [_P, _P, C.c_int]),
+    "vp_upload_from_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vp_infer_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vp_detect_infer_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
 }
 # multi-camera exchange (csrc/vp_comm.cpp): part of libvp_hip.so, absent from the CPU-emulated test build
 _COMM_SIGS = {
@@ -172,6 +183,10 @@ VP_GATHER_MASK, VP_GATHER_LOGITS = 0, 1
 VP_COMM_ID_BYTES = 128
 
 VP_RANGE_BINS, VP_RANGE_EXP_MIN = 40, -24
+VP_FRAME_BGR8, VP_FRAME_RGB8, VP_FRAME_BGRA8, VP_FRAME_RGBA8, VP_FRAME_GRAY8, VP_FRAME_NV12, VP_FRAME_YUY2, VP_FRAME_UYVY = range(8)
+FRAME_FORMATS = {"bgr8": VP_FRAME_BGR8, "rgb8": VP_FRAME_RGB8, "bgra8": VP_FRAME_BGRA8, "rgba8": VP_FRAME_RGBA8, "gray8": VP_FRAME_GRAY8, "nv12": VP_FRAME_NV12,
+                 "yuy2": VP_FRAME_YUY2, "uyvy": VP_FRAME_UYVY}
+_FRAME_PX_BYTES = (3, 3, 4, 4, 1, 1, 2, 2)   # bytes per pixel of plane 0
 
 
 class RangeStats(C.Structure):
@@ -565,6 +580,17 @@ class Engine:
             self._keep_n[index] = f
             self._ck(self._lib.vp_upload_frame_n(self._h, int(index), _ptr(f), f.shape[0], f.shape[1], f.strides[0]))
 
+    def upload_from_frame(self, frame, region=None):
+        """vp_upload_from_frame: asynchronous region copy out of a device-resident Frame into this engine's frame buffer (region = (x0, y0, w, h); None =
+        the whole frame); enqueue() / sync() / fetch_outputs() follow as behind upload_frame."""
+        x0, y0, w, h = (0, 0, 0, 0) if region is None else (int(v) for v in region)
+        self._ck(self._lib.vp_upload_from_frame(self._h, frame._h, x0, y0, w, h))
+
+    def infer_frame(self, frame, region=None):
+        """vp_infer_frame: infer() on a region of a device-resident Frame (no staging copy, no H2D)."""
+        x0, y0, w, h = (0, 0, 0, 0) if region is None else (int(v) for v in region)
+        self._ck(self._lib.vp_infer_frame(self._h, frame._h, x0, y0, w, h))
+
     def frames(self):
         return self._lib.vp_frames(self._h)
 
@@ -662,6 +688,91 @@ class Engine:
             raise VpError(f"vp_range_survey answered {n} tensors, vp_tensor_count {len(info)}")
         return [{"name": name, "c": c, "h": h, "w": w, "exp": int(r.exp), "absmax": np.float32(r.absmax), "count": int(r.count), "nonfinite": int(r.nonfinite),
                  "zeros": int(r.zeros), "bins": np.array(r.bins[:], dtype=np.int64)} for (name, c, h, w), r in zip(info, buf)]
+
+
+class Frame:
+    """vp_frame: one camera frame, uploaded once in its native format, converted to BGR8 on the device and handed to any number of consumers
+    (Engine.infer_frame / upload_from_frame, Detector.infer_frame).  One thread uploads, any number consume; ping-pong two Frames between capture
+    and consumers (include/vp_hip.h)."""
+
+    def __init__(self, gpu_id=0):
+        self._lib = load()
+        self._h = _P()
+        err = C.create_string_buffer(512)
+        rc = self._lib.vp_frame_create(C.byref(self._h), gpu_id, err, len(err))
+        if rc != 0:
+            self._h = None
+            raise (ValueError if rc == -1 else VpError)(f"vp_frame_create failed ({rc}): {err.value.decode(errors='replace')}")
+        self._keep = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vp_frame_destroy(self._h)
+            self._h = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _ck(self, rc):
+        if rc < 0:
+            msg = self._lib.vp_frame_last_error(self._h).decode(errors="replace")
+            raise (ValueError if rc == -1 else VpError)(f"libvp_hip frame error {rc}: {msg}")
+        return rc
+
+    @staticmethod
+    def _fmt(fmt):
+        return FRAME_FORMATS[fmt.lower()] if isinstance(fmt, str) else int(fmt)
+
+    def upload(self, array_or_planes, fmt="bgr8", hw=None):
+        """vp_frame_upload (asynchronous).  One uint8 array -- HxWx3 (bgr8 / rgb8), HxWx4 (bgra8 / rgba8), HxW (gray8), Hx(2W) or HxWx2 (yuy2 / uyvy) -- or,
+        for nv12, the pair (Y [H][W], UV [H/2][W]) or one [H * 3 / 2][W] array.  Row strides are taken from the arrays (the bytes of a row must be
+        contiguous); `hw` overrides the (h, w) read off plane 0."""
+        f = self._fmt(fmt)
+        planes = list(array_or_planes) if isinstance(array_or_planes, (list, tuple)) else [array_or_planes]
+        planes = [np.asarray(p) for p in planes]
+        if f == VP_FRAME_NV12 and len(planes) == 1 and planes[0].ndim == 2 and planes[0].shape[0] % 3 == 0:
+            a = planes[0]
+            planes = [a[: a.shape[0] // 3 * 2], a[a.shape[0] // 3 * 2:]]
+        fixed = []
+        for p in planes:
+            if p.dtype != np.uint8 or p.ndim < 2 or any(p.strides[i] != int(np.prod(p.shape[i + 1:])) for i in range(1, p.ndim)) or p.strides[0] < 0:
+                p = np.ascontiguousarray(p, dtype=np.uint8)
+            fixed.append(p)
+        p0 = fixed[0]
+        h, w = (int(hw[0]), int(hw[1])) if hw is not None else (p0.shape[0], int(np.prod(p0.shape[1:])) // _FRAME_PX_BYTES[f] if 0 <= f < 8 else 0)
+        self._keep = fixed   # a registered pool is read by DMA after the call returns
+        arr = (_P * len(fixed))(*[p.ctypes.data for p in fixed])
+        strides = (C.c_int * len(fixed))(*[int(p.strides[0]) for p in fixed])
+        self._ck(self._lib.vp_frame_upload(self._h, f, arr, strides, len(fixed), h, w))
+
+    def upload_device(self, plane_ptrs, strides, fmt, h, w, producer_stream=None):
+        """vp_frame_upload_device: device pointers (ints) of the planes on this frame's GPU and their row strides in bytes; producer_stream: the
+        hipStream_t handle (int) the planes are ready on, None = ready now.  The planes stay valid and unmodified until sync() or a consumer's
+        synchronising call."""
+        arr = (_P * len(plane_ptrs))(*[int(p) for p in plane_ptrs])
+        st = (C.c_int * len(strides))(*[int(s) for s in strides])
+        self._ck(self._lib.vp_frame_upload_device(self._h, self._fmt(fmt), arr, st, len(plane_ptrs), int(h), int(w), _P(int(producer_stream)) if producer_stream else None))
+
+    def sync(self):
+        self._ck(self._lib.vp_frame_sync(self._h))
+
+    def hw(self):
+        h, w = C.c_int(), C.c_int()
+        rc = self._lib.vp_frame_dims(self._h, C.byref(h), C.byref(w))
+        if rc != 0:
+            raise VpError(f"vp_frame_dims failed ({rc}): nothing was uploaded yet")
+        return h.value, w.value
+
+    def fetch_bgr8(self):
+        """the converted image, HxWx3 uint8 (synchronises the frame's stream)"""
+        h, w = self.hw()
+        out = np.empty((h, w, 3), np.uint8)
+        self._ck(self._lib.vp_frame_fetch_bgr8(self._h, _ptr(out), out.strides[0]))
+        return out
 
 
 def decode_logits_host(logits_chw, decode_mode=VP_DECODE_SEG_MASK, gpu_id=0):
@@ -1028,6 +1139,11 @@ class Detector:
         """vp_detect_infer: HxWx3 BGR uint8 frame -> ([n][6] float32 rows x1, y1, x2, y2, confidence, class_id; total kept) through the attached network."""
         f = self._frame(frame_bgr_u8)
         return self._rows("vp_detect_infer", (_ptr(f), f.shape[0], f.shape[1], f.strides[0]), conf_thresh, iou_thresh, 1024 if cap is None else cap, True, True)
+
+    def infer_frame(self, frame, conf_thresh, iou_thresh, region=None, cap=None):
+        """vp_detect_infer_frame: infer() on a region (x0, y0, w, h; None = the whole frame) of a device-resident Frame."""
+        x0, y0, w, h = (0, 0, 0, 0) if region is None else (int(v) for v in region)
+        return self._rows("vp_detect_infer_frame", (frame._h, x0, y0, w, h), conf_thresh, iou_thresh, 1024 if cap is None else cap, True, True)
 
     __del__ = close
 

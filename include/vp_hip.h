@@ -343,6 +343,62 @@ int vp_use_graph(vp_engine* e, int enable);                                    /
 int vp_timer_begin(vp_engine* e);                                              /* hipEvent on the engine stream */
 int vp_timer_end(vp_engine* e, float* elapsed_ms);                             /* records, syncs, returns elapsed */
 
+/* ---- vp_frame: one camera frame, uploaded once in its native format, for every engine ------------------------------------------
+ * The reference's production application (VisionPilot/production_release/main.cpp) feeds ONE captured frame to a lateral thread (EgoLanes on the
+ * crop rows >= 420, main.cpp:497-505) and a longitudinal thread (AutoSpeed), and its sensor path converts to BGR on the CPU first
+ * (common/sensors/gstreamer_engine.cpp:33-47 `videoconvert ! video/x-raw,format=BGR`; run_model_node.cpp:70 toCvCopy(BGR8)) although V4L2 cameras and
+ * hardware decoders deliver YUY2 / UYVY / NV12.  With vp_infer / vp_detect_infer every network pays its own staging copy and its own H2D for the
+ * same bytes.  A vp_frame takes the frame ONCE, in the format it arrives in, converts it on the device to BGR8 and hands regions of it to any number
+ * of consumers:
+ *     vp_frame_upload(f, VP_FRAME_YUY2, &data, &stride, 1, 720, 1280);
+ *     thread A: vp_infer_frame(egolanes, f, 0, 420, 1280, 300);      thread B: vp_detect_infer_frame(det, f, 0, 0, 0, 0, ...);
+ * A vp_frame always holds packed BGR8.  BGR8 is copied straight in; RGB8 / BGRA8 / RGBA8 are permuted or lose alpha; GRAY8 is replicated to three
+ * channels; the YUV formats use the integer BT.601 limited-range form OpenCV documents for cvtColor(COLOR_YUV2BGR_NV12 / _YUY2 / _UYVY): 20-bit fixed
+ * point, no chroma interpolation (NV12 shares one (U, V) per 2x2 block, YUY2 = Y0 U Y1 V and UYVY = U Y0 V Y1 one per horizontal pixel pair):
+ *     y = 1220542 * max(0, Y - 16);  u = U - 128;  v = V - 128
+ *     R = sat8((y + 1673527 * v               + (1 << 19)) >> 20)
+ *     G = sat8((y -  852492 * v - 409993 * u  + (1 << 19)) >> 20)
+ *     B = sat8((y + 2116026 * u               + (1 << 19)) >> 20)         arithmetic shift, then clamp to 0 .. 255
+ * This formula IS the definition; parity with OpenCV itself is not pinned (OpenCV is absent here: DESIGN.md section 4).
+ * planes / strides: 1 plane (2 for NV12: Y, then interleaved UV), strides in bytes.  VP_ERR_ARG (with text): odd w for NV12 / YUY2 / UYVY, odd h for
+ * NV12, h or w below 2, a stride below the row's bytes, a wrong n_planes, an unknown format.
+ * vp_frame_upload is ASYNCHRONOUS on the frame's own stream.  Host planes are staged through the frame's pinned double buffer (copied before the call
+ * returns) or, when every plane lies inside a vp_register_frames range, copied by one DMA per plane straight from the caller's memory -- the rules
+ * of vp_upload_frame, including that such planes stay unmodified until vp_frame_sync or a consumer's synchronising call.
+ * vp_frame_upload_device takes the planes from DEVICE memory on the frame's GPU (a decoder surface, another HIP producer) and converts straight from
+ * them (no intermediate copy): they must stay valid and unmodified until the conversion has run (vp_frame_sync, or any consumer's synchronising
+ * call).  producer_stream: a hipStream_t the planes are ready on -- the frame's stream waits for the work queued on it so far -- or NULL = ready now
+ * (NULL also spells HIP's legacy default stream, which therefore cannot be named: synchronise it first, or produce on a created stream).
+ * ORDERING CONTRACT.  Consumers never wait on the host for the frame: the consumer's stream waits (hipStreamWaitEvent) for the frame's "content
+ * ready" event.  A later vp_frame_upload* orders itself ON THE DEVICE behind every consumer copy queued so far (each consumer records an event behind
+ * its copy; the frame waits for them in its own stream), so the host may re-upload without synchronising anything:
+ *     upload(A); vp_upload_from_frame(e1, f, ..); vp_enqueue(e1); upload(B); vp_upload_from_frame(e2, f, ..); vp_enqueue(e2);   e1 sees A, e2 sees B.
+ * THREADING.  One thread uploads; any number of threads consume concurrently, each on its own engine / detector.  An upload CONCURRENT with a
+ * consumer call on the same vp_frame is the host's race to avoid: use two frames, ping-pong, as the reference's DoubleFrameBuffer does
+ * (INTEGRATION.md "One camera frame, several networks").  A frame must outlive the passes that consume it.  No process-wide state. */
+typedef struct vp_frame vp_frame;
+enum vp_frame_format { VP_FRAME_BGR8 = 0, VP_FRAME_RGB8 = 1, VP_FRAME_BGRA8 = 2, VP_FRAME_RGBA8 = 3, VP_FRAME_GRAY8 = 4,
+                       VP_FRAME_NV12 = 5, VP_FRAME_YUY2 = 6, VP_FRAME_UYVY = 7 };
+int vp_frame_create(vp_frame** out, int gpu_id, char* err, size_t err_len);
+void vp_frame_destroy(vp_frame* f);
+const char* vp_frame_last_error(const vp_frame* f);
+int vp_frame_upload(vp_frame* f, int format, const uint8_t* const* planes, const int* strides, int n_planes, int h, int w);
+int vp_frame_upload_device(vp_frame* f, int format, const void* const* dev_planes, const int* strides, int n_planes, int h, int w, void* producer_stream);
+int vp_frame_sync(vp_frame* f);                                          /* waits for the frame's own stream (upload + conversion) */
+int vp_frame_dims(const vp_frame* f, int* h, int* w);                    /* geometry of the last upload; VP_ERR_STATE before it (vp_frame_hw is the engine's) */
+int vp_frame_fetch_bgr8(vp_frame* f, uint8_t* dst, int dst_stride);      /* the converted image, synchronous (tests, hosts that still want a cv::Mat) */
+/* Consumers.  vp_upload_from_frame is the asynchronous twin of vp_upload_frame: the engine's stream waits for the frame's content, then copies the
+ * region (x0, y0, w, h; all four 0: the whole frame) device to device, rows packed, into the engine's own frame buffer -- from there on the pass is
+ * vp_enqueue / vp_sync / vp_fetch_outputs as today, and everything behind the upload is the host path's: tap tables, a geometry change leading to
+ * graph re-capture, vp_visualize_mask_bgr8's "last frame", AutoDrive's streaming pair.  A region gives the bits vp_upload_frame gives for the same
+ * pixels passed as a strided view.  vp_infer_frame = that + what vp_infer does behind its upload.  vp_detect_infer_frame = vp_detect_infer on the
+ * region (VP_AUTOSPEED engine attached).
+ * Accepted: the scene kinds, VP_AUTODRIVE (streaming form), VP_AUTOSTEER (the region must be 512 x 1024).  VP_ERR_ARG: a shared-prefix head (frames
+ * go to the base), a batched encoder, an engine whose vp_set_input_format pixel format is not VP_BGR8, a frame on another GPU, a region outside the
+ * frame or smaller than 2 x 2; a VP_AUTOSPEED engine: the refusal vp_upload_frame gives; a frame never uploaded: VP_ERR_STATE. */
+int vp_upload_from_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h);
+int vp_infer_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h);
+
 /* ---- multi-camera result exchange (BASELINE configs[3]) ---------------------------------------
  * One process (or thread) per GPU, camera r on rank r, weights replicated, no data-path collective in the networks.  For the
  * fused ego-path / BEV consumer every rank needs all cameras' results: ONE ncclAllGather (RCCL over xGMI) per frame of a
@@ -430,6 +486,11 @@ int vp_detect_postprocess(vp_detect* d, const float* raw, int raw_on_device, int
 int vp_detect_attach(vp_detect* d, vp_engine* net);
 int vp_detect_infer(vp_detect* d, const uint8_t* bgr, int h, int w, int stride_bytes, float conf_thresh, float iou_thresh, vp_detection* out,
                     int out_cap, int* count);
+/* vp_detect_infer on the region (x0, y0, w, h; all four 0: the whole frame) of a device-resident vp_frame (above): the detector's stream waits for
+ * the frame's content and copies the region device to device into its frame buffer; no staging copy, no H2D; everything behind is vp_detect_infer.
+ * VP_ERR_ARG for a frame on another GPU or a bad region, VP_ERR_STATE for a frame never uploaded. */
+int vp_detect_infer_frame(vp_detect* d, vp_frame* f, int x0, int y0, int w, int h, float conf_thresh, float iou_thresh, vp_detection* out, int out_cap,
+                          int* count);
 /* The same stages in the arithmetic of the PYTHON wrapper, Models/inference/auto_speed_infer.py AutoSpeedNetworkInfer, which no thresholds of the
  * entries above reproduce (infer.AutoSpeedNetworkInfer is built on these; they share the handle, its buffers and its stored geometry with them):
  *   vp_detect_preprocess_pil  resize_letterbox + ToTensor (:24-42): scale = min(net_w / w, net_h / h) in double, new size int(w * scale), Pillow's
