@@ -110,6 +110,12 @@ struct FrameView {
 // the region (x0, y0, w, h) of a frame as a consumer takes it (w == h == 0: the whole frame); throws std::invalid_argument / std::runtime_error
 void resolve_frame_region(const FrameView& f, int x0, int y0, int* w, int* h);
 
+// Where an engine's resident input came from (vp_canvas draws there): the region (x0, y0, w, h) of a source frame of H x W.  vp_upload_from_frame /
+// vp_infer_frame record the region they took; the host uploads record the whole frame, (0, 0, w, h) of h x w.  H == 0: no frame was taken yet.
+struct SourceRegion {
+  int x0 = 0, y0 = 0, w = 0, h = 0, H = 0, W = 0;
+};
+
 struct ConvChoice;   // engine_internal.hpp: what the dispatch rules of engine_dispatch.cpp give one convolution
 struct HostWeights;  // engine_internal.hpp: a layer's packed weights on the host
 
@@ -195,6 +201,7 @@ class Engine {
   const uint8_t* host_mask();
   int frame_h() const { return frame_h_; }
   int frame_w() const { return frame_w_; }
+  const SourceRegion& source_region() const { return base_ ? base_->source_region() : src_region_; }   // a shared-prefix head: its base's
   void* dev_logits() const { return d_logits_; }
   void* dev_mask() const { return d_mask_; }
   float* alloc_f32(size_t n) { return static_cast<float*>(dalloc(n * sizeof(float))); }  // test operator entry: a logits buffer
@@ -381,6 +388,8 @@ class Engine {
   uint8_t* d_frame_ = nullptr;
   size_t frame_cap_ = 0;
   int frame_h_ = 0, frame_w_ = 0, frame_stride_ = 0;
+  SourceRegion src_region_;
+  friend class Canvas;   // reads the last mask / logits on the device and orders its stream against this engine's
   int* d_xtab_ = nullptr;
   int* d_ytab_ = nullptr;
   int tab_h_ = 0, tab_w_ = 0;
@@ -455,6 +464,72 @@ class Engine {
   bool graph_valid_ = false;
   bool warmed_ = false;
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
+};
+
+// vp_canvas (include/vp_hip.h; handle: vp_handle.hpp; kernels: kernels_misc.hip canvas_*): one BGR8 picture per camera frame on the device.  begin()
+// copies a vp_frame's image; every engine, heads included, blends its mask or pastes its depth map into the region its input came from; the detector's
+// boxes are drawn on top; fetch() hands the picture out once, in any vp_frame format.  The blend and the depth pipeline are those of
+// Engine::visualize_mask / visualize_depth (same tables, same LUTs, same kernels or their region forms).  Owns its stream and buffers.
+// Ordering, all on the device: a draw makes the canvas's stream wait for the work queued on the engine's stream so far (the pass that wrote the mask),
+// and makes the engine's stream wait for the canvas's read before anything queued on it later (the next pass) runs.  The only host waits are fetch(),
+// sync(), a buffer that has to grow and the first use of a resize table of a new (source, destination) size: once per geometry.
+class Canvas {
+ public:
+  explicit Canvas(int gpu);
+  ~Canvas();
+  Canvas(const Canvas&) = delete;
+  Canvas& operator=(const Canvas&) = delete;
+  void begin(const FrameView& f);   // the caller records the frame's consumer event behind it, on stream()
+  void blend_mask(Engine& e, int viz_type);
+  void blend_mask_u8(const uint8_t* mask, bool on_device, int mh, int mw, int viz_type, int x0, int y0, int w, int h);
+  void paste_depth(Engine& e);
+  void draw_boxes(const CanvasBox* boxes, int n);   // inclusive rectangles before clipping, in drawing order
+  void sync();
+  // planes / strides / row_bytes / rows: what vp_canvas_layout answers for (format, h(), w()), checked by the caller
+  void fetch(int format, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows, int n_planes);
+  hipStream_t stream() const { return stream_; }
+  int gpu() const { return gpu_; }
+  bool begun() const { return begun_; }
+  int h() const { return h_; }
+  int w() const { return w_; }
+  int pitch() const { return pitch_; }
+  uint8_t* device() const { return d_bgr_; }
+
+ private:
+  struct Table {
+    int src, dst;
+    int* idx;      // nearest: [dst]; linear: [dst][2]
+    float* wgt;    // linear: [dst][2]; nearest: null
+  };
+  Table table(bool linear, int src, int dst);
+  void release();
+  const Engine& source_of(Engine& e, const char* who, SourceRegion* r) const;
+  void need_begun(const char* who) const;
+  void wait_for(Engine& e);        // the canvas's stream behind the engine's work so far
+  void release_to(Engine& e);      // the engine's later work behind the canvas's read
+  void blend(const uint8_t* d_mask, int mh, int mw, int viz_type, const SourceRegion& r);
+  template <class T>
+  void grow(T*& p, size_t& cap, size_t bytes);
+  int gpu_;
+  hipStream_t stream_ = nullptr;
+  hipEvent_t ev_src_ = nullptr, ev_read_ = nullptr;
+  uint8_t* d_bgr_ = nullptr;
+  size_t bgr_cap_ = 0;
+  int h_ = 0, w_ = 0, pitch_ = 0;
+  bool begun_ = false;
+  std::vector<Table> tables_;
+  uint8_t* d_lut_ = nullptr;       // [3 viz types][256][3], then viridis [256][3]
+  unsigned* d_minmax_ = nullptr;   // [0, 2): the keys of the plane in work; [2, 4): their start values
+  float* d_depth_ = nullptr;       // the depth plane at region size
+  size_t depth_cap_ = 0;
+  uint8_t* d_out_ = nullptr;       // fetch: the planes of the requested format
+  size_t out_cap_ = 0;
+  uint8_t* d_umask_ = nullptr;     // blend_mask_u8 from the host: the caller's mask
+  size_t umask_cap_ = 0;
+  uint8_t* h_umask_ = nullptr;     // ... staged through two pinned slots, as a frame upload is
+  size_t h_umask_cap_ = 0;
+  int umask_slot_ = 0;
+  hipEvent_t umask_ev_[2] = {nullptr, nullptr};
 };
 
 #define VP_HIP_CHECK(expr)                                                                                   \

@@ -294,6 +294,7 @@ void Engine::upload_from_frame(const FrameView& f, int x0, int y0, int w, int h)
   uint8_t* dst = accept_frame_geometry(true, h, w, 3 * w, 0);
   VP_HIP_CHECK(hipStreamWaitEvent(stream_, f.ready, 0));   // never a host wait: the copy runs once the frame's content is complete
   VP_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)3 * w, f.bgr + (size_t)y0 * f.pitch + (size_t)3 * x0, f.pitch, (size_t)3 * w, h, hipMemcpyDeviceToDevice, stream_));
+  src_region_ = {x0, y0, w, h, f.h, f.w};
   note_frame_input();
 }
 
@@ -333,6 +334,7 @@ void Engine::upload_frame(const uint8_t* frame, int h, int w, int stride, int in
   } else {
     VP_HIP_CHECK(hipMemcpy2DAsync(dst, stride, frame, stride, (size_t)3 * w, h, hipMemcpyHostToDevice, stream_));
   }
+  src_region_ = {0, 0, w, h, h, w};   // a host frame is its own source
   note_frame_input();
 }
 
@@ -620,6 +622,21 @@ void Engine::mask_resized(uint8_t* dst, int h, int w) {
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
+// createColorMask (masks_visualization_engine.cpp:41-58), BGR: [3 viz types][256][3]; label values not listed stay black
+static std::vector<uint8_t> viz_color_lut() {
+  std::vector<uint8_t> lut(3 * 256 * 3, 0);
+  for (int v = 1; v < 256; ++v) { lut[(0 * 256 + v) * 3 + 2] = 255; }                          // "scene": 1..255 -> (0,0,255)
+  const uint8_t dom0[3] = {255, 93, 61}, dom255[3] = {145, 28, 255};                            // "domain"
+  for (int c = 0; c < 3; ++c) { lut[(1 * 256 + 0) * 3 + c] = dom0[c]; lut[(1 * 256 + 255) * 3 + c] = dom255[c]; }
+  const uint8_t ego[3][3] = {{255, 0, 0}, {255, 0, 200}, {0, 153, 0}};                          // "egolanes": labels 0,1,2
+  for (int v = 0; v < 3; ++v)
+    for (int c = 0; c < 3; ++c) lut[(2 * 256 + v) * 3 + c] = ego[v][c];
+  return lut;
+}
+static const uint8_t kViridisBgr[256 * 3] = {
+#include "viridis_lut.inc"
+};
+
 // MasksVisualizationEngine::visualize on the device: the mask of the LAST inference, coloured, nearest-resized to the frame
 // that produced it and blended 50/50 with that (still resident) frame; BGR8 out, frame size.
 void Engine::visualize_mask(int viz_type, uint8_t* dst, int dst_h, int dst_w) {
@@ -632,17 +649,7 @@ void Engine::visualize_mask(int viz_type, uint8_t* dst, int dst_h, int dst_w) {
   if (dst_h != h || dst_w != w)
     throw std::invalid_argument("visualize_mask: destination is " + std::to_string(dst_w) + "x" + std::to_string(dst_h) +
                                 " but the last inferred frame was " + std::to_string(w) + "x" + std::to_string(h));
-  if (!d_viz_lut_) {
-    // createColorMask (masks_visualization_engine.cpp:41-58), BGR
-    std::vector<uint8_t> lut(3 * 256 * 3, 0);
-    for (int v = 1; v < 256; ++v) { lut[(0 * 256 + v) * 3 + 2] = 255; }                          // "scene": 1..255 -> (0,0,255)
-    const uint8_t dom0[3] = {255, 93, 61}, dom255[3] = {145, 28, 255};                            // "domain"
-    for (int c = 0; c < 3; ++c) { lut[(1 * 256 + 0) * 3 + c] = dom0[c]; lut[(1 * 256 + 255) * 3 + c] = dom255[c]; }
-    const uint8_t ego[3][3] = {{255, 0, 0}, {255, 0, 200}, {0, 153, 0}};                          // "egolanes": labels 0,1,2
-    for (int v = 0; v < 3; ++v)
-      for (int c = 0; c < 3; ++c) lut[(2 * 256 + v) * 3 + c] = ego[v][c];
-    d_viz_lut_ = dupload(lut);
-  }
+  if (!d_viz_lut_) d_viz_lut_ = dupload(viz_color_lut());
   const size_t need = (size_t)3 * h * w, tabn = (size_t)(h + w);
   if (need > resize_cap_) {
     dfree(d_resize_out_);   // only this family of calls uses it, and each returns synchronised
@@ -705,9 +712,6 @@ void Engine::depth_resized(float* dst, int h, int w) {
 void Engine::visualize_depth(uint8_t* dst, int h, int w) {
   if (!have_outputs_) throw std::runtime_error("Inference has not been run yet");
   if (!dst || h < 1 || w < 1) throw std::invalid_argument("bad visualisation target");
-  static const uint8_t kViridisBgr[256 * 3] = {
-#include "viridis_lut.inc"
-  };
   if (!d_viridis_) {
     d_viridis_ = dupload(std::vector<uint8_t>(kViridisBgr, kViridisBgr + sizeof(kViridisBgr)));
     d_minmax_ = static_cast<unsigned*>(dalloc(2 * sizeof(unsigned), false));
@@ -724,6 +728,269 @@ void Engine::visualize_depth(uint8_t* dst, int h, int w) {
   VP_HIP_CHECK(launch_minmax_f32(static_cast<const float*>(d_resize_out_), n, d_minmax_, stream_));
   VP_HIP_CHECK(launch_depth_colorize(static_cast<const float*>(d_resize_out_), n, d_minmax_, d_viridis_, static_cast<uint8_t*>(d_depth_viz_), stream_));
   VP_HIP_CHECK(hipMemcpyAsync(dst, d_depth_viz_, 3 * n, hipMemcpyDeviceToHost, stream_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+// -------------------------------------------------------------------------------------------------- vp_canvas
+Canvas::Canvas(int gpu) : gpu_(gpu) {
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  try {
+    VP_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    for (hipEvent_t* ev : {&ev_src_, &ev_read_, &umask_ev_[0], &umask_ev_[1]}) VP_HIP_CHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    std::vector<uint8_t> lut = viz_color_lut();
+    lut.insert(lut.end(), kViridisBgr, kViridisBgr + sizeof(kViridisBgr));
+    static const unsigned kKeys[4] = {0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_lut_), lut.size()));
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_minmax_), sizeof(kKeys)));
+    VP_HIP_CHECK(hipMemcpyAsync(d_lut_, lut.data(), lut.size(), hipMemcpyHostToDevice, stream_));
+    VP_HIP_CHECK(hipMemcpyAsync(d_minmax_, kKeys, sizeof(kKeys), hipMemcpyHostToDevice, stream_));
+    VP_HIP_CHECK(hipStreamSynchronize(stream_));   // `lut` is a local
+  } catch (...) {
+    release();
+    throw;
+  }
+}
+
+Canvas::~Canvas() { release(); }
+
+void Canvas::release() {
+  (void)hipSetDevice(gpu_);
+  if (stream_) (void)hipStreamSynchronize(stream_);
+  for (hipEvent_t ev : {ev_src_, ev_read_, umask_ev_[0], umask_ev_[1]})
+    if (ev) (void)hipEventDestroy(ev);
+  for (const Table& t : tables_) {
+    (void)hipFree(t.idx);
+    if (t.wgt) (void)hipFree(t.wgt);
+  }
+  tables_.clear();
+  for (void* p : {(void*)d_bgr_, (void*)d_lut_, (void*)d_minmax_, (void*)d_depth_, (void*)d_out_, (void*)d_umask_})
+    if (p) (void)hipFree(p);
+  if (h_umask_) (void)hipHostFree(h_umask_);
+  if (stream_) (void)hipStreamDestroy(stream_);
+  stream_ = nullptr;
+  ev_src_ = ev_read_ = umask_ev_[0] = umask_ev_[1] = nullptr;
+  d_bgr_ = d_lut_ = d_out_ = d_umask_ = h_umask_ = nullptr;
+  d_minmax_ = nullptr;
+  d_depth_ = nullptr;
+}
+
+// a device buffer that has to grow is freed only once the canvas's own work has run
+template <class T>
+void Canvas::grow(T*& p, size_t& cap, size_t bytes) {
+  if (bytes <= cap) return;
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  const size_t n = (bytes + 255) & ~(size_t)255;
+  VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), n));
+  cap = n;
+}
+
+// The resize tables of visualize_mask / resize_depth_on_device (nearest_tab, linear_taps_f32), kept on the device per (source, destination) size: the
+// first use of a size uploads it and waits (the host vector is a local); every later draw finds it.  A handful of sizes per camera; the one unused
+// longest goes when there are 16, so the two tables of one draw never push each other out.
+Canvas::Table Canvas::table(bool linear, int src, int dst) {
+  for (size_t i = 0; i < tables_.size(); ++i)
+    if ((tables_[i].wgt != nullptr) == linear && tables_[i].src == src && tables_[i].dst == dst) {
+      std::rotate(tables_.begin() + i, tables_.begin() + i + 1, tables_.end());
+      return tables_.back();
+    }
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  if (tables_.size() >= 16) {
+    (void)hipFree(tables_.front().idx);
+    if (tables_.front().wgt) (void)hipFree(tables_.front().wgt);
+    tables_.erase(tables_.begin());
+  }
+  Table t{src, dst, nullptr, nullptr};
+  std::vector<int> idx((linear ? 2 : 1) * (size_t)dst);
+  std::vector<float> wgt;
+  if (linear) {
+    wgt.resize(2 * (size_t)dst);
+    linear_taps_f32(src, dst, idx.data(), wgt.data());
+  } else {
+    nearest_tab(src, dst, idx.data());
+  }
+  VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t.idx), idx.size() * sizeof(int)));
+  tables_.push_back(t);   // owned from here on
+  VP_HIP_CHECK(hipMemcpyAsync(t.idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
+  if (linear) {
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tables_.back().wgt), wgt.size() * sizeof(float)));
+    VP_HIP_CHECK(hipMemcpyAsync(tables_.back().wgt, wgt.data(), wgt.size() * sizeof(float), hipMemcpyHostToDevice, stream_));
+  }
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  return tables_.back();
+}
+
+void Canvas::need_begun(const char* who) const {
+  if (!begun_) throw std::runtime_error(std::string(who) + ": the canvas holds no picture (vp_canvas_begin first)");
+}
+
+void Canvas::begin(const FrameView& f) {
+  if (f.gpu != gpu_) throw std::invalid_argument("vp_canvas_begin: the frame lives on GPU " + std::to_string(f.gpu) + ", the canvas on GPU " + std::to_string(gpu_));
+  if (!f.bgr) throw std::runtime_error("vp_canvas_begin: the frame was never uploaded (vp_frame_upload / vp_frame_upload_device first)");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  begun_ = false;
+  grow(d_bgr_, bgr_cap_, (size_t)f.h * f.pitch);
+  VP_HIP_CHECK(hipStreamWaitEvent(stream_, f.ready, 0));   // never a host wait: the copy runs once the frame's content is complete
+  VP_HIP_CHECK(hipMemcpyAsync(d_bgr_, f.bgr, (size_t)f.h * f.pitch, hipMemcpyDeviceToDevice, stream_));   // same pitch on both sides: one copy
+  h_ = f.h;
+  w_ = f.w;
+  pitch_ = f.pitch;
+  begun_ = true;
+}
+
+// the refusals of blend_mask / paste_depth, the engine whose record counts (a head: its base) and the region the draw goes to
+const Engine& Canvas::source_of(Engine& e, const char* who, SourceRegion* r) const {
+  const std::string me(who);
+  need_begun(who);
+  if (e.gpu_ != gpu_) throw std::invalid_argument(me + ": the engine lives on GPU " + std::to_string(e.gpu_) + ", the canvas on GPU " + std::to_string(gpu_));
+  if (e.kind_ < 0 || e.kind_ > 3) throw std::invalid_argument(me + ": VP_AUTODRIVE / VP_AUTOSPEED / VP_AUTOSTEER engines have no mask or depth plane to draw");
+  if (e.frames_ > 1) throw std::invalid_argument(me + ": a batched encoder has no outputs of its own (draw its per-camera heads)");
+  if (!e.have_outputs_) throw std::runtime_error("Inference has not been run yet");
+  const Engine& src = e.base_ ? *e.base_ : e;
+  if (src.input_is_tensor_) throw std::invalid_argument(me + ": the engine's input was a tensor (vp_infer_tensor): there is no frame region to draw into");
+  *r = src.src_region_;
+  if (r->H != h_ || r->W != w_)
+    throw std::invalid_argument(me + ": the engine's input came from a " + std::to_string(r->W) + " x " + std::to_string(r->H) + " frame, the canvas holds a " +
+                                std::to_string(w_) + " x " + std::to_string(h_) + " picture");
+  return src;
+}
+
+void Canvas::wait_for(Engine& e) {
+  VP_HIP_CHECK(hipEventRecord(ev_src_, e.stream_));
+  VP_HIP_CHECK(hipStreamWaitEvent(stream_, ev_src_, 0));
+}
+void Canvas::release_to(Engine& e) {
+  VP_HIP_CHECK(hipEventRecord(ev_read_, stream_));
+  VP_HIP_CHECK(hipStreamWaitEvent(e.stream_, ev_read_, 0));
+}
+
+void Canvas::blend(const uint8_t* d_mask, int mh, int mw, int viz_type, const SourceRegion& r) {
+  const int* ytab = table(false, mh, r.h).idx;
+  const int* xtab = table(false, mw, r.w).idx;
+  CanvasBlendParams q{};
+  q.mask = d_mask;
+  q.mw = mw;
+  q.ytab = ytab;
+  q.xtab = xtab;
+  q.lut = d_lut_ + (size_t)viz_type * 768;
+  q.canvas = d_bgr_;
+  q.pitch = pitch_;
+  q.x0 = r.x0;
+  q.y0 = r.y0;
+  q.w = r.w;
+  q.h = r.h;
+  VP_HIP_CHECK(launch_canvas_blend(q, h_, w_, stream_));
+}
+
+void Canvas::blend_mask(Engine& e, int viz_type) {
+  SourceRegion r;
+  source_of(e, "vp_canvas_blend_mask", &r);
+  if (viz_type < 0 || viz_type > 2) throw std::invalid_argument("vp_canvas_blend_mask: viz_type 0 (scene), 1 (domain) or 2 (egolanes)");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  wait_for(e);
+  blend(e.d_mask_, e.out_h_, e.out_w_, viz_type, r);
+  release_to(e);
+}
+
+void Canvas::blend_mask_u8(const uint8_t* mask, bool on_device, int mh, int mw, int viz_type, int x0, int y0, int w, int h) {
+  need_begun("vp_canvas_blend_mask_u8");
+  if (!mask || mh < 1 || mw < 1 || mh > 16384 || mw > 16384) throw std::invalid_argument("vp_canvas_blend_mask_u8: null mask or a mask size outside 1 .. 16384");
+  if (viz_type < 0 || viz_type > 2) throw std::invalid_argument("vp_canvas_blend_mask_u8: viz_type 0 (scene), 1 (domain) or 2 (egolanes)");
+  if (x0 < 0 || y0 < 0 || w < 2 || h < 2 || (long long)x0 + w > w_ || (long long)y0 + h > h_)
+    throw std::invalid_argument("vp_canvas_blend_mask_u8: region (x0 " + std::to_string(x0) + ", y0 " + std::to_string(y0) + ", " + std::to_string(w) + " x " + std::to_string(h) +
+                                ") must be at least 2 x 2 and lie inside the " + std::to_string(w_) + " x " + std::to_string(h_) + " canvas");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  const uint8_t* d_mask = mask;
+  if (!on_device) {   // the caller's pageable mask: copied into a pinned slot before the call returns, then one H2D
+    const size_t n = (size_t)mh * mw;
+    grow(d_umask_, umask_cap_, n);
+    if (n > h_umask_cap_) {
+      VP_HIP_CHECK(hipStreamSynchronize(stream_));
+      if (h_umask_) (void)hipHostFree(h_umask_);
+      h_umask_ = nullptr;
+      h_umask_cap_ = 0;
+      const size_t cap = (n + 255) & ~(size_t)255;
+      VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_umask_), 2 * cap, hipHostMallocDefault));
+      h_umask_cap_ = cap;
+    }
+    umask_slot_ ^= 1;
+    uint8_t* slot = h_umask_ + (size_t)umask_slot_ * h_umask_cap_;
+    VP_HIP_CHECK(hipEventSynchronize(umask_ev_[umask_slot_]));   // the H2D that last read this slot, two calls ago
+    std::memcpy(slot, mask, n);
+    VP_HIP_CHECK(hipMemcpyAsync(d_umask_, slot, n, hipMemcpyHostToDevice, stream_));
+    VP_HIP_CHECK(hipEventRecord(umask_ev_[umask_slot_], stream_));
+    d_mask = d_umask_;
+  }
+  blend(d_mask, mh, mw, viz_type, SourceRegion{x0, y0, w, h, h_, w_});
+}
+
+// Engine::visualize_depth's pipeline at the region's size on the canvas's stream and buffers; only the last step differs: the colours go into the region
+void Canvas::paste_depth(Engine& e) {
+  SourceRegion r;
+  source_of(e, "vp_canvas_paste_depth", &r);
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  const size_t n = (size_t)r.h * r.w;
+  grow(d_depth_, depth_cap_, n * sizeof(float));
+  const Table ty = table(true, e.out_h_, r.h), tx = table(true, e.out_w_, r.w);
+  wait_for(e);
+  VP_HIP_CHECK(launch_resize_bilinear_f32(e.d_logits_, e.out_w_, ty.idx, ty.wgt, tx.idx, tx.wgt, r.h, r.w, d_depth_, stream_));
+  release_to(e);   // the logits are read: the engine's next pass may overwrite them
+  VP_HIP_CHECK(hipMemcpyAsync(d_minmax_, d_minmax_ + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToDevice, stream_));
+  VP_HIP_CHECK(launch_minmax_f32(d_depth_, n, d_minmax_, stream_));
+  VP_HIP_CHECK(launch_canvas_depth(d_depth_, d_minmax_, d_lut_ + 3 * 768, d_bgr_, pitch_, r.x0, r.y0, r.w, r.h, h_, w_, stream_));
+}
+
+void Canvas::draw_boxes(const CanvasBox* boxes, int n) {
+  need_begun("vp_canvas_draw_detections");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  for (int first = 0; first < n; first += kCanvasBoxChunk) {
+    CanvasBoxParams q{};
+    q.canvas = d_bgr_;
+    q.pitch = pitch_;
+    q.ux0 = q.uy0 = INT_MAX;
+    q.ux1 = q.uy1 = INT_MIN;
+    for (int i = first; i < std::min(n, first + kCanvasBoxChunk); ++i) {
+      const CanvasBox& b = boxes[i];
+      const int cx0 = std::max(b.x0, 0), cy0 = std::max(b.y0, 0), cx1 = std::min(b.x1, w_ - 1), cy1 = std::min(b.y1, h_ - 1);
+      if (cx1 < cx0 || cy1 < cy0) continue;   // empty, or wholly outside
+      q.box[q.n++] = b;
+      q.ux0 = std::min(q.ux0, cx0);
+      q.uy0 = std::min(q.uy0, cy0);
+      q.ux1 = std::max(q.ux1, cx1);
+      q.uy1 = std::max(q.uy1, cy1);
+    }
+    if (q.n) VP_HIP_CHECK(launch_canvas_boxes(q, h_, w_, stream_));
+  }
+}
+
+void Canvas::sync() {
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+void Canvas::fetch(int format, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows, int n_planes) {
+  need_begun("vp_canvas_fetch");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (format == VP_FRAME_BGR8) {
+    VP_HIP_CHECK(hipMemcpy2DAsync(planes[0], strides[0], d_bgr_, pitch_, row_bytes[0], rows[0], hipMemcpyDeviceToHost, stream_));
+  } else {
+    const size_t pp = (size_t)canvas_plane_pitch(format, w_);
+    grow(d_out_, out_cap_, pp * (rows[0] + (n_planes == 2 ? rows[1] : 0)));
+    CanvasToFormatParams q{};
+    q.src = d_bgr_;
+    q.src_pitch = pitch_;
+    q.h = h_;
+    q.w = w_;
+    q.format = format;
+    q.p0 = d_out_;
+    q.p1 = n_planes == 2 ? d_out_ + pp * rows[0] : nullptr;
+    q.dst_pitch = (int)pp;
+    VP_HIP_CHECK(launch_canvas_to_format(q, stream_));
+    VP_HIP_CHECK(hipMemcpy2DAsync(planes[0], strides[0], q.p0, pp, row_bytes[0], rows[0], hipMemcpyDeviceToHost, stream_));
+    if (n_planes == 2) VP_HIP_CHECK(hipMemcpy2DAsync(planes[1], strides[1], q.p1, pp, row_bytes[1], rows[1], hipMemcpyDeviceToHost, stream_));
+  }
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 

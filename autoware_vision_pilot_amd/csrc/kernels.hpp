@@ -58,6 +58,60 @@ struct FrameToBgrParams {
 };
 hipError_t launch_frame_to_bgr8(const FrameToBgrParams& p, hipStream_t st);
 
+// vp_canvas (include/vp_hip.h): one BGR8 picture per camera frame with the geometry and pitch of a vp_frame's image (rows frame_bgr_pitch(w) apart, base and
+// pitch multiples of 4), drawn into IN PLACE.  Every kernel below gives one work-item an aligned four-pixel block of a canvas row -- three 32-bit words
+// in, three out -- and leaves the pixels of the block it does not own as it read them (a region's odd edge, the zero bytes behind a row's end).
+// canvas_blend_kernel: viz_blend_kernel's label -> LUT -> 50/50 blend on the region (x0, y0, w, h) of the canvas; ytab [h] / xtab [w]: nearest tables
+// of the region's size into the mh x mw label mask.
+struct CanvasBlendParams {
+  const uint8_t* mask;
+  int mw;
+  const int* ytab;
+  const int* xtab;
+  const uint8_t* lut;   // [256][3] BGR
+  uint8_t* canvas;
+  int pitch;
+  int x0, y0, w, h;
+};
+hipError_t launch_canvas_blend(const CanvasBlendParams& p, int canvas_h, int canvas_w, hipStream_t st);
+// canvas_boxes_kernel: up to kCanvasBoxChunk boxes per launch, walked IN ORDER by every work-item over its own pixels, so the result is the sequential
+// one with one read and one write per pixel.  A box is the inclusive rectangle [x0, x1] x [y0, y1] before clipping (it may reach outside the canvas):
+// its one-pixel outline takes the colour, its interior d = (colour + 4 d) / 5 rounded to nearest (never a tie).  ux / uy: the union of the clipped
+// boxes, the pixels the launch visits.
+constexpr int kCanvasBoxChunk = 64;
+struct CanvasBox {
+  int x0, y0, x1, y1;
+  unsigned bgr;         // b | g << 8 | r << 16
+};
+struct CanvasBoxParams {
+  uint8_t* canvas;
+  int pitch;
+  int ux0, uy0, ux1, uy1;
+  int n;
+  CanvasBox box[kCanvasBoxChunk];
+};
+hipError_t launch_canvas_boxes(const CanvasBoxParams& p, int canvas_h, int canvas_w, hipStream_t st);
+// canvas_to_format_kernel: the inverse of frame_to_bgr8_kernel -- the same four-pixel blocks, row pairs for NV12, chroma of the even pixel (NV12: of
+// the top-left pixel of the 2x2 block).  The planes are the canvas's own staging: rows canvas_plane_pitch(format, w) apart, whole words stored, bytes
+// behind a row's end zero.  BGR8 needs no kernel.  Forward BT.601 limited range, 20 fractional bits: include/vp_hip.h vp_canvas_fetch.
+inline int canvas_plane_pitch(int format, int w) {
+  static const int block_bytes[kFrameFormats] = {12, 12, 16, 16, 4, 4, 8, 8};   // of four pixels
+  return block_bytes[format] * ((w + 3) / 4);
+}
+struct CanvasToFormatParams {
+  const uint8_t* src;
+  int src_pitch;
+  int h, w;
+  int format;
+  uint8_t* p0;
+  uint8_t* p1;          // NV12: interleaved UV, rows dst_pitch apart as well
+  int dst_pitch;        // canvas_plane_pitch(format, w)
+};
+hipError_t launch_canvas_to_format(const CanvasToFormatParams& p, hipStream_t st);
+// depth_colorize_kernel's value -> u8 -> table step, written into the region (x0, y0, w, h) of the canvas instead of a packed image; src: [h][w] fp32
+hipError_t launch_canvas_depth(const float* src, const unsigned* mm, const uint8_t* lut, uint8_t* canvas, int pitch, int x0, int y0, int w, int h,
+                               int canvas_h, int canvas_w, hipStream_t st);
+
 struct StemParams {
   const float* in;  // [3][H][W]
   int H, W;         // input size (output is H/2 x W/2)

@@ -388,6 +388,10 @@ __global__ __launch_bounds__(256) void decode_mask_kernel(const float* logits, i
 // (createColorMask :41-58; label values not listed stay black), cv::resize INTER_NEAREST to the frame size (:21-25),
 // cv::addWeighted(color, 0.5, frame, 0.5, 0) (:29) = saturate_cast<uchar>(cvRound(0.5*a + 0.5*b)): both halves are exact
 // in float, cvRound rounds half to even -> (a+b)>>1, plus 1 when the sum is odd and that half is odd.
+__device__ __forceinline__ unsigned blend_half_even(unsigned a, unsigned b) {
+  const unsigned s2 = a + b, h = s2 >> 1;
+  return (s2 & 1) ? h + (h & 1) : h;
+}
 __global__ __launch_bounds__(256) void viz_blend_kernel(const uint8_t* mask, int mw, const int* ytab, const int* xtab, const uint8_t* frame,
                                                         int stride, int oh, int ow, const uint8_t* lut /* [256][3] BGR */, int frame_is_rgb,
                                                         uint8_t* dst) {
@@ -398,9 +402,7 @@ __global__ __launch_bounds__(256) void viz_blend_kernel(const uint8_t* mask, int
   uint8_t* d = dst + ((size_t)y * ow + x) * 3;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const int a = lut[label * 3 + c], b = f[frame_is_rgb ? 2 - c : c];
-    const int s2 = a + b, h = s2 >> 1;
-    d[c] = (uint8_t)((s2 & 1) ? h + (h & 1) : h);
+    d[c] = (uint8_t)blend_half_even(lut[label * 3 + c], f[frame_is_rgb ? 2 - c : c]);
   }
 }
 
@@ -494,20 +496,169 @@ __global__ __launch_bounds__(256) void minmax_f32_kernel(const float* src, size_
 
 // u8 = saturate(cvRound(x * alpha + beta)) with alpha, beta formed in double and applied in float, as cv::Mat::convertTo does
 // (fused multiply-add, the AVX2 / NEON build's v_fma; cvRound = round-half-even), then the 256 x BGR table.
+__device__ __forceinline__ int depth_level(float x, float mn, float mx) {
+  if (!(mx > mn)) return 0;
+  const double range = (double)mx - (double)mn;
+  const float a = (float)(255.0 / range), b = (float)(-(double)mn * 255.0 / range);
+  const int r = __float2int_rn(__builtin_fmaf(x, a, b));
+  return r < 0 ? 0 : (r > 255 ? 255 : r);
+}
 __global__ __launch_bounds__(256) void depth_colorize_kernel(const float* src, size_t n, const unsigned* mm, const uint8_t* lut, uint8_t* dst) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float mn = f32_from_order_key(mm[0]), mx = f32_from_order_key(mm[1]);
-  int v = 0;
-  if (mx > mn) {
-    const double range = (double)mx - (double)mn;
-    const float a = (float)(255.0 / range), b = (float)(-(double)mn * 255.0 / range);
-    const int r = __float2int_rn(__builtin_fmaf(src[i], a, b));
-    v = r < 0 ? 0 : (r > 255 ? 255 : r);
-  }
+  const int v = depth_level(src[i], f32_from_order_key(mm[0]), f32_from_order_key(mm[1]));
   dst[3 * i] = lut[3 * v];
   dst[3 * i + 1] = lut[3 * v + 1];
   dst[3 * i + 2] = lut[3 * v + 2];
+}
+
+// ------------------------------------------------------------------------------------------ vp_canvas: overlays drawn in place
+// kernels.hpp CanvasBlendParams: a work-item owns the aligned four-pixel block j of a canvas row, reads its three words, changes the pixels that are
+// its to change and stores the three words again.  One work-item per block and launches in stream order: the pixels it merely carries are not raced for.
+__device__ __forceinline__ void load_bgr4(const uint8_t* row, int j, unsigned px[4]) {
+  const uint32_t* s = reinterpret_cast<const uint32_t*>(row + 12 * (size_t)j);
+  const unsigned a = s[0], b = s[1], c = s[2];
+  px[0] = a & 0xFFFFFFu;
+  px[1] = (a >> 24) | ((b & 0xFFFFu) << 8);
+  px[2] = (b >> 16) | ((c & 0xFFu) << 16);
+  px[3] = c >> 8;
+}
+// the mask overlay of viz_blend_kernel on a region: same label, same LUT, same blend; the frame is the canvas itself and always BGR
+__global__ __launch_bounds__(256) void canvas_blend_kernel(const CanvasBlendParams p) {
+  const int jb0 = p.x0 >> 2, nb = ((p.x0 + p.w - 1) >> 2) - jb0 + 1;
+  const int i = blockIdx.x * 256 + threadIdx.x, ry = blockIdx.y;
+  if (i >= nb) return;
+  const int j = jb0 + i;
+  uint8_t* row = p.canvas + (size_t)(p.y0 + ry) * p.pitch;
+  const uint8_t* mrow = p.mask + (size_t)p.ytab[ry] * p.mw;
+  unsigned px[4];
+  load_bgr4(row, j, px);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int rx = 4 * j + k - p.x0;
+    if (rx < 0 || rx >= p.w) continue;   // the region's edge inside a block: carried, not drawn
+    const uint8_t* c = p.lut + 3 * (int)mrow[p.xtab[rx]];
+    px[k] = blend_half_even(c[0], px[k] & 255u) | (blend_half_even(c[1], (px[k] >> 8) & 255u) << 8) | (blend_half_even(c[2], px[k] >> 16) << 16);
+  }
+  store_bgr4(row, j, px);
+}
+// drawUntrackedDetection's box (autospeed_visualization_engine.cpp:126-140) without the text, kernels.hpp CanvasBoxParams
+__device__ __forceinline__ unsigned fill_fifth(unsigned colour, unsigned d) { return (2u * colour + 8u * d + 5u) / 10u; }   // nearest to (colour + 4 d) / 5
+__global__ __launch_bounds__(256) void canvas_boxes_kernel(const CanvasBoxParams p) {
+  const int jb0 = p.ux0 >> 2, nb = (p.ux1 >> 2) - jb0 + 1;
+  const int i = blockIdx.x * 256 + threadIdx.x, y = p.uy0 + (int)blockIdx.y;
+  if (i >= nb) return;
+  const int j = jb0 + i;
+  uint8_t* row = p.canvas + (size_t)y * p.pitch;
+  unsigned px[4];
+  load_bgr4(row, j, px);
+  for (int b = 0; b < p.n; ++b) {
+    const CanvasBox q = p.box[b];
+    if (y < q.y0 || y > q.y1) continue;
+    const bool yedge = y == q.y0 || y == q.y1;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int x = 4 * j + k;
+      if (x < q.x0 || x > q.x1 || x < p.ux0 || x > p.ux1) continue;   // ux: inside the canvas
+      if (yedge || x == q.x0 || x == q.x1)
+        px[k] = q.bgr;
+      else
+        px[k] = fill_fifth(q.bgr & 255u, px[k] & 255u) | (fill_fifth((q.bgr >> 8) & 255u, (px[k] >> 8) & 255u) << 8) |
+                (fill_fifth(q.bgr >> 16, px[k] >> 16) << 16);
+    }
+  }
+  store_bgr4(row, j, px);
+}
+// depth_colorize_kernel into a region of the canvas (opaque)
+__global__ __launch_bounds__(256) void canvas_depth_kernel(const float* src, const unsigned* mm, const uint8_t* lut, uint8_t* canvas, int pitch, int x0,
+                                                           int y0, int w, int h) {
+  const int jb0 = x0 >> 2, nb = ((x0 + w - 1) >> 2) - jb0 + 1;
+  const int i = blockIdx.x * 256 + threadIdx.x, ry = blockIdx.y;
+  if (i >= nb) return;
+  const int j = jb0 + i;
+  const float mn = f32_from_order_key(mm[0]), mx = f32_from_order_key(mm[1]);
+  uint8_t* row = canvas + (size_t)(y0 + ry) * pitch;
+  unsigned px[4];
+  load_bgr4(row, j, px);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int rx = 4 * j + k - x0;
+    if (rx < 0 || rx >= w) continue;
+    const uint8_t* c = lut + 3 * depth_level(src[(size_t)ry * w + rx], mn, mx);
+    px[k] = (unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16);
+  }
+  store_bgr4(row, j, px);
+}
+// Canvas -> a vp_frame format (kernels.hpp CanvasToFormatParams).  Forward BT.601 limited range, the integer counterpart of the upload formula above
+// (include/vp_hip.h states it as the DEFINITION; not pinned against OpenCV):
+//   Y = sat8((269484 R + 528482 G + 102760 B + (16 << 20) + 2^19) >> 20)
+//   U = sat8((-155188 R - 305135 G + 460324 B + (128 << 20) + 2^19) >> 20),  V = sat8((460324 R - 385875 G - 74448 B + (128 << 20) + 2^19) >> 20)
+__device__ __forceinline__ unsigned luma_of(unsigned px) {
+  const int b = px & 255u, g = (px >> 8) & 255u, r = px >> 16;
+  return sat8((269484 * r + 528482 * g + 102760 * b + (16 << 20) + (1 << 19)) >> 20);
+}
+// U | V << 8
+__device__ __forceinline__ unsigned chroma_of(unsigned px) {
+  const int b = px & 255u, g = (px >> 8) & 255u, r = px >> 16;
+  return sat8((-155188 * r - 305135 * g + 460324 * b + (128 << 20) + (1 << 19)) >> 20) |
+         (sat8((460324 * r - 385875 * g - 74448 * b + (128 << 20) + (1 << 19)) >> 20) << 8);
+}
+__device__ __forceinline__ unsigned swap_rb(unsigned px) { return (px & 0x00FF00u) | (px >> 16) | ((px & 255u) << 16); }
+__global__ __launch_bounds__(256) void canvas_to_format_kernel(const CanvasToFormatParams p) {
+  const int bpr = (p.w + 3) >> 2;
+  const int rows = p.format == 5 ? p.h >> 1 : p.h;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)rows * bpr) return;
+  const int r = (int)(t / bpr), j = (int)(t - (long long)r * bpr), x0 = 4 * j;
+  const size_t pitch = (size_t)p.dst_pitch;
+  unsigned px[4];
+  if (p.format == 5) {   // NV12: rows 2r, 2r + 1; chroma of the top-left pixel of each 2x2 block
+    unsigned px1[4], y0 = 0u, y1 = 0u, uv = 0u;
+    load_bgr4(p.src + (size_t)(2 * r) * p.src_pitch, j, px);
+    load_bgr4(p.src + (size_t)(2 * r + 1) * p.src_pitch, j, px1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (x0 + k >= p.w) break;
+      y0 |= luma_of(px[k]) << (8 * k);
+      y1 |= luma_of(px1[k]) << (8 * k);
+      if (!(k & 1)) uv |= chroma_of(px[k]) << (8 * k);
+    }
+    *reinterpret_cast<uint32_t*>(p.p0 + (size_t)(2 * r) * pitch + 4 * (size_t)j) = y0;
+    *reinterpret_cast<uint32_t*>(p.p0 + (size_t)(2 * r + 1) * pitch + 4 * (size_t)j) = y1;
+    *reinterpret_cast<uint32_t*>(p.p1 + (size_t)r * pitch + 4 * (size_t)j) = uv;
+    return;
+  }
+  load_bgr4(p.src + (size_t)r * p.src_pitch, j, px);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (x0 + k >= p.w) px[k] = 0u;   // behind the row's end: zero bytes out, whatever the canvas carries there
+  uint8_t* drow = p.p0 + (size_t)r * pitch;
+  if (p.format >= 6) {   // YUY2: Y0 U Y1 V; UYVY: U Y0 V Y1 -- one word per pixel pair, chroma of the even pixel
+    uint32_t* d = reinterpret_cast<uint32_t*>(drow + 8 * (size_t)j);
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      unsigned wd = 0u;
+      if (x0 + 2 * g < p.w) {
+        const unsigned ya = luma_of(px[2 * g]), yb = luma_of(px[2 * g + 1]), c = chroma_of(px[2 * g]);
+        wd = p.format == 6 ? (ya | ((c & 255u) << 8) | (yb << 16) | ((c >> 8) << 24)) : ((c & 255u) | (ya << 8) | ((c >> 8) << 16) | (yb << 24));
+      }
+      d[g] = wd;
+    }
+  } else if (p.format == 4) {   // GRAY8 = Y
+    unsigned wd = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (x0 + k < p.w) wd |= luma_of(px[k]) << (8 * k);
+    *reinterpret_cast<uint32_t*>(drow + 4 * (size_t)j) = wd;
+  } else if (p.format >= 2) {   // BGRA8 / RGBA8: alpha 255
+    uint32_t* d = reinterpret_cast<uint32_t*>(drow + 16 * (size_t)j);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = x0 + k < p.w ? ((p.format == 3 ? swap_rb(px[k]) : px[k]) | 0xFF000000u) : 0u;
+  } else {                      // RGB8 (BGR8 is copied, not converted)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) px[k] = swap_rb(px[k]);
+    store_bgr4(drow, j, px);
+  }
 }
 
 // ----------------------------------------------------------------------------------- layout conversions
@@ -702,6 +853,37 @@ hipError_t launch_depth_colorize(const float* src, size_t n, const unsigned* mm,
 hipError_t launch_resize_bilinear_f32(const float* src, int sw, const int* yi, const float* yf, const int* xi, const float* xf,
                                       int oh, int ow, float* dst, hipStream_t st) {
   VP_LAUNCH(resize_bilinear_f32_kernel, dim3(nblk(ow), oh), dim3(256), 0, st, src, sw, yi, yf, xi, xf, oh, ow, dst);
+}
+// a region drawn in place: inside the canvas, the canvas with the pitch and alignment the three-word blocks need
+static bool canvas_region_ok(const uint8_t* canvas, int pitch, int canvas_h, int canvas_w, int x0, int y0, int w, int h) {
+  return canvas && canvas_h >= 1 && canvas_w >= 1 && pitch >= frame_bgr_pitch(canvas_w) && !(pitch & 3) && !(reinterpret_cast<uintptr_t>(canvas) & 3) && x0 >= 0 &&
+         y0 >= 0 && w >= 1 && h >= 1 && (long long)x0 + w <= canvas_w && (long long)y0 + h <= canvas_h;
+}
+hipError_t launch_canvas_blend(const CanvasBlendParams& p, int canvas_h, int canvas_w, hipStream_t st) {
+  if (!p.mask || !p.ytab || !p.xtab || !p.lut || p.mw < 1 || !canvas_region_ok(p.canvas, p.pitch, canvas_h, canvas_w, p.x0, p.y0, p.w, p.h)) return hipErrorInvalidValue;
+  const int nb = ((p.x0 + p.w - 1) >> 2) - (p.x0 >> 2) + 1;
+  VP_LAUNCH(canvas_blend_kernel, dim3(nblk(nb), p.h), dim3(256), 0, st, p);
+}
+hipError_t launch_canvas_boxes(const CanvasBoxParams& p, int canvas_h, int canvas_w, hipStream_t st) {
+  if (p.n < 1 || p.n > kCanvasBoxChunk || p.ux1 < p.ux0 || p.uy1 < p.uy0 ||
+      !canvas_region_ok(p.canvas, p.pitch, canvas_h, canvas_w, p.ux0, p.uy0, p.ux1 - p.ux0 + 1, p.uy1 - p.uy0 + 1))
+    return hipErrorInvalidValue;
+  const int nb = (p.ux1 >> 2) - (p.ux0 >> 2) + 1;
+  VP_LAUNCH(canvas_boxes_kernel, dim3(nblk(nb), p.uy1 - p.uy0 + 1), dim3(256), 0, st, p);
+}
+hipError_t launch_canvas_depth(const float* src, const unsigned* mm, const uint8_t* lut, uint8_t* canvas, int pitch, int x0, int y0, int w, int h,
+                               int canvas_h, int canvas_w, hipStream_t st) {
+  if (!src || !mm || !lut || !canvas_region_ok(canvas, pitch, canvas_h, canvas_w, x0, y0, w, h)) return hipErrorInvalidValue;
+  const int nb = ((x0 + w - 1) >> 2) - (x0 >> 2) + 1;
+  VP_LAUNCH(canvas_depth_kernel, dim3(nblk(nb), h), dim3(256), 0, st, src, mm, lut, canvas, pitch, x0, y0, w, h);
+}
+hipError_t launch_canvas_to_format(const CanvasToFormatParams& p, hipStream_t st) {
+  const bool pairs = p.format >= 5;
+  if (!p.src || !p.p0 || p.format < 1 || p.format >= kFrameFormats || p.h < 1 || p.w < 1 || (pairs && (p.w & 1)) || (p.format == 5 && (!p.p1 || (p.h & 1))) ||
+      p.src_pitch < frame_bgr_pitch(p.w) || (p.src_pitch & 3) || p.dst_pitch != canvas_plane_pitch(p.format, p.w) || ((reinterpret_cast<uintptr_t>(p.src) | reinterpret_cast<uintptr_t>(p.p0) | reinterpret_cast<uintptr_t>(p.p1)) & 3))
+    return hipErrorInvalidValue;
+  const long long n = (long long)(p.format == 5 ? p.h / 2 : p.h) * ((p.w + 3) / 4);
+  VP_LAUNCH(canvas_to_format_kernel, dim3(nblk(n)), dim3(256), 0, st, p);
 }
 hipError_t launch_nchw_to_act(const float* src, int Creal, const ActView& a, hipStream_t st) {
   VP_LAUNCH(nchw_to_act_kernel, dim3(nblk((long long)a.H * a.W * a.C)), dim3(256), 0, st, src, Creal, a);

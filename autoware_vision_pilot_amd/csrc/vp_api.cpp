@@ -549,26 +549,35 @@ struct FramePlanes {
   int rows[2] = {0, 0};
 };
 
-// the refusals of vp_frame_upload*, and the planes the format has
-FramePlanes check_frame_planes(const char* who, int format, const void* const* planes, const int* strides, int n_planes, int h, int w) {
-  static const char* const names[vp::kFrameFormats] = {"BGR8", "RGB8", "BGRA8", "RGBA8", "GRAY8", "NV12", "YUY2", "UYVY"};
+const char* const kFormatNames[vp::kFrameFormats] = {"BGR8", "RGB8", "BGRA8", "RGBA8", "GRAY8", "NV12", "YUY2", "UYVY"};
+
+// the planes an h x w image has in `format` (vp_frame_upload*, vp_canvas_layout / vp_canvas_fetch), and the refusals of the geometry
+FramePlanes frame_layout(const std::string& me, int format, int h, int w) {
   static const int px_bytes[vp::kFrameFormats] = {3, 3, 4, 4, 1, 1, 2, 2};
-  const std::string me(who);
   if (format < 0 || format >= vp::kFrameFormats) throw std::invalid_argument(me + ": unknown format " + std::to_string(format));
-  const std::string fmt = names[format];
-  FramePlanes fp;
-  fp.n = format == VP_FRAME_NV12 ? 2 : 1;
-  if (n_planes != fp.n) throw std::invalid_argument(me + ": " + fmt + " has " + std::to_string(fp.n) + " plane(s), got n_planes = " + std::to_string(n_planes));
-  if (!planes || !strides) throw std::invalid_argument(me + ": null planes / strides");
+  const std::string fmt = kFormatNames[format];
   if (h < 2 || w < 2 || h > 16384 || w > 16384) throw std::invalid_argument(me + ": frame size " + std::to_string(w) + " x " + std::to_string(h) + " (2 .. 16384 each way)");
   if (format >= VP_FRAME_NV12 && (w & 1)) throw std::invalid_argument(me + ": " + fmt + " needs an even width (one chroma pair per two pixels), got " + std::to_string(w));
   if (format == VP_FRAME_NV12 && (h & 1)) throw std::invalid_argument(me + ": NV12 needs an even height (one chroma pair per 2x2 block), got " + std::to_string(h));
+  FramePlanes fp;
+  fp.n = format == VP_FRAME_NV12 ? 2 : 1;
   fp.row_bytes[0] = (size_t)px_bytes[format] * w;
   fp.rows[0] = h;
   if (fp.n == 2) {
     fp.row_bytes[1] = (size_t)w;   // w / 2 interleaved (U, V) pairs
     fp.rows[1] = h / 2;
   }
+  return fp;
+}
+
+// the refusals of vp_frame_upload* / vp_canvas_fetch, and the planes the format has
+FramePlanes check_frame_planes(const char* who, int format, const void* const* planes, const int* strides, int n_planes, int h, int w) {
+  const std::string me(who);
+  if (format < 0 || format >= vp::kFrameFormats) throw std::invalid_argument(me + ": unknown format " + std::to_string(format));
+  const int n = format == VP_FRAME_NV12 ? 2 : 1;
+  if (n_planes != n) throw std::invalid_argument(me + ": " + kFormatNames[format] + " has " + std::to_string(n) + " plane(s), got n_planes = " + std::to_string(n_planes));
+  if (!planes || !strides) throw std::invalid_argument(me + ": null planes / strides");
+  const FramePlanes fp = frame_layout(me, format, h, w);
   for (int i = 0; i < fp.n; ++i) {
     if (!planes[i]) throw std::invalid_argument(me + ": plane " + std::to_string(i) + " is null");
     if (strides[i] < 0 || (size_t)strides[i] < fp.row_bytes[i])
@@ -754,6 +763,153 @@ int vp_infer_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h) {
     g.fetch_outputs();
   });
 }
+
+// ---- vp_canvas: one picture per camera frame (include/vp_hip.h; vp::Canvas: engine.hpp / engine_io.cpp; kernels: kernels_misc.hip canvas_*)
+}  // extern "C"
+
+namespace {
+
+template <class F>
+int canvas_guarded(vp_canvas* c, F&& fn) {
+  if (!c || !c->impl) return VP_ERR_ARG;
+  try {
+    fn(*c->impl);
+    return VP_OK;
+  } catch (const std::invalid_argument& ex) {
+    c->err = ex.what();
+    return VP_ERR_ARG;
+  } catch (const std::exception& ex) {
+    c->err = ex.what();
+    return std::strncmp(ex.what(), "HIP error", 9) == 0 ? VP_ERR_HIP : VP_ERR_STATE;
+  }
+}
+
+// drawUntrackedDetection's rectangle (autospeed_visualization_engine.cpp:131-132) and getColorByClass's colour: float subtraction, truncation toward
+// zero; false: nothing to draw.  Coordinates the int conversion cannot hold (a detector clamps to the frame: never its output) are refused by the caller.
+bool detection_box(const vp_detection& d, vp::CanvasBox* b) {
+  const int bx = (int)d.x1, by = (int)d.y1, bw = (int)(d.x2 - d.x1), bh = (int)(d.y2 - d.y1);
+  if (bw <= 0 || bh <= 0) return false;
+  b->x0 = bx;
+  b->y0 = by;
+  b->x1 = bx + bw - 1;
+  b->y1 = by + bh - 1;
+  b->bgr = d.class_id == 1 ? 0xFF0000u : d.class_id == 2 ? 0xFFFF00u : d.class_id == 3 ? 0x00FFFFu : 0xFFFFFFu;   // b | g << 8 | r << 16
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vp_canvas_create(vp_canvas** out, int gpu_id, char* err, size_t err_len) {
+  if (!out) return VP_ERR_ARG;
+  *out = nullptr;
+  try {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) throw std::runtime_error("HIP error: no HIP device visible: a vp_canvas lives on the device");
+    if (gpu_id < 0 || gpu_id >= n) throw std::invalid_argument("gpu_id out of range");
+    auto c = std::make_unique<vp_canvas>();
+    c->impl = std::make_unique<vp::Canvas>(gpu_id);
+    *out = c.release();
+    return VP_OK;
+  } catch (const std::invalid_argument& ex) {
+    set_err(err, err_len, ex.what());
+    return VP_ERR_ARG;
+  } catch (const std::exception& ex) {
+    set_err(err, err_len, ex.what());
+    return VP_ERR_HIP;
+  }
+}
+
+void vp_canvas_destroy(vp_canvas* c) { delete c; }
+
+const char* vp_canvas_last_error(const vp_canvas* c) { return c ? c->err.c_str() : "null canvas"; }
+
+int vp_canvas_begin(vp_canvas* c, vp_frame* f) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (!f) throw std::invalid_argument("vp_canvas_begin: null frame");
+    g.begin(f->view());
+    f->note_consumer(g.stream());   // the next upload into the frame waits for this copy, on the device
+  });
+}
+
+int vp_canvas_blend_mask(vp_canvas* c, vp_engine* e, int viz_type) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (!e || !e->impl) throw std::invalid_argument("vp_canvas_blend_mask: null engine");
+    g.blend_mask(*e->impl, viz_type);
+  });
+}
+
+int vp_canvas_blend_mask_u8(vp_canvas* c, const uint8_t* mask, int mask_on_device, int mh, int mw, int viz_type, int x0, int y0, int w, int h) {
+  return canvas_guarded(c, [&](vp::Canvas& g) { g.blend_mask_u8(mask, mask_on_device != 0, mh, mw, viz_type, x0, y0, w, h); });
+}
+
+int vp_canvas_paste_depth(vp_canvas* c, vp_engine* e) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (!e || !e->impl) throw std::invalid_argument("vp_canvas_paste_depth: null engine");
+    g.paste_depth(*e->impl);
+  });
+}
+
+int vp_canvas_draw_detections(vp_canvas* c, const vp_detection* dets, int n) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (n < 0 || (n > 0 && !dets)) throw std::invalid_argument("vp_canvas_draw_detections: n < 0, or null detections with n > 0");
+    std::vector<vp::CanvasBox> boxes;
+    boxes.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      const vp_detection& d = dets[i];
+      for (float v : {d.x1, d.y1, d.x2, d.y2})
+        if (!(v > -1e8f && v < 1e8f)) throw std::invalid_argument("vp_canvas_draw_detections: detection " + std::to_string(i) + " has a coordinate that is not a pixel position");
+      vp::CanvasBox b;
+      if (detection_box(d, &b)) boxes.push_back(b);
+    }
+    g.draw_boxes(boxes.data(), (int)boxes.size());
+  });
+}
+
+int vp_canvas_sync(vp_canvas* c) {
+  return canvas_guarded(c, [&](vp::Canvas& g) { g.sync(); });
+}
+
+int vp_canvas_dims(const vp_canvas* c, int* h, int* w) {
+  if (!c || !c->impl || !h || !w) return VP_ERR_ARG;
+  if (!c->impl->begun()) return VP_ERR_STATE;
+  *h = c->impl->h();
+  *w = c->impl->w();
+  return VP_OK;
+}
+
+int vp_canvas_device(const vp_canvas* c, void** dev_bgr8, int* pitch_bytes) {
+  if (!c || !c->impl || !dev_bgr8 || !pitch_bytes) return VP_ERR_ARG;
+  if (!c->impl->begun()) return VP_ERR_STATE;
+  *dev_bgr8 = c->impl->device();
+  *pitch_bytes = c->impl->pitch();
+  return VP_OK;
+}
+
+int vp_canvas_layout(int format, int h, int w, int* n_planes, int row_bytes[2], int rows[2]) {
+  if (!n_planes || !row_bytes || !rows) return VP_ERR_ARG;
+  try {
+    const FramePlanes fp = frame_layout("vp_canvas_layout", format, h, w);
+    *n_planes = fp.n;
+    for (int i = 0; i < 2; ++i) {
+      row_bytes[i] = (int)fp.row_bytes[i];
+      rows[i] = fp.rows[i];
+    }
+    return VP_OK;
+  } catch (const std::exception&) {
+    return VP_ERR_ARG;
+  }
+}
+
+int vp_canvas_fetch(vp_canvas* c, int format, uint8_t* const* planes, const int* strides, int n_planes) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (!g.begun()) throw std::runtime_error("vp_canvas_fetch: the canvas holds no picture (vp_canvas_begin first)");
+    const FramePlanes fp = check_frame_planes("vp_canvas_fetch", format, reinterpret_cast<const void* const*>(planes), strides, n_planes, g.h(), g.w());
+    g.fetch(format, planes, strides, fp.row_bytes, fp.rows, fp.n);
+  });
+}
+
 int vp_sync(vp_engine* e) {
   return guarded(e, [&](vp::Engine& g) { g.sync(); });
 }

@@ -49,3 +49,9 @@ struct vp_frame {
   void note_consumer(hipStream_t s);   // behind a consumer's copy, on the consumer's stream
   void wait_for_consumers();           // ahead of an upload, on the frame's stream
 };
+
+// vp_canvas: one picture per camera frame, composed on the device (vp::Canvas, engine.hpp / engine_io.cpp; C ABI: vp_api.cpp).  One thread drives it.
+struct vp_canvas {
+  std::unique_ptr<vp::Canvas> impl;
+  std::string err;
+};

@@ -162,6 +162,19 @@ _SIGS = {
     "vp_upload_from_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vp_infer_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vp_detect_infer_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
+    "vp_canvas_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_size_t]),
+    "vp_canvas_destroy": (None, [_P]),
+    "vp_canvas_last_error": (C.c_char_p, [_P]),
+    "vp_canvas_begin": (C.c_int, [_P, _P]),
+    "vp_canvas_blend_mask": (C.c_int, [_P, _P, C.c_int]),
+    "vp_canvas_blend_mask_u8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vp_canvas_paste_depth": (C.c_int, [_P, _P]),
+    "vp_canvas_draw_detections": (C.c_int, [_P, _P, C.c_int]),
+    "vp_canvas_sync": (C.c_int, [_P]),
+    "vp_canvas_dims": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vp_canvas_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int)]),
+    "vp_canvas_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vp_canvas_fetch": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int]),
 }
 # multi-camera exchange (csrc/vp_comm.cpp): part of libvp_hip.so, absent from the CPU-emulated test build
 _COMM_SIGS = {
@@ -183,6 +196,7 @@ VP_GATHER_MASK, VP_GATHER_LOGITS = 0, 1
 VP_COMM_ID_BYTES = 128
 
 VP_RANGE_BINS, VP_RANGE_EXP_MIN = 40, -24
+VP_VIZ_SCENE, VP_VIZ_DOMAIN, VP_VIZ_EGOLANES = 0, 1, 2
 VP_FRAME_BGR8, VP_FRAME_RGB8, VP_FRAME_BGRA8, VP_FRAME_RGBA8, VP_FRAME_GRAY8, VP_FRAME_NV12, VP_FRAME_YUY2, VP_FRAME_UYVY = range(8)
 FRAME_FORMATS = {"bgr8": VP_FRAME_BGR8, "rgb8": VP_FRAME_RGB8, "bgra8": VP_FRAME_BGRA8, "rgba8": VP_FRAME_RGBA8, "gray8": VP_FRAME_GRAY8, "nv12": VP_FRAME_NV12,
                  "yuy2": VP_FRAME_YUY2, "uyvy": VP_FRAME_UYVY}
@@ -773,6 +787,110 @@ class Frame:
         out = np.empty((h, w, 3), np.uint8)
         self._ck(self._lib.vp_frame_fetch_bgr8(self._h, _ptr(out), out.strides[0]))
         return out
+
+
+def canvas_layout(fmt, h, w):
+    """vp_canvas_layout (host only): [(bytes per row, rows)] of each plane an h x w picture has in `fmt`; ValueError for a geometry the format refuses."""
+    n = C.c_int()
+    rb, rows = (C.c_int * 2)(), (C.c_int * 2)()
+    if load().vp_canvas_layout(Frame._fmt(fmt), int(h), int(w), C.byref(n), rb, rows) != 0:
+        raise ValueError(f"vp_canvas_layout: no {fmt} layout for a {w} x {h} picture")
+    return [(rb[i], rows[i]) for i in range(n.value)]
+
+
+class Canvas:
+    """vp_canvas: one picture per camera frame, composed on the device.  begin(frame) copies the Frame's BGR8 picture; every Engine (heads included)
+    blends its mask or pastes its depth map into the region its input came from; detections are drawn as boxes; fetch(fmt) returns the picture once,
+    in any Frame format.  One thread drives a canvas (include/vp_hip.h)."""
+
+    def __init__(self, gpu_id=0):
+        self._lib = load()
+        self._h = _P()
+        err = C.create_string_buffer(512)
+        rc = self._lib.vp_canvas_create(C.byref(self._h), gpu_id, err, len(err))
+        if rc != 0:
+            self._h = None
+            raise (ValueError if rc == -1 else VpError)(f"vp_canvas_create failed ({rc}): {err.value.decode(errors='replace')}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vp_canvas_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _ck(self, rc):
+        if rc < 0:
+            msg = self._lib.vp_canvas_last_error(self._h).decode(errors="replace")
+            raise (ValueError if rc == -1 else VpError)(f"libvp_hip canvas error {rc}: {msg}")
+        return rc
+
+    def begin(self, frame):
+        self._ck(self._lib.vp_canvas_begin(self._h, frame._h))
+
+    def blend_mask(self, engine, viz_type=VP_VIZ_SCENE):
+        self._ck(self._lib.vp_canvas_blend_mask(self._h, engine._h, int(viz_type)))
+
+    def blend_mask_u8(self, mask, viz_type, region, device_hw=None):
+        """mask: an HxW uint8 array, or (with device_hw = (mh, mw)) a device pointer (int); region: (x0, y0, w, h) of the canvas"""
+        x0, y0, w, h = (int(v) for v in region)
+        if device_hw is not None:
+            self._ck(self._lib.vp_canvas_blend_mask_u8(self._h, _P(int(mask)), 1, int(device_hw[0]), int(device_hw[1]), int(viz_type), x0, y0, w, h))
+            return
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.ndim != 2:
+            raise ValueError("blend_mask_u8: the mask is an HxW uint8 array")
+        self._ck(self._lib.vp_canvas_blend_mask_u8(self._h, _ptr(m), 0, m.shape[0], m.shape[1], int(viz_type), x0, y0, w, h))
+
+    def paste_depth(self, engine):
+        self._ck(self._lib.vp_canvas_paste_depth(self._h, engine._h))
+
+    def draw_detections(self, rows):
+        """rows: [n][6] x1, y1, x2, y2, confidence, class_id, as Detector.infer / postprocess return them"""
+        r = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 6)
+        rec = r.copy()
+        rec[:, 5].view(np.int32)[:] = r[:, 5].astype(np.int32)   # vp_detection.class_id is an int
+        self._ck(self._lib.vp_canvas_draw_detections(self._h, _ptr(rec) if len(rec) else None, len(rec)))
+
+    def sync(self):
+        self._ck(self._lib.vp_canvas_sync(self._h))
+
+    def hw(self):
+        h, w = C.c_int(), C.c_int()
+        rc = self._lib.vp_canvas_dims(self._h, C.byref(h), C.byref(w))
+        if rc != 0:
+            raise VpError(f"vp_canvas_dims failed ({rc}): the canvas holds no picture yet")
+        return h.value, w.value
+
+    def device(self):
+        """(device pointer of the BGR8 picture, row pitch in bytes): valid until the next begin() / close(), complete after sync()"""
+        p, pitch = _P(), C.c_int()
+        rc = self._lib.vp_canvas_device(self._h, C.byref(p), C.byref(pitch))
+        if rc != 0:
+            raise VpError(f"vp_canvas_device failed ({rc}): the canvas holds no picture yet")
+        return p.value, pitch.value
+
+    def fetch(self, fmt="bgr8", strides=None):
+        """vp_canvas_fetch (synchronous): the picture as numpy planes -- bgr8 / rgb8 HxWx3, bgra8 / rgba8 HxWx4, gray8 HxW, yuy2 / uyvy Hx(2W), nv12 the
+        pair (Y [H][W], UV [H/2][W]).  `strides`: row strides in bytes of the buffers fetched into (default: packed)."""
+        f = Frame._fmt(fmt)
+        h, w = self.hw()
+        n = C.c_int()
+        rb, rows = (C.c_int * 2)(), (C.c_int * 2)()
+        if not 0 <= f < 8 or self._lib.vp_canvas_layout(f, h, w, C.byref(n), rb, rows) != 0:
+            n.value, rb[0], rows[0], rb[1], rows[1] = (2 if f == VP_FRAME_NV12 else 1), 1, 1, 1, 1   # no layout: the library words the refusal
+        st = [int(v) for v in strides] if strides is not None else [rb[i] for i in range(n.value)]
+        bufs = [np.zeros((rows[min(i, 1)], max(st[i], 1)), np.uint8) for i in range(len(st))]
+        arr = (_P * len(bufs))(*[b.ctypes.data for b in bufs])
+        self._ck(self._lib.vp_canvas_fetch(self._h, f, arr, (C.c_int * len(st))(*st), len(st)))
+        planes = [np.ascontiguousarray(b[:, :rb[i]]) for i, b in enumerate(bufs)]
+        if f <= VP_FRAME_RGBA8:
+            planes[0] = planes[0].reshape(h, w, _FRAME_PX_BYTES[f])
+        return planes[0] if len(planes) == 1 else tuple(planes)
 
 
 def decode_logits_host(logits_chw, decode_mode=VP_DECODE_SEG_MASK, gpu_id=0):

@@ -399,6 +399,74 @@ int vp_frame_fetch_bgr8(vp_frame* f, uint8_t* dst, int dst_stride);      /* the 
 int vp_upload_from_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h);
 int vp_infer_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h);
 
+/* ---- vp_canvas: one picture per camera frame, composed on the device, fetched once in any vp_frame format -------------------------
+ * The output side of vp_frame.  MasksVisualizationEngine / DepthVisualizationEngine / AutoSpeedVisualizationEngine each take the host frame and return
+ * one host picture per network (the ROS2 README times the step at 25 ms per frame); vp_visualize_mask_bgr8 / vp_visualize_depth_bgr8 above are their
+ * device twins: one overlay, one host synchronisation and one full-frame D2H per call, base engines only, each blending with its own crop.  A vp_canvas
+ * is ONE picture of the camera frame that every engine -- of any scene kind, shared-prefix heads included -- and the detector draw into on the device:
+ *     vp_canvas_begin(c, f);                                  the canvas becomes a copy of the frame's BGR8 picture (device to device)
+ *     vp_canvas_blend_mask(c, sceneseg, VP_VIZ_SCENE);        each engine draws into the region its input came from
+ *     vp_canvas_paste_depth(c, scene3d_head);  vp_canvas_blend_mask(c, egolanes, VP_VIZ_EGOLANES);  vp_canvas_draw_detections(c, dets, n);
+ *     vp_canvas_fetch(c, VP_FRAME_NV12, planes, strides, 2);  one synchronisation, one D2H, in the format the encoder / display wants
+ * WHERE AN ENGINE DRAWS.  An engine records where its resident input came from: vp_upload_from_frame / vp_infer_frame record the region (x0, y0, w, h)
+ * and the source frame's (H, W); the host uploads (vp_upload_frame*, vp_infer*) record the whole frame, (0, 0, w, h) of (h, w); a shared-prefix head
+ * uses its base's record.  vp_canvas_blend_mask / vp_canvas_paste_depth return VP_ERR_ARG when the recorded (H, W) is not the canvas's geometry (the
+ * text names both), for an engine on another GPU, a tensor-input engine, a batched encoder and the VP_AUTODRIVE / VP_AUTOSPEED / VP_AUTOSTEER kinds (no
+ * mask or depth plane); VP_ERR_STATE ("Inference has not been run yet") before the engine's first pass, and on a canvas without a picture.
+ * vp_canvas_begin: the picture, geometry and row pitch (12 * ceil(w / 4) bytes) of the frame; the copy runs on the canvas's own stream behind the
+ *   frame's "content ready" event and counts as a consumer of the frame: a later vp_frame_upload* orders itself behind it on the device.  VP_ERR_STATE
+ *   for a frame never uploaded, VP_ERR_ARG for a frame on another GPU.  A second begin discards the picture and may change the geometry.
+ * vp_canvas_blend_mask: viz_type as vp_visualize_mask_bgr8 (VP_VIZ_EGOLANES wants VP_DECODE_LANE_LABEL, as there).  The engine's last mask is
+ *   nearest-resized to the region (the index rule of vp_mask_resized_u8, tables of the region's h and w), coloured through the same table and blended
+ *   50 / 50 with the canvas pixels of the region, in place: (a + b) >> 1, odd sums to even.  Pixels outside the region are untouched.  EXACT against
+ *   the existing call: on a fresh canvas the region's bytes equal vp_visualize_mask_bgr8 of a base engine that took that region.
+ * vp_canvas_blend_mask_u8: the operator entry -- the same for a caller's mh x mw u8 label mask (host, or device memory on the canvas's GPU that is
+ *   complete when the call is made) into an explicit region.  VP_ERR_ARG: a region outside the canvas or smaller than 2 x 2, mh or mw < 1.  A host
+ *   mask is copied before the call returns.
+ * vp_canvas_paste_depth: plane 0 of the engine's logits through the pipeline of vp_visualize_depth_bgr8(e, dst, region h, region w) -- bilinear resize
+ *   to the region's size, min-max, the same rounding, the same table -- written opaquely into the region.  EXACT: the region's bytes equal that call's.
+ * vp_canvas_draw_detections: AutoSpeedVisualizationEngine::drawUntrackedDetection (autospeed_visualization_engine.cpp:126-140) without its text.  For
+ *   each detection in order: bx = (int)x1, by = (int)y1, bw = (int)(x2 - x1), bh = (int)(y2 - y1) (float subtraction, truncation toward zero); nothing
+ *   if bw <= 0 or bh <= 0; the inclusive rectangle [bx, bx + bw - 1] x [by, by + bh - 1], clipped to the canvas, gets the 20 % fill
+ *   d = nearest integer to (colour + 4 d) / 5 per channel (never a tie: the fraction is a multiple of 0.2; both float32 spellings of
+ *   addWeighted(overlay, 0.2, frame, 0.8) give it), then the rectangle's one-pixel outline is set to the colour -- the outline of the rectangle BEFORE
+ *   clipping, as cv::rectangle draws it: a side that lies outside the canvas is not drawn, the box stays open there.  Colours by class_id, BGR:
+ *   1 (0, 0, 255), 2 (0, 255, 255), 3 (255, 255, 0), anything else white.  Later boxes draw over earlier ones.  n = 0: nothing; VP_ERR_ARG for
+ *   n < 0, null with n > 0, a non-finite or absurd (|v| >= 1e8) coordinate.  This rule IS the definition; it is not pinned against OpenCV (absent
+ *   here, as for the other OpenCV restatements: DESIGN.md section 4).  Text, the tracked-object style, the CIPO tag and the warnings are not built.
+ * vp_canvas_fetch: synchronous; every vp_frame_format.  BGR8 as it is; RGB8 / BGRA8 / RGBA8 permuted, alpha 255; GRAY8 / NV12 / YUY2 / UYVY by the
+ *   BT.601 limited-range FORWARD form, the integer counterpart of the upload formula above (20 fractional bits, arithmetic shift, clamp 0 .. 255):
+ *     Y = ( 269484 R + 528482 G + 102760 B + (16  << 20) + (1 << 19)) >> 20
+ *     U = (-155188 R - 305135 G + 460324 B + (128 << 20) + (1 << 19)) >> 20
+ *     V = ( 460324 R - 385875 G -  74448 B + (128 << 20) + (1 << 19)) >> 20
+ *   GRAY8 is Y; chroma is taken from the EVEN pixel of a pair (NV12: the top-left pixel of the 2x2 block), no averaging.  Black gives (16, 128, 128),
+ *   white (235, 128, 128), pure red V = 240.  This formula IS the definition; it is not pinned against OpenCV.  Refusals as vp_frame_upload: odd w
+ *   for NV12 / YUY2 / UYVY, odd h for NV12, a stride below the row's bytes, a wrong n_planes, an unknown format.  vp_canvas_layout (host only, no
+ *   device) answers the planes of (format, h, w): n_planes, bytes per row and rows of each; VP_ERR_ARG for the same geometry refusals.
+ * vp_canvas_device / vp_canvas_sync: the device picture (BGR8, rows *pitch_bytes apart) for a device consumer such as an encoder; complete after
+ *   vp_canvas_sync, valid until the next vp_canvas_begin or vp_canvas_destroy.
+ * ORDERING CONTRACT (vp_frame's, in the other direction).  Nothing waits on the host before vp_canvas_fetch / vp_canvas_sync.  A draw call makes the
+ *   canvas's stream wait for the work queued on the engine's stream so far, and the engine's stream wait for the canvas's read of the mask / logits
+ *   before anything queued on it afterwards: `infer A; blend; infer B; fetch` shows A's mask.  The exceptions are once per geometry: a buffer that
+ *   has to grow, and the first use of a resize table of a new (network size, region size) pair, which is uploaded and waited for.
+ * THREADING.  One thread drives a canvas; a draw call is also a call on the engine it names (one thread at a time per engine, as ever).  No
+ *   process-wide state. */
+typedef struct vp_canvas vp_canvas;
+struct vp_detection;   /* the detector's record, defined with the detector below */
+int vp_canvas_create(vp_canvas** out, int gpu_id, char* err, size_t err_len);
+void vp_canvas_destroy(vp_canvas* c);
+const char* vp_canvas_last_error(const vp_canvas* c);
+int vp_canvas_begin(vp_canvas* c, vp_frame* f);
+int vp_canvas_blend_mask(vp_canvas* c, vp_engine* e, int viz_type);
+int vp_canvas_blend_mask_u8(vp_canvas* c, const uint8_t* mask, int mask_on_device, int mh, int mw, int viz_type, int x0, int y0, int w, int h);
+int vp_canvas_paste_depth(vp_canvas* c, vp_engine* e);
+int vp_canvas_draw_detections(vp_canvas* c, const struct vp_detection* dets, int n);
+int vp_canvas_sync(vp_canvas* c);
+int vp_canvas_dims(const vp_canvas* c, int* h, int* w);                  /* VP_ERR_STATE before the first vp_canvas_begin */
+int vp_canvas_device(const vp_canvas* c, void** dev_bgr8, int* pitch_bytes);
+int vp_canvas_layout(int format, int h, int w, int* n_planes, int row_bytes[2], int rows[2]);   /* host only */
+int vp_canvas_fetch(vp_canvas* c, int format, uint8_t* const* planes, const int* strides, int n_planes);
+
 /* ---- multi-camera result exchange (BASELINE configs[3]) ---------------------------------------
  * One process (or thread) per GPU, camera r on rank r, weights replicated, no data-path collective in the networks.  For the
  * fused ego-path / BEV consumer every rank needs all cameras' results: ONE ncclAllGather (RCCL over xGMI) per frame of a
