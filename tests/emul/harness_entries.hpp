@@ -175,6 +175,42 @@ int emu_dwconv_plain(void* ihi, void* ilo, void* ahi, void* alo, void* ohi, void
   DwPlainParams p{view(ihi, ilo, H, W, C), view(ohi, olo, H, W, C), view(ahi, alo, H, W, C), w, b};
   return harness_done(launch_dwconv_plain(p, nullptr));
 }
+// the matvec that builds the one-channel map fused with the 3x3 convolution that reads it (ctx_exp_conv1_kernel<2 | 8 | 16>): x or slab partials, fp32 rows or
+// e4m3 codes + row scales, the (tile, glanes) of the plan
+int emu_ctx_exp_conv1(const float* x, const float* partial, int nslab, int Kstride, float inv_hw, const float* w, const unsigned char* w8, const float* wscale8,
+                      const float* fb, int K, int fc_act, int H, int W, const float* cw, const float* cb, void* hi, void* lo, int C, int cv_act, int tile, int glanes) {
+  CtxExpConv1Params p{};
+  p.fc.x = x; p.fc.w = w; p.fc.w8 = w8; p.fc.wscale8 = wscale8; p.fc.b = fb; p.fc.N = H * W; p.fc.K = K; p.fc.act = fc_act; p.fc.partial = partial; p.fc.nslab = nslab;
+  p.fc.Kstride = Kstride; p.fc.inv_hw = inv_hw;
+  p.cv = CtxConv1Params{nullptr, H, W, cw, cb, view(hi, lo, H, W, C), cv_act};
+  p.tile = tile; p.glanes = glanes;
+  return harness_done(launch_ctx_exp_conv1(p, nullptr));
+}
+// the range probe: flags = VP_PROBE_BLOCKS words, every one rewritten by every pass
+int emu_finite_probe(const float* src, size_t n, unsigned* flags) { return harness_done(launch_finite_probe(src, n, flags, nullptr)); }
+// a small stacked matrix with an activation per row (FcParams::act_rows: byte r = row r's ActFn)
+int emu_fc_act_rows(const float* x, const float* w, const float* b, float* out, int N, int K, unsigned act_rows) {
+  FcParams p{};
+  p.x = x; p.w = w; p.b = b; p.out = out; p.N = N; p.K = K; p.act = ACT_NONE; p.Kstride = K; p.act_rows = act_rows;
+  return harness_done(launch_fc(p, nullptr));
+}
+// VP_ACT_SCALE forms: tensors stored times 2^-exp (in_mul / add_mul = 2^exp of the tensor read, out_mul = 2^-exp of the tensor written)
+int emu_stem_scaled(const float* in, int H, int W, const float* w, const float* b, void* out_hi, void* out_lo, int out_exp) {
+  StemParams p{in, H, W, w, b, view(out_hi, out_lo, H / 2, W / 2, 32)};
+  p.scaled = 1; p.out_mul = ldexpf(1.0f, -out_exp);
+  return harness_done(launch_stem(p, nullptr));
+}
+int emu_ctx_conv1_scaled(const float* map, int H, int W, const float* w, const float* b, void* hi, void* lo, int C, int act, int out_exp) {
+  CtxConv1Params p{map, H, W, w, b, view(hi, lo, H, W, C), act};
+  p.scaled = 1; p.out_mul = ldexpf(1.0f, -out_exp);
+  return harness_done(launch_ctx_conv1(p, nullptr));
+}
+int emu_dwconv_plain_scaled(void* ihi, void* ilo, void* ahi, void* alo, void* ohi, void* olo, int H, int W, int C, const float* w, const float* b, int act, int in_exp,
+                            int add_exp, int out_exp) {
+  DwPlainParams p{view(ihi, ilo, H, W, C), view(ohi, olo, H, W, C), ahi ? view(ahi, alo, H, W, C) : ActView{}, w, b};
+  p.act = act; p.scaled = 1; p.in_mul = ldexpf(1.0f, in_exp); p.add_mul = ldexpf(1.0f, add_exp); p.out_mul = ldexpf(1.0f, -out_exp);
+  return harness_done(launch_dwconv_plain(p, nullptr));
+}
 int emu_nchw_to_act(const float* src, int Creal, void* hi, void* lo, int H, int W, int C) { return harness_done(launch_nchw_to_act(src, Creal, view(hi, lo, H, W, C), nullptr)); }
 int emu_act_to_nchw(void* hi, void* lo, int H, int W, int C, int Creal, float* dst) { return harness_done(launch_act_to_nchw(view(hi, lo, H, W, C), Creal, dst, nullptr)); }
 

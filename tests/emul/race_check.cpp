@@ -32,6 +32,8 @@ int emu_attention(void*, void*, int, int, int, int, int, float, void*, void*, vo
 int emu_sppf_pool(void*, void*, int, int, int, void*, void*, int, int);
 int emu_depth_viz(const float*, size_t, const uint8_t*, uint8_t*);
 int emu_maxpool5(void*, int, int, int, int, void*, int, int, int);
+int emu_ctx_exp_conv1(const float*, const float*, int, int, float, const float*, const unsigned char*, const float*, const float*, int, int, int, int, const float*, const float*, void*,
+                      void*, int, int, int, int);
 }
 
 static std::mt19937 rng(1);
@@ -232,6 +234,15 @@ int main(int argc, char** argv) {
     std::vector<half_t> ph = rnd16(10 * 20 * 96), pl = rnd16(ph.size());
     std::vector<float> partial(4 * 96);
     bad |= emu_pool_partial(ph.data(), pl.data(), 10, 20, 96, partial.data(), 4);
+    // fused context matvec + 3x3 convolution (kernels_misc.hip ctx_exp_conv1_kernel): x and the map under the patch in LDS, a barrier behind each; the three
+    // patch sizes, 16 / 2 / 1 lanes per map row, maps that are no multiple of the patch
+    const int ctx_cases[3][5] = {{5, 7, 32, 2, 16}, {9, 11, 64, 8, 2}, {17, 19, 32, 16, 1}};   // H, W, K, tile, glanes
+    for (const auto& c : ctx_cases) {
+      const int h = c[0], ww = c[1], K = c[2], C = 16;
+      std::vector<float> cx = rnd(K), cwm = rnd((size_t)h * ww * K, 0.2f), cfb = rnd((size_t)h * ww, 0.1f), cw9 = rnd(9 * C, 0.5f), ccb = rnd(C, 0.1f);
+      std::vector<half_t> chi((size_t)h * ww * C), clo(chi.size());
+      bad |= emu_ctx_exp_conv1(cx.data(), nullptr, 0, K, 0.f, cwm.data(), nullptr, nullptr, cfb.data(), K, 10, h, ww, cw9.data(), ccb.data(), chi.data(), clo.data(), C, 2, c[3], c[4]);
+    }
   }
   {  // AutoDrive attention, SPPF pool; depth visualisation
     const int heads = 2, dk = 8, dv = 16, Hq = 6, Wq = 7, T = Hq * Wq, per = 2 * dk + dv;

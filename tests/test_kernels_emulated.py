@@ -502,9 +502,40 @@ def test_fc_kernel(emu):
     x, w, b = rng.standard_normal(K).astype(np.float32), (rng.standard_normal((N, K)) * 0.1).astype(np.float32), rng.standard_normal(N).astype(np.float32)
     z = torch.from_numpy(w @ x + b)
     out = np.zeros(N, np.float32)
-    for act, want in ((0, z), (1, F.gelu(z)), (3, torch.sigmoid(z)), (2, F.silu(z)), (10, F.silu(F.silu(z)))):
+    for act, want in ((0, z), (1, F.gelu(z)), (3, torch.sigmoid(z)), (2, F.silu(z)), (10, F.silu(F.silu(z))), (8, torch.relu(z)), (9, torch.tanh(z))):
         assert emu.emu_fc(x, w, b, out, N, K, act) == 0
         assert np.abs(out - want.numpy()).max() <= 2e-5, act
+
+
+_ACT64 = {0: lambda z: z, 1: F.gelu, 2: F.silu, 3: torch.sigmoid, 8: torch.relu, 9: torch.tanh, 10: lambda z: F.silu(F.silu(z))}   # ActFn code -> fp64 torch
+
+
+@pytest.mark.parametrize("acts", [(8, 9, 0), (9, 8, 3), (0, 8, 9, 2), (9,)])
+def test_fc_per_row_activations(emu, acts):
+    """FcParams::act_rows: a stacked [N <= 4][512] matrix with one activation per row in one launch (AutoDrive's distance / curvature / flag heads:
+    ReLU / tanh / none), encoded as the engine does -- byte r = row r's ActFn, 0x80000000 or-ed in for N < 4 so the word is non-zero even when
+    every row's code is 0.  Row 0 is driven negative (ReLU really clamps there).  fp64 reference, test_fc_kernel's absolute bar of 2e-5; the
+    emulation measures 7.8e-8 or less on every case.  More than four rows with act_rows set are refused."""
+    rng = np.random.default_rng(31)
+    N, K = len(acts), 512
+    x = rng.standard_normal(K).astype(np.float32)
+    w = (rng.standard_normal((N, K)) * 0.05).astype(np.float32)
+    w[0] = (-0.004 * np.sign(x) * np.abs(rng.standard_normal(K))).astype(np.float32)     # z[0] = -0.004 * sum |x| |g| ~ -1.3
+    b = (rng.standard_normal(N) * 0.1).astype(np.float32)
+    z = torch.from_numpy(w.astype(np.float64) @ x.astype(np.float64) + b)
+    assert float(z[0]) < -0.5
+    want = np.array([float(_ACT64[a](z[r])) for r, a in enumerate(acts)])
+    if acts[0] == 8:
+        assert want[0] == 0.0
+    act_rows = sum(a << (8 * r) for r, a in enumerate(acts)) | (0x80000000 if N < 4 else 0)
+    out = np.full(N, 7, np.float32)
+    emu.emu_fc_act_rows.argtypes = [ct.c_void_p] * 4 + [ct.c_int, ct.c_int, ct.c_uint]
+    assert emu.emu_fc_act_rows(x, w, b, out, N, K, act_rows) == 0
+    err = float(np.abs(out - want).max())
+    print(f"fc act_rows {acts}: {err:.2e} against fp64 (bar 2.0e-05)")
+    assert err <= 2e-5, (acts, err)
+    w5, b5, out5 = np.zeros((5, K), np.float32), np.zeros(5, np.float32), np.zeros(5, np.float32)
+    assert emu.emu_fc_act_rows(x, w5, b5, out5, 5, K, act_rows) != 0
 
 
 # ------------------------------------------------------------------------------------------------ AutoDrive blocks
@@ -643,6 +674,136 @@ def test_context_path_kernels(emu):
     check_ctx_conv1(emu, H, W, 32, rng)
 
 
+_CTX_EXP_ARGS = [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_float] + [ct.c_void_p] * 4 + [ct.c_int] * 4 + [ct.c_void_p] * 4 + [ct.c_int] * 4
+# H, W, K, C, tile, glanes, fc act, conv act, (nslab, Kstride - K) of a slab-partial source or None for x
+_CTX_EXP_CASES = [
+    (10, 20, 800, 128, 2, 16, 3, 1, None),     # the scene networks' launch; K / 4 = 200 is not a multiple of 16
+    (10, 20, 72, 32, 2, 16, 3, 1, (4, 24)),    # slab rebuild with a pitch above K
+    (5, 7, 32, 16, 2, 1, 10, 2, None),         # odd map on 2x2 patches; 16 rows in one pass of 256
+    (10, 20, 32, 16, 8, 2, 10, 2, None),       # AutoDrive's small-map launch; 100 halo rows in one pass of 128
+    (9, 11, 64, 24, 8, 64, 10, 2, (3, 8)),     # lanes 16..63 hold no piece; 25 passes; both edges overhang
+    (3, 5, 32, 8, 8, 2, 10, 2, None),          # a map smaller than one patch
+    (20, 23, 32, 16, 16, 1, 10, 2, None),      # AutoDrive's large-map launch; 324 rows in two passes, the second partly dead
+    (17, 33, 64, 16, 16, 4, 10, 2, None),      # W = 2 patches + 1 column
+    (1, 1, 4, 8, 2, 16, 3, 1, None),           # the smallest accepted shape; the halo is all padding
+]
+
+
+def _ctx_exp_inputs(H, W, K, C, src, fp8, rng):
+    """operands of one fused launch and the fp64 map -> convolution reference inputs: (x, partial, nslab, Kstride, inv_hw), the matrix as the
+    kernel reads it (fp32 rows, or e4m3 codes + row scales and the matrix they stand for), biases, the 3x3 filters"""
+    N = H * W
+    inv_hw = np.float32(1.0 / 200.0)
+    if src is None:
+        x, partial, nslab, Kstride = rng.standard_normal(K).astype(np.float32), None, 0, K
+        x64 = x.astype(np.float64)
+    else:
+        nslab, Kstride = src[0], K + src[1]
+        partial = (rng.standard_normal((nslab, Kstride)) * 100.0).astype(np.float32)      # columns K.. are the pitch: never read
+        x, x64 = None, partial.astype(np.float64).sum(axis=0)[:K] * np.float64(inv_hw)
+    w = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    fb = (rng.standard_normal(N) * 0.1).astype(np.float32)
+    codes = scales = None
+    if fp8:
+        from autoware_vision_pilot_amd import lib as vplib
+        codes, scales = vplib.fp8_encode_rows(w)
+        w = vplib_dequant(codes, scales)              # the reference's matrix: quantisation is not part of the error
+    cw = (rng.standard_normal((C, 1, 3, 3)) * 0.5).astype(np.float32)
+    cb = (rng.standard_normal(C) * 0.1).astype(np.float32)
+    return dict(x=x, partial=partial, nslab=nslab, Kstride=Kstride, inv_hw=inv_hw, x64=x64, w=w, codes=codes, scales=scales, fb=fb, cw=cw, cb=cb)
+
+
+def _ctx_exp_call(emu, d, H, W, K, C, fc_act, cv_act, hi, lo, **over):
+    """one launch; `over` gives tile and glanes and may replace an operand or the matvec's K (the refusals)"""
+    a = dict(x=d["x"], partial=d["partial"], w=None if d["codes"] is not None else d["w"], w8=d["codes"], wscale8=d["scales"], Kfc=K)
+    a.update(over)
+    emu.emu_ctx_exp_conv1.argtypes = _CTX_EXP_ARGS
+    w9 = np.ascontiguousarray(d["cw"].reshape(C, 9).T)
+    return emu.emu_ctx_exp_conv1(a["x"], a["partial"], d["nslab"], d["Kstride"], float(d["inv_hw"]), a["w"], a["w8"], a["wscale8"], d["fb"], a["Kfc"], fc_act, H, W,
+                                 w9, d["cb"], hi, lo, C, cv_act, a["tile"], a["glanes"])
+
+
+@pytest.mark.parametrize("fp8", [False, True], ids=["fp32", "e4m3"])
+@pytest.mark.parametrize("H,W,K,C,tile,glanes,fc_act,cv_act,src", _CTX_EXP_CASES)
+def test_ctx_exp_conv1_kernel(emu, H, W, K, C, tile, glanes, fc_act, cv_act, src, fp8):
+    """ctx_exp_conv1_kernel<2 | 8 | 16> on its own: the matvec that builds the one-channel H x W map (x, or the average pool rebuilt from slab
+    partials; fp32 rows or e4m3 codes + row scales) fused with the 3x3 convolution 1 -> C that reads it, against fp64
+    act(conv2d(act(Wq x + b).reshape(H, W), cw, cb, padding = 1)).  The cases: patches that hang over the map's right / bottom edge and halo rows
+    outside it (`inside` / `live`), pass counts that do not divide (T + 2)^2, glanes above K / 4, the pitch of the partials.  The outputs start
+    from a non-zero pattern, so an element no work-item wrote shows.  Bar: check_ctx_conv1's 2e-6 (same output format: the (hi, lo) store
+    dominates); the emulation measures 1.0e-7 ... 3.3e-7 over the 18 cases."""
+    rng = np.random.default_rng(1000 * H + 10 * W + K + (1 if fp8 else 0))
+    d = _ctx_exp_inputs(H, W, K, C, src, fp8, rng)
+    hi, lo = np.full((H, W, C), 7, np.float16), np.full((H, W, C), 7, np.float16)
+    assert _ctx_exp_call(emu, d, H, W, K, C, fc_act, cv_act, hi, lo, tile=tile, glanes=glanes) == 0
+    m = _ACT64[fc_act](torch.from_numpy(d["w"].astype(np.float64) @ d["x64"] + d["fb"])).reshape(1, 1, H, W)
+    want = _ACT64[cv_act](F.conv2d(m, torch.from_numpy(d["cw"]).double(), torch.from_numpy(d["cb"]).double(), padding=1))[0].numpy()
+    err = _rel((hi.astype(np.float64) + lo.astype(np.float64)).transpose(2, 0, 1), want)
+    print(f"ctx_exp_conv1 {H}x{W} K={K} C={C} tile={tile} glanes={glanes} {'e4m3' if fp8 else 'fp32'} {'partial' if src else 'x'}: {err:.2e} against fp64 (bar 2.0e-06)")
+    assert err <= 2e-6, err
+
+
+def test_ctx_exp_conv1_refusals(emu):
+    """what launch_ctx_exp_conv1 does not take is an error, not a launch: a patch size without an instantiation, a lane count that is no power of
+    two, a K that is no multiple of four, both forms of the matrix at once, no source for x."""
+    H, W, K, C = 5, 7, 32, 16
+    rng = np.random.default_rng(37)
+    d = _ctx_exp_inputs(H, W, K, C, None, False, rng)
+    codes, scales = np.zeros((H * W, K), np.uint8), np.ones(H * W, np.float32)
+    hi, lo = np.full((H, W, C), 7, np.float16), np.full((H, W, C), 7, np.float16)
+    assert _ctx_exp_call(emu, d, H, W, K, C, 10, 2, hi, lo, tile=2, glanes=1) == 0
+    for over in (dict(tile=4), dict(glanes=3), dict(Kfc=6), dict(w8=codes, wscale8=scales), dict(x=None)):
+        hi[...], lo[...] = 7, 7
+        assert _ctx_exp_call(emu, d, H, W, K, C, 10, 2, hi, lo, **{**dict(tile=2, glanes=1), **over}) != 0, over
+        assert np.all(hi == 7) and np.all(lo == 7), over          # refused before anything ran
+
+
+# ------------------------------------------------------------------------------------------------ range probe
+_PROBE_BLOCKS = 64      # kernels.hpp VP_PROBE_BLOCKS
+
+
+def _probe_positions(n):
+    """where the one non-finite element goes: both ends, the middle, the last element of the part read as 16-byte vectors, the first element of
+    the n & 3 tail (workgroup 0's), and an element of a workgroup other than 0 (vector i belongs to workgroup (i / 256) % 64) where n has one"""
+    n4 = n >> 2
+    pos = {0, n - 1, n // 2}
+    if n4:
+        pos.add(4 * n4 - 1)
+    if n & 3:
+        pos.add(4 * n4)
+    if n4 > 256 * 5 + 17:
+        pos.add(4 * (256 * 5 + 17) + 2)
+    return sorted(pos)
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 7, 1023, 1024, 65539, 131077])
+def test_finite_probe_kernel(emu, n):
+    """finite_probe_kernel, the range guard's only device code: all VP_PROBE_BLOCKS words are rewritten by every pass (they start from
+    0xDEADBEEF here), all 0 on finite data -- +-FLT_MAX, 65504, the smallest subnormal and +-0 included -- and exactly one word 1, the rest 0,
+    when one element is +-inf or a NaN of either sign / payload, wherever it sits: in the 16-byte vector part (n = 65539 = 64 * 256 * 4 + 3 gives
+    every workgroup exactly one vector per thread, 131077 a second round for workgroup 0 only) or in the n & 3 tail (AutoDrive's n = 3 is tail only)."""
+    rng = np.random.default_rng(n)
+    base = rng.standard_normal(n).astype(np.float32)
+    edge = np.array([np.finfo(np.float32).max, -np.finfo(np.float32).max, 65504.0, 0, 0.0, -0.0], np.float32)
+    edge.view(np.uint32)[3] = 1                                    # the smallest subnormal
+    base[:min(n, 6)] = edge[:n]
+    assert np.isfinite(base).all()
+    emu.emu_finite_probe.argtypes = [ct.c_void_p, ct.c_size_t, ct.c_void_p]
+    flags = np.full(_PROBE_BLOCKS, 0xDEADBEEF, np.uint32)
+    assert emu.emu_finite_probe(base, n, flags) == 0
+    assert not flags.any(), flags
+    launches = 1
+    for pos in _probe_positions(n):
+        for bits in (0x7F800000, 0xFF800000, 0x7FC00000, 0x7F800001, 0xFFFFFFFF):
+            src = base.copy()
+            src.view(np.uint32)[pos] = bits
+            flags[:] = 0xDEADBEEF
+            assert emu.emu_finite_probe(src, n, flags) == 0
+            assert np.all(flags <= 1) and int(flags.sum()) == 1, (pos, hex(bits), flags)
+            launches += 1
+    print(f"finite_probe n={n}: {launches} launches, positions {_probe_positions(n)}")
+
+
 _ints5 = lambda xs: (ct.c_int * 5)(*xs)
 
 
@@ -710,6 +871,66 @@ def test_autodrive_glue_kernels(emu):
     want = (F.conv2d(xin, torch.from_numpy(wt), torch.from_numpy(b), padding=1, groups=C)[0].numpy()
             + (ah.astype(np.float32) + al.astype(np.float32)).transpose(2, 0, 1))
     assert _rel((oh.astype(np.float32) + ol.astype(np.float32)).transpose(2, 0, 1), want) <= 2e-6
+
+
+# ------------------------------------------------------------------------------------------------ VP_ACT_SCALE stores
+def _stored_err(name, hi, lo, out_exp, want, single_bar=None):
+    """stored (hi, lo) planes [H][W][C] times 2^out_exp against the true-valued fp64 `want` [C][H][W]; the bar is the module's _bar rule applied to
+    the STORED tensor: 2e-6 plus the (hi, lo) format's own error at the stored scale (a single plane keeps its own bar)"""
+    got = (hi.astype(np.float64) + (lo.astype(np.float64) if lo is not None else 0.0)).transpose(2, 0, 1) * 2.0 ** out_exp
+    err = _rel(got, want)
+    bar = single_bar if single_bar is not None else 2e-6 + storage_rel(want * 2.0 ** -out_exp)
+    print(f"{name} out_exp={out_exp}: {err:.2e} against fp64 (bar {bar:.2e})")
+    assert err <= bar, (name, out_exp, err, bar)
+    return err
+
+
+def test_scaled_stores_of_stem_context_and_depthwise(emu):
+    """The `scaled` forms of stem_kernel, ctx_conv1_kernel and dwconv_plain_kernel (VP_ACT_SCALE: a tensor t is stored as t * 2^-exp): stored
+    inputs x * 2^-in_exp in, stored output * 2^out_exp against the fp64 reference of the true-valued operation; the depthwise kernel also in its
+    SiLU / no-add form (the detector head's class branch).  Bars: 2e-6 + the (hi, lo) format's storage error of the stored tensor (2.04e-6 ...
+    2.77e-6 here); the stem's single fp16 plane keeps 2e-3.  The emulation measures 6.9e-8 ... 8.9e-7 (single plane: 3.8e-4)."""
+    rng = np.random.default_rng(41)
+    # stem 18x28: conv 3x3 / s2 3 -> 32 + SiLU
+    H, W = 18, 28
+    x = rng.standard_normal((3, H, W)).astype(np.float32)
+    wt = (rng.standard_normal((32, 3, 3, 3)) * 0.3).astype(np.float32)
+    b = (rng.standard_normal(32) * 0.1).astype(np.float32)
+    want = F.silu(F.conv2d(torch.from_numpy(x).double()[None], torch.from_numpy(wt).double(), torch.from_numpy(b).double(), stride=2, padding=1))[0].numpy()
+    w27 = np.ascontiguousarray(wt.reshape(32, 27).T)
+    for out_exp in (-6, -1, 3, 7):
+        for split in (True, False):
+            hi = np.full((H // 2, W // 2, 32), 7, np.float16)
+            lo = np.full_like(hi, 7) if split else None
+            assert emu.emu_stem_scaled(x, H, W, w27, b, hi, lo, out_exp) == 0
+            _stored_err("stem" + ("" if split else " (single plane)"), hi, lo, out_exp, want, None if split else 2e-3)
+    # ctx_conv1 10x20x32: conv 3x3 1 -> 32 on a (0, 1) map, GELU / SiLU
+    H, W, C = 10, 20, 32
+    m = rng.uniform(0, 1, size=(H, W)).astype(np.float32)
+    wt = (rng.standard_normal((C, 1, 3, 3)) * 0.5).astype(np.float32)
+    bc = (rng.standard_normal(C) * 0.1).astype(np.float32)
+    w9 = np.ascontiguousarray(wt.reshape(C, 9).T)
+    conv = F.conv2d(torch.from_numpy(m).double()[None, None], torch.from_numpy(wt).double(), torch.from_numpy(bc).double(), padding=1)[0]
+    for act, out_exp in ((1, -5), (2, 4), (1, 6), (2, -2)):
+        hi, lo = np.full((H, W, C), 7, np.float16), np.full((H, W, C), 7, np.float16)
+        assert emu.emu_ctx_conv1_scaled(m, H, W, w9, bc, hi, lo, C, act, out_exp) == 0
+        _stored_err(f"ctx_conv1 act={act}", hi, lo, out_exp, _ACT64[act](conv).numpy())
+    # dwconv_plain 5x7x32: [add +] act(depthwise 3x3(in) + b), every tensor with its own exponent
+    H, W, C = 5, 7, 32
+    x, add = rng.standard_normal((C, H, W)).astype(np.float32), rng.standard_normal((C, H, W)).astype(np.float32)
+    wt, b = (rng.standard_normal((C, 1, 3, 3)) * 0.3).astype(np.float32), (rng.standard_normal(C) * 0.1).astype(np.float32)
+    w9 = np.ascontiguousarray(wt.reshape(C, 9).T)
+    for act, with_add, (in_exp, add_exp, out_exp) in ((0, True, (3, -2, 4)), (0, True, (-4, 5, -3)), (2, False, (5, 0, -6)), (2, False, (-3, 0, 2)),
+                                                       (0, True, (0, 0, 5)), (2, True, (2, 2, 2))):
+        xh, xl = split16(nhwc(x * np.float32(2.0 ** -in_exp), C))
+        ah, al = split16(nhwc(add * np.float32(2.0 ** -add_exp), C))
+        xin = torch.from_numpy(((xh.astype(np.float64) + xl.astype(np.float64)) * 2.0 ** in_exp).transpose(2, 0, 1))[None]     # the true values the planes stand for
+        want = _ACT64[act](F.conv2d(xin, torch.from_numpy(wt).double(), torch.from_numpy(b).double(), padding=1, groups=C))[0].numpy()
+        if with_add:
+            want = want + ((ah.astype(np.float64) + al.astype(np.float64)) * 2.0 ** add_exp).transpose(2, 0, 1)
+        oh, ol = np.full((H, W, C), 7, np.float16), np.full((H, W, C), 7, np.float16)
+        assert emu.emu_dwconv_plain_scaled(xh, xl, ah if with_add else None, al if with_add else None, oh, ol, H, W, C, w9, b, act, in_exp, add_exp, out_exp) == 0
+        _stored_err(f"dwconv_plain act={act} add={with_add} exps ({in_exp}, {add_exp})", oh, ol, out_exp, want)
 
 
 # ------------------------------------------------------------------------------------------------ batched encoder kernels
