@@ -487,6 +487,9 @@ class Canvas {
   void sync();
   // planes / strides / row_bytes / rows: what vp_canvas_layout answers for (format, h(), w()), checked by the caller
   void fetch(int format, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows, int n_planes);
+  // vp_canvas_set_color (values checked by the caller): the standard and chroma rule of later fetches into the YUV formats and GRAY8
+  void set_color(int matrix, int range, int chroma_mode) { matrix_ = matrix, range_ = range, chroma_mode_ = chroma_mode; }
+  void get_color(int* matrix, int* range, int* chroma_mode) const { *matrix = matrix_, *range = range_, *chroma_mode = chroma_mode_; }
   hipStream_t stream() const { return stream_; }
   int gpu() const { return gpu_; }
   bool begun() const { return begun_; }
@@ -517,6 +520,7 @@ class Canvas {
   size_t bgr_cap_ = 0;
   int h_ = 0, w_ = 0, pitch_ = 0;
   bool begun_ = false;
+  int matrix_ = 0, range_ = 0, chroma_mode_ = 0;   // BT.601, limited range, chroma of the even pixel
   std::vector<Table> tables_;
   uint8_t* d_lut_ = nullptr;       // [3 viz types][256][3], then viridis [256][3]
   unsigned* d_minmax_ = nullptr;   // [0, 2): the keys of the plane in work; [2, 4): their start values

@@ -976,20 +976,28 @@ void Canvas::fetch(int format, uint8_t* const* planes, const int* strides, const
   if (format == VP_FRAME_BGR8) {
     VP_HIP_CHECK(hipMemcpy2DAsync(planes[0], strides[0], d_bgr_, pitch_, row_bytes[0], rows[0], hipMemcpyDeviceToHost, stream_));
   } else {
-    const size_t pp = (size_t)canvas_plane_pitch(format, w_);
-    grow(d_out_, out_cap_, pp * (rows[0] + (n_planes == 2 ? rows[1] : 0)));
+    const size_t pp = (size_t)canvas_plane_pitch(format, w_), ppc = (size_t)canvas_plane_pitch(format, w_, 1);   // both multiples of 4
+    uint8_t* dev[3] = {nullptr, nullptr, nullptr};
+    size_t off[4] = {0, 0, 0, 0};
+    for (int i = 0; i < n_planes; ++i) off[i + 1] = off[i] + (i ? ppc : pp) * rows[i];
+    grow(d_out_, out_cap_, off[n_planes]);
+    for (int i = 0; i < n_planes; ++i) dev[i] = d_out_ + off[i];
     CanvasToFormatParams q{};
     q.src = d_bgr_;
     q.src_pitch = pitch_;
     q.h = h_;
     q.w = w_;
     q.format = format;
-    q.p0 = d_out_;
-    q.p1 = n_planes == 2 ? d_out_ + pp * rows[0] : nullptr;
+    q.p0 = dev[0];
+    q.p1 = dev[1];
+    q.p2 = dev[2];
     q.dst_pitch = (int)pp;
+    q.dst_pitch_c = (int)ppc;
+    q.chroma_mean = chroma_mode_;
+    q.k = color_standard(matrix_, range_).fwd;
     VP_HIP_CHECK(launch_canvas_to_format(q, stream_));
-    VP_HIP_CHECK(hipMemcpy2DAsync(planes[0], strides[0], q.p0, pp, row_bytes[0], rows[0], hipMemcpyDeviceToHost, stream_));
-    if (n_planes == 2) VP_HIP_CHECK(hipMemcpy2DAsync(planes[1], strides[1], q.p1, pp, row_bytes[1], rows[1], hipMemcpyDeviceToHost, stream_));
+    for (int i = 0; i < n_planes; ++i)
+      VP_HIP_CHECK(hipMemcpy2DAsync(planes[i], strides[i], dev[i], i ? ppc : pp, row_bytes[i], rows[i], hipMemcpyDeviceToHost, stream_));
   }
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
 }

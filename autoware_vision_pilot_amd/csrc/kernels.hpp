@@ -42,19 +42,51 @@ struct PilResampleParams {
 };
 
 // vp_frame (include/vp_hip.h): a camera frame in its native format -> packed BGR8 on the device, once, behind the upload.  kernels_misc.hip
-// frame_to_bgr8_kernel.  format: the vp_frame_format code.  p0 / s0: the single plane (NV12: the Y plane) and its row stride in bytes; p1 / s1: NV12's
-// interleaved UV plane.  dst rows are dst_pitch = 12 * ceil(w / 4) bytes apart (== 3 * w when w is a multiple of 4): one work-item stores the three
-// words of four pixels, bytes behind the last pixel of a row are written as 0.
-constexpr int kFrameFormats = 8;   // BGR8, RGB8, BGRA8, RGBA8, GRAY8, NV12, YUY2, UYVY
+// frame_to_bgr8_kernel.  format: the vp_frame_format code.  p0 / s0: the first plane (the 4:2:0 formats: the Y plane) and its row stride in bytes;
+// p1 / s1: NV12's interleaved UV plane, NV21's VU plane, I420's U plane, YV12's V plane; p2 / s2: I420's V plane, YV12's U plane (the planes in the
+// format's own order: the launcher hands the kernel YV12 as I420 with the two chroma planes exchanged).  dst rows are dst_pitch = 12 * ceil(w / 4)
+// bytes apart (== 3 * w when w is a multiple of 4): one work-item stores the three words of four pixels, bytes behind the last pixel of a row are
+// written as 0.
+// Format codes 0 .. 7 and 16 .. 18 (8 .. 15 stay unknown); frame_format_index: their dense index for tables, -1 for anything else.
+constexpr int kFrameFormats = 11;   // BGR8, RGB8, BGRA8, RGBA8, GRAY8, NV12, YUY2, UYVY, I420, YV12, NV21
+inline int frame_format_index(int format) { return format >= 0 && format < 8 ? format : (format >= 16 && format <= 18 ? format - 8 : -1); }
+inline bool frame_format_420(int format) { return format == 5 || (format >= 16 && format <= 18); }   // one (U, V) per 2x2 block
+inline bool frame_format_planar(int format) { return format == 16 || format == 17; }                // three planes
 inline int frame_bgr_pitch(int w) { return 12 * ((w + 3) / 4); }
+// The colour standards (include/vp_hip.h vp_color_matrix x vp_color_range), 20 fractional bits.  ONE table, color_standard() below; both kernels take
+// their constants from it as uniform parameters.
+//   inverse:  y = cy * max(0, Y - off), u = U - 128, v = V - 128;  R = y + cvr v,  G = y - cvg v - cug u,  B = y + cub u
+//   forward:  Y = yk . (R, G, B) + (off << 20),  U = uk . (R, G, B) + (128 << 20),  V = vk . (R, G, B) + (128 << 20)
+// each + 2^19, arithmetic shift by 20, clamp to 0 .. 255.
+struct YuvToBgr {
+  int off, cy, cvr, cvg, cug, cub;
+};
+struct BgrToYuv {
+  int off;
+  int yk[3], uk[3], vk[3];   // R, G, B
+};
+struct ColorStandard {
+  YuvToBgr inv;
+  BgrToYuv fwd;
+};
+inline const ColorStandard& color_standard(int matrix, int range) {
+  static const ColorStandard table[2][2] = {
+      {{{16, 1220542, 1673527, 852492, 409993, 2116026}, {16, {269484, 528482, 102760}, {-155188, -305135, 460324}, {460324, -385875, -74448}}},     // BT.601 limited: OpenCV's
+       {{0, 1048576, 1470104, 748826, 360853, 1858077}, {0, {313524, 615514, 119538}, {-176932, -347356, 524288}, {524288, -439026, -85262}}}},      // BT.601 full
+      {{{16, 1220945, 1879825, 558796, 223607, 2215014}, {16, {191455, 644067, 65019}, {-105533, -355018, 460551}, {460551, -418321, -42230}}},      // BT.709 limited
+       {{0, 1048576, 1651297, 490864, 196424, 1945738}, {0, {222927, 749942, 75707}, {-120138, -404150, 524288}, {524288, -476214, -48074}}}}};      // BT.709 full
+  return table[matrix & 1][range & 1];
+}
 struct FrameToBgrParams {
   const uint8_t* p0;
   const uint8_t* p1;
-  int s0, s1;
+  const uint8_t* p2;
+  int s0, s1, s2;
   int h, w;
   int format;
   uint8_t* dst;
   int dst_pitch;
+  YuvToBgr k;           // color_standard(matrix, range).inv; read by the YUV formats only
 };
 hipError_t launch_frame_to_bgr8(const FrameToBgrParams& p, hipStream_t st);
 
@@ -91,12 +123,16 @@ struct CanvasBoxParams {
   CanvasBox box[kCanvasBoxChunk];
 };
 hipError_t launch_canvas_boxes(const CanvasBoxParams& p, int canvas_h, int canvas_w, hipStream_t st);
-// canvas_to_format_kernel: the inverse of frame_to_bgr8_kernel -- the same four-pixel blocks, row pairs for NV12, chroma of the even pixel (NV12: of
-// the top-left pixel of the 2x2 block).  The planes are the canvas's own staging: rows canvas_plane_pitch(format, w) apart, whole words stored, bytes
-// behind a row's end zero.  BGR8 needs no kernel.  Forward BT.601 limited range, 20 fractional bits: include/vp_hip.h vp_canvas_fetch.
-inline int canvas_plane_pitch(int format, int w) {
-  static const int block_bytes[kFrameFormats] = {12, 12, 16, 16, 4, 4, 8, 8};   // of four pixels
-  return block_bytes[format] * ((w + 3) / 4);
+// canvas_to_format_kernel: the inverse of frame_to_bgr8_kernel -- the same four-pixel blocks, row pairs for the 4:2:0 formats.  Chroma: of the even
+// pixel (4:2:0: of the top-left pixel of the 2x2 block), or with chroma_mean the rounded mean of the group's per-pixel (clamped) samples, all of which
+// the one work-item owns.  The planes are the canvas's own staging: rows canvas_plane_pitch(format, w, plane) apart, bytes behind a row's end zero up to
+// the last block's store.  Plane 0 and the interleaved chroma plane are stored as whole words; a work-item's share of a planar chroma row is two bytes,
+// stored as one aligned 16-bit value.  p1 / p2: as FrameToBgrParams, the format's own order.  BGR8 needs no kernel.  include/vp_hip.h vp_canvas_fetch.
+inline int canvas_plane_pitch(int format, int w, int plane = 0) {
+  static const int block_bytes[kFrameFormats] = {12, 12, 16, 16, 4, 4, 8, 8, 4, 4, 4};   // of four pixels, plane 0
+  const int blocks = (w + 3) / 4;
+  if (plane > 0 && frame_format_planar(format)) return (2 * blocks + 3) & ~3;
+  return block_bytes[frame_format_index(format)] * blocks;
 }
 struct CanvasToFormatParams {
   const uint8_t* src;
@@ -104,8 +140,12 @@ struct CanvasToFormatParams {
   int h, w;
   int format;
   uint8_t* p0;
-  uint8_t* p1;          // NV12: interleaved UV, rows dst_pitch apart as well
+  uint8_t* p1;          // 4:2:0: the second plane, rows dst_pitch_c apart
+  uint8_t* p2;          // planar: the third plane, likewise
   int dst_pitch;        // canvas_plane_pitch(format, w)
+  int dst_pitch_c;      // canvas_plane_pitch(format, w, 1)
+  int chroma_mean;      // 0: the even pixel; 1: the mean of the group
+  BgrToYuv k;           // color_standard(matrix, range).fwd
 };
 hipError_t launch_canvas_to_format(const CanvasToFormatParams& p, hipStream_t st);
 // depth_colorize_kernel's value -> u8 -> table step, written into the region (x0, y0, w, h) of the canvas instead of a packed image; src: [h][w] fp32

@@ -37,24 +37,25 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreprocessParams 
 }
 
 // ------------------------------------------------------------------------------------------ vp_frame: native camera formats -> BGR8
-// One work-item produces four pixels of a row (NV12: of two rows, i.e. two whole 2x2 chroma groups; YUY2 / UYVY: two 2x1 groups), so every chroma
-// sample is read once, and stores them as three aligned 32-bit words per row (kernels.hpp FrameToBgrParams: rows are 12 * ceil(w / 4) bytes apart).
+// One work-item produces four pixels of a row (the 4:2:0 formats: of two rows, i.e. two whole 2x2 chroma groups; YUY2 / UYVY: two 2x1 groups), so every
+// chroma sample is read once, and stores them as three aligned 32-bit words per row (kernels.hpp FrameToBgrParams: rows are 12 * ceil(w / 4) bytes apart).
 // Pixels beyond the row's end are written as zero bytes.  Source planes are read byte by byte: a decoder surface or a caller's view promises no alignment.
-// The YUV formats use the integer BT.601 limited-range form documented for OpenCV's cvtColor(COLOR_YUV2BGR_NV12 / _YUY2 / _UYVY) -- 20 fractional
-// bits, no chroma interpolation -- which include/vp_hip.h states as the DEFINITION (parity with OpenCV itself is not pinned):
-//   y = 1220542 * max(0, Y - 16), u = U - 128, v = V - 128
-//   R = sat8((y + 1673527 v + 2^19) >> 20), G = sat8((y - 852492 v - 409993 u + 2^19) >> 20), B = sat8((y + 2116026 u + 2^19) >> 20)
+// The YUV formats use the 20-bit integer form include/vp_hip.h states as the DEFINITION, no chroma interpolation; its constants p.k are those of the
+// frame's colour standard (kernels.hpp color_standard), uniform over the launch.  The default, BT.601 limited range, is the form documented for OpenCV's
+// cvtColor(COLOR_YUV2BGR_NV12 / _YUY2 / _UYVY) (parity with OpenCV itself is not pinned):
+//   y = cy * max(0, Y - off), u = U - 128, v = V - 128
+//   R = sat8((y + cvr v + 2^19) >> 20), G = sat8((y - cvg v - cug u + 2^19) >> 20), B = sat8((y + cub u + 2^19) >> 20)
 struct ChromaTerms {
   int r, g, b;   // the chroma part of each channel, rounding constant included
 };
-__device__ __forceinline__ ChromaTerms chroma_terms(int U, int V) {
+__device__ __forceinline__ ChromaTerms chroma_terms(const YuvToBgr& k, int U, int V) {
   const int u = U - 128, v = V - 128;
-  return {1673527 * v + (1 << 19), -852492 * v - 409993 * u + (1 << 19), 2116026 * u + (1 << 19)};
+  return {k.cvr * v + (1 << 19), -k.cvg * v - k.cug * u + (1 << 19), k.cub * u + (1 << 19)};
 }
 __device__ __forceinline__ unsigned sat8(int x) { return (unsigned)min(max(x, 0), 255); }
 // one pixel as b | g << 8 | r << 16
-__device__ __forceinline__ unsigned yuv_pixel(int Y, const ChromaTerms& c) {
-  const int y = 1220542 * max(0, Y - 16);
+__device__ __forceinline__ unsigned yuv_pixel(const YuvToBgr& k, int Y, const ChromaTerms& c) {
+  const int y = k.cy * max(0, Y - k.off);
   return sat8((y + c.b) >> 20) | (sat8((y + c.g) >> 20) << 8) | (sat8((y + c.r) >> 20) << 16);
 }
 __device__ __forceinline__ void store_bgr4(uint8_t* row, int j, const unsigned px[4]) {
@@ -65,24 +66,28 @@ __device__ __forceinline__ void store_bgr4(uint8_t* row, int j, const unsigned p
 }
 __global__ __launch_bounds__(256) void frame_to_bgr8_kernel(const FrameToBgrParams p) {
   const int bpr = (p.w + 3) >> 2;                          // four-pixel blocks per row
-  const int rows = p.format == 5 ? p.h >> 1 : p.h;         // NV12: row pairs
+  const bool f420 = p.format == 5 || p.format >= 16;       // NV12, I420 (YV12 arrives as I420), NV21
+  const int rows = f420 ? p.h >> 1 : p.h;                  // 4:2:0: row pairs
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= (long long)rows * bpr) return;
   const int r = (int)(t / bpr), j = (int)(t - (long long)r * bpr), x0 = 4 * j;
   unsigned px[4] = {0u, 0u, 0u, 0u};
-  if (p.format == 5) {   // NV12: Y rows 2r, 2r + 1; one (U, V) per 2x2 block
+  if (f420) {   // Y rows 2r, 2r + 1; one (U, V) per 2x2 block.  The formats differ only in where a group's two chroma bytes lie:
     const uint8_t* y0 = p.p0 + (size_t)(2 * r) * p.s0 + x0;
     const uint8_t* y1 = y0 + p.s0;
-    const uint8_t* uv = p.p1 + (size_t)r * p.s1 + x0;
+    const bool planar = p.format == 16;                    // I420: U from p1, V from p2, one byte a group; NV12 / NV21: U V / V U pairs in p1
+    const int step = planar ? 1 : 2;
+    const uint8_t* cu = p.p1 + (size_t)r * p.s1 + (planar ? x0 >> 1 : x0 + (p.format == 18 ? 1 : 0));
+    const uint8_t* cv = planar ? p.p2 + (size_t)r * p.s2 + (x0 >> 1) : p.p1 + (size_t)r * p.s1 + x0 + (p.format == 18 ? 0 : 1);
     unsigned px1[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       if (x0 + 2 * g >= p.w) break;                        // w is even: a group is whole or absent
-      const ChromaTerms c = chroma_terms(uv[2 * g], uv[2 * g + 1]);
-      px[2 * g] = yuv_pixel(y0[2 * g], c);
-      px[2 * g + 1] = yuv_pixel(y0[2 * g + 1], c);
-      px1[2 * g] = yuv_pixel(y1[2 * g], c);
-      px1[2 * g + 1] = yuv_pixel(y1[2 * g + 1], c);
+      const ChromaTerms c = chroma_terms(p.k, cu[step * g], cv[step * g]);
+      px[2 * g] = yuv_pixel(p.k, y0[2 * g], c);
+      px[2 * g + 1] = yuv_pixel(p.k, y0[2 * g + 1], c);
+      px1[2 * g] = yuv_pixel(p.k, y1[2 * g], c);
+      px1[2 * g + 1] = yuv_pixel(p.k, y1[2 * g + 1], c);
     }
     store_bgr4(p.dst + (size_t)(2 * r) * p.dst_pitch, j, px);
     store_bgr4(p.dst + (size_t)(2 * r + 1) * p.dst_pitch, j, px1);
@@ -95,9 +100,9 @@ __global__ __launch_bounds__(256) void frame_to_bgr8_kernel(const FrameToBgrPara
     for (int g = 0; g < 2; ++g) {
       if (x0 + 2 * g >= p.w) break;
       const uint8_t* s = row + 2 * (size_t)(x0 + 2 * g);
-      const ChromaTerms c = chroma_terms(s[co], s[co + 2]);
-      px[2 * g] = yuv_pixel(s[yo], c);
-      px[2 * g + 1] = yuv_pixel(s[yo + 2], c);
+      const ChromaTerms c = chroma_terms(p.k, s[co], s[co + 2]);
+      px[2 * g] = yuv_pixel(p.k, s[yo], c);
+      px[2 * g + 1] = yuv_pixel(p.k, s[yo + 2], c);
     }
   } else {
 #pragma unroll
@@ -589,43 +594,71 @@ __global__ __launch_bounds__(256) void canvas_depth_kernel(const float* src, con
   }
   store_bgr4(row, j, px);
 }
-// Canvas -> a vp_frame format (kernels.hpp CanvasToFormatParams).  Forward BT.601 limited range, the integer counterpart of the upload formula above
-// (include/vp_hip.h states it as the DEFINITION; not pinned against OpenCV):
-//   Y = sat8((269484 R + 528482 G + 102760 B + (16 << 20) + 2^19) >> 20)
-//   U = sat8((-155188 R - 305135 G + 460324 B + (128 << 20) + 2^19) >> 20),  V = sat8((460324 R - 385875 G - 74448 B + (128 << 20) + 2^19) >> 20)
-__device__ __forceinline__ unsigned luma_of(unsigned px) {
+// Canvas -> a vp_frame format (kernels.hpp CanvasToFormatParams).  The forward form, the integer counterpart of the upload formula above, with the
+// constants p.k of the canvas's colour standard (include/vp_hip.h states it as the DEFINITION; not pinned against OpenCV):
+//   Y = sat8((yk . (R, G, B) + (off << 20) + 2^19) >> 20),  U = sat8((uk . (R, G, B) + (128 << 20) + 2^19) >> 20),  V likewise with vk
+// In full range pure blue / pure red reach 256 before the clamp: there sat8 decides.
+__device__ __forceinline__ unsigned luma_of(const BgrToYuv& k, unsigned px) {
   const int b = px & 255u, g = (px >> 8) & 255u, r = px >> 16;
-  return sat8((269484 * r + 528482 * g + 102760 * b + (16 << 20) + (1 << 19)) >> 20);
+  return sat8((k.yk[0] * r + k.yk[1] * g + k.yk[2] * b + (k.off << 20) + (1 << 19)) >> 20);
 }
-// U | V << 8
-__device__ __forceinline__ unsigned chroma_of(unsigned px) {
+// U | V << 8, bits 16 .. 31 zero.  V is pinned in a register of its own: left to itself the backend packs the two shift-and-clamp steps into one
+// v_ashr_pk_u8_i32 and then takes bits 16 .. 31 of that result for zero; on the MI355X they were not (the NV12 / I420 bytes of a block's second group came
+// back OR-ed with them).
+__device__ __forceinline__ unsigned chroma_of(const BgrToYuv& k, unsigned px) {
   const int b = px & 255u, g = (px >> 8) & 255u, r = px >> 16;
-  return sat8((-155188 * r - 305135 * g + 460324 * b + (128 << 20) + (1 << 19)) >> 20) |
-         (sat8((460324 * r - 385875 * g - 74448 * b + (128 << 20) + (1 << 19)) >> 20) << 8);
+  unsigned v = sat8((k.vk[0] * r + k.vk[1] * g + k.vk[2] * b + (128 << 20) + (1 << 19)) >> 20);
+  asm volatile("" : "+v"(v));
+  return sat8((k.uk[0] * r + k.uk[1] * g + k.uk[2] * b + (128 << 20) + (1 << 19)) >> 20) | (v << 8);
+}
+// VP_CHROMA_MEAN: U | V << 8 of the n = 2 or 4 such (clamped) pairs of a group, (sum + n / 2) / n per component
+__device__ __forceinline__ unsigned chroma_mean2(unsigned a, unsigned b) {
+  const unsigned u = (a & 255u) + (b & 255u) + 1u, v = (a >> 8) + (b >> 8) + 1u;
+  return (u >> 1) | ((v >> 1) << 8);
+}
+__device__ __forceinline__ unsigned chroma_mean4(unsigned a, unsigned b, unsigned c, unsigned d) {
+  const unsigned u = (a & 255u) + (b & 255u) + (c & 255u) + (d & 255u) + 2u, v = (a >> 8) + (b >> 8) + (c >> 8) + (d >> 8) + 2u;
+  return (u >> 2) | ((v >> 2) << 8);
 }
 __device__ __forceinline__ unsigned swap_rb(unsigned px) { return (px & 0x00FF00u) | (px >> 16) | ((px & 255u) << 16); }
 __global__ __launch_bounds__(256) void canvas_to_format_kernel(const CanvasToFormatParams p) {
   const int bpr = (p.w + 3) >> 2;
-  const int rows = p.format == 5 ? p.h >> 1 : p.h;
+  const bool f420 = p.format == 5 || p.format >= 16;       // NV12, I420 (YV12 arrives as I420), NV21
+  const int rows = f420 ? p.h >> 1 : p.h;
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= (long long)rows * bpr) return;
   const int r = (int)(t / bpr), j = (int)(t - (long long)r * bpr), x0 = 4 * j;
   const size_t pitch = (size_t)p.dst_pitch;
   unsigned px[4];
-  if (p.format == 5) {   // NV12: rows 2r, 2r + 1; chroma of the top-left pixel of each 2x2 block
-    unsigned px1[4], y0 = 0u, y1 = 0u, uv = 0u;
+  if (f420) {   // rows 2r, 2r + 1; chroma of the top-left pixel of each 2x2 block, or the mean of the block's four
+    unsigned px1[4], y0 = 0u, y1 = 0u, uv[2] = {0u, 0u};
     load_bgr4(p.src + (size_t)(2 * r) * p.src_pitch, j, px);
     load_bgr4(p.src + (size_t)(2 * r + 1) * p.src_pitch, j, px1);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (x0 + k >= p.w) break;
-      y0 |= luma_of(px[k]) << (8 * k);
-      y1 |= luma_of(px1[k]) << (8 * k);
-      if (!(k & 1)) uv |= chroma_of(px[k]) << (8 * k);
+      y0 |= luma_of(p.k, px[k]) << (8 * k);
+      y1 |= luma_of(p.k, px1[k]) << (8 * k);
+    }
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      if (x0 + 2 * g >= p.w) break;                        // w is even: a group is whole or absent
+      const unsigned c = chroma_of(p.k, px[2 * g]);
+      uv[g] = p.chroma_mean ? chroma_mean4(c, chroma_of(p.k, px[2 * g + 1]), chroma_of(p.k, px1[2 * g]), chroma_of(p.k, px1[2 * g + 1])) : c;
     }
     *reinterpret_cast<uint32_t*>(p.p0 + (size_t)(2 * r) * pitch + 4 * (size_t)j) = y0;
     *reinterpret_cast<uint32_t*>(p.p0 + (size_t)(2 * r + 1) * pitch + 4 * (size_t)j) = y1;
-    *reinterpret_cast<uint32_t*>(p.p1 + (size_t)r * pitch + 4 * (size_t)j) = uv;
+    const size_t crow = (size_t)r * p.dst_pitch_c;
+    if (p.format == 16) {   // I420: a plane each, this block's two samples as one 16-bit store
+      *reinterpret_cast<uint16_t*>(p.p1 + crow + 2 * (size_t)j) = (uint16_t)((uv[0] & 255u) | ((uv[1] & 255u) << 8));
+      *reinterpret_cast<uint16_t*>(p.p2 + crow + 2 * (size_t)j) = (uint16_t)((uv[0] >> 8) | ((uv[1] >> 8) << 8));
+    } else {                // NV12: U V pairs; NV21: V U
+      if (p.format == 18) {
+        uv[0] = (uv[0] >> 8) | ((uv[0] & 255u) << 8);
+        uv[1] = (uv[1] >> 8) | ((uv[1] & 255u) << 8);
+      }
+      *reinterpret_cast<uint32_t*>(p.p1 + crow + 4 * (size_t)j) = uv[0] | (uv[1] << 16);
+    }
     return;
   }
   load_bgr4(p.src + (size_t)r * p.src_pitch, j, px);
@@ -633,13 +666,15 @@ __global__ __launch_bounds__(256) void canvas_to_format_kernel(const CanvasToFor
   for (int k = 0; k < 4; ++k)
     if (x0 + k >= p.w) px[k] = 0u;   // behind the row's end: zero bytes out, whatever the canvas carries there
   uint8_t* drow = p.p0 + (size_t)r * pitch;
-  if (p.format >= 6) {   // YUY2: Y0 U Y1 V; UYVY: U Y0 V Y1 -- one word per pixel pair, chroma of the even pixel
+  if (p.format >= 6) {   // YUY2: Y0 U Y1 V; UYVY: U Y0 V Y1 -- one word per pixel pair, chroma of the even pixel or the mean of the pair
     uint32_t* d = reinterpret_cast<uint32_t*>(drow + 8 * (size_t)j);
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       unsigned wd = 0u;
       if (x0 + 2 * g < p.w) {
-        const unsigned ya = luma_of(px[2 * g]), yb = luma_of(px[2 * g + 1]), c = chroma_of(px[2 * g]);
+        const unsigned ya = luma_of(p.k, px[2 * g]), yb = luma_of(p.k, px[2 * g + 1]);
+        unsigned c = chroma_of(p.k, px[2 * g]);
+        if (p.chroma_mean) c = chroma_mean2(c, chroma_of(p.k, px[2 * g + 1]));
         wd = p.format == 6 ? (ya | ((c & 255u) << 8) | (yb << 16) | ((c >> 8) << 24)) : ((c & 255u) | (ya << 8) | ((c >> 8) << 16) | (yb << 24));
       }
       d[g] = wd;
@@ -648,7 +683,7 @@ __global__ __launch_bounds__(256) void canvas_to_format_kernel(const CanvasToFor
     unsigned wd = 0u;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (x0 + k < p.w) wd |= luma_of(px[k]) << (8 * k);
+      if (x0 + k < p.w) wd |= luma_of(p.k, px[k]) << (8 * k);
     *reinterpret_cast<uint32_t*>(drow + 4 * (size_t)j) = wd;
   } else if (p.format >= 2) {   // BGRA8 / RGBA8: alpha 255
     uint32_t* d = reinterpret_cast<uint32_t*>(drow + 16 * (size_t)j);
@@ -777,12 +812,18 @@ __global__ __launch_bounds__(256) void act_exp_hist_kernel(const half_t* hi, con
 hipError_t launch_preprocess(const PreprocessParams& p, hipStream_t st) {
   VP_LAUNCH(preprocess_kernel, dim3(nblk(p.out_w), p.out_h), dim3(256), 0, st, p);
 }
-hipError_t launch_frame_to_bgr8(const FrameToBgrParams& p, hipStream_t st) {
-  const bool pairs = p.format >= 5;   // 4:2:x: whole chroma groups only
-  if (!p.p0 || !p.dst || p.format < 0 || p.format >= kFrameFormats || p.h < 2 || p.w < 2 || (pairs && (p.w & 1)) || (p.format == 5 && (!p.p1 || (p.h & 1))) ||
-      p.dst_pitch < frame_bgr_pitch(p.w) || (p.dst_pitch & 3) || (reinterpret_cast<uintptr_t>(p.dst) & 3))
+hipError_t launch_frame_to_bgr8(const FrameToBgrParams& q, hipStream_t st) {
+  FrameToBgrParams p = q;
+  const bool pairs = p.format >= 5, f420 = frame_format_420(p.format);   // 4:2:x: whole chroma groups only
+  if (!p.p0 || !p.dst || frame_format_index(p.format) < 0 || p.h < 2 || p.w < 2 || (pairs && (p.w & 1)) || (f420 && (!p.p1 || (p.h & 1))) ||
+      (frame_format_planar(p.format) && !p.p2) || p.dst_pitch < frame_bgr_pitch(p.w) || (p.dst_pitch & 3) || (reinterpret_cast<uintptr_t>(p.dst) & 3))
     return hipErrorInvalidValue;
-  const long long n = (long long)(p.format == 5 ? p.h / 2 : p.h) * ((p.w + 3) / 4);
+  if (p.format == 17) {   // YV12 = I420 with the chroma planes exchanged
+    std::swap(p.p1, p.p2);
+    std::swap(p.s1, p.s2);
+    p.format = 16;
+  }
+  const long long n = (long long)(f420 ? p.h / 2 : p.h) * ((p.w + 3) / 4);
   VP_LAUNCH(frame_to_bgr8_kernel, dim3(nblk(n)), dim3(256), 0, st, p);
 }
 hipError_t launch_pil_resample(const PilResampleParams& p, hipStream_t st) {
@@ -877,12 +918,19 @@ hipError_t launch_canvas_depth(const float* src, const unsigned* mm, const uint8
   const int nb = ((x0 + w - 1) >> 2) - (x0 >> 2) + 1;
   VP_LAUNCH(canvas_depth_kernel, dim3(nblk(nb), h), dim3(256), 0, st, src, mm, lut, canvas, pitch, x0, y0, w, h);
 }
-hipError_t launch_canvas_to_format(const CanvasToFormatParams& p, hipStream_t st) {
-  const bool pairs = p.format >= 5;
-  if (!p.src || !p.p0 || p.format < 1 || p.format >= kFrameFormats || p.h < 1 || p.w < 1 || (pairs && (p.w & 1)) || (p.format == 5 && (!p.p1 || (p.h & 1))) ||
-      p.src_pitch < frame_bgr_pitch(p.w) || (p.src_pitch & 3) || p.dst_pitch != canvas_plane_pitch(p.format, p.w) || ((reinterpret_cast<uintptr_t>(p.src) | reinterpret_cast<uintptr_t>(p.p0) | reinterpret_cast<uintptr_t>(p.p1)) & 3))
+hipError_t launch_canvas_to_format(const CanvasToFormatParams& q, hipStream_t st) {
+  CanvasToFormatParams p = q;
+  const bool pairs = p.format >= 5, f420 = frame_format_420(p.format);
+  if (!p.src || !p.p0 || p.format < 1 || frame_format_index(p.format) < 0 || p.h < 1 || p.w < 1 || (pairs && (p.w & 1)) || (f420 && (!p.p1 || (p.h & 1))) ||
+      (frame_format_planar(p.format) && !p.p2) || p.src_pitch < frame_bgr_pitch(p.w) || (p.src_pitch & 3) || p.dst_pitch != canvas_plane_pitch(p.format, p.w) ||
+      (f420 && p.dst_pitch_c != canvas_plane_pitch(p.format, p.w, 1)) ||
+      ((reinterpret_cast<uintptr_t>(p.src) | reinterpret_cast<uintptr_t>(p.p0) | reinterpret_cast<uintptr_t>(p.p1) | reinterpret_cast<uintptr_t>(p.p2)) & 3))
     return hipErrorInvalidValue;
-  const long long n = (long long)(p.format == 5 ? p.h / 2 : p.h) * ((p.w + 3) / 4);
+  if (p.format == 17) {   // YV12 = I420 with the chroma planes exchanged
+    std::swap(p.p1, p.p2);
+    p.format = 16;
+  }
+  const long long n = (long long)(f420 ? p.h / 2 : p.h) * ((p.w + 3) / 4);
   VP_LAUNCH(canvas_to_format_kernel, dim3(nblk(n)), dim3(256), 0, st, p);
 }
 hipError_t launch_nchw_to_act(const float* src, int Creal, const ActView& a, hipStream_t st) {

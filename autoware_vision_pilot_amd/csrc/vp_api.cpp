@@ -545,27 +545,30 @@ int frame_guarded(vp_frame* f, F&& fn) {
 
 struct FramePlanes {
   int n = 1;
-  size_t row_bytes[2] = {0, 0};
-  int rows[2] = {0, 0};
+  size_t row_bytes[3] = {0, 0, 0};
+  int rows[3] = {0, 0, 0};
 };
 
-const char* const kFormatNames[vp::kFrameFormats] = {"BGR8", "RGB8", "BGRA8", "RGBA8", "GRAY8", "NV12", "YUY2", "UYVY"};
+const char* const kFormatNames[vp::kFrameFormats] = {"BGR8", "RGB8", "BGRA8", "RGBA8", "GRAY8", "NV12", "YUY2", "UYVY", "I420", "YV12", "NV21"};
 
-// the planes an h x w image has in `format` (vp_frame_upload*, vp_canvas_layout / vp_canvas_fetch), and the refusals of the geometry
+int format_planes(int format) { return vp::frame_format_planar(format) ? 3 : (vp::frame_format_420(format) ? 2 : 1); }
+
+// the planes an h x w image has in `format` (vp_frame_upload*, vp_canvas_layout* / vp_canvas_fetch), and the refusals of the geometry
 FramePlanes frame_layout(const std::string& me, int format, int h, int w) {
-  static const int px_bytes[vp::kFrameFormats] = {3, 3, 4, 4, 1, 1, 2, 2};
-  if (format < 0 || format >= vp::kFrameFormats) throw std::invalid_argument(me + ": unknown format " + std::to_string(format));
-  const std::string fmt = kFormatNames[format];
+  static const int px_bytes[vp::kFrameFormats] = {3, 3, 4, 4, 1, 1, 2, 2, 1, 1, 1};
+  const int fi = vp::frame_format_index(format);
+  if (fi < 0) throw std::invalid_argument(me + ": unknown format " + std::to_string(format));
+  const std::string fmt = kFormatNames[fi];
   if (h < 2 || w < 2 || h > 16384 || w > 16384) throw std::invalid_argument(me + ": frame size " + std::to_string(w) + " x " + std::to_string(h) + " (2 .. 16384 each way)");
   if (format >= VP_FRAME_NV12 && (w & 1)) throw std::invalid_argument(me + ": " + fmt + " needs an even width (one chroma pair per two pixels), got " + std::to_string(w));
-  if (format == VP_FRAME_NV12 && (h & 1)) throw std::invalid_argument(me + ": NV12 needs an even height (one chroma pair per 2x2 block), got " + std::to_string(h));
+  if (vp::frame_format_420(format) && (h & 1)) throw std::invalid_argument(me + ": " + fmt + " needs an even height (one chroma pair per 2x2 block), got " + std::to_string(h));
   FramePlanes fp;
-  fp.n = format == VP_FRAME_NV12 ? 2 : 1;
-  fp.row_bytes[0] = (size_t)px_bytes[format] * w;
+  fp.n = format_planes(format);
+  fp.row_bytes[0] = (size_t)px_bytes[fi] * w;
   fp.rows[0] = h;
-  if (fp.n == 2) {
-    fp.row_bytes[1] = (size_t)w;   // w / 2 interleaved (U, V) pairs
-    fp.rows[1] = h / 2;
+  for (int i = 1; i < fp.n; ++i) {
+    fp.row_bytes[i] = fp.n == 2 ? (size_t)w : (size_t)w / 2;   // w / 2 interleaved pairs, or w / 2 samples of one plane
+    fp.rows[i] = h / 2;
   }
   return fp;
 }
@@ -573,9 +576,10 @@ FramePlanes frame_layout(const std::string& me, int format, int h, int w) {
 // the refusals of vp_frame_upload* / vp_canvas_fetch, and the planes the format has
 FramePlanes check_frame_planes(const char* who, int format, const void* const* planes, const int* strides, int n_planes, int h, int w) {
   const std::string me(who);
-  if (format < 0 || format >= vp::kFrameFormats) throw std::invalid_argument(me + ": unknown format " + std::to_string(format));
-  const int n = format == VP_FRAME_NV12 ? 2 : 1;
-  if (n_planes != n) throw std::invalid_argument(me + ": " + kFormatNames[format] + " has " + std::to_string(n) + " plane(s), got n_planes = " + std::to_string(n_planes));
+  const int fi = vp::frame_format_index(format);
+  if (fi < 0) throw std::invalid_argument(me + ": unknown format " + std::to_string(format));
+  const int n = format_planes(format);
+  if (n_planes != n) throw std::invalid_argument(me + ": " + kFormatNames[fi] + " has " + std::to_string(n) + " plane(s), got n_planes = " + std::to_string(n_planes));
   if (!planes || !strides) throw std::invalid_argument(me + ": null planes / strides");
   const FramePlanes fp = frame_layout(me, format, h, w);
   for (int i = 0; i < fp.n; ++i) {
@@ -584,6 +588,11 @@ FramePlanes check_frame_planes(const char* who, int format, const void* const* p
       throw std::invalid_argument(me + ": stride " + std::to_string(strides[i]) + " of plane " + std::to_string(i) + " is below the row's " + std::to_string(fp.row_bytes[i]) + " bytes");
   }
   return fp;
+}
+
+void check_color(const std::string& me, int matrix, int range) {
+  if (matrix != VP_COLOR_BT601 && matrix != VP_COLOR_BT709) throw std::invalid_argument(me + ": unknown colour matrix " + std::to_string(matrix) + " (VP_COLOR_BT601, VP_COLOR_BT709)");
+  if (range != VP_COLOR_RANGE_LIMITED && range != VP_COLOR_RANGE_FULL) throw std::invalid_argument(me + ": unknown colour range " + std::to_string(range) + " (VP_COLOR_RANGE_LIMITED, VP_COLOR_RANGE_FULL)");
 }
 
 template <class T>
@@ -625,17 +634,21 @@ void end_upload(vp_frame* f, int h, int w) {
   f->uploaded = true;
 }
 
-void convert_planes(vp_frame* f, int format, const uint8_t* p0, int s0, const uint8_t* p1, int s1, int h, int w) {
+// planes / strides in the format's own order, device memory
+void convert_planes(vp_frame* f, int format, const uint8_t* const* p, const int* s, int n, int h, int w) {
   vp::FrameToBgrParams q{};
-  q.p0 = p0;
-  q.p1 = p1;
-  q.s0 = s0;
-  q.s1 = s1;
+  q.p0 = p[0];
+  q.s0 = s[0];
+  q.p1 = n > 1 ? p[1] : nullptr;
+  q.s1 = n > 1 ? s[1] : 0;
+  q.p2 = n > 2 ? p[2] : nullptr;
+  q.s2 = n > 2 ? s[2] : 0;
   q.h = h;
   q.w = w;
   q.format = format;
   q.dst = f->d_bgr;
   q.dst_pitch = vp::frame_bgr_pitch(w);
+  q.k = vp::color_standard(f->color_matrix, f->color_range).inv;
   VP_HIP_CHECK(vp::launch_frame_to_bgr8(q, f->stream));
 }
 
@@ -703,7 +716,15 @@ int vp_frame_upload(vp_frame* f, int format, const uint8_t* const* planes, const
       else VP_HIP_CHECK(hipMemcpyAsync(f->d_src, slot, total, hipMemcpyHostToDevice, f->stream));
       VP_HIP_CHECK(hipEventRecord(f->stage_ev[f->stage_slot], f->stream));
     }
-    if (!bgr) convert_planes(f, format, f->d_src, (int)fp.row_bytes[0], fp.n == 2 ? f->d_src + fp.row_bytes[0] * fp.rows[0] : nullptr, (int)fp.row_bytes[1], h, w);
+    if (!bgr) {   // d_src: rows packed, plane after plane
+      const uint8_t* dp[3] = {f->d_src, nullptr, nullptr};
+      int ds[3] = {0, 0, 0};
+      for (int i = 0; i < fp.n; ++i) {
+        ds[i] = (int)fp.row_bytes[i];
+        if (i + 1 < fp.n) dp[i + 1] = dp[i] + fp.row_bytes[i] * fp.rows[i];
+      }
+      convert_planes(f, format, dp, ds, fp.n, h, w);
+    }
     end_upload(f, h, w);
   });
 }
@@ -719,10 +740,24 @@ int vp_frame_upload_device(vp_frame* f, int format, const void* const* dev_plane
     if (format == VP_FRAME_BGR8)
       VP_HIP_CHECK(hipMemcpy2DAsync(f->d_bgr, vp::frame_bgr_pitch(w), dev_planes[0], strides[0], fp.row_bytes[0], h, hipMemcpyDeviceToDevice, f->stream));
     else
-      convert_planes(f, format, static_cast<const uint8_t*>(dev_planes[0]), strides[0], fp.n == 2 ? static_cast<const uint8_t*>(dev_planes[1]) : nullptr,
-                     fp.n == 2 ? strides[1] : 0, h, w);
+      convert_planes(f, format, reinterpret_cast<const uint8_t* const*>(dev_planes), strides, fp.n, h, w);
     end_upload(f, h, w);
   });
+}
+
+int vp_frame_set_color(vp_frame* f, int matrix, int range) {
+  return frame_guarded(f, [&] {
+    check_color("vp_frame_set_color", matrix, range);
+    f->color_matrix = matrix;
+    f->color_range = range;
+  });
+}
+
+int vp_frame_get_color(const vp_frame* f, int* matrix, int* range) {
+  if (!f || !matrix || !range) return VP_ERR_ARG;
+  *matrix = f->color_matrix;
+  *range = f->color_range;
+  return VP_OK;
 }
 
 int vp_frame_sync(vp_frame* f) {
@@ -887,12 +922,12 @@ int vp_canvas_device(const vp_canvas* c, void** dev_bgr8, int* pitch_bytes) {
   return VP_OK;
 }
 
-int vp_canvas_layout(int format, int h, int w, int* n_planes, int row_bytes[2], int rows[2]) {
+int vp_canvas_layout3(int format, int h, int w, int* n_planes, int row_bytes[3], int rows[3]) {
   if (!n_planes || !row_bytes || !rows) return VP_ERR_ARG;
   try {
-    const FramePlanes fp = frame_layout("vp_canvas_layout", format, h, w);
+    const FramePlanes fp = frame_layout("vp_canvas_layout3", format, h, w);
     *n_planes = fp.n;
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < 3; ++i) {
       row_bytes[i] = (int)fp.row_bytes[i];
       rows[i] = fp.rows[i];
     }
@@ -900,6 +935,33 @@ int vp_canvas_layout(int format, int h, int w, int* n_planes, int row_bytes[2], 
   } catch (const std::exception&) {
     return VP_ERR_ARG;
   }
+}
+
+int vp_canvas_layout(int format, int h, int w, int* n_planes, int row_bytes[2], int rows[2]) {
+  if (!n_planes || !row_bytes || !rows || format_planes(format) > 2) return VP_ERR_ARG;   // the three-plane formats: vp_canvas_layout3
+  int rb[3], rw[3];
+  const int rc = vp_canvas_layout3(format, h, w, n_planes, rb, rw);
+  if (rc != VP_OK) return rc;
+  for (int i = 0; i < 2; ++i) {
+    row_bytes[i] = rb[i];
+    rows[i] = rw[i];
+  }
+  return VP_OK;
+}
+
+int vp_canvas_set_color(vp_canvas* c, int matrix, int range, int chroma_mode) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    check_color("vp_canvas_set_color", matrix, range);
+    if (chroma_mode != VP_CHROMA_EVEN && chroma_mode != VP_CHROMA_MEAN)
+      throw std::invalid_argument("vp_canvas_set_color: unknown chroma mode " + std::to_string(chroma_mode) + " (VP_CHROMA_EVEN, VP_CHROMA_MEAN)");
+    g.set_color(matrix, range, chroma_mode);
+  });
+}
+
+int vp_canvas_get_color(const vp_canvas* c, int* matrix, int* range, int* chroma_mode) {
+  if (!c || !c->impl || !matrix || !range || !chroma_mode) return VP_ERR_ARG;
+  c->impl->get_color(matrix, range, chroma_mode);
+  return VP_OK;
 }
 
 int vp_canvas_fetch(vp_canvas* c, int format, uint8_t* const* planes, const int* strides, int n_planes) {

@@ -33,6 +33,7 @@ struct vp_frame {
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   int h = 0, w = 0, pitch = 0;
   bool uploaded = false;
+  int color_matrix = 0, color_range = 0;   // vp_frame_set_color: the standard of later YUV uploads (BT.601, limited range)
   hipEvent_t ready = nullptr;     // content complete
   hipEvent_t producer = nullptr;  // vp_frame_upload_device: recorded on the caller's producer stream
   struct Consumer {

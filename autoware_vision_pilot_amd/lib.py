@@ -156,6 +156,8 @@ _SIGS = {
     "vp_frame_last_error": (C.c_char_p, [_P]),
     "vp_frame_upload": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]),
     "vp_frame_upload_device": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, _P]),
+    "vp_frame_set_color": (C.c_int, [_P, C.c_int, C.c_int]),
+    "vp_frame_get_color": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vp_frame_sync": (C.c_int, [_P]),
     "vp_frame_dims": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vp_frame_fetch_bgr8": (C.c_int, [_P, _P, C.c_int]),
@@ -174,6 +176,9 @@ _SIGS = {
     "vp_canvas_dims": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vp_canvas_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int)]),
     "vp_canvas_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vp_canvas_layout3": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vp_canvas_set_color": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "vp_canvas_get_color": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vp_canvas_fetch": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int]),
 }
 # multi-camera exchange (csrc/vp_comm.cpp): part of libvp_hip.so, absent from the CPU-emulated test build
@@ -198,9 +203,21 @@ VP_COMM_ID_BYTES = 128
 VP_RANGE_BINS, VP_RANGE_EXP_MIN = 40, -24
 VP_VIZ_SCENE, VP_VIZ_DOMAIN, VP_VIZ_EGOLANES = 0, 1, 2
 VP_FRAME_BGR8, VP_FRAME_RGB8, VP_FRAME_BGRA8, VP_FRAME_RGBA8, VP_FRAME_GRAY8, VP_FRAME_NV12, VP_FRAME_YUY2, VP_FRAME_UYVY = range(8)
+VP_FRAME_I420, VP_FRAME_YV12, VP_FRAME_NV21 = 16, 17, 18
 FRAME_FORMATS = {"bgr8": VP_FRAME_BGR8, "rgb8": VP_FRAME_RGB8, "bgra8": VP_FRAME_BGRA8, "rgba8": VP_FRAME_RGBA8, "gray8": VP_FRAME_GRAY8, "nv12": VP_FRAME_NV12,
-                 "yuy2": VP_FRAME_YUY2, "uyvy": VP_FRAME_UYVY}
-_FRAME_PX_BYTES = (3, 3, 4, 4, 1, 1, 2, 2)   # bytes per pixel of plane 0
+                 "yuy2": VP_FRAME_YUY2, "uyvy": VP_FRAME_UYVY, "i420": VP_FRAME_I420, "yv12": VP_FRAME_YV12, "nv21": VP_FRAME_NV21}
+_FRAME_PX_BYTES = {0: 3, 1: 3, 2: 4, 3: 4, 4: 1, 5: 1, 6: 2, 7: 2, 16: 1, 17: 1, 18: 1}   # bytes per pixel of plane 0
+_FRAME_PLANES = {VP_FRAME_NV12: 2, VP_FRAME_NV21: 2, VP_FRAME_I420: 3, VP_FRAME_YV12: 3}    # every other format: 1
+VP_COLOR_BT601, VP_COLOR_BT709 = 0, 1
+VP_COLOR_RANGE_LIMITED, VP_COLOR_RANGE_FULL = 0, 1
+VP_CHROMA_EVEN, VP_CHROMA_MEAN = 0, 1
+COLOR_MATRICES = {"bt601": VP_COLOR_BT601, "bt709": VP_COLOR_BT709}
+COLOR_RANGES = {"limited": VP_COLOR_RANGE_LIMITED, "full": VP_COLOR_RANGE_FULL}
+CHROMA_MODES = {"even": VP_CHROMA_EVEN, "mean": VP_CHROMA_MEAN}
+
+
+def _named(table, v):
+    return table[v.lower()] if isinstance(v, str) else int(v)
 
 
 class RangeStats(C.Structure):
@@ -743,21 +760,33 @@ class Frame:
 
     def upload(self, array_or_planes, fmt="bgr8", hw=None):
         """vp_frame_upload (asynchronous).  One uint8 array -- HxWx3 (bgr8 / rgb8), HxWx4 (bgra8 / rgba8), HxW (gray8), Hx(2W) or HxWx2 (yuy2 / uyvy) -- or,
-        for nv12, the pair (Y [H][W], UV [H/2][W]) or one [H * 3 / 2][W] array.  Row strides are taken from the arrays (the bytes of a row must be
-        contiguous); `hw` overrides the (h, w) read off plane 0."""
+        for nv12, the pair (Y [H][W], UV [H/2][W]) or one [H * 3 / 2][W] array; for nv21 the pair (Y, VU); for i420 / yv12 the three planes (Y [H][W],
+        then U, V / V, U [H/2][W/2]); for those three also ONE flat contiguous buffer of H * W * 3 / 2 bytes, 1-D (with `hw`) or [H * 3 / 2][W].  Row
+        strides are taken from the arrays (the bytes of a row must be contiguous); `hw` overrides the (h, w) read off plane 0."""
         f = self._fmt(fmt)
         planes = list(array_or_planes) if isinstance(array_or_planes, (list, tuple)) else [array_or_planes]
         planes = [np.asarray(p) for p in planes]
         if f == VP_FRAME_NV12 and len(planes) == 1 and planes[0].ndim == 2 and planes[0].shape[0] % 3 == 0:
             a = planes[0]
             planes = [a[: a.shape[0] // 3 * 2], a[a.shape[0] // 3 * 2:]]
+        if f in (VP_FRAME_I420, VP_FRAME_YV12, VP_FRAME_NV21) and len(planes) == 1:
+            a = np.ascontiguousarray(planes[0], dtype=np.uint8)
+            fh, fw = (int(hw[0]), int(hw[1])) if hw is not None else ((a.shape[0] // 3 * 2, a.shape[1]) if a.ndim == 2 else (0, 0))
+            a = a.reshape(-1)
+            if fh < 2 or fw < 2 or fh % 2 or fw % 2 or a.size != fh * fw * 3 // 2:
+                pass   # not a flat frame of that size: one plane where the format has more, the library words the refusal
+            elif f == VP_FRAME_NV21:
+                planes = [a[:fh * fw].reshape(fh, fw), a[fh * fw:].reshape(fh // 2, fw)]
+            else:
+                q = fh * fw // 4
+                planes = [a[:fh * fw].reshape(fh, fw), a[fh * fw:fh * fw + q].reshape(fh // 2, fw // 2), a[fh * fw + q:].reshape(fh // 2, fw // 2)]
         fixed = []
         for p in planes:
             if p.dtype != np.uint8 or p.ndim < 2 or any(p.strides[i] != int(np.prod(p.shape[i + 1:])) for i in range(1, p.ndim)) or p.strides[0] < 0:
                 p = np.ascontiguousarray(p, dtype=np.uint8)
             fixed.append(p)
         p0 = fixed[0]
-        h, w = (int(hw[0]), int(hw[1])) if hw is not None else (p0.shape[0], int(np.prod(p0.shape[1:])) // _FRAME_PX_BYTES[f] if 0 <= f < 8 else 0)
+        h, w = (int(hw[0]), int(hw[1])) if hw is not None else (p0.shape[0], int(np.prod(p0.shape[1:])) // _FRAME_PX_BYTES[f] if f in _FRAME_PX_BYTES else 0)
         self._keep = fixed   # a registered pool is read by DMA after the call returns
         arr = (_P * len(fixed))(*[p.ctypes.data for p in fixed])
         strides = (C.c_int * len(fixed))(*[int(p.strides[0]) for p in fixed])
@@ -770,6 +799,16 @@ class Frame:
         arr = (_P * len(plane_ptrs))(*[int(p) for p in plane_ptrs])
         st = (C.c_int * len(strides))(*[int(s) for s in strides])
         self._ck(self._lib.vp_frame_upload_device(self._h, self._fmt(fmt), arr, st, len(plane_ptrs), int(h), int(w), _P(int(producer_stream)) if producer_stream else None))
+
+    def set_color(self, matrix="bt601", range="limited"):  # noqa: A002 -- the C ABI's word
+        """vp_frame_set_color: the colour standard of LATER YUV uploads -- matrix "bt601" / "bt709", range "limited" / "full" (or the VP_COLOR_* values)"""
+        self._ck(self._lib.vp_frame_set_color(self._h, _named(COLOR_MATRICES, matrix), _named(COLOR_RANGES, range)))
+
+    def get_color(self):
+        """(matrix, range) as VP_COLOR_* values"""
+        m, r = C.c_int(), C.c_int()
+        self._ck(self._lib.vp_frame_get_color(self._h, C.byref(m), C.byref(r)))
+        return m.value, r.value
 
     def sync(self):
         self._ck(self._lib.vp_frame_sync(self._h))
@@ -795,6 +834,15 @@ def canvas_layout(fmt, h, w):
     rb, rows = (C.c_int * 2)(), (C.c_int * 2)()
     if load().vp_canvas_layout(Frame._fmt(fmt), int(h), int(w), C.byref(n), rb, rows) != 0:
         raise ValueError(f"vp_canvas_layout: no {fmt} layout for a {w} x {h} picture")
+    return [(rb[i], rows[i]) for i in range(n.value)]
+
+
+def canvas_layout3(fmt, h, w):
+    """vp_canvas_layout3 (host only): canvas_layout for every format, the three-plane ones (i420, yv12) included"""
+    n = C.c_int()
+    rb, rows = (C.c_int * 3)(), (C.c_int * 3)()
+    if load().vp_canvas_layout3(Frame._fmt(fmt), int(h), int(w), C.byref(n), rb, rows) != 0:
+        raise ValueError(f"vp_canvas_layout3: no {fmt} layout for a {w} x {h} picture")
     return [(rb[i], rows[i]) for i in range(n.value)]
 
 
@@ -874,20 +922,34 @@ class Canvas:
             raise VpError(f"vp_canvas_device failed ({rc}): the canvas holds no picture yet")
         return p.value, pitch.value
 
+    def set_color(self, matrix="bt601", range="limited", chroma_mode="even"):  # noqa: A002 -- the C ABI's word
+        """vp_canvas_set_color: the colour standard and chroma rule ("even" / "mean") of LATER fetches into the YUV formats and gray8.  Not inherited from
+        the frame the canvas is begun on."""
+        self._ck(self._lib.vp_canvas_set_color(self._h, _named(COLOR_MATRICES, matrix), _named(COLOR_RANGES, range), _named(CHROMA_MODES, chroma_mode)))
+
+    def get_color(self):
+        """(matrix, range, chroma_mode) as VP_COLOR_* / VP_CHROMA_* values"""
+        m, r, k = C.c_int(), C.c_int(), C.c_int()
+        self._ck(self._lib.vp_canvas_get_color(self._h, C.byref(m), C.byref(r), C.byref(k)))
+        return m.value, r.value, k.value
+
     def fetch(self, fmt="bgr8", strides=None):
-        """vp_canvas_fetch (synchronous): the picture as numpy planes -- bgr8 / rgb8 HxWx3, bgra8 / rgba8 HxWx4, gray8 HxW, yuy2 / uyvy Hx(2W), nv12 the
-        pair (Y [H][W], UV [H/2][W]).  `strides`: row strides in bytes of the buffers fetched into (default: packed)."""
+        """vp_canvas_fetch (synchronous): the picture as numpy planes -- bgr8 / rgb8 HxWx3, bgra8 / rgba8 HxWx4, gray8 HxW, yuy2 / uyvy Hx(2W), nv12 / nv21
+        the pair (Y [H][W], UV / VU [H/2][W]), i420 / yv12 the three planes (Y [H][W], U, V / V, U [H/2][W/2]).  `strides`: row strides in bytes of the
+        buffers fetched into (default: packed)."""
         f = Frame._fmt(fmt)
         h, w = self.hw()
         n = C.c_int()
-        rb, rows = (C.c_int * 2)(), (C.c_int * 2)()
-        if not 0 <= f < 8 or self._lib.vp_canvas_layout(f, h, w, C.byref(n), rb, rows) != 0:
-            n.value, rb[0], rows[0], rb[1], rows[1] = (2 if f == VP_FRAME_NV12 else 1), 1, 1, 1, 1   # no layout: the library words the refusal
+        rb, rows = (C.c_int * 3)(), (C.c_int * 3)()
+        if self._lib.vp_canvas_layout3(f, h, w, C.byref(n), rb, rows) != 0:
+            n.value = _FRAME_PLANES.get(f, 1)   # no layout: the library words the refusal
+            for i in range(3):
+                rb[i], rows[i] = 1, 1
         st = [int(v) for v in strides] if strides is not None else [rb[i] for i in range(n.value)]
-        bufs = [np.zeros((rows[min(i, 1)], max(st[i], 1)), np.uint8) for i in range(len(st))]
+        bufs = [np.zeros((rows[min(i, 2)], max(st[i], 1)), np.uint8) for i in range(len(st))]
         arr = (_P * len(bufs))(*[b.ctypes.data for b in bufs])
         self._ck(self._lib.vp_canvas_fetch(self._h, f, arr, (C.c_int * len(st))(*st), len(st)))
-        planes = [np.ascontiguousarray(b[:, :rb[i]]) for i, b in enumerate(bufs)]
+        planes = [np.ascontiguousarray(b[:, :rb[min(i, 2)]]) for i, b in enumerate(bufs)]
         if f <= VP_FRAME_RGBA8:
             planes[0] = planes[0].reshape(h, w, _FRAME_PX_BYTES[f])
         return planes[0] if len(planes) == 1 else tuple(planes)

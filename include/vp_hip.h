@@ -353,15 +353,32 @@ int vp_timer_end(vp_engine* e, float* elapsed_ms);                             /
  *     vp_frame_upload(f, VP_FRAME_YUY2, &data, &stride, 1, 720, 1280);
  *     thread A: vp_infer_frame(egolanes, f, 0, 420, 1280, 300);      thread B: vp_detect_infer_frame(det, f, 0, 0, 0, 0, ...);
  * A vp_frame always holds packed BGR8.  BGR8 is copied straight in; RGB8 / BGRA8 / RGBA8 are permuted or lose alpha; GRAY8 is replicated to three
- * channels; the YUV formats use the integer BT.601 limited-range form OpenCV documents for cvtColor(COLOR_YUV2BGR_NV12 / _YUY2 / _UYVY): 20-bit fixed
- * point, no chroma interpolation (NV12 shares one (U, V) per 2x2 block, YUY2 = Y0 U Y1 V and UYVY = U Y0 V Y1 one per horizontal pixel pair):
+ * channels; the YUV formats use, by default, the integer BT.601 limited-range form OpenCV documents for cvtColor(COLOR_YUV2BGR_NV12 / _YUY2 / _UYVY):
+ * 20-bit fixed point, no chroma interpolation (NV12 / NV21 / I420 / YV12 share one (U, V) per 2x2 block, YUY2 = Y0 U Y1 V and UYVY = U Y0 V Y1 one per
+ * horizontal pixel pair):
  *     y = 1220542 * max(0, Y - 16);  u = U - 128;  v = V - 128
  *     R = sat8((y + 1673527 * v               + (1 << 19)) >> 20)
  *     G = sat8((y -  852492 * v - 409993 * u  + (1 << 19)) >> 20)
  *     B = sat8((y + 2116026 * u               + (1 << 19)) >> 20)         arithmetic shift, then clamp to 0 .. 255
  * This formula IS the definition; parity with OpenCV itself is not pinned (OpenCV is absent here: DESIGN.md section 4).
- * planes / strides: 1 plane (2 for NV12: Y, then interleaved UV), strides in bytes.  VP_ERR_ARG (with text): odd w for NV12 / YUY2 / UYVY, odd h for
- * NV12, h or w below 2, a stride below the row's bytes, a wrong n_planes, an unknown format.
+ * COLOUR STANDARD.  vp_frame_set_color(f, matrix, range) chooses the constants of LATER uploads of the YUV formats (the picture a frame already holds
+ * stays as its upload made it); the default (VP_COLOR_BT601, VP_COLOR_RANGE_LIMITED) is the formula above, to the bit.  The form never changes:
+ *     y = CY * max(0, Y - off);  u = U - 128;  v = V - 128
+ *     R = sat8((y + CVR v + (1 << 19)) >> 20);  G = sat8((y - CVG v - CUG u + (1 << 19)) >> 20);  B = sat8((y + CUB u + (1 << 19)) >> 20)
+ *                        off       CY      CVR      CVG      CUG      CUB
+ *     BT.601 limited      16  1220542  1673527   852492   409993  2116026     OpenCV's constants, kept as they are
+ *     BT.601 full          0  1048576  1470104   748826   360853  1858077
+ *     BT.709 limited      16  1220945  1879825   558796   223607  2215014
+ *     BT.709 full          0  1048576  1651297   490864   196424  1945738
+ * The three new rows are exact: each constant is the nearest integer to coefficient x 2^20, the coefficients derived from (Kr, Kb) = (0.299, 0.114) /
+ * (0.2126, 0.0722) as rationals, scaled by 255/219 (luma) and 255/224 (chroma) in limited range and by 1 in full range.  |y + chroma| < 2^30 for every
+ * byte input.  Black is (off, 128, 128), white (235 or 255, 128, 128).  Like the default they ARE the definition and are not pinned against OpenCV.
+ * HD cameras and hardware decoders deliver BT.709; MJPEG cameras and every JPEG-derived stream are full range (BT.601 full).  The settings do not touch
+ * BGR8 / RGB8 / BGRA8 / RGBA8 / GRAY8 uploads.  VP_ERR_ARG (with text) for an unknown matrix or range; a refused call changes nothing.
+ * planes / strides, in bytes: 1 plane; 2 for NV12 (Y, then interleaved U V) and NV21 (Y, then interleaved V U: rows of w bytes, h / 2 of them); 3 for
+ * I420 (Y, U, V) and YV12 (Y, V, U): chroma planes of h / 2 rows of w / 2 bytes.  One (U, V) per 2x2 block in all four.  VP_ERR_ARG (with text): odd w
+ * for NV12 / YUY2 / UYVY / I420 / YV12 / NV21, odd h for NV12 / I420 / YV12 / NV21, h or w below 2, a stride below the row's bytes, a wrong n_planes, an
+ * unknown format (codes 8 .. 15 are not used).
  * vp_frame_upload is ASYNCHRONOUS on the frame's own stream.  Host planes are staged through the frame's pinned double buffer (copied before the call
  * returns) or, when every plane lies inside a vp_register_frames range, copied by one DMA per plane straight from the caller's memory -- the rules
  * of vp_upload_frame, including that such planes stay unmodified until vp_frame_sync or a consumer's synchronising call.
@@ -378,12 +395,17 @@ int vp_timer_end(vp_engine* e, float* elapsed_ms);                             /
  * (INTEGRATION.md "One camera frame, several networks").  A frame must outlive the passes that consume it.  No process-wide state. */
 typedef struct vp_frame vp_frame;
 enum vp_frame_format { VP_FRAME_BGR8 = 0, VP_FRAME_RGB8 = 1, VP_FRAME_BGRA8 = 2, VP_FRAME_RGBA8 = 3, VP_FRAME_GRAY8 = 4,
-                       VP_FRAME_NV12 = 5, VP_FRAME_YUY2 = 6, VP_FRAME_UYVY = 7 };
+                       VP_FRAME_NV12 = 5, VP_FRAME_YUY2 = 6, VP_FRAME_UYVY = 7, VP_FRAME_I420 = 16, VP_FRAME_YV12 = 17, VP_FRAME_NV21 = 18 };
+enum vp_color_matrix { VP_COLOR_BT601 = 0, VP_COLOR_BT709 = 1 };
+enum vp_color_range { VP_COLOR_RANGE_LIMITED = 0, VP_COLOR_RANGE_FULL = 1 };
+enum vp_chroma_mode { VP_CHROMA_EVEN = 0, VP_CHROMA_MEAN = 1 };
 int vp_frame_create(vp_frame** out, int gpu_id, char* err, size_t err_len);
 void vp_frame_destroy(vp_frame* f);
 const char* vp_frame_last_error(const vp_frame* f);
 int vp_frame_upload(vp_frame* f, int format, const uint8_t* const* planes, const int* strides, int n_planes, int h, int w);
 int vp_frame_upload_device(vp_frame* f, int format, const void* const* dev_planes, const int* strides, int n_planes, int h, int w, void* producer_stream);
+int vp_frame_set_color(vp_frame* f, int matrix, int range);              /* applies to later uploads */
+int vp_frame_get_color(const vp_frame* f, int* matrix, int* range);
 int vp_frame_sync(vp_frame* f);                                          /* waits for the frame's own stream (upload + conversion) */
 int vp_frame_dims(const vp_frame* f, int* h, int* w);                    /* geometry of the last upload; VP_ERR_STATE before it (vp_frame_hw is the engine's) */
 int vp_frame_fetch_bgr8(vp_frame* f, uint8_t* dst, int dst_stride);      /* the converted image, synchronous (tests, hosts that still want a cv::Mat) */
@@ -434,15 +456,32 @@ int vp_infer_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h);
  *   1 (0, 0, 255), 2 (0, 255, 255), 3 (255, 255, 0), anything else white.  Later boxes draw over earlier ones.  n = 0: nothing; VP_ERR_ARG for
  *   n < 0, null with n > 0, a non-finite or absurd (|v| >= 1e8) coordinate.  This rule IS the definition; it is not pinned against OpenCV (absent
  *   here, as for the other OpenCV restatements: DESIGN.md section 4).  Text, the tracked-object style, the CIPO tag and the warnings are not built.
- * vp_canvas_fetch: synchronous; every vp_frame_format.  BGR8 as it is; RGB8 / BGRA8 / RGBA8 permuted, alpha 255; GRAY8 / NV12 / YUY2 / UYVY by the
- *   BT.601 limited-range FORWARD form, the integer counterpart of the upload formula above (20 fractional bits, arithmetic shift, clamp 0 .. 255):
+ * vp_canvas_fetch: synchronous; every vp_frame_format.  BGR8 as it is; RGB8 / BGRA8 / RGBA8 permuted, alpha 255; GRAY8 and the YUV formats by the
+ *   FORWARD form, the integer counterpart of the upload formula above (20 fractional bits, arithmetic shift, clamp 0 .. 255); by default BT.601
+ *   limited range:
  *     Y = ( 269484 R + 528482 G + 102760 B + (16  << 20) + (1 << 19)) >> 20
  *     U = (-155188 R - 305135 G + 460324 B + (128 << 20) + (1 << 19)) >> 20
  *     V = ( 460324 R - 385875 G -  74448 B + (128 << 20) + (1 << 19)) >> 20
- *   GRAY8 is Y; chroma is taken from the EVEN pixel of a pair (NV12: the top-left pixel of the 2x2 block), no averaging.  Black gives (16, 128, 128),
- *   white (235, 128, 128), pure red V = 240.  This formula IS the definition; it is not pinned against OpenCV.  Refusals as vp_frame_upload: odd w
- *   for NV12 / YUY2 / UYVY, odd h for NV12, a stride below the row's bytes, a wrong n_planes, an unknown format.  vp_canvas_layout (host only, no
- *   device) answers the planes of (format, h, w): n_planes, bytes per row and rows of each; VP_ERR_ARG for the same geometry refusals.
+ *   GRAY8 is Y; chroma is taken from the EVEN pixel of a pair (the 2x2 formats: the top-left pixel of the block), no averaging.  Black gives
+ *   (16, 128, 128), white (235, 128, 128), pure red V = 240.  This formula IS the definition; it is not pinned against OpenCV.
+ *   vp_canvas_set_color(c, matrix, range, chroma_mode) chooses the standard and the chroma rule of LATER fetches; it outlives vp_canvas_begin.  A canvas
+ *   does NOT inherit the standard of the frame it was begun on: a host that wants the camera's standard back sets it here as well.  The default
+ *   (VP_COLOR_BT601, VP_COLOR_RANGE_LIMITED, VP_CHROMA_EVEN) is the formula above, to the bit.  In general
+ *     Y = (YR R + YG G + YB B + (off << 20) + (1 << 19)) >> 20;   U, V likewise with (128 << 20) in place of the offset
+ *                        off       YR      YG      YB        UR       UG      UB       VR       VG      VB
+ *     BT.601 limited      16   269484  528482  102760   -155188  -305135  460324   460324  -385875  -74448
+ *     BT.601 full          0   313524  615514  119538   -176932  -347356  524288   524288  -439026  -85262
+ *     BT.709 limited      16   191455  644067   65019   -105533  -355018  460551   460551  -418321  -42230
+ *     BT.709 full          0   222927  749942   75707   -120138  -404150  524288   524288  -476214  -48074
+ *   The three new rows are the nearest integers to coefficient x 2^20 (derived as for the upload), except UB and VR, which are minus the sum of their
+ *   row's other two constants, so that grey gives exactly (128, 128).  |pre-shift| < 2^30 for every byte input.  In full range pure blue (U) and pure
+ *   red (V) reach 256 before the clamp: there the clamp decides.  GRAY8 is the Y of the chosen standard; the RGB family is untouched.
+ *   VP_CHROMA_MEAN: U and V are first formed per pixel as clamped bytes by the forward formula; a 2x2 group (NV12 / NV21 / I420 / YV12) then stores
+ *   (a + b + c + d + 2) >> 2, a 2x1 pair (YUY2 / UYVY) (a + b + 1) >> 1.  VP_CHROMA_EVEN is the rule above.  (Upload has no counterpart: no chroma
+ *   interpolation there.)  VP_ERR_ARG (with text) for an unknown matrix, range or chroma mode.
+ *   Refusals as vp_frame_upload: odd w for the YUV formats, odd h for NV12 / I420 / YV12 / NV21, a stride below the row's bytes, a wrong n_planes, an
+ *   unknown format.  vp_canvas_layout3 (host only, no device) answers the planes of (format, h, w): n_planes, bytes per row and rows of each;
+ *   VP_ERR_ARG for the same geometry refusals.  vp_canvas_layout is the same with room for two planes: VP_ERR_ARG for I420 / YV12.
  * vp_canvas_device / vp_canvas_sync: the device picture (BGR8, rows *pitch_bytes apart) for a device consumer such as an encoder; complete after
  *   vp_canvas_sync, valid until the next vp_canvas_begin or vp_canvas_destroy.
  * ORDERING CONTRACT (vp_frame's, in the other direction).  Nothing waits on the host before vp_canvas_fetch / vp_canvas_sync.  A draw call makes the
@@ -465,6 +504,9 @@ int vp_canvas_sync(vp_canvas* c);
 int vp_canvas_dims(const vp_canvas* c, int* h, int* w);                  /* VP_ERR_STATE before the first vp_canvas_begin */
 int vp_canvas_device(const vp_canvas* c, void** dev_bgr8, int* pitch_bytes);
 int vp_canvas_layout(int format, int h, int w, int* n_planes, int row_bytes[2], int rows[2]);   /* host only */
+int vp_canvas_layout3(int format, int h, int w, int* n_planes, int row_bytes[3], int rows[3]);  /* host only; every format */
+int vp_canvas_set_color(vp_canvas* c, int matrix, int range, int chroma_mode);   /* applies to later fetches; not inherited from the frame */
+int vp_canvas_get_color(const vp_canvas* c, int* matrix, int* range, int* chroma_mode);
 int vp_canvas_fetch(vp_canvas* c, int format, uint8_t* const* planes, const int* strides, int n_planes);
 
 /* ---- multi-camera result exchange (BASELINE configs[3]) ---------------------------------------

@@ -9,7 +9,11 @@ Each in two host shapes, one thread either way: "serial" -- one synchronous call
 enqueued first (vp_upload_frame / vp_upload_from_frame + vp_enqueue), the detector's synchronous call, then vp_fetch_outputs twice -- so the three
 networks share the GPU as the application's threads make them.  No ratio is promised: the figures say what was measured.  Needs a GPU.
 
-python tools/bench_frame.py > profiles/frame_fanout.txt"""
+python tools/bench_frame.py > profiles/frame_fanout.txt
+
+python tools/bench_frame.py --convert: the upload leg alone, no engines -- vp_frame_upload + vp_frame_sync (staging copy, H2D, conversion kernel) of one
+1280 x 720 frame from pageable host memory, p50 / p99 host to host, for every YUV format at the default colour standard and for NV12 / I420 under the
+other three standards (the constants are kernel parameters: a standard should cost nothing)."""
 import json
 import os
 import sys
@@ -40,6 +44,40 @@ def yuv_planes(bgr):
     yuy2 = [np.ascontiguousarray(np.stack([Y[:, 0::2], U[:, 0::2], Y[:, 1::2], V[:, 0::2]], axis=2).reshape(h, 2 * w))]
     return nv12, yuy2
 
+
+def convert_leg(h=720, w=1280, warm=50, timed=500):
+    bgr = synthetic.synthetic_frame(h, w, 21)
+    nv12, yuy2 = yuv_planes(bgr)
+    y, uv = nv12[0], nv12[1].reshape(h // 2, w // 2, 2)
+    u, v = np.ascontiguousarray(uv[:, :, 0]), np.ascontiguousarray(uv[:, :, 1])
+    q = yuy2[0].reshape(h, w // 2, 4)
+    sources = {"nv12": nv12, "nv21": [y, np.ascontiguousarray(uv[:, :, ::-1]).reshape(h // 2, w)], "i420": [y, u, v], "yv12": [y, v, u], "yuy2": yuy2,
+               "uyvy": [np.ascontiguousarray(q[:, :, [1, 0, 3, 2]]).reshape(h, 2 * w)], "bgr8": [bgr.reshape(h, 3 * w)]}
+    default = ("bt601", "limited")
+    cases = [(fmt, default) for fmt in sources] + [(fmt, std) for fmt in ("nv12", "i420") for std in (("bt601", "full"), ("bt709", "limited"), ("bt709", "full"))]
+    res = {"library": lib.version(), "protocol": f"vp_frame_upload + vp_frame_sync of one {w} x {h} frame from pageable host memory; per case {warm} warm-up + {timed} "
+                                                 "timed uploads, one thread, one process; p50 / p99 in us host to host"}
+    f = lib.Frame()
+    for fmt, std in cases:
+        f.set_color(*std)
+        src = sources[fmt]
+        for _ in range(warm):
+            f.upload(src, fmt, hw=(h, w))
+            f.sync()
+        t = []
+        for _ in range(timed):
+            t0 = time.perf_counter()
+            f.upload(src, fmt, hw=(h, w))
+            f.sync()
+            t.append((time.perf_counter() - t0) * 1e6)
+        res[f"{w}x{h}_upload_{fmt}_{std[0]}_{std[1]}_us"] = {"p50": round(float(np.percentile(t, 50)), 1), "p99": round(float(np.percentile(t, 99)), 1)}
+    f.close()
+    print(json.dumps(res, indent=1))
+
+
+if "--convert" in sys.argv[1:]:
+    convert_leg()
+    sys.exit(0)
 
 ego = lib.Engine("egolanes", vw.pack_state_dict(weights.make_state_dict("egolanes", 2)), precision="fp16", plan_latency=True)
 seg = lib.Engine("sceneseg", vw.pack_state_dict(weights.make_state_dict("sceneseg", 0)), precision="fp16", plan_latency=True)
