@@ -235,6 +235,7 @@ class Engine {
                   const std::vector<float>& ws, const std::vector<float>& bs, const std::vector<float>& w3, const std::vector<float>& b3, int cm,
                   int cout, int act, int shape = -1, int nsplit = 0, const std::string& out_name = std::string());
   bool upconv_wanted() const;  // composed up-sampling stages in this engine's plan (parity mode; VP_UPCONV=0: the three-op form of rounds 1-5)
+  Act* alias_slice(const std::string& name, Act* whole, int ch_off, int nch);  // view of channels [ch_off, ch_off + nch) with the tensor's row pitch (no allocation)
   void run_eager();
   void run_ops(hipStream_t st, size_t begin, size_t end);
   void enqueue_multi(const std::vector<Engine*>& heads);
@@ -330,7 +331,6 @@ class Engine {
   };
   AdFeatures build_ad_backbone(const WeightBlob& blob, const std::string& prefix, const std::function<Act*(int, int, int)>& p5_dest);
   void push_op(const std::string& name, const char* kernel, std::function<hipError_t(hipStream_t)> fn, double flops = 0, double bytes = 0);
-  Act* alias_slice(const std::string& name, Act* whole, int ch_off, int nch);  // view of channels [ch_off, ch_off + nch) with the tensor's row pitch (no allocation)
   // blocks of the AutoSpeed / AutoSteer necks (engine.cpp, in front of build_autospeed): Conv + BN + SiLU [+ residual behind the activation], a channel
   // slice copy, C3K2 (common_layers.py:166-180) and cat([up(a), b]) as one launch
   Act* neck_conv_bn(const WeightBlob& blob, const std::string& name, const Act* in, int ks, int stride, const Act* res = nullptr, Act* dst = nullptr);

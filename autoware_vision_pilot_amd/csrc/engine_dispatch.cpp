@@ -520,6 +520,11 @@ void Engine::push_conv_op(const std::string& name, const Act* in, const PackedCo
                           int store_mode, int cout_real) {
   ConvGemmParams p{};
   const int cstride = std::max(1, o.stride);
+  // the epilogues read the residual at the element offset they store at (conv_epilogue.hpp: res_hi + o, out_hi + o): one row pitch, one map size
+  if (o.res_mode != RES_NONE && o.res && out && (o.res->C != out->C || o.res->H != out->H || o.res->W != out->W))
+    throw std::invalid_argument("conv residual: the residual needs the destination's row pitch and map size (" + std::to_string(o.res->C) + " x " +
+                                std::to_string(o.res->H) + " x " + std::to_string(o.res->W) + " against " + std::to_string(out->C) + " x " + std::to_string(out->H) +
+                                " x " + std::to_string(out->W) + "): " + name);
   p.in_hi = in->hi;
   p.in_lo = in->lo;
   p.H = in->H / cstride;  // output size (== input size for stride 1)
@@ -669,6 +674,8 @@ Act* Engine::add_conv(const std::string& name, const Act* in, const std::vector<
   }
   const int cin = in->Creal, cin_pad = in->C, taps = ks * ks;
   if (w.size() != (size_t)cout * cin * taps) throw std::runtime_error("conv weight size mismatch: " + name);
+  // the kernels take the input's channel count as its row pitch (the comment in front of build_autospeed): an alias view narrower than its tensor is no input
+  if (in->C != round_up(in->Creal, 32)) throw std::invalid_argument("conv input: a convolution's input cannot be a slice of a wider tensor: " + name);
   ConvQuery q;
   q.H = in->H, q.W = in->W, q.stride = o.stride;
   q.cin = cin, q.cin_pad = cin_pad, q.cout = cout, q.ks = ks;

@@ -1510,6 +1510,69 @@ int vp_op_conv2d_scaled(int gpu_id, int precision, int mode, const float* in, in
   });
 }
 
+// ---- the convolution forms the networks launch beyond vp_op_conv2d's (unit tests): stride 2, activation behind the residual, alias-slice
+// destination, residual read from a slice, all of them with or without exponents -- through add_conv, as the plan builders do
+int vp_op_conv2d_forms(int gpu_id, int precision, const vp_conv_form* form, const float* in, const float* weight, const float* bias, const float* res,
+                       const float* dst_init, uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!form || !in || !weight || !bias || !out_hi) throw std::invalid_argument("bad argument");
+    const vp_conv_form& f = *form;
+    if (f.cin < 1 || f.cout < 1 || f.h < 1 || f.w < 1 || (long long)f.h * f.w > (1 << 20) || (f.ks != 1 && f.ks != 3) || (f.stride != 1 && f.stride != 2) || f.res_mode < 0 ||
+        f.res_mode > 2 || f.res_where < 0 || f.res_where > 1 || f.res_h < 0 || f.res_w < 0 || (long long)f.res_h * f.res_w > (1 << 20))
+      throw std::invalid_argument("bad argument (ks 1 or 3, stride 1 or 2, res_mode 0 .. 2, res_where 0 or 1)");
+    if (f.dst_c != 0 && (f.dst_c < 32 || (f.dst_c & 31) || f.dst_off < 0 || (f.dst_off & 31) || (f.cout & 31) || f.dst_off + f.cout > f.dst_c))
+      throw std::invalid_argument("bad argument (dst_c, dst_off, cout: multiples of 32 with dst_off + cout <= dst_c)");
+    if (f.res_mode != 0 && f.res_where == 1 && (f.dst_c == 0 || f.res_off < 0 || (f.res_off & 31) || f.res_off + f.cout > f.dst_c))
+      throw std::invalid_argument("bad argument (res_where 1: a slice destination, res_off a multiple of 32 with res_off + cout <= dst_c)");
+    if (f.res_mode != 0 && f.res_where == 0 && !res) throw std::invalid_argument("res_mode set but res is null");
+    if (f.in_c != 0 && (f.in_c < 32 || (f.in_c & 31) || f.in_off < 0 || (f.in_off & 31) || (f.cin & 31) || f.in_off + f.cin > f.in_c))
+      throw std::invalid_argument("bad argument (in_c, in_off, cin: multiples of 32 with in_off + cin <= in_c)");
+    const bool scaled = (f.in_exp | f.res_exp | f.out_exp) != 0 || (precision & VP_ACT_SCALE) != 0;   // the flag alone: a flagged engine with every exponent 0
+    vp::Engine g(-1, nullptr, precision | (scaled ? VP_ACT_SCALE : 0), gpu_id);
+    const int oh = f.h / f.stride, ow = f.w / f.stride;
+    const vp::Act* a;
+    if (f.in_c != 0) {   // only ever refused (add_conv): nothing is uploaded
+      a = g.alias_slice("in", g.new_act("in.whole", f.in_c, f.h, f.w), f.in_off, f.cin);
+    } else {
+      vp::Act* t = g.new_act("in", f.cin, f.h, f.w);
+      upload_act_scaled(g, t, in, f.in_exp);
+      if (scaled) g.set_act_exp(t, f.in_exp);
+      a = t;
+    }
+    vp::Act* dst = nullptr;
+    if (f.dst_c != 0) {
+      dst = g.new_act("dst", f.dst_c, oh, ow);
+      if (dst_init) upload_act_scaled(g, dst, dst_init, f.out_exp);
+      if (scaled) g.set_act_exp(dst, f.out_exp);   // its alias slices share the exponent
+    }
+    vp::ConvOpts o;
+    o.act = f.act;
+    o.post_act = f.post_act;
+    o.stride = f.stride;
+    o.tile = f.tile;
+    o.bk = f.bk;
+    o.nsplit = f.nsplit;
+    if (f.res_mode != 0) {
+      o.res_mode = f.res_mode;
+      if (f.res_where == 1) {
+        o.res = g.alias_slice("res", dst, f.res_off, f.cout);
+      } else {
+        vp::Act* r = g.new_act("res", f.cout, f.res_h > 0 ? f.res_h : oh, f.res_w > 0 ? f.res_w : ow);
+        upload_act_scaled(g, r, res, f.res_exp);
+        if (scaled) g.set_act_exp(r, f.res_exp);
+        o.res = r;
+      }
+    }
+    const size_t wn = (size_t)f.cin * f.cout * f.ks * f.ks;
+    vp::Act* y = g.add_conv("op", a, std::vector<float>(weight, weight + wn), std::vector<float>(bias, bias + f.cout), f.cout, f.ks, o,
+                            dst ? g.alias_slice("op", dst, f.dst_off, f.cout) : nullptr);
+    if (scaled && !dst) g.set_act_exp(y, f.out_exp);
+    g.run_eager();
+    g.sync();
+    read_planes_chw(g, dst ? dst : y, out_hi, out_lo);
+  });
+}
+
 // ---- single-operator entries of the AutoSteer head's kernels (unit tests)
 int vp_op_rowpair_conv(int gpu_id, int precision, const float* in, int cin, int h, int w, const float* weight, const float* bias, int replicate,
                        int dst_c, int dst_off, const float* dst_init, uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len) {

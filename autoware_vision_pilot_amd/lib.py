@@ -137,6 +137,7 @@ _SIGS = {
                                             C.c_char_p, C.c_size_t]),
     "vp_op_lane_rows_head_scaled": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, C.c_int,
                                               _P, C.c_char_p, C.c_size_t]),
+    "vp_op_conv2d_forms": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "vp_version": (C.c_char_p, []),
     "vp_set_lane_ring": (C.c_int, [_P, C.c_int]),
     "vp_lane_ring_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int)]),
@@ -1108,6 +1109,41 @@ def op_conv2d_scaled(x, weight, bias, ks=3, act=0, res=None, res_mode=0, in_exp=
                                     tile, bk, nsplit, int(in_exp), int(res_exp), int(out_exp), _ptr(hi), _ptr(lo), err, len(err))
     if rc != 0:
         raise (ValueError if rc == -1 else VpError)(f"vp_op_conv2d_scaled failed ({rc}): {err.value.decode(errors='replace')}")
+    return hi, lo
+
+
+# vp_conv_form (include/vp_hip.h): its int fields in the header's order
+_CONV_FORM_FIELDS = ("cin", "h", "w", "cout", "ks", "stride", "act", "post_act", "res_mode", "tile", "bk", "nsplit", "dst_c", "dst_off", "res_where", "res_off",
+                     "res_h", "res_w", "in_c", "in_off", "in_exp", "res_exp", "out_exp")
+
+
+def op_conv2d_forms(x, weight, bias, ks=3, stride=1, act=0, post_act=0, res_mode=0, res=None, res_off=None, dst=None, dst_off=0, in_c=0, in_off=0, in_exp=0,
+                    res_exp=0, out_exp=0, precision=VP_FP16X3, tile=-1, bk=-1, nsplit=-1, gpu_id=0):
+    """vp_op_conv2d_forms: Conv2d ks x ks (stride 1 or 2) + bias + act, the residual behind the activation (res_mode 1 add, 2 mul-add), then post_act,
+    through the engine's own add_conv.  dst: None = a fresh output, else the destination's initial content [dst_c][oh][ow], into whose channels
+    [dst_off, dst_off + cout) the launch stores through an alias view.  Residual: `res` [cout][rh][rw] = a fresh tensor (a map size other than the
+    output's is refused), or res_off = channels [res_off, res_off + cout) of the destination itself.  in_c / in_off: the input as an alias view of a
+    wider tensor (always refused).  Exponents: x, res and dst are true values stored as v * 2^-exp (a slice residual under out_exp); all 0 = an
+    unflagged engine.  Returns the STORED (hi, lo) float16 planes of the whole destination [dst_c or cout][oh][ow]."""
+    x, weight, bias, res, dst = _f32(x), _f32(weight), _f32(bias), _f32(res), _f32(dst)
+    cin, h, w = x.shape
+    cout = weight.shape[0]
+    assert weight.shape == (cout, cin, ks, ks) and bias.shape == (cout,) and stride in (1, 2)
+    oh, ow = h // stride, w // stride
+    assert dst is None or dst.shape[1:] == (oh, ow)
+    assert res is None or (res.ndim == 3 and res.shape[0] == cout and res_off is None)
+    f = dict.fromkeys(_CONV_FORM_FIELDS, 0)
+    f.update(cin=cin, h=h, w=w, cout=cout, ks=ks, stride=stride, act=act, post_act=post_act, res_mode=res_mode, tile=tile, bk=bk, nsplit=nsplit,
+             dst_c=0 if dst is None else dst.shape[0], dst_off=dst_off, res_where=0 if res_off is None else 1, res_off=res_off or 0,
+             res_h=0 if res is None else res.shape[1], res_w=0 if res is None else res.shape[2], in_c=in_c, in_off=in_off, in_exp=in_exp, res_exp=res_exp,
+             out_exp=out_exp)
+    form = np.array([int(f[k]) for k in _CONV_FORM_FIELDS], dtype=np.int32)
+    hi = np.empty((cout if dst is None else dst.shape[0], oh, ow), np.float16)
+    lo = np.empty_like(hi)
+    err = C.create_string_buffer(512)
+    pr = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    _op_rc(load().vp_op_conv2d_forms(gpu_id, pr, _ptr(form), _ptr(x), _ptr(weight), _ptr(bias), None if res is None else _ptr(res),
+                                     None if dst is None else _ptr(dst), _ptr(hi), _ptr(lo), err, len(err)), err, "vp_op_conv2d_forms")
     return hi, lo
 
 

@@ -676,6 +676,32 @@ int vp_op_lane_rows_head_scaled(int gpu_id, int precision, const float* features
                                 float c2_b, const float* h1_w, float h1_b, const float* h2_w, float h2_b, int in_exp, float* out_2xh, char* err,
                                 size_t err_len);
 
+/* ---- the convolution forms the networks launch beyond vp_op_conv2d's (unit tests; not used by callers) ------------
+ * vp_op_conv2d_forms: Conv2d ks x ks (pad ks / 2, stride 1 or 2: stride 2 needs ks == 3 and even h, w) + bias + act, then the residual (res_mode
+ *   1: y + r, 2: y * r + r, applied BEHIND the activation), then post_act -- through the engine's own add_conv, so dispatch, weight packing and
+ *   epilogue routing are the production ones.  in [cin][h][w], weight [cout][cin][ks][ks], bias [cout] fp32; precision may carry VP_WEIGHTS_FP8.
+ *   Destination: dst_c == 0: a fresh [cout][oh][ow] tensor (oh = h / stride).  Else a dst_c-channel tensor that starts as dst_init ([dst_c][oh][ow];
+ *   NULL = zeros), and the launch stores through an alias view of its channels [dst_off, dst_off + cout) (dst_c, dst_off, cout: multiples of 32).
+ *   Residual (res_mode != 0): res_where 0: a fresh tensor uploaded from res [cout][res_h][res_w] (res_h / res_w 0 = the output's size; any other size
+ *   is refused when the plan is built); res_where 1: channels [res_off, res_off + cout) of the destination tensor itself, values from dst_init.
+ *   Input: in_c == 0: a fresh [cin][h][w] tensor; else an alias view of channels [in_off, in_off + cin) of an in_c-channel tensor (refused when the
+ *   plan is built: a convolution's input cannot be a slice).
+ *   Exponents: all 0: an unflagged engine (unless precision itself carries VP_ACT_SCALE).  Else an engine with VP_ACT_SCALE: in / res / dst_init are TRUE values, stored as x * 2^-exp (scaled on
+ *   the host: exact) under in_exp / res_exp / out_exp; a slice shares its tensor's exponent, so with res_where 1 the residual is stored under
+ *   out_exp and res_exp is not read.
+ *   out_hi / out_lo: the STORED planes of the WHOLE destination tensor, fp16 bit patterns [dst_c or cout][oh][ow] (out_lo all zero for VP_FP16). */
+typedef struct vp_conv_form {
+  int cin, h, w, cout, ks, stride;
+  int act, post_act, res_mode;            /* ActFn / residual codes as vp_op_conv2d */
+  int tile, bk, nsplit;                   /* -1 = the dispatch rule */
+  int dst_c, dst_off;
+  int res_where, res_off, res_h, res_w;
+  int in_c, in_off;
+  int in_exp, res_exp, out_exp;
+} vp_conv_form;
+int vp_op_conv2d_forms(int gpu_id, int precision, const vp_conv_form* form, const float* in, const float* weight, const float* bias, const float* res,
+                       const float* dst_init, uint16_t* out_hi, uint16_t* out_lo, char* err, size_t err_len);
+
 /* ---- single-operator entry (unit parity tests of the MFMA conv kernel; not used by callers) -------------- */
 /* mode 0: Conv2d k=ks stride 1 pad ks/2, weight [Cout][Cin][ks][ks]; mode 1: ConvTranspose2d k2 s2, weight
  * [Cin][Cout][2][2].  act: 0 none 1 GELU 2 SiLU.  res_mode: 0 none 1 add 2 mul-add; res has the output shape.
