@@ -514,7 +514,7 @@ hipError_t launch_sppf_pool(const ActView& src, const ActView& dst, int nch, hip
 struct AttnParams {
   ActView qkv;   // [HW][heads * (2*dk + dv)]: per head q(dk) | k(dk) | v(dv)   (Attention.forward, common_layers.py:95-99)
   ActView out;   // [HW][heads * dv] = v @ softmax(q^T k * scale)^T
-  ActView vout;  // [HW][heads * dv] copy of v (input of the depthwise positional conv)
+  ActView vout;  // [HW][heads * dv] copy of v (input of the depthwise positional conv); same row pitch C as out, or the launch is refused
   int heads, dk, dv;
   float scale;
   int qblock;    // 4: four query tokens per workgroup (attention_block_kernel: dk = 32, dv = 64, <= 1760 tokens); 0: one workgroup per query token

@@ -430,6 +430,7 @@ hipError_t launch_sppf_pool(const ActView& src, const ActView& dst, int nch, hip
 hipError_t launch_attention(const AttnParams& p, hipStream_t st) {
   const int T = p.qkv.H * p.qkv.W;
   if (p.dk > 256 || p.dv > 256) return hipErrorInvalidValue;
+  if (p.out.C != p.vout.C) return hipErrorInvalidValue;   // both kernels index out and vout with out's row pitch
   if (p.qblock == 4) {   // the engine selects it at plan time (attention_block_ok)
     if (!attention_block_ok(p)) return hipErrorInvalidValue;
     constexpr int QB = 4;

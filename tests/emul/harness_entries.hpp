@@ -133,6 +133,17 @@ int emu_attention(void* qkv_hi, void* qkv_lo, int H, int W, int heads, int dk, i
   AttnParams p{view(qkv_hi, qkv_lo, H, W, heads * (2 * dk + dv)), view(out_hi, out_lo, H, W, heads * dv), view(v_hi, v_lo, H, W, heads * dv), heads, dk, dv, scale, qblock};
   return harness_done(launch_attention(p, nullptr));
 }
+// the same with the row pitch of each tensor given (>= its real width: the channels behind it, and the rows behind H * W of a longer array, are not the launch's)
+int emu_attention_pitched(void* qkv_hi, void* qkv_lo, int H, int W, int heads, int dk, int dv, float scale, void* out_hi, void* out_lo, void* v_hi, void* v_lo, int qblock,
+                          int qkv_pitch, int out_pitch, int vout_pitch) {
+  if (qkv_pitch < heads * (2 * dk + dv) || out_pitch < heads * dv || vout_pitch < heads * dv) return (int)hipErrorInvalidValue;
+  AttnParams p{view(qkv_hi, qkv_lo, H, W, qkv_pitch), view(out_hi, out_lo, H, W, out_pitch), view(v_hi, v_lo, H, W, vout_pitch), heads, dk, dv, scale, qblock};
+  return harness_done(launch_attention(p, nullptr));
+}
+// maxpool5 on (hi, lo) planes; src == dst with disjoint slices is the engine's in-place chain on the SPPF concat tensor
+int emu_maxpool5_planes(void* src_hi, void* src_lo, int H, int W, int C, int src_off, void* dst_hi, void* dst_lo, int dstC, int dst_off, int nch) {
+  return harness_done(launch_maxpool5(view(src_hi, src_lo, H, W, C), src_off, view(dst_hi, dst_lo, H, W, dstC), dst_off, nch, nullptr));
+}
 int emu_pool_partial(void* hi, void* lo, int H, int W, int C, float* partial, int nslab) {
   PoolParams p{view(hi, lo, H, W, C), partial, nslab};
   return harness_done(launch_pool_partial(p, nullptr));

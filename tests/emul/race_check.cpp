@@ -253,6 +253,12 @@ int main(int argc, char** argv) {
       std::vector<half_t> q2 = rnd16((size_t)T * heads * per2), q2l = rnd16(q2.size()), o2((size_t)T * heads * dv2), o2l(o2.size()), v2(o2.size()), v2l(o2.size());
       bad |= emu_attention(q2.data(), q2l.data(), Hq, Wq, heads, dk2, dv2, 0.18f, o2.data(), o2l.data(), v2.data(), v2l.data(), 4);
     }
+    {  // 323 tokens (17x19), both kernels: above 256 a thread scores a second key (stride 256) and every value-pass thread reads probabilities that two strides of
+       // other threads wrote; the last block of the four-query kernel holds three queries
+      const int H3 = 17, W3 = 19, T3 = H3 * W3, per3 = 2 * 32 + 64;
+      std::vector<half_t> q3 = rnd16((size_t)T3 * per3), q3l = rnd16(q3.size()), o3((size_t)T3 * 64), o3l(o3.size()), v3(o3.size()), v3l(o3.size());
+      for (int qb : {4, 0}) bad |= emu_attention(q3.data(), q3l.data(), H3, W3, 1, 32, 64, 0.18f, o3.data(), o3l.data(), v3.data(), v3l.data(), qb);
+    }
     {  // SPPF pyramid: the octet's map and its three row-maximum images in LDS, two barriers
       std::vector<half_t> s2 = rnd16(11 * 14 * 32), s2l = rnd16(s2.size()), d2(11 * 14 * 64), d2l(d2.size());
       bad |= emu_sppf_pool(s2.data(), s2l.data(), 11, 14, 32, d2.data(), d2l.data(), 64, 16);
