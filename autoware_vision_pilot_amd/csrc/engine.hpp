@@ -470,6 +470,8 @@ class Engine {
 // copies a vp_frame's image; every engine, heads included, blends its mask or pastes its depth map into the region its input came from; the detector's
 // boxes are drawn on top; fetch() hands the picture out once, in any vp_frame format.  The blend and the depth pipeline are those of
 // Engine::visualize_mask / visualize_depth (same tables, same LUTs, same kernels or their region forms).  Owns its stream and buffers.
+// The production display on top of that: overlay_lanes() (drawRawMasksInPlace's additive overlays from an EgoLanes engine's logits), draw_lane_rows()
+// (an AutoSteer engine's valid rows, decided on the device) and fetch_resized() (the preprocess path's integer bilinear into a second picture).
 // Ordering, all on the device: a draw makes the canvas's stream wait for the work queued on the engine's stream so far (the pass that wrote the mask),
 // and makes the engine's stream wait for the canvas's read before anything queued on it later (the next pass) runs.  The only host waits are fetch(),
 // sync(), a buffer that has to grow and the first use of a resize table of a new (source, destination) size: once per geometry.
@@ -484,9 +486,17 @@ class Canvas {
   void blend_mask_u8(const uint8_t* mask, bool on_device, int mh, int mw, int viz_type, int x0, int y0, int w, int h);
   void paste_depth(Engine& e);
   void draw_boxes(const CanvasBox* boxes, int n);   // inclusive rectangles before clipping, in drawing order
+  // the production display's lanes: one clamped additive overlay of up to kCanvasMaxPlanes fp32 planes (add_bgr: [n_planes][3]), and its engine form on the
+  // three logit planes of a VP_EGOLANES engine
+  void add_planes(const float* planes, bool on_device, int n_planes, int mh, int mw, float threshold, const uint8_t* add_bgr, int x0, int y0, int w, int h);
+  void overlay_lanes(Engine& e, float threshold);
+  void draw_points(const int* xy, int n, int radius, unsigned bgr);   // filled discs, clipped to the canvas
+  void draw_lane_rows(Engine& e);                                     // a VP_AUTOSTEER engine's valid rows, read on the device
   void sync();
   // planes / strides / row_bytes / rows: what vp_canvas_layout answers for (format, h(), w()), checked by the caller
   void fetch(int format, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows, int n_planes);
+  // the same for the picture resized to out_h x out_w (the integer bilinear of the preprocess path); the canvas's own picture is left as it is
+  void fetch_resized(int format, int out_h, int out_w, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows, int n_planes);
   // vp_canvas_set_color (values checked by the caller): the standard and chroma rule of later fetches into the YUV formats and GRAY8
   void set_color(int matrix, int range, int chroma_mode) { matrix_ = matrix, range_ = range, chroma_mode_ = chroma_mode; }
   void get_color(int* matrix, int* range, int* chroma_mode) const { *matrix = matrix_, *range = range_, *chroma_mode = chroma_mode_; }
@@ -499,18 +509,25 @@ class Canvas {
   uint8_t* device() const { return d_bgr_; }
 
  private:
+  enum TableKind { kNearest = 0, kLinearF32 = 1, kLinearU8 = 2 };
   struct Table {
-    int src, dst;
-    int* idx;      // nearest: [dst]; linear: [dst][2]
-    float* wgt;    // linear: [dst][2]; nearest: null
+    int kind, src, dst;
+    int* idx;      // nearest: [dst]; linear f32: [dst][2]; linear u8 (linear_taps_u8): [dst][4]
+    float* wgt;    // linear f32: [dst][2]; else null
   };
-  Table table(bool linear, int src, int dst);
+  Table table(TableKind kind, int src, int dst);
   void release();
-  const Engine& source_of(Engine& e, const char* who, SourceRegion* r) const;
+  enum Draws { kMaskOrDepth, kLanePlanes, kLaneRows };   // what a draw call needs of the engine: the kinds it accepts
+  const Engine& source_of(Engine& e, const char* who, SourceRegion* r, Draws draws = kMaskOrDepth) const;
   void need_begun(const char* who) const;
   void wait_for(Engine& e);        // the canvas's stream behind the engine's work so far
   void release_to(Engine& e);      // the engine's later work behind the canvas's read
   void blend(const uint8_t* d_mask, int mh, int mw, int viz_type, const SourceRegion& r);
+  void add(const float* d_planes, int n_planes, int mh, int mw, float threshold, const unsigned* add, const SourceRegion& r);
+  void check_region(const char* who, int x0, int y0, int w, int h) const;
+  const uint8_t* stage_host(const void* src, size_t bytes);   // a caller's pageable array: copied before the call returns, then one H2D into d_umask_
+  void fetch_picture(const uint8_t* d_bgr, int pitch, int h, int w, int format, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows,
+                     int n_planes);
   template <class T>
   void grow(T*& p, size_t& cap, size_t bytes);
   int gpu_;
@@ -528,7 +545,9 @@ class Canvas {
   size_t depth_cap_ = 0;
   uint8_t* d_out_ = nullptr;       // fetch: the planes of the requested format
   size_t out_cap_ = 0;
-  uint8_t* d_umask_ = nullptr;     // blend_mask_u8 from the host: the caller's mask
+  uint8_t* d_small_ = nullptr;     // fetch_resized: the resized picture, rows frame_bgr_pitch(out_w) apart
+  size_t small_cap_ = 0;
+  uint8_t* d_umask_ = nullptr;     // blend_mask_u8 / add_planes from the host: the caller's mask or planes
   size_t umask_cap_ = 0;
   uint8_t* h_umask_ = nullptr;     // ... staged through two pinned slots, as a frame upload is
   size_t h_umask_cap_ = 0;

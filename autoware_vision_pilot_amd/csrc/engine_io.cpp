@@ -763,13 +763,13 @@ void Canvas::release() {
     if (t.wgt) (void)hipFree(t.wgt);
   }
   tables_.clear();
-  for (void* p : {(void*)d_bgr_, (void*)d_lut_, (void*)d_minmax_, (void*)d_depth_, (void*)d_out_, (void*)d_umask_})
+  for (void* p : {(void*)d_bgr_, (void*)d_lut_, (void*)d_minmax_, (void*)d_depth_, (void*)d_out_, (void*)d_small_, (void*)d_umask_})
     if (p) (void)hipFree(p);
   if (h_umask_) (void)hipHostFree(h_umask_);
   if (stream_) (void)hipStreamDestroy(stream_);
   stream_ = nullptr;
   ev_src_ = ev_read_ = umask_ev_[0] = umask_ev_[1] = nullptr;
-  d_bgr_ = d_lut_ = d_out_ = d_umask_ = h_umask_ = nullptr;
+  d_bgr_ = d_lut_ = d_out_ = d_small_ = d_umask_ = h_umask_ = nullptr;
   d_minmax_ = nullptr;
   d_depth_ = nullptr;
 }
@@ -787,12 +787,13 @@ void Canvas::grow(T*& p, size_t& cap, size_t bytes) {
   cap = n;
 }
 
-// The resize tables of visualize_mask / resize_depth_on_device (nearest_tab, linear_taps_f32), kept on the device per (source, destination) size: the
-// first use of a size uploads it and waits (the host vector is a local); every later draw finds it.  A handful of sizes per camera; the one unused
-// longest goes when there are 16, so the two tables of one draw never push each other out.
-Canvas::Table Canvas::table(bool linear, int src, int dst) {
+// The resize tables of visualize_mask / resize_depth_on_device (nearest_tab, linear_taps_f32) and of the preprocess path (linear_taps_u8), kept on the
+// device per (kind, source, destination) size: the first use of a size uploads it and waits (the host vector is a local); every later draw finds it.  A
+// handful of sizes per camera; the one unused longest goes when there are 16, so the two tables of one draw never push each other out.
+Canvas::Table Canvas::table(TableKind kind, int src, int dst) {
+  const bool linear = kind == kLinearF32;
   for (size_t i = 0; i < tables_.size(); ++i)
-    if ((tables_[i].wgt != nullptr) == linear && tables_[i].src == src && tables_[i].dst == dst) {
+    if (tables_[i].kind == kind && tables_[i].src == src && tables_[i].dst == dst) {
       std::rotate(tables_.begin() + i, tables_.begin() + i + 1, tables_.end());
       return tables_.back();
     }
@@ -802,12 +803,14 @@ Canvas::Table Canvas::table(bool linear, int src, int dst) {
     if (tables_.front().wgt) (void)hipFree(tables_.front().wgt);
     tables_.erase(tables_.begin());
   }
-  Table t{src, dst, nullptr, nullptr};
+  Table t{kind, src, dst, nullptr, nullptr};
   std::vector<int> idx((linear ? 2 : 1) * (size_t)dst);
   std::vector<float> wgt;
   if (linear) {
     wgt.resize(2 * (size_t)dst);
     linear_taps_f32(src, dst, idx.data(), wgt.data());
+  } else if (kind == kLinearU8) {
+    linear_taps_u8(src, dst, &idx);
   } else {
     nearest_tab(src, dst, idx.data());
   }
@@ -841,11 +844,14 @@ void Canvas::begin(const FrameView& f) {
 }
 
 // the refusals of blend_mask / paste_depth, the engine whose record counts (a head: its base) and the region the draw goes to
-const Engine& Canvas::source_of(Engine& e, const char* who, SourceRegion* r) const {
+const Engine& Canvas::source_of(Engine& e, const char* who, SourceRegion* r, Draws draws) const {
   const std::string me(who);
   need_begun(who);
   if (e.gpu_ != gpu_) throw std::invalid_argument(me + ": the engine lives on GPU " + std::to_string(e.gpu_) + ", the canvas on GPU " + std::to_string(gpu_));
-  if (e.kind_ < 0 || e.kind_ > 3) throw std::invalid_argument(me + ": VP_AUTODRIVE / VP_AUTOSPEED / VP_AUTOSTEER engines have no mask or depth plane to draw");
+  if (draws == kLanePlanes && e.kind_ != 3) throw std::invalid_argument(me + ": VP_EGOLANES engines only (the three lane planes of its logits)");
+  if (draws == kLaneRows && e.kind_ != 6) throw std::invalid_argument(me + ": VP_AUTOSTEER engines only (the lane rows xp / h_vector of its logits)");
+  if (draws == kMaskOrDepth && (e.kind_ < 0 || e.kind_ > 3))
+    throw std::invalid_argument(me + ": VP_AUTODRIVE / VP_AUTOSPEED / VP_AUTOSTEER engines have no mask or depth plane to draw");
   if (e.frames_ > 1) throw std::invalid_argument(me + ": a batched encoder has no outputs of its own (draw its per-camera heads)");
   if (!e.have_outputs_) throw std::runtime_error("Inference has not been run yet");
   const Engine& src = e.base_ ? *e.base_ : e;
@@ -867,8 +873,8 @@ void Canvas::release_to(Engine& e) {
 }
 
 void Canvas::blend(const uint8_t* d_mask, int mh, int mw, int viz_type, const SourceRegion& r) {
-  const int* ytab = table(false, mh, r.h).idx;
-  const int* xtab = table(false, mw, r.w).idx;
+  const int* ytab = table(kNearest, mh, r.h).idx;
+  const int* xtab = table(kNearest, mw, r.w).idx;
   CanvasBlendParams q{};
   q.mask = d_mask;
   q.mw = mw;
@@ -898,32 +904,133 @@ void Canvas::blend_mask_u8(const uint8_t* mask, bool on_device, int mh, int mw, 
   need_begun("vp_canvas_blend_mask_u8");
   if (!mask || mh < 1 || mw < 1 || mh > 16384 || mw > 16384) throw std::invalid_argument("vp_canvas_blend_mask_u8: null mask or a mask size outside 1 .. 16384");
   if (viz_type < 0 || viz_type > 2) throw std::invalid_argument("vp_canvas_blend_mask_u8: viz_type 0 (scene), 1 (domain) or 2 (egolanes)");
-  if (x0 < 0 || y0 < 0 || w < 2 || h < 2 || (long long)x0 + w > w_ || (long long)y0 + h > h_)
-    throw std::invalid_argument("vp_canvas_blend_mask_u8: region (x0 " + std::to_string(x0) + ", y0 " + std::to_string(y0) + ", " + std::to_string(w) + " x " + std::to_string(h) +
-                                ") must be at least 2 x 2 and lie inside the " + std::to_string(w_) + " x " + std::to_string(h_) + " canvas");
+  check_region("vp_canvas_blend_mask_u8", x0, y0, w, h);
   VP_HIP_CHECK(hipSetDevice(gpu_));
-  const uint8_t* d_mask = mask;
-  if (!on_device) {   // the caller's pageable mask: copied into a pinned slot before the call returns, then one H2D
-    const size_t n = (size_t)mh * mw;
-    grow(d_umask_, umask_cap_, n);
-    if (n > h_umask_cap_) {
-      VP_HIP_CHECK(hipStreamSynchronize(stream_));
-      if (h_umask_) (void)hipHostFree(h_umask_);
-      h_umask_ = nullptr;
-      h_umask_cap_ = 0;
-      const size_t cap = (n + 255) & ~(size_t)255;
-      VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_umask_), 2 * cap, hipHostMallocDefault));
-      h_umask_cap_ = cap;
-    }
-    umask_slot_ ^= 1;
-    uint8_t* slot = h_umask_ + (size_t)umask_slot_ * h_umask_cap_;
-    VP_HIP_CHECK(hipEventSynchronize(umask_ev_[umask_slot_]));   // the H2D that last read this slot, two calls ago
-    std::memcpy(slot, mask, n);
-    VP_HIP_CHECK(hipMemcpyAsync(d_umask_, slot, n, hipMemcpyHostToDevice, stream_));
-    VP_HIP_CHECK(hipEventRecord(umask_ev_[umask_slot_], stream_));
-    d_mask = d_umask_;
-  }
+  const uint8_t* d_mask = on_device ? mask : stage_host(mask, (size_t)mh * mw);
   blend(d_mask, mh, mw, viz_type, SourceRegion{x0, y0, w, h, h_, w_});
+}
+
+void Canvas::check_region(const char* who, int x0, int y0, int w, int h) const {
+  if (x0 < 0 || y0 < 0 || w < 2 || h < 2 || (long long)x0 + w > w_ || (long long)y0 + h > h_)
+    throw std::invalid_argument(std::string(who) + ": region (x0 " + std::to_string(x0) + ", y0 " + std::to_string(y0) + ", " + std::to_string(w) + " x " + std::to_string(h) +
+                                ") must be at least 2 x 2 and lie inside the " + std::to_string(w_) + " x " + std::to_string(h_) + " canvas");
+}
+
+// the caller's pageable array: copied into a pinned slot before the call returns, then one H2D
+const uint8_t* Canvas::stage_host(const void* src, size_t n) {
+  grow(d_umask_, umask_cap_, n);
+  if (n > h_umask_cap_) {
+    VP_HIP_CHECK(hipStreamSynchronize(stream_));
+    if (h_umask_) (void)hipHostFree(h_umask_);
+    h_umask_ = nullptr;
+    h_umask_cap_ = 0;
+    const size_t cap = (n + 255) & ~(size_t)255;
+    VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_umask_), 2 * cap, hipHostMallocDefault));
+    h_umask_cap_ = cap;
+  }
+  umask_slot_ ^= 1;
+  uint8_t* slot = h_umask_ + (size_t)umask_slot_ * h_umask_cap_;
+  VP_HIP_CHECK(hipEventSynchronize(umask_ev_[umask_slot_]));   // the H2D that last read this slot, two calls ago
+  std::memcpy(slot, src, n);
+  VP_HIP_CHECK(hipMemcpyAsync(d_umask_, slot, n, hipMemcpyHostToDevice, stream_));
+  VP_HIP_CHECK(hipEventRecord(umask_ev_[umask_slot_], stream_));
+  return d_umask_;
+}
+
+// ---- the production display's lanes: drawRawMasksInPlace's three additive overlays as one clamped sum per pixel
+void Canvas::add(const float* d_planes, int n_planes, int mh, int mw, float threshold, const unsigned* add, const SourceRegion& r) {
+  CanvasAddPlanesParams q{};
+  q.planes = d_planes;
+  q.n_planes = n_planes;
+  q.plane_stride = mh * mw;
+  q.mw = mw;
+  q.ytab = table(kNearest, mh, r.h).idx;
+  q.xtab = table(kNearest, mw, r.w).idx;
+  q.threshold = threshold;
+  for (int k = 0; k < n_planes; ++k) q.add[k] = add[k];
+  q.canvas = d_bgr_;
+  q.pitch = pitch_;
+  q.x0 = r.x0;
+  q.y0 = r.y0;
+  q.w = r.w;
+  q.h = r.h;
+  VP_HIP_CHECK(launch_canvas_add_planes(q, h_, w_, stream_));
+}
+
+void Canvas::add_planes(const float* planes, bool on_device, int n_planes, int mh, int mw, float threshold, const uint8_t* add_bgr, int x0, int y0, int w, int h) {
+  need_begun("vp_canvas_add_planes_f32");
+  if (n_planes < 1 || n_planes > kCanvasMaxPlanes) throw std::invalid_argument("vp_canvas_add_planes_f32: n_planes " + std::to_string(n_planes) + " (1 .. 4)");
+  if (!planes || !add_bgr) throw std::invalid_argument("vp_canvas_add_planes_f32: null planes or null add_bgr");
+  if (mh < 1 || mw < 1 || mh > 16384 || mw > 16384) throw std::invalid_argument("vp_canvas_add_planes_f32: a plane size outside 1 .. 16384");
+  if (!std::isfinite(threshold)) throw std::invalid_argument("vp_canvas_add_planes_f32: the threshold is not finite");
+  check_region("vp_canvas_add_planes_f32", x0, y0, w, h);
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  unsigned add_px[kCanvasMaxPlanes];
+  for (int k = 0; k < n_planes; ++k) add_px[k] = (unsigned)add_bgr[3 * k] | ((unsigned)add_bgr[3 * k + 1] << 8) | ((unsigned)add_bgr[3 * k + 2] << 16);
+  const float* d_planes = on_device ? planes : reinterpret_cast<const float*>(stage_host(planes, (size_t)n_planes * mh * mw * sizeof(float)));
+  add(d_planes, n_planes, mh, mw, threshold, add_px, SourceRegion{x0, y0, w, h, h_, w_});
+}
+
+void Canvas::overlay_lanes(Engine& e, float threshold) {
+  SourceRegion r;
+  source_of(e, "vp_canvas_overlay_lanes", &r, kLanePlanes);
+  if (!std::isfinite(threshold)) throw std::invalid_argument("vp_canvas_overlay_lanes: the threshold is not finite");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  // rint(0.4 * colour) of drawRawMasksInPlace's colours, BGR, in plane order: ego left (255, 0, 0), ego right (255, 0, 200), other lanes (0, 153, 0)
+  static const unsigned kAdd[3] = {102u, 102u | (80u << 16), 61u << 8};
+  wait_for(e);
+  add(e.d_logits_, 3, e.out_h_, e.out_w_, threshold, kAdd, r);
+  release_to(e);
+}
+
+// ---- points
+void Canvas::draw_points(const int* xy, int n, int radius, unsigned bgr) {
+  need_begun("vp_canvas_draw_points");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  for (int first = 0; first < n; first += kCanvasPointChunk) {
+    CanvasPointParams q{};
+    q.canvas = d_bgr_;
+    q.pitch = pitch_;
+    q.radius = radius;
+    q.bgr = bgr;
+    q.ux0 = q.uy0 = INT_MAX;
+    q.ux1 = q.uy1 = INT_MIN;
+    for (int i = first; i < std::min(n, first + kCanvasPointChunk); ++i) {
+      const long long x = xy[2 * i], y = xy[2 * i + 1];
+      const long long cx0 = std::max(x - radius, 0ll), cy0 = std::max(y - radius, 0ll), cx1 = std::min(x + radius, (long long)w_ - 1), cy1 = std::min(y + radius, (long long)h_ - 1);
+      if (cx1 < cx0 || cy1 < cy0) continue;   // wholly outside
+      q.pt[q.n++] = CanvasPoint{(int)x, (int)y};
+      q.ux0 = std::min(q.ux0, (int)cx0);
+      q.uy0 = std::min(q.uy0, (int)cy0);
+      q.ux1 = std::max(q.ux1, (int)cx1);
+      q.uy1 = std::max(q.uy1, (int)cy1);
+    }
+    if (q.n) VP_HIP_CHECK(launch_canvas_points(q, h_, w_, stream_));
+  }
+}
+
+// make_visualization (Models/visualizations/AutoSteer/video_visualization.py:19-44): which rows count is decided on the device, so the launch visits every
+// pixel a valid row could reach: the rows oy - 3 .. oy + 511 + 3 of the canvas, all columns
+void Canvas::draw_lane_rows(Engine& e) {
+  SourceRegion r;
+  source_of(e, "vp_canvas_draw_lane_rows", &r, kLaneRows);
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  CanvasPointParams q{};
+  q.canvas = d_bgr_;
+  q.pitch = pitch_;
+  q.radius = 3;
+  q.bgr = 0x00FF00u;
+  q.n = e.out_h_;   // 64 rows
+  q.rows = e.d_logits_;
+  q.ox = r.x0;
+  q.oy = r.y0;
+  q.ux0 = 0;
+  q.ux1 = w_ - 1;
+  q.uy0 = std::max(r.y0 - q.radius, 0);
+  q.uy1 = std::min(r.y0 + 511 + q.radius, h_ - 1);
+  wait_for(e);
+  VP_HIP_CHECK(launch_canvas_points(q, h_, w_, stream_));
+  release_to(e);
 }
 
 // Engine::visualize_depth's pipeline at the region's size on the canvas's stream and buffers; only the last step differs: the colours go into the region
@@ -933,7 +1040,7 @@ void Canvas::paste_depth(Engine& e) {
   VP_HIP_CHECK(hipSetDevice(gpu_));
   const size_t n = (size_t)r.h * r.w;
   grow(d_depth_, depth_cap_, n * sizeof(float));
-  const Table ty = table(true, e.out_h_, r.h), tx = table(true, e.out_w_, r.w);
+  const Table ty = table(kLinearF32, e.out_h_, r.h), tx = table(kLinearF32, e.out_w_, r.w);
   wait_for(e);
   VP_HIP_CHECK(launch_resize_bilinear_f32(e.d_logits_, e.out_w_, ty.idx, ty.wgt, tx.idx, tx.wgt, r.h, r.w, d_depth_, stream_));
   release_to(e);   // the logits are read: the engine's next pass may overwrite them
@@ -973,20 +1080,46 @@ void Canvas::sync() {
 void Canvas::fetch(int format, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows, int n_planes) {
   need_begun("vp_canvas_fetch");
   VP_HIP_CHECK(hipSetDevice(gpu_));
+  fetch_picture(d_bgr_, pitch_, h_, w_, format, planes, strides, row_bytes, rows, n_planes);
+}
+
+// cv::resize(unified_frame, display_frame, Size(1280, 720)) of the display thread (production_release/main.cpp:907), in the integer bilinear this library
+// defines for the preprocess path; the result is a second picture, converted and copied by the path of fetch()
+void Canvas::fetch_resized(int format, int out_h, int out_w, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows, int n_planes) {
+  need_begun("vp_canvas_fetch_resized");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  CanvasResizeParams q{};
+  q.dst_pitch = frame_bgr_pitch(out_w);
+  grow(d_small_, small_cap_, (size_t)out_h * q.dst_pitch);
+  q.ytab = table(kLinearU8, h_, out_h).idx;
+  q.xtab = table(kLinearU8, w_, out_w).idx;
+  q.src = d_bgr_;
+  q.src_pitch = pitch_;
+  q.src_h = h_;
+  q.src_w = w_;
+  q.dst = d_small_;
+  q.out_h = out_h;
+  q.out_w = out_w;
+  VP_HIP_CHECK(launch_canvas_resize(q, stream_));
+  fetch_picture(d_small_, q.dst_pitch, out_h, out_w, format, planes, strides, row_bytes, rows, n_planes);
+}
+
+void Canvas::fetch_picture(const uint8_t* d_bgr, int pitch, int h, int w, int format, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows,
+                           int n_planes) {
   if (format == VP_FRAME_BGR8) {
-    VP_HIP_CHECK(hipMemcpy2DAsync(planes[0], strides[0], d_bgr_, pitch_, row_bytes[0], rows[0], hipMemcpyDeviceToHost, stream_));
+    VP_HIP_CHECK(hipMemcpy2DAsync(planes[0], strides[0], d_bgr, pitch, row_bytes[0], rows[0], hipMemcpyDeviceToHost, stream_));
   } else {
-    const size_t pp = (size_t)canvas_plane_pitch(format, w_), ppc = (size_t)canvas_plane_pitch(format, w_, 1);   // both multiples of 4
+    const size_t pp = (size_t)canvas_plane_pitch(format, w), ppc = (size_t)canvas_plane_pitch(format, w, 1);   // both multiples of 4
     uint8_t* dev[3] = {nullptr, nullptr, nullptr};
     size_t off[4] = {0, 0, 0, 0};
     for (int i = 0; i < n_planes; ++i) off[i + 1] = off[i] + (i ? ppc : pp) * rows[i];
     grow(d_out_, out_cap_, off[n_planes]);
     for (int i = 0; i < n_planes; ++i) dev[i] = d_out_ + off[i];
     CanvasToFormatParams q{};
-    q.src = d_bgr_;
-    q.src_pitch = pitch_;
-    q.h = h_;
-    q.w = w_;
+    q.src = d_bgr;
+    q.src_pitch = pitch;
+    q.h = h;
+    q.w = w;
     q.format = format;
     q.p0 = dev[0];
     q.p1 = dev[1];

@@ -151,6 +151,56 @@ hipError_t launch_canvas_to_format(const CanvasToFormatParams& p, hipStream_t st
 // depth_colorize_kernel's value -> u8 -> table step, written into the region (x0, y0, w, h) of the canvas instead of a packed image; src: [h][w] fp32
 hipError_t launch_canvas_depth(const float* src, const unsigned* mm, const uint8_t* lut, uint8_t* canvas, int pitch, int x0, int y0, int w, int h,
                                int canvas_h, int canvas_w, hipStream_t st);
+// canvas_add_planes_kernel: the additive overlays of drawRawMasksInPlace (visualize.cpp:312-388) as ONE clamped sum per pixel.  planes: fp32
+// [n_planes][mh][mw], plane_stride = mh * mw; ytab [h] / xtab [w]: nearest tables of the region's size into mh x mw, as CanvasBlendParams.  Every plane k
+// with planes[k][my][mx] > threshold (fp32 compare: NaN is false) adds add[k] = b | g << 8 | r << 16 to the pixel, each channel min(255, d + sum): all
+// increments are non-negative, so this equals the overlays applied one after the other, with one read and one write per pixel.
+constexpr int kCanvasMaxPlanes = 4;
+struct CanvasAddPlanesParams {
+  const float* planes;
+  int n_planes, plane_stride, mw;
+  const int* ytab;
+  const int* xtab;
+  float threshold;
+  unsigned add[kCanvasMaxPlanes];
+  uint8_t* canvas;
+  int pitch;
+  int x0, y0, w, h;
+};
+hipError_t launch_canvas_add_planes(const CanvasAddPlanesParams& p, int canvas_h, int canvas_w, hipStream_t st);
+// canvas_points_kernel: filled discs of one colour, dx * dx + dy * dy <= radius * radius around each point, clipped to the canvas.  Up to kCanvasPointChunk
+// points per launch, walked by every work-item over its own block (one colour: the order does not matter).  ux / uy: the pixels the launch visits.
+// rows == nullptr: the points are pt[0, n).  rows != nullptr (vp_canvas_draw_lane_rows): the kernel forms them itself from the AutoSteer engine's
+// device logits rows[0, n) = xp, rows[n, 2n) = h_vector (n = 64 <= kCanvasPointChunk): row i counts when h_vector[i] >= 0.5f and the fp32 product
+// xp[i] * 1024.0f lies inside (-1e8, 1e8) (NaN does not); it sits at x = ox + (int)product, y = oy + i * 511 / 63.
+constexpr int kCanvasPointChunk = 64;
+constexpr int kCanvasMaxRadius = 16;
+struct CanvasPoint {
+  int x, y;
+};
+struct CanvasPointParams {
+  uint8_t* canvas;
+  int pitch;
+  int ux0, uy0, ux1, uy1;
+  int n, radius;
+  unsigned bgr;         // b | g << 8 | r << 16
+  const float* rows;
+  int ox, oy;           // rows != nullptr: the region's origin
+  CanvasPoint pt[kCanvasPointChunk];
+};
+hipError_t launch_canvas_points(const CanvasPointParams& p, int canvas_h, int canvas_w, hipStream_t st);
+// canvas_resize_kernel: the u8 integer bilinear of preprocess_kernel (the same device function, the same linear_taps_u8 tables: oracle/pre_post.py
+// resize_bilinear_u8) from one BGR8 picture into another.  One work-item forms an aligned four-pixel block of a destination row and stores its three
+// words; bytes behind the row's end are written as 0.  dst rows are dst_pitch >= frame_bgr_pitch(out_w) apart: a picture canvas_to_format_kernel takes.
+struct CanvasResizeParams {
+  const uint8_t* src;
+  int src_pitch, src_h, src_w;
+  const int* xtab;      // [out_w][4] = x0, x1, a0, a1
+  const int* ytab;      // [out_h][4] = y0, y1, b0, b1
+  uint8_t* dst;
+  int dst_pitch, out_h, out_w;
+};
+hipError_t launch_canvas_resize(const CanvasResizeParams& p, hipStream_t st);
 
 struct StemParams {
   const float* in;  // [3][H][W]

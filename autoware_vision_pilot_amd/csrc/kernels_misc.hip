@@ -17,6 +17,13 @@ namespace vp {
 __device__ __forceinline__ float unit_from_u8(int q, int norm_form) {
   return norm_form ? __fmul_rn((float)q, (float)(1.0 / 255.0)) : __fdiv_rn((float)q, 255.0f);
 }
+// byte `sc` of one resized pixel: r0 / r1 the two source rows of yt, xt / yt one entry of the tap tables (linear_taps_u8).  Shared with canvas_resize_kernel.
+__device__ __forceinline__ int bilinear_u8(const uint8_t* r0, const uint8_t* r1, const int4& xt, const int4& yt, int sc) {
+  const int s0 = (int)r0[xt.x * 3 + sc] * xt.z + (int)r0[xt.y * 3 + sc] * xt.w;
+  const int s1 = (int)r1[xt.x * 3 + sc] * xt.z + (int)r1[xt.y * 3 + sc] * xt.w;
+  const int q = (((yt.z * (s0 >> 4)) >> 16) + ((yt.w * (s1 >> 4)) >> 16) + 2) >> 2;
+  return min(max(q, 0), 255);
+}
 __global__ __launch_bounds__(256) void preprocess_kernel(const PreprocessParams p) {
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
   if (x >= p.out_w) return;
@@ -26,11 +33,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreprocessParams 
   const uint8_t* r1 = p.frame + (size_t)yt.y * p.stride;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const int sc = p.src_c[c];
-    const int s0 = (int)r0[xt.x * 3 + sc] * xt.z + (int)r0[xt.y * 3 + sc] * xt.w;
-    const int s1 = (int)r1[xt.x * 3 + sc] * xt.z + (int)r1[xt.y * 3 + sc] * xt.w;
-    int q = (((yt.z * (s0 >> 4)) >> 16) + ((yt.w * (s1 >> 4)) >> 16) + 2) >> 2;
-    q = min(max(q, 0), 255);
+    const int q = bilinear_u8(r0, r1, xt, yt, p.src_c[c]);
     const float t = unit_from_u8(q, p.norm_form);
     p.out[((size_t)c * p.out_h + y) * p.out_w + x] = __fdiv_rn(__fsub_rn(t, p.mean[c]), p.stdv[c]);
   }
@@ -594,6 +597,85 @@ __global__ __launch_bounds__(256) void canvas_depth_kernel(const float* src, con
   }
   store_bgr4(row, j, px);
 }
+// drawRawMasksInPlace's additive overlays (visualize.cpp:312-388) as one clamped sum per pixel, kernels.hpp CanvasAddPlanesParams
+__device__ __forceinline__ unsigned add_sat8(unsigned d, unsigned s) { return min(255u, d + s); }
+__global__ __launch_bounds__(256) void canvas_add_planes_kernel(const CanvasAddPlanesParams p) {
+  const int jb0 = p.x0 >> 2, nb = ((p.x0 + p.w - 1) >> 2) - jb0 + 1;
+  const int i = blockIdx.x * 256 + threadIdx.x, ry = blockIdx.y;
+  if (i >= nb) return;
+  const int j = jb0 + i;
+  uint8_t* row = p.canvas + (size_t)(p.y0 + ry) * p.pitch;
+  const float* mrow = p.planes + (size_t)p.ytab[ry] * p.mw;
+  unsigned px[4];
+  load_bgr4(row, j, px);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int rx = 4 * j + k - p.x0;
+    if (rx < 0 || rx >= p.w) continue;   // the region's edge inside a block: carried, not drawn
+    const float* m = mrow + p.xtab[rx];
+    unsigned sb = 0u, sg = 0u, sr = 0u;
+#pragma unroll
+    for (int q = 0; q < kCanvasMaxPlanes; ++q) {
+      if (q < p.n_planes && m[(size_t)q * p.plane_stride] > p.threshold) {   // NaN compares false
+        sb += p.add[q] & 255u;
+        sg += (p.add[q] >> 8) & 255u;
+        sr += p.add[q] >> 16;
+      }
+    }
+    px[k] = add_sat8(px[k] & 255u, sb) | (add_sat8((px[k] >> 8) & 255u, sg) << 8) | (add_sat8(px[k] >> 16, sr) << 16);
+  }
+  store_bgr4(row, j, px);
+}
+// filled discs of one colour, kernels.hpp CanvasPointParams; with p.rows the points are the valid rows of an AutoSteer engine's device logits
+// (make_visualization, Models/visualizations/AutoSteer/video_visualization.py:19-44)
+__global__ __launch_bounds__(256) void canvas_points_kernel(const CanvasPointParams p) {
+  const int jb0 = p.ux0 >> 2, nb = (p.ux1 >> 2) - jb0 + 1;
+  const int i = blockIdx.x * 256 + threadIdx.x, y = p.uy0 + (int)blockIdx.y;
+  if (i >= nb) return;
+  const int j = jb0 + i, r = p.radius;
+  uint8_t* row = p.canvas + (size_t)y * p.pitch;
+  unsigned px[4];
+  load_bgr4(row, j, px);
+  for (int b = 0; b < p.n; ++b) {
+    int cx, cy;
+    if (p.rows) {
+      const float v = __fmul_rn(p.rows[b], 1024.0f);
+      if (!(p.rows[p.n + b] >= 0.5f) || !(v > -1e8f && v < 1e8f)) continue;   // an invalid row; NaN or no pixel position
+      cx = p.ox + (int)v;
+      cy = p.oy + b * 511 / 63;
+    } else {
+      cx = p.pt[b].x;
+      cy = p.pt[b].y;
+    }
+    const int dy = y - cy;
+    if (dy < -r || dy > r) continue;
+    const int lim = r * r - dy * dy;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int x = 4 * j + k, dx = x - cx;
+      if (x < p.ux0 || x > p.ux1 || dx < -r || dx > r) continue;   // ux: inside the canvas
+      if (dx * dx <= lim) px[k] = p.bgr;
+    }
+  }
+  store_bgr4(row, j, px);
+}
+// preprocess_kernel's u8 value from one BGR8 picture into another, kernels.hpp CanvasResizeParams
+__global__ __launch_bounds__(256) void canvas_resize_kernel(const CanvasResizeParams p) {
+  const int j = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (j >= (p.out_w + 3) >> 2) return;
+  const int4 yt = *reinterpret_cast<const int4*>(p.ytab + 4 * y);
+  const uint8_t* r0 = p.src + (size_t)yt.x * p.src_pitch;
+  const uint8_t* r1 = p.src + (size_t)yt.y * p.src_pitch;
+  unsigned px[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int x = 4 * j + k;
+    if (x >= p.out_w) break;
+    const int4 xt = *reinterpret_cast<const int4*>(p.xtab + 4 * x);
+    px[k] = (unsigned)bilinear_u8(r0, r1, xt, yt, 0) | ((unsigned)bilinear_u8(r0, r1, xt, yt, 1) << 8) | ((unsigned)bilinear_u8(r0, r1, xt, yt, 2) << 16);
+  }
+  store_bgr4(p.dst + (size_t)y * p.dst_pitch, j, px);
+}
 // Canvas -> a vp_frame format (kernels.hpp CanvasToFormatParams).  The forward form, the integer counterpart of the upload formula above, with the
 // constants p.k of the canvas's colour standard (include/vp_hip.h states it as the DEFINITION; not pinned against OpenCV):
 //   Y = sat8((yk . (R, G, B) + (off << 20) + 2^19) >> 20),  U = sat8((uk . (R, G, B) + (128 << 20) + 2^19) >> 20),  V likewise with vk
@@ -917,6 +999,27 @@ hipError_t launch_canvas_depth(const float* src, const unsigned* mm, const uint8
   if (!src || !mm || !lut || !canvas_region_ok(canvas, pitch, canvas_h, canvas_w, x0, y0, w, h)) return hipErrorInvalidValue;
   const int nb = ((x0 + w - 1) >> 2) - (x0 >> 2) + 1;
   VP_LAUNCH(canvas_depth_kernel, dim3(nblk(nb), h), dim3(256), 0, st, src, mm, lut, canvas, pitch, x0, y0, w, h);
+}
+hipError_t launch_canvas_add_planes(const CanvasAddPlanesParams& p, int canvas_h, int canvas_w, hipStream_t st) {
+  if (!p.planes || !p.ytab || !p.xtab || p.n_planes < 1 || p.n_planes > kCanvasMaxPlanes || p.mw < 1 || p.plane_stride < p.mw || !(p.threshold == p.threshold) ||
+      (reinterpret_cast<uintptr_t>(p.planes) & 3) || !canvas_region_ok(p.canvas, p.pitch, canvas_h, canvas_w, p.x0, p.y0, p.w, p.h))
+    return hipErrorInvalidValue;
+  const int nb = ((p.x0 + p.w - 1) >> 2) - (p.x0 >> 2) + 1;
+  VP_LAUNCH(canvas_add_planes_kernel, dim3(nblk(nb), p.h), dim3(256), 0, st, p);
+}
+hipError_t launch_canvas_points(const CanvasPointParams& p, int canvas_h, int canvas_w, hipStream_t st) {
+  if (p.n < 1 || p.n > kCanvasPointChunk || p.radius < 0 || p.radius > kCanvasMaxRadius || p.ux1 < p.ux0 || p.uy1 < p.uy0 || (reinterpret_cast<uintptr_t>(p.rows) & 3) ||
+      !canvas_region_ok(p.canvas, p.pitch, canvas_h, canvas_w, p.ux0, p.uy0, p.ux1 - p.ux0 + 1, p.uy1 - p.uy0 + 1))
+    return hipErrorInvalidValue;
+  const int nb = (p.ux1 >> 2) - (p.ux0 >> 2) + 1;
+  VP_LAUNCH(canvas_points_kernel, dim3(nblk(nb), p.uy1 - p.uy0 + 1), dim3(256), 0, st, p);
+}
+hipError_t launch_canvas_resize(const CanvasResizeParams& p, hipStream_t st) {
+  if (!p.src || !p.dst || !p.xtab || !p.ytab || p.src_h < 1 || p.src_w < 1 || p.src_pitch < 3 * p.src_w || p.out_h < 1 || p.out_w < 1 || p.out_h > 16384 || p.out_w > 16384 ||
+      p.dst_pitch < frame_bgr_pitch(p.out_w) || (p.dst_pitch & 3) || (reinterpret_cast<uintptr_t>(p.dst) & 3) ||
+      ((reinterpret_cast<uintptr_t>(p.xtab) | reinterpret_cast<uintptr_t>(p.ytab)) & 15))
+    return hipErrorInvalidValue;
+  VP_LAUNCH(canvas_resize_kernel, dim3(nblk((p.out_w + 3) / 4), p.out_h), dim3(256), 0, st, p);
 }
 hipError_t launch_canvas_to_format(const CanvasToFormatParams& q, hipStream_t st) {
   CanvasToFormatParams p = q;

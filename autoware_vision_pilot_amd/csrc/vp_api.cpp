@@ -554,12 +554,14 @@ const char* const kFormatNames[vp::kFrameFormats] = {"BGR8", "RGB8", "BGRA8", "R
 int format_planes(int format) { return vp::frame_format_planar(format) ? 3 : (vp::frame_format_420(format) ? 2 : 1); }
 
 // the planes an h x w image has in `format` (vp_frame_upload*, vp_canvas_layout* / vp_canvas_fetch), and the refusals of the geometry
-FramePlanes frame_layout(const std::string& me, int format, int h, int w) {
+// min_side: 2 for a frame or a canvas; 1 for the resized picture of vp_canvas_fetch_resized
+FramePlanes frame_layout(const std::string& me, int format, int h, int w, int min_side = 2) {
   static const int px_bytes[vp::kFrameFormats] = {3, 3, 4, 4, 1, 1, 2, 2, 1, 1, 1};
   const int fi = vp::frame_format_index(format);
   if (fi < 0) throw std::invalid_argument(me + ": unknown format " + std::to_string(format));
   const std::string fmt = kFormatNames[fi];
-  if (h < 2 || w < 2 || h > 16384 || w > 16384) throw std::invalid_argument(me + ": frame size " + std::to_string(w) + " x " + std::to_string(h) + " (2 .. 16384 each way)");
+  if (h < min_side || w < min_side || h > 16384 || w > 16384)
+    throw std::invalid_argument(me + ": frame size " + std::to_string(w) + " x " + std::to_string(h) + " (" + std::to_string(min_side) + " .. 16384 each way)");
   if (format >= VP_FRAME_NV12 && (w & 1)) throw std::invalid_argument(me + ": " + fmt + " needs an even width (one chroma pair per two pixels), got " + std::to_string(w));
   if (vp::frame_format_420(format) && (h & 1)) throw std::invalid_argument(me + ": " + fmt + " needs an even height (one chroma pair per 2x2 block), got " + std::to_string(h));
   FramePlanes fp;
@@ -574,14 +576,14 @@ FramePlanes frame_layout(const std::string& me, int format, int h, int w) {
 }
 
 // the refusals of vp_frame_upload* / vp_canvas_fetch, and the planes the format has
-FramePlanes check_frame_planes(const char* who, int format, const void* const* planes, const int* strides, int n_planes, int h, int w) {
+FramePlanes check_frame_planes(const char* who, int format, const void* const* planes, const int* strides, int n_planes, int h, int w, int min_side = 2) {
   const std::string me(who);
   const int fi = vp::frame_format_index(format);
   if (fi < 0) throw std::invalid_argument(me + ": unknown format " + std::to_string(format));
   const int n = format_planes(format);
   if (n_planes != n) throw std::invalid_argument(me + ": " + kFormatNames[fi] + " has " + std::to_string(n) + " plane(s), got n_planes = " + std::to_string(n_planes));
   if (!planes || !strides) throw std::invalid_argument(me + ": null planes / strides");
-  const FramePlanes fp = frame_layout(me, format, h, w);
+  const FramePlanes fp = frame_layout(me, format, h, w, min_side);
   for (int i = 0; i < fp.n; ++i) {
     if (!planes[i]) throw std::invalid_argument(me + ": plane " + std::to_string(i) + " is null");
     if (strides[i] < 0 || (size_t)strides[i] < fp.row_bytes[i])
@@ -969,6 +971,42 @@ int vp_canvas_fetch(vp_canvas* c, int format, uint8_t* const* planes, const int*
     if (!g.begun()) throw std::runtime_error("vp_canvas_fetch: the canvas holds no picture (vp_canvas_begin first)");
     const FramePlanes fp = check_frame_planes("vp_canvas_fetch", format, reinterpret_cast<const void* const*>(planes), strides, n_planes, g.h(), g.w());
     g.fetch(format, planes, strides, fp.row_bytes, fp.rows, fp.n);
+  });
+}
+
+int vp_canvas_add_planes_f32(vp_canvas* c, const float* planes, int planes_on_device, int n_planes, int mh, int mw, float threshold, const uint8_t* add_bgr, int x0,
+                             int y0, int w, int h) {
+  return canvas_guarded(c, [&](vp::Canvas& g) { g.add_planes(planes, planes_on_device != 0, n_planes, mh, mw, threshold, add_bgr, x0, y0, w, h); });
+}
+
+int vp_canvas_overlay_lanes(vp_canvas* c, vp_engine* e, float threshold) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (!e || !e->impl) throw std::invalid_argument("vp_canvas_overlay_lanes: null engine");
+    g.overlay_lanes(*e->impl, threshold);
+  });
+}
+
+int vp_canvas_draw_points(vp_canvas* c, const int* xy, int n, int radius, const uint8_t* bgr) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (n < 0 || n > 4096 || (n > 0 && !xy)) throw std::invalid_argument("vp_canvas_draw_points: n outside 0 .. 4096, or null points with n > 0");
+    if (radius < 0 || radius > vp::kCanvasMaxRadius) throw std::invalid_argument("vp_canvas_draw_points: radius " + std::to_string(radius) + " (0 .. 16)");
+    if (!bgr) throw std::invalid_argument("vp_canvas_draw_points: null colour");
+    g.draw_points(xy, n, radius, (unsigned)bgr[0] | ((unsigned)bgr[1] << 8) | ((unsigned)bgr[2] << 16));
+  });
+}
+
+int vp_canvas_draw_lane_rows(vp_canvas* c, vp_engine* e) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (!e || !e->impl) throw std::invalid_argument("vp_canvas_draw_lane_rows: null engine");
+    g.draw_lane_rows(*e->impl);
+  });
+}
+
+int vp_canvas_fetch_resized(vp_canvas* c, int format, int out_h, int out_w, uint8_t* const* planes, const int* strides, int n_planes) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (!g.begun()) throw std::runtime_error("vp_canvas_fetch_resized: the canvas holds no picture (vp_canvas_begin first)");
+    const FramePlanes fp = check_frame_planes("vp_canvas_fetch_resized", format, reinterpret_cast<const void* const*>(planes), strides, n_planes, out_h, out_w, 1);
+    g.fetch_resized(format, out_h, out_w, planes, strides, fp.row_bytes, fp.rows, fp.n);
   });
 }
 

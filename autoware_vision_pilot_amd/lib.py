@@ -181,6 +181,11 @@ _SIGS = {
     "vp_canvas_set_color": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "vp_canvas_get_color": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vp_canvas_fetch": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int]),
+    "vp_canvas_add_planes_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vp_canvas_overlay_lanes": (C.c_int, [_P, _P, C.c_float]),
+    "vp_canvas_draw_points": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "vp_canvas_draw_lane_rows": (C.c_int, [_P, _P]),
+    "vp_canvas_fetch_resized": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int]),
 }
 # multi-camera exchange (csrc/vp_comm.cpp): part of libvp_hip.so, absent from the CPU-emulated test build
 _COMM_SIGS = {
@@ -849,8 +854,9 @@ def canvas_layout3(fmt, h, w):
 
 class Canvas:
     """vp_canvas: one picture per camera frame, composed on the device.  begin(frame) copies the Frame's BGR8 picture; every Engine (heads included)
-    blends its mask or pastes its depth map into the region its input came from; detections are drawn as boxes; fetch(fmt) returns the picture once,
-    in any Frame format.  One thread drives a canvas (include/vp_hip.h)."""
+    blends its mask or pastes its depth map into the region its input came from; detections are drawn as boxes; overlay_lanes draws an EgoLanes
+    engine's lanes in the production display's look and draw_lane_rows an AutoSteer engine's rows; fetch(fmt) returns the picture once, in any Frame
+    format, at its own size or (size=) resized on the device.  One thread drives a canvas (include/vp_hip.h)."""
 
     def __init__(self, gpu_id=0):
         self._lib = load()
@@ -934,22 +940,59 @@ class Canvas:
         self._ck(self._lib.vp_canvas_get_color(self._h, C.byref(m), C.byref(r), C.byref(k)))
         return m.value, r.value, k.value
 
-    def fetch(self, fmt="bgr8", strides=None):
+    def add_planes(self, planes, threshold, add_bgr, region, device_shape=None):
+        """vp_canvas_add_planes_f32.  planes: an [n][mh][mw] float32 array, or (with device_shape = (n, mh, mw)) a device pointer (int); add_bgr: [n][3]
+        uint8 increments; region: (x0, y0, w, h) of the canvas"""
+        x0, y0, w, h = (int(v) for v in region)
+        add = np.ascontiguousarray(add_bgr, dtype=np.uint8).reshape(-1, 3)
+        if device_shape is not None:
+            n, mh, mw = (int(v) for v in device_shape)
+            src, on_device = _P(int(planes)), 1
+        else:
+            p = np.ascontiguousarray(planes, dtype=np.float32)
+            if p.ndim != 3:
+                raise ValueError("add_planes: the planes are an [n][mh][mw] float32 array")
+            (n, mh, mw), src, on_device = p.shape, _ptr(p), 0
+        if len(add) != n:
+            raise ValueError(f"add_planes: {n} planes but {len(add)} increments")
+        self._ck(self._lib.vp_canvas_add_planes_f32(self._h, src, on_device, n, mh, mw, float(threshold), _ptr(add), x0, y0, w, h))
+
+    def overlay_lanes(self, engine, threshold=0.0):
+        """vp_canvas_overlay_lanes: the production display's three additive lane overlays, from an EgoLanes engine's device logits"""
+        self._ck(self._lib.vp_canvas_overlay_lanes(self._h, engine._h, float(threshold)))
+
+    def draw_points(self, xy, radius=3, bgr=(0, 255, 0)):
+        """vp_canvas_draw_points: xy [n][2] integer (x, y) in canvas pixels, each a filled disc of `radius` in `bgr`"""
+        pts = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+        col = np.array(bgr, dtype=np.uint8).reshape(3)
+        self._ck(self._lib.vp_canvas_draw_points(self._h, _ptr(pts) if len(pts) else None, len(pts), int(radius), _ptr(col)))
+
+    def draw_lane_rows(self, engine):
+        """vp_canvas_draw_lane_rows: the valid rows of an AutoSteer engine, read on the device"""
+        self._ck(self._lib.vp_canvas_draw_lane_rows(self._h, engine._h))
+
+    def fetch(self, fmt="bgr8", strides=None, size=None):
         """vp_canvas_fetch (synchronous): the picture as numpy planes -- bgr8 / rgb8 HxWx3, bgra8 / rgba8 HxWx4, gray8 HxW, yuy2 / uyvy Hx(2W), nv12 / nv21
         the pair (Y [H][W], UV / VU [H/2][W]), i420 / yv12 the three planes (Y [H][W], U, V / V, U [H/2][W/2]).  `strides`: row strides in bytes of the
-        buffers fetched into (default: packed)."""
+        buffers fetched into (default: packed).  `size` = (out_h, out_w): vp_canvas_fetch_resized -- the picture resized on the device (the integer
+        bilinear of the preprocess path), H x W above being the size asked for; the canvas keeps its full-size picture."""
         f = Frame._fmt(fmt)
-        h, w = self.hw()
+        h, w = self.hw() if size is None else (int(size[0]), int(size[1]))
         n = C.c_int()
         rb, rows = (C.c_int * 3)(), (C.c_int * 3)()
         if self._lib.vp_canvas_layout3(f, h, w, C.byref(n), rb, rows) != 0:
             n.value = _FRAME_PLANES.get(f, 1)   # no layout: the library words the refusal
             for i in range(3):
                 rb[i], rows[i] = 1, 1
+            if size is not None and min(h, w) == 1 and max(h, w) <= 16384 and f <= VP_FRAME_GRAY8:   # a side of 1: layouts start at 2, the resized fetch at 1
+                rb[0], rows[0] = _FRAME_PX_BYTES[f] * w, h
         st = [int(v) for v in strides] if strides is not None else [rb[i] for i in range(n.value)]
         bufs = [np.zeros((rows[min(i, 2)], max(st[i], 1)), np.uint8) for i in range(len(st))]
         arr = (_P * len(bufs))(*[b.ctypes.data for b in bufs])
-        self._ck(self._lib.vp_canvas_fetch(self._h, f, arr, (C.c_int * len(st))(*st), len(st)))
+        if size is None:
+            self._ck(self._lib.vp_canvas_fetch(self._h, f, arr, (C.c_int * len(st))(*st), len(st)))
+        else:
+            self._ck(self._lib.vp_canvas_fetch_resized(self._h, f, h, w, arr, (C.c_int * len(st))(*st), len(st)))
         planes = [np.ascontiguousarray(b[:, :rb[min(i, 2)]]) for i, b in enumerate(bufs)]
         if f <= VP_FRAME_RGBA8:
             planes[0] = planes[0].reshape(h, w, _FRAME_PX_BYTES[f])

@@ -482,6 +482,43 @@ int vp_infer_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h);
  *   Refusals as vp_frame_upload: odd w for the YUV formats, odd h for NV12 / I420 / YV12 / NV21, a stride below the row's bytes, a wrong n_planes, an
  *   unknown format.  vp_canvas_layout3 (host only, no device) answers the planes of (format, h, w): n_planes, bytes per row and rows of each;
  *   VP_ERR_ARG for the same geometry refusals.  vp_canvas_layout is the same with room for two planes: VP_ERR_ARG for I420 / YV12.
+ * THE PRODUCTION DISPLAY (production_release/main.cpp:881-907: boxes, lanes by drawRawMasksInPlace, cv::resize to 1280 x 720) as calls:
+ *     vp_canvas_begin(c, f);  vp_canvas_draw_detections(c, dets, n);  vp_canvas_overlay_lanes(c, egolanes, 0.0f);
+ *     vp_canvas_fetch_resized(c, VP_FRAME_NV12, 720, 1280, planes, strides, 2);
+ * vp_canvas_add_planes_f32: the operator entry of the additive overlay.  planes: fp32 [n_planes][mh][mw] -- host memory, copied before the call returns,
+ *   or (planes_on_device) device memory on the canvas's GPU that is complete when the call is made; add_bgr: u8 [n_planes][3], host.  For every canvas
+ *   pixel of the region (x0, y0, w, h), (my, mx) comes from the nearest tables of vp_mask_resized_u8 (the region's h and w into mh and mw, as
+ *   vp_canvas_blend_mask_u8); every plane k with planes[k][my][mx] > threshold (fp32 compare: NaN is false) adds add_bgr[k] to the pixel, and each
+ *   channel becomes min(255, d + the sum of those increments).  All increments are non-negative, so the one clamped sum equals the overlays applied one
+ *   after the other in any order; a pixel that belongs to two planes shows both.  VP_ERR_ARG: n_planes outside 1 .. 4, a null pointer, mh or mw
+ *   outside 1 .. 16384, a threshold that is not finite, a region outside the canvas or smaller than 2 x 2.  VP_ERR_STATE on a canvas without a picture.
+ * vp_canvas_overlay_lanes: drawRawMasksInPlace (production_release/src/visualization/visualize.cpp:312-388) on a VP_EGOLANES engine (base or
+ *   shared-prefix head): the engine's device logits {1, 3, 80, 160} are the planes -- 0 ego left, 1 ego right, 2 other lanes -- drawn into the region
+ *   the engine's input came from.  The reference makes three overlays addWeighted(image, 1.0, colour layer under the mask, 0.4) with the BGR colours
+ *   (0, 153, 0) other, (255, 0, 0) ego left, (255, 0, 200) ego right: on a byte d that is d + 0.4 colour rounded, the same increment for every d and
+ *   never a tie in either float32 spelling of addWeighted -- other (0, 61, 0), ego left (102, 0, 0), ego right (102, 0, 80) -- then the clamp to 255.
+ *   `threshold` is compared with the raw logit (the reference thresholds its own post-processed planes: the caller chooses the value that corresponds).
+ *   Any decode mode: only the logits are read.  The reference overlays on a 640 x 320 copy of the region and resizes that copy back; this call draws
+ *   at the region's own resolution instead (the picture's pixels are never resampled).  VP_ERR_ARG for any kind but VP_EGOLANES, a non-finite
+ *   threshold and the geometry / GPU / tensor-input refusals of vp_canvas_blend_mask; VP_ERR_STATE before the engine's first pass.
+ * vp_canvas_draw_points: host int xy[n][2] (x, y) in canvas pixels, bgr u8 [3].  Each point sets the disc dx * dx + dy * dy <= radius * radius around it
+ *   to the colour, clipped to the canvas; for radius 3 the row half-widths are 3, 2, 2, 0 (dy = 0, 1, 2, 3: 29 pixels).  This rule IS the definition;
+ *   like the other OpenCV restatements it is not pinned against cv::circle.  radius 0 .. 16, n 0 .. 4096; n = 0 draws nothing, a point whose disc
+ *   lies outside the canvas draws nothing.  VP_ERR_ARG: n < 0 or > 4096, null xy with n > 0, a null colour, a radius out of range.
+ * vp_canvas_draw_lane_rows: make_visualization (Models/visualizations/AutoSteer/video_visualization.py:19-44) on a VP_AUTOSTEER engine.  The kernel
+ *   reads xp[64] and h_vector[64] from the engine's device logits itself: no D2H, no host wait.  Row i is drawn when h_vector[i] >= 0.5f, as the disc
+ *   of vp_canvas_draw_points with radius 3 and BGR (0, 255, 0) around x = x0 + (int)(xp[i] * 1024.0f) (fp32 product, truncation toward zero),
+ *   y = y0 + i * 511 / 63 (integer division: numpy.linspace(0, 511, 64, dtype=int)), (x0, y0) the origin of the region the engine's input came from;
+ *   the discs are clipped to the canvas.  A row whose product is NaN or not inside (-1e8, 1e8) draws nothing.  Refusals as vp_canvas_blend_mask with
+ *   the kinds reversed: VP_ERR_ARG for any kind but VP_AUTOSTEER.  The other two lanes the script keeps commented out, text and curves are not built.
+ * vp_canvas_fetch_resized: vp_canvas_fetch of the picture resized to out_h x out_w (each 1 .. 16384) -- the display thread's
+ *   cv::resize(unified_frame, display_frame, Size(1280, 720)) -- without a full-size D2H.  The resize is the integer bilinear of VP_RESIZE_CV_LINEAR:
+ *   the u8 value the preprocess path forms ahead of normalisation (same tap tables, same device arithmetic; restated by oracle/pre_post.py
+ *   resize_bilinear_u8).  The result is a second device picture; format conversion, colour standard, chroma rule and refusals are vp_canvas_fetch's,
+ *   applied to (out_h, out_w); vp_canvas_layout3(format, out_h, out_w, ..) answers the planes (for a side of 1, which only the one-plane formats
+ *   without chroma pairs take, a plane is out_h rows of pixel bytes x out_w).  The canvas itself is unchanged: later draws and fetches see the
+ *   full-size picture.  With (out_h, out_w) the canvas's own geometry the bytes equal vp_canvas_fetch's (the identity taps weigh (2048, 0)).  Host waits
+ *   beyond the fetch itself: the once-per-geometry ones of the ORDERING CONTRACT (the second picture growing, the first use of a tap table).
  * vp_canvas_device / vp_canvas_sync: the device picture (BGR8, rows *pitch_bytes apart) for a device consumer such as an encoder; complete after
  *   vp_canvas_sync, valid until the next vp_canvas_begin or vp_canvas_destroy.
  * ORDERING CONTRACT (vp_frame's, in the other direction).  Nothing waits on the host before vp_canvas_fetch / vp_canvas_sync.  A draw call makes the
@@ -508,6 +545,12 @@ int vp_canvas_layout3(int format, int h, int w, int* n_planes, int row_bytes[3],
 int vp_canvas_set_color(vp_canvas* c, int matrix, int range, int chroma_mode);   /* applies to later fetches; not inherited from the frame */
 int vp_canvas_get_color(const vp_canvas* c, int* matrix, int* range, int* chroma_mode);
 int vp_canvas_fetch(vp_canvas* c, int format, uint8_t* const* planes, const int* strides, int n_planes);
+int vp_canvas_add_planes_f32(vp_canvas* c, const float* planes, int planes_on_device, int n_planes, int mh, int mw, float threshold, const uint8_t* add_bgr, int x0,
+                             int y0, int w, int h);
+int vp_canvas_overlay_lanes(vp_canvas* c, vp_engine* egolanes, float threshold);
+int vp_canvas_draw_points(vp_canvas* c, const int* xy, int n, int radius, const uint8_t* bgr);
+int vp_canvas_draw_lane_rows(vp_canvas* c, vp_engine* autosteer);
+int vp_canvas_fetch_resized(vp_canvas* c, int format, int out_h, int out_w, uint8_t* const* planes, const int* strides, int n_planes);
 
 /* ---- multi-camera result exchange (BASELINE configs[3]) ---------------------------------------
  * One process (or thread) per GPU, camera r on rank r, weights replicated, no data-path collective in the networks.  For the
