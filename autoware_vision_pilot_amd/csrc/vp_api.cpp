@@ -1191,79 +1191,7 @@ int vp_range_survey(vp_engine* e, vp_range_stats* out, int cap) {
   return rc == VP_OK ? n : rc;
 }
 
-int vp_op_conv2d(int gpu_id, int precision, int mode, const float* in, int cin, int h, int w, const float* weight, const float* bias,
-                 int cout, int ks, int act, int res_mode, const float* res, int tile, int bk, int nsplit, float* out, char* err,
-                 size_t err_len) {
-  if (!in || !weight || !bias || !out || cin < 1 || cout < 1 || h < 1 || w < 1) {
-    set_err(err, err_len, "bad argument");
-    return VP_ERR_ARG;
-  }
-  try {
-    vp::Engine g(-1, nullptr, precision, gpu_id);
-    vp::Act* a = g.new_act("in", cin, h, w);
-    g.upload_act(a, in);
-    const int oh = mode >= 1 ? 2 * h : h, ow = mode >= 1 ? 2 * w : w;
-    if (mode == 2) {  // ConvTranspose2d(k2, s2)(in) + Conv2d 1x1(skip): `res` is the skip INPUT [res_mode channels][2h][2w]
-      const int cs = res_mode;
-      if (!res || cs < 1) throw std::invalid_argument("mode 2: res = skip tensor, res_mode = its channel count");
-      vp::Act* sk = g.new_act("skip", cs, oh, ow);
-      g.upload_act(sk, res);
-      const size_t wt_n = (size_t)cin * cout * 4;
-      std::vector<float> wt(weight, weight + wt_n), ws(weight + wt_n, weight + wt_n + (size_t)cout * cs), bt(bias, bias + cout),
-          bs(bias + cout, bias + 2 * cout);
-      vp::Act* y = g.add_convT_skip("op", "op.skip", a, sk, wt, bt, ws, bs, cout);
-      g.run_eager();
-      g.sync();
-      for (size_t i = 0; i < g.acts().size(); ++i)
-        if (g.acts()[i].get() == y) g.read_act((int)i, out);
-      return VP_OK;
-    }
-    if (mode == 3) {  // a head's logits convolution: 3x3, fp32 NCHW output straight from the kernel (STORE_NCHW_F32)
-      if (ks != 3 || act != 0 || res_mode != 0) throw std::invalid_argument("mode 3: 3x3, no activation, no residual");
-      float* d_out = g.alloc_f32((size_t)cout * h * w);
-      vp::ConvOpts lo;
-      lo.tile = tile;
-      lo.logits_out = d_out;
-      const size_t wn3 = (size_t)cin * cout * 9;
-      g.add_conv("op", a, std::vector<float>(weight, weight + wn3), std::vector<float>(bias, bias + cout), cout, 3, lo);
-      g.run_eager();
-      g.sync();
-      g.copy_d2h(out, d_out, (size_t)cout * h * w * sizeof(float));
-      return VP_OK;
-    }
-    vp::ConvOpts o;
-    o.act = act;
-    o.tile = tile;
-    o.bk = bk;
-    o.nsplit = nsplit;
-    vp::Act* r = nullptr;
-    if (res_mode != 0) {
-      if (!res) throw std::invalid_argument("res_mode set but res is null");
-      r = g.new_act("res", cout, oh, ow);
-      g.upload_act(r, res);
-      o.res_mode = res_mode;
-      o.res = r;
-    }
-    const size_t wn = (size_t)cin * cout * (mode == 1 ? 4 : ks * ks);
-    std::vector<float> wv(weight, weight + wn), bv(bias, bias + cout);
-    vp::Act* y = mode == 1 ? g.add_convT("op", a, wv, bv, cout, o) : g.add_conv("op", a, wv, bv, cout, ks, o);
-    g.run_eager();
-    g.sync();
-    int idx = -1;
-    for (size_t i = 0; i < g.acts().size(); ++i)
-      if (g.acts()[i].get() == y) idx = (int)i;
-    g.read_act(idx, out);
-    return VP_OK;
-  } catch (const std::invalid_argument& ex) {
-    set_err(err, err_len, ex.what());
-    return VP_ERR_ARG;
-  } catch (const std::exception& ex) {
-    set_err(err, err_len, ex.what());
-    return VP_ERR_HIP;
-  }
-}
-
-// ---- single-operator entries of the detector network's kernels (unit tests)
+// ---- single-operator entries (unit tests launch one kernel or one add_* call through them; no host calls them)
 }  // extern "C"
 namespace {
 // (hi, lo) planes of an activation, NHWC with padded channels on the device -> fp16 bit patterns [Creal][H][W] on the host
@@ -1282,14 +1210,18 @@ void read_planes_chw(vp::Engine& g, const vp::Act* a, uint16_t* out_hi, uint16_t
       for (int i = 0; i < a->H * a->W; ++i) dst[(size_t)c * a->H * a->W + i] = buf[(size_t)i * a->C + c];
   }
 }
+// on_range: what a vp::RangeError (a weight beyond the fp16 range) becomes -- VP_ERR_RANGE for vp_op_upconv alone
 template <class F>
-int op_guarded(char* err, size_t err_len, F&& f) {
+int op_guarded(char* err, size_t err_len, F&& f, int on_range = VP_ERR_HIP) {
   try {
     f();
     return VP_OK;
   } catch (const std::invalid_argument& ex) {
     set_err(err, err_len, ex.what());
     return VP_ERR_ARG;
+  } catch (const vp::RangeError& ex) {
+    set_err(err, err_len, ex.what());
+    return on_range;
   } catch (const std::exception& ex) {
     set_err(err, err_len, ex.what());
     return VP_ERR_HIP;
@@ -1302,6 +1234,34 @@ void upload_act_scaled(vp::Engine& g, vp::Act* a, const float* chw, int e) {
   std::vector<float> v(chw, chw + (size_t)a->Creal * a->H * a->W);
   for (float& x : v) x = std::ldexp(x, -e);
   g.upload_act(a, v.data());
+}
+// fp32 CHW values of a tensor the entry holds (Engine::read_act goes by the index in acts())
+void read_act_chw(vp::Engine& g, const vp::Act* a, float* out) {
+  for (size_t i = 0; i < g.acts().size(); ++i)
+    if (g.acts()[i].get() == a) return g.read_act((int)i, out);
+  throw std::runtime_error("read_act_chw: not a tensor of this engine");
+}
+float* to_device(vp::Engine& g, const std::vector<float>& v) {
+  float* d = g.alloc_f32(v.size());
+  g.copy_h2d(d, v.data(), v.size() * sizeof(float));
+  return d;
+}
+// vp_op_absmax / vp_op_exp_hist: fp16 bit patterns [h][w][c_pitch], lo may be null -- the refusals both share (ahead of the engine, so that they do
+// not need a device), and the planes on the engine's device
+void check_planes(bool pointers, int c, int h, int w, int c_pitch) {   // pointers: hi and the entry's result pointers are all there
+  if (!pointers || c < 1 || h < 1 || w < 1 || c_pitch < ((c + 7) & ~7) || (c_pitch & 7) || (long long)h * w * c_pitch > (1ll << 28))
+    throw std::invalid_argument("bad argument (c_pitch: a multiple of 8, at least c rounded up to 8)");
+}
+struct DevPlanes {
+  vp::half_t *hi, *lo;
+};
+DevPlanes upload_planes(vp::Engine& g, const uint16_t* hi, const uint16_t* lo, size_t n) {
+  DevPlanes d;
+  d.hi = reinterpret_cast<vp::half_t*>(g.alloc_f32((n + 1) / 2));
+  d.lo = lo ? reinterpret_cast<vp::half_t*>(g.alloc_f32((n + 1) / 2)) : nullptr;
+  g.copy_h2d(d.hi, hi, n * sizeof(uint16_t));
+  if (lo) g.copy_h2d(d.lo, lo, n * sizeof(uint16_t));
+  return d;
 }
 
 // exps: null = the unflagged launch (vp_op_detect_head_decode); else [3][2] exponents of (box, cls) per level
@@ -1351,9 +1311,8 @@ void op_rowpair_conv(int gpu_id, int precision, const float* in, int cin, int h,
   for (int co = 0; co < 32; ++co)
     for (int ci = 0; ci < cin; ++ci)
       for (int ky = 0; ky < 2; ++ky) wk[((size_t)ky * cin + ci) * 32 + co] = weight[((size_t)co * cin + ci) * 2 + ky];
-  float* dw = g.alloc_f32(wk.size());
+  float* dw = to_device(g, wk);
   float* db = g.alloc_f32(32);
-  g.copy_h2d(dw, wk.data(), wk.size() * sizeof(float));
   g.copy_h2d(db, bias, 32 * sizeof(float));
   vp::RowpairConvParams q{};
   q.in = ti->view();
@@ -1392,10 +1351,8 @@ void op_lane_rows_head(int gpu_id, int precision, const float* features, int cin
   hk[33] = c2_b;
   hk[34] = h1_b;
   hk[35] = h2_b;
-  float* dw = g.alloc_f32(wk.size());
-  float* dh = g.alloc_f32(hk.size());
-  g.copy_h2d(dw, wk.data(), wk.size() * sizeof(float));
-  g.copy_h2d(dh, hk.data(), hk.size() * sizeof(float));
+  float* dw = to_device(g, wk);
+  float* dh = to_device(g, hk);
   vp::LaneRowsHeadParams q{};
   q.features = tf->view();
   q.cin = cin;
@@ -1409,6 +1366,62 @@ void op_lane_rows_head(int gpu_id, int precision, const float* features, int cin
 }
 }  // namespace
 extern "C" {
+
+int vp_op_conv2d(int gpu_id, int precision, int mode, const float* in, int cin, int h, int w, const float* weight, const float* bias,
+                 int cout, int ks, int act, int res_mode, const float* res, int tile, int bk, int nsplit, float* out, char* err,
+                 size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!in || !weight || !bias || !out || cin < 1 || cout < 1 || h < 1 || w < 1) throw std::invalid_argument("bad argument");
+    vp::Engine g(-1, nullptr, precision, gpu_id);
+    vp::Act* a = g.new_act("in", cin, h, w);
+    g.upload_act(a, in);
+    const int oh = mode >= 1 ? 2 * h : h, ow = mode >= 1 ? 2 * w : w;
+    if (mode == 2) {  // ConvTranspose2d(k2, s2)(in) + Conv2d 1x1(skip): `res` is the skip INPUT [res_mode channels][2h][2w]
+      const int cs = res_mode;
+      if (!res || cs < 1) throw std::invalid_argument("mode 2: res = skip tensor, res_mode = its channel count");
+      vp::Act* sk = g.new_act("skip", cs, oh, ow);
+      g.upload_act(sk, res);
+      const size_t wt_n = (size_t)cin * cout * 4;
+      std::vector<float> wt(weight, weight + wt_n), ws(weight + wt_n, weight + wt_n + (size_t)cout * cs), bt(bias, bias + cout),
+          bs(bias + cout, bias + 2 * cout);
+      vp::Act* y = g.add_convT_skip("op", "op.skip", a, sk, wt, bt, ws, bs, cout);
+      g.run_eager();
+      g.sync();
+      return read_act_chw(g, y, out);
+    }
+    if (mode == 3) {  // a head's logits convolution: 3x3, fp32 NCHW output straight from the kernel (STORE_NCHW_F32)
+      if (ks != 3 || act != 0 || res_mode != 0) throw std::invalid_argument("mode 3: 3x3, no activation, no residual");
+      float* d_out = g.alloc_f32((size_t)cout * h * w);
+      vp::ConvOpts lo;
+      lo.tile = tile;
+      lo.logits_out = d_out;
+      const size_t wn3 = (size_t)cin * cout * 9;
+      g.add_conv("op", a, std::vector<float>(weight, weight + wn3), std::vector<float>(bias, bias + cout), cout, 3, lo);
+      g.run_eager();
+      g.sync();
+      return g.copy_d2h(out, d_out, (size_t)cout * h * w * sizeof(float));
+    }
+    vp::ConvOpts o;
+    o.act = act;
+    o.tile = tile;
+    o.bk = bk;
+    o.nsplit = nsplit;
+    vp::Act* r = nullptr;
+    if (res_mode != 0) {
+      if (!res) throw std::invalid_argument("res_mode set but res is null");
+      r = g.new_act("res", cout, oh, ow);
+      g.upload_act(r, res);
+      o.res_mode = res_mode;
+      o.res = r;
+    }
+    const size_t wn = (size_t)cin * cout * (mode == 1 ? 4 : ks * ks);
+    std::vector<float> wv(weight, weight + wn), bv(bias, bias + cout);
+    vp::Act* y = mode == 1 ? g.add_convT("op", a, wv, bv, cout, o) : g.add_conv("op", a, wv, bv, cout, ks, o);
+    g.run_eager();
+    g.sync();
+    read_act_chw(g, y, out);
+  });
+}
 
 int vp_op_detect_head_decode(int gpu_id, int precision, const float* box, const float* cls, int nc, int h0, int w0, float* out, char* err, size_t err_len) {
   return op_guarded(err, err_len, [&] { op_detect_head_decode(gpu_id, precision, box, cls, nc, h0, w0, nullptr, out); });
@@ -1449,10 +1462,8 @@ int vp_op_dwconv3x3(int gpu_id, int precision, const float* in, int c, int h, in
       for (int k = 0; k < 9; ++k) wk[(size_t)k * ti->C + ch] = weight[(size_t)ch * 9 + k];
       bk[ch] = bias[ch];
     }
-    float* dw = g.alloc_f32(wk.size());
-    float* db = g.alloc_f32(bk.size());
-    g.copy_h2d(dw, wk.data(), wk.size() * sizeof(float));
-    g.copy_h2d(db, bk.data(), bk.size() * sizeof(float));
+    float* dw = to_device(g, wk);
+    float* db = to_device(g, bk);
     vp::DwPlainParams dp{};
     dp.in = ti->view();
     dp.out = to->view();
@@ -1472,16 +1483,11 @@ int vp_op_dwconv3x3(int gpu_id, int precision, const float* in, int c, int h, in
 // ---- single-operator entries of the VP_ACT_SCALE mechanism (unit tests)
 int vp_op_absmax(int gpu_id, const uint16_t* hi, const uint16_t* lo, int c, int h, int w, int c_pitch, float* absmax, unsigned* nonfinite, char* err, size_t err_len) {
   return op_guarded(err, err_len, [&] {
-    if (!hi || !absmax || !nonfinite || c < 1 || h < 1 || w < 1 || c_pitch < ((c + 7) & ~7) || (c_pitch & 7) || (long long)h * w * c_pitch > (1ll << 28))
-      throw std::invalid_argument("bad argument (c_pitch: a multiple of 8, at least c rounded up to 8)");
+    check_planes(hi && absmax && nonfinite, c, h, w, c_pitch);
     vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
-    const size_t n = (size_t)h * w * c_pitch;
-    vp::half_t* dh = reinterpret_cast<vp::half_t*>(g.alloc_f32((n + 1) / 2));
-    vp::half_t* dl = lo ? reinterpret_cast<vp::half_t*>(g.alloc_f32((n + 1) / 2)) : nullptr;
+    const DevPlanes d = upload_planes(g, hi, lo, (size_t)h * w * c_pitch);
     unsigned* dr = reinterpret_cast<unsigned*>(g.alloc_f32(2));   // zeroed
-    g.copy_h2d(dh, hi, n * sizeof(uint16_t));
-    if (lo) g.copy_h2d(dl, lo, n * sizeof(uint16_t));
-    VP_HIP_CHECK(vp::launch_act_absmax(dh, dl, c, h, w, c_pitch, dr, g.stream()));
+    VP_HIP_CHECK(vp::launch_act_absmax(d.hi, d.lo, c, h, w, c_pitch, dr, g.stream()));
     unsigned r[2];
     g.copy_d2h(r, dr, sizeof(r));
     std::memcpy(absmax, &r[0], sizeof(float));
@@ -1492,16 +1498,11 @@ int vp_op_absmax(int gpu_id, const uint16_t* hi, const uint16_t* lo, int c, int 
 int vp_op_exp_hist(int gpu_id, const uint16_t* hi, const uint16_t* lo, int c, int h, int w, int c_pitch, unsigned long long* bins, unsigned long long* zeros,
                    unsigned long long* count, char* err, size_t err_len) {
   return op_guarded(err, err_len, [&] {
-    if (!hi || !bins || !zeros || !count || c < 1 || h < 1 || w < 1 || c_pitch < ((c + 7) & ~7) || (c_pitch & 7) || (long long)h * w * c_pitch > (1ll << 28))
-      throw std::invalid_argument("bad argument (c_pitch: a multiple of 8, at least c rounded up to 8)");
+    check_planes(hi && bins && zeros && count, c, h, w, c_pitch);
     vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
-    const size_t n = (size_t)h * w * c_pitch;
-    vp::half_t* dh = reinterpret_cast<vp::half_t*>(g.alloc_f32((n + 1) / 2));
-    vp::half_t* dl = lo ? reinterpret_cast<vp::half_t*>(g.alloc_f32((n + 1) / 2)) : nullptr;
+    const DevPlanes d = upload_planes(g, hi, lo, (size_t)h * w * c_pitch);
     unsigned long long* dr = reinterpret_cast<unsigned long long*>(g.alloc_f32(2 * vp::VP_HIST_WORDS));   // zeroed
-    g.copy_h2d(dh, hi, n * sizeof(uint16_t));
-    if (lo) g.copy_h2d(dl, lo, n * sizeof(uint16_t));
-    VP_HIP_CHECK(vp::launch_act_exp_hist(dh, dl, c, h, w, c_pitch, dr, g.stream()));
+    VP_HIP_CHECK(vp::launch_act_exp_hist(d.hi, d.lo, c, h, w, c_pitch, dr, g.stream()));
     unsigned long long r[vp::VP_HIST_WORDS];
     g.copy_d2h(r, dr, sizeof(r));
     std::memcpy(bins, r, VP_RANGE_BINS * sizeof(unsigned long long));
@@ -1517,14 +1518,8 @@ int vp_op_conv2d_scaled(int gpu_id, int precision, int mode, const float* in, in
     if (!in || !weight || !bias || !out_hi || cin < 1 || cout < 1 || h < 1 || w < 1 || (long long)h * w > (1 << 20)) throw std::invalid_argument("bad argument");
     if (mode != 0) throw std::invalid_argument("vp_op_conv2d_scaled: mode 0 (Conv2d) only");
     vp::Engine g(-1, nullptr, precision | VP_ACT_SCALE, gpu_id);
-    // the planes hold x * 2^-s: the host scales the true-valued arguments (exact) before they are split
-    auto scaled_copy = [](const float* src, size_t n, int e) {
-      std::vector<float> v(src, src + n);
-      for (float& x : v) x = std::ldexp(x, -e);
-      return v;
-    };
     vp::Act* a = g.new_act("in", cin, h, w);
-    g.upload_act(a, scaled_copy(in, (size_t)cin * h * w, in_exp).data());
+    upload_act_scaled(g, a, in, in_exp);
     g.set_act_exp(a, in_exp);
     vp::ConvOpts o;
     o.act = act;
@@ -1534,7 +1529,7 @@ int vp_op_conv2d_scaled(int gpu_id, int precision, int mode, const float* in, in
     if (res_mode != 0) {
       if (!res) throw std::invalid_argument("res_mode set but res is null");
       vp::Act* r = g.new_act("res", cout, h, w);
-      g.upload_act(r, scaled_copy(res, (size_t)cout * h * w, res_exp).data());
+      upload_act_scaled(g, r, res, res_exp);
       g.set_act_exp(r, res_exp);
       o.res_mode = res_mode;
       o.res = r;
@@ -1669,39 +1664,24 @@ int vp_op_lane_rows_head_scaled(int gpu_id, int precision, const float* features
 // ---- composed up-sampling stage (round 6): the load-time weight composition alone, and the whole stage as one operator
 int vp_compose_upconv(int gpu_id, const float* wt, const float* bt, const float* ws, const float* bs, const float* w3, const float* b3, int cin, int cm,
                       int cout, int cs, double* wx, double* wsk, double* bias, char* err, size_t err_len) {
-  if (!wt || !bt || !w3 || !b3 || !wx || !bias || cin < 1 || cm < 1 || cout < 1 || cs < 0 || (cs > 0 && (!ws || !bs || !wsk))) {
-    set_err(err, err_len, "bad argument");
-    return VP_ERR_ARG;
-  }
-  try {
+  return op_guarded(err, err_len, [&] {
+    if (!wt || !bt || !w3 || !b3 || !wx || !bias || cin < 1 || cm < 1 || cout < 1 || cs < 0 || (cs > 0 && (!ws || !bs || !wsk))) throw std::invalid_argument("bad argument");
     vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
     vp::UpconvComposed c;
     g.compose_upconv(wt, bt, ws, bs, w3, b3, cin, cm, cout, cs, &c);
     std::memcpy(wx, c.wx.data(), c.wx.size() * sizeof(double));
     if (cs > 0) std::memcpy(wsk, c.ws.data(), c.ws.size() * sizeof(double));
     std::memcpy(bias, c.bias.data(), c.bias.size() * sizeof(double));
-    return VP_OK;
-  } catch (const std::invalid_argument& ex) {
-    set_err(err, err_len, ex.what());
-    return VP_ERR_ARG;
-  } catch (const std::exception& ex) {
-    set_err(err, err_len, ex.what());
-    return VP_ERR_HIP;
-  }
+  });
 }
 
 int vp_op_upconv(int gpu_id, const float* in, int cin, int h, int w, const float* skip, int cs, const float* wt, const float* bt, const float* ws,
                  const float* bs, const float* w3, const float* b3, int cm, int cout, int act, int shape, int nsplit, int precision, float* out, char* err,
                  size_t err_len) {
-  if (precision != VP_FP16 && precision != VP_FP16X3) {
-    set_err(err, err_len, "precision must be VP_FP16 or VP_FP16X3");
-    return VP_ERR_ARG;
-  }
-  if (!in || !wt || !bt || !w3 || !b3 || !out || cin < 1 || cm < 1 || cout < 1 || h < 1 || w < 1 || cs < 0 || (cs > 0 && (!skip || !ws || !bs))) {
-    set_err(err, err_len, "bad argument");
-    return VP_ERR_ARG;
-  }
-  try {
+  return op_guarded(err, err_len, [&] {
+    if (precision != VP_FP16 && precision != VP_FP16X3) throw std::invalid_argument("precision must be VP_FP16 or VP_FP16X3");
+    if (!in || !wt || !bt || !w3 || !b3 || !out || cin < 1 || cm < 1 || cout < 1 || h < 1 || w < 1 || cs < 0 || (cs > 0 && (!skip || !ws || !bs)))
+      throw std::invalid_argument("bad argument");
     vp::Engine g(-1, nullptr, precision, gpu_id);
     vp::Act* a = g.new_act("in", cin, h, w);
     g.upload_act(a, in);
@@ -1715,19 +1695,8 @@ int vp_op_upconv(int gpu_id, const float* in, int cin, int h, int w, const float
     vp::Act* y = g.add_upconv("op", a, sk, vwt, vbt, vws, vbs, vw3, vb3, cm, cout, act, shape, nsplit);
     g.run_eager();
     g.sync();
-    for (size_t i = 0; i < g.acts().size(); ++i)
-      if (g.acts()[i].get() == y) g.read_act((int)i, out);
-    return VP_OK;
-  } catch (const vp::RangeError& ex) {
-    set_err(err, err_len, ex.what());
-    return VP_ERR_RANGE;
-  } catch (const std::invalid_argument& ex) {
-    set_err(err, err_len, ex.what());
-    return VP_ERR_ARG;
-  } catch (const std::exception& ex) {
-    set_err(err, err_len, ex.what());
-    return VP_ERR_HIP;
-  }
+    read_act_chw(g, y, out);
+  }, VP_ERR_RANGE);
 }
 
 }  // extern "C"

@@ -3,7 +3,6 @@ CPU-emulated engine (tests/emul: the real kernel and engine sources on the HIP-o
 groups of both plans, and the lane network end to end.  The GPU twin is tests/test_gpu_act_scale_nets.py; the cases are tests/act_scale_nets_cases.py."""
 import ctypes as ct
 import os
-import re
 import subprocess
 import sys
 
@@ -14,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
 sys.path.insert(0, HERE)
+import abi  # noqa: E402
 import act_scale_nets_cases as cases  # noqa: E402
 
 NEW_SYMBOLS = ("vp_op_upsample2_cat_scaled", "vp_op_detect_head_decode_scaled", "vp_op_rowpair_conv_scaled", "vp_op_lane_rows_head_scaled")
@@ -22,11 +22,9 @@ NEW_SYMBOLS = ("vp_op_upsample2_cat_scaled", "vp_op_detect_head_decode_scaled", 
 def test_abi_exports_the_new_operator_entries():
     from autoware_vision_pilot_amd import lib
 
-    header = open(os.path.join(ROOT, "include", "vp_hip.h")).read()
-    nm = subprocess.run(["nm", "-D", "--defined-only", lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (vp_[a-z0-9_]+)", nm))
+    declared, exported = abi.declared_symbols(), abi.exported_symbols()
     for s in NEW_SYMBOLS:
-        assert re.search(r"\b%s\(" % s, header), s
+        assert s in declared, s
         assert s in lib.EXPORTED_SYMBOLS and s in exported, s
 
 

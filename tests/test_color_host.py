@@ -5,16 +5,15 @@ consumer and the refusals.  Cases: tests/color_cases.py."""
 import ctypes as ct
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+import abi  # noqa: E402
 import canvas_cases as cc  # noqa: E402
 import color_cases as kc  # noqa: E402
 import frame_cases as fc  # noqa: E402
@@ -46,10 +45,8 @@ def emu_lib():
 def test_new_symbols_and_codes_are_declared_exported_and_bound():
     from autoware_vision_pilot_amd import lib
 
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vp_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(vp_[a-z0-9_]+)\s*\(", src))
-    nm = subprocess.run(["nm", "-D", "--defined-only", lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (vp_[a-z0-9_]+)", nm))
+    src = abi.header_source()
+    declared, exported = abi.declared_symbols(), abi.exported_symbols()
     for s in NEW_SYMBOLS:
         assert s in declared and s in exported and s in lib.EXPORTED_SYMBOLS, s
     for name, code in kc.CODES.items():
@@ -62,7 +59,7 @@ def test_new_symbols_and_codes_are_declared_exported_and_bound():
 
 def test_header_states_every_constant():
     """both tables of include/vp_hip.h, row by row, are the ones the oracle uses"""
-    text = open(os.path.join(ROOT, "include", "vp_hip.h")).read()
+    text = open(abi.HEADER).read()
     rows = {}
     for m in re.finditer(r"\*\s+BT\.(601|709) (limited|full)\s+((?:-?\d+\s+)+)", text):
         rows.setdefault(("bt" + m.group(1), m.group(2)), []).append(tuple(int(v) for v in m.group(3).split()))

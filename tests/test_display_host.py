@@ -4,17 +4,15 @@ real kernel and engine code (tests/emul) -- the operator entries bit for bit on 
 pass whose overlay equals the restatement on the logits vp_logits returns."""
 import ctypes as ct
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+import abi  # noqa: E402
 import canvas_cases as cc  # noqa: E402
 import display_cases as dc  # noqa: E402
 
@@ -42,10 +40,7 @@ def emu_lib():
 def test_new_symbols_are_declared_exported_and_bound():
     from autoware_vision_pilot_amd import lib
 
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vp_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(vp_[a-z0-9_]+)\s*\(", src))
-    nm = subprocess.run(["nm", "-D", "--defined-only", lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (vp_[a-z0-9_]+)", nm))
+    declared, exported = abi.declared_symbols(), abi.exported_symbols()
     for s in NEW_SYMBOLS:
         assert s in declared, s
         assert s in exported, s

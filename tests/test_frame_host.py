@@ -3,17 +3,15 @@ oracle, and -- on the HIP-on-CPU emulation of the real kernel and engine code (t
 (AutoDrive: frame region in, the host path's bits out)."""
 import ctypes as ct
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+import abi  # noqa: E402
 import frame_cases as fc  # noqa: E402
 
 NEW_SYMBOLS = ("vp_frame_create", "vp_frame_destroy", "vp_frame_last_error", "vp_frame_upload", "vp_frame_upload_device", "vp_frame_sync", "vp_frame_dims",
@@ -41,10 +39,8 @@ def emu_lib():
 def test_new_symbols_are_declared_exported_and_bound():
     from autoware_vision_pilot_amd import lib
 
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vp_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(vp_[a-z0-9_]+)\s*\(", src))
-    nm = subprocess.run(["nm", "-D", "--defined-only", lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (vp_[a-z0-9_]+)", nm))
+    src = abi.header_source()
+    declared, exported = abi.declared_symbols(), abi.exported_symbols()
     for s in NEW_SYMBOLS:
         assert s in declared, s
         assert s in exported, s

@@ -1,6 +1,6 @@
 """CPU suite, part 2: the host logic and the C-ABI surface (no compute calls: there is no GPU here).
 
-* libvp_hip.so loads and exports every symbol include/vp_hip.h declares;
+* libvp_hip.so loads and exports exactly the symbols include/vp_hip.h declares;
 * the product fails LOUDLY without a GPU / with bad weights (no CPU fallback exists);
 * weight-blob writer layout; Python operator API argument checks;
 * multi-camera sharding + record gather under a world_size-2 gloo process group;
@@ -19,22 +19,20 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _header_symbols():
-    src = open(os.path.join(ROOT, "include", "vp_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(vp_[a-z0-9_]+)\s*\(", src)))
-
-
 def test_abi_exports_every_declared_symbol():
+    """the header, the binding and the library's dynamic symbol table name the same entries: nothing else leaves the library"""
+    import abi
     from autoware_vision_pilot_amd import lib
 
-    declared = _header_symbols()
+    declared = sorted(abi.declared_symbols())
     assert len(declared) >= 30
     assert sorted(lib.EXPORTED_SYMBOLS) == declared, set(declared) ^ set(lib.EXPORTED_SYMBOLS)
     so = lib.load()  # binds all of them; AttributeError if one is missing
-    nm = subprocess.run(["nm", "-D", "--defined-only", lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (vp_[a-z0-9_]+)", nm))
-    assert set(declared) <= exported
+    exported = abi.exported_symbols()   # every defined dynamic symbol, of any type
+    expected = set(declared)
+    if not exported & set(lib._COMM_SIGS):   # built with VP_NO_COMM=1: a library without the multi-camera exchange (vp_comm_*, vp_gather)
+        expected -= set(lib._COMM_SIGS)
+    assert exported == expected, exported ^ expected
     assert so.vp_version().startswith(b"libvp_hip")
 
 
