@@ -201,6 +201,28 @@ struct CanvasResizeParams {
   int dst_pitch, out_h, out_w;
 };
 hipError_t launch_canvas_resize(const CanvasResizeParams& p, hipStream_t st);
+// frame_remap_kernel: one BGR8 picture resampled through a per-pixel map (vp_frame's rectification: undistort, warp to the standard pose; include/vp_hip.h
+// states the sample as the DEFINITION).  A map entry is (X, Y), the source coordinates of a destination pixel in units of 1/32 pixel, both inside
+// [-2^20, 2^20 - 1]: ix = X >> 5, fx = X & 31 (likewise y); taps (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1) with the weights (32 - fx)(32 - fy),
+// fx (32 - fy), (32 - fx) fy, fx fy; out = (sum w p + 512) >> 10 per channel.  border 0 (CONSTANT): a tap outside the source contributes 0; border 1
+// (REPLICATE): tap coordinates are clamped to the picture.  Either way the addresses read are the clamped ones: no map value reads outside the source.
+// The map is row-major with rows map_pitch = frame_remap_map_pitch(out_w) entries apart (a multiple of 4, base 16-byte aligned), so that one work-item
+// reads the entries of its four pixels as two aligned 16-byte loads; it stores the three words of the block, bytes behind the row's end as 0.
+// src rows are src_pitch >= 3 * src_w bytes apart and are read byte by byte.
+struct RemapEntry {
+  int x, y;
+};
+inline int frame_remap_map_pitch(int out_w) { return 4 * ((out_w + 3) / 4); }
+struct FrameRemapParams {
+  const uint8_t* src;
+  int src_pitch, src_h, src_w;
+  const RemapEntry* map;   // [out_h][map_pitch]
+  int map_pitch;
+  int border;              // 0 CONSTANT (value 0), 1 REPLICATE
+  uint8_t* dst;
+  int dst_pitch, out_h, out_w;
+};
+hipError_t launch_frame_remap(const FrameRemapParams& p, hipStream_t st);
 
 struct StemParams {
   const float* in;  // [3][H][W]

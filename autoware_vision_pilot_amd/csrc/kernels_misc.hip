@@ -124,6 +124,48 @@ __global__ __launch_bounds__(256) void frame_to_bgr8_kernel(const FrameToBgrPara
   store_bgr4(p.dst + (size_t)r * p.dst_pitch, j, px);
 }
 
+// vp_frame's rectification passes (kernels.hpp FrameRemapParams): a gather through a map of 1/32-pixel source coordinates plus one integer blend per
+// channel, the blocks and the store of frame_to_bgr8_kernel.  The four weights sum to 1024, so (sum + 512) >> 10 stays inside 0 .. 255: no clamp.  Each
+// channel's value is held in a register of its own before the pixel is packed (see chroma_of below for what a packed shift once did on the device).
+__device__ __forceinline__ unsigned own_register(unsigned v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ unsigned remap_pixel(const FrameRemapParams& p, int X, int Y) {
+  const int ix = X >> 5, iy = Y >> 5, fx = X & 31, fy = Y & 31;
+  const int x0 = min(max(ix, 0), p.src_w - 1), x1 = min(max(ix + 1, 0), p.src_w - 1);
+  const int y0 = min(max(iy, 0), p.src_h - 1), y1 = min(max(iy + 1, 0), p.src_h - 1);
+  int wx0 = 32 - fx, wx1 = fx, wy0 = 32 - fy, wy1 = fy;
+  if (p.border == 0) {   // CONSTANT: a tap the clamp moved lies outside the source and counts as 0
+    wx0 = x0 == ix ? wx0 : 0;
+    wx1 = x1 == ix + 1 ? wx1 : 0;
+    wy0 = y0 == iy ? wy0 : 0;
+    wy1 = y1 == iy + 1 ? wy1 : 0;
+  }
+  const unsigned w00 = (unsigned)(wx0 * wy0), w01 = (unsigned)(wx1 * wy0), w10 = (unsigned)(wx0 * wy1), w11 = (unsigned)(wx1 * wy1);
+  const uint8_t* r0 = p.src + (size_t)y0 * p.src_pitch;
+  const uint8_t* r1 = p.src + (size_t)y1 * p.src_pitch;
+  const uint8_t *a = r0 + 3 * x0, *b = r0 + 3 * x1, *c = r1 + 3 * x0, *d = r1 + 3 * x1;
+  const unsigned c0 = (w00 * a[0] + w01 * b[0] + w10 * c[0] + w11 * d[0] + 512u) >> 10;
+  const unsigned c1 = own_register((w00 * a[1] + w01 * b[1] + w10 * c[1] + w11 * d[1] + 512u) >> 10);
+  const unsigned c2 = own_register((w00 * a[2] + w01 * b[2] + w10 * c[2] + w11 * d[2] + 512u) >> 10);
+  return c0 | (c1 << 8) | (c2 << 16);
+}
+__global__ __launch_bounds__(256) void frame_remap_kernel(const FrameRemapParams p) {
+  const int j = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (j >= (p.out_w + 3) >> 2) return;
+  const int4* m = reinterpret_cast<const int4*>(p.map + (size_t)y * p.map_pitch + 4 * (size_t)j);
+  const int4 m01 = m[0], m23 = m[1];
+  const int X[4] = {m01.x, m01.z, m23.x, m23.z}, Y[4] = {m01.y, m01.w, m23.y, m23.w};
+  unsigned px[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (4 * j + k >= p.out_w) break;
+    px[k] = remap_pixel(p, X[k], Y[k]);
+  }
+  store_bgr4(p.dst + (size_t)y * p.dst_pitch, j, px);
+}
+
 // Pillow's 8-bit resample passes (kernels.hpp PilResampleParams): int32 accumulation from 1 << 21 of u8 x 22-bit coefficients,
 // `>> 22`, clip to u8 (Resample.c clip8) -- integer work, bit-exact by construction.
 __device__ __forceinline__ int pil_clip8(int acc) { return min(max(acc >> 22, 0), 255); }
@@ -907,6 +949,13 @@ hipError_t launch_frame_to_bgr8(const FrameToBgrParams& q, hipStream_t st) {
   }
   const long long n = (long long)(f420 ? p.h / 2 : p.h) * ((p.w + 3) / 4);
   VP_LAUNCH(frame_to_bgr8_kernel, dim3(nblk(n)), dim3(256), 0, st, p);
+}
+hipError_t launch_frame_remap(const FrameRemapParams& p, hipStream_t st) {
+  if (!p.src || !p.map || !p.dst || p.src_h < 1 || p.src_w < 1 || p.src_h > 32768 || p.src_w > 32768 || p.src_pitch < 3 * p.src_w || p.out_h < 1 || p.out_w < 1 ||
+      p.out_h > 16384 || p.out_w > 16384 || p.map_pitch < frame_remap_map_pitch(p.out_w) || (p.map_pitch & 3) || (reinterpret_cast<uintptr_t>(p.map) & 15) ||
+      (p.border != 0 && p.border != 1) || p.dst_pitch < frame_bgr_pitch(p.out_w) || (p.dst_pitch & 3) || (reinterpret_cast<uintptr_t>(p.dst) & 3))
+    return hipErrorInvalidValue;
+  VP_LAUNCH(frame_remap_kernel, dim3(nblk((p.out_w + 3) / 4), p.out_h), dim3(256), 0, st, p);
 }
 hipError_t launch_pil_resample(const PilResampleParams& p, hipStream_t st) {
   hipLaunchKernelGGL(pil_resample_h_kernel, dim3(nblk(p.out_w), p.in_h), dim3(256), 0, st, p);

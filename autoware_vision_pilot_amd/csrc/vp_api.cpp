@@ -1,5 +1,6 @@
 // C ABI of libvp_hip.so (declarations + reference citations: include/vp_hip.h).  No exception crosses it.
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -486,6 +487,8 @@ vp_frame::~vp_frame() {
     if (ev) (void)hipEventDestroy(ev);
   if (d_bgr) (void)hipFree(d_bgr);
   if (d_src) (void)hipFree(d_src);
+  for (void* p : {(void*)d_raw, (void*)d_mid, (void*)d_map[0], (void*)d_map[1]})
+    if (p) (void)hipFree(p);
   if (h_stage) (void)hipHostFree(h_stage);
   if (stream) (void)hipStreamDestroy(stream);
 }
@@ -608,14 +611,184 @@ void grow(T*& p, size_t& cap, size_t need, bool pinned) {
   cap = n;
 }
 
+// ---- rectification maps: host code, the formulas of include/vp_hip.h in IEEE double in the order written.  `#pragma clang fp contract(off)` keeps the
+// compiler from contracting a multiply and an add into one fused operation, whatever the build's flags say: the numpy restatement of the tests rounds
+// after every operation, and the maps are compared bit for bit.
+int coord32(double v) {   // rne (the default rounding mode), then the clamp; a NaN takes the lower clamp
+  v = std::nearbyint(v);
+  if (!(v >= -1048576.0)) return -1048576;
+  return v > 1048575.0 ? 1048575 : (int)v;
+}
+void distort_point(const vp_rectify& r, double x, double y, double* u, double* v) {
+#pragma clang fp contract(off)
+  const double k1 = r.dist[0], k2 = r.dist[1], p1 = r.dist[2], p2 = r.dist[3], k3 = r.dist[4];
+  const double r2 = x * x + y * y;
+  const double kr = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2;
+  const double xy2 = 2.0 * (x * y);
+  const double xd = x * kr + p1 * xy2 + p2 * (r2 + 2.0 * (x * x));
+  const double yd = y * kr + p1 * (r2 + 2.0 * (y * y)) + p2 * xy2;
+  *u = r.K[0] * xd + r.K[2];
+  *v = r.K[4] * yd + r.K[5];
+}
+double homography_adjugate(const double* H, double* a) {   // the nine cofactors; returns det H
+#pragma clang fp contract(off)
+  a[0] = H[4] * H[8] - H[5] * H[7];
+  a[1] = H[2] * H[7] - H[1] * H[8];
+  a[2] = H[1] * H[5] - H[2] * H[4];
+  a[3] = H[5] * H[6] - H[3] * H[8];
+  a[4] = H[0] * H[8] - H[2] * H[6];
+  a[5] = H[2] * H[3] - H[0] * H[5];
+  a[6] = H[3] * H[7] - H[4] * H[6];
+  a[7] = H[1] * H[6] - H[0] * H[7];
+  a[8] = H[0] * H[4] - H[1] * H[3];
+  return (H[0] * a[0] + H[1] * a[3]) + H[2] * a[6];
+}
+bool rectify_h_is_identity(const vp_rectify& r) {
+  for (int i = 0; i < 9; ++i)
+    if (r.H[i] != (i % 4 == 0 ? 1.0 : 0.0)) return false;
+  return true;
+}
+bool rectify_dist_is_zero(const vp_rectify& r) {
+  for (double d : r.dist)
+    if (d != 0.0) return false;
+  return true;
+}
+void check_rectify(const std::string& me, const vp_rectify& r) {
+  for (double v : r.K)
+    if (!std::isfinite(v)) throw std::invalid_argument(me + ": K holds a non-finite value");
+  for (double v : r.dist)
+    if (!std::isfinite(v)) throw std::invalid_argument(me + ": dist holds a non-finite value");
+  for (double v : r.H)
+    if (!std::isfinite(v)) throw std::invalid_argument(me + ": H holds a non-finite value");
+  if (r.K[0] == 0.0 || r.K[4] == 0.0) throw std::invalid_argument(me + ": fx and fy of K must not be 0");
+  if (r.K[1] != 0.0 || r.K[3] != 0.0 || r.K[6] != 0.0 || r.K[7] != 0.0 || r.K[8] != 1.0)
+    throw std::invalid_argument(me + ": K must be [fx 0 cx; 0 fy cy; 0 0 1] (no skew)");
+  double a[9];
+  const double det = homography_adjugate(r.H, a);
+  if (det == 0.0 || !std::isfinite(det)) throw std::invalid_argument(me + ": det H is 0 or not finite: H has no inverse");
+  if (r.out_w < 2 || r.out_h < 2 || r.out_w > 16384 || r.out_h > 16384)
+    throw std::invalid_argument(me + ": output size " + std::to_string(r.out_w) + " x " + std::to_string(r.out_h) + " (2 .. 16384 each way)");
+  if (r.mode != VP_RECTIFY_TWO_PASS && r.mode != VP_RECTIFY_ONE_PASS)
+    throw std::invalid_argument(me + ": unknown mode " + std::to_string(r.mode) + " (VP_RECTIFY_TWO_PASS, VP_RECTIFY_ONE_PASS)");
+}
+void check_rectify_source(const std::string& me, int src_h, int src_w) {
+  if (src_h < 2 || src_w < 2 || src_h > 16384 || src_w > 16384)
+    throw std::invalid_argument(me + ": source size " + std::to_string(src_w) + " x " + std::to_string(src_h) + " (2 .. 16384 each way)");
+}
+// which: 0 undistort (src_h x src_w), 1 warp, 2 one-pass (both out_h x out_w); rows `pitch` entries apart
+void build_rectify_map(const vp_rectify& r, int src_h, int src_w, int which, vp::RemapEntry* out, int pitch) {
+#pragma clang fp contract(off)
+  const double fx = r.K[0], fy = r.K[4], cx = r.K[2], cy = r.K[5];
+  if (which == 0) {
+    for (int i = 0; i < src_h; ++i)
+      for (int j = 0; j < src_w; ++j) {
+        double u, v;
+        distort_point(r, ((double)j - cx) / fx, ((double)i - cy) / fy, &u, &v);
+        out[(size_t)i * pitch + j] = {coord32(32.0 * u), coord32(32.0 * v)};
+      }
+    return;
+  }
+  double M[9];
+  const double det = homography_adjugate(r.H, M);
+  for (double& m : M) m = m / det;
+  for (int yi = 0; yi < r.out_h; ++yi)
+    for (int xi = 0; xi < r.out_w; ++xi) {
+      const double x = (double)xi, y = (double)yi;
+      const double X0 = (M[0] * x + M[1] * y) + M[2], Y0 = (M[3] * x + M[4] * y) + M[5], W = (M[6] * x + M[7] * y) + M[8];
+      vp::RemapEntry& e = out[(size_t)yi * pitch + xi];
+      if (which == 1) {
+        const double s = W != 0.0 ? 32.0 / W : 0.0;
+        const double lim = 2147483648.0;
+        const double xs = X0 * s, ys = Y0 * s;
+        e = {coord32(xs < -lim ? -lim : (xs > lim ? lim : xs)), coord32(ys < -lim ? -lim : (ys > lim ? lim : ys))};
+      } else {
+        double px = W != 0.0 ? X0 / W : 0.0, py = W != 0.0 ? Y0 / W : 0.0;
+        px = px >= 0.0 ? (px > (double)(src_w - 1) ? (double)(src_w - 1) : px) : 0.0;   // a NaN takes 0
+        py = py >= 0.0 ? (py > (double)(src_h - 1) ? (double)(src_h - 1) : py) : 0.0;
+        double u, v;
+        distort_point(r, (px - cx) / fx, (py - cy) / fy, &u, &v);
+        e = {coord32(32.0 * u), coord32(32.0 * v)};
+      }
+    }
+}
+
+// what an upload of an h x w frame does under the frame's rectification setting: the passes that run and the picture's geometry
+struct RectifyPlan {
+  bool on = false;
+  bool pass[2] = {false, false};   // [0]: undistort, or the one-pass map (border CONSTANT); [1]: warp (border REPLICATE)
+  int out_h = 0, out_w = 0;
+};
+RectifyPlan rectify_plan(const vp_frame* f, int h, int w) {
+  RectifyPlan p;
+  p.out_h = h;
+  p.out_w = w;
+  if (!f->rect_on) return p;
+  const vp_rectify& r = f->rect;
+  p.out_h = r.out_h;
+  p.out_w = r.out_w;
+  if (r.mode == VP_RECTIFY_ONE_PASS) {
+    p.pass[0] = true;
+  } else {
+    p.pass[0] = !rectify_dist_is_zero(r);
+    p.pass[1] = !(rectify_h_is_identity(r) && r.out_h == h && r.out_w == w);
+  }
+  p.on = p.pass[0] || p.pass[1];
+  return p;
+}
+// where the format conversion (or the BGR8 copy) of the upload in flight writes: the picture itself, or the raw-sized buffer ahead of the passes
+uint8_t* conversion_target(const vp_frame* f, int h, int w) { return rectify_plan(f, h, w).on ? f->d_raw : f->d_bgr; }
+
+// the maps of the frame's setting for an h x w source, on the device: one host computation (and one host wait) per geometry and setting
+void ensure_rectify_maps(vp_frame* f, const RectifyPlan& p, int h, int w) {
+  if (f->map_h == h && f->map_w == w) return;
+  VP_HIP_CHECK(hipStreamSynchronize(f->stream));   // a pass queued earlier may still read the maps
+  f->map_h = f->map_w = 0;
+  const bool one = f->rect.mode == VP_RECTIFY_ONE_PASS;
+  std::vector<vp::RemapEntry> host;
+  for (int i = 0; i < 2; ++i) {
+    if (!p.pass[i]) continue;
+    const int mh = (i == 0 && !one) ? h : p.out_h, mw = (i == 0 && !one) ? w : p.out_w, pitch = vp::frame_remap_map_pitch(mw);
+    host.assign((size_t)mh * pitch, vp::RemapEntry{0, 0});
+    build_rectify_map(f->rect, h, w, i == 0 ? (one ? 2 : 0) : 1, host.data(), pitch);
+    grow(f->d_map[i], f->map_cap[i], host.size() * sizeof(vp::RemapEntry), false);
+    VP_HIP_CHECK(hipMemcpyAsync(f->d_map[i], host.data(), host.size() * sizeof(vp::RemapEntry), hipMemcpyHostToDevice, f->stream));
+    VP_HIP_CHECK(hipStreamSynchronize(f->stream));   // `host` is pageable and about to be reused
+  }
+  f->map_h = h;
+  f->map_w = w;
+}
+
+void remap_pass(vp_frame* f, const uint8_t* src, int src_h, int src_w, int which, int border, uint8_t* dst, int out_h, int out_w) {
+  vp::FrameRemapParams q{};
+  q.src = src;
+  q.src_pitch = vp::frame_bgr_pitch(src_w);
+  q.src_h = src_h;
+  q.src_w = src_w;
+  q.map = f->d_map[which];
+  q.map_pitch = vp::frame_remap_map_pitch(out_w);
+  q.border = border;
+  q.dst = dst;
+  q.dst_pitch = vp::frame_bgr_pitch(out_w);
+  q.out_h = out_h;
+  q.out_w = out_w;
+  VP_HIP_CHECK(vp::launch_frame_remap(q, f->stream));
+}
+
 // ahead of every upload: the image is about to be overwritten, so the frame's stream falls in behind every consumer copy queued so far; a buffer that
-// has to grow is freed only once those copies and the frame's own work have run (the one host wait of this path, once per geometry)
+// has to grow is freed only once those copies and the frame's own work have run (the one host wait of this path, once per geometry).  With
+// rectification on, the picture buffer is sized by the setting's output, the raw-sized buffers by (h, w), and the maps are built here (once per
+// geometry and setting, ensure_rectify_maps).
 void begin_upload(vp_frame* f, int h, int w, size_t src_bytes, size_t stage_bytes) {
   f->wait_for_consumers();
-  const int pitch = vp::frame_bgr_pitch(w);
-  if ((size_t)h * pitch > f->bgr_cap || src_bytes > f->src_cap || stage_bytes > f->stage_cap) {
+  const RectifyPlan plan = rectify_plan(f, h, w);
+  const size_t bgr_bytes = (size_t)plan.out_h * vp::frame_bgr_pitch(plan.out_w);
+  const size_t raw_bytes = plan.on ? (size_t)h * vp::frame_bgr_pitch(w) : 0, mid_bytes = plan.pass[0] && plan.pass[1] ? raw_bytes : 0;
+  if (plan.on) ensure_rectify_maps(f, plan, h, w);
+  if (bgr_bytes > f->bgr_cap || raw_bytes > f->raw_cap || mid_bytes > f->mid_cap || src_bytes > f->src_cap || stage_bytes > f->stage_cap) {
     VP_HIP_CHECK(hipStreamSynchronize(f->stream));
-    grow(f->d_bgr, f->bgr_cap, (size_t)h * pitch, false);
+    grow(f->d_bgr, f->bgr_cap, bgr_bytes, false);
+    grow(f->d_raw, f->raw_cap, raw_bytes, false);
+    grow(f->d_mid, f->mid_cap, mid_bytes, false);
     grow(f->d_src, f->src_cap, src_bytes, false);
     if (stage_bytes > f->stage_cap) {
       if (f->h_stage) (void)hipHostFree(f->h_stage);
@@ -628,11 +801,21 @@ void begin_upload(vp_frame* f, int h, int w, size_t src_bytes, size_t stage_byte
   }
 }
 
+// behind the conversion of an h x w frame: the rectification passes, if any, on the frame's stream; then "content ready"
 void end_upload(vp_frame* f, int h, int w) {
+  const RectifyPlan plan = rectify_plan(f, h, w);
+  if (plan.pass[0] && plan.pass[1]) {
+    remap_pass(f, f->d_raw, h, w, 0, VP_BORDER_CONSTANT, f->d_mid, h, w);
+    remap_pass(f, f->d_mid, h, w, 1, VP_BORDER_REPLICATE, f->d_bgr, plan.out_h, plan.out_w);
+  } else if (plan.pass[0]) {
+    remap_pass(f, f->d_raw, h, w, 0, VP_BORDER_CONSTANT, f->d_bgr, plan.out_h, plan.out_w);
+  } else if (plan.pass[1]) {
+    remap_pass(f, f->d_raw, h, w, 1, VP_BORDER_REPLICATE, f->d_bgr, plan.out_h, plan.out_w);
+  }
   VP_HIP_CHECK(hipEventRecord(f->ready, f->stream));
-  f->h = h;
-  f->w = w;
-  f->pitch = vp::frame_bgr_pitch(w);
+  f->h = plan.out_h;
+  f->w = plan.out_w;
+  f->pitch = vp::frame_bgr_pitch(plan.out_w);
   f->uploaded = true;
 }
 
@@ -648,7 +831,7 @@ void convert_planes(vp_frame* f, int format, const uint8_t* const* p, const int*
   q.h = h;
   q.w = w;
   q.format = format;
-  q.dst = f->d_bgr;
+  q.dst = conversion_target(f, h, w);
   q.dst_pitch = vp::frame_bgr_pitch(w);
   q.k = vp::color_standard(f->color_matrix, f->color_range).inv;
   VP_HIP_CHECK(vp::launch_frame_to_bgr8(q, f->stream));
@@ -699,10 +882,11 @@ int vp_frame_upload(vp_frame* f, int format, const uint8_t* const* planes, const
     const bool bgr = format == VP_FRAME_BGR8;
     begin_upload(f, h, w, bgr ? 0 : total, registered ? 0 : total);
     const int pitch = vp::frame_bgr_pitch(w);
+    uint8_t* const image = conversion_target(f, h, w);   // the picture, or the raw-sized buffer ahead of the rectification passes
     if (registered) {
       size_t off = 0;
       for (int i = 0; i < fp.n; ++i) {
-        uint8_t* dst = bgr ? f->d_bgr : f->d_src + off;
+        uint8_t* dst = bgr ? image : f->d_src + off;
         VP_HIP_CHECK(hipMemcpy2DAsync(dst, bgr ? (size_t)pitch : fp.row_bytes[i], planes[i], strides[i], fp.row_bytes[i], fp.rows[i], hipMemcpyHostToDevice, f->stream));
         off += fp.row_bytes[i] * fp.rows[i];
       }
@@ -714,7 +898,7 @@ int vp_frame_upload(vp_frame* f, int format, const uint8_t* const* planes, const
       uint8_t* o = slot;
       for (int i = 0; i < fp.n; ++i)
         for (int y = 0; y < fp.rows[i]; ++y, o += fp.row_bytes[i]) std::memcpy(o, planes[i] + (size_t)y * strides[i], fp.row_bytes[i]);
-      if (bgr) VP_HIP_CHECK(hipMemcpy2DAsync(f->d_bgr, pitch, slot, fp.row_bytes[0], fp.row_bytes[0], h, hipMemcpyHostToDevice, f->stream));
+      if (bgr) VP_HIP_CHECK(hipMemcpy2DAsync(image, pitch, slot, fp.row_bytes[0], fp.row_bytes[0], h, hipMemcpyHostToDevice, f->stream));
       else VP_HIP_CHECK(hipMemcpyAsync(f->d_src, slot, total, hipMemcpyHostToDevice, f->stream));
       VP_HIP_CHECK(hipEventRecord(f->stage_ev[f->stage_slot], f->stream));
     }
@@ -740,7 +924,7 @@ int vp_frame_upload_device(vp_frame* f, int format, const void* const* dev_plane
       VP_HIP_CHECK(hipStreamWaitEvent(f->stream, f->producer, 0));
     }
     if (format == VP_FRAME_BGR8)
-      VP_HIP_CHECK(hipMemcpy2DAsync(f->d_bgr, vp::frame_bgr_pitch(w), dev_planes[0], strides[0], fp.row_bytes[0], h, hipMemcpyDeviceToDevice, f->stream));
+      VP_HIP_CHECK(hipMemcpy2DAsync(conversion_target(f, h, w), vp::frame_bgr_pitch(w), dev_planes[0], strides[0], fp.row_bytes[0], h, hipMemcpyDeviceToDevice, f->stream));
     else
       convert_planes(f, format, reinterpret_cast<const uint8_t* const*>(dev_planes), strides, fp.n, h, w);
     end_upload(f, h, w);
@@ -759,6 +943,84 @@ int vp_frame_get_color(const vp_frame* f, int* matrix, int* range) {
   if (!f || !matrix || !range) return VP_ERR_ARG;
   *matrix = f->color_matrix;
   *range = f->color_range;
+  return VP_OK;
+}
+
+int vp_frame_set_rectify(vp_frame* f, const vp_rectify* r) {
+  return frame_guarded(f, [&] {
+    if (r) check_rectify("vp_frame_set_rectify", *r);
+    f->rect_on = r != nullptr;
+    if (r) f->rect = *r;
+    f->map_h = f->map_w = 0;   // the next upload builds the maps of the new setting
+  });
+}
+
+int vp_frame_get_rectify(const vp_frame* f, vp_rectify* out) {
+  if (!f || !out) return VP_ERR_ARG;
+  if (!f->rect_on) return VP_ERR_STATE;
+  *out = f->rect;
+  return VP_OK;
+}
+
+int vp_rectify_map(const vp_rectify* r, int src_h, int src_w, int which, int16_t* xy, uint16_t* frac) {
+  try {
+    if (!r || !xy || !frac || which < 0 || which > 2) return VP_ERR_ARG;
+    check_rectify("vp_rectify_map", *r);
+    check_rectify_source("vp_rectify_map", src_h, src_w);
+    const int mh = which == 0 ? src_h : r->out_h, mw = which == 0 ? src_w : r->out_w;
+    std::vector<vp::RemapEntry> m((size_t)mh * mw);
+    build_rectify_map(*r, src_h, src_w, which, m.data(), mw);
+    for (size_t i = 0; i < m.size(); ++i) {
+      xy[2 * i] = (int16_t)(m[i].x >> 5);
+      xy[2 * i + 1] = (int16_t)(m[i].y >> 5);
+      frac[i] = (uint16_t)(((m[i].y & 31) << 5) | (m[i].x & 31));
+    }
+    return VP_OK;
+  } catch (const std::invalid_argument&) {
+    return VP_ERR_ARG;
+  } catch (...) {
+    return VP_ERR_STATE;
+  }
+}
+
+int vp_rectify_homography(const vp_camera_pose* inference, const vp_camera_pose* standard, double H_out[9]) {
+  if (!inference || !standard || !H_out) return VP_ERR_ARG;
+  const vp_camera_pose &pi = *inference, &ps = *standard;
+  for (double v : {pi.pitch_deg, pi.yaw_deg, pi.roll_deg, pi.camera_height, ps.pitch_deg, ps.yaw_deg, ps.roll_deg, ps.camera_height, ps.hfov_deg})
+    if (!std::isfinite(v)) return VP_ERR_ARG;
+  for (double v : pi.K)
+    if (!std::isfinite(v)) return VP_ERR_ARG;
+  const double* K = pi.K;
+  if (K[0] == 0.0 || K[4] == 0.0 || K[1] != 0.0 || K[3] != 0.0 || K[6] != 0.0 || K[7] != 0.0 || K[8] != 1.0) return VP_ERR_ARG;
+  if (pi.camera_height == 0.0 || ps.img_w < 1 || ps.img_h < 1 || !(ps.hfov_deg > 0.0 && ps.hfov_deg < 180.0)) return VP_ERR_ARG;
+  const double rad = 3.14159265358979323846 / 180.0;
+  auto rodrigues = [&](const vp_camera_pose& p, double* R) {   // cos I + (1 - cos) k k^T + sin [k]x of the vector (pitch, yaw, roll)
+    const double v[3] = {p.pitch_deg * rad, p.yaw_deg * rad, p.roll_deg * rad};
+    const double th = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    for (int i = 0; i < 9; ++i) R[i] = i % 4 == 0 ? 1.0 : 0.0;
+    if (th == 0.0) return;
+    const double k[3] = {v[0] / th, v[1] / th, v[2] / th}, c = std::cos(th), s = std::sin(th);
+    const double kx[9] = {0.0, -k[2], k[1], k[2], 0.0, -k[0], -k[1], k[0], 0.0};
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) R[3 * i + j] = c * (i == j ? 1.0 : 0.0) + (1.0 - c) * k[i] * k[j] + s * kx[3 * i + j];
+  };
+  auto mul = [](const double* A, const double* B, double* Cm) {
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) Cm[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
+  };
+  double Rs[9], Ri[9], RiT[9], Rrel[9], T[9];
+  rodrigues(ps, Rs);
+  rodrigues(pi, Ri);
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) RiT[3 * i + j] = Ri[3 * j + i];
+  mul(Rs, RiT, Rrel);
+  const double fs = (ps.img_w / 2.0) / std::tan(ps.hfov_deg * rad / 2.0);
+  const double Ks[9] = {fs, 0.0, ps.img_w / 2.0, 0.0, fs * (ps.camera_height / pi.camera_height), ps.img_h / 2.0, 0.0, 0.0, 1.0};
+  const double Kinv[9] = {1.0 / K[0], 0.0, -K[2] / K[0], 0.0, 1.0 / K[4], -K[5] / K[4], 0.0, 0.0, 1.0};
+  mul(Ks, Rrel, T);
+  mul(T, Kinv, H_out);
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(H_out[i])) return VP_ERR_ARG;
   return VP_OK;
 }
 
@@ -1672,6 +1934,50 @@ int vp_compose_upconv(int gpu_id, const float* wt, const float* bt, const float*
     std::memcpy(wx, c.wx.data(), c.wx.size() * sizeof(double));
     if (cs > 0) std::memcpy(wsk, c.ws.data(), c.ws.size() * sizeof(double));
     std::memcpy(bias, c.bias.data(), c.bias.size() * sizeof(double));
+  });
+}
+
+// ---- vp_frame's rectification kernel on a host picture through any map (unit tests)
+int vp_op_remap_bgr8(int gpu_id, const uint8_t* src, int src_h, int src_w, int src_stride, const int16_t* xy, const uint16_t* frac, int out_h, int out_w,
+                     int border, uint8_t* dst, int dst_stride, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!src || !xy || !frac || !dst || src_h < 1 || src_w < 1 || src_h > 16384 || src_w > 16384 || out_h < 1 || out_w < 1 || out_h > 16384 || out_w > 16384 ||
+        src_stride < 3 * src_w || dst_stride < 3 * out_w || (border != VP_BORDER_CONSTANT && border != VP_BORDER_REPLICATE))
+      throw std::invalid_argument("vp_op_remap_bgr8: bad argument (sizes 1 .. 16384, strides of at least 3 * width, border VP_BORDER_CONSTANT / VP_BORDER_REPLICATE)");
+    const size_t n = (size_t)out_h * out_w;
+    const int mp = vp::frame_remap_map_pitch(out_w);
+    std::vector<vp::RemapEntry> m((size_t)out_h * mp, vp::RemapEntry{0, 0});
+    for (size_t i = 0; i < n; ++i) {
+      if (frac[i] >= 1024) throw std::invalid_argument("vp_op_remap_bgr8: frac = fy << 5 | fx with fx, fy below 32");
+      m[(i / out_w) * mp + i % out_w] = {(int)xy[2 * i] * 32 + (frac[i] & 31), (int)xy[2 * i + 1] * 32 + (frac[i] >> 5)};
+    }
+    vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
+    const size_t src_bytes = (size_t)(src_h - 1) * src_stride + (size_t)3 * src_w;
+    const int pitch = vp::frame_bgr_pitch(out_w);
+    const size_t dst_bytes = (size_t)out_h * pitch;
+    uint8_t* d_src = reinterpret_cast<uint8_t*>(g.alloc_f32((src_bytes + 3) / 4));
+    vp::RemapEntry* d_map = reinterpret_cast<vp::RemapEntry*>(g.alloc_f32(2 * m.size()));
+    uint8_t* d_dst = reinterpret_cast<uint8_t*>(g.alloc_f32(dst_bytes / 4));
+    g.copy_h2d(d_src, src, src_bytes);
+    g.copy_h2d(d_map, m.data(), m.size() * sizeof(vp::RemapEntry));
+    VP_HIP_CHECK(hipMemsetAsync(d_dst, 0xFF, dst_bytes, g.stream()));
+    vp::FrameRemapParams q{};
+    q.src = d_src;
+    q.src_pitch = src_stride;
+    q.src_h = src_h;
+    q.src_w = src_w;
+    q.map = d_map;
+    q.map_pitch = mp;
+    q.border = border;
+    q.dst = d_dst;
+    q.dst_pitch = pitch;
+    q.out_h = out_h;
+    q.out_w = out_w;
+    VP_HIP_CHECK(vp::launch_frame_remap(q, g.stream()));
+    std::vector<uint8_t> back(dst_bytes);
+    g.copy_d2h(back.data(), d_dst, dst_bytes);
+    const size_t row = (size_t)(dst_stride >= pitch ? pitch : 3 * out_w);
+    for (int y = 0; y < out_h; ++y) std::memcpy(dst + (size_t)y * dst_stride, back.data() + (size_t)y * pitch, row);
   });
 }
 

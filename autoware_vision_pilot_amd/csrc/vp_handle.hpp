@@ -34,6 +34,18 @@ struct vp_frame {
   int h = 0, w = 0, pitch = 0;
   bool uploaded = false;
   int color_matrix = 0, color_range = 0;   // vp_frame_set_color: the standard of later YUV uploads (BT.601, limited range)
+  // vp_frame_set_rectify: later uploads convert into d_raw (the camera's geometry) and are resampled into d_bgr (the standard pose's) on the frame's
+  // stream, ahead of `ready`.  Maps: built on the host once per (raw geometry, setting), kept on the device; d_map[0] undistort or the one-pass map,
+  // d_map[1] the warp (an identity pass has no map and is skipped).
+  bool rect_on = false;
+  vp_rectify rect{};
+  uint8_t* d_raw = nullptr;      // [raw h][frame_bgr_pitch(raw w)]: what the conversion writes while rectification is on
+  size_t raw_cap = 0;
+  uint8_t* d_mid = nullptr;      // the undistorted picture between the two passes, raw geometry
+  size_t mid_cap = 0;
+  vp::RemapEntry* d_map[2] = {nullptr, nullptr};
+  size_t map_cap[2] = {0, 0};
+  int map_h = 0, map_w = 0;      // the raw geometry the maps were built for; 0: none (the setting changed)
   hipEvent_t ready = nullptr;     // content complete
   hipEvent_t producer = nullptr;  // vp_frame_upload_device: recorded on the caller's producer stream
   struct Consumer {

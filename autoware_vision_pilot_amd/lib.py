@@ -162,6 +162,11 @@ _SIGS = {
     "vp_frame_sync": (C.c_int, [_P]),
     "vp_frame_dims": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vp_frame_fetch_bgr8": (C.c_int, [_P, _P, C.c_int]),
+    "vp_frame_set_rectify": (C.c_int, [_P, _P]),
+    "vp_frame_get_rectify": (C.c_int, [_P, _P]),
+    "vp_rectify_map": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "vp_rectify_homography": (C.c_int, [_P, _P, _P]),
+    "vp_op_remap_bgr8": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_char_p, C.c_size_t]),
     "vp_upload_from_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vp_infer_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vp_detect_infer_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
@@ -220,6 +225,11 @@ VP_CHROMA_EVEN, VP_CHROMA_MEAN = 0, 1
 COLOR_MATRICES = {"bt601": VP_COLOR_BT601, "bt709": VP_COLOR_BT709}
 COLOR_RANGES = {"limited": VP_COLOR_RANGE_LIMITED, "full": VP_COLOR_RANGE_FULL}
 CHROMA_MODES = {"even": VP_CHROMA_EVEN, "mean": VP_CHROMA_MEAN}
+VP_RECTIFY_TWO_PASS, VP_RECTIFY_ONE_PASS = 0, 1
+VP_BORDER_CONSTANT, VP_BORDER_REPLICATE = 0, 1
+RECTIFY_MODES = {"two_pass": VP_RECTIFY_TWO_PASS, "one_pass": VP_RECTIFY_ONE_PASS}
+RECTIFY_MAPS = {"undistort": 0, "warp": 1, "one_pass": 2}
+BORDERS = {"constant": VP_BORDER_CONSTANT, "replicate": VP_BORDER_REPLICATE}
 
 
 def _named(table, v):
@@ -230,6 +240,27 @@ class RangeStats(C.Structure):
     """vp_range_stats (include/vp_hip.h)"""
     _fields_ = [("absmax", C.c_float), ("exp", C.c_int), ("count", C.c_ulonglong), ("nonfinite", C.c_ulonglong), ("zeros", C.c_ulonglong),
                 ("bins", C.c_ulonglong * VP_RANGE_BINS)]
+
+
+class Rectify(C.Structure):
+    """vp_rectify (include/vp_hip.h)"""
+    _fields_ = [("K", C.c_double * 9), ("dist", C.c_double * 5), ("H", C.c_double * 9), ("out_w", C.c_int), ("out_h", C.c_int), ("mode", C.c_int)]
+
+
+class CameraPose(C.Structure):
+    """vp_camera_pose (include/vp_hip.h)"""
+    _fields_ = [("pitch_deg", C.c_double), ("yaw_deg", C.c_double), ("roll_deg", C.c_double), ("camera_height", C.c_double), ("K", C.c_double * 9),
+                ("img_w", C.c_int), ("img_h", C.c_int), ("hfov_deg", C.c_double)]
+
+
+def _rectify(K, dist, H, out_hw, mode):
+    r = Rectify()
+    r.K[:] = [float(v) for v in np.asarray(K, dtype=np.float64).reshape(9)]
+    r.dist[:] = [float(v) for v in np.asarray(dist, dtype=np.float64).reshape(5)]
+    r.H[:] = [float(v) for v in np.asarray(H, dtype=np.float64).reshape(9)]
+    r.out_h, r.out_w = int(out_hw[0]), int(out_hw[1])
+    r.mode = _named(RECTIFY_MODES, mode)
+    return r
 
 
 _lib = None
@@ -816,6 +847,25 @@ class Frame:
         self._ck(self._lib.vp_frame_get_color(self._h, C.byref(m), C.byref(r)))
         return m.value, r.value
 
+    def set_rectify(self, K, dist=None, H=None, out_hw=None, mode="two_pass"):
+        """vp_frame_set_rectify: LATER uploads are undistorted (K 3x3, dist = (k1, k2, p1, p2, k3)) and warped by the homography H (source -> destination,
+        3x3) to out_hw = (h, w) on the device; the frame then IS that picture (hw(), fetch_bgr8(), every consumer, Canvas.begin).  mode "two_pass" (the
+        calibration protocol's pipeline) or "one_pass" (one resampling, not bit-equal).  K = None switches rectification off."""
+        if K is None:
+            self._ck(self._lib.vp_frame_set_rectify(self._h, None))
+            return
+        r = _rectify(K, dist, H, out_hw, mode)
+        self._ck(self._lib.vp_frame_set_rectify(self._h, C.byref(r)))
+
+    def get_rectify(self):
+        """the setting in force as a dict (K, dist, H, out_hw, mode), None when rectification is off"""
+        r = Rectify()
+        rc = self._lib.vp_frame_get_rectify(self._h, C.byref(r))
+        if rc == -4:
+            return None
+        self._ck(rc)
+        return {"K": np.array(r.K[:]).reshape(3, 3), "dist": np.array(r.dist[:]), "H": np.array(r.H[:]).reshape(3, 3), "out_hw": (r.out_h, r.out_w), "mode": r.mode}
+
     def sync(self):
         self._ck(self._lib.vp_frame_sync(self._h))
 
@@ -832,6 +882,63 @@ class Frame:
         out = np.empty((h, w, 3), np.uint8)
         self._ck(self._lib.vp_frame_fetch_bgr8(self._h, _ptr(out), out.strides[0]))
         return out
+
+
+def rectify_map(K, dist, H, out_hw, src_hw, which, mode="two_pass"):
+    """vp_rectify_map (host only): the map "undistort" (0), "warp" (1) or "one_pass" (2) of the setting for a src_hw = (h, w) source ->
+    (xy int16 [rows][cols][2] = (ix, iy), frac uint16 [rows][cols] = fy << 5 | fx); rows x cols = src_hw for "undistort", out_hw otherwise.
+    ValueError for a setting or a size the library refuses."""
+    r = _rectify(K, dist, H, out_hw, mode)
+    which = _named(RECTIFY_MAPS, which)
+    rows, cols = (int(src_hw[0]), int(src_hw[1])) if which == 0 else (r.out_h, r.out_w)
+    ok = 2 <= rows <= 16384 and 2 <= cols <= 16384
+    xy = np.empty((rows, cols, 2) if ok else (1, 1, 2), np.int16)
+    frac = np.empty((rows, cols) if ok else (1, 1), np.uint16)
+    rc = load().vp_rectify_map(C.byref(r), int(src_hw[0]), int(src_hw[1]), which, _ptr(xy), _ptr(frac))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_rectify_map failed ({rc}): a setting, a source size or a map the library refuses")
+    return xy, frac
+
+
+def _camera_pose(d):
+    p = CameraPose()
+    p.pitch_deg, p.yaw_deg, p.roll_deg = float(d.get("pitch", 0.0)), float(d.get("yaw", 0.0)), float(d.get("roll", 0.0))
+    p.camera_height = float(d.get("camera_height", 0.0))
+    p.K[:] = [float(v) for v in np.asarray(d.get("intrinsic_matrix", np.eye(3)), dtype=np.float64).reshape(9)]
+    p.img_w, p.img_h = int(d.get("img_width", 0)), int(d.get("img_height", 0))
+    p.hfov_deg = float(d.get("hfov", 0.0))
+    return p
+
+
+def rectify_homography(inference_pose, standard_pose):
+    """vp_rectify_homography (host only): the two config dicts of the calibration demo -- inference: pitch, yaw, roll (degrees), camera_height,
+    intrinsic_matrix; standard: pitch, yaw, roll, camera_height, img_width, img_height, hfov (degrees) -> H 3x3 float64, source -> standard pose."""
+    pi, ps = _camera_pose(inference_pose), _camera_pose(standard_pose)
+    H = np.empty(9, np.float64)
+    rc = load().vp_rectify_homography(C.byref(pi), C.byref(ps), _ptr(H))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_rectify_homography failed ({rc}): a pose the library refuses")
+    return H.reshape(3, 3)
+
+
+def op_remap_bgr8(src, xy, frac, border="replicate", dst_stride=None, gpu_id=0):
+    """vp_op_remap_bgr8: frame_remap_kernel on src (uint8 [h][w][3]; a view with its own row stride is passed as it is) through the map (xy int16
+    [oh][ow][2], frac uint16 [oh][ow]).  dst_stride None: the picture [oh][ow][3]; else the raw destination rows [oh][dst_stride], where bytes the
+    entry does not write stay 0xAA."""
+    src = np.asarray(src)
+    if src.dtype != np.uint8 or src.ndim != 3 or src.shape[2] != 3 or src.strides[2] != 1 or src.strides[1] != 3 or src.strides[0] < 0:
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+    xy = np.ascontiguousarray(xy, dtype=np.int16)
+    frac = np.ascontiguousarray(frac, dtype=np.uint16)
+    oh, ow = frac.shape
+    stride = 3 * ow if dst_stride is None else int(dst_stride)
+    out = np.full((oh, max(stride, 1)), 0xAA, np.uint8)
+    err = C.create_string_buffer(512)
+    rc = load().vp_op_remap_bgr8(gpu_id, C.c_void_p(src.ctypes.data), src.shape[0], src.shape[1], int(src.strides[0]), _ptr(xy), _ptr(frac), oh, ow,
+                                 _named(BORDERS, border), _ptr(out), stride, err, len(err))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_op_remap_bgr8 failed ({rc}): {err.value.decode(errors='replace')}")
+    return out.reshape(oh, ow, 3) if dst_stride is None else out
 
 
 def canvas_layout(fmt, h, w):

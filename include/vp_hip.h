@@ -421,6 +421,76 @@ int vp_frame_fetch_bgr8(vp_frame* f, uint8_t* dst, int dst_stride);      /* the 
 int vp_upload_from_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h);
 int vp_infer_frame(vp_engine* e, vp_frame* f, int x0, int y0, int w, int h);
 
+/* ---- vp_frame rectification: undistort and warp to the standard camera pose, on the device ---------------------------------------
+ * The reference's Camera Calibration Protocol (VisionPilot/calibration/README.md, calibration.py, demo.py) puts every deployed camera's frame through
+ *     cv2.undistort(frame, K, dist)                                                                          (calibration.py:52-81)
+ *     cv2.warpPerspective(frame, K_s_mod . R_rel . K_i^-1, (w_s, h_s), borderMode = BORDER_REPLICATE)         (calibration.py:170-204)
+ * before any network sees it (standard pose: 1024 x 512).  vp_frame_set_rectify makes LATER uploads do both on the device, on the frame's own stream,
+ * behind the format conversion and ahead of the "content ready" event: from there on the frame IS the standard-pose picture -- vp_frame_dims answers
+ * (out_h, out_w), vp_frame_fetch_bgr8, every region consumer and vp_canvas_begin see it, and detections, masks and lane rows come out in
+ * standard-pose coordinates.  The ordering contract above is unchanged.  NULL switches rectification off; without the setting an upload runs exactly
+ * the launches and gives exactly the bits it did before the setting existed.
+ * The formulas below ARE the definition.  OpenCV is absent here, so parity with cv2.undistort / cv2.warpPerspective is not pinned (as for cv::resize
+ * and cvtColor).
+ * SAMPLE.  A map entry of a destination pixel is (X, Y): the source coordinates in units of 1/32 pixel, integers.
+ *     ix = X >> 5, iy = Y >> 5 (arithmetic shift);  fx = X & 31, fy = Y & 31
+ *     taps     (ix, iy)            (ix + 1, iy)      (ix, iy + 1)      (ix + 1, iy + 1)
+ *     weights  (32 - fx)(32 - fy)  fx (32 - fy)      (32 - fx) fy      fx fy                     sum 1024
+ *     out = (sum of weight x byte + 512) >> 10                                                  per channel
+ *   (the familiar 32 x 32 table of 15-bit weights with + 2^14 >> 15 gives the same value: every weight times 32 is an integer).
+ *   VP_BORDER_CONSTANT: a tap outside the source contributes 0.  VP_BORDER_REPLICATE: tap coordinates are clamped to the picture.
+ * COORDINATES are computed in IEEE double, in the order written, with no fused multiply-add.  X = rne(32 u): round half to even, then clamp to
+ *   [-2^20, 2^20 - 1] (a NaN takes the lower clamp).  They are exchanged as int16 (ix, iy) pairs plus uint16 frac = fy << 5 | fx.
+ * UNDISTORT MAP.  Destination size = source size.  K = [fx 0 cx; 0 fy cy; 0 0 1], dist = (k1, k2, p1, p2, k3) (OpenCV's order).  For pixel (j, i):
+ *     x = (j - cx) / fx;  y = (i - cy) / fy;  r2 = x x + y y
+ *     kr = 1 + ((k3 r2 + k2) r2 + k1) r2
+ *     xd = x kr + p1 (2 (x y)) + p2 (r2 + 2 (x x))
+ *     yd = y kr + p1 (r2 + 2 (y y)) + p2 (2 (x y))
+ *     u = fx xd + cx;  v = fy yd + cy                        X = rne(32 u), Y = rne(32 v);  border CONSTANT (value 0), as cv2.undistort
+ * PERSPECTIVE MAP.  Destination out_w x out_h; H maps source to destination, as cv2.warpPerspective takes it.  M = adj(H) / det(H) with
+ *     a0 = H4 H8 - H5 H7   a1 = H2 H7 - H1 H8   a2 = H1 H5 - H2 H4
+ *     a3 = H5 H6 - H3 H8   a4 = H0 H8 - H2 H6   a5 = H2 H3 - H0 H5
+ *     a6 = H3 H7 - H4 H6   a7 = H1 H6 - H0 H7   a8 = H0 H4 - H1 H3        det = (H0 a0 + H1 a3) + H2 a6;   Mi = ai / det
+ *   For destination (x, y):  X0 = (M0 x + M1 y) + M2;  Y0 = (M3 x + M4 y) + M5;  W = (M6 x + M7 y) + M8;  s = W != 0 ? 32 / W : 0
+ *     X = rne(clamp(X0 s, -2^31, 2^31)), Y likewise, then the clamp to [-2^20, 2^20 - 1];  border REPLICATE.
+ * MODES.  VP_RECTIFY_TWO_PASS (default) is the protocol's own pipeline: pass 1 undistort, raw -> raw-sized; pass 2 warp, raw-sized -> out.  A pass whose
+ *   map is the identity is skipped, which is exact (frac = 0: (1024 p + 512) >> 10 = p): pass 1 when all five coefficients are 0, pass 2 when H is the
+ *   identity and out equals the raw size.
+ *   VP_RECTIFY_ONE_PASS (opt-in): ONE map, one resampling.  For destination (x, y): (px, py) = (W != 0 ? X0 / W : 0, likewise Y0) clamped to
+ *   [0, w - 1] x [0, h - 1] (REPLICATE on the undistorted domain); then the distortion formulas with x = (px - cx) / fx, y = (py - cy) / fy;
+ *   X = rne(32 u), Y = rne(32 v); border CONSTANT on the raw picture.  Half the traffic and one interpolation instead of two -- and therefore NOT bit-equal
+ *   to the two passes (DESIGN.md records the difference on a smooth picture).
+ * COST.  The maps are built on the host (the code behind vp_rectify_map), uploaded and kept per raw geometry (src_h, src_w); they are rebuilt only when
+ *   the geometry or the setting changes: one host computation and one host wait per geometry, next to the one of a growing buffer.
+ * REFUSALS (VP_ERR_ARG with text; a refused call changes nothing): a non-finite value; fx or fy equal to 0; K[1], K[3], K[6], K[7] not 0 or K[8] not 1
+ *   (no skew); det H = 0 (or not finite); out_w / out_h outside 2 .. 16384; an unknown mode.
+ * vp_rectify_map (host only, no device): the map `which` (0 undistort, 1 warp, 2 one-pass) for a src_h x src_w source in the exchange form: xy
+ *   [n][2] int16 (ix, iy), frac [n] uint16, n = src_h * src_w (which 0) or out_h * out_w, row-major.
+ * vp_rectify_homography (host only) restates calibration.py:16-49, 84-204: R = Rodrigues of the vector (pitch, yaw, roll) in radians (identity at
+ *   angle 0); R_rel = R_s . R_i^-1 (the inverse of a rotation: its transpose);  f_s = (w_s / 2) / tan(hfov_s / 2), K_s = [f_s 0 w_s/2; 0 f_s h_s/2; 0 0 1];
+ *   K_s_mod = K_s with its [1][1] multiplied by camera_height_s / camera_height_i;  H = K_s_mod . R_rel . K_i^-1.  Of `inference` it reads the angles,
+ *   camera_height and K; of `standard` the angles, camera_height, img_w, img_h and hfov_deg.  VP_ERR_ARG: a non-finite value, a zero camera_height of
+ *   the inference pose, fx or fy of K 0 or K skewed, img_w / img_h below 1, hfov outside (0, 180). */
+enum vp_rectify_mode { VP_RECTIFY_TWO_PASS = 0, VP_RECTIFY_ONE_PASS = 1 };
+enum vp_border { VP_BORDER_CONSTANT = 0, VP_BORDER_REPLICATE = 1 };
+typedef struct vp_rectify {
+  double K[9];
+  double dist[5];
+  double H[9];
+  int out_w, out_h;
+  int mode;
+} vp_rectify;
+int vp_frame_set_rectify(vp_frame* f, const vp_rectify* r);              /* NULL: off; applies to LATER uploads, like vp_frame_set_color */
+int vp_frame_get_rectify(const vp_frame* f, vp_rectify* out);            /* VP_ERR_STATE when off */
+int vp_rectify_map(const vp_rectify* r, int src_h, int src_w, int which, int16_t* xy, uint16_t* frac);
+typedef struct vp_camera_pose {
+  double pitch_deg, yaw_deg, roll_deg, camera_height;
+  double K[9];
+  int img_w, img_h;
+  double hfov_deg;
+} vp_camera_pose;
+int vp_rectify_homography(const vp_camera_pose* inference, const vp_camera_pose* standard, double H_out[9]);
+
 /* ---- vp_canvas: one picture per camera frame, composed on the device, fetched once in any vp_frame format -------------------------
  * The output side of vp_frame.  MasksVisualizationEngine / DepthVisualizationEngine / AutoSpeedVisualizationEngine each take the host frame and return
  * one host picture per network (the ROS2 README times the step at 25 ms per frame); vp_visualize_mask_bgr8 / vp_visualize_depth_bgr8 above are their
@@ -776,6 +846,14 @@ int vp_compose_upconv(int gpu_id, const float* wt, const float* bt, const float*
 int vp_op_upconv(int gpu_id, const float* in, int cin, int h, int w, const float* skip, int cs, const float* wt, const float* bt, const float* ws,
                  const float* bs, const float* w3, const float* b3, int cm, int cout, int act, int shape, int nsplit, int precision, float* out,
                  char* err, size_t err_len);
+
+/* ---- single-operator entry of vp_frame's rectification kernel (unit tests; not used by callers) ------------
+ * vp_op_remap_bgr8: frame_remap_kernel on a host BGR8 picture src [src_h][src_w][3] (rows src_stride >= 3 * src_w bytes apart) through ANY map in the
+ * exchange form of vp_rectify_map (xy [out_h * out_w][2] int16, frac [out_h * out_w] uint16 = fy << 5 | fx, both below 32) with either vp_border.
+ * dst [out_h][out_w][3], rows dst_stride >= 3 * out_w bytes apart; a dst_stride of at least 12 * ceil(out_w / 4) also receives the bytes the kernel
+ * writes behind each row's end (zeros).  The device destination is filled with 0xFF before the launch.  Sizes 1 .. 16384 each way. */
+int vp_op_remap_bgr8(int gpu_id, const uint8_t* src, int src_h, int src_w, int src_stride, const int16_t* xy, const uint16_t* frac, int out_h, int out_w,
+                     int border, uint8_t* dst, int dst_stride, char* err, size_t err_len);
 
 /* ---- developer options ------------------------------------------------------------------------------------
  * The library NEVER reads the environment.  The dispatch rules' developer knobs (A/B timing of a kernel against the one it replaced,

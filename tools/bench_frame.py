@@ -13,7 +13,16 @@ python tools/bench_frame.py > profiles/frame_fanout.txt
 
 python tools/bench_frame.py --convert: the upload leg alone, no engines -- vp_frame_upload + vp_frame_sync (staging copy, H2D, conversion kernel) of one
 1280 x 720 frame from pageable host memory, p50 / p99 host to host, for every YUV format at the default colour standard and for NV12 / I420 under the
-other three standards (the constants are kernel parameters: a standard should cost nothing)."""
+other three standards (the constants are kernel parameters: a standard should cost nothing).
+
+python tools/bench_frame.py --rectify > profiles/frame_rectify.txt: what vp_frame_set_rectify adds to an upload.  One 1920 x 1080 frame, NV12 and BGR8, taken
+from DEVICE planes (vp_frame_upload_device: no H2D in the figure), rectified to the 1024 x 512 standard pose under a mild distortion, two-pass and
+one-pass, next to the same upload without the setting.  The frame's stream is not visible across the C boundary, so no event can be recorded on it.
+The device time per upload is taken behind a GATE instead: the first upload of a round names a producer stream that is busy with tens of milliseconds
+of matrix products, the host queues N uploads while the frame's stream waits for that stream's event, and the host clock runs from the gate's
+completion to vp_frame_sync -- the device then runs the N uploads back to back, and the quotient holds no host time (the tool checks that the gate
+was still closed when the last upload was queued).  Bytes of the passes, from shapes: source picture read + map read (8 bytes an entry) + picture
+written."""
 import json
 import os
 import sys
@@ -74,6 +83,75 @@ def convert_leg(h=720, w=1280, warm=50, timed=500):
     f.close()
     print(json.dumps(res, indent=1))
 
+
+def rectify_leg(h=1080, w=1920, out_hw=(512, 1024), rounds=5, queued=300, gate_matmuls=6):
+    K = np.array([[1400.0, 0.0, 960.0], [0.0, 1400.0, 540.0], [0.0, 0.0, 1.0]])
+    dist = (-0.08, 0.01, 0.0005, -0.0003, 0.0)
+    H = lib.rectify_homography({"pitch": 1.5, "yaw": -0.8, "roll": 0.4, "camera_height": 1.6, "intrinsic_matrix": K},
+                               {"pitch": 0.0, "yaw": 0.0, "roll": 0.0, "camera_height": 1.45, "img_width": out_hw[1], "img_height": out_hw[0], "hfov": 70.0})
+    bgr = synthetic.synthetic_frame(h, w, 21)
+    nv12, _ = yuv_planes(bgr)
+    dev = {"nv12": [torch.from_numpy(p).cuda() for p in nv12], "bgr8": [torch.from_numpy(bgr.reshape(h, 3 * w)).cuda()]}
+    gate_stream = torch.cuda.Stream()
+    a = torch.randn(8192, 8192, device="cuda")
+    torch.cuda.synchronize()
+
+    def close_gate():   # tens of milliseconds of work on the producer stream: the frame's stream waits behind it while the host queues the uploads
+        with torch.cuda.stream(gate_stream):
+            for _ in range(gate_matmuls):
+                a @ a
+
+    close_gate()
+    gate_stream.synchronize()
+    oh, ow = out_hw
+    raw, out = 3 * h * w, 3 * oh * ow
+    pass_bytes = {"off": 0, "two_pass": (raw + 8 * h * w + raw) + (raw + 8 * oh * ow + out), "one_pass": raw + 8 * oh * ow + out}
+    res = {"library": lib.version(),
+           "protocol": f"vp_frame_upload_device of one {w} x {h} frame from device planes, rectified to {ow} x {oh}; per case {rounds} rounds; a round queues {queued} "
+                       "uploads while the frame's stream waits for the producer stream's event behind a gate of matrix products, so the device runs them back to "
+                       "back; us_per_upload = (host clock from the gate's completion to vp_frame_sync) / uploads, median, min and max of the rounds; "
+                       "gate_held = the gate was still closed when the last upload was queued in every round (false: the figure holds host time and is "
+                       "only an upper bound); enqueue_us = host time per upload call; passes_GBps = bytes of the passes (source read + map read + picture "
+                       "written, from shapes) / (us_per_upload - that of the same upload without the setting)",
+           "K": K.reshape(-1).tolist(), "dist": list(dist), "H": H.reshape(-1).tolist(), "pass_bytes": pass_bytes}
+    f = lib.Frame()
+    for fmt, planes in dev.items():
+        ptrs, strides = [p.data_ptr() for p in planes], [p.stride(0) for p in planes]
+        base = None
+        for mode in ("off", "two_pass", "one_pass"):
+            f.set_rectify(None) if mode == "off" else f.set_rectify(K, dist, H, out_hw, mode)
+            for _ in range(20):   # the maps are built in the first of these
+                f.upload_device(ptrs, strides, fmt, h, w)
+            f.sync()
+            t, enq, held = [], [], True
+            for _ in range(rounds):
+                close_gate()
+                t0 = time.perf_counter()
+                f.upload_device(ptrs, strides, fmt, h, w, producer_stream=gate_stream.cuda_stream)
+                for _ in range(queued - 1):
+                    f.upload_device(ptrs, strides, fmt, h, w)
+                enq.append((time.perf_counter() - t0) * 1e6 / queued)
+                held = held and not gate_stream.query()
+                gate_stream.synchronize()
+                t1 = time.perf_counter()
+                f.sync()
+                t.append((time.perf_counter() - t1) * 1e6 / queued)
+            us = float(np.median(t))
+            rec = {"us_per_upload": round(us, 2), "min": round(min(t), 2), "max": round(max(t), 2), "gate_held": held, "enqueue_us": round(float(np.median(enq)), 2),
+                   "picture_hw": list(f.hw())}
+            if mode == "off":
+                base = us
+            else:
+                rec["us_over_off"] = round(us - base, 2)
+                rec["passes_GBps"] = round(pass_bytes[mode] / ((us - base) * 1e-6) / 1e9, 1) if us > base else None
+            res[f"{fmt}_{mode}"] = rec
+    f.close()
+    print(json.dumps(res, indent=1))
+
+
+if "--rectify" in sys.argv[1:]:
+    rectify_leg()
+    sys.exit(0)
 
 if "--convert" in sys.argv[1:]:
     convert_leg()
