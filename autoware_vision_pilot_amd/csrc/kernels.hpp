@@ -90,6 +90,47 @@ struct FrameToBgrParams {
 };
 hipError_t launch_frame_to_bgr8(const FrameToBgrParams& p, hipStream_t st);
 
+// The upload-only formats of vp_frame (include/vp_hip.h): 16-bit grey (20), P010 (21), raw Bayer in 8-bit (32 .. 35) and 16-bit (36 .. 39) containers.
+// They have kernels of their own and no dense index: frame_format_index answers -1 for them, so the canvas and every table of kFrameFormats entries
+// keep refusing them.  16-bit samples are little-endian words; their planes and strides are 2-byte aligned (checked at the upload).
+inline bool frame_format_deep(int format) { return format == 20 || format == 21; }
+inline bool frame_format_bayer(int format) { return format >= 32 && format <= 39; }
+inline bool frame_format_bayer16(int format) { return format >= 36 && format <= 39; }
+// frame_deep_to_bgr8_kernel: every 16-bit sample is narrowed first, x8 = min(255, (s + 128) >> 8) (MSB-aligned, as P010 / P012 / P016 are); from there
+// P010 (Y words in p0, interleaved U V words in p1) is NV12's arithmetic and GRAY16 is GRAY8's, with their work-item shapes.
+struct FrameDeepParams {
+  const uint8_t* p0;
+  const uint8_t* p1;
+  int s0, s1;           // bytes
+  int h, w;
+  int format;           // 20 GRAY16, 21 P010
+  uint8_t* dst;
+  int dst_pitch;
+  YuvToBgr k;           // read by P010 only
+};
+hipError_t launch_frame_deep_to_bgr8(const FrameDeepParams& p, hipStream_t st);
+// frame_raw_to_bgr8_kernel: linearise, white balance, bilinear demosaic, optional matrix, tone -- include/vp_hip.h states the arithmetic as the
+// DEFINITION.  One work-item produces a 4 x 2 block (two whole CFA cells) from its 6 x 4 sample window, read at mirrored addresses (-1 -> 1, n -> n - 2:
+// CFA parity is kept and no index leaves the plane).  The CFA order is two bits: green00 (the site (0, 0) is green) and red_row0 (row 0 holds the red
+// sites), so a site (y, x) is green when (x ^ y ^ green00) & 1, and otherwise red when (y & 1) != red_row0.  Everything but the samples is uniform
+// over the launch.  lut: device memory, 1 << min(bits, 12) entries, or nullptr for the rounding shift to 8 bits.
+struct FrameRawParams {
+  const uint8_t* src;
+  int stride;           // bytes
+  int h, w;
+  int wide;             // 1: 16-bit words, 0: bytes
+  int green00, red_row0;
+  int bits;             // B, the significant bits: 8, 10, 12, 14 or 16 (8 only with bytes, the others only with words)
+  int shift, black;
+  int gains[3];         // Q8; R, G, B
+  int ccm_on;
+  int ccm[9];           // Q10, rows and columns R, G, B
+  const uint8_t* lut;
+  uint8_t* dst;
+  int dst_pitch;
+};
+hipError_t launch_frame_raw_to_bgr8(const FrameRawParams& p, hipStream_t st);
+
 // vp_canvas (include/vp_hip.h): one BGR8 picture per camera frame with the geometry and pitch of a vp_frame's image (rows frame_bgr_pitch(w) apart, base and
 // pitch multiples of 4), drawn into IN PLACE.  Every kernel below gives one work-item an aligned four-pixel block of a canvas row -- three 32-bit words
 // in, three out -- and leaves the pixels of the block it does not own as it read them (a region's odd edge, the zero bytes behind a row's end).

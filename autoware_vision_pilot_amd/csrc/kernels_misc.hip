@@ -166,6 +166,125 @@ __global__ __launch_bounds__(256) void frame_remap_kernel(const FrameRemapParams
   store_bgr4(p.dst + (size_t)y * p.dst_pitch, j, px);
 }
 
+// vp_frame's 16-bit formats (kernels.hpp FrameDeepParams): P010 with NV12's work-item (four pixels of two rows, two whole chroma groups), GRAY16 with
+// GRAY8's (four pixels of a row).  Every sample is one aligned 16-bit load, narrowed to x8 = min(255, (s + 128) >> 8) before anything else, so the
+// arithmetic behind it is frame_to_bgr8_kernel's to the bit.  The narrowed byte is held in a register of its own (chroma_of: a packed shift-and-clamp).
+__device__ __forceinline__ int narrow16(const uint8_t* s) {
+  return (int)own_register(min(255u, ((unsigned)*reinterpret_cast<const uint16_t*>(s) + 128u) >> 8));
+}
+__global__ __launch_bounds__(256) void frame_deep_to_bgr8_kernel(const FrameDeepParams p) {
+  const int bpr = (p.w + 3) >> 2;
+  const bool p010 = p.format == 21;
+  const int rows = p010 ? p.h >> 1 : p.h;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)rows * bpr) return;
+  const int r = (int)(t / bpr), j = (int)(t - (long long)r * bpr), x0 = 4 * j;
+  unsigned px[4] = {0u, 0u, 0u, 0u};
+  if (p010) {   // Y rows 2r, 2r + 1; row r of the U V plane: the words U, V of the group at pixel x lie 2 x bytes in
+    const uint8_t* y0 = p.p0 + (size_t)(2 * r) * p.s0 + 2 * (size_t)x0;
+    const uint8_t* y1 = y0 + p.s0;
+    const uint8_t* uv = p.p1 + (size_t)r * p.s1 + 2 * (size_t)x0;
+    unsigned px1[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      if (x0 + 2 * g >= p.w) break;                        // w is even: a group is whole or absent
+      const ChromaTerms c = chroma_terms(p.k, narrow16(uv + 4 * g), narrow16(uv + 4 * g + 2));
+      px[2 * g] = yuv_pixel(p.k, narrow16(y0 + 4 * g), c);
+      px[2 * g + 1] = yuv_pixel(p.k, narrow16(y0 + 4 * g + 2), c);
+      px1[2 * g] = yuv_pixel(p.k, narrow16(y1 + 4 * g), c);
+      px1[2 * g + 1] = yuv_pixel(p.k, narrow16(y1 + 4 * g + 2), c);
+    }
+    store_bgr4(p.dst + (size_t)(2 * r) * p.dst_pitch, j, px);
+    store_bgr4(p.dst + (size_t)(2 * r + 1) * p.dst_pitch, j, px1);
+    return;
+  }
+  const uint8_t* row = p.p0 + (size_t)r * p.s0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (x0 + i >= p.w) break;
+    px[i] = 0x010101u * (unsigned)narrow16(row + 2 * (size_t)(x0 + i));
+  }
+  store_bgr4(p.dst + (size_t)r * p.dst_pitch, j, px);
+}
+
+// vp_frame's raw Bayer formats (kernels.hpp FrameRawParams; include/vp_hip.h states the arithmetic as the DEFINITION).  One work-item owns the 4 x 2
+// block at (4 j, 2 r) -- two whole CFA cells, two store_bgr4 rows -- and reads its 6 x 4 window once, linearising and white-balancing each sample as it
+// arrives.  Window position (wy, wx) is the site (2 r - 1 + wy, 4 j - 1 + wx), so its CFA colour depends on (wy, wx) and the two uniform order bits only:
+// every colour decision below is uniform over the launch.  16-bit samples are aligned 16-bit loads, 8-bit samples bytes.  No LDS, no atomics.
+__device__ __forceinline__ int mirror_index(int i, int n) {   // -1 -> 1, n -> n - 2; the clamp only meets columns that no pixel inside the row reads
+  i = i < 0 ? -i : i;
+  i = i >= n ? 2 * n - 2 - i : i;
+  return min(max(i, 0), n - 1);
+}
+__device__ __forceinline__ int raw_matrix_row(const int* k, int r, int g, int b, int M) { return min(max((k[0] * r + k[1] * g + k[2] * b + 512) >> 10, 0), M); }
+__global__ __launch_bounds__(256) void frame_raw_to_bgr8_kernel(const FrameRawParams p) {
+  const int bpr = (p.w + 3) >> 2;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)(p.h >> 1) * bpr) return;
+  const int r = (int)(t / bpr), j = (int)(t - (long long)r * bpr), x0 = 4 * j, y0 = 2 * r;
+  const int M = (1 << p.bits) - 1;
+  int cx[6];
+#pragma unroll
+  for (int wx = 0; wx < 6; ++wx) cx[wx] = mirror_index(x0 - 1 + wx, p.w);
+  int v[4][6];
+#pragma unroll
+  for (int wy = 0; wy < 4; ++wy) {
+    const uint8_t* row = p.src + (size_t)mirror_index(y0 - 1 + wy, p.h) * p.stride;
+    const int yodd = (wy + 1) & 1;                         // y0 is even
+#pragma unroll
+    for (int wx = 0; wx < 6; ++wx) {
+      const int xodd = (wx + 1) & 1;                       // x0 is a multiple of 4
+      const int gain = ((xodd ^ yodd ^ p.green00) & 1) ? p.gains[1] : (yodd != p.red_row0 ? p.gains[0] : p.gains[2]);
+      const int s = p.wide ? (int)*reinterpret_cast<const uint16_t*>(row + 2 * (size_t)cx[wx]) : (int)row[cx[wx]];
+      const int lin = max(0, min(s >> p.shift, M) - p.black);
+      v[wy][wx] = min(M, (lin * gain + 128) >> 8);
+    }
+  }
+  const int lut_shift = p.bits > 12 ? p.bits - 12 : 0;
+  const int tone_shift = p.bits - 8, tone_round = p.bits > 8 ? 1 << (p.bits - 9) : 0;
+  unsigned px[2][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+#pragma unroll
+  for (int py = 0; py < 2; ++py) {
+    const bool red_row = py != p.red_row0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (x0 + k >= p.w) break;
+      const int wy = py + 1, wx = k + 1;
+      const int c = v[wy][wx], n = v[wy - 1][wx], s = v[wy + 1][wx], w = v[wy][wx - 1], e = v[wy][wx + 1];
+      int R, G, B;
+      if ((k ^ py ^ p.green00) & 1) {   // a green site: one colour left and right, the other above and below
+        const int hor = (w + e + 1) >> 1, ver = (n + s + 1) >> 1;
+        G = c;
+        R = red_row ? hor : ver;
+        B = red_row ? ver : hor;
+      } else {                          // a red or blue site: green on the cross, the opposite colour on the diagonals
+        const int diag = (v[wy - 1][wx - 1] + v[wy - 1][wx + 1] + v[wy + 1][wx - 1] + v[wy + 1][wx + 1] + 2) >> 2;
+        G = (n + s + w + e + 2) >> 2;
+        R = red_row ? c : diag;
+        B = red_row ? diag : c;
+      }
+      if (p.ccm_on) {
+        const int r2 = raw_matrix_row(p.ccm, R, G, B, M), g2 = raw_matrix_row(p.ccm + 3, R, G, B, M), b2 = raw_matrix_row(p.ccm + 6, R, G, B, M);
+        R = r2;
+        G = g2;
+        B = b2;
+      }
+      if (p.lut) {
+        R = p.lut[R >> lut_shift];
+        G = p.lut[G >> lut_shift];
+        B = p.lut[B >> lut_shift];
+      } else if (p.bits > 8) {
+        R = min(255, (R + tone_round) >> tone_shift);
+        G = min(255, (G + tone_round) >> tone_shift);
+        B = min(255, (B + tone_round) >> tone_shift);
+      }
+      px[py][k] = own_register((unsigned)B) | (own_register((unsigned)G) << 8) | (own_register((unsigned)R) << 16);   // own registers: see chroma_of
+    }
+  }
+  store_bgr4(p.dst + (size_t)y0 * p.dst_pitch, j, px[0]);
+  store_bgr4(p.dst + (size_t)(y0 + 1) * p.dst_pitch, j, px[1]);
+}
+
 // Pillow's 8-bit resample passes (kernels.hpp PilResampleParams): int32 accumulation from 1 << 21 of u8 x 22-bit coefficients,
 // `>> 22`, clip to u8 (Resample.c clip8) -- integer work, bit-exact by construction.
 __device__ __forceinline__ int pil_clip8(int acc) { return min(max(acc >> 22, 0), 255); }
@@ -949,6 +1068,28 @@ hipError_t launch_frame_to_bgr8(const FrameToBgrParams& q, hipStream_t st) {
   }
   const long long n = (long long)(f420 ? p.h / 2 : p.h) * ((p.w + 3) / 4);
   VP_LAUNCH(frame_to_bgr8_kernel, dim3(nblk(n)), dim3(256), 0, st, p);
+}
+hipError_t launch_frame_deep_to_bgr8(const FrameDeepParams& p, hipStream_t st) {
+  const bool p010 = p.format == 21;
+  const auto odd = [](const void* a, int s) { return ((reinterpret_cast<uintptr_t>(a) | (uintptr_t)s) & 1) != 0; };
+  if (!frame_format_deep(p.format) || !p.p0 || !p.dst || p.h < 2 || p.w < 2 || p.h > 16384 || p.w > 16384 || p.s0 < 2 * p.w || odd(p.p0, p.s0) ||
+      (p010 && (!p.p1 || ((p.h | p.w) & 1) || p.s1 < 2 * p.w || odd(p.p1, p.s1))) || p.dst_pitch < frame_bgr_pitch(p.w) || (p.dst_pitch & 3) ||
+      (reinterpret_cast<uintptr_t>(p.dst) & 3))
+    return hipErrorInvalidValue;
+  const long long n = (long long)(p010 ? p.h / 2 : p.h) * ((p.w + 3) / 4);
+  VP_LAUNCH(frame_deep_to_bgr8_kernel, dim3(nblk(n)), dim3(256), 0, st, p);
+}
+hipError_t launch_frame_raw_to_bgr8(const FrameRawParams& p, hipStream_t st) {
+  const int px_bytes = p.wide ? 2 : 1;
+  bool ok = p.src && p.dst && p.h >= 2 && p.w >= 2 && p.h <= 16384 && p.w <= 16384 && !((p.h | p.w) & 1) && p.stride >= px_bytes * p.w &&
+            (p.wide ? p.bits == 10 || p.bits == 12 || p.bits == 14 || p.bits == 16 : p.bits == 8) &&
+            (!p.wide || !((reinterpret_cast<uintptr_t>(p.src) | (uintptr_t)p.stride) & 1)) && p.shift >= 0 && p.shift <= 8 && p.black >= 0 &&
+            p.black < (1 << p.bits) && (p.wide | p.green00 | p.red_row0 | p.ccm_on | 1) == 1 && p.dst_pitch >= frame_bgr_pitch(p.w) && !(p.dst_pitch & 3) &&
+            !(reinterpret_cast<uintptr_t>(p.dst) & 3);
+  for (int g : p.gains) ok = ok && g >= 0 && g <= 16383;         // 65535 * 16383 + 128 < 2^31
+  for (int c : p.ccm) ok = ok && (!p.ccm_on || (c >= -8191 && c <= 8191));   // 3 * 8191 * 65535 + 512 < 2^31
+  if (!ok) return hipErrorInvalidValue;
+  VP_LAUNCH(frame_raw_to_bgr8_kernel, dim3(nblk((long long)(p.h / 2) * ((p.w + 3) / 4))), dim3(256), 0, st, p);
 }
 hipError_t launch_frame_remap(const FrameRemapParams& p, hipStream_t st) {
   if (!p.src || !p.map || !p.dst || p.src_h < 1 || p.src_w < 1 || p.src_h > 32768 || p.src_w > 32768 || p.src_pitch < 3 * p.src_w || p.out_h < 1 || p.out_w < 1 ||

@@ -1,4 +1,5 @@
 // C ABI of libvp_hip.so (declarations + reference citations: include/vp_hip.h).  No exception crosses it.
+#include <algorithm>
 #include <cctype>
 #include <cmath>
 #include <cstdio>
@@ -487,7 +488,7 @@ vp_frame::~vp_frame() {
     if (ev) (void)hipEventDestroy(ev);
   if (d_bgr) (void)hipFree(d_bgr);
   if (d_src) (void)hipFree(d_src);
-  for (void* p : {(void*)d_raw, (void*)d_mid, (void*)d_map[0], (void*)d_map[1]})
+  for (void* p : {(void*)d_raw, (void*)d_mid, (void*)d_map[0], (void*)d_map[1], (void*)d_lut})
     if (p) (void)hipFree(p);
   if (h_stage) (void)hipHostFree(h_stage);
   if (stream) (void)hipStreamDestroy(stream);
@@ -593,6 +594,61 @@ FramePlanes check_frame_planes(const char* who, int format, const void* const* p
       throw std::invalid_argument(me + ": stride " + std::to_string(strides[i]) + " of plane " + std::to_string(i) + " is below the row's " + std::to_string(fp.row_bytes[i]) + " bytes");
   }
   return fp;
+}
+
+// ---- the upload-only formats (GRAY16, P010, raw Bayer): layouts and refusals of their own, so vp_canvas_* keeps answering "unknown format" for them
+bool upload_only_format(int format) { return vp::frame_format_deep(format) || vp::frame_format_bayer(format); }
+std::string upload_only_name(int format) {
+  static const char* const order[4] = {"RGGB", "GRBG", "GBRG", "BGGR"};
+  if (format == VP_FRAME_GRAY16) return "GRAY16";
+  if (format == VP_FRAME_P010) return "P010";
+  return std::string("BAYER_") + order[(format - VP_FRAME_BAYER_RGGB8) & 3] + (vp::frame_format_bayer16(format) ? "16" : "8");
+}
+// B of the definition (include/vp_hip.h) for a Bayer upload under the frame's raw setting, and the refusals that need B
+int raw_significant_bits(const std::string& me, const vp_frame* f, int format) {
+  const vp_raw& r = f->raw;
+  const bool wide = vp::frame_format_bayer16(format);
+  const std::string fmt = upload_only_name(format);
+  if (r.bits == 8 && wide) throw std::invalid_argument(me + ": the raw setting's bits = 8 does not fit " + fmt + " (16-bit words: 10, 12, 14, 16 or 0)");
+  if (r.bits > 8 && !wide) throw std::invalid_argument(me + ": the raw setting's bits = " + std::to_string(r.bits) + " does not fit " + fmt + " (bytes: 8 or 0)");
+  const int B = r.bits ? r.bits : (wide ? 16 : 8), M = (1 << B) - 1;
+  if (r.black > M) throw std::invalid_argument(me + ": the raw setting's black = " + std::to_string(r.black) + " is above the " + std::to_string(B) + "-bit maximum " + std::to_string(M));
+  if (r.lut_len && r.lut_len != 1 << (B < 12 ? B : 12))
+    throw std::invalid_argument(me + ": the raw setting's LUT has " + std::to_string(r.lut_len) + " entries, " + std::to_string(B) + "-bit samples need " + std::to_string(1 << (B < 12 ? B : 12)));
+  return B;
+}
+FramePlanes check_upload_only_planes(const std::string& me, const vp_frame* f, int format, const void* const* planes, const int* strides, int n_planes, int h, int w) {
+  const std::string fmt = upload_only_name(format);
+  const bool p010 = format == VP_FRAME_P010, bayer = vp::frame_format_bayer(format), wide = !bayer || vp::frame_format_bayer16(format);
+  const int n = p010 ? 2 : 1;
+  if (n_planes != n) throw std::invalid_argument(me + ": " + fmt + " has " + std::to_string(n) + " plane(s), got n_planes = " + std::to_string(n_planes));
+  if (!planes || !strides) throw std::invalid_argument(me + ": null planes / strides");
+  if (h < 2 || w < 2 || h > 16384 || w > 16384) throw std::invalid_argument(me + ": frame size " + std::to_string(w) + " x " + std::to_string(h) + " (2 .. 16384 each way)");
+  const char* why = p010 ? "one chroma pair per 2x2 block" : "whole 2x2 CFA cells";
+  if (format != VP_FRAME_GRAY16 && (w & 1)) throw std::invalid_argument(me + ": " + fmt + " needs an even width (" + why + "), got " + std::to_string(w));
+  if (format != VP_FRAME_GRAY16 && (h & 1)) throw std::invalid_argument(me + ": " + fmt + " needs an even height (" + why + "), got " + std::to_string(h));
+  FramePlanes fp;
+  fp.n = n;
+  fp.row_bytes[0] = (size_t)(wide ? 2 : 1) * w;
+  fp.rows[0] = h;
+  if (p010) {
+    fp.row_bytes[1] = 2 * (size_t)w;   // w / 2 pairs of U V words
+    fp.rows[1] = h / 2;
+  }
+  for (int i = 0; i < fp.n; ++i) {
+    if (!planes[i]) throw std::invalid_argument(me + ": plane " + std::to_string(i) + " is null");
+    if (strides[i] < 0 || (size_t)strides[i] < fp.row_bytes[i])
+      throw std::invalid_argument(me + ": stride " + std::to_string(strides[i]) + " of plane " + std::to_string(i) + " is below the row's " + std::to_string(fp.row_bytes[i]) + " bytes");
+    if (wide && (strides[i] & 1)) throw std::invalid_argument(me + ": stride " + std::to_string(strides[i]) + " of plane " + std::to_string(i) + " is odd: " + fmt + " holds 16-bit words");
+    if (wide && (reinterpret_cast<uintptr_t>(planes[i]) & 1)) throw std::invalid_argument(me + ": plane " + std::to_string(i) + " lies at an odd address: " + fmt + " holds 16-bit words");
+  }
+  if (bayer) (void)raw_significant_bits(me, f, format);
+  return fp;
+}
+// every refusal of vp_frame_upload* ahead of the first change to the frame
+FramePlanes check_upload(const char* who, const vp_frame* f, int format, const void* const* planes, const int* strides, int n_planes, int h, int w) {
+  if (upload_only_format(format)) return check_upload_only_planes(who, f, format, planes, strides, n_planes, h, w);
+  return check_frame_planes(who, format, planes, strides, n_planes, h, w);
 }
 
 void check_color(const std::string& me, int matrix, int range) {
@@ -821,6 +877,44 @@ void end_upload(vp_frame* f, int h, int w) {
 
 // planes / strides in the format's own order, device memory
 void convert_planes(vp_frame* f, int format, const uint8_t* const* p, const int* s, int n, int h, int w) {
+  if (vp::frame_format_bayer(format)) {
+    const vp_raw& r = f->raw;
+    const int order = (format - VP_FRAME_BAYER_RGGB8) & 3;   // RGGB, GRBG, GBRG, BGGR
+    vp::FrameRawParams q{};
+    q.src = p[0];
+    q.stride = s[0];
+    q.h = h;
+    q.w = w;
+    q.wide = vp::frame_format_bayer16(format) ? 1 : 0;
+    q.green00 = order == 1 || order == 2;
+    q.red_row0 = order < 2;
+    q.bits = raw_significant_bits("vp_frame_upload", f, format);
+    q.shift = r.shift;
+    q.black = r.black;
+    std::copy(r.gains, r.gains + 3, q.gains);
+    q.ccm_on = r.ccm_on ? 1 : 0;
+    std::copy(r.ccm, r.ccm + 9, q.ccm);
+    q.lut = r.lut_len ? f->d_lut : nullptr;
+    q.dst = conversion_target(f, h, w);
+    q.dst_pitch = vp::frame_bgr_pitch(w);
+    VP_HIP_CHECK(vp::launch_frame_raw_to_bgr8(q, f->stream));
+    return;
+  }
+  if (vp::frame_format_deep(format)) {
+    vp::FrameDeepParams q{};
+    q.p0 = p[0];
+    q.s0 = s[0];
+    q.p1 = n > 1 ? p[1] : nullptr;
+    q.s1 = n > 1 ? s[1] : 0;
+    q.h = h;
+    q.w = w;
+    q.format = format;
+    q.dst = conversion_target(f, h, w);
+    q.dst_pitch = vp::frame_bgr_pitch(w);
+    q.k = vp::color_standard(f->color_matrix, f->color_range).inv;
+    VP_HIP_CHECK(vp::launch_frame_deep_to_bgr8(q, f->stream));
+    return;
+  }
   vp::FrameToBgrParams q{};
   q.p0 = p[0];
   q.s0 = s[0];
@@ -872,7 +966,7 @@ const char* vp_frame_last_error(const vp_frame* f) { return f ? f->err.c_str() :
 
 int vp_frame_upload(vp_frame* f, int format, const uint8_t* const* planes, const int* strides, int n_planes, int h, int w) {
   return frame_guarded(f, [&] {
-    const FramePlanes fp = check_frame_planes("vp_frame_upload", format, reinterpret_cast<const void* const*>(planes), strides, n_planes, h, w);
+    const FramePlanes fp = check_upload("vp_frame_upload", f, format, reinterpret_cast<const void* const*>(planes), strides, n_planes, h, w);
     size_t total = 0;
     bool registered = true;   // every plane inside a vp_register_frames range: one DMA per plane straight from the caller's memory
     for (int i = 0; i < fp.n; ++i) {
@@ -917,7 +1011,7 @@ int vp_frame_upload(vp_frame* f, int format, const uint8_t* const* planes, const
 
 int vp_frame_upload_device(vp_frame* f, int format, const void* const* dev_planes, const int* strides, int n_planes, int h, int w, void* producer_stream) {
   return frame_guarded(f, [&] {
-    const FramePlanes fp = check_frame_planes("vp_frame_upload_device", format, dev_planes, strides, n_planes, h, w);
+    const FramePlanes fp = check_upload("vp_frame_upload_device", f, format, dev_planes, strides, n_planes, h, w);
     begin_upload(f, h, w, 0, 0);
     if (producer_stream) {   // the planes are complete once the work queued on the producer's stream so far has run
       VP_HIP_CHECK(hipEventRecord(f->producer, static_cast<hipStream_t>(producer_stream)));
@@ -943,6 +1037,41 @@ int vp_frame_get_color(const vp_frame* f, int* matrix, int* range) {
   if (!f || !matrix || !range) return VP_ERR_ARG;
   *matrix = f->color_matrix;
   *range = f->color_range;
+  return VP_OK;
+}
+
+int vp_frame_set_raw(vp_frame* f, const vp_raw* r) {
+  return frame_guarded(f, [&] {
+    const std::string me = "vp_frame_set_raw";
+    vp_raw s{0, 0, 0, {256, 256, 256}, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}, nullptr, 0};
+    if (r) s = *r;
+    if (s.bits != 0 && s.bits != 8 && s.bits != 10 && s.bits != 12 && s.bits != 14 && s.bits != 16)
+      throw std::invalid_argument(me + ": bits = " + std::to_string(s.bits) + " (0, 8, 10, 12, 14 or 16)");
+    if (s.shift < 0 || s.shift > 8) throw std::invalid_argument(me + ": shift = " + std::to_string(s.shift) + " (0 .. 8)");
+    if (s.black < 0) throw std::invalid_argument(me + ": black = " + std::to_string(s.black) + " is negative");
+    for (int g : s.gains)
+      if (g < 0 || g > 16383) throw std::invalid_argument(me + ": gain " + std::to_string(g) + " (Q8, 0 .. 16383)");
+    if (s.ccm_on)
+      for (int c : s.ccm)
+        if (c < -8191 || c > 8191) throw std::invalid_argument(me + ": ccm entry " + std::to_string(c) + " (Q10, -8191 .. 8191)");
+    if ((s.lut != nullptr) != (s.lut_len != 0)) throw std::invalid_argument(me + ": lut and lut_len go together (one is set, the other is not)");
+    if (s.lut && s.lut_len != 256 && s.lut_len != 1024 && s.lut_len != 4096)
+      throw std::invalid_argument(me + ": lut_len = " + std::to_string(s.lut_len) + " (256, 1024 or 4096)");
+    if (s.lut) {   // ordered like the rectification maps: behind every conversion queued so far, and copied before the call returns
+      VP_HIP_CHECK(hipStreamSynchronize(f->stream));
+      if (!f->d_lut) VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&f->d_lut), 4096));
+      VP_HIP_CHECK(hipMemcpyAsync(f->d_lut, s.lut, (size_t)s.lut_len, hipMemcpyHostToDevice, f->stream));
+      VP_HIP_CHECK(hipStreamSynchronize(f->stream));
+    }
+    s.ccm_on = s.ccm_on ? 1 : 0;
+    s.lut = nullptr;
+    f->raw = s;
+  });
+}
+
+int vp_frame_get_raw(const vp_frame* f, vp_raw* out) {
+  if (!f || !out) return VP_ERR_ARG;
+  *out = f->raw;
   return VP_OK;
 }
 

@@ -34,6 +34,10 @@ struct vp_frame {
   int h = 0, w = 0, pitch = 0;
   bool uploaded = false;
   int color_matrix = 0, color_range = 0;   // vp_frame_set_color: the standard of later YUV uploads (BT.601, limited range)
+  // vp_frame_set_raw: the setting of later Bayer uploads (raw.lut stays null: the table lives in d_lut, raw.lut_len entries of it, copied on the
+  // frame's stream at the call, behind every conversion queued before it)
+  vp_raw raw{0, 0, 0, {256, 256, 256}, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}, nullptr, 0};
+  uint8_t* d_lut = nullptr;      // [4096]
   // vp_frame_set_rectify: later uploads convert into d_raw (the camera's geometry) and are resampled into d_bgr (the standard pose's) on the frame's
   // stream, ahead of `ready`.  Maps: built on the host once per (raw geometry, setting), kept on the device; d_map[0] undistort or the one-pass map,
   // d_map[1] the warp (an identity pass has no map and is skipped).

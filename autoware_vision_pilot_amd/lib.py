@@ -159,6 +159,8 @@ _SIGS = {
     "vp_frame_upload_device": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, _P]),
     "vp_frame_set_color": (C.c_int, [_P, C.c_int, C.c_int]),
     "vp_frame_get_color": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vp_frame_set_raw": (C.c_int, [_P, _P]),
+    "vp_frame_get_raw": (C.c_int, [_P, _P]),
     "vp_frame_sync": (C.c_int, [_P]),
     "vp_frame_dims": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vp_frame_fetch_bgr8": (C.c_int, [_P, _P, C.c_int]),
@@ -217,8 +219,15 @@ VP_FRAME_BGR8, VP_FRAME_RGB8, VP_FRAME_BGRA8, VP_FRAME_RGBA8, VP_FRAME_GRAY8, VP
 VP_FRAME_I420, VP_FRAME_YV12, VP_FRAME_NV21 = 16, 17, 18
 FRAME_FORMATS = {"bgr8": VP_FRAME_BGR8, "rgb8": VP_FRAME_RGB8, "bgra8": VP_FRAME_BGRA8, "rgba8": VP_FRAME_RGBA8, "gray8": VP_FRAME_GRAY8, "nv12": VP_FRAME_NV12,
                  "yuy2": VP_FRAME_YUY2, "uyvy": VP_FRAME_UYVY, "i420": VP_FRAME_I420, "yv12": VP_FRAME_YV12, "nv21": VP_FRAME_NV21}
-_FRAME_PX_BYTES = {0: 3, 1: 3, 2: 4, 3: 4, 4: 1, 5: 1, 6: 2, 7: 2, 16: 1, 17: 1, 18: 1}   # bytes per pixel of plane 0
-_FRAME_PLANES = {VP_FRAME_NV12: 2, VP_FRAME_NV21: 2, VP_FRAME_I420: 3, VP_FRAME_YV12: 3}    # every other format: 1
+# upload-only: 16-bit grey, P010, raw Bayer in 8-bit and 16-bit containers (little-endian words)
+VP_FRAME_GRAY16, VP_FRAME_P010 = 20, 21
+BAYER_ORDERS = ("rggb", "grbg", "gbrg", "bggr")
+FRAME_FORMATS.update({"gray16": VP_FRAME_GRAY16, "p010": VP_FRAME_P010})
+FRAME_FORMATS.update({f"bayer_{o}8": 32 + i for i, o in enumerate(BAYER_ORDERS)})
+FRAME_FORMATS.update({f"bayer_{o}16": 36 + i for i, o in enumerate(BAYER_ORDERS)})
+_FRAME_PX_BYTES = {0: 3, 1: 3, 2: 4, 3: 4, 4: 1, 5: 1, 6: 2, 7: 2, 16: 1, 17: 1, 18: 1, 20: 2, 21: 2, 32: 1, 33: 1, 34: 1, 35: 1, 36: 2, 37: 2, 38: 2, 39: 2}   # bytes per pixel of plane 0
+_FRAME_WORDS = frozenset((20, 21, 36, 37, 38, 39))                                          # formats of 16-bit samples
+_FRAME_PLANES = {VP_FRAME_NV12: 2, VP_FRAME_NV21: 2, VP_FRAME_I420: 3, VP_FRAME_YV12: 3, VP_FRAME_P010: 2}    # every other format: 1
 VP_COLOR_BT601, VP_COLOR_BT709 = 0, 1
 VP_COLOR_RANGE_LIMITED, VP_COLOR_RANGE_FULL = 0, 1
 VP_CHROMA_EVEN, VP_CHROMA_MEAN = 0, 1
@@ -245,6 +254,12 @@ class RangeStats(C.Structure):
 class Rectify(C.Structure):
     """vp_rectify (include/vp_hip.h)"""
     _fields_ = [("K", C.c_double * 9), ("dist", C.c_double * 5), ("H", C.c_double * 9), ("out_w", C.c_int), ("out_h", C.c_int), ("mode", C.c_int)]
+
+
+class Raw(C.Structure):
+    """vp_raw (include/vp_hip.h)"""
+    _fields_ = [("bits", C.c_int), ("shift", C.c_int), ("black", C.c_int), ("gains", C.c_int * 3), ("ccm_on", C.c_int), ("ccm", C.c_int * 9),
+                ("lut", C.c_void_p), ("lut_len", C.c_int)]
 
 
 class CameraPose(C.Structure):
@@ -798,8 +813,10 @@ class Frame:
     def upload(self, array_or_planes, fmt="bgr8", hw=None):
         """vp_frame_upload (asynchronous).  One uint8 array -- HxWx3 (bgr8 / rgb8), HxWx4 (bgra8 / rgba8), HxW (gray8), Hx(2W) or HxWx2 (yuy2 / uyvy) -- or,
         for nv12, the pair (Y [H][W], UV [H/2][W]) or one [H * 3 / 2][W] array; for nv21 the pair (Y, VU); for i420 / yv12 the three planes (Y [H][W],
-        then U, V / V, U [H/2][W/2]); for those three also ONE flat contiguous buffer of H * W * 3 / 2 bytes, 1-D (with `hw`) or [H * 3 / 2][W].  Row
-        strides are taken from the arrays (the bytes of a row must be contiguous); `hw` overrides the (h, w) read off plane 0."""
+        then U, V / V, U [H/2][W/2]); for those three also ONE flat contiguous buffer of H * W * 3 / 2 bytes, 1-D (with `hw`) or [H * 3 / 2][W].  The
+        upload-only formats: HxW uint8 (bayer_*8), HxW uint16 (bayer_*16, gray16), for p010 the pair (Y [H][W], UV [H/2][W]) of uint16 arrays; a
+        uint8 array is taken as the bytes of the little-endian words.  Row strides are taken from the arrays (the bytes of a row must be contiguous);
+        `hw` overrides the (h, w) read off plane 0."""
         f = self._fmt(fmt)
         planes = list(array_or_planes) if isinstance(array_or_planes, (list, tuple)) else [array_or_planes]
         planes = [np.asarray(p) for p in planes]
@@ -819,11 +836,13 @@ class Frame:
                 planes = [a[:fh * fw].reshape(fh, fw), a[fh * fw:fh * fw + q].reshape(fh // 2, fw // 2), a[fh * fw + q:].reshape(fh // 2, fw // 2)]
         fixed = []
         for p in planes:
-            if p.dtype != np.uint8 or p.ndim < 2 or any(p.strides[i] != int(np.prod(p.shape[i + 1:])) for i in range(1, p.ndim)) or p.strides[0] < 0:
-                p = np.ascontiguousarray(p, dtype=np.uint8)
+            # the 16-bit formats take uint16 arrays (little-endian words) as they are; their byte strides go to the library like any other
+            dt = np.dtype("<u2") if f in _FRAME_WORDS and p.dtype.itemsize == 2 and p.dtype.kind == "u" else np.dtype(np.uint8)
+            if p.dtype != dt or p.ndim < 2 or any(p.strides[i] != int(np.prod(p.shape[i + 1:])) * dt.itemsize for i in range(1, p.ndim)) or p.strides[0] < 0:
+                p = np.ascontiguousarray(p, dtype=dt)
             fixed.append(p)
         p0 = fixed[0]
-        h, w = (int(hw[0]), int(hw[1])) if hw is not None else (p0.shape[0], int(np.prod(p0.shape[1:])) // _FRAME_PX_BYTES[f] if f in _FRAME_PX_BYTES else 0)
+        h, w = (int(hw[0]), int(hw[1])) if hw is not None else (p0.shape[0], int(np.prod(p0.shape[1:])) * p0.dtype.itemsize // _FRAME_PX_BYTES[f] if f in _FRAME_PX_BYTES else 0)
         self._keep = fixed   # a registered pool is read by DMA after the call returns
         arr = (_P * len(fixed))(*[p.ctypes.data for p in fixed])
         strides = (C.c_int * len(fixed))(*[int(p.strides[0]) for p in fixed])
@@ -846,6 +865,25 @@ class Frame:
         m, r = C.c_int(), C.c_int()
         self._ck(self._lib.vp_frame_get_color(self._h, C.byref(m), C.byref(r)))
         return m.value, r.value
+
+    def set_raw(self, bits=0, shift=0, black=0, gains=(256, 256, 256), ccm=None, lut=None):
+        """vp_frame_set_raw: the setting of LATER uploads of the Bayer formats -- bits: the significant bits (0: the container's width), shift: right
+        shift of every sample, black: level subtracted behind it, gains: Q8 in R, G, B order, ccm: None or nine Q10 integers (rows and columns R, G, B),
+        lut: None or 256 / 1024 / 4096 uint8 entries (copied at the call).  The arithmetic: include/vp_hip.h."""
+        r = Raw()
+        r.bits, r.shift, r.black = int(bits), int(shift), int(black)
+        r.gains[:] = [int(g) for g in gains]
+        r.ccm_on = 0 if ccm is None else 1
+        r.ccm[:] = [0] * 9 if ccm is None else [int(v) for v in np.asarray(ccm).reshape(9)]
+        table = None if lut is None else np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1)
+        r.lut, r.lut_len = (None, 0) if table is None else (table.ctypes.data, int(table.size))
+        self._ck(self._lib.vp_frame_set_raw(self._h, C.byref(r)))
+
+    def get_raw(self):
+        """the setting in force as a dict (bits, shift, black, gains, ccm: None when off, lut_len: 0 when no LUT is installed)"""
+        r = Raw()
+        self._ck(self._lib.vp_frame_get_raw(self._h, C.byref(r)))
+        return {"bits": r.bits, "shift": r.shift, "black": r.black, "gains": tuple(r.gains[:]), "ccm": tuple(r.ccm[:]) if r.ccm_on else None, "lut_len": r.lut_len}
 
     def set_rectify(self, K, dist=None, H=None, out_hw=None, mode="two_pass"):
         """vp_frame_set_rectify: LATER uploads are undistorted (K 3x3, dist = (k1, k2, p1, p2, k3)) and warped by the homography H (source -> destination,

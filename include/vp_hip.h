@@ -392,10 +392,45 @@ int vp_timer_end(vp_engine* e, float* elapsed_ms);                             /
  *     upload(A); vp_upload_from_frame(e1, f, ..); vp_enqueue(e1); upload(B); vp_upload_from_frame(e2, f, ..); vp_enqueue(e2);   e1 sees A, e2 sees B.
  * THREADING.  One thread uploads; any number of threads consume concurrently, each on its own engine / detector.  An upload CONCURRENT with a
  * consumer call on the same vp_frame is the host's race to avoid: use two frames, ping-pong, as the reference's DoubleFrameBuffer does
- * (INTEGRATION.md "One camera frame, several networks").  A frame must outlive the passes that consume it.  No process-wide state. */
+ * (INTEGRATION.md "One camera frame, several networks").  A frame must outlive the passes that consume it.  No process-wide state.
+ *
+ * RAW BAYER, P010 AND 16-BIT GREY (upload only: vp_frame_upload / vp_frame_upload_device take them, vp_canvas_fetch* and vp_canvas_layout* refuse them
+ * as unknown formats).  GMSL / MIPI sensors deliver raw Bayer, 8 bits or 10 / 12 bits in 16-bit words; HEVC Main10 and AV1 10-bit decoders deliver P010
+ * surfaces; thermal and mono sensors 16-bit grey.  16-bit samples are little-endian words.
+ *   VP_FRAME_BAYER_<order>8 / _<order>16: 1 plane, rows of w bytes / 2 w bytes.  The four letters name the 2x2 cell at (row 0, column 0) in reading
+ *     order: RGGB means row 0 is R G and row 1 is G B.
+ *   VP_FRAME_P010: 2 planes; plane 0 holds Y as 16-bit words in rows of 2 w bytes, plane 1 interleaved U V words in rows of 2 w bytes, h / 2 rows.
+ *   VP_FRAME_GRAY16: 1 plane, rows of 2 w bytes.
+ * VP_ERR_ARG (with text; a refused call changes nothing): odd w or h for P010 and every Bayer format, h or w below 2, a stride below the row's bytes, a
+ * wrong n_planes, for the 16-bit formats an odd stride or an odd plane address, a raw setting that does not fit the format (below).
+ * P010 and GRAY16 narrow every 16-bit sample first, x8 = min(255, (s + 128) >> 8) (samples are MSB-aligned, as P010, P012 and P016 all are); P010 is
+ * then NV12's arithmetic on (Y8, U8, V8) to the bit, the colour standard of vp_frame_set_color included, and GRAY16 is GRAY8's on the narrowed sample.
+ * (A full 10-bit matrix form would overflow the 32-bit form the YUV definition rests on; narrowing first keeps ONE definition.)
+ * THE RAW DEFINITION.  vp_frame_set_raw(f, &r) holds for LATER uploads of the Bayer formats and touches no other format.  Let B be the significant
+ * bits (r.bits, or with r.bits = 0 the container's width, 8 or 16) and M = 2^B - 1.  Every sample s is processed by the colour c of its CFA site, all
+ * in 32-bit integer arithmetic:
+ *   1. linearise       v = max(0, min(s >> shift, M) - black)
+ *   2. white balance   v = min(M, (v * gains[c] + 128) >> 8)                    gains in Q8, order R, G, B
+ *   3. bilinear demosaic at B bits: at a site of colour c, channel c is v; at an R or B site, G = (N + S + W + E + 2) >> 2 and the opposite colour is
+ *      (NW + NE + SW + SE + 2) >> 2; at a G site, the colour of its horizontal neighbours is (W + E + 1) >> 1 and the other colour (N + S + 1) >> 1.
+ *      Borders mirror without repeating the edge, index -1 -> 1 and n -> n - 2: CFA parity is kept, so every average takes same-colour samples only.
+ *   4. optional matrix o_i = clamp((sum_j ccm[3 i + j] * x_j + 512) >> 10, 0, M)     Q10, rows and columns in R, G, B order
+ *   5. tone            with a LUT: out8 = lut[x >> (B - min(B, 12))];  without: out8 = x for B = 8, else min(255, (x + (1 << (B - 9))) >> (B - 8))
+ *   6. store B, G, R.
+ * 65535 * 16383 + 128 < 2^31 and 3 * 8191 * 65535 + 512 < 2^31, so nothing overflows.  This IS the definition (tests/raw_cases.py restates it in numpy);
+ * like every sibling conversion it is not pinned against OpenCV.  A picture that is constant per channel comes back exact at every pixel, borders
+ * included.
+ * vp_raw defaults (vp_frame_set_raw(f, NULL)): bits 0, shift 0, black 0, gains {256, 256, 256}, ccm_on 0, no LUT.  The LUT is copied at the call.
+ * VP_ERR_ARG at set (nothing changes): bits not in {0, 8, 10, 12, 14, 16}, shift outside 0 .. 8, black < 0, a gain outside 0 .. 16383, ccm_on with any
+ * |ccm[i]| > 8191, lut without lut_len or lut_len without lut, lut_len not in {256, 1024, 4096}.  VP_ERR_ARG at the upload, where B is known: bits == 8
+ * with a 16-bit format, bits > 8 with an 8-bit format, black > M, lut_len != 2^min(B, 12). */
 typedef struct vp_frame vp_frame;
 enum vp_frame_format { VP_FRAME_BGR8 = 0, VP_FRAME_RGB8 = 1, VP_FRAME_BGRA8 = 2, VP_FRAME_RGBA8 = 3, VP_FRAME_GRAY8 = 4,
-                       VP_FRAME_NV12 = 5, VP_FRAME_YUY2 = 6, VP_FRAME_UYVY = 7, VP_FRAME_I420 = 16, VP_FRAME_YV12 = 17, VP_FRAME_NV21 = 18 };
+                       VP_FRAME_NV12 = 5, VP_FRAME_YUY2 = 6, VP_FRAME_UYVY = 7, VP_FRAME_I420 = 16, VP_FRAME_YV12 = 17, VP_FRAME_NV21 = 18,
+                       VP_FRAME_GRAY16 = 20, VP_FRAME_P010 = 21,      /* 8 .. 15 and 19 are not used */
+                       VP_FRAME_BAYER_RGGB8 = 32, VP_FRAME_BAYER_GRBG8 = 33, VP_FRAME_BAYER_GBRG8 = 34, VP_FRAME_BAYER_BGGR8 = 35,
+                       VP_FRAME_BAYER_RGGB16 = 36, VP_FRAME_BAYER_GRBG16 = 37, VP_FRAME_BAYER_GBRG16 = 38, VP_FRAME_BAYER_BGGR16 = 39 };
+typedef struct vp_raw { int bits, shift, black; int gains[3]; int ccm_on; int ccm[9]; const uint8_t* lut; int lut_len; } vp_raw;
 enum vp_color_matrix { VP_COLOR_BT601 = 0, VP_COLOR_BT709 = 1 };
 enum vp_color_range { VP_COLOR_RANGE_LIMITED = 0, VP_COLOR_RANGE_FULL = 1 };
 enum vp_chroma_mode { VP_CHROMA_EVEN = 0, VP_CHROMA_MEAN = 1 };
@@ -406,6 +441,8 @@ int vp_frame_upload(vp_frame* f, int format, const uint8_t* const* planes, const
 int vp_frame_upload_device(vp_frame* f, int format, const void* const* dev_planes, const int* strides, int n_planes, int h, int w, void* producer_stream);
 int vp_frame_set_color(vp_frame* f, int matrix, int range);              /* applies to later uploads */
 int vp_frame_get_color(const vp_frame* f, int* matrix, int* range);
+int vp_frame_set_raw(vp_frame* f, const vp_raw* r);                      /* NULL: defaults; applies to LATER uploads of the Bayer formats, like vp_frame_set_color */
+int vp_frame_get_raw(const vp_frame* f, vp_raw* out);                    /* lut comes back NULL; lut_len tells whether one is installed */
 int vp_frame_sync(vp_frame* f);                                          /* waits for the frame's own stream (upload + conversion) */
 int vp_frame_dims(const vp_frame* f, int* h, int* w);                    /* geometry of the last upload; VP_ERR_STATE before it (vp_frame_hw is the engine's) */
 int vp_frame_fetch_bgr8(vp_frame* f, uint8_t* dst, int dst_stride);      /* the converted image, synchronous (tests, hosts that still want a cv::Mat) */

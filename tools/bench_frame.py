@@ -22,7 +22,11 @@ The device time per upload is taken behind a GATE instead: the first upload of a
 of matrix products, the host queues N uploads while the frame's stream waits for that stream's event, and the host clock runs from the gate's
 completion to vp_frame_sync -- the device then runs the N uploads back to back, and the quotient holds no host time (the tool checks that the gate
 was still closed when the last upload was queued).  Bytes of the passes, from shapes: source picture read + map read (8 bytes an entry) + picture
-written."""
+written.
+
+python tools/bench_frame.py --raw: the conversion of the upload-only formats next to NV12 in one run.  One 1920 x 1080 frame from device planes behind the
+same gate: NV12 (the yardstick), RGGB8, RGGB12 in 16-bit words under the default raw setting and under black + gains + ccm + a 4096-entry LUT, P010 and
+GRAY16; device time per upload, the bytes moved (source planes + 3 bytes a pixel) and the resulting GB/s.  Recorded in profiles/frame_raw.txt."""
 import json
 import os
 import sys
@@ -84,6 +88,41 @@ def convert_leg(h=720, w=1280, warm=50, timed=500):
     print(json.dumps(res, indent=1))
 
 
+class Gate:
+    """tens of milliseconds of matrix products on a producer stream: the frame's stream waits behind its event while the host queues uploads"""
+
+    def __init__(self, matmuls=6):
+        self.stream = torch.cuda.Stream()
+        self.a = torch.randn(8192, 8192, device="cuda")
+        self.matmuls = matmuls
+        torch.cuda.synchronize()
+        self.close()
+        self.stream.synchronize()
+
+    def close(self):
+        with torch.cuda.stream(self.stream):
+            for _ in range(self.matmuls):
+                self.a @ self.a
+
+    def timed_uploads(self, f, ptrs, strides, fmt, h, w, rounds, queued):
+        """per round: (host clock from the gate's completion to vp_frame_sync) / uploads and host time per upload call, in us; whether the gate was still
+        closed when the last upload was queued in every round"""
+        t, enq, held = [], [], True
+        for _ in range(rounds):
+            self.close()
+            t0 = time.perf_counter()
+            f.upload_device(ptrs, strides, fmt, h, w, producer_stream=self.stream.cuda_stream)
+            for _ in range(queued - 1):
+                f.upload_device(ptrs, strides, fmt, h, w)
+            enq.append((time.perf_counter() - t0) * 1e6 / queued)
+            held = held and not self.stream.query()
+            self.stream.synchronize()
+            t1 = time.perf_counter()
+            f.sync()
+            t.append((time.perf_counter() - t1) * 1e6 / queued)
+        return t, enq, held
+
+
 def rectify_leg(h=1080, w=1920, out_hw=(512, 1024), rounds=5, queued=300, gate_matmuls=6):
     K = np.array([[1400.0, 0.0, 960.0], [0.0, 1400.0, 540.0], [0.0, 0.0, 1.0]])
     dist = (-0.08, 0.01, 0.0005, -0.0003, 0.0)
@@ -92,17 +131,7 @@ def rectify_leg(h=1080, w=1920, out_hw=(512, 1024), rounds=5, queued=300, gate_m
     bgr = synthetic.synthetic_frame(h, w, 21)
     nv12, _ = yuv_planes(bgr)
     dev = {"nv12": [torch.from_numpy(p).cuda() for p in nv12], "bgr8": [torch.from_numpy(bgr.reshape(h, 3 * w)).cuda()]}
-    gate_stream = torch.cuda.Stream()
-    a = torch.randn(8192, 8192, device="cuda")
-    torch.cuda.synchronize()
-
-    def close_gate():   # tens of milliseconds of work on the producer stream: the frame's stream waits behind it while the host queues the uploads
-        with torch.cuda.stream(gate_stream):
-            for _ in range(gate_matmuls):
-                a @ a
-
-    close_gate()
-    gate_stream.synchronize()
+    gate = Gate(gate_matmuls)
     oh, ow = out_hw
     raw, out = 3 * h * w, 3 * oh * ow
     pass_bytes = {"off": 0, "two_pass": (raw + 8 * h * w + raw) + (raw + 8 * oh * ow + out), "one_pass": raw + 8 * oh * ow + out}
@@ -123,19 +152,7 @@ def rectify_leg(h=1080, w=1920, out_hw=(512, 1024), rounds=5, queued=300, gate_m
             for _ in range(20):   # the maps are built in the first of these
                 f.upload_device(ptrs, strides, fmt, h, w)
             f.sync()
-            t, enq, held = [], [], True
-            for _ in range(rounds):
-                close_gate()
-                t0 = time.perf_counter()
-                f.upload_device(ptrs, strides, fmt, h, w, producer_stream=gate_stream.cuda_stream)
-                for _ in range(queued - 1):
-                    f.upload_device(ptrs, strides, fmt, h, w)
-                enq.append((time.perf_counter() - t0) * 1e6 / queued)
-                held = held and not gate_stream.query()
-                gate_stream.synchronize()
-                t1 = time.perf_counter()
-                f.sync()
-                t.append((time.perf_counter() - t1) * 1e6 / queued)
+            t, enq, held = gate.timed_uploads(f, ptrs, strides, fmt, h, w, rounds, queued)
             us = float(np.median(t))
             rec = {"us_per_upload": round(us, 2), "min": round(min(t), 2), "max": round(max(t), 2), "gate_held": held, "enqueue_us": round(float(np.median(enq)), 2),
                    "picture_hw": list(f.hw())}
@@ -148,6 +165,52 @@ def rectify_leg(h=1080, w=1920, out_hw=(512, 1024), rounds=5, queued=300, gate_m
     f.close()
     print(json.dumps(res, indent=1))
 
+
+def raw_leg(h=1080, w=1920, rounds=5, queued=300):
+    def mosaic(rgb):   # RGGB
+        raw = rgb[:, :, 1].copy()
+        raw[0::2, 0::2] = rgb[0::2, 0::2, 0]
+        raw[1::2, 1::2] = rgb[1::2, 1::2, 2]
+        return raw
+
+    bgr = synthetic.synthetic_frame(h, w, 21)
+    nv12, _ = yuv_planes(bgr)
+    raw8 = mosaic(bgr[:, :, ::-1])
+    raw12 = (raw8.astype(np.uint16) << 4) | (raw8 >> 4)                  # 12 significant bits in 16-bit words
+    p010 = [p.astype(np.uint16) << 8 for p in nv12]                       # MSB-aligned
+    n = np.arange(4096) / 4095.0
+    full = {"bits": 12, "black": 256, "gains": (520, 256, 410), "ccm": (1434, -307, -103, -205, 1331, -102, 51, -410, 1383),
+            "lut": np.round(255.0 * n ** (1 / 2.2)).astype(np.uint8)}
+    # (leg, format, planes, raw setting, source bytes a pixel)
+    legs = (("nv12", "nv12", nv12, None, 1.5), ("rggb8", "bayer_rggb8", [raw8], {}, 1.0), ("rggb12", "bayer_rggb16", [raw12], {"bits": 12}, 2.0),
+            ("rggb12_black_gains_ccm_lut", "bayer_rggb16", [raw12], full, 2.0), ("p010", "p010", p010, None, 3.0), ("gray16", "gray16", [p010[0]], None, 2.0))
+    gate = Gate()
+    res = {"library": lib.version(),
+           "protocol": f"vp_frame_upload_device of one {w} x {h} frame from device planes; per leg {rounds} rounds; a round queues {queued} uploads while the frame's "
+                       "stream waits for the producer stream's event behind a gate of matrix products, so the device runs them back to back; us_per_upload = (host "
+                       "clock from the gate's completion to vp_frame_sync) / uploads, median, min and max of the rounds; gate_held = the gate was still closed when "
+                       "the last upload was queued in every round; bytes = source planes read + 3 bytes a pixel written, from shapes; GBps = bytes / us_per_upload"}
+    f = lib.Frame()
+    for leg, fmt, planes, setting, src_px in legs:
+        dev = [torch.from_numpy(np.ascontiguousarray(p).view(np.uint8).reshape(p.shape[0], -1)).cuda() for p in planes]
+        ptrs, strides = [p.data_ptr() for p in dev], [p.stride(0) for p in dev]
+        if setting is not None:
+            f.set_raw(**setting)
+        for _ in range(20):
+            f.upload_device(ptrs, strides, fmt, h, w)
+        f.sync()
+        t, enq, held = gate.timed_uploads(f, ptrs, strides, fmt, h, w, rounds, queued)
+        us = float(np.median(t))
+        moved = int((src_px + 3.0) * h * w)
+        res[leg] = {"us_per_upload": round(us, 2), "min": round(min(t), 2), "max": round(max(t), 2), "gate_held": held, "enqueue_us": round(float(np.median(enq)), 2),
+                    "bytes": moved, "GBps": round(moved / (us * 1e-6) / 1e9, 1)}
+    f.close()
+    print(json.dumps(res, indent=1))
+
+
+if "--raw" in sys.argv[1:]:
+    raw_leg()
+    sys.exit(0)
 
 if "--rectify" in sys.argv[1:]:
     rectify_leg()
