@@ -390,6 +390,7 @@ class Engine {
   int frame_h_ = 0, frame_w_ = 0, frame_stride_ = 0;
   SourceRegion src_region_;
   friend class Canvas;   // reads the last mask / logits on the device and orders its stream against this engine's
+  friend class Metric;   // reads the last logits on the device, ordered the same way
   int* d_xtab_ = nullptr;
   int* d_ytab_ = nullptr;
   int tab_h_ = 0, tab_w_ = 0;
@@ -553,6 +554,58 @@ class Canvas {
   size_t h_umask_cap_ = 0;
   int umask_slot_ = 0;
   hipEvent_t umask_ev_[2] = {nullptr, nullptr};
+};
+
+// vp_metric (include/vp_hip.h; handle: vp_handle.hpp; kernels: kernels_misc.hip metric_*): the validation scores of the segmentation and depth trainers,
+// one MetricRecord per frame in a device array of max_frames records.  An add_* call reads an engine's device-resident logits behind its pass (the
+// canvas's ordering: wait_for / release_to), or a caller's tensors, queues the kernels on the metric's own stream and returns; fetch() is the one
+// synchronisation.  Host waits besides it: a scratch or staging buffer that has to grow (once per geometry) and a pinned slot still being read by the
+// copy queued two calls earlier.  Owns its stream and buffers.  One thread drives it.
+class Metric {
+ public:
+  Metric(int gpu, int max_frames);
+  ~Metric();
+  Metric(const Metric&) = delete;
+  Metric& operator=(const Metric&) = delete;
+  void reset();
+  // gt: u8 [h][w] of the engine's output size; gt_form 0 (class index) or 1 (bit c = plane c)
+  void add_seg(Engine& e, const uint8_t* gt, bool gt_on_device, int gt_form);
+  void add_depth(Engine& e, const float* gt, bool gt_on_device);
+  void add_seg_pair(Engine& e, Engine& ref);
+  void add_depth_pair(Engine& e, Engine& ref);
+  void add_seg_logits(const float* logits, bool on_device, int c, int h, int w, const uint8_t* gt, bool gt_on_device, int gt_form);
+  void add_depth_plane(const float* pred, bool pred_on_device, const float* gt, bool gt_on_device, int h, int w);
+  int frames() const { return frames_; }
+  int max_frames() const { return max_frames_; }
+  void fetch(MetricRecord* out, int count);   // records [0, count), synchronous
+  int gpu() const { return gpu_; }
+
+ private:
+  struct Stage {   // a caller's pageable array: copied into one of two pinned slots before the call returns, then one H2D into `d`
+    uint8_t* h = nullptr;
+    size_t hcap = 0;
+    uint8_t* d = nullptr;
+    size_t dcap = 0;
+    int slot = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  };
+  void release();
+  template <class T>
+  void grow(T*& p, size_t& cap, size_t bytes);
+  const void* stage_host(Stage& s, const void* src, size_t bytes);
+  const Engine& source_of(Engine& e, const char* who, bool depth) const;
+  void wait_for(Engine& e, hipEvent_t ev);
+  void release_to(Engine& e, hipEvent_t ev);
+  MetricRecord* next_record(const char* who);
+  void seg(const float* d_logits, const float* d_ref, const uint8_t* d_gt, int c, int h, int w, int gt_form, MetricRecord* rec);
+  void depth(const float* d_pred, const float* d_gt, int h, int w, MetricRecord* rec);
+  int gpu_, max_frames_, frames_ = 0;
+  hipStream_t stream_ = nullptr;
+  hipEvent_t ev_src_[2] = {nullptr, nullptr}, ev_read_[2] = {nullptr, nullptr};
+  MetricRecord* d_records_ = nullptr;
+  Stage stage_[2];   // [0] the prediction, [1] the ground truth
+  uint8_t* d_scratch_ = nullptr;   // the depth chain's: see depth()
+  size_t scratch_cap_ = 0;
 };
 
 #define VP_HIP_CHECK(expr)                                                                                   \

@@ -1135,6 +1135,245 @@ void Canvas::fetch_picture(const uint8_t* d_bgr, int pitch, int h, int w, int fo
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
+// -------------------------------------------------------------------------------------------------- vp_metric
+Metric::Metric(int gpu, int max_frames) : gpu_(gpu), max_frames_(max_frames) {
+  if (max_frames < 1 || max_frames > (1 << 20)) throw std::invalid_argument("vp_metric_create: max_frames " + std::to_string(max_frames) + " (1 .. 1048576)");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  try {
+    VP_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    for (hipEvent_t* ev : {&ev_src_[0], &ev_src_[1], &ev_read_[0], &ev_read_[1], &stage_[0].ev[0], &stage_[0].ev[1], &stage_[1].ev[0], &stage_[1].ev[1]})
+      VP_HIP_CHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_records_), (size_t)max_frames * sizeof(MetricRecord)));
+    VP_HIP_CHECK(hipMemsetAsync(d_records_, 0, (size_t)max_frames * sizeof(MetricRecord), stream_));
+  } catch (...) {
+    release();
+    throw;
+  }
+}
+
+Metric::~Metric() { release(); }
+
+void Metric::release() {
+  (void)hipSetDevice(gpu_);
+  if (stream_) (void)hipStreamSynchronize(stream_);
+  for (hipEvent_t* ev : {&ev_src_[0], &ev_src_[1], &ev_read_[0], &ev_read_[1], &stage_[0].ev[0], &stage_[0].ev[1], &stage_[1].ev[0], &stage_[1].ev[1]}) {
+    if (*ev) (void)hipEventDestroy(*ev);
+    *ev = nullptr;
+  }
+  for (Stage& s : stage_) {
+    if (s.d) (void)hipFree(s.d);
+    if (s.h) (void)hipHostFree(s.h);
+    s.d = s.h = nullptr;
+    s.dcap = s.hcap = 0;
+  }
+  if (d_records_) (void)hipFree(d_records_);
+  if (d_scratch_) (void)hipFree(d_scratch_);
+  d_records_ = nullptr;
+  d_scratch_ = nullptr;
+  scratch_cap_ = 0;
+  if (stream_) (void)hipStreamDestroy(stream_);
+  stream_ = nullptr;
+}
+
+// behind everything queued so far: the used records become zero again (the segmentation kernel adds into its record)
+void Metric::reset() {
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (frames_) VP_HIP_CHECK(hipMemsetAsync(d_records_, 0, (size_t)frames_ * sizeof(MetricRecord), stream_));
+  frames_ = 0;
+}
+
+// a device buffer that has to grow is freed only once the metric's own work has run
+template <class T>
+void Metric::grow(T*& p, size_t& cap, size_t bytes) {
+  if (bytes <= cap) return;
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  const size_t n = (bytes + 255) & ~(size_t)255;
+  VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), n));
+  cap = n;
+}
+
+// Canvas::stage_host's scheme, one Stage per argument
+const void* Metric::stage_host(Stage& s, const void* src, size_t n) {
+  grow(s.d, s.dcap, n);
+  if (n > s.hcap) {
+    VP_HIP_CHECK(hipStreamSynchronize(stream_));
+    if (s.h) (void)hipHostFree(s.h);
+    s.h = nullptr;
+    s.hcap = 0;
+    const size_t cap = (n + 255) & ~(size_t)255;
+    VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h), 2 * cap, hipHostMallocDefault));
+    s.hcap = cap;
+  }
+  s.slot ^= 1;
+  uint8_t* slot = s.h + (size_t)s.slot * s.hcap;
+  VP_HIP_CHECK(hipEventSynchronize(s.ev[s.slot]));   // the H2D that last read this slot, two calls ago
+  std::memcpy(slot, src, n);
+  VP_HIP_CHECK(hipMemcpyAsync(s.d, slot, n, hipMemcpyHostToDevice, stream_));
+  VP_HIP_CHECK(hipEventRecord(s.ev[s.slot], stream_));
+  return s.d;
+}
+
+// the refusals of the engine entries; the engine itself is the source (a head has logits of its own)
+const Engine& Metric::source_of(Engine& e, const char* who, bool depth) const {
+  const std::string me(who);
+  if (e.gpu_ != gpu_) throw std::invalid_argument(me + ": the engine lives on GPU " + std::to_string(e.gpu_) + ", the metric on GPU " + std::to_string(gpu_));
+  if (depth ? e.kind_ != 1 : (e.kind_ != 0 && e.kind_ != 2))
+    throw std::invalid_argument(me + (depth ? ": VP_SCENE3D engines only (plane 0 of its logits is the depth map)" : ": VP_SCENESEG and VP_DOMAINSEG engines only"));
+  if (e.frames_ > 1) throw std::invalid_argument(me + ": a batched encoder has no outputs of its own (score its per-camera heads)");
+  if (!e.have_outputs_) throw std::runtime_error("Inference has not been run yet");
+  if (!e.d_logits_ || (e.out_c_ != 1 && e.out_c_ != 3) || e.out_h_ < 1 || e.out_w_ < 1) throw std::invalid_argument(me + ": the engine has no logits of one or three planes");
+  return e;
+}
+
+void Metric::wait_for(Engine& e, hipEvent_t ev) {
+  VP_HIP_CHECK(hipEventRecord(ev, e.stream_));
+  VP_HIP_CHECK(hipStreamWaitEvent(stream_, ev, 0));
+}
+void Metric::release_to(Engine& e, hipEvent_t ev) {
+  VP_HIP_CHECK(hipEventRecord(ev, stream_));
+  VP_HIP_CHECK(hipStreamWaitEvent(e.stream_, ev, 0));
+}
+
+MetricRecord* Metric::next_record(const char* who) {
+  if (frames_ >= max_frames_) throw std::runtime_error(std::string(who) + ": the accumulator is full (" + std::to_string(max_frames_) + " frames; vp_metric_fetch, then vp_metric_reset)");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  return d_records_ + frames_;
+}
+
+void Metric::seg(const float* d_logits, const float* d_ref, const uint8_t* d_gt, int c, int h, int w, int gt_form, MetricRecord* rec) {
+  MetricSegParams q{};   // the record's counters are zero: the constructor and reset() leave every unused record so
+  q.logits = d_logits;
+  q.ref = d_ref;
+  q.gt = d_gt;
+  q.c = c;
+  q.gt_form = gt_form;
+  q.kind = c == 3 ? 0 : 2;   // VP_SCENESEG : VP_DOMAINSEG
+  q.n = (unsigned)h * (unsigned)w;
+  q.rec = rec;
+  VP_HIP_CHECK(launch_metric_seg_count(q, stream_));
+}
+
+void Metric::depth(const float* d_pred, const float* d_gt, int h, int w, MetricRecord* rec) {
+  const size_t n = (size_t)h * w, pe = metric_pooled_elems(h, w);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_a = up(4 * n), o_pool = o_a + up(4 * n), o_stat = o_pool + up(4 * pe), o_kept = o_stat + up(kMetricBlocks * sizeof(MetricStatPartial)),
+               o_edge = o_kept + up(kMetricBlocks * sizeof(MetricKeptPartial)), o_sel = o_edge + up(4 * kMetricBlocks * sizeof(double)), o_ssc = o_sel + 256, total = o_ssc + up(metric_select_scratch_bytes((unsigned)n));
+  grow(d_scratch_, scratch_cap_, total);
+  MetricDepthParams q{};
+  q.pred = d_pred;
+  q.gt = d_gt;
+  q.h = h;
+  q.w = w;
+  q.kind = 1;   // VP_SCENE3D
+  q.d = reinterpret_cast<float*>(d_scratch_);
+  q.a_bits = reinterpret_cast<unsigned*>(d_scratch_ + o_a);
+  q.pooled = reinterpret_cast<float*>(d_scratch_ + o_pool);
+  q.stat = reinterpret_cast<MetricStatPartial*>(d_scratch_ + o_stat);
+  q.kept = reinterpret_cast<MetricKeptPartial*>(d_scratch_ + o_kept);
+  q.edge = reinterpret_cast<double*>(d_scratch_ + o_edge);
+  q.sel = reinterpret_cast<unsigned*>(d_scratch_ + o_sel);
+  q.sel_scratch = reinterpret_cast<unsigned*>(d_scratch_ + o_ssc);
+  q.rec = rec;
+  VP_HIP_CHECK(launch_metric_depth(q, stream_));
+}
+
+static void metric_check_seg_args(const char* who, const void* logits, int c, int h, int w, const void* gt, int gt_form) {
+  const std::string me(who);
+  if (!logits || !gt) throw std::invalid_argument(me + ": null logits or null ground truth");
+  if (c != 1 && c != 3) throw std::invalid_argument(me + ": c " + std::to_string(c) + " (1: DomainSeg, 3: SceneSeg)");
+  if (h < 1 || w < 1 || (long long)h * w > (long long)kMetricMaxN) throw std::invalid_argument(me + ": h * w outside 1 .. 2^24");
+  if (gt_form != 0 && gt_form != 1) throw std::invalid_argument(me + ": gt_form " + std::to_string(gt_form) + " (VP_GT_LABEL, VP_GT_BITS)");
+}
+static void metric_check_depth_args(const char* who, const void* pred, const void* gt, int h, int w) {
+  const std::string me(who);
+  if (!pred || !gt) throw std::invalid_argument(me + ": null prediction or null ground truth");
+  if (h < 8 || w < 8) throw std::invalid_argument(me + ": a plane of " + std::to_string(h) + " x " + std::to_string(w) + " (the three 2x2 pools need 8 x 8 at least)");
+  if ((long long)h * w > (long long)kMetricMaxN) throw std::invalid_argument(me + ": h * w above 2^24");
+}
+
+void Metric::add_seg(Engine& e, const uint8_t* gt, bool gt_on_device, int gt_form) {
+  source_of(e, "vp_metric_add_seg", false);
+  metric_check_seg_args("vp_metric_add_seg", e.d_logits_, e.out_c_, e.out_h_, e.out_w_, gt, gt_form);
+  MetricRecord* rec = next_record("vp_metric_add_seg");
+  const uint8_t* d_gt = gt_on_device ? gt : static_cast<const uint8_t*>(stage_host(stage_[1], gt, (size_t)e.out_h_ * e.out_w_));
+  wait_for(e, ev_src_[0]);
+  seg(e.d_logits_, nullptr, d_gt, e.out_c_, e.out_h_, e.out_w_, gt_form, rec);
+  release_to(e, ev_read_[0]);
+  ++frames_;
+}
+
+void Metric::add_depth(Engine& e, const float* gt, bool gt_on_device) {
+  source_of(e, "vp_metric_add_depth", true);
+  metric_check_depth_args("vp_metric_add_depth", e.d_logits_, gt, e.out_h_, e.out_w_);
+  MetricRecord* rec = next_record("vp_metric_add_depth");
+  const float* d_gt = gt_on_device ? gt : static_cast<const float*>(stage_host(stage_[1], gt, sizeof(float) * (size_t)e.out_h_ * e.out_w_));
+  wait_for(e, ev_src_[0]);
+  depth(e.d_logits_, d_gt, e.out_h_, e.out_w_, rec);
+  release_to(e, ev_read_[0]);
+  ++frames_;
+}
+
+void Metric::add_seg_pair(Engine& e, Engine& ref) {
+  source_of(e, "vp_metric_add_seg_pair", false);
+  source_of(ref, "vp_metric_add_seg_pair", false);
+  if (e.kind_ != ref.kind_ || e.out_c_ != ref.out_c_ || e.out_h_ != ref.out_h_ || e.out_w_ != ref.out_w_)
+    throw std::invalid_argument("vp_metric_add_seg_pair: the two engines are of different kinds or output sizes");
+  metric_check_seg_args("vp_metric_add_seg_pair", e.d_logits_, e.out_c_, e.out_h_, e.out_w_, ref.d_logits_, 0);
+  MetricRecord* rec = next_record("vp_metric_add_seg_pair");
+  wait_for(e, ev_src_[0]);
+  if (&ref != &e) wait_for(ref, ev_src_[1]);
+  seg(e.d_logits_, ref.d_logits_, nullptr, e.out_c_, e.out_h_, e.out_w_, 0, rec);
+  release_to(e, ev_read_[0]);
+  if (&ref != &e) release_to(ref, ev_read_[1]);
+  ++frames_;
+}
+
+void Metric::add_depth_pair(Engine& e, Engine& ref) {
+  source_of(e, "vp_metric_add_depth_pair", true);
+  source_of(ref, "vp_metric_add_depth_pair", true);
+  if (e.out_h_ != ref.out_h_ || e.out_w_ != ref.out_w_) throw std::invalid_argument("vp_metric_add_depth_pair: the two engines are of different output sizes");
+  metric_check_depth_args("vp_metric_add_depth_pair", e.d_logits_, ref.d_logits_, e.out_h_, e.out_w_);
+  MetricRecord* rec = next_record("vp_metric_add_depth_pair");
+  wait_for(e, ev_src_[0]);
+  if (&ref != &e) wait_for(ref, ev_src_[1]);
+  depth(e.d_logits_, ref.d_logits_, e.out_h_, e.out_w_, rec);
+  release_to(e, ev_read_[0]);
+  if (&ref != &e) release_to(ref, ev_read_[1]);
+  ++frames_;
+}
+
+void Metric::add_seg_logits(const float* logits, bool on_device, int c, int h, int w, const uint8_t* gt, bool gt_on_device, int gt_form) {
+  metric_check_seg_args("vp_metric_add_seg_logits", logits, c, h, w, gt, gt_form);
+  MetricRecord* rec = next_record("vp_metric_add_seg_logits");
+  const size_t n = (size_t)h * w;
+  const float* d_logits = on_device ? logits : static_cast<const float*>(stage_host(stage_[0], logits, sizeof(float) * n * c));
+  const uint8_t* d_gt = gt_on_device ? gt : static_cast<const uint8_t*>(stage_host(stage_[1], gt, n));
+  if (reinterpret_cast<uintptr_t>(d_logits) & 3) throw std::invalid_argument("vp_metric_add_seg_logits: device logits not aligned to 4 bytes");
+  seg(d_logits, nullptr, d_gt, c, h, w, gt_form, rec);
+  ++frames_;
+}
+
+void Metric::add_depth_plane(const float* pred, bool pred_on_device, const float* gt, bool gt_on_device, int h, int w) {
+  metric_check_depth_args("vp_metric_add_depth_plane", pred, gt, h, w);
+  MetricRecord* rec = next_record("vp_metric_add_depth_plane");
+  const size_t bytes = sizeof(float) * (size_t)h * w;
+  const float* d_pred = pred_on_device ? pred : static_cast<const float*>(stage_host(stage_[0], pred, bytes));
+  const float* d_gt = gt_on_device ? gt : static_cast<const float*>(stage_host(stage_[1], gt, bytes));
+  if ((reinterpret_cast<uintptr_t>(d_pred) | reinterpret_cast<uintptr_t>(d_gt)) & 3) throw std::invalid_argument("vp_metric_add_depth_plane: device planes not aligned to 4 bytes");
+  depth(d_pred, d_gt, h, w, rec);
+  ++frames_;
+}
+
+void Metric::fetch(MetricRecord* out, int count) {
+  if (count < 0 || count > frames_ || (count > 0 && !out)) throw std::invalid_argument("vp_metric_fetch: more records than were added, or a null buffer");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (count) VP_HIP_CHECK(hipMemcpyAsync(out, d_records_, (size_t)count * sizeof(MetricRecord), hipMemcpyDeviceToHost, stream_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
 // -------------------------------------------------------------------------------------------------- timing
 void Engine::timer_begin() { VP_HIP_CHECK(hipEventRecord(ev0_, stream_)); }
 float Engine::timer_end() {

@@ -707,4 +707,67 @@ struct LaneRowsHeadParams {
 bool lane_rows_head_ok(const LaneRowsHeadParams& p);
 hipError_t launch_lane_rows_head(const LaneRowsHeadParams& p, hipStream_t st);
 
+// ---- vp_metric (include/vp_hip.h; kernels_misc.hip metric_*): the validation scores of the segmentation and depth trainers, one record per frame.
+// No kernel talks to another workgroup of its own launch: a workgroup writes its partial, and the NEXT launch folds the partials in index order (every
+// workgroup of it repeats the same fold), so a record has the same bits on every run.  Integer atomics only (LDS histograms, the ten u32 counters).
+// MetricRecord is vp_metric_frame's layout (vp_api.cpp checks it).
+struct MetricRecord {
+  int kind;
+  unsigned I[3], P[3], G[3];
+  unsigned nonfinite, n, kept;
+  float q_lo, q_hi, q, mae, mel;
+};
+constexpr int kMetricBlocks = 128;   // workgroups (of 256) of every partial-writing launch, at most
+constexpr unsigned kMetricMaxN = 1u << 24;
+// metric_seg_count_kernel: logits fp32 [c][n] (c 1 or 3); the ground truth is gt (u8 [n], gt_form 0: class index, 1: bit c = plane c) or, with gt null,
+// the class ref's logits [c][n] predict.  Adds into rec->I / P / G / nonfinite (zeroed by the caller) and stores rec->kind and rec->n.
+struct MetricSegParams {
+  const float* logits;
+  const float* ref;
+  const uint8_t* gt;
+  int c, gt_form, kind;
+  unsigned n;
+  MetricRecord* rec;
+};
+hipError_t launch_metric_seg_count(const MetricSegParams& p, hipStream_t st);
+// the depth chain's scratch, owned by the caller: D and the bits of |D| ([n] each), the three pooled scales of D one after the other ([n / 4 + n / 16 + n / 64]
+// at most), and the partials
+struct MetricStatPartial {
+  double sum[2];
+  float mn[2], mx[2];
+  unsigned bad[2];
+};
+struct MetricKeptPartial {
+  double sum;
+  unsigned long long count;
+};
+struct MetricDepthParams {
+  const float* pred;   // [h][w]
+  const float* gt;     // [h][w]
+  int h, w, kind;
+  float* d;            // [n]
+  unsigned* a_bits;    // [n]
+  float* pooled;       // scales 1 .. 3
+  MetricStatPartial* stat;   // [kMetricBlocks]
+  MetricKeptPartial* kept;   // [kMetricBlocks]
+  double* edge;              // [4][kMetricBlocks]
+  unsigned* sel;             // [2]: the bits of the order statistics lo and lo + 1
+  unsigned* sel_scratch;     // metric_select_scratch_bytes(h * w)
+  MetricRecord* rec;
+};
+size_t metric_pooled_elems(int h, int w);
+// the whole chain for one frame: stats, D and |D|, select, kept count and sum, the four edge sums, the record.  h, w >= 8, h * w <= kMetricMaxN.
+hipError_t launch_metric_depth(const MetricDepthParams& p, hipStream_t st);
+// ranks k0 and k1 of n u32 keys in ascending order: out[0], out[1].  Four 8-bit passes of per-workgroup LDS histograms, each folded by the launch behind it.
+size_t metric_select_scratch_bytes(unsigned n);
+hipError_t launch_metric_select(const unsigned* bits, unsigned n, unsigned k0, unsigned k1, unsigned* scratch, unsigned* out, hipStream_t st);
+// the rank pair of the 0.9 quantile with linear interpolation over n values and its weight: lo = floor(r), w = r - lo with r = fp32(0.9f * (n - 1))
+inline void metric_quantile_rank(unsigned n, unsigned* lo, unsigned* hi, float* w) {
+  const float r = 0.9f * (float)(n - 1);
+  const float f = (float)(unsigned)r;
+  *lo = (unsigned)r;
+  *hi = *lo + 1 < n ? *lo + 1 : n - 1;
+  *w = r - f;
+}
+
 }  // namespace vp

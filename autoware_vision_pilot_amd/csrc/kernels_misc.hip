@@ -1250,4 +1250,414 @@ hipError_t launch_act_to_nchw(const ActView& a, int Creal, float* dst, hipStream
   VP_LAUNCH(act_to_nchw_kernel, dim3(nblk((long long)a.H * a.W * Creal)), dim3(256), 0, st, a, Creal, dst, mul);
 }
 
+// ------------------------------------------------------------------------------------------ vp_metric
+// The validation scores of Models/training/scene_seg_trainer.py:206-244, domain_seg_trainer.py:236-252 and scene_3d_trainer.py:94-109, 159-210,
+// restated (kernels.hpp: the rules every kernel here follows).
+// calc_IoU_val's cascade: the first maximum for finite logits; a NaN fails every branch (3: no class)
+__device__ __forceinline__ int metric_class3(float a, float b, float c) { return (a >= b && a >= c) ? 0 : ((b >= a && b >= c) ? 1 : ((c >= a && c >= b) ? 2 : 3)); }
+__device__ __forceinline__ bool metric_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+// one pixel: pred 0 .. 2 or 3 (none), truth a mask of planes; cnt = I[3] P[3] G[3]
+__device__ __forceinline__ void metric_count(int pred, unsigned truth, unsigned* cnt) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const unsigned p = pred == k, g = (truth >> k) & 1u;
+    cnt[k] += p & g;
+    cnt[3 + k] += p;
+    cnt[6 + k] += g;
+  }
+}
+__device__ __forceinline__ unsigned metric_truth(unsigned v, int c, int gt_form) {
+  if (gt_form) return v & (c == 3 ? 7u : 1u);
+  return c == 3 ? (v < 3u ? 1u << v : 0u) : (v ? 1u : 0u);
+}
+__global__ __launch_bounds__(256) void metric_seg_count_kernel(const MetricSegParams p) {
+  __shared__ unsigned wave_cnt[4][10];
+  unsigned cnt[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) cnt[k] = 0;
+  const unsigned n = p.n;
+  const float* l0 = p.logits;
+  const float* r0 = p.ref;
+  // four pixels per step where every plane starts on a 16-byte boundary
+  const bool vec = !(n & 3u) && !((reinterpret_cast<uintptr_t>(l0) | reinterpret_cast<uintptr_t>(r0)) & 15) && !(reinterpret_cast<uintptr_t>(p.gt) & 3);
+  const unsigned nq = vec ? n >> 2 : 0u;
+  for (unsigned q = blockIdx.x * 256 + threadIdx.x; q < nq; q += gridDim.x * 256) {
+    int4 l[3], r[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      l[k].x = l[k].y = l[k].z = l[k].w = 0;
+      r[k] = l[k];
+      if (k < p.c) l[k] = *reinterpret_cast<const int4*>(l0 + (size_t)k * n + 4 * (size_t)q);
+      if (r0 && k < p.c) r[k] = *reinterpret_cast<const int4*>(r0 + (size_t)k * n + 4 * (size_t)q);
+    }
+    const unsigned gt4 = p.gt ? *reinterpret_cast<const unsigned*>(p.gt + 4 * (size_t)q) : 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float a[3], b[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        a[k] = __uint_as_float((unsigned)(j == 0 ? l[k].x : j == 1 ? l[k].y : j == 2 ? l[k].z : l[k].w));
+        b[k] = __uint_as_float((unsigned)(j == 0 ? r[k].x : j == 1 ? r[k].y : j == 2 ? r[k].z : r[k].w));
+      }
+      int pred;
+      unsigned truth;
+      if (p.c == 3) {
+        pred = metric_class3(a[0], a[1], a[2]);
+        cnt[9] += pred == 3;
+        const int rc = r0 ? metric_class3(b[0], b[1], b[2]) : 3;
+        truth = r0 ? (rc < 3 ? 1u << rc : 0u) : metric_truth((gt4 >> (8 * j)) & 255u, 3, p.gt_form);
+      } else {
+        pred = a[0] > 0.0f ? 0 : 3;
+        cnt[9] += a[0] != a[0];
+        truth = r0 ? (b[0] > 0.0f ? 1u : 0u) : metric_truth((gt4 >> (8 * j)) & 255u, 1, p.gt_form);
+      }
+      metric_count(pred, truth, cnt);
+    }
+  }
+  for (unsigned i = 4 * nq + blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    int pred;
+    unsigned truth;
+    if (p.c == 3) {
+      pred = metric_class3(l0[i], l0[(size_t)n + i], l0[2 * (size_t)n + i]);
+      cnt[9] += pred == 3;
+      const int rc = r0 ? metric_class3(r0[i], r0[(size_t)n + i], r0[2 * (size_t)n + i]) : 3;
+      truth = r0 ? (rc < 3 ? 1u << rc : 0u) : metric_truth(p.gt[i], 3, p.gt_form);
+    } else {
+      pred = l0[i] > 0.0f ? 0 : 3;
+      cnt[9] += l0[i] != l0[i];
+      truth = r0 ? (r0[i] > 0.0f ? 1u : 0u) : metric_truth(p.gt[i], 1, p.gt_form);
+    }
+    metric_count(pred, truth, cnt);
+  }
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt[k] += __shfl_xor(cnt[k], o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 10; ++k) wave_cnt[threadIdx.x >> 6][k] = cnt[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 10) {   // one integer atomic per workgroup per counter: the sum does not depend on the order
+    const unsigned v = wave_cnt[0][threadIdx.x] + wave_cnt[1][threadIdx.x] + wave_cnt[2][threadIdx.x] + wave_cnt[3][threadIdx.x];
+    if (v) atomicAdd(&p.rec->I[0] + threadIdx.x, v);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 10) {
+    p.rec->kind = p.kind;
+    p.rec->n = n;
+  }
+}
+
+// one value per work-item of a 256-thread workgroup combined in a fixed tree (the same bits on every run); every work-item gets the result
+template <class T, class Op>
+__device__ __forceinline__ T metric_block_reduce(T v, T* lds, Op op) {
+  lds[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) lds[threadIdx.x] = op(lds[threadIdx.x], lds[threadIdx.x + o]);
+    __syncthreads();
+  }
+  const T r = lds[0];
+  __syncthreads();
+  return r;
+}
+struct MetricStat {   // one plane's sum, extremes and non-finite count
+  double sum;
+  float mn, mx;
+  unsigned bad;
+};
+struct MetricStatJoin {
+  __device__ __forceinline__ MetricStat operator()(const MetricStat& a, const MetricStat& b) const {
+    return MetricStat{a.sum + b.sum, b.mn < a.mn ? b.mn : a.mn, b.mx > a.mx ? b.mx : a.mx, a.bad + b.bad};
+  }
+};
+struct MetricSumJoin {
+  __device__ __forceinline__ double operator()(double a, double b) const { return a + b; }
+};
+// 1. min, max, sum and non-finite count of both planes: one partial per workgroup
+__global__ __launch_bounds__(256) void metric_depth_stats_kernel(const MetricDepthParams p) {
+  __shared__ MetricStat lds[256];
+  const unsigned n = (unsigned)p.h * (unsigned)p.w;
+  MetricStatPartial out;
+  for (int j = 0; j < 2; ++j) {
+    const float* src = j ? p.gt : p.pred;
+    MetricStat s{0.0, INFINITY, -INFINITY, 0u};
+    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+      const float v = src[i];
+      if (metric_finite(v)) {
+        s.sum += (double)v;
+        s.mn = v < s.mn ? v : s.mn;
+        s.mx = v > s.mx ? v : s.mx;
+      } else {
+        ++s.bad;
+      }
+    }
+    s = metric_block_reduce(s, lds, MetricStatJoin());
+    out.sum[j] = s.sum;
+    out.mn[j] = s.mn;
+    out.mx[j] = s.mx;
+    out.bad[j] = s.bad;
+  }
+  if (threadIdx.x == 0) p.stat[blockIdx.x] = out;
+}
+// the fold of the stats partials (nb <= 256, partial b through work-item b, the fixed tree): ssi(t) = (t - mn) / den with den = max - mean, all fp32
+// (get_ssi_nom_tensor); bad: non-finite inputs.  Called by the whole workgroup.
+struct MetricNorm {
+  float mn[2], den[2];
+  unsigned bad;
+};
+__device__ __forceinline__ MetricNorm metric_fold_stats(const MetricStatPartial* stat, unsigned nb, unsigned n, MetricStat* lds) {
+  MetricNorm r;
+  r.bad = 0;
+  for (int j = 0; j < 2; ++j) {
+    MetricStat s{0.0, INFINITY, -INFINITY, 0u};
+    if (threadIdx.x < nb) s = MetricStat{stat[threadIdx.x].sum[j], stat[threadIdx.x].mn[j], stat[threadIdx.x].mx[j], stat[threadIdx.x].bad[j]};
+    s = metric_block_reduce(s, lds, MetricStatJoin());
+    r.bad += s.bad;
+    r.mn[j] = s.mn;
+    r.den[j] = __fsub_rn(s.mx, (float)(s.sum / (double)n));
+  }
+  return r;
+}
+// 2. D = ssi(pred) - ssi(gt) and the bits of |D|
+__global__ __launch_bounds__(256) void metric_depth_diff_kernel(const MetricDepthParams p, unsigned nb_stat) {
+  __shared__ MetricStat lds[256];
+  const unsigned n = (unsigned)p.h * (unsigned)p.w;
+  const MetricNorm nm = metric_fold_stats(p.stat, nb_stat, n, lds);
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const float a = __fdiv_rn(__fsub_rn(p.pred[i], nm.mn[0]), nm.den[0]);
+    const float b = __fdiv_rn(__fsub_rn(p.gt[i], nm.mn[1]), nm.den[1]);
+    const float d = __fsub_rn(a, b);
+    p.d[i] = d;
+    p.a_bits[i] = __float_as_uint(d) & 0x7FFFFFFFu;
+  }
+}
+// 3. radix select on u32 keys for two ranks at once, most significant byte first.  Launch `pass` (0 .. 3) first folds the histograms launch pass - 1
+// left (every workgroup repeats that fold; workgroup 0 stores the state for the launch after it), then counts byte `pass` of the keys that carry the
+// chosen prefix into an LDS histogram and stores it as its partial; launch 4 (one workgroup) folds the last histograms and stores the two keys.
+// A work-item counts runs of equal digits before it touches LDS: the keys of |D| share their exponent byte almost everywhere.
+// scratch: state [5][4] (prefix0, prefix1, rest0, rest1 ahead of pass s), then partial [4 passes][nb][2][256].
+constexpr int kMetricSelState = 32;   // words in front of the partials
+__global__ __launch_bounds__(256) void metric_select_pass_kernel(const unsigned* bits, unsigned n, unsigned k0, unsigned k1, int pass, unsigned nb, unsigned* scratch,
+                                                                 unsigned* out) {
+  __shared__ unsigned hist[2][256];
+  __shared__ unsigned scan[2][256];
+  __shared__ unsigned st[4];
+  const unsigned t = threadIdx.x;
+  unsigned* state = scratch;
+  unsigned* partial = scratch + kMetricSelState;
+  if (t == 0) {
+    st[0] = pass >= 2 ? state[4 * (pass - 1)] : 0u;
+    st[1] = pass >= 2 ? state[4 * (pass - 1) + 1] : 0u;
+    st[2] = pass >= 2 ? state[4 * (pass - 1) + 2] : k0;
+    st[3] = pass >= 2 ? state[4 * (pass - 1) + 3] : k1;
+  }
+  __syncthreads();
+  if (pass >= 1) {   // the fold of pass - 1: column sums in workgroup order, an inclusive scan, the bin that holds the rank
+    const bool both = st[0] != st[1];
+    const unsigned* src = partial + (size_t)(pass - 1) * nb * 512;
+    unsigned h[2] = {0u, 0u};
+    for (unsigned b = 0; b < nb; ++b) {
+      h[0] += src[(size_t)b * 512 + t];
+      if (both) h[1] += src[(size_t)b * 512 + 256 + t];
+    }
+    if (!both) h[1] = h[0];
+    scan[0][t] = h[0];
+    scan[1][t] = h[1];
+    __syncthreads();
+    for (unsigned o = 1; o < 256; o <<= 1) {
+      const unsigned v0 = t >= o ? scan[0][t - o] : 0u, v1 = t >= o ? scan[1][t - o] : 0u;
+      __syncthreads();
+      scan[0][t] += v0;
+      scan[1][t] += v1;
+      __syncthreads();
+    }
+    const unsigned r0 = st[2], r1 = st[3], p0 = st[0], p1 = st[1];
+    const unsigned e0 = scan[0][t] - h[0], e1 = scan[1][t] - h[1];
+    __syncthreads();
+    if (h[0] && e0 <= r0 && r0 < e0 + h[0]) {   // exactly one work-item: the rank lies below the total
+      st[0] = (p0 << 8) | t;
+      st[2] = r0 - e0;
+    }
+    if (h[1] && e1 <= r1 && r1 < e1 + h[1]) {
+      st[1] = (p1 << 8) | t;
+      st[3] = r1 - e1;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && t < 4 && pass < 4) state[4 * pass + t] = st[t];
+  }
+  if (pass == 4) {
+    if (t < 2) out[t] = st[t];
+    return;
+  }
+  const int shift = 24 - 8 * pass;
+  hist[0][t] = 0;
+  hist[1][t] = 0;
+  __syncthreads();
+  const unsigned p0 = st[0], p1 = st[1];
+  const bool both = p0 != p1;   // one histogram serves both ranks while their prefixes agree
+  unsigned last = 0, run = 0;
+  for (unsigned i = blockIdx.x * 256 + t; i < n; i += gridDim.x * 256) {
+    const unsigned v = bits[i];
+    const unsigned hi = pass ? v >> (shift + 8) : 0u;
+    const unsigned key = (hi == p0 ? 256u : 0u) | ((both && hi == p1) ? 512u : 0u) | ((v >> shift) & 255u);
+    if (key == last) {
+      ++run;
+      continue;
+    }
+    if (run && (last & 256u)) atomicAdd(&hist[0][last & 255u], run);
+    if (run && (last & 512u)) atomicAdd(&hist[1][last & 255u], run);
+    last = key;
+    run = 1;
+  }
+  if (run && (last & 256u)) atomicAdd(&hist[0][last & 255u], run);
+  if (run && (last & 512u)) atomicAdd(&hist[1][last & 255u], run);
+  __syncthreads();
+  unsigned* dst = partial + ((size_t)pass * nb + blockIdx.x) * 512;
+  dst[t] = hist[0][t];
+  dst[256 + t] = hist[1][t];
+}
+// torch.quantile's interpolation (lerp): a + w (b - a) below w = 0.5, b - (b - a)(1 - w) from there on; fp32
+__device__ __forceinline__ float metric_quantile(float a, float b, float w) {
+  const float d = __fsub_rn(b, a);
+  return w < 0.5f ? __fadd_rn(a, __fmul_rn(w, d)) : __fsub_rn(b, __fmul_rn(d, __fsub_rn(1.0f, w)));
+}
+// 4a. the kept set {A < q}: count and sum (double) per workgroup
+__global__ __launch_bounds__(256) void metric_depth_kept_kernel(const MetricDepthParams p, float w) {
+  __shared__ double lds[256];
+  const unsigned n = (unsigned)p.h * (unsigned)p.w;
+  const float q = metric_quantile(__uint_as_float(p.sel[0]), __uint_as_float(p.sel[1]), w);
+  double s = 0.0, c = 0.0;
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const float a = __uint_as_float(p.a_bits[i]);
+    if (a < q) {
+      s += (double)a;
+      c += 1.0;
+    }
+  }
+  s = metric_block_reduce(s, lds, MetricSumJoin());
+  c = metric_block_reduce(c, lds, MetricSumJoin());   // counts below 2^24: exact
+  if (threadIdx.x == 0) p.kept[blockIdx.x] = MetricKeptPartial{s, (unsigned long long)c};
+}
+// 4b. one scale: sum of |Gx(src)| + |Gy(src)| (the 3x3 filters of scene_3d_trainer.py:96-106, zero padding 1) per workgroup, and the 2x2 mean pool of src
+// (stride 2, a trailing odd row / column dropped) into dst (null at the last scale)
+__device__ __forceinline__ float metric_at(const float* s, int h, int w, int y, int x) { return (y >= 0 && y < h && x >= 0 && x < w) ? s[(size_t)y * w + x] : 0.0f; }
+__global__ __launch_bounds__(256) void metric_depth_edge_kernel(const float* src, int h, int w, float* dst, double* partial) {
+  __shared__ double lds[256];
+  const unsigned n = (unsigned)h * (unsigned)w;
+  double s = 0.0;
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const int y = (int)(i / (unsigned)w), x = (int)(i % (unsigned)w);
+    const float a00 = metric_at(src, h, w, y - 1, x - 1), a01 = metric_at(src, h, w, y - 1, x), a02 = metric_at(src, h, w, y - 1, x + 1);
+    const float a10 = metric_at(src, h, w, y, x - 1), a12 = metric_at(src, h, w, y, x + 1);
+    const float a20 = metric_at(src, h, w, y + 1, x - 1), a21 = metric_at(src, h, w, y + 1, x), a22 = metric_at(src, h, w, y + 1, x + 1);
+    const float gx = __fadd_rn(__fmul_rn(0.125f, __fadd_rn(__fsub_rn(a00, a02), __fsub_rn(a20, a22))), __fmul_rn(0.25f, __fsub_rn(a10, a12)));
+    const float gy = __fadd_rn(__fmul_rn(0.125f, __fadd_rn(__fsub_rn(a00, a20), __fsub_rn(a02, a22))), __fmul_rn(0.25f, __fsub_rn(a01, a21)));
+    s += (double)__fadd_rn(fabsf(gx), fabsf(gy));
+  }
+  s = metric_block_reduce(s, lds, MetricSumJoin());
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+  if (!dst) return;
+  const int h2 = h >> 1, w2 = w >> 1;
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < (unsigned)h2 * (unsigned)w2; i += gridDim.x * 256) {
+    const float* r0 = src + (size_t)(2 * (i / (unsigned)w2)) * w + 2 * (i % (unsigned)w2);
+    dst[i] = __fmul_rn(0.25f, __fadd_rn(__fadd_rn(r0[0], r0[1]), __fadd_rn(r0[w], r0[w + 1])));
+  }
+}
+// 5. the record: the partials folded in the fixed tree, means as one fp32 division each (sums below 2^24 ulps of their terms are exact in the double)
+struct MetricFinishParams {
+  unsigned nb_stat, nb_kept, nb_edge[4], n_edge[4];
+  float w;
+};
+__global__ __launch_bounds__(256) void metric_depth_finish_kernel(const MetricDepthParams p, const MetricFinishParams f) {
+  __shared__ MetricStat lds_stat[256];
+  __shared__ double lds[256];
+  const unsigned n = (unsigned)p.h * (unsigned)p.w, t = threadIdx.x;
+  const MetricNorm nm = metric_fold_stats(p.stat, f.nb_stat, n, lds_stat);
+  const double ks = metric_block_reduce(t < f.nb_kept ? p.kept[t].sum : 0.0, lds, MetricSumJoin());
+  const double kc = metric_block_reduce(t < f.nb_kept ? (double)p.kept[t].count : 0.0, lds, MetricSumJoin());
+  float mel = 0.0f;
+  for (int s = 0; s < 4; ++s) {
+    const double es = metric_block_reduce(t < f.nb_edge[s] ? p.edge[s * kMetricBlocks + t] : 0.0, lds, MetricSumJoin());
+    mel = __fadd_rn(mel, __fdiv_rn((float)es, (float)f.n_edge[s]));
+  }
+  if (t != 0) return;
+  MetricRecord r;
+  r.kind = p.kind;
+  for (int k = 0; k < 3; ++k) r.I[k] = r.P[k] = r.G[k] = 0;
+  r.nonfinite = nm.bad;
+  r.n = n;
+  const float a = __uint_as_float(p.sel[0]), b = __uint_as_float(p.sel[1]);
+  const float nan = __uint_as_float(0x7FC00000u);
+  const bool bad = nm.bad != 0;
+  r.kept = bad ? 0u : (unsigned)kc;
+  r.q_lo = bad ? nan : a;
+  r.q_hi = bad ? nan : b;
+  r.q = bad ? nan : metric_quantile(a, b, f.w);
+  r.mae = bad ? nan : __fdiv_rn((float)ks, (float)kc);   // an empty kept set: 0 / 0, the reference's empty mean
+  r.mel = bad ? nan : __fmul_rn(mel, 0.25f);
+  *p.rec = r;
+}
+
+hipError_t launch_metric_seg_count(const MetricSegParams& p, hipStream_t st) {
+  if (!p.logits || !p.rec || (p.c != 1 && p.c != 3) || p.n < 1 || p.n > kMetricMaxN || (!p.gt && !p.ref) || (p.gt && p.ref) || (p.gt_form != 0 && p.gt_form != 1) ||
+      ((reinterpret_cast<uintptr_t>(p.logits) | reinterpret_cast<uintptr_t>(p.ref)) & 3))
+    return hipErrorInvalidValue;
+  const unsigned blocks = nblk(((long long)p.n + 3) / 4);
+  VP_LAUNCH(metric_seg_count_kernel, dim3(blocks < (unsigned)kMetricBlocks ? blocks : (unsigned)kMetricBlocks), dim3(256), 0, st, p);
+}
+static unsigned metric_select_blocks(unsigned n) {
+  const unsigned b = (n + 4095) / 4096;   // sixteen keys per work-item, then more
+  return b < (unsigned)kMetricBlocks ? b : (unsigned)kMetricBlocks;
+}
+size_t metric_select_scratch_bytes(unsigned n) { return sizeof(unsigned) * (kMetricSelState + (size_t)4 * metric_select_blocks(n) * 512); }
+hipError_t launch_metric_select(const unsigned* bits, unsigned n, unsigned k0, unsigned k1, unsigned* scratch, unsigned* out, hipStream_t st) {
+  if (!bits || !out || !scratch || n < 1 || n > kMetricMaxN || k0 >= n || k1 >= n) return hipErrorInvalidValue;
+  const unsigned nb = metric_select_blocks(n);
+  for (int pass = 0; pass < 4; ++pass) hipLaunchKernelGGL(metric_select_pass_kernel, dim3(nb), dim3(256), 0, st, bits, n, k0, k1, pass, nb, scratch, out);
+  VP_LAUNCH(metric_select_pass_kernel, dim3(1), dim3(256), 0, st, bits, n, k0, k1, 4, nb, scratch, out);
+}
+size_t metric_pooled_elems(int h, int w) {
+  size_t t = 0;
+  for (int s = 0; s < 3; ++s) {
+    h >>= 1;
+    w >>= 1;
+    t += (size_t)h * w;
+  }
+  return t;
+}
+static unsigned metric_blocks(size_t n) {
+  const size_t b = (n + 255) / 256;
+  return (unsigned)(b < (size_t)kMetricBlocks ? (b ? b : 1) : (size_t)kMetricBlocks);
+}
+hipError_t launch_metric_depth(const MetricDepthParams& p, hipStream_t st) {
+  if (!p.pred || !p.gt || !p.d || !p.a_bits || !p.pooled || !p.stat || !p.kept || !p.edge || !p.sel || !p.sel_scratch || !p.rec || p.h < 8 || p.w < 8 ||
+      (long long)p.h * p.w > (long long)kMetricMaxN)
+    return hipErrorInvalidValue;
+  const unsigned n = (unsigned)p.h * (unsigned)p.w, nb = metric_blocks(n);
+  unsigned lo, hi;
+  MetricFinishParams f{};
+  metric_quantile_rank(n, &lo, &hi, &f.w);
+  f.nb_stat = f.nb_kept = nb;
+  hipLaunchKernelGGL(metric_depth_stats_kernel, dim3(nb), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(metric_depth_diff_kernel, dim3(nb), dim3(256), 0, st, p, nb);
+  const hipError_t e = launch_metric_select(p.a_bits, n, lo, hi, p.sel_scratch, p.sel, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(metric_depth_kept_kernel, dim3(nb), dim3(256), 0, st, p, f.w);
+  const float* src = p.d;
+  float* dst = p.pooled;
+  int h = p.h, w = p.w;
+  for (int s = 0; s < 4; ++s) {
+    f.n_edge[s] = (unsigned)h * (unsigned)w;
+    f.nb_edge[s] = metric_blocks(f.n_edge[s]);
+    hipLaunchKernelGGL(metric_depth_edge_kernel, dim3(f.nb_edge[s]), dim3(256), 0, st, src, h, w, s < 3 ? dst : (float*)nullptr, p.edge + s * kMetricBlocks);
+    src = dst;
+    h >>= 1;
+    w >>= 1;
+    dst += (size_t)h * w;
+  }
+  VP_LAUNCH(metric_depth_finish_kernel, dim3(1), dim3(256), 0, st, p, f);
+}
+
 }  // namespace vp

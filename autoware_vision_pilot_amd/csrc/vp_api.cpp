@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cctype>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -1583,6 +1584,159 @@ int vp_range_survey(vp_engine* e, vp_range_stats* out, int cap) {
 }
 
 // ---- single-operator entries (unit tests launch one kernel or one add_* call through them; no host calls them)
+// ---- vp_metric: the reference's validation scores on the device (include/vp_hip.h; vp::Metric: engine.hpp / engine_io.cpp; kernels: kernels_misc.hip metric_*)
+}  // extern "C"
+
+namespace {
+
+static_assert(sizeof(vp_metric_frame) == sizeof(vp::MetricRecord) && offsetof(vp_metric_frame, nonfinite) == offsetof(vp::MetricRecord, nonfinite) &&
+                  offsetof(vp_metric_frame, q_lo) == offsetof(vp::MetricRecord, q_lo) && offsetof(vp_metric_frame, mel) == offsetof(vp::MetricRecord, mel),
+              "vp_metric_frame is the record the kernels write");
+
+template <class F>
+int metric_guarded(vp_metric* m, F&& fn) {
+  if (!m || !m->impl) return VP_ERR_ARG;
+  try {
+    fn(*m->impl);
+    return VP_OK;
+  } catch (const std::invalid_argument& ex) {
+    m->err = ex.what();
+    return VP_ERR_ARG;
+  } catch (const std::exception& ex) {
+    m->err = ex.what();
+    return std::strncmp(ex.what(), "HIP error", 9) == 0 ? VP_ERR_HIP : VP_ERR_STATE;
+  }
+}
+
+vp::Engine& metric_engine(vp_engine* e, const char* who) {
+  if (!e || !e->impl) throw std::invalid_argument(std::string(who) + ": null engine");
+  return *e->impl;
+}
+
+// the scores of one segmentation record, in double: iou[c] = (I + 1) / (U + 1), U = P + G - I; *full over the sums
+void seg_scores(const vp_metric_frame& r, int classes, double iou[3], double* full) {
+  double si = 0.0, su = 0.0;
+  for (int c = 0; c < classes; ++c) {
+    const double i = (double)r.I[c], u = (double)r.P[c] + (double)r.G[c] - (double)r.I[c];
+    iou[c] = (i + 1.0) / (u + 1.0);
+    si += i;
+    su += u;
+  }
+  *full = (si + 1.0) / (su + 1.0);
+}
+
+void metric_summary(const std::vector<vp_metric_frame>& recs, vp_metric_summary* s) {
+  std::memset(s, 0, sizeof(*s));
+  double iou[3] = {0, 0, 0}, full = 0, dom = 0, mae = 0, mel = 0;
+  int scored = 0;
+  for (const vp_metric_frame& r : recs) {
+    ++s->frames;
+    double f[3], ff;
+    if (r.kind == VP_SCENESEG) {
+      seg_scores(r, 3, f, &ff);
+      for (int c = 0; c < 3; ++c) iou[c] += f[c];
+      full += ff;
+      ++s->sceneseg_frames;
+    } else if (r.kind == VP_DOMAINSEG) {
+      seg_scores(r, 1, f, &ff);
+      dom += ff;
+      ++s->domainseg_frames;
+    } else {
+      ++s->scene3d_frames;
+      if (std::isnan(r.mae) || std::isnan(r.mel)) {
+        ++s->nan_frames;
+      } else {
+        mae += (double)r.mae;
+        mel += (double)r.mel;
+        ++scored;
+      }
+    }
+  }
+  const double nan = std::nan("");
+  for (int c = 0; c < 3; ++c) s->sceneseg_iou[c] = s->sceneseg_frames ? iou[c] / s->sceneseg_frames : nan;
+  s->sceneseg_iou_full = s->sceneseg_frames ? full / s->sceneseg_frames : nan;
+  s->domainseg_iou = s->domainseg_frames ? dom / s->domainseg_frames : nan;
+  s->mae = scored ? mae / scored : nan;
+  s->mel = scored ? mel / scored : nan;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vp_metric_create(vp_metric** out, int gpu_id, int max_frames, char* err, size_t err_len) {
+  if (!out) return VP_ERR_ARG;
+  *out = nullptr;
+  try {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) throw std::runtime_error("HIP error: no HIP device visible: a vp_metric lives on the device");
+    if (gpu_id < 0 || gpu_id >= n) throw std::invalid_argument("gpu_id out of range");
+    auto m = std::make_unique<vp_metric>();
+    m->impl = std::make_unique<vp::Metric>(gpu_id, max_frames);
+    *out = m.release();
+    return VP_OK;
+  } catch (const std::invalid_argument& ex) {
+    set_err(err, err_len, ex.what());
+    return VP_ERR_ARG;
+  } catch (const std::exception& ex) {
+    set_err(err, err_len, ex.what());
+    return VP_ERR_HIP;
+  }
+}
+
+void vp_metric_destroy(vp_metric* m) { delete m; }
+
+const char* vp_metric_last_error(const vp_metric* m) { return m ? m->err.c_str() : "null metric"; }
+
+int vp_metric_reset(vp_metric* m) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.reset(); });
+}
+
+int vp_metric_add_seg(vp_metric* m, vp_engine* e, const uint8_t* gt, int gt_on_device, int gt_form) {
+  return metric_guarded(m, [&](vp::Metric& g) {
+    vp::Engine& en = metric_engine(e, "vp_metric_add_seg");
+    if (!gt) throw std::invalid_argument("vp_metric_add_seg: null ground truth");
+    g.add_seg(en, gt, gt_on_device != 0, gt_form);
+  });
+}
+
+int vp_metric_add_depth(vp_metric* m, vp_engine* e, const float* gt, int gt_on_device) {
+  return metric_guarded(m, [&](vp::Metric& g) {
+    vp::Engine& en = metric_engine(e, "vp_metric_add_depth");
+    if (!gt) throw std::invalid_argument("vp_metric_add_depth: null ground truth");
+    g.add_depth(en, gt, gt_on_device != 0);
+  });
+}
+
+int vp_metric_add_seg_pair(vp_metric* m, vp_engine* e, vp_engine* ref) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_seg_pair(metric_engine(e, "vp_metric_add_seg_pair"), metric_engine(ref, "vp_metric_add_seg_pair")); });
+}
+
+int vp_metric_add_depth_pair(vp_metric* m, vp_engine* e, vp_engine* ref) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_depth_pair(metric_engine(e, "vp_metric_add_depth_pair"), metric_engine(ref, "vp_metric_add_depth_pair")); });
+}
+
+int vp_metric_frames(const vp_metric* m) { return m && m->impl ? m->impl->frames() : VP_ERR_ARG; }
+
+int vp_metric_fetch(vp_metric* m, vp_metric_frame* records, int cap, vp_metric_summary* summary) {
+  return metric_guarded(m, [&](vp::Metric& g) {
+    if (cap < 0 || (cap > 0 && !records)) throw std::invalid_argument("vp_metric_fetch: cap < 0, or null records with cap > 0");
+    m->host.resize((size_t)g.frames());
+    g.fetch(reinterpret_cast<vp::MetricRecord*>(m->host.data()), g.frames());
+    const int n = std::min(cap, g.frames());
+    if (n) std::memcpy(records, m->host.data(), (size_t)n * sizeof(vp_metric_frame));
+    if (summary) metric_summary(m->host, summary);
+  });
+}
+
+int vp_metric_add_seg_logits(vp_metric* m, const float* logits_chw, int on_device, int c, int h, int w, const uint8_t* gt, int gt_on_device, int gt_form) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_seg_logits(logits_chw, on_device != 0, c, h, w, gt, gt_on_device != 0, gt_form); });
+}
+
+int vp_metric_add_depth_plane(vp_metric* m, const float* pred, int pred_on_device, const float* gt, int gt_on_device, int h, int w) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_depth_plane(pred, pred_on_device != 0, gt, gt_on_device != 0, h, w); });
+}
+
 }  // extern "C"
 namespace {
 // (hi, lo) planes of an activation, NHWC with padded channels on the device -> fp16 bit patterns [Creal][H][W] on the host
@@ -2132,6 +2286,26 @@ int vp_op_upconv(int gpu_id, const float* in, int cin, int h, int w, const float
     g.sync();
     read_act_chw(g, y, out);
   }, VP_ERR_RANGE);
+}
+
+// ---- vp_metric's radix select alone (unit tests)
+int vp_op_select_f32(int gpu_id, const float* values, int n, int k, float* out, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!values || !out || n < 1 || n > (int)vp::kMetricMaxN || k < 0 || k >= n) throw std::invalid_argument("vp_op_select_f32: bad argument (n 1 .. 2^24, k 0 .. n - 1)");
+    std::vector<unsigned> bits((size_t)n);
+    std::memcpy(bits.data(), values, (size_t)n * sizeof(float));
+    for (int i = 0; i < n; ++i)
+      if (bits[i] >= 0x7F800000u) throw std::invalid_argument("vp_op_select_f32: value " + std::to_string(i) + " is negative or not finite");
+    vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
+    unsigned* d_bits = reinterpret_cast<unsigned*>(g.alloc_f32((size_t)n));
+    unsigned* d_out = reinterpret_cast<unsigned*>(g.alloc_f32(2));
+    unsigned* d_scratch = reinterpret_cast<unsigned*>(g.alloc_f32(vp::metric_select_scratch_bytes((unsigned)n) / sizeof(float)));
+    g.copy_h2d(d_bits, bits.data(), (size_t)n * sizeof(unsigned));
+    VP_HIP_CHECK(vp::launch_metric_select(d_bits, (unsigned)n, (unsigned)k, (unsigned)k, d_scratch, d_out, g.stream()));
+    unsigned got[2];
+    g.copy_d2h(got, d_out, sizeof(got));
+    std::memcpy(out, got, sizeof(float));
+  });
 }
 
 }  // extern "C"

@@ -72,3 +72,11 @@ struct vp_canvas {
   std::unique_ptr<vp::Canvas> impl;
   std::string err;
 };
+
+// vp_metric: the validation scores of the reference's trainers, one record per frame on the device (vp::Metric, engine.hpp / engine_io.cpp; C ABI:
+// vp_api.cpp).  `host`: the records of the last fetch, from which the summary is formed.  One thread drives it.
+struct vp_metric {
+  std::unique_ptr<vp::Metric> impl;
+  std::vector<vp_metric_frame> host;
+  std::string err;
+};

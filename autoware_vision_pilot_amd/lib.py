@@ -193,6 +193,19 @@ _SIGS = {
     "vp_canvas_draw_points": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "vp_canvas_draw_lane_rows": (C.c_int, [_P, _P]),
     "vp_canvas_fetch_resized": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int]),
+    "vp_metric_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "vp_metric_destroy": (None, [_P]),
+    "vp_metric_last_error": (C.c_char_p, [_P]),
+    "vp_metric_reset": (C.c_int, [_P]),
+    "vp_metric_add_seg": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
+    "vp_metric_add_depth": (C.c_int, [_P, _P, _P, C.c_int]),
+    "vp_metric_add_seg_pair": (C.c_int, [_P, _P, _P]),
+    "vp_metric_add_depth_pair": (C.c_int, [_P, _P, _P]),
+    "vp_metric_frames": (C.c_int, [_P]),
+    "vp_metric_fetch": (C.c_int, [_P, _P, C.c_int, _P]),
+    "vp_metric_add_seg_logits": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
+    "vp_metric_add_depth_plane": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
+    "vp_op_select_f32": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_char_p, C.c_size_t]),
 }
 # multi-camera exchange (csrc/vp_comm.cpp): part of libvp_hip.so, absent from the CPU-emulated test build
 _COMM_SIGS = {
@@ -239,6 +252,8 @@ VP_BORDER_CONSTANT, VP_BORDER_REPLICATE = 0, 1
 RECTIFY_MODES = {"two_pass": VP_RECTIFY_TWO_PASS, "one_pass": VP_RECTIFY_ONE_PASS}
 RECTIFY_MAPS = {"undistort": 0, "warp": 1, "one_pass": 2}
 BORDERS = {"constant": VP_BORDER_CONSTANT, "replicate": VP_BORDER_REPLICATE}
+VP_GT_LABEL, VP_GT_BITS = 0, 1
+GT_FORMS = {"label": VP_GT_LABEL, "bits": VP_GT_BITS}
 
 
 def _named(table, v):
@@ -260,6 +275,23 @@ class Raw(C.Structure):
     """vp_raw (include/vp_hip.h)"""
     _fields_ = [("bits", C.c_int), ("shift", C.c_int), ("black", C.c_int), ("gains", C.c_int * 3), ("ccm_on", C.c_int), ("ccm", C.c_int * 9),
                 ("lut", C.c_void_p), ("lut_len", C.c_int)]
+
+
+class MetricFrame(C.Structure):
+    """vp_metric_frame (include/vp_hip.h)"""
+    _fields_ = [("kind", C.c_int), ("I", C.c_uint32 * 3), ("P", C.c_uint32 * 3), ("G", C.c_uint32 * 3), ("nonfinite", C.c_uint32), ("n", C.c_uint32),
+                ("kept", C.c_uint32), ("q_lo", C.c_float), ("q_hi", C.c_float), ("q", C.c_float), ("mae", C.c_float), ("mel", C.c_float)]
+
+
+class MetricSummary(C.Structure):
+    """vp_metric_summary (include/vp_hip.h)"""
+    _fields_ = [("frames", C.c_int), ("sceneseg_frames", C.c_int), ("domainseg_frames", C.c_int), ("scene3d_frames", C.c_int), ("nan_frames", C.c_int),
+                ("reserved", C.c_int), ("sceneseg_iou", C.c_double * 3), ("sceneseg_iou_full", C.c_double), ("domainseg_iou", C.c_double), ("mae", C.c_double),
+                ("mel", C.c_double)]
+
+
+METRIC_FRAME_DTYPE = np.dtype([("kind", "<i4"), ("I", "<u4", (3,)), ("P", "<u4", (3,)), ("G", "<u4", (3,)), ("nonfinite", "<u4"), ("n", "<u4"), ("kept", "<u4"),
+                               ("q_lo", "<f4"), ("q_hi", "<f4"), ("q", "<f4"), ("mae", "<f4"), ("mel", "<f4")])
 
 
 class CameraPose(C.Structure):
@@ -1142,6 +1174,114 @@ class Canvas:
         if f <= VP_FRAME_RGBA8:
             planes[0] = planes[0].reshape(h, w, _FRAME_PX_BYTES[f])
         return planes[0] if len(planes) == 1 else tuple(planes)
+
+
+class Metric:
+    """vp_metric: the reference's validation scores (IoU of the segmentation trainers, mAE / mEL of the depth trainer) computed on the device, one record
+    per frame.  add_* reads an Engine's device-resident logits behind its pass (or the caller's arrays) and returns without waiting; fetch() is the one
+    synchronisation: (records, summary) -- a numpy array of METRIC_FRAME_DTYPE and a dict.  One thread drives a metric (include/vp_hip.h)."""
+
+    def __init__(self, gpu_id=0, max_frames=4096):
+        self._lib = load()
+        self._h = _P()
+        err = C.create_string_buffer(512)
+        rc = self._lib.vp_metric_create(C.byref(self._h), gpu_id, int(max_frames), err, len(err))
+        if rc != 0:
+            self._h = None
+            raise (ValueError if rc == -1 else VpError)(f"vp_metric_create failed ({rc}): {err.value.decode(errors='replace')}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vp_metric_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _ck(self, rc):
+        if rc < 0:
+            msg = self._lib.vp_metric_last_error(self._h).decode(errors="replace")
+            raise (ValueError if rc == -1 else VpError)(f"libvp_hip metric error {rc}: {msg}")
+        return rc
+
+    @staticmethod
+    def _arg(a, dtype, device):
+        """(pointer, on_device, keep-alive): a numpy array (host) or, with device=True, a device pointer (int)"""
+        if device:
+            return _P(int(a)), 1, None
+        arr = np.ascontiguousarray(a, dtype=dtype)
+        return _ptr(arr), 0, arr
+
+    def reset(self):
+        self._ck(self._lib.vp_metric_reset(self._h))
+
+    def frames(self):
+        return self._ck(self._lib.vp_metric_frames(self._h))
+
+    def add_seg(self, engine, gt, gt_form="label", gt_device=False):
+        """gt: uint8 [h][w] of the engine's output size (or a device pointer with gt_device=True); gt_form: "label" or "bits" (VP_GT_LABEL, VP_GT_BITS)"""
+        g, dev, keep = self._arg(gt, np.uint8, gt_device)
+        if keep is not None and keep.size != int(np.prod(engine.output_dims()[-2:])):
+            raise ValueError("add_seg: the ground truth has the engine's output size")
+        self._ck(self._lib.vp_metric_add_seg(self._h, engine._h, g, dev, _named(GT_FORMS, gt_form)))
+
+    def add_depth(self, engine, gt, gt_device=False):
+        g, dev, keep = self._arg(gt, np.float32, gt_device)
+        if keep is not None and keep.size != int(np.prod(engine.output_dims()[-2:])):
+            raise ValueError("add_depth: the ground truth has the engine's output size")
+        self._ck(self._lib.vp_metric_add_depth(self._h, engine._h, g, dev))
+
+    def add_seg_pair(self, engine, ref):
+        self._ck(self._lib.vp_metric_add_seg_pair(self._h, engine._h, ref._h))
+
+    def add_depth_pair(self, engine, ref):
+        self._ck(self._lib.vp_metric_add_depth_pair(self._h, engine._h, ref._h))
+
+    def add_seg_logits(self, logits, gt, gt_form="label", device_chw=None):
+        """logits fp32 [c][h][w] and gt uint8 [h][w]: numpy arrays, or (with device_chw = (c, h, w)) device pointers (ints)"""
+        if device_chw is not None:
+            c, h, w = (int(v) for v in device_chw)
+            self._ck(self._lib.vp_metric_add_seg_logits(self._h, _P(int(logits)), 1, c, h, w, _P(int(gt)), 1, _named(GT_FORMS, gt_form)))
+            return
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        g = np.ascontiguousarray(gt, dtype=np.uint8)
+        if lg.ndim != 3 or g.shape != lg.shape[1:]:
+            raise ValueError("add_seg_logits: logits [c][h][w] and a ground truth [h][w]")
+        self._ck(self._lib.vp_metric_add_seg_logits(self._h, _ptr(lg), 0, lg.shape[0], lg.shape[1], lg.shape[2], _ptr(g), 0, _named(GT_FORMS, gt_form)))
+
+    def add_depth_plane(self, pred, gt, device_hw=None):
+        if device_hw is not None:
+            self._ck(self._lib.vp_metric_add_depth_plane(self._h, _P(int(pred)), 1, _P(int(gt)), 1, int(device_hw[0]), int(device_hw[1])))
+            return
+        p = np.ascontiguousarray(pred, dtype=np.float32)
+        g = np.ascontiguousarray(gt, dtype=np.float32)
+        if p.ndim != 2 or g.shape != p.shape:
+            raise ValueError("add_depth_plane: two planes [h][w] of one size")
+        self._ck(self._lib.vp_metric_add_depth_plane(self._h, _ptr(p), 0, _ptr(g), 0, p.shape[0], p.shape[1]))
+
+    def fetch(self):
+        n = self.frames()
+        rec = np.zeros(n, dtype=METRIC_FRAME_DTYPE)
+        s = MetricSummary()
+        self._ck(self._lib.vp_metric_fetch(self._h, _ptr(rec) if n else None, n, C.byref(s)))
+        summary = {"frames": s.frames, "sceneseg_frames": s.sceneseg_frames, "domainseg_frames": s.domainseg_frames, "scene3d_frames": s.scene3d_frames,
+                   "nan_frames": s.nan_frames, "sceneseg_iou": tuple(s.sceneseg_iou), "sceneseg_iou_full": s.sceneseg_iou_full, "domainseg_iou": s.domainseg_iou,
+                   "mae": s.mae, "mel": s.mel}
+        return rec, summary
+
+
+def select_f32(values, k, gpu_id=0):
+    """vp_op_select_f32: the k-th smallest (0-based) of non-negative finite float32 values, by the metric's radix select"""
+    v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    out = C.c_float()
+    err = C.create_string_buffer(512)
+    rc = load().vp_op_select_f32(gpu_id, _ptr(v), v.size, int(k), C.byref(out), err, len(err))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_op_select_f32 failed ({rc}): {err.value.decode(errors='replace')}")
+    return np.float32(out.value)
 
 
 def decode_logits_host(logits_chw, decode_mode=VP_DECODE_SEG_MASK, gpu_id=0):

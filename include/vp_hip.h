@@ -659,6 +659,79 @@ int vp_canvas_draw_points(vp_canvas* c, const int* xy, int n, int radius, const 
 int vp_canvas_draw_lane_rows(vp_canvas* c, vp_engine* autosteer);
 int vp_canvas_fetch_resized(vp_canvas* c, int format, int out_h, int out_w, uint8_t* const* planes, const int* strides, int n_planes);
 
+/* ---- vp_metric: the reference's validation scores, computed on the device, one small record per frame -----------------------------
+ * The reference qualifies its runtimes by task score: the IoU of SceneSegTrainer.calc_IoU_val / IoU (Models/training/scene_seg_trainer.py:206-244,
+ * domain_seg_trainer.py:236-252) and the mAE / mEL of Scene3DTrainer.validate (scene_3d_trainer.py:94-109, 159-162, 171-210, 295-319).  A vp_metric is a
+ * per-GPU accumulator of those scores: an add call reads an engine's device-resident logits behind its pass (as a vp_canvas draw does) or a caller's
+ * tensors, queues a few kernels on the metric's own stream and returns; a run over a dataset costs ONE fetch at the end.
+ *     vp_metric_create(&m, 0, n_frames, err, sizeof err);
+ *     for each frame:  vp_infer(seg, ...);  vp_metric_add_seg(m, seg, gt, 0, VP_GT_LABEL);      no host wait
+ *     vp_metric_fetch(m, records, n_frames, &summary);                                            the one synchronisation
+ * SEGMENTATION.  Prediction, C = 3: class 0 if l0 >= l1 && l0 >= l2, else 1 if l1 >= l0 && l1 >= l2, else 2 if l2 >= l0 && l2 >= l1 (the first maximum
+ *   for finite logits); C = 1: positive (class 0 of the record) where logit > 0.  Ground truth, u8 of the output's size: VP_GT_LABEL -- the value is the
+ *   class index, a value >= C is no class (C = 1: nonzero is positive); VP_GT_BITS -- bit c is plane c, planes may overlap (the reference's stacked
+ *   one-hot planes).  Counts per class c, u32: I[c] = #(pred == c and gt_c), P[c] = #(pred == c), G[c] = #gt_c; U[c] = P[c] + G[c] - I[c].  Scores, double
+ *   on the host: iou[c] = (I[c] + 1) / (U[c] + 1), iou_full = (sum I + 1) / (sum U + 1) (C = 1: both coincide); the dataset score is the mean over the
+ *   frames of the per-frame scores (train_scene_seg.py, benchmark_onnx_models.py).
+ *   DEPARTURE 1: a pixel with a NaN logit fails all three branches; it predicts NO class and is counted in `nonfinite` (C = 1: a NaN logit is not
+ *   positive and is counted).  The reference leaves the raw values in its one-hot planes there.
+ * DEPTH.  Plane 0 of the logits (p) and an fp32 plane g of the same size; ssi(t) = (t - min t) / (max t - mean t) on both; D = ssi(p) - ssi(g), A = |D|.
+ *   mAE: q = the 0.9 quantile of A, linear interpolation between the order statistics q_lo = A_(lo) and q_hi = A_(min(lo + 1, n - 1)), lo = floor(r),
+ *   r = fp32(0.9f * (n - 1)), weight w = r - lo, evaluated as torch.lerp does in fp32 (q_lo + w (q_hi - q_lo) for w < 0.5, q_hi - (q_hi - q_lo)(1 - w)
+ *   otherwise); mae = mean of the elements of A STRICTLY below q (`kept` of them: elements equal to q are excluded, so with q_lo == q_hi the kept set is
+ *   {A < q_lo}).  mEL: the mean over four scales of mean(|Gx(D)| + |Gy(D)|) -- scale 0 the plane, scales 1 .. 3 2x2 mean pools with stride 2 (a trailing
+ *   odd row or column dropped), Gx / Gy the 3x3 filters of lines 96-106 with zero padding 1; the filters and pools are applied to D, the same linear map
+ *   as the reference's difference of filtered planes.  What the reference answers, this answers: p identical to g gives a NaN mae (an empty mean) and
+ *   mel 0; a constant plane gives NaN for both.  A non-finite input value gives NaN scores and a `nonfinite` count.
+ *   DEPARTURE 2: the dataset score (the mean of the per-frame mae and mel, train_scene_3d.py:161-172) leaves frames with a NaN mae or mel out of both
+ *   means and reports them in nan_frames; the reference would propagate the NaN.
+ * vp_metric_create: max_frames records (1 .. 1 << 20) on gpu_id; VP_ERR_ARG / VP_ERR_HIP with the text in err.
+ * vp_metric_add_seg / vp_metric_add_depth: VP_SCENESEG and VP_DOMAINSEG / VP_SCENE3D engines, shared-prefix heads included; gt has the engine's output
+ *   size (vp_output_dims) and lies in host memory (copied before the call returns) or, gt_on_device != 0, in complete device memory on the metric's GPU.
+ * vp_metric_add_seg_pair / vp_metric_add_depth_pair: ref's own prediction (its class by the rule above / its plane 0) is the ground truth.
+ * vp_metric_add_seg_logits / vp_metric_add_depth_plane: the operator entries -- the same kernels on a caller's fp32 tensors (logits [c][h][w], c 1 or 3;
+ *   planes [h][w]) of any size with h * w <= 1 << 24; the record's kind is VP_SCENESEG (c = 3), VP_DOMAINSEG (c = 1) or VP_SCENE3D.
+ * vp_metric_fetch: waits for the metric's stream, copies the first min(cap, frames) records (records may be NULL with cap 0) and fills *summary (may be
+ *   NULL) from ALL records.  vp_metric_reset empties the accumulator (queued work stays ordered); vp_metric_frames: records added since.
+ * Records are bit-identical from run to run: integer counters, partial sums folded in a fixed order.
+ * ERRORS.  VP_ERR_ARG: another engine kind, an engine on another GPU, a pair of different kinds or sizes, h or w below 8 in the depth entries, h * w above
+ *   1 << 24, c outside {1, 3}, an unknown gt_form, a null pointer.  VP_ERR_STATE: an engine with no pass yet, a full accumulator.
+ * ORDERING CONTRACT: the canvas's.  An add call makes the metric's stream wait for the work queued on the engine's stream so far, and the engine's stream
+ *   wait for the metric's read before anything queued on it afterwards (both engines in the pair forms).  No add call waits for the device, with the
+ *   once-per-geometry exceptions of a scratch or staging buffer that has to grow, and a pinned staging slot still read by the copy of two calls earlier.
+ * THREADING.  One thread drives a metric; an add call is also a call on the engines it names.
+ * vp_op_select_f32: the chain's radix select alone -- *out = the k-th smallest (k = 0 .. n - 1) of n (1 .. 1 << 24) non-negative finite host floats,
+ *   bit for bit; VP_ERR_ARG for a negative (-0.0f included) or non-finite value. */
+typedef struct vp_metric vp_metric;
+enum vp_gt_form { VP_GT_LABEL = 0, VP_GT_BITS = 1 };
+typedef struct vp_metric_frame {
+  int kind;                       /* VP_SCENESEG, VP_DOMAINSEG or VP_SCENE3D */
+  uint32_t I[3], P[3], G[3];      /* segmentation counts (C = 1: index 0) */
+  uint32_t nonfinite;             /* pixels with a NaN logit / non-finite values of the two depth planes */
+  uint32_t n;                     /* h * w */
+  uint32_t kept;                  /* depth: elements of A below q */
+  float q_lo, q_hi, q, mae, mel;  /* depth */
+} vp_metric_frame;
+typedef struct vp_metric_summary {
+  int frames, sceneseg_frames, domainseg_frames, scene3d_frames;
+  int nan_frames;                 /* VP_SCENE3D records left out of mae / mel */
+  int reserved;
+  double sceneseg_iou[3], sceneseg_iou_full, domainseg_iou, mae, mel;   /* means over the frames of the kind; NaN where there is none */
+} vp_metric_summary;
+int vp_metric_create(vp_metric** out, int gpu_id, int max_frames, char* err, size_t err_len);
+void vp_metric_destroy(vp_metric* m);
+const char* vp_metric_last_error(const vp_metric* m);
+int vp_metric_reset(vp_metric* m);
+int vp_metric_add_seg(vp_metric* m, vp_engine* e, const uint8_t* gt, int gt_on_device, int gt_form);
+int vp_metric_add_depth(vp_metric* m, vp_engine* e, const float* gt, int gt_on_device);
+int vp_metric_add_seg_pair(vp_metric* m, vp_engine* e, vp_engine* ref);
+int vp_metric_add_depth_pair(vp_metric* m, vp_engine* e, vp_engine* ref);
+int vp_metric_frames(const vp_metric* m);
+int vp_metric_fetch(vp_metric* m, vp_metric_frame* records, int cap, vp_metric_summary* summary);
+int vp_metric_add_seg_logits(vp_metric* m, const float* logits_chw, int on_device, int c, int h, int w, const uint8_t* gt, int gt_on_device, int gt_form);
+int vp_metric_add_depth_plane(vp_metric* m, const float* pred, int pred_on_device, const float* gt, int gt_on_device, int h, int w);
+int vp_op_select_f32(int gpu_id, const float* values, int n, int k, float* out, char* err, size_t err_len);
+
 /* ---- multi-camera result exchange (BASELINE configs[3]) ---------------------------------------
  * One process (or thread) per GPU, camera r on rank r, weights replicated, no data-path collective in the networks.  For the
  * fused ego-path / BEV consumer every rank needs all cameras' results: ONE ncclAllGather (RCCL over xGMI) per frame of a
