@@ -579,6 +579,17 @@ class Metric {
   int max_frames() const { return max_frames_; }
   void fetch(MetricRecord* out, int count);   // records [0, count), synchronous
   int gpu() const { return gpu_; }
+  // the detector part (kernels.hpp DetValParams): records of its own, storage allocated by the first add_det*.  labels: host floats [n_labels][5]
+  // (cls, cx, cy, w, h normalised to the network input), copied before the call returns
+  void add_det(Engine& e, const float* labels, int n_labels, float conf, float iou, const float* iou_v, int n_iou);
+  void add_det_pair(Engine& e, Engine& ref, float label_conf, float conf, float iou, const float* iou_v, int n_iou);
+  void add_det_raw(const float* raw, bool on_device, int nc, int nb, int net_h, int net_w, const float* labels, int n_labels, float conf, float iou, const float* iou_v, int n_iou);
+  int det_frames() const { return det_frames_; }
+  int det_capacity() const { return max_frames_ < kDetFramesCap ? max_frames_ : kDetFramesCap; }
+  // synchronous: the frame records, then rows and label classes up to the totals the device reports
+  void fetch_det(std::vector<DetFrameRecord>* frames, std::vector<DetRowRecord>* rows, std::vector<float>* label_cls);
+  int det_n_iou() const { return det_n_iou_; }
+  static constexpr int kDetFramesCap = 16384, kDetLabelsPerFrame = 64;
 
  private:
   struct Stage {   // a caller's pageable array: copied into one of two pinned slots before the call returns, then one H2D into `d`
@@ -599,6 +610,10 @@ class Metric {
   MetricRecord* next_record(const char* who);
   void seg(const float* d_logits, const float* d_ref, const uint8_t* d_gt, int c, int h, int w, int gt_form, MetricRecord* rec);
   void depth(const float* d_pred, const float* d_gt, int h, int w, MetricRecord* rec);
+  const Engine& det_source_of(Engine& e, const char* who) const;
+  void det_begin(const char* who, int nc, int nb, int n_labels_bound, const float* iou_v, int n_iou, float conf, float iou);
+  DetValParams det_chain(const float* d_raw, int nc, int nb, float conf, float iou, int which);
+  void det_match(const float* d_labels, const unsigned* d_n_labels, int n_labels, int label_form, int net_h, int net_w);
   int gpu_, max_frames_, frames_ = 0;
   hipStream_t stream_ = nullptr;
   hipEvent_t ev_src_[2] = {nullptr, nullptr}, ev_read_[2] = {nullptr, nullptr};
@@ -606,6 +621,17 @@ class Metric {
   Stage stage_[2];   // [0] the prediction, [1] the ground truth
   uint8_t* d_scratch_ = nullptr;   // the depth chain's: see depth()
   size_t scratch_cap_ = 0;
+  // detector part
+  int det_frames_ = 0, det_n_iou_ = 0;
+  size_t det_labels_bound_ = 0;      // labels added so far, at most (the pair form's count lives on the device)
+  float det_iou_v_[kDetValMaxIou] = {};
+  DetFrameRecord* d_det_frames_ = nullptr;
+  DetRowRecord* d_det_rows_ = nullptr;
+  float* d_det_label_cls_ = nullptr;
+  uint8_t* d_det_small_ = nullptr;   // totals [2] | two sets of {rows [300][7], counts [3]} | pair labels [300][5] | their count
+  uint8_t* d_det_scratch_ = nullptr; // the chain's keys, ranks, order, boxes
+  size_t det_scratch_cap_ = 0;
+  Stage det_stage_;                  // host labels
 };
 
 #define VP_HIP_CHECK(expr)                                                                                   \

@@ -1171,6 +1171,20 @@ void Metric::release() {
   d_records_ = nullptr;
   d_scratch_ = nullptr;
   scratch_cap_ = 0;
+  for (hipEvent_t& ev : det_stage_.ev) {
+    if (ev) (void)hipEventDestroy(ev);
+    ev = nullptr;
+  }
+  if (det_stage_.d) (void)hipFree(det_stage_.d);
+  if (det_stage_.h) (void)hipHostFree(det_stage_.h);
+  det_stage_.d = det_stage_.h = nullptr;
+  det_stage_.dcap = det_stage_.hcap = 0;
+  for (void** p : {reinterpret_cast<void**>(&d_det_frames_), reinterpret_cast<void**>(&d_det_rows_), reinterpret_cast<void**>(&d_det_label_cls_),
+                   reinterpret_cast<void**>(&d_det_small_), reinterpret_cast<void**>(&d_det_scratch_)}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  det_scratch_cap_ = 0;
   if (stream_) (void)hipStreamDestroy(stream_);
   stream_ = nullptr;
 }
@@ -1180,6 +1194,9 @@ void Metric::reset() {
   VP_HIP_CHECK(hipSetDevice(gpu_));
   if (frames_) VP_HIP_CHECK(hipMemsetAsync(d_records_, 0, (size_t)frames_ * sizeof(MetricRecord), stream_));
   frames_ = 0;
+  if (d_det_small_) VP_HIP_CHECK(hipMemsetAsync(d_det_small_, 0, 2 * sizeof(unsigned), stream_));   // the running totals
+  det_frames_ = det_n_iou_ = 0;
+  det_labels_bound_ = 0;
 }
 
 // a device buffer that has to grow is freed only once the metric's own work has run
@@ -1371,6 +1388,162 @@ void Metric::fetch(MetricRecord* out, int count) {
   if (count < 0 || count > frames_ || (count > 0 && !out)) throw std::invalid_argument("vp_metric_fetch: more records than were added, or a null buffer");
   VP_HIP_CHECK(hipSetDevice(gpu_));
   if (count) VP_HIP_CHECK(hipMemcpyAsync(out, d_records_, (size_t)count * sizeof(MetricRecord), hipMemcpyDeviceToHost, stream_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+// ---- the detector part: records, rows and label classes of their own, allocated by the first add_det*
+namespace {
+// d_det_small_: totals [2] | set 0 {rows [300][7], counts [3]} | set 1 (the pair form's reference chain) | pair labels [300][5] | their count
+constexpr size_t kDetSmallRows = 8448, kDetSmallSet = kDetSmallRows + 256, kDetSmallLabels = 256 + 2 * kDetSmallSet, kDetSmallBytes = kDetSmallLabels + 6144 + 256;
+static_assert(kDetSmallRows >= (size_t)kDetValMaxDet * kDetValRowWords * sizeof(float) && 6144 >= (size_t)kDetValMaxDet * 5 * sizeof(float), "d_det_small_ layout");
+}  // namespace
+
+const Engine& Metric::det_source_of(Engine& e, const char* who) const {
+  const std::string me(who);
+  if (e.gpu_ != gpu_) throw std::invalid_argument(me + ": the engine lives on GPU " + std::to_string(e.gpu_) + ", the metric on GPU " + std::to_string(gpu_));
+  if (e.kind_ != 5) throw std::invalid_argument(me + ": VP_AUTOSPEED engines only");
+  if (!e.have_outputs_) throw std::runtime_error("Inference has not been run yet");
+  if (!e.d_logits_ || e.out_c_ < 5 || e.out_w_ < 1) throw std::invalid_argument(me + ": the engine has no raw detector tensor");
+  return e;
+}
+
+void Metric::det_begin(const char* who, int nc, int nb, int n_labels_bound, const float* iou_v, int n_iou, float conf, float iou) {
+  const std::string me(who);
+  if (nc < 1 || nc > kDetValMaxClasses || nb < 1 || nb > kDetValMaxBoxes || (long long)nb * nc > (long long)kDetValMaxPairs)
+    throw std::invalid_argument(me + ": nc " + std::to_string(nc) + ", nb " + std::to_string(nb) + " (nc 1 .. 80, nb 1 .. 16384, nb * nc <= 131072)");
+  if (!iou_v || n_iou < 1 || n_iou > kDetValMaxIou) throw std::invalid_argument(me + ": a null threshold table, or n_iou outside 1 .. 16");
+  if (n_labels_bound < 0 || n_labels_bound > kDetValMaxLabels) throw std::invalid_argument(me + ": n_labels outside 0 .. 4096");
+  if (conf != conf || iou != iou) throw std::invalid_argument(me + ": a NaN threshold");
+  if (det_frames_ && (n_iou != det_n_iou_ || std::memcmp(iou_v, det_iou_v_, sizeof(float) * (size_t)n_iou) != 0))
+    throw std::invalid_argument(me + ": another threshold table than the records added so far were matched with (vp_metric_reset first)");
+  const size_t label_cap = (size_t)det_capacity() * kDetLabelsPerFrame + kDetValMaxLabels;
+  if (det_frames_ >= det_capacity() || det_labels_bound_ + (size_t)n_labels_bound > label_cap)
+    throw std::runtime_error(me + ": the detector accumulator is full (" + std::to_string(det_capacity()) + " frames, " + std::to_string(label_cap) + " labels; vp_metric_fetch_det, then vp_metric_reset)");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (!d_det_small_) {   // allocated last: a failure half way is cleaned up by the next attempt or by release()
+    for (void** p : {reinterpret_cast<void**>(&d_det_frames_), reinterpret_cast<void**>(&d_det_rows_), reinterpret_cast<void**>(&d_det_label_cls_)}) {
+      if (*p) (void)hipFree(*p);
+      *p = nullptr;
+    }
+    for (hipEvent_t& ev : det_stage_.ev)
+      if (!ev) VP_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    const size_t cap = (size_t)det_capacity();
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_det_frames_), cap * sizeof(DetFrameRecord)));
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_det_rows_), cap * kDetValMaxDet * sizeof(DetRowRecord)));
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_det_label_cls_), label_cap * sizeof(float)));
+    uint8_t* small = nullptr;
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&small), kDetSmallBytes));
+    if (hipError_t err = hipMemsetAsync(small, 0, kDetSmallBytes, stream_); err != hipSuccess) {
+      (void)hipFree(small);
+      VP_HIP_CHECK(err);
+    }
+    d_det_small_ = small;
+  }
+  det_n_iou_ = n_iou;
+  std::memcpy(det_iou_v_, iou_v, sizeof(float) * (size_t)n_iou);
+}
+
+DetValParams Metric::det_chain(const float* d_raw, int nc, int nb, float conf, float iou, int which) {
+  grow(d_det_scratch_, det_scratch_cap_, det_val_scratch_bytes((unsigned)nb, (unsigned)nc));
+  DetValParams q{};
+  q.raw = d_raw;
+  q.nb = (unsigned)nb;
+  q.nc = (unsigned)nc;
+  q.conf = conf;
+  q.iou = iou;
+  q.max_nms = kDetValMaxNms;
+  q.max_det = kDetValMaxDet;
+  det_val_carve(d_det_scratch_, &q);
+  uint8_t* set = d_det_small_ + 256 + (size_t)which * kDetSmallSet;
+  q.rows = reinterpret_cast<float*>(set);
+  q.counts = reinterpret_cast<unsigned*>(set + kDetSmallRows);
+  VP_HIP_CHECK(launch_det_validate(q, stream_));
+  return q;
+}
+
+void Metric::det_match(const float* d_labels, const unsigned* d_n_labels, int n_labels, int label_form, int net_h, int net_w) {
+  DetMatchParams q{};
+  q.rows = reinterpret_cast<const float*>(d_det_small_ + 256);
+  q.counts = reinterpret_cast<const unsigned*>(d_det_small_ + 256 + kDetSmallRows);
+  q.labels = d_labels;
+  q.n_labels_dev = d_n_labels;
+  q.n_labels = n_labels;
+  q.label_form = label_form;
+  q.W = (float)net_w;
+  q.H = (float)net_h;
+  std::memcpy(q.iou_v, det_iou_v_, sizeof(q.iou_v));
+  q.n_iou = det_n_iou_;
+  q.totals = reinterpret_cast<unsigned*>(d_det_small_);
+  q.frame = d_det_frames_ + det_frames_;
+  q.rows_out = d_det_rows_;
+  q.label_cls_out = d_det_label_cls_;
+  VP_HIP_CHECK(launch_det_val_match(q, stream_));
+  ++det_frames_;
+  det_labels_bound_ += (size_t)n_labels;
+}
+
+void Metric::add_det(Engine& e, const float* labels, int n_labels, float conf, float iou, const float* iou_v, int n_iou) {
+  det_source_of(e, "vp_metric_add_det");
+  if (n_labels > 0 && !labels) throw std::invalid_argument("vp_metric_add_det: null labels");
+  const int nc = e.out_c_ - 4, nb = e.out_h_ * e.out_w_;
+  det_begin("vp_metric_add_det", nc, nb, n_labels, iou_v, n_iou, conf, iou);
+  const float* d_labels = n_labels > 0 ? static_cast<const float*>(stage_host(det_stage_, labels, sizeof(float) * 5 * (size_t)n_labels)) : nullptr;
+  wait_for(e, ev_src_[0]);
+  det_chain(e.d_logits_, nc, nb, conf, iou, 0);
+  release_to(e, ev_read_[0]);
+  det_match(d_labels, nullptr, n_labels, 0, e.net_h(), e.net_w());
+}
+
+void Metric::add_det_pair(Engine& e, Engine& ref, float label_conf, float conf, float iou, const float* iou_v, int n_iou) {
+  det_source_of(e, "vp_metric_add_det_pair");
+  det_source_of(ref, "vp_metric_add_det_pair");
+  if (e.out_c_ != ref.out_c_ || e.out_h_ * e.out_w_ != ref.out_h_ * ref.out_w_) throw std::invalid_argument("vp_metric_add_det_pair: the two engines differ in nc or nb");
+  if (label_conf != label_conf) throw std::invalid_argument("vp_metric_add_det_pair: a NaN threshold");
+  const int nc = e.out_c_ - 4, nb = e.out_h_ * e.out_w_;
+  det_begin("vp_metric_add_det_pair", nc, nb, kDetValMaxDet, iou_v, n_iou, conf, iou);
+  wait_for(e, ev_src_[0]);
+  if (&ref != &e) wait_for(ref, ev_src_[1]);
+  const DetValParams r = det_chain(ref.d_logits_, nc, nb, conf, iou, 1);
+  DetValLabelsParams lp{};
+  lp.rows = r.rows;
+  lp.counts = r.counts;
+  lp.label_conf = label_conf;
+  lp.labels = reinterpret_cast<float*>(d_det_small_ + kDetSmallLabels);
+  lp.n_labels = reinterpret_cast<unsigned*>(d_det_small_ + kDetSmallLabels + 6144);
+  VP_HIP_CHECK(launch_det_val_labels(lp, stream_));
+  det_chain(e.d_logits_, nc, nb, conf, iou, 0);
+  release_to(e, ev_read_[0]);
+  if (&ref != &e) release_to(ref, ev_read_[1]);
+  det_match(lp.labels, lp.n_labels, kDetValMaxDet, 1, e.net_h(), e.net_w());
+}
+
+void Metric::add_det_raw(const float* raw, bool on_device, int nc, int nb, int net_h, int net_w, const float* labels, int n_labels, float conf, float iou, const float* iou_v,
+                         int n_iou) {
+  if (!raw || (n_labels > 0 && !labels)) throw std::invalid_argument("vp_metric_add_det_raw: null tensor or null labels");
+  if (net_h < 1 || net_w < 1) throw std::invalid_argument("vp_metric_add_det_raw: net_h, net_w below 1");
+  det_begin("vp_metric_add_det_raw", nc, nb, n_labels, iou_v, n_iou, conf, iou);
+  const float* d_raw = on_device ? raw : static_cast<const float*>(stage_host(stage_[0], raw, sizeof(float) * (size_t)(4 + nc) * nb));
+  if (reinterpret_cast<uintptr_t>(d_raw) & 3) throw std::invalid_argument("vp_metric_add_det_raw: device tensor not aligned to 4 bytes");
+  const float* d_labels = n_labels > 0 ? static_cast<const float*>(stage_host(det_stage_, labels, sizeof(float) * 5 * (size_t)n_labels)) : nullptr;
+  det_chain(d_raw, nc, nb, conf, iou, 0);
+  det_match(d_labels, nullptr, n_labels, 0, net_h, net_w);
+}
+
+void Metric::fetch_det(std::vector<DetFrameRecord>* frames, std::vector<DetRowRecord>* rows, std::vector<float>* label_cls) {
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  frames->assign((size_t)det_frames_, DetFrameRecord{});
+  rows->clear();
+  label_cls->clear();
+  unsigned totals[2] = {0, 0};
+  if (det_frames_) {
+    VP_HIP_CHECK(hipMemcpyAsync(frames->data(), d_det_frames_, (size_t)det_frames_ * sizeof(DetFrameRecord), hipMemcpyDeviceToHost, stream_));
+    VP_HIP_CHECK(hipMemcpyAsync(totals, d_det_small_, sizeof(totals), hipMemcpyDeviceToHost, stream_));
+  }
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  rows->assign((size_t)totals[0], DetRowRecord{});
+  label_cls->assign((size_t)totals[1], 0.0f);
+  if (totals[0]) VP_HIP_CHECK(hipMemcpyAsync(rows->data(), d_det_rows_, (size_t)totals[0] * sizeof(DetRowRecord), hipMemcpyDeviceToHost, stream_));
+  if (totals[1]) VP_HIP_CHECK(hipMemcpyAsync(label_cls->data(), d_det_label_cls_, (size_t)totals[1] * sizeof(float), hipMemcpyDeviceToHost, stream_));
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 

@@ -770,4 +770,74 @@ inline void metric_quantile_rank(unsigned n, unsigned* lo, unsigned* hi, float* 
   *w = r - f;
 }
 
+// ---- vp_metric, detector part (include/vp_hip.h "vp_metric: the detector"; kernels_detect.hip det_val_*): the validation post-process of the detector's
+// trainer (auto_speed_util.py non_max_suppression + compute_metric) on a raw tensor [4 + nc][nb].  The chain, one launch each, no workgroup talking to
+// another inside a launch:
+//   expand    every (box, class) pair above conf -> a 64-bit key (orderable score bits << 32 | ~candidate index) at an atomic slot; the arrival order is
+//             erased by the rank (keys are unique, a rank depends on the SET of keys only)
+//   rank      rank = number of greater keys, by counting: a grid of (256 keys) x (slices of 4096 keys), tiles of 1024 keys through LDS, one integer
+//             atomic per key and slice
+//   place     rank r < max_nms: candidate index -> order[r], class-offset corners -> boxes[r]
+//   suppress  ONE workgroup: greedy in rank order, byte flags of the <= 30000 ranks in LDS, boxes in global memory, a barrier per kept box, stops at
+//             max_det; writes the kept rows and {candidates, ranked, kept}
+//   labels    (pair form) the kept rows of the reference chain above label_conf -> label rows
+//   match     ONE workgroup: compute_metric's tp word per kept row, then the frame's record, rows and label classes behind the accumulator's running totals
+constexpr int kDetValMaxNms = 30000;      // VP_DET_MAX_NMS
+constexpr int kDetValMaxDet = 300;        // VP_DET_MAX_DET
+constexpr int kDetValMaxClasses = 80;
+constexpr int kDetValMaxBoxes = 16384;
+constexpr int kDetValMaxPairs = 131072;   // nb * nc
+constexpr int kDetValMaxIou = 16;
+constexpr int kDetValMaxLabels = 4096;    // per frame
+constexpr int kDetValRowWords = 7;        // x1, y1, x2, y2, conf, cls, tp
+struct DetValParams {
+  const float* raw;            // [4 + nc][nb]
+  unsigned nb, nc;
+  float conf, iou;
+  int max_nms, max_det;
+  unsigned* slots;             // [1] zeroed by launch_det_validate: the candidate count
+  unsigned long long* keys;    // [nb * nc]
+  unsigned* rank;              // [nb * nc]
+  unsigned* order;             // [min(nb * nc, max_nms)] candidate index i * nc + c of rank r
+  float* boxes;                // [min(nb * nc, max_nms)][4] class-offset corners in rank order
+  float* rows;                 // out [max_det][7]: un-offset corners, score, class, tp = 0
+  unsigned* counts;            // out [3]: candidates, ranked, kept
+};
+size_t det_val_scratch_bytes(unsigned nb, unsigned nc);
+// carves slots .. boxes out of `scratch` (256-byte aligned, det_val_scratch_bytes(nb, nc))
+void det_val_carve(uint8_t* scratch, DetValParams* p);
+bool det_val_ok(const DetValParams& p);
+hipError_t launch_det_validate(const DetValParams& p, hipStream_t st);
+struct DetValLabelsParams {
+  const float* rows;           // [max_det][7] of the reference chain
+  const unsigned* counts;      // its [3]
+  float label_conf;
+  float* labels;               // out [max_det][5]: cls, x1, y1, x2, y2
+  unsigned* n_labels;          // out [1]
+};
+hipError_t launch_det_val_labels(const DetValLabelsParams& p, hipStream_t st);
+struct DetFrameRecord {        // == vp_metric_det_frame
+  unsigned candidates, ranked, kept, labels, first_row;
+};
+struct DetRowRecord {          // == vp_metric_det_row
+  float x1, y1, x2, y2, conf, cls;
+  unsigned tp;
+};
+struct DetMatchParams {
+  const float* rows;           // [max_det][7] of launch_det_validate
+  const unsigned* counts;      // its [3]
+  const float* labels;         // [n_labels][5]
+  const unsigned* n_labels_dev;   // pair form: the count on the device (<= n_labels); else null
+  int n_labels;
+  int label_form;              // 0: cls, cx, cy, w, h normalised -> wh2xy, times (W, H, W, H); 1: cls, x1, y1, x2, y2 in pixels
+  float W, H;
+  float iou_v[kDetValMaxIou];
+  int n_iou;
+  unsigned* totals;            // [2] rows and labels of the accumulator so far; advanced by this launch
+  DetFrameRecord* frame;       // out [1]
+  DetRowRecord* rows_out;      // the accumulator's rows; this frame's go to rows_out[totals[0] ..]
+  float* label_cls_out;        // the accumulator's label classes; this frame's go to label_cls_out[totals[1] ..]
+};
+hipError_t launch_det_val_match(const DetMatchParams& p, hipStream_t st);
+
 }  // namespace vp

@@ -408,4 +408,289 @@ hipError_t launch_lane_rows_head(const LaneRowsHeadParams& p, hipStream_t st) {
   VP_LAUNCH(lane_rows_head_kernel, dim3(p.features.H), dim3(256), 0, st, p);
 }
 
+// ------------------------------------------------------------------------------------------------ validation NMS + matching (vp_metric_add_det*)
+// The trainer's validation post-process (Models/training/auto_speed_util.py non_max_suppression :123-169, compute_metric :99-120), as include/vp_hip.h
+// defines it; the chain and its buffers: kernels.hpp DetValParams.  Every fp32 operation is one __f*_rn in the order of the definition.
+constexpr int kDetRankSlice = 4096, kDetRankTile = 1024, kDetSupThreads = 1024;
+
+// a float's bits, ordered as the floats are (negative scores included: the operator entry takes any tensor); a candidate's is never 0
+__device__ __forceinline__ unsigned det_ord(const float s) {
+  const unsigned b = __float_as_uint(s);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__global__ __launch_bounds__(256) void det_val_expand_kernel(const DetValParams p) {
+  __shared__ unsigned s_n, s_base;
+  const unsigned N = p.nb * p.nc, k = blockIdx.x * 256 + threadIdx.x;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  bool cand = false;
+  float s = 0.0f;
+  if (k < N) {
+    const unsigned i = k / p.nc, c = k - i * p.nc;
+    s = p.raw[(size_t)(4 + c) * p.nb + i];
+    cand = s > p.conf;   // false for a NaN
+    p.rank[k] = 0;
+  }
+  unsigned slot = 0;
+  if (cand) slot = atomicAdd(&s_n, 1u);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_n) s_base = atomicAdd(p.slots, s_n);
+  __syncthreads();
+  if (cand) p.keys[s_base + slot] = ((unsigned long long)det_ord(s) << 32) | (unsigned long long)(0xFFFFFFFFu - k);
+}
+
+// grid (ceil(N / 256), ceil(N / 4096)): the keys [256 x, 256 x + 256) against the slice [4096 y, 4096 y + 4096); workgroups past the count leave
+__global__ __launch_bounds__(256) void det_val_rank_kernel(const DetValParams p) {
+  __shared__ unsigned long long tile[kDetRankTile];
+  const unsigned n = min(*p.slots, p.nb * p.nc), tid = threadIdx.x;
+  const unsigned k0 = blockIdx.x * 256, j0 = blockIdx.y * kDetRankSlice;
+  if (k0 >= n || j0 >= n) return;
+  const unsigned k = k0 + tid, j1 = min(n, j0 + (unsigned)kDetRankSlice);
+  const unsigned long long mine = k < n ? p.keys[k] : ~0ull;
+  unsigned cnt = 0;
+  for (unsigned t = 0; t < kDetRankSlice / kDetRankTile; ++t) {
+    const unsigned b = j0 + t * kDetRankTile;
+    if (b >= j1) break;   // uniform
+    for (unsigned u = tid; u < kDetRankTile; u += 256) tile[u] = b + u < j1 ? p.keys[b + u] : 0ull;
+    __syncthreads();
+#pragma unroll 8
+    for (unsigned u = 0; u < kDetRankTile; ++u) cnt += tile[u] > mine ? 1u : 0u;
+    __syncthreads();
+  }
+  if (k < n && cnt) atomicAdd(&p.rank[k], cnt);
+}
+
+// candidate (box i, class c): the corners of wh2xy, and the class offset of the batched NMS
+__device__ __forceinline__ f32x4_t det_val_corners(const DetValParams& p, const unsigned i) {
+  const float cx = p.raw[i], cy = p.raw[(size_t)p.nb + i], w = p.raw[(size_t)2 * p.nb + i], h = p.raw[(size_t)3 * p.nb + i];
+  const float hw = __fdiv_rn(w, 2.0f), hh = __fdiv_rn(h, 2.0f);
+  return f32x4_t{__fsub_rn(cx, hw), __fsub_rn(cy, hh), __fadd_rn(cx, hw), __fadd_rn(cy, hh)};
+}
+
+__global__ __launch_bounds__(256) void det_val_place_kernel(const DetValParams p) {
+  const unsigned n = min(*p.slots, p.nb * p.nc), k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const unsigned r = p.rank[k];
+  if (r >= (unsigned)p.max_nms) return;
+  const unsigned cand = 0xFFFFFFFFu - (unsigned)(p.keys[k] & 0xFFFFFFFFull);
+  const unsigned i = cand / p.nc, c = cand - i * p.nc;
+  const f32x4_t b = det_val_corners(p, i);
+  const float off = __fmul_rn((float)c, 7680.0f);
+  p.order[r] = cand;
+  *reinterpret_cast<f32x4_t*>(p.boxes + (size_t)r * 4) = f32x4_t{__fadd_rn(b[0], off), __fadd_rn(b[1], off), __fadd_rn(b[2], off), __fadd_rn(b[3], off)};
+}
+
+// One workgroup.  A kept box costs one pass of all threads over the ranks behind it and one barrier; the walk to the next unsuppressed rank is uniform
+// (every thread reads the same flags behind the barrier) and skips four suppressed ranks per LDS word.
+__global__ __launch_bounds__(kDetSupThreads) void det_val_suppress_kernel(const DetValParams p) {
+  __shared__ __attribute__((aligned(16))) unsigned char flags[kDetValMaxNms];
+  __shared__ int kept_rank[kDetValMaxDet];
+  const int tid = threadIdx.x, n = (int)min(*p.slots, p.nb * p.nc), m = min(n, p.max_nms);
+  for (int j = tid; j < m; j += kDetSupThreads) flags[j] = 0;
+  __syncthreads();
+  int kept = 0, i = 0;
+  for (int it = 0; it < p.max_det; ++it) {
+    while (i < m) {
+      if (!(i & 3) && i + 4 <= m && *reinterpret_cast<const unsigned*>(flags + i) == 0x01010101u) {
+        i += 4;
+        continue;
+      }
+      if (!flags[i]) break;
+      ++i;
+    }
+    if (i >= m) break;
+    if (tid == 0) kept_rank[kept] = i;
+    ++kept;
+    if (kept == p.max_det) break;   // the list is full: nothing behind this box is looked at
+    const f32x4_t bi = *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)i * 4);
+    // eight boxes per thread and trip, loaded whatever their flags say: the loads of a trip are in flight together (the boxes come from L2)
+    for (int j0 = i + 1 + tid; j0 < m; j0 += 8 * kDetSupThreads) {
+      f32x4_t bj[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int j = j0 + u * kDetSupThreads;
+        bj[u] = j < m ? *reinterpret_cast<const f32x4_t*>(p.boxes + (size_t)j * 4) : f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int j = j0 + u * kDetSupThreads;
+        if (j < m && !flags[j] && det_iou<true>(bi, bj[u]) > p.iou) flags[j] = 1;
+      }
+    }
+    __syncthreads();
+    ++i;
+  }
+  __syncthreads();
+  for (int t = tid; t < kept; t += kDetSupThreads) {
+    const unsigned cand = p.order[kept_rank[t]];
+    const unsigned bi = cand / p.nc, c = cand - bi * p.nc;
+    const f32x4_t b = det_val_corners(p, bi);
+    float* o = p.rows + (size_t)t * kDetValRowWords;
+    o[0] = b[0];
+    o[1] = b[1];
+    o[2] = b[2];
+    o[3] = b[3];
+    o[4] = p.raw[(size_t)(4 + c) * p.nb + bi];
+    o[5] = (float)c;
+    o[6] = 0.0f;   // the tp word: no bit
+  }
+  if (tid == 0) {
+    p.counts[0] = (unsigned)n;
+    p.counts[1] = (unsigned)m;
+    p.counts[2] = (unsigned)kept;
+  }
+}
+
+size_t det_val_scratch_bytes(const unsigned nb, const unsigned nc) {
+  const size_t N = (size_t)nb * nc, m = N < (size_t)kDetValMaxNms ? N : (size_t)kDetValMaxNms;
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  return 256 + up(8 * N) + up(4 * N) + up(4 * m) + up(16 * m);
+}
+
+void det_val_carve(uint8_t* s, DetValParams* p) {
+  const size_t N = (size_t)p->nb * p->nc, m = N < (size_t)kDetValMaxNms ? N : (size_t)kDetValMaxNms;
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  p->slots = reinterpret_cast<unsigned*>(s);
+  p->keys = reinterpret_cast<unsigned long long*>(s + 256);
+  p->rank = reinterpret_cast<unsigned*>(s + 256 + up(8 * N));
+  p->order = reinterpret_cast<unsigned*>(s + 256 + up(8 * N) + up(4 * N));
+  p->boxes = reinterpret_cast<float*>(s + 256 + up(8 * N) + up(4 * N) + up(4 * m));
+}
+
+bool det_val_ok(const DetValParams& p) {
+  return p.raw && p.slots && p.keys && p.rank && p.order && p.boxes && p.rows && p.counts && p.nc >= 1 && p.nc <= (unsigned)kDetValMaxClasses && p.nb >= 1 &&
+         p.nb <= (unsigned)kDetValMaxBoxes && (unsigned long long)p.nb * p.nc <= (unsigned long long)kDetValMaxPairs && p.max_nms >= 1 && p.max_nms <= kDetValMaxNms &&
+         p.max_det >= 1 && p.max_det <= kDetValMaxDet && !(reinterpret_cast<uintptr_t>(p.boxes) & 15) && !(reinterpret_cast<uintptr_t>(p.keys) & 7);
+}
+
+hipError_t launch_det_validate(const DetValParams& p, hipStream_t st) {
+  if (!det_val_ok(p)) return hipErrorInvalidValue;
+  const unsigned N = p.nb * p.nc, gx = nblk(N), gy = (N + kDetRankSlice - 1) / kDetRankSlice;
+  if (hipError_t e = hipMemsetAsync(p.slots, 0, sizeof(unsigned), st); e != hipSuccess) return e;
+  hipLaunchKernelGGL(det_val_expand_kernel, dim3(gx), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(det_val_rank_kernel, dim3(gx, gy), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(det_val_place_kernel, dim3(gx), dim3(256), 0, st, p);
+  VP_LAUNCH(det_val_suppress_kernel, dim3(1), dim3(kDetSupThreads), 0, st, p);
+}
+
+// pair form: the reference chain's kept rows with score > label_conf, in order, as label rows in pixels
+__global__ __launch_bounds__(256) void det_val_labels_kernel(const DetValLabelsParams p) {
+  __shared__ int flag[kDetValMaxDet];
+  const int tid = threadIdx.x, kept = (int)min(p.counts[2], (unsigned)kDetValMaxDet);
+  for (int d = tid; d < kept; d += 256) flag[d] = p.rows[(size_t)d * kDetValRowWords + 4] > p.label_conf ? 1 : 0;
+  __syncthreads();
+  for (int d = tid; d < kept; d += 256) {
+    if (!flag[d]) continue;
+    int pos = 0;
+    for (int e = 0; e < d; ++e) pos += flag[e];
+    const float* r = p.rows + (size_t)d * kDetValRowWords;
+    float* o = p.labels + (size_t)pos * 5;
+    o[0] = r[5];
+    o[1] = r[0];
+    o[2] = r[1];
+    o[3] = r[2];
+    o[4] = r[3];
+  }
+  if (tid == 0) {
+    int total = 0;
+    for (int e = 0; e < kept; ++e) total += flag[e];
+    *p.n_labels = (unsigned)total;
+  }
+}
+
+hipError_t launch_det_val_labels(const DetValLabelsParams& p, hipStream_t st) {
+  if (!p.rows || !p.counts || !p.labels || !p.n_labels) return hipErrorInvalidValue;
+  VP_LAUNCH(det_val_labels_kernel, dim3(1), dim3(256), 0, st, p);
+}
+
+// torch.min / torch.max / clamp(0) hand a NaN on (fminf / fmaxf would drop it)
+__device__ __forceinline__ float det_min_nan(const float a, const float b) { return (a != a || b != b) ? __uint_as_float(0x7FC00000u) : fminf(a, b); }
+__device__ __forceinline__ float det_max_nan(const float a, const float b) { return (a != a || b != b) ? __uint_as_float(0x7FC00000u) : fmaxf(a, b); }
+
+__device__ __forceinline__ f32x4_t det_val_label_box(const DetMatchParams& p, const float* l) {
+  if (p.label_form) return f32x4_t{l[1], l[2], l[3], l[4]};
+  const float hw = __fdiv_rn(l[3], 2.0f), hh = __fdiv_rn(l[4], 2.0f);
+  return f32x4_t{__fmul_rn(__fsub_rn(l[1], hw), p.W), __fmul_rn(__fsub_rn(l[2], hh), p.H), __fmul_rn(__fadd_rn(l[1], hw), p.W), __fmul_rn(__fadd_rn(l[2], hh), p.H)};
+}
+
+// compute_metric (:99-120).  The best label of a detection is its same-class label of highest IoU (the first of equals), whatever the threshold: at
+// threshold t the detection is eligible when that IoU >= t.  Among the eligible detections that share a best label the one of LOWEST index is correct
+// (what the two numpy.unique(..., return_index=True) calls leave).
+__global__ __launch_bounds__(256) void det_val_match_kernel(const DetMatchParams p) {
+  __shared__ float best_iou[kDetValMaxDet];
+  __shared__ int best_lab[kDetValMaxDet];
+  const int tid = threadIdx.x, kept = (int)min(p.counts[2], (unsigned)kDetValMaxDet);
+  const int nl = p.n_labels_dev ? (int)min(*p.n_labels_dev, (unsigned)p.n_labels) : p.n_labels;
+  const unsigned row0 = p.totals[0], lab0 = p.totals[1];
+  for (int d = tid; d < kept; d += 256) {
+    const float* r = p.rows + (size_t)d * kDetValRowWords;
+    const float area_d = __fmul_rn(__fsub_rn(r[2], r[0]), __fsub_rn(r[3], r[1]));
+    float best = 0.0f;
+    int lab = -1;
+    for (int l = 0; l < nl; ++l) {
+      const float* L = p.labels + (size_t)l * 5;
+      if (!(L[0] == r[5])) continue;
+      const f32x4_t a = det_val_label_box(p, L);
+      float iw = __fsub_rn(det_min_nan(a[2], r[2]), det_max_nan(a[0], r[0]));
+      float ih = __fsub_rn(det_min_nan(a[3], r[3]), det_max_nan(a[1], r[1]));
+      iw = iw < 0.0f ? 0.0f : iw;
+      ih = ih < 0.0f ? 0.0f : ih;
+      const float inter = __fmul_rn(iw, ih);
+      const float area_l = __fmul_rn(__fsub_rn(a[2], a[0]), __fsub_rn(a[3], a[1]));
+      const float iou = __fdiv_rn(inter, __fadd_rn(__fsub_rn(__fadd_rn(area_l, area_d), inter), 1e-7f));
+      if (iou == iou && (lab < 0 || iou > best)) {
+        best = iou;
+        lab = l;
+      }
+    }
+    best_iou[d] = best;
+    best_lab[d] = lab;
+  }
+  __syncthreads();
+  for (int d = tid; d < kept; d += 256) {
+    unsigned tp = 0;
+    const int lab = best_lab[d];
+    if (lab >= 0) {
+      for (int t = 0; t < p.n_iou; ++t) {
+        bool ok = best_iou[d] >= p.iou_v[t];
+        for (int e = 0; e < d && ok; ++e) ok = !(best_lab[e] == lab && best_iou[e] >= p.iou_v[t]);
+        tp |= ok ? 1u << t : 0u;
+      }
+    }
+    const float* r = p.rows + (size_t)d * kDetValRowWords;
+    DetRowRecord o;
+    o.x1 = r[0];
+    o.y1 = r[1];
+    o.x2 = r[2];
+    o.y2 = r[3];
+    o.conf = r[4];
+    o.cls = r[5];
+    o.tp = tp;
+    p.rows_out[(size_t)row0 + d] = o;
+  }
+  for (int l = tid; l < nl; l += 256) p.label_cls_out[(size_t)lab0 + l] = p.labels[(size_t)l * 5];
+  if (tid == 0) {
+    DetFrameRecord f;
+    f.candidates = p.counts[0];
+    f.ranked = p.counts[1];
+    f.kept = (unsigned)kept;
+    f.labels = (unsigned)nl;
+    f.first_row = row0;
+    *p.frame = f;
+  }
+  __syncthreads();   // every thread has read the totals
+  if (tid == 0) {
+    p.totals[0] = row0 + (unsigned)kept;
+    p.totals[1] = lab0 + (unsigned)nl;
+  }
+}
+
+hipError_t launch_det_val_match(const DetMatchParams& p, hipStream_t st) {
+  if (!p.rows || !p.counts || (p.n_labels > 0 && !p.labels) || p.n_labels < 0 || p.n_labels > kDetValMaxLabels || p.n_iou < 1 || p.n_iou > kDetValMaxIou || !p.totals ||
+      !p.frame || !p.rows_out || !p.label_cls_out)
+    return hipErrorInvalidValue;
+  VP_LAUNCH(det_val_match_kernel, dim3(1), dim3(256), 0, st, p);
+}
+
 }  // namespace vp

@@ -1660,6 +1660,173 @@ void metric_summary(const std::vector<vp_metric_frame>& recs, vp_metric_summary*
   s->mel = scored ? mel / scored : nan;
 }
 
+// ---- the detector's dataset scores: compute_ap (Models/training/auto_speed_util.py:225-300) in double, statement for statement
+static_assert(sizeof(vp_metric_det_frame) == sizeof(vp::DetFrameRecord) && sizeof(vp_metric_det_row) == sizeof(vp::DetRowRecord) && offsetof(vp_metric_det_row, tp) == offsetof(vp::DetRowRecord, tp) &&
+                  offsetof(vp_metric_det_frame, first_row) == offsetof(vp::DetFrameRecord, first_row),
+              "vp_metric_det_frame / vp_metric_det_row are the records the kernels write");
+static_assert(VP_DET_MAX_NMS == vp::kDetValMaxNms && VP_DET_MAX_DET == vp::kDetValMaxDet && VP_DET_MAX_CLASSES == vp::kDetValMaxClasses && VP_DET_MAX_IOU == vp::kDetValMaxIou &&
+                  VP_DET_MAX_LABELS == vp::kDetValMaxLabels,
+              "the header's limits are the kernels'");
+
+// numpy.interp for one x (compiled_base.c arr_interp): xp non-decreasing, j = the last index with xp[j] <= x
+double np_interp(double x, const std::vector<double>& xp, const std::vector<double>& fp, double left, double right) {
+  const size_t n = xp.size();
+  if (n == 1) return x < xp[0] ? left : (x > xp[0] ? right : fp[0]);
+  if (x > xp[n - 1]) return right;
+  if (x < xp[0]) return left;
+  const size_t j = (size_t)(std::upper_bound(xp.begin(), xp.end(), x) - xp.begin()) - 1;
+  if (j == n - 1 || xp[j] == x) return fp[j];
+  const double slope = (fp[j + 1] - fp[j]) / (xp[j + 1] - xp[j]);
+  double r = slope * (x - xp[j]) + fp[j];
+  if (std::isnan(r)) {
+    r = slope * (x - xp[j + 1]) + fp[j + 1];
+    if (std::isnan(r) && fp[j] == fp[j + 1]) r = fp[j];
+  }
+  return r;
+}
+
+// numpy.linspace(0, 1, num)
+std::vector<double> np_linspace01(int num) {
+  std::vector<double> x((size_t)num);
+  const double step = 1.0 / (double)(num - 1);
+  for (int i = 0; i < num; ++i) x[(size_t)i] = (double)i * step;
+  x[(size_t)num - 1] = 1.0;
+  return x;
+}
+
+void det_ap(const uint32_t* tp_in, const float* conf_in, const float* cls_in, int n_rows, const float* label_cls, int n_labels, int n_iou, vp_metric_det_summary* s) {
+  const double eps = 1e-16;
+  const int frames = s->frames;
+  std::memset(s, 0, sizeof(*s));
+  s->frames = frames;
+  s->rows = n_rows;
+  s->labels = n_labels;
+  s->n_iou = n_iou;
+  s->grid_index = -1;
+  // unique_classes, nt = numpy.unique(target, return_counts=True)
+  std::vector<float> uc(label_cls, label_cls + n_labels);
+  std::sort(uc.begin(), uc.end());
+  std::vector<double> nt;
+  {
+    std::vector<float> u;
+    for (float v : uc) {
+      if (u.empty() || u.back() != v) {
+        u.push_back(v);
+        nt.push_back(0.0);
+      }
+      nt.back() += 1.0;
+    }
+    uc.swap(u);
+  }
+  const int nc = (int)uc.size();
+  s->classes = nc;
+  for (int ci = 0; ci < nc && ci < VP_DET_MAX_CLASSES; ++ci) {
+    s->class_id[ci] = uc[(size_t)ci];
+    s->class_labels[ci] = (uint32_t)nt[(size_t)ci];
+  }
+  const uint32_t mask = n_iou >= 32 ? 0xFFFFFFFFu : (1u << n_iou) - 1u;
+  bool any = false;
+  for (int i = 0; i < n_rows; ++i) any = any || (tp_in[i] & mask) != 0;
+  if (!any || nc == 0) return;   // the trainer's `metrics[0].any()`: the scores stay 0
+  // i = numpy.argsort(-conf)
+  std::vector<int> order((size_t)n_rows);
+  for (int i = 0; i < n_rows; ++i) order[(size_t)i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return -conf_in[a] < -conf_in[b]; });
+  const std::vector<double> px = np_linspace01(1000), x101 = np_linspace01(101);
+  std::vector<std::vector<double>> p((size_t)nc, std::vector<double>(1000, 0.0)), r((size_t)nc, std::vector<double>(1000, 0.0)), ap((size_t)nc, std::vector<double>((size_t)n_iou, 0.0));
+  for (int ci = 0; ci < nc; ++ci) {
+    std::vector<int> idx;
+    for (int k : order)
+      if (cls_in[k] == uc[(size_t)ci]) idx.push_back(k);
+    const double nl = nt[(size_t)ci];
+    const size_t no = idx.size();
+    if (no == 0 || nl == 0.0) continue;
+    std::vector<double> neg_conf(no);
+    for (size_t k = 0; k < no; ++k) neg_conf[k] = (double)(-conf_in[idx[k]]);
+    std::vector<double> recall(no), precision(no), m_rec(no + 2), m_pre(no + 2), y(101);
+    for (int j = 0; j < n_iou; ++j) {
+      long long tpc = 0, fpc = 0;
+      for (size_t k = 0; k < no; ++k) {
+        const int t = (int)((tp_in[idx[k]] >> j) & 1u);
+        tpc += t;
+        fpc += 1 - t;
+        recall[k] = (double)tpc / (nl + eps);
+        precision[k] = (double)tpc / (double)(tpc + fpc);
+      }
+      if (j == 0)
+        for (int g = 0; g < 1000; ++g) {
+          r[(size_t)ci][(size_t)g] = np_interp(-px[(size_t)g], neg_conf, recall, 0.0, recall[no - 1]);
+          p[(size_t)ci][(size_t)g] = np_interp(-px[(size_t)g], neg_conf, precision, 1.0, precision[no - 1]);
+        }
+      m_rec[0] = 0.0;
+      m_pre[0] = 1.0;
+      for (size_t k = 0; k < no; ++k) {
+        m_rec[k + 1] = recall[k];
+        m_pre[k + 1] = precision[k];
+      }
+      m_rec[no + 1] = 1.0;
+      m_pre[no + 1] = 0.0;
+      for (size_t k = no + 1; k-- > 0;) m_pre[k] = std::max(m_pre[k], m_pre[k + 1]);   // the precision envelope
+      for (int g = 0; g < 101; ++g) y[(size_t)g] = np_interp(x101[(size_t)g], m_rec, m_pre, m_pre[0], m_pre[no + 1]);
+      double area = 0.0;   // numpy.trapz
+      for (int g = 0; g < 100; ++g) area += (x101[(size_t)g + 1] - x101[(size_t)g]) * (y[(size_t)g + 1] + y[(size_t)g]) / 2.0;
+      ap[(size_t)ci][(size_t)j] = area;
+    }
+  }
+  // f1 = 2 * p * r / (p + r + eps);  i = smooth(f1.mean(0), 0.1).argmax()
+  std::vector<double> mean_f1(1000);
+  for (int g = 0; g < 1000; ++g) {
+    double acc = 0.0;
+    for (int ci = 0; ci < nc; ++ci) {
+      const double pv = p[(size_t)ci][(size_t)g], rv = r[(size_t)ci][(size_t)g];
+      const double f1 = 2.0 * pv * rv / (pv + rv + eps);
+      acc = ci == 0 ? f1 : acc + f1;
+    }
+    mean_f1[(size_t)g] = acc / (double)nc;
+  }
+  const int nf = 101, half = nf / 2;   // round(1000 * 0.1 * 2) // 2 + 1
+  std::vector<double> yp((size_t)(1000 + 2 * half));
+  for (int k = 0; k < half; ++k) {
+    yp[(size_t)k] = 1.0 * mean_f1[0];
+    yp[(size_t)(half + 1000 + k)] = 1.0 * mean_f1[999];
+  }
+  for (int g = 0; g < 1000; ++g) yp[(size_t)(half + g)] = mean_f1[(size_t)g];
+  const double tap = 1.0 / (double)nf;
+  int best = 0;
+  double best_v = 0.0;
+  for (int g = 0; g < 1000; ++g) {
+    double acc = 0.0;
+    for (int k = 0; k < nf; ++k) acc += yp[(size_t)(g + k)] * tap;
+    if (g == 0 || acc > best_v) {
+      best = g;
+      best_v = acc;
+    }
+  }
+  s->grid_index = best;
+  double sp = 0.0, sr = 0.0, s50 = 0.0, sap = 0.0;
+  for (int ci = 0; ci < nc; ++ci) {
+    const double pv = p[(size_t)ci][(size_t)best], rv = r[(size_t)ci][(size_t)best];
+    const double tpv = std::nearbyint(rv * nt[(size_t)ci]), fpv = std::nearbyint(tpv / (pv + eps) - tpv);
+    double a = 0.0;
+    for (int j = 0; j < n_iou; ++j) a += ap[(size_t)ci][(size_t)j];
+    a /= (double)n_iou;
+    sp += pv;
+    sr += rv;
+    s50 += ap[(size_t)ci][0];
+    sap += a;
+    if (ci < VP_DET_MAX_CLASSES) {
+      s->ap50[ci] = ap[(size_t)ci][0];
+      s->ap[ci] = a;
+      s->tp[ci] = tpv;
+      s->fp[ci] = fpv;
+    }
+  }
+  s->precision = sp / (double)nc;
+  s->recall = sr / (double)nc;
+  s->map50 = s50 / (double)nc;
+  s->map = sap / (double)nc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1735,6 +1902,58 @@ int vp_metric_add_seg_logits(vp_metric* m, const float* logits_chw, int on_devic
 
 int vp_metric_add_depth_plane(vp_metric* m, const float* pred, int pred_on_device, const float* gt, int gt_on_device, int h, int w) {
   return metric_guarded(m, [&](vp::Metric& g) { g.add_depth_plane(pred, pred_on_device != 0, gt, gt_on_device != 0, h, w); });
+}
+
+// ---- the detector part
+int vp_metric_add_det(vp_metric* m, vp_engine* e, const float* labels, int n_labels, float conf, float iou, const float* iou_v, int n_iou) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_det(metric_engine(e, "vp_metric_add_det"), labels, n_labels, conf, iou, iou_v, n_iou); });
+}
+
+int vp_metric_add_det_pair(vp_metric* m, vp_engine* e, vp_engine* ref, float label_conf, float conf, float iou, const float* iou_v, int n_iou) {
+  return metric_guarded(m, [&](vp::Metric& g) {
+    g.add_det_pair(metric_engine(e, "vp_metric_add_det_pair"), metric_engine(ref, "vp_metric_add_det_pair"), label_conf, conf, iou, iou_v, n_iou);
+  });
+}
+
+int vp_metric_add_det_raw(vp_metric* m, const float* raw, int on_device, int nc, int nb, int net_h, int net_w, const float* labels, int n_labels, float conf, float iou,
+                          const float* iou_v, int n_iou) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_det_raw(raw, on_device != 0, nc, nb, net_h, net_w, labels, n_labels, conf, iou, iou_v, n_iou); });
+}
+
+int vp_metric_det_frames(const vp_metric* m) { return m && m->impl ? m->impl->det_frames() : VP_ERR_ARG; }
+
+int vp_metric_fetch_det(vp_metric* m, vp_metric_det_frame* frames_out, int frames_cap, vp_metric_det_row* rows_out, int rows_cap, vp_metric_det_summary* summary) {
+  return metric_guarded(m, [&](vp::Metric& g) {
+    if (frames_cap < 0 || rows_cap < 0 || (frames_cap > 0 && !frames_out) || (rows_cap > 0 && !rows_out))
+      throw std::invalid_argument("vp_metric_fetch_det: a negative capacity, or a null buffer with a capacity above 0");
+    g.fetch_det(&m->det_frames, &m->det_rows, &m->det_label_cls);
+    const size_t nf = std::min((size_t)frames_cap, m->det_frames.size()), nr = std::min((size_t)rows_cap, m->det_rows.size());
+    if (nf) std::memcpy(frames_out, m->det_frames.data(), nf * sizeof(vp_metric_det_frame));
+    if (nr) std::memcpy(rows_out, m->det_rows.data(), nr * sizeof(vp_metric_det_row));
+    if (summary) {
+      const size_t n = m->det_rows.size();
+      std::vector<uint32_t> tp(n);
+      std::vector<float> conf(n), cls(n);
+      for (size_t i = 0; i < n; ++i) {
+        tp[i] = m->det_rows[i].tp;
+        conf[i] = m->det_rows[i].conf;
+        cls[i] = m->det_rows[i].cls;
+      }
+      summary->frames = (int)m->det_frames.size();
+      det_ap(tp.data(), conf.data(), cls.data(), (int)n, m->det_label_cls.data(), (int)m->det_label_cls.size(), std::max(1, g.det_n_iou()), summary);
+    }
+  });
+}
+
+int vp_metric_det_ap(const uint32_t* tp, const float* conf, const float* det_cls, int n_rows, const float* label_cls, int n_labels, int n_iou, vp_metric_det_summary* summary) {
+  if (!summary || n_rows < 0 || n_labels < 0 || n_iou < 1 || n_iou > VP_DET_MAX_IOU || (n_rows > 0 && (!tp || !conf || !det_cls)) || (n_labels > 0 && !label_cls)) return VP_ERR_ARG;
+  try {
+    summary->frames = 0;
+    det_ap(tp, conf, det_cls, n_rows, label_cls, n_labels, n_iou, summary);
+    return VP_OK;
+  } catch (const std::exception&) {
+    return VP_ERR_STATE;
+  }
 }
 
 }  // extern "C"
@@ -2305,6 +2524,43 @@ int vp_op_select_f32(int gpu_id, const float* values, int n, int k, float* out, 
     unsigned got[2];
     g.copy_d2h(got, d_out, sizeof(got));
     std::memcpy(out, got, sizeof(float));
+  });
+}
+
+// ---- the detector validation's candidate / rank / suppression chain alone (unit tests)
+int vp_op_detect_validate(int gpu_id, const float* raw, int nc, int nb, float conf, float iou, float* rows_out, int cap, uint32_t* counts_out, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!raw || !counts_out || cap < 0 || (cap > 0 && !rows_out) || nc < 1 || nc > vp::kDetValMaxClasses || nb < 1 || nb > vp::kDetValMaxBoxes ||
+        (long long)nb * nc > (long long)vp::kDetValMaxPairs || conf != conf || iou != iou)
+      throw std::invalid_argument("vp_op_detect_validate: bad argument (nc 1 .. 80, nb 1 .. 16384, nb * nc <= 131072, thresholds not NaN)");
+    vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
+    const size_t words = (size_t)(4 + nc) * nb;
+    float* d_raw = g.alloc_f32(words);
+    uint8_t* d_scratch = reinterpret_cast<uint8_t*>(g.alloc_f32(vp::det_val_scratch_bytes((unsigned)nb, (unsigned)nc) / sizeof(float)));
+    float* d_rows = g.alloc_f32((size_t)vp::kDetValMaxDet * vp::kDetValRowWords);
+    unsigned* d_counts = reinterpret_cast<unsigned*>(g.alloc_f32(4));
+    g.copy_h2d(d_raw, raw, words * sizeof(float));
+    vp::DetValParams q{};
+    q.raw = d_raw;
+    q.nb = (unsigned)nb;
+    q.nc = (unsigned)nc;
+    q.conf = conf;
+    q.iou = iou;
+    q.max_nms = vp::kDetValMaxNms;
+    q.max_det = vp::kDetValMaxDet;
+    vp::det_val_carve(d_scratch, &q);
+    q.rows = d_rows;
+    q.counts = d_counts;
+    VP_HIP_CHECK(vp::launch_det_validate(q, g.stream()));
+    unsigned counts[3];
+    g.copy_d2h(counts, d_counts, sizeof(counts));
+    for (int i = 0; i < 3; ++i) counts_out[i] = counts[i];
+    const size_t n = std::min((size_t)cap, (size_t)counts[2]);
+    if (n) {
+      std::vector<float> rows((size_t)counts[2] * vp::kDetValRowWords);
+      g.copy_d2h(rows.data(), d_rows, rows.size() * sizeof(float));
+      for (size_t r = 0; r < n; ++r) std::memcpy(rows_out + r * 6, rows.data() + r * vp::kDetValRowWords, 6 * sizeof(float));
+    }
   });
 }
 

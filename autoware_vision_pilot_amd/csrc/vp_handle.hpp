@@ -78,5 +78,9 @@ struct vp_canvas {
 struct vp_metric {
   std::unique_ptr<vp::Metric> impl;
   std::vector<vp_metric_frame> host;
+  // the detector part's last fetch: frame records, kept rows and label classes
+  std::vector<vp::DetFrameRecord> det_frames;
+  std::vector<vp::DetRowRecord> det_rows;
+  std::vector<float> det_label_cls;
   std::string err;
 };

@@ -206,6 +206,13 @@ _SIGS = {
     "vp_metric_add_seg_logits": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "vp_metric_add_depth_plane": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
     "vp_op_select_f32": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_char_p, C.c_size_t]),
+    "vp_metric_add_det": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.c_float, _P, C.c_int]),
+    "vp_metric_add_det_pair": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_float, _P, C.c_int]),
+    "vp_metric_add_det_raw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_float, _P, C.c_int]),
+    "vp_metric_det_frames": (C.c_int, [_P]),
+    "vp_metric_fetch_det": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P]),
+    "vp_metric_det_ap": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "vp_op_detect_validate": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, C.c_char_p, C.c_size_t]),
 }
 # multi-camera exchange (csrc/vp_comm.cpp): part of libvp_hip.so, absent from the CPU-emulated test build
 _COMM_SIGS = {
@@ -292,6 +299,44 @@ class MetricSummary(C.Structure):
 
 METRIC_FRAME_DTYPE = np.dtype([("kind", "<i4"), ("I", "<u4", (3,)), ("P", "<u4", (3,)), ("G", "<u4", (3,)), ("nonfinite", "<u4"), ("n", "<u4"), ("kept", "<u4"),
                                ("q_lo", "<f4"), ("q_hi", "<f4"), ("q", "<f4"), ("mae", "<f4"), ("mel", "<f4")])
+
+
+VP_DET_MAX_NMS, VP_DET_MAX_DET, VP_DET_MAX_CLASSES, VP_DET_MAX_IOU, VP_DET_MAX_LABELS = 30000, 300, 80, 16, 4096
+DET_CONF, DET_IOU = 0.001, 0.65          # the trainer's validation thresholds (auto_speed_util.py:123)
+# torch.linspace(0.5, 0.95, 10), from its bits
+DET_IOU_V = np.array([0x3F000000, 0x3F0CCCCD, 0x3F19999A, 0x3F266666, 0x3F333333, 0x3F400000, 0x3F4CCCCD, 0x3F59999A, 0x3F666666, 0x3F733333], dtype="<u4").view("<f4")
+METRIC_DET_FRAME_DTYPE = np.dtype([("candidates", "<u4"), ("ranked", "<u4"), ("kept", "<u4"), ("labels", "<u4"), ("first_row", "<u4")])
+METRIC_DET_ROW_DTYPE = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("conf", "<f4"), ("cls", "<f4"), ("tp", "<u4")])
+
+
+class MetricDetSummary(C.Structure):
+    """vp_metric_det_summary (include/vp_hip.h)"""
+    _fields_ = [("frames", C.c_int), ("rows", C.c_int), ("labels", C.c_int), ("classes", C.c_int), ("n_iou", C.c_int), ("grid_index", C.c_int),
+                ("precision", C.c_double), ("recall", C.c_double), ("map50", C.c_double), ("map", C.c_double),
+                ("class_id", C.c_float * VP_DET_MAX_CLASSES), ("class_labels", C.c_uint32 * VP_DET_MAX_CLASSES), ("ap50", C.c_double * VP_DET_MAX_CLASSES),
+                ("ap", C.c_double * VP_DET_MAX_CLASSES), ("tp", C.c_double * VP_DET_MAX_CLASSES), ("fp", C.c_double * VP_DET_MAX_CLASSES)]
+
+
+def _det_summary_dict(s):
+    n = min(s.classes, VP_DET_MAX_CLASSES)
+    return {"frames": s.frames, "rows": s.rows, "labels": s.labels, "classes": s.classes, "n_iou": s.n_iou, "grid_index": s.grid_index, "precision": s.precision,
+            "recall": s.recall, "map50": s.map50, "map": s.map, "class_id": np.array(s.class_id[:n], dtype=np.float32), "class_labels": np.array(s.class_labels[:n], dtype=np.uint32),
+            "ap50": np.array(s.ap50[:n]), "ap": np.array(s.ap[:n]), "tp": np.array(s.tp[:n]), "fp": np.array(s.fp[:n])}
+
+
+def _det_table(iou_v):
+    t = np.ascontiguousarray(DET_IOU_V if iou_v is None else iou_v, dtype=np.float32).reshape(-1)
+    return t, _ptr(t), int(t.size)
+
+
+def _det_labels(labels):
+    """(array [n][5] or None, pointer, n): rows cls, cx, cy, w, h normalised to the network input"""
+    if labels is None or np.size(labels) == 0:
+        return None, None, 0
+    lb = np.ascontiguousarray(labels, dtype=np.float32)
+    if lb.ndim != 2 or lb.shape[1] != 5:
+        raise ValueError("labels: rows [cls, cx, cy, w, h]")
+    return lb, _ptr(lb), int(lb.shape[0])
 
 
 class CameraPose(C.Structure):
@@ -1262,6 +1307,42 @@ class Metric:
             raise ValueError("add_depth_plane: two planes [h][w] of one size")
         self._ck(self._lib.vp_metric_add_depth_plane(self._h, _ptr(p), 0, _ptr(g), 0, p.shape[0], p.shape[1]))
 
+    def det_frames(self):
+        return self._ck(self._lib.vp_metric_det_frames(self._h))
+
+    def add_det(self, engine, labels, conf=DET_CONF, iou=DET_IOU, iou_v=None):
+        """the detector's validation record of a VP_AUTOSPEED engine's last pass; labels: rows [cls, cx, cy, w, h] normalised to the network input (or None)"""
+        lb, lp, n = _det_labels(labels)
+        t, tp, nt = _det_table(iou_v)
+        self._ck(self._lib.vp_metric_add_det(self._h, engine._h, lp, n, conf, iou, tp, nt))
+
+    def add_det_pair(self, engine, ref, label_conf=0.25, conf=DET_CONF, iou=DET_IOU, iou_v=None):
+        """ref's own kept rows with score > label_conf are the labels"""
+        t, tp, nt = _det_table(iou_v)
+        self._ck(self._lib.vp_metric_add_det_pair(self._h, engine._h, ref._h, label_conf, conf, iou, tp, nt))
+
+    def add_det_raw(self, raw, labels, net_hw=(512, 1024), conf=DET_CONF, iou=DET_IOU, iou_v=None, device_shape=None):
+        """raw fp32 [4 + nc][nb]: a numpy array, or (with device_shape = (nc, nb)) a device pointer (int)"""
+        lb, lp, n = _det_labels(labels)
+        t, tp, nt = _det_table(iou_v)
+        if device_shape is not None:
+            nc, nb = (int(v) for v in device_shape)
+            self._ck(self._lib.vp_metric_add_det_raw(self._h, _P(int(raw)), 1, nc, nb, int(net_hw[0]), int(net_hw[1]), lp, n, conf, iou, tp, nt))
+            return
+        x = np.ascontiguousarray(raw, dtype=np.float32)
+        if x.ndim != 2 or x.shape[0] < 5:
+            raise ValueError("add_det_raw: a tensor [4 + nc][nb]")
+        self._ck(self._lib.vp_metric_add_det_raw(self._h, _ptr(x), 0, x.shape[0] - 4, x.shape[1], int(net_hw[0]), int(net_hw[1]), lp, n, conf, iou, tp, nt))
+
+    def fetch_det(self):
+        """(frames, rows, summary): numpy arrays of METRIC_DET_FRAME_DTYPE and METRIC_DET_ROW_DTYPE (frame f's rows: rows[first_row : first_row + kept]) and a dict"""
+        n = self.det_frames()
+        fr = np.zeros(n, dtype=METRIC_DET_FRAME_DTYPE)
+        rows = np.zeros(n * VP_DET_MAX_DET, dtype=METRIC_DET_ROW_DTYPE)
+        s = MetricDetSummary()
+        self._ck(self._lib.vp_metric_fetch_det(self._h, _ptr(fr) if n else None, n, _ptr(rows) if n else None, rows.size, C.byref(s)))
+        return fr, rows[:s.rows].copy(), _det_summary_dict(s)
+
     def fetch(self):
         n = self.frames()
         rec = np.zeros(n, dtype=METRIC_FRAME_DTYPE)
@@ -1282,6 +1363,37 @@ def select_f32(values, k, gpu_id=0):
     if rc != 0:
         raise (ValueError if rc == -1 else VpError)(f"vp_op_select_f32 failed ({rc}): {err.value.decode(errors='replace')}")
     return np.float32(out.value)
+
+
+def detect_validate(raw, conf=DET_CONF, iou=DET_IOU, gpu_id=0):
+    """vp_op_detect_validate: the validation post-process's candidate / rank / suppression part on raw fp32 [4 + nc][nb] -> (rows [kept][6] x1, y1, x2, y2,
+    score, cls; counts {candidates, ranked, kept})"""
+    x = np.ascontiguousarray(raw, dtype=np.float32)
+    if x.ndim != 2 or x.shape[0] < 5:
+        raise ValueError("detect_validate: a tensor [4 + nc][nb]")
+    rows = np.zeros((VP_DET_MAX_DET, 6), dtype=np.float32)
+    counts = np.zeros(3, dtype=np.uint32)
+    err = C.create_string_buffer(512)
+    rc = load().vp_op_detect_validate(gpu_id, _ptr(x), x.shape[0] - 4, x.shape[1], conf, iou, _ptr(rows), VP_DET_MAX_DET, _ptr(counts), err, len(err))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_op_detect_validate failed ({rc}): {err.value.decode(errors='replace')}")
+    return rows[:int(counts[2])].copy(), {"candidates": int(counts[0]), "ranked": int(counts[1]), "kept": int(counts[2])}
+
+
+def det_ap(tp, conf, det_cls, label_cls, n_iou=10):
+    """vp_metric_det_ap: compute_ap on the host, no device -- tp words (bit t: correct at threshold t), conf and classes per kept row, the label classes"""
+    tpw = np.ascontiguousarray(tp, dtype=np.uint32).reshape(-1)
+    cf = np.ascontiguousarray(conf, dtype=np.float32).reshape(-1)
+    dc = np.ascontiguousarray(det_cls, dtype=np.float32).reshape(-1)
+    lc = np.ascontiguousarray(label_cls, dtype=np.float32).reshape(-1)
+    if not (tpw.size == cf.size == dc.size):
+        raise ValueError("det_ap: tp, conf and det_cls have one entry per kept row")
+    s = MetricDetSummary()
+    rc = load().vp_metric_det_ap(_ptr(tpw) if tpw.size else None, _ptr(cf) if cf.size else None, _ptr(dc) if dc.size else None, tpw.size, _ptr(lc) if lc.size else None, lc.size,
+                                 int(n_iou), C.byref(s))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_metric_det_ap failed ({rc})")
+    return _det_summary_dict(s)
 
 
 def decode_logits_host(logits_chw, decode_mode=VP_DECODE_SEG_MASK, gpu_id=0):

@@ -732,6 +732,92 @@ int vp_metric_add_seg_logits(vp_metric* m, const float* logits_chw, int on_devic
 int vp_metric_add_depth_plane(vp_metric* m, const float* pred, int pred_on_device, const float* gt, int gt_on_device, int h, int w);
 int vp_op_select_f32(int gpu_id, const float* values, int n, int k, float* out, char* err, size_t err_len);
 
+/* ---- vp_metric: the detector's validation mAP --------------------------------------------------------------------------------------
+ * The detector's trainer validates with non_max_suppression at conf 0.001 / iou 0.65, compute_metric and compute_ap (Models/training/
+ * auto_speed_trainer.py:176-229, auto_speed_util.py:99-169, 225-300): precision, recall, mAP@50 and mAP.  That post-process is NOT the inference one
+ * (vp_detect_postprocess*): it is multi-label, offsets boxes per class, ranks up to 43 008 candidates and keeps at most 300.  The same vp_metric handle
+ * accumulates it: one small record, the kept rows and the label classes per frame on the device, ONE vp_metric_fetch_det per dataset run.  Detector
+ * records are counted apart (vp_metric_det_frames); vp_metric_fetch / _frames / vp_metric_frame / vp_metric_summary know nothing of them.
+ * THE PER-FRAME STAGE.  Input: raw[4 + nc][nb] fp32, rows cx, cy, w, h, score_0 .. score_{nc-1}; nc 1 .. 80, nb 1 .. 16384, nb * nc <= 131072.  Every
+ *   floating operation below is a single IEEE fp32 operation in the order written, without contraction.
+ *   Candidates: every pair (box i, class c) with score > conf; a NaN score is no candidate.  Candidate order is i major, c minor (nc == 1: the
+ *     reference's "best class" branch gives the same set).
+ *   Rank: by descending score.  TIE DEFINITION 1: equal scores keep candidate order (the reference's argsort leaves it open).  The first
+ *     VP_DET_MAX_NMS candidates go on (`ranked`); `candidates` reports how many there were.
+ *   Corners: x1 = cx - w / 2, y1 = cy - h / 2, x2 = cx + w / 2, y2 = cy + h / 2.  The suppression box is each corner + (float)c * 7680.0f.
+ *   Suppression: greedy in rank order with torchvision's rule on the offset boxes: iw = max(0, min(x2) - max(x1)), ih likewise (fmaxf / fminf),
+ *     inter = iw * ih; a later box j is suppressed by a kept box i when inter / (area_i + area_j - inter) > iou.  0 / 0 is NaN and suppresses
+ *     nothing.  It stops when VP_DET_MAX_DET boxes are kept or the list ends.
+ *   Output: per kept row the un-offset corners, the score and the class.
+ *   Labels: n_labels (0 .. 4096) rows [cls, cx, cy, w, h] in the reference's dataset form, normalised to the network input W x H; the device forms the
+ *     corners as above and multiplies by (W, H, W, H).
+ *   Matching (compute_metric): for label l and detection d, iw = min(x2_l, x2_d) - max(x1_l, x1_d) and ih likewise, each replaced by 0 when negative
+ *     (a NaN stays), inter = iw * ih, iou = inter / (((area_l + area_d) - inter) + 1e-7f), areas = (x2 - x1) * (y2 - y1).  For threshold t of the
+ *     caller's table iou_v[n_iou] (n_iou 1 .. 16) a pair is eligible when iou >= t and cls_l == cls_d as floats.  Each detection's best label is its
+ *     eligible pair of highest IoU (TIE DEFINITION 2: of equal IoUs the label of lowest index; the reference leaves it to an unstable argsort).  Among
+ *     the detections whose best label is l, the one of LOWEST INDEX (highest score) is correct at t -- not the one of highest IoU: this is what the two
+ *     numpy.unique(..., return_index=True) calls of compute_metric leave, and it is NOT the usual greedy rule.  Bit t of the row's `tp` word says so.
+ *   Threshold table: the library takes it from the caller and does not recompute it.  The trainer's is torch.linspace(0.5, 0.95, 10), whose bits are
+ *     3f000000 3f0ccccd 3f19999a 3f266666 3f333333 3f400000 3f4ccccd 3f59999a 3f666666 3f733333.  One table per dataset run: an add with another table
+ *     than the records so far is refused.
+ *   Frame bookkeeping (auto_speed_trainer.py:208-219): a frame with no kept row and no label adds nothing to the dataset; no kept row but labels: only
+ *     its label classes; kept rows and no labels: its rows with tp = 0.  Every frame still gets its vp_metric_det_frame.
+ * DEPARTURE: the trainer's validate() runs the model and the NMS in half precision.  This stage scores the engine's fp32 tensor with fp32 arithmetic,
+ *   which is what non_max_suppression does on a float tensor.
+ * vp_metric_add_det: e is a VP_AUTOSPEED engine with a pass behind it; its raw tensor (vp_logits) is read on the device under the ordering contract of
+ *   vp_metric_add_seg.  labels are host floats, copied before the call returns; n_labels may be 0 (labels may then be NULL).  W x H is the engine's input.
+ * vp_metric_add_det_pair: the labels are ref's own kept rows (the same stage on ref's tensor at conf / iou) with score > label_conf, formed on the
+ *   device; they are in pixels already.
+ * vp_metric_add_det_raw: the operator entry on a caller's tensor, in host memory (copied before return) or, on_device != 0, device memory on the
+ *   metric's GPU.
+ * vp_metric_det_frames: detector frames added since the last reset.  Capacity: min(max_frames, 16384) frames and 64 labels per frame of capacity
+ *   (+ 4096) in all; the pair form counts 300 labels per frame against it.  vp_metric_reset empties the detector storage too.
+ * vp_metric_fetch_det: the one synchronisation.  Copies the first min(frames_cap, frames) frame records and the first min(rows_cap, rows) kept rows
+ *   (frame f's rows are rows[first_row .. first_row + kept), in rank order) and fills *summary (may be NULL) from ALL of them.
+ * vp_metric_det_summary is computed on the host in double exactly as compute_ap does: rows sorted by -conf; the classes are those of the LABELS only,
+ *   ascending; cumulative sums; recall = tpc / (n_labels + 1e-16), precision = tpc / (tpc + fpc), both interpolated (numpy.interp) at
+ *   numpy.linspace(0, 1, 1000) over -conf with left = 0 / left = 1; per threshold the precision envelope, the 101-point interp and trapz; f1 =
+ *   2 p r / (p + r + 1e-16); grid_index = the first maximum of smooth(f1.mean(0), 0.1) (a 101-tap box filter over the edge-padded curve); precision and
+ *   recall are the class means at that index, tp = round(r * n_labels), fp = round(tp / (p + 1e-16) - tp) (half to even), map50 / map the class means
+ *   of ap50 / ap.  If no row has a tp bit set the four scores are 0 and grid_index is -1, as the trainer's `metrics[0].any()` decides.  The per-class
+ *   arrays hold the first VP_DET_MAX_CLASSES label classes; `classes` counts all and the means run over all.  The plots of compute_ap are not made.
+ * vp_metric_det_ap: the same host code over caller arrays (tp words, conf, detection classes [n_rows]; label classes [n_labels]); no device, no handle.
+ * vp_op_detect_validate: the candidate / rank / suppression part alone on a host tensor: rows [x1, y1, x2, y2, score, cls] (the first min(cap, kept)
+ *   of them) and counts_out = {candidates, ranked, kept}.
+ * Records are bit-identical from run to run: the one atomic slot counter only places keys that the rank (which depends on the SET of keys) reorders.
+ * ERRORS.  VP_ERR_ARG: another engine kind, an engine on another GPU, sizes beyond the limits above, n_iou outside 1 .. 16, another table than before, a
+ *   NaN threshold, a null pointer, a pair of different nc / nb.  VP_ERR_STATE: an engine with no pass yet, a full accumulator. */
+#define VP_DET_MAX_NMS 30000
+#define VP_DET_MAX_DET 300
+#define VP_DET_MAX_CLASSES 80
+#define VP_DET_MAX_IOU 16
+#define VP_DET_MAX_LABELS 4096
+typedef struct vp_metric_det_frame {
+  uint32_t candidates, ranked, kept, labels, first_row;
+} vp_metric_det_frame;
+typedef struct vp_metric_det_row {
+  float x1, y1, x2, y2, conf, cls;
+  uint32_t tp;                    /* bit t: correct at iou_v[t] */
+} vp_metric_det_row;
+typedef struct vp_metric_det_summary {
+  int frames, rows, labels;
+  int classes;                    /* distinct label classes */
+  int n_iou;
+  int grid_index;                 /* on the 1000-point confidence grid; -1: not scored */
+  double precision, recall, map50, map;
+  float class_id[VP_DET_MAX_CLASSES];
+  uint32_t class_labels[VP_DET_MAX_CLASSES];
+  double ap50[VP_DET_MAX_CLASSES], ap[VP_DET_MAX_CLASSES], tp[VP_DET_MAX_CLASSES], fp[VP_DET_MAX_CLASSES];
+} vp_metric_det_summary;
+int vp_metric_add_det(vp_metric* m, vp_engine* e, const float* labels, int n_labels, float conf, float iou, const float* iou_v, int n_iou);
+int vp_metric_add_det_pair(vp_metric* m, vp_engine* e, vp_engine* ref, float label_conf, float conf, float iou, const float* iou_v, int n_iou);
+int vp_metric_add_det_raw(vp_metric* m, const float* raw, int on_device, int nc, int nb, int net_h, int net_w, const float* labels, int n_labels, float conf, float iou,
+                          const float* iou_v, int n_iou);
+int vp_metric_det_frames(const vp_metric* m);
+int vp_metric_fetch_det(vp_metric* m, vp_metric_det_frame* frames_out, int frames_cap, vp_metric_det_row* rows_out, int rows_cap, vp_metric_det_summary* summary);
+int vp_metric_det_ap(const uint32_t* tp, const float* conf, const float* det_cls, int n_rows, const float* label_cls, int n_labels, int n_iou, vp_metric_det_summary* summary);
+int vp_op_detect_validate(int gpu_id, const float* raw, int nc, int nb, float conf, float iou, float* rows_out, int cap, uint32_t* counts_out, char* err, size_t err_len);
+
 /* ---- multi-camera result exchange (BASELINE configs[3]) ---------------------------------------
  * One process (or thread) per GPU, camera r on rank r, weights replicated, no data-path collective in the networks.  For the
  * fused ego-path / BEV consumer every rank needs all cameras' results: ONE ncclAllGather (RCCL over xGMI) per frame of a
