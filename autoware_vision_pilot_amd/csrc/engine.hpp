@@ -590,6 +590,21 @@ class Metric {
   void fetch_det(std::vector<DetFrameRecord>* frames, std::vector<DetRowRecord>* rows, std::vector<float>* label_cls);
   int det_n_iou() const { return det_n_iou_; }
   static constexpr int kDetFramesCap = 16384, kDetLabelsPerFrame = 64;
+  // the lane part (kernels.hpp MetricLanesParams / MetricRowsParams): records of their own, max_frames of each, storage allocated by the first add.
+  // gt_form: kLanesGtPlanes (fp32 [3][h][w]), kLanesGtBits (u8 [h][w]) or kLanesGtBits4x (u8 [4h][4w])
+  void add_lanes(Engine& e, const void* gt, bool gt_on_device, int gt_form);
+  void add_lanes_pair(Engine& e, Engine& ref);
+  void add_lanes_logits(const float* logits, bool on_device, int h, int w, const void* gt, bool gt_on_device, int gt_form);
+  int lanes_frames() const { return lanes_frames_; }
+  void fetch_lanes(LanesRecord* out, int count);
+  // targets: host floats [64] each, copied before the call returns; thr: the run's table (another one is refused until reset())
+  void add_rows(Engine& e, const float* target_xp, const float* target_h, const double* thr, int n_thr);
+  void add_rows_pair(Engine& e, Engine& ref, const double* thr, int n_thr);
+  void add_rows_raw(const float* xp, const float* hv, const float* target_xp, const float* target_h, int n_lines, int rows, const double* thr, int n_thr);
+  int rows_lines() const { return rows_lines_; }
+  int rows_n_thr() const { return rows_n_thr_; }
+  const double* rows_thr() const { return rows_thr_; }
+  void fetch_rows(RowsRecord* out, int count);
 
  private:
   struct Stage {   // a caller's pageable array: copied into one of two pinned slots before the call returns, then one H2D into `d`
@@ -632,6 +647,19 @@ class Metric {
   uint8_t* d_det_scratch_ = nullptr; // the chain's keys, ranks, order, boxes
   size_t det_scratch_cap_ = 0;
   Stage det_stage_;                  // host labels
+  // lane part
+  const Engine& lanes_source_of(Engine& e, const char* who) const;
+  const Engine& rows_source_of(Engine& e, const char* who) const;
+  LanesRecord* lanes_next(const char* who);
+  void lanes(const float* d_logits, const void* d_gt, int gt_form, int h, int w, LanesRecord* rec);
+  RowsRecord* rows_next(const char* who, int n_lines, const double* thr, int n_thr);
+  void rows(const float* xp, const float* hv, const float* txp, const float* thv, int n_lines, int n_rows, RowsRecord* rec);
+  int lanes_frames_ = 0, rows_lines_ = 0, rows_n_thr_ = 0;
+  double rows_thr_[kMetricRowsMaxThr] = {};
+  LanesRecord* d_lanes_records_ = nullptr;
+  RowsRecord* d_rows_records_ = nullptr;
+  uint8_t* d_lanes_scratch_ = nullptr;   // the partials, then the general path's D0 and pooled levels: see lanes()
+  size_t lanes_scratch_cap_ = 0;
 };
 
 #define VP_HIP_CHECK(expr)                                                                                   \

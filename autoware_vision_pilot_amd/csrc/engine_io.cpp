@@ -1185,6 +1185,11 @@ void Metric::release() {
     *p = nullptr;
   }
   det_scratch_cap_ = 0;
+  for (void** p : {reinterpret_cast<void**>(&d_lanes_records_), reinterpret_cast<void**>(&d_rows_records_), reinterpret_cast<void**>(&d_lanes_scratch_)}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  lanes_scratch_cap_ = 0;
   if (stream_) (void)hipStreamDestroy(stream_);
   stream_ = nullptr;
 }
@@ -1197,6 +1202,7 @@ void Metric::reset() {
   if (d_det_small_) VP_HIP_CHECK(hipMemsetAsync(d_det_small_, 0, 2 * sizeof(unsigned), stream_));   // the running totals
   det_frames_ = det_n_iou_ = 0;
   det_labels_bound_ = 0;
+  lanes_frames_ = rows_lines_ = rows_n_thr_ = 0;   // their kernels store whole records
 }
 
 // a device buffer that has to grow is freed only once the metric's own work has run
@@ -1544,6 +1550,190 @@ void Metric::fetch_det(std::vector<DetFrameRecord>* frames, std::vector<DetRowRe
   label_cls->assign((size_t)totals[1], 0.0f);
   if (totals[0]) VP_HIP_CHECK(hipMemcpyAsync(rows->data(), d_det_rows_, (size_t)totals[0] * sizeof(DetRowRecord), hipMemcpyDeviceToHost, stream_));
   if (totals[1]) VP_HIP_CHECK(hipMemcpyAsync(label_cls->data(), d_det_label_cls_, (size_t)totals[1] * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+// ---- the lane part: EgoLanes records and AutoSteer line records of their own, allocated by the first add
+const Engine& Metric::lanes_source_of(Engine& e, const char* who) const {
+  const std::string me(who);
+  if (e.gpu_ != gpu_) throw std::invalid_argument(me + ": the engine lives on GPU " + std::to_string(e.gpu_) + ", the metric on GPU " + std::to_string(gpu_));
+  if (e.kind_ != 3) throw std::invalid_argument(me + ": VP_EGOLANES engines only (the three lane planes of its logits)");
+  if (e.frames_ > 1) throw std::invalid_argument(me + ": a batched encoder has no outputs of its own (score its per-camera heads)");
+  if (!e.have_outputs_) throw std::runtime_error("Inference has not been run yet");
+  if (!e.d_logits_ || e.out_c_ != 3) throw std::invalid_argument(me + ": the engine has no logits of three planes");
+  return e;
+}
+
+const Engine& Metric::rows_source_of(Engine& e, const char* who) const {
+  const std::string me(who);
+  if (e.gpu_ != gpu_) throw std::invalid_argument(me + ": the engine lives on GPU " + std::to_string(e.gpu_) + ", the metric on GPU " + std::to_string(gpu_));
+  if (e.kind_ != 6) throw std::invalid_argument(me + ": VP_AUTOSTEER engines only (the lane rows xp / h_vector of its logits)");
+  if (!e.have_outputs_) throw std::runtime_error("Inference has not been run yet");
+  if (!e.d_logits_ || e.out_c_ != 2 || e.out_w_ != 1 || e.out_h_ < 1 || e.out_h_ > kMetricRowsMaxRows) throw std::invalid_argument(me + ": the engine has no xp / h_vector rows");
+  return e;
+}
+
+static void metric_check_lanes_args(const char* who, const void* logits, int h, int w, const void* gt, int gt_form) {
+  const std::string me(who);
+  if (!logits || !gt) throw std::invalid_argument(me + ": null logits or null ground truth");
+  if (gt_form < kLanesGtPlanes || gt_form > kLanesGtBits4x) throw std::invalid_argument(me + ": gt_form " + std::to_string(gt_form) + " (VP_LANES_GT_PLANES, VP_LANES_GT_BITS, VP_LANES_GT_BITS_4X)");
+  if (h < kMetricLanesMinSide || w < kMetricLanesMinSide)
+    throw std::invalid_argument(me + ": planes of " + std::to_string(h) + " x " + std::to_string(w) + " (the four 2x2 pools need 16 x 16 at least)");
+  if ((long long)h * w > (long long)kMetricLanesMaxN) throw std::invalid_argument(me + ": h * w above 2^22");
+}
+
+static size_t lanes_gt_bytes(int gt_form, int h, int w) {
+  const size_t n = (size_t)h * w;
+  return gt_form == kLanesGtPlanes ? 3 * sizeof(float) * n : (gt_form == kLanesGtBits ? n : 16 * n);
+}
+
+LanesRecord* Metric::lanes_next(const char* who) {
+  if (lanes_frames_ >= max_frames_)
+    throw std::runtime_error(std::string(who) + ": the lanes accumulator is full (" + std::to_string(max_frames_) + " frames; vp_metric_fetch_lanes, then vp_metric_reset)");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (!d_lanes_records_) VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_lanes_records_), (size_t)max_frames_ * sizeof(LanesRecord)));
+  return d_lanes_records_ + lanes_frames_;
+}
+
+// scratch: the partials [3][7][kMetricBlocks] doubles, then (h * w above kMetricLanesLdsN) D0 [3][n] and the pooled levels [3][metric_lanes_pooled_elems]
+void Metric::lanes(const float* d_logits, const void* d_gt, int gt_form, int h, int w, LanesRecord* rec) {
+  const size_t n = (size_t)h * w, pe = metric_lanes_pooled_elems(h, w);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const bool general = n > kMetricLanesLdsN;
+  const size_t o_d0 = up(3 * 7 * kMetricBlocks * sizeof(double)), o_pool = o_d0 + (general ? up(12 * n) : 0), total = o_pool + (general ? up(12 * pe) : 0);
+  grow(d_lanes_scratch_, lanes_scratch_cap_, total);
+  if ((reinterpret_cast<uintptr_t>(d_logits) & 3) || (gt_form != kLanesGtBits && (reinterpret_cast<uintptr_t>(d_gt) & 3)))
+    throw std::invalid_argument("vp_metric lanes: device logits or ground truth not aligned to 4 bytes");
+  MetricLanesParams q{};
+  q.logits = d_logits;
+  q.gt = d_gt;
+  q.gt_form = gt_form;
+  q.h = h;
+  q.w = w;
+  q.part = reinterpret_cast<double*>(d_lanes_scratch_);
+  q.d0 = general ? reinterpret_cast<float*>(d_lanes_scratch_ + o_d0) : nullptr;
+  q.pooled = general ? reinterpret_cast<float*>(d_lanes_scratch_ + o_pool) : nullptr;
+  q.rec = rec;
+  VP_HIP_CHECK(launch_metric_lanes(q, stream_));
+}
+
+void Metric::add_lanes(Engine& e, const void* gt, bool gt_on_device, int gt_form) {
+  lanes_source_of(e, "vp_metric_add_lanes");
+  metric_check_lanes_args("vp_metric_add_lanes", e.d_logits_, e.out_h_, e.out_w_, gt, gt_form);
+  LanesRecord* rec = lanes_next("vp_metric_add_lanes");
+  const void* d_gt = gt_on_device ? gt : stage_host(stage_[1], gt, lanes_gt_bytes(gt_form, e.out_h_, e.out_w_));
+  wait_for(e, ev_src_[0]);
+  lanes(e.d_logits_, d_gt, gt_form, e.out_h_, e.out_w_, rec);
+  release_to(e, ev_read_[0]);
+  ++lanes_frames_;
+}
+
+void Metric::add_lanes_pair(Engine& e, Engine& ref) {
+  lanes_source_of(e, "vp_metric_add_lanes_pair");
+  lanes_source_of(ref, "vp_metric_add_lanes_pair");
+  if (e.out_h_ != ref.out_h_ || e.out_w_ != ref.out_w_) throw std::invalid_argument("vp_metric_add_lanes_pair: the two engines are of different output sizes");
+  metric_check_lanes_args("vp_metric_add_lanes_pair", e.d_logits_, e.out_h_, e.out_w_, ref.d_logits_, kLanesGtPlanes);
+  LanesRecord* rec = lanes_next("vp_metric_add_lanes_pair");
+  wait_for(e, ev_src_[0]);
+  if (&ref != &e) wait_for(ref, ev_src_[1]);
+  lanes(e.d_logits_, ref.d_logits_, kLanesGtRef, e.out_h_, e.out_w_, rec);
+  release_to(e, ev_read_[0]);
+  if (&ref != &e) release_to(ref, ev_read_[1]);
+  ++lanes_frames_;
+}
+
+void Metric::add_lanes_logits(const float* logits, bool on_device, int h, int w, const void* gt, bool gt_on_device, int gt_form) {
+  metric_check_lanes_args("vp_metric_add_lanes_logits", logits, h, w, gt, gt_form);
+  LanesRecord* rec = lanes_next("vp_metric_add_lanes_logits");
+  const float* d_logits = on_device ? logits : static_cast<const float*>(stage_host(stage_[0], logits, 3 * sizeof(float) * (size_t)h * w));
+  const void* d_gt = gt_on_device ? gt : stage_host(stage_[1], gt, lanes_gt_bytes(gt_form, h, w));
+  lanes(d_logits, d_gt, gt_form, h, w, rec);
+  ++lanes_frames_;
+}
+
+void Metric::fetch_lanes(LanesRecord* out, int count) {
+  if (count < 0 || count > lanes_frames_ || (count > 0 && !out)) throw std::invalid_argument("vp_metric_fetch_lanes: more records than were added, or a null buffer");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (count) VP_HIP_CHECK(hipMemcpyAsync(out, d_lanes_records_, (size_t)count * sizeof(LanesRecord), hipMemcpyDeviceToHost, stream_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+RowsRecord* Metric::rows_next(const char* who, int n_lines, const double* thr, int n_thr) {
+  const std::string me(who);
+  if (!thr || n_thr < 1 || n_thr > kMetricRowsMaxThr) throw std::invalid_argument(me + ": a null threshold table, or n_thr outside 1 .. 8");
+  for (int k = 0; k < n_thr; ++k)
+    if (thr[k] != thr[k]) throw std::invalid_argument(me + ": a NaN threshold");
+  if (rows_lines_ && (n_thr != rows_n_thr_ || std::memcmp(thr, rows_thr_, sizeof(double) * (size_t)n_thr) != 0))
+    throw std::invalid_argument(me + ": another threshold table than the lines added so far were scored with (vp_metric_reset first)");
+  if (rows_lines_ + n_lines > max_frames_)
+    throw std::runtime_error(me + ": the rows accumulator is full (" + std::to_string(max_frames_) + " lines; vp_metric_fetch_rows, then vp_metric_reset)");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (!d_rows_records_) VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_rows_records_), (size_t)max_frames_ * sizeof(RowsRecord)));
+  rows_n_thr_ = n_thr;
+  std::memcpy(rows_thr_, thr, sizeof(double) * (size_t)n_thr);
+  return d_rows_records_ + rows_lines_;
+}
+
+void Metric::rows(const float* xp, const float* hv, const float* txp, const float* thv, int n_lines, int n_rows, RowsRecord* rec) {
+  MetricRowsParams q{};
+  q.xp = xp;
+  q.hv = hv;
+  q.txp = txp;
+  q.thv = thv;
+  q.n_lines = n_lines;
+  q.rows = n_rows;
+  q.n_thr = rows_n_thr_;
+  std::memcpy(q.thr, rows_thr_, sizeof(q.thr));
+  q.rec = rec;
+  VP_HIP_CHECK(launch_metric_rows(q, stream_));
+  rows_lines_ += n_lines;
+}
+
+// the engine's logits {1, 2, rows, 1}: xp, then h_vector
+void Metric::add_rows(Engine& e, const float* target_xp, const float* target_h, const double* thr, int n_thr) {
+  rows_source_of(e, "vp_metric_add_rows");
+  if (!target_xp || !target_h) throw std::invalid_argument("vp_metric_add_rows: null targets");
+  RowsRecord* rec = rows_next("vp_metric_add_rows", 1, thr, n_thr);
+  const int n = e.out_h_;
+  std::vector<float> both(2 * (size_t)n);
+  std::memcpy(both.data(), target_xp, sizeof(float) * (size_t)n);
+  std::memcpy(both.data() + n, target_h, sizeof(float) * (size_t)n);
+  const float* d_t = static_cast<const float*>(stage_host(stage_[1], both.data(), sizeof(float) * both.size()));
+  wait_for(e, ev_src_[0]);
+  rows(e.d_logits_, e.d_logits_ + n, d_t, d_t + n, 1, n, rec);
+  release_to(e, ev_read_[0]);
+}
+
+void Metric::add_rows_pair(Engine& e, Engine& ref, const double* thr, int n_thr) {
+  rows_source_of(e, "vp_metric_add_rows_pair");
+  rows_source_of(ref, "vp_metric_add_rows_pair");
+  if (e.out_h_ != ref.out_h_) throw std::invalid_argument("vp_metric_add_rows_pair: the two engines differ in their rows");
+  RowsRecord* rec = rows_next("vp_metric_add_rows_pair", 1, thr, n_thr);
+  const int n = e.out_h_;
+  wait_for(e, ev_src_[0]);
+  if (&ref != &e) wait_for(ref, ev_src_[1]);
+  rows(e.d_logits_, e.d_logits_ + n, ref.d_logits_, ref.d_logits_ + n, 1, n, rec);
+  release_to(e, ev_read_[0]);
+  if (&ref != &e) release_to(ref, ev_read_[1]);
+}
+
+void Metric::add_rows_raw(const float* xp, const float* hv, const float* target_xp, const float* target_h, int n_lines, int n_rows, const double* thr, int n_thr) {
+  if (!xp || !hv || !target_xp || !target_h) throw std::invalid_argument("vp_metric_add_rows_raw: a null array");
+  if (n_lines < 1 || n_lines > kMetricRowsMaxLines || n_rows < 1 || n_rows > kMetricRowsMaxRows)
+    throw std::invalid_argument("vp_metric_add_rows_raw: n_lines " + std::to_string(n_lines) + ", rows " + std::to_string(n_rows) + " (n_lines 1 .. 8, rows 1 .. 1024)");
+  RowsRecord* rec = rows_next("vp_metric_add_rows_raw", n_lines, thr, n_thr);
+  const size_t n = (size_t)n_lines * n_rows;
+  std::vector<float> all(4 * n);
+  const float* src[4] = {xp, hv, target_xp, target_h};
+  for (int k = 0; k < 4; ++k) std::memcpy(all.data() + k * n, src[k], sizeof(float) * n);
+  const float* d = static_cast<const float*>(stage_host(stage_[0], all.data(), sizeof(float) * all.size()));
+  rows(d, d + n, d + 2 * n, d + 3 * n, n_lines, n_rows, rec);
+}
+
+void Metric::fetch_rows(RowsRecord* out, int count) {
+  if (count < 0 || count > rows_lines_ || (count > 0 && !out)) throw std::invalid_argument("vp_metric_fetch_rows: more records than were added, or a null buffer");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (count) VP_HIP_CHECK(hipMemcpyAsync(out, d_rows_records_, (size_t)count * sizeof(RowsRecord), hipMemcpyDeviceToHost, stream_));
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 

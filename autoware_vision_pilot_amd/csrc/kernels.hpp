@@ -770,6 +770,50 @@ inline void metric_quantile_rank(unsigned n, unsigned* lo, unsigned* hi, float* 
   *w = r - f;
 }
 
+// ---- vp_metric, lane part (include/vp_hip.h "vp_metric: the lane networks"; kernels_misc.hip metric_lanes_* / metric_rows_*): the EgoLanes trainer's loss
+// as a validation score (ego_lanes_trainer.py:280-356) and the per-line stage of the AutoSteer trainer's val() (auto_steer_trainer.py:203-222).
+// Lanes: per plane c the sum of the per-pixel BCE-with-logits terms, and five edge sums: scale 0 on D0 = relu(x) - g, scales 1 .. 4 on the 2x2 mean pools of
+// E = Threshold(0, 1)(relu(x)) - g.  Two shapes of the same device code:
+//   small    h * w <= kMetricLanesLdsN: ONE launch of three workgroups, plane c in workgroup c, D0 and the four pooled levels in LDS;
+//   general  prep (grid nb x 3: BCE partials, D0 and pooled level 1 into scratch), then one edge launch per scale (grid nb_s x 3; it pools into the next level).
+// Both write partials (double, one per workgroup) that metric_lanes_finish_kernel (one workgroup) folds in index order through the fixed tree.
+// LanesRecord is vp_metric_lanes_frame's layout, RowsRecord vp_metric_rows_line's (vp_api.cpp checks both).
+struct LanesRecord {
+  float bce[3], edge[3][5], loss[3], score;
+  unsigned n, nonfinite;
+};
+constexpr unsigned kMetricLanesLdsN = 12800;       // the production 80 x 160 plane
+constexpr unsigned kMetricLanesMaxN = 1u << 22;
+constexpr int kMetricLanesMinSide = 16;            // four 2x2 pools leave a pixel
+// ground truth of a lanes record: fp32 planes [3][h][w]; u8 [h][w], bit c = plane c; u8 [4h][4w], bit c of the OR over each 4x4 block; the planes
+// ref's logits [3][h][w] predict (1 where > 0)
+enum { kLanesGtPlanes = 0, kLanesGtBits = 1, kLanesGtBits4x = 2, kLanesGtRef = 3 };
+struct MetricLanesParams {
+  const float* logits;   // [3][h][w]
+  const void* gt;
+  int gt_form, h, w;
+  float* d0;             // general path: [3][n]
+  float* pooled;         // general path: [3][metric_lanes_pooled_elems(h, w)], the four levels of a plane one after the other
+  double* part;          // [3][7][kMetricBlocks]: BCE sum, five edge sums, non-finite count
+  LanesRecord* rec;
+};
+size_t metric_lanes_pooled_elems(int h, int w);
+hipError_t launch_metric_lanes(const MetricLanesParams& p, hipStream_t st);
+// Rows: one workgroup per line.  Term r = |xp[r] * m - txp[r] * mt| with m = h[r] > 0.5, mt = th[r] > 0.5 as fp32 operations; the sums of the terms and of h
+// are formed in double: element r into slot r mod 256 in ascending r, the 256 slots by the fixed tree; dist / conf = fp32(sum / rows).
+struct RowsRecord {
+  float dist, conf;
+  unsigned tp, valid, target_valid;
+};
+constexpr int kMetricRowsMaxLines = 8, kMetricRowsMaxRows = 1024, kMetricRowsMaxThr = 8;
+struct MetricRowsParams {
+  const float *xp, *hv, *txp, *thv;   // [n_lines][rows] each
+  int n_lines, rows, n_thr;
+  double thr[kMetricRowsMaxThr];
+  RowsRecord* rec;                    // [n_lines]
+};
+hipError_t launch_metric_rows(const MetricRowsParams& p, hipStream_t st);
+
 // ---- vp_metric, detector part (include/vp_hip.h "vp_metric: the detector"; kernels_detect.hip det_val_*): the validation post-process of the detector's
 // trainer (auto_speed_util.py non_max_suppression + compute_metric) on a raw tensor [4 + nc][nb].  The chain, one launch each, no workgroup talking to
 // another inside a launch:

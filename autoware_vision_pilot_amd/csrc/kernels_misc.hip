@@ -1660,4 +1660,258 @@ hipError_t launch_metric_depth(const MetricDepthParams& p, hipStream_t st) {
   VP_LAUNCH(metric_depth_finish_kernel, dim3(1), dim3(256), 0, st, p, f);
 }
 
+// ------------------------------------------------------------------------------------------ vp_metric, lane part
+// ego_lanes_trainer.py:280-356 and auto_steer_trainer.py:203-222, restated (kernels.hpp: the two shapes of the lanes chain, the rows' summation order).
+constexpr int kLanesParts = 7;   // per plane: the BCE sum, five edge sums, the non-finite count
+__device__ __forceinline__ double* metric_lanes_part(const MetricLanesParams& p, int c, int k) { return p.part + (size_t)(c * kLanesParts + k) * kMetricBlocks; }
+// the ground truth of pixel (y, x) of plane c; *bad counts a non-finite value of the fp32 form
+__device__ __forceinline__ float metric_lanes_gt(const MetricLanesParams& p, int c, int y, int x, unsigned* bad) {
+  const size_t n = (size_t)p.h * p.w, i = (size_t)y * p.w + x;
+  if (p.gt_form == kLanesGtPlanes) {
+    const float v = static_cast<const float*>(p.gt)[c * n + i];
+    *bad += !metric_finite(v);
+    return v;
+  }
+  if (p.gt_form == kLanesGtRef) return static_cast<const float*>(p.gt)[c * n + i] > 0.0f ? 1.0f : 0.0f;
+  unsigned v;
+  if (p.gt_form == kLanesGtBits) {
+    v = static_cast<const uint8_t*>(p.gt)[i];
+  } else {   // the two 2x2 maximum pools of binary planes: the OR over the 4x4 block, four bytes per row (the launcher checks the alignment)
+    const unsigned* q = reinterpret_cast<const unsigned*>(static_cast<const uint8_t*>(p.gt) + 16 * (size_t)y * p.w + 4 * (size_t)x);
+    v = q[0] | q[p.w] | q[2 * (size_t)p.w] | q[3 * (size_t)p.w];
+    v |= v >> 16;
+    v |= v >> 8;
+  }
+  return (float)((v >> c) & 1u);
+}
+// one 2x2 cell of plane c: per pixel the BCEWithLogits term (1 - g) x + max(-x, 0) + log1p(exp(-|x|)) and D0 = R - g with R = relu(x); the mean of
+// E = T - g over a whole cell into p1, T = Threshold(0, 1)(R): R where R > 0, 1 elsewhere.  A trailing odd row or column has cells of two pixels or one.
+__device__ __forceinline__ void metric_lanes_cell(const MetricLanesParams& p, int c, int cy, int cx, float* d0, float* p1, double* bce, unsigned* bad) {
+  const int h = p.h, w = p.w;
+  const float* x0 = p.logits + (size_t)c * h * w;
+  float e[2][2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int y = 2 * cy + j, x = 2 * cx + k;
+      e[j][k] = 0.0f;
+      if (y < h && x < w) {
+        const float v = x0[(size_t)y * w + x];
+        const float g = metric_lanes_gt(p, c, y, x, bad);
+        *bad += !metric_finite(v);
+        *bce += (double)__fadd_rn(__fmul_rn(__fsub_rn(1.0f, g), v), __fadd_rn(fmaxf(-v, 0.0f), log1pf(expf(-fabsf(v)))));
+        const float r = v > 0.0f ? v : 0.0f;
+        d0[(size_t)y * w + x] = __fsub_rn(r, g);
+        e[j][k] = __fsub_rn(r > 0.0f ? r : 1.0f, g);
+      }
+    }
+  }
+  if (2 * cy + 1 < h && 2 * cx + 1 < w) p1[(size_t)cy * (w >> 1) + cx] = __fmul_rn(0.25f, __fadd_rn(__fadd_rn(e[0][0], e[0][1]), __fadd_rn(e[1][0], e[1][1])));
+}
+// the pixels first, first + step, ... of one scale: the sum of |Gx(src)| + |Gy(src)| (metric_depth_edge_kernel's filters and expression) and, with dst, the
+// 2x2 mean pool of src
+__device__ __forceinline__ double metric_lanes_edge_part(const float* src, int h, int w, float* dst, unsigned first, unsigned step) {
+  const unsigned n = (unsigned)h * (unsigned)w;
+  double s = 0.0;
+  for (unsigned i = first; i < n; i += step) {
+    const int y = (int)(i / (unsigned)w), x = (int)(i % (unsigned)w);
+    const float a00 = metric_at(src, h, w, y - 1, x - 1), a01 = metric_at(src, h, w, y - 1, x), a02 = metric_at(src, h, w, y - 1, x + 1);
+    const float a10 = metric_at(src, h, w, y, x - 1), a12 = metric_at(src, h, w, y, x + 1);
+    const float a20 = metric_at(src, h, w, y + 1, x - 1), a21 = metric_at(src, h, w, y + 1, x), a22 = metric_at(src, h, w, y + 1, x + 1);
+    const float gx = __fadd_rn(__fmul_rn(0.125f, __fadd_rn(__fsub_rn(a00, a02), __fsub_rn(a20, a22))), __fmul_rn(0.25f, __fsub_rn(a10, a12)));
+    const float gy = __fadd_rn(__fmul_rn(0.125f, __fadd_rn(__fsub_rn(a00, a20), __fsub_rn(a02, a22))), __fmul_rn(0.25f, __fsub_rn(a01, a21)));
+    s += (double)__fadd_rn(fabsf(gx), fabsf(gy));
+  }
+  if (dst) {
+    const int h2 = h >> 1, w2 = w >> 1;
+    for (unsigned i = first; i < (unsigned)h2 * (unsigned)w2; i += step) {
+      const float* r0 = src + (size_t)(2 * (i / (unsigned)w2)) * w + 2 * (i % (unsigned)w2);
+      dst[i] = __fmul_rn(0.25f, __fadd_rn(__fadd_rn(r0[0], r0[1]), __fadd_rn(r0[w], r0[w + 1])));
+    }
+  }
+  return s;
+}
+// small: plane blockIdx.x, everything in LDS (h * w <= kMetricLanesLdsN, so level l holds at most kMetricLanesLdsN >> 2 l values)
+__global__ __launch_bounds__(256) void metric_lanes_small_kernel(const MetricLanesParams p) {
+  __shared__ float d0[kMetricLanesLdsN];
+  __shared__ float pool[kMetricLanesLdsN / 4 + kMetricLanesLdsN / 16 + kMetricLanesLdsN / 64 + kMetricLanesLdsN / 256];
+  __shared__ double lds[256];
+  const int c = blockIdx.x, t = threadIdx.x;
+  const int ch = (p.h + 1) >> 1, cw = (p.w + 1) >> 1;
+  double bce = 0.0;
+  unsigned bad = 0;
+  for (int i = t; i < ch * cw; i += 256) metric_lanes_cell(p, c, i / cw, i % cw, d0, pool, &bce, &bad);
+  bce = metric_block_reduce(bce, lds, MetricSumJoin());   // its barriers also publish d0 and level 1
+  const double nbad = metric_block_reduce((double)bad, lds, MetricSumJoin());
+  if (t == 0) {
+    *metric_lanes_part(p, c, 0) = bce;
+    *metric_lanes_part(p, c, 6) = nbad;
+  }
+  double e = metric_lanes_edge_part(d0, p.h, p.w, nullptr, (unsigned)t, 256u);
+  e = metric_block_reduce(e, lds, MetricSumJoin());
+  if (t == 0) *metric_lanes_part(p, c, 1) = e;
+  float* src = pool;
+  int h = p.h >> 1, w = p.w >> 1;
+  for (int s = 1; s < 5; ++s) {   // level s + 1 is written behind level s while that is read; the reduction's barriers publish it
+    float* dst = src + (size_t)h * w;
+    e = metric_lanes_edge_part(src, h, w, s < 4 ? dst : (float*)nullptr, (unsigned)t, 256u);
+    e = metric_block_reduce(e, lds, MetricSumJoin());
+    if (t == 0) *metric_lanes_part(p, c, 1 + s) = e;
+    src = dst;
+    h >>= 1;
+    w >>= 1;
+  }
+}
+// general, launch 1: grid (nb, 3); D0 and level 1 into scratch, the BCE and non-finite partials
+__global__ __launch_bounds__(256) void metric_lanes_prep_kernel(const MetricLanesParams p, unsigned pooled_elems) {
+  __shared__ double lds[256];
+  const int c = blockIdx.y;
+  const unsigned ch = (unsigned)(p.h + 1) >> 1, cw = (unsigned)(p.w + 1) >> 1;
+  float* d0 = p.d0 + (size_t)c * p.h * p.w;
+  float* p1 = p.pooled + (size_t)c * pooled_elems;
+  double bce = 0.0;
+  unsigned bad = 0;
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < ch * cw; i += gridDim.x * 256) metric_lanes_cell(p, c, (int)(i / cw), (int)(i % cw), d0, p1, &bce, &bad);
+  bce = metric_block_reduce(bce, lds, MetricSumJoin());
+  const double nbad = metric_block_reduce((double)bad, lds, MetricSumJoin());
+  if (threadIdx.x == 0) {
+    metric_lanes_part(p, c, 0)[blockIdx.x] = bce;
+    metric_lanes_part(p, c, 6)[blockIdx.x] = nbad;
+  }
+}
+// general, launches 2 .. 6: grid (nb, 3); scale s of plane blockIdx.y, src and dst planes `src_stride` / `dst_stride` floats apart
+__global__ __launch_bounds__(256) void metric_lanes_edge_kernel(const MetricLanesParams p, int s, const float* src, size_t src_stride, int h, int w, float* dst, size_t dst_stride) {
+  __shared__ double lds[256];
+  const int c = blockIdx.y;
+  double e = metric_lanes_edge_part(src + c * src_stride, h, w, dst ? dst + c * dst_stride : (float*)nullptr, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
+  e = metric_block_reduce(e, lds, MetricSumJoin());
+  if (threadIdx.x == 0) metric_lanes_part(p, c, 1 + s)[blockIdx.x] = e;
+}
+// the record: partials folded in the fixed tree (nb[0] prep workgroups, nb[1 + s] of scale s; all 1 behind the small kernel), every mean one fp32 division of
+// the double sum rounded to fp32, then the trainer's fp32 expressions: edge_c = ((((e0 + e1) + e2) + e3) + e4) / 5, loss_c = edge_c + bce_c, score = (2 l0 + 2 l1) + l2
+struct MetricLanesFinish {
+  unsigned nb[6], n_edge[5];
+};
+__global__ __launch_bounds__(256) void metric_lanes_finish_kernel(const MetricLanesParams p, const MetricLanesFinish f) {
+  __shared__ double lds[256];
+  const unsigned t = threadIdx.x, n = (unsigned)p.h * (unsigned)p.w;
+  LanesRecord r;
+  double bad = 0.0;
+  for (int c = 0; c < 3; ++c) {
+    double v[kLanesParts];
+    for (int k = 0; k < kLanesParts; ++k) {
+      const unsigned nb = (k == 0 || k == 6) ? f.nb[0] : f.nb[k];
+      v[k] = nb == 1 ? metric_lanes_part(p, c, k)[0] : metric_block_reduce(t < nb ? metric_lanes_part(p, c, k)[t] : 0.0, lds, MetricSumJoin());   // nb is uniform
+    }
+    bad += v[6];
+    r.bce[c] = __fdiv_rn((float)v[0], (float)n);
+    float e = 0.0f;
+    for (int s = 0; s < 5; ++s) {
+      r.edge[c][s] = __fdiv_rn((float)v[1 + s], (float)f.n_edge[s]);
+      e = s ? __fadd_rn(e, r.edge[c][s]) : r.edge[c][s];
+    }
+    r.loss[c] = __fadd_rn(__fdiv_rn(e, 5.0f), r.bce[c]);
+  }
+  if (t != 0) return;
+  r.score = __fadd_rn(__fadd_rn(__fmul_rn(2.0f, r.loss[0]), __fmul_rn(2.0f, r.loss[1])), r.loss[2]);
+  r.n = n;
+  r.nonfinite = (unsigned)bad;
+  if (r.nonfinite) {
+    const float nan = __uint_as_float(0x7FC00000u);
+    for (int c = 0; c < 3; ++c) {
+      r.bce[c] = r.loss[c] = nan;
+      for (int s = 0; s < 5; ++s) r.edge[c][s] = nan;
+    }
+    r.score = nan;
+  }
+  *p.rec = r;
+}
+
+size_t metric_lanes_pooled_elems(int h, int w) {
+  size_t t = 0;
+  for (int s = 0; s < 4; ++s) {
+    h >>= 1;
+    w >>= 1;
+    t += (size_t)h * w;
+  }
+  return t;
+}
+hipError_t launch_metric_lanes(const MetricLanesParams& p, hipStream_t st) {
+  if (!p.logits || !p.gt || !p.part || !p.rec || p.h < kMetricLanesMinSide || p.w < kMetricLanesMinSide || (long long)p.h * p.w > (long long)kMetricLanesMaxN ||
+      p.gt_form < kLanesGtPlanes || p.gt_form > kLanesGtRef || (reinterpret_cast<uintptr_t>(p.logits) & 3) ||
+      (p.gt_form != kLanesGtBits && (reinterpret_cast<uintptr_t>(p.gt) & 3)))
+    return hipErrorInvalidValue;
+  const unsigned n = (unsigned)p.h * (unsigned)p.w;
+  MetricLanesFinish f{};
+  int h = p.h, w = p.w;
+  for (int s = 0; s < 5; ++s) {
+    f.n_edge[s] = (unsigned)h * (unsigned)w;
+    h >>= 1;
+    w >>= 1;
+  }
+  if (n <= kMetricLanesLdsN) {
+    for (unsigned& b : f.nb) b = 1;
+    hipLaunchKernelGGL(metric_lanes_small_kernel, dim3(3), dim3(256), 0, st, p);
+    VP_LAUNCH(metric_lanes_finish_kernel, dim3(1), dim3(256), 0, st, p, f);
+  }
+  if (!p.d0 || !p.pooled) return hipErrorInvalidValue;
+  const size_t pe = metric_lanes_pooled_elems(p.h, p.w);
+  f.nb[0] = metric_blocks((size_t)((p.h + 1) >> 1) * (size_t)((p.w + 1) >> 1));
+  hipLaunchKernelGGL(metric_lanes_prep_kernel, dim3(f.nb[0], 3), dim3(256), 0, st, p, (unsigned)pe);
+  const float* src = p.d0;
+  size_t src_stride = n;
+  float* dst = p.pooled;
+  h = p.h;
+  w = p.w;
+  for (int s = 0; s < 5; ++s) {
+    f.nb[1 + s] = metric_blocks(f.n_edge[s]);
+    if (s > 0) dst += (size_t)h * w;   // level s + 1 behind level s
+    hipLaunchKernelGGL(metric_lanes_edge_kernel, dim3(f.nb[1 + s], 3), dim3(256), 0, st, p, s, src, src_stride, h, w, (s > 0 && s < 4) ? dst : (float*)nullptr, pe);
+    if (s == 0) {
+      src = p.pooled;
+      src_stride = pe;
+    } else {
+      src = dst;
+    }
+    h >>= 1;
+    w >>= 1;
+  }
+  VP_LAUNCH(metric_lanes_finish_kernel, dim3(1), dim3(256), 0, st, p, f);
+}
+
+// one line per workgroup (kernels.hpp: the summation order)
+__global__ __launch_bounds__(256) void metric_rows_kernel(const MetricRowsParams p) {
+  __shared__ double lds[256];
+  const size_t o = (size_t)blockIdx.x * p.rows;
+  double sd = 0.0, sc = 0.0, nv = 0.0, nt = 0.0;
+  for (int r = threadIdx.x; r < p.rows; r += 256) {
+    const float hv = p.hv[o + r], th = p.thv[o + r];
+    const float m = hv > 0.5f ? 1.0f : 0.0f, mt = th > 0.5f ? 1.0f : 0.0f;
+    sd += (double)fabsf(__fsub_rn(__fmul_rn(p.xp[o + r], m), __fmul_rn(p.txp[o + r], mt)));
+    sc += (double)hv;
+    nv += (double)m;
+    nt += (double)mt;
+  }
+  sd = metric_block_reduce(sd, lds, MetricSumJoin());
+  sc = metric_block_reduce(sc, lds, MetricSumJoin());
+  nv = metric_block_reduce(nv, lds, MetricSumJoin());
+  nt = metric_block_reduce(nt, lds, MetricSumJoin());
+  if (threadIdx.x != 0) return;
+  RowsRecord r;
+  r.dist = (float)(sd / (double)p.rows);
+  r.conf = (float)(sc / (double)p.rows);
+  r.tp = 0;
+  for (int k = 0; k < p.n_thr; ++k) r.tp |= ((double)r.dist < p.thr[k] ? 1u : 0u) << k;   // in double against the fp32 value, as .item() compares
+  r.valid = (unsigned)nv;
+  r.target_valid = (unsigned)nt;
+  p.rec[blockIdx.x] = r;
+}
+hipError_t launch_metric_rows(const MetricRowsParams& p, hipStream_t st) {
+  if (!p.xp || !p.hv || !p.txp || !p.thv || !p.rec || p.n_lines < 1 || p.n_lines > kMetricRowsMaxLines || p.rows < 1 || p.rows > kMetricRowsMaxRows || p.n_thr < 1 ||
+      p.n_thr > kMetricRowsMaxThr)
+    return hipErrorInvalidValue;
+  VP_LAUNCH(metric_rows_kernel, dim3(p.n_lines), dim3(256), 0, st, p);
+}
+
 }  // namespace vp

@@ -1827,6 +1827,100 @@ void det_ap(const uint32_t* tp_in, const float* conf_in, const float* cls_in, in
   s->map = sap / (double)nc;
 }
 
+// ---- the lane part
+static_assert(sizeof(vp_metric_lanes_frame) == sizeof(vp::LanesRecord) && offsetof(vp_metric_lanes_frame, edge) == offsetof(vp::LanesRecord, edge) &&
+                  offsetof(vp_metric_lanes_frame, score) == offsetof(vp::LanesRecord, score) && offsetof(vp_metric_lanes_frame, nonfinite) == offsetof(vp::LanesRecord, nonfinite) &&
+                  sizeof(vp_metric_rows_line) == sizeof(vp::RowsRecord) && offsetof(vp_metric_rows_line, tp) == offsetof(vp::RowsRecord, tp) &&
+                  offsetof(vp_metric_rows_line, target_valid) == offsetof(vp::RowsRecord, target_valid),
+              "vp_metric_lanes_frame / vp_metric_rows_line are the records the kernels write");
+static_assert(VP_LANES_GT_PLANES == vp::kLanesGtPlanes && VP_LANES_GT_BITS == vp::kLanesGtBits && VP_LANES_GT_BITS_4X == vp::kLanesGtBits4x && VP_ROWS_MAX_THR == vp::kMetricRowsMaxThr &&
+                  VP_ROWS_MAX_LINES == vp::kMetricRowsMaxLines && VP_ROWS_MAX_ROWS == vp::kMetricRowsMaxRows,
+              "the header's lane constants are the kernels'");
+
+// the dataset score of train_ego_lanes.py:387-417 and its parts: means over the frames without NaN, in double
+void lanes_summary(const std::vector<vp_metric_lanes_frame>& recs, vp_metric_lanes_summary* s) {
+  std::memset(s, 0, sizeof(*s));
+  int scored = 0;
+  for (const vp_metric_lanes_frame& r : recs) {
+    ++s->frames;
+    if (std::isnan(r.score)) {
+      ++s->nan_frames;
+      continue;
+    }
+    ++scored;
+    s->score += (double)r.score;
+    for (int c = 0; c < 3; ++c) {
+      s->loss[c] += (double)r.loss[c];
+      s->bce[c] += (double)r.bce[c];
+      double e = 0.0;
+      for (int k = 0; k < 5; ++k) e += (double)r.edge[c][k];
+      s->edge[c] += e / 5.0;
+    }
+  }
+  const double nan = std::nan("");
+  s->score = scored ? s->score / scored : nan;
+  for (int c = 0; c < 3; ++c) {
+    s->loss[c] = scored ? s->loss[c] / scored : nan;
+    s->bce[c] = scored ? s->bce[c] / scored : nan;
+    s->edge[c] = scored ? s->edge[c] / scored : nan;
+  }
+}
+
+// compute_vector_ap (Models/training/auto_steer_util.py:353-399) in double, statement for statement; the table in the caller's order
+void rows_ap(const uint32_t* tp_in, const float* conf_in, int n, const double* thr, int n_thr, vp_metric_rows_summary* s) {
+  const double eps = 1e-16, nan = std::nan("");
+  std::memset(s, 0, sizeof(*s));
+  s->lines = n;
+  s->n_thr = n_thr;
+  s->map50 = nan;
+  for (int j = 0; j < n_thr; ++j)
+    if (thr[j] == 0.05) s->map50 = 0.0;
+  if (n == 0) return;   // val(): "No valid predictions found", every score 0
+  // i = numpy.argsort(-conf); equal conf keep line order, a NaN goes last
+  std::vector<int> order((size_t)n);
+  for (int i = 0; i < n; ++i) order[(size_t)i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+    const float ca = conf_in[a], cb = conf_in[b];
+    if (std::isnan(ca)) return false;
+    if (std::isnan(cb)) return true;
+    return ca > cb;
+  });
+  const std::vector<double> x101 = np_linspace01(101);
+  const size_t no = (size_t)n;
+  std::vector<double> m_rec(no + 2), m_pre(no + 2), y(101);
+  double sum_p = 0.0, sum_r = 0.0, sum_ap = 0.0;
+  for (int j = 0; j < n_thr; ++j) {
+    long long tpc = 0, fpc = 0;
+    double mp = 0.0, mr = 0.0;
+    for (size_t k = 0; k < no; ++k) {
+      const int t = (int)((tp_in[order[k]] >> j) & 1u);
+      tpc += t;
+      fpc += 1 - t;
+      const double precision = (double)tpc / ((double)(tpc + fpc) + eps), recall = (double)tpc / ((double)n + eps);
+      m_pre[k + 1] = precision;
+      m_rec[k + 1] = recall;
+      mp += precision;
+      mr += recall;
+    }
+    m_rec[0] = 0.0;
+    m_pre[0] = 0.0;
+    m_rec[no + 1] = 1.0;
+    m_pre[no + 1] = 0.0;
+    for (size_t k = no + 1; k-- > 0;) m_pre[k] = std::max(m_pre[k], m_pre[k + 1]);   // the precision envelope
+    for (int g = 0; g < 101; ++g) y[(size_t)g] = np_interp(x101[(size_t)g], m_rec, m_pre, m_pre[0], m_pre[no + 1]);
+    double area = 0.0;   // numpy.trapz
+    for (int g = 0; g < 100; ++g) area += (x101[(size_t)g + 1] - x101[(size_t)g]) * (y[(size_t)g + 1] + y[(size_t)g]) / 2.0;
+    s->ap[j] = area;
+    if (thr[j] == 0.05) s->map50 = area;
+    sum_ap += area;
+    sum_p += mp / (double)n;
+    sum_r += mr / (double)n;
+  }
+  s->precision = sum_p / (double)n_thr;
+  s->recall = sum_r / (double)n_thr;
+  s->mean_ap = sum_ap / (double)n_thr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1950,6 +2044,82 @@ int vp_metric_det_ap(const uint32_t* tp, const float* conf, const float* det_cls
   try {
     summary->frames = 0;
     det_ap(tp, conf, det_cls, n_rows, label_cls, n_labels, n_iou, summary);
+    return VP_OK;
+  } catch (const std::exception&) {
+    return VP_ERR_STATE;
+  }
+}
+
+// ---- the lane part
+int vp_metric_add_lanes(vp_metric* m, vp_engine* e, const void* gt, int gt_on_device, int gt_form) {
+  return metric_guarded(m, [&](vp::Metric& g) {
+    vp::Engine& en = metric_engine(e, "vp_metric_add_lanes");
+    if (!gt) throw std::invalid_argument("vp_metric_add_lanes: null ground truth");
+    g.add_lanes(en, gt, gt_on_device != 0, gt_form);
+  });
+}
+
+int vp_metric_add_lanes_pair(vp_metric* m, vp_engine* e, vp_engine* ref) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_lanes_pair(metric_engine(e, "vp_metric_add_lanes_pair"), metric_engine(ref, "vp_metric_add_lanes_pair")); });
+}
+
+int vp_metric_add_lanes_logits(vp_metric* m, const float* logits_chw, int on_device, int h, int w, const void* gt, int gt_on_device, int gt_form) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_lanes_logits(logits_chw, on_device != 0, h, w, gt, gt_on_device != 0, gt_form); });
+}
+
+int vp_metric_lanes_frames(const vp_metric* m) { return m && m->impl ? m->impl->lanes_frames() : VP_ERR_ARG; }
+
+int vp_metric_fetch_lanes(vp_metric* m, vp_metric_lanes_frame* records, int cap, vp_metric_lanes_summary* summary) {
+  return metric_guarded(m, [&](vp::Metric& g) {
+    if (cap < 0 || (cap > 0 && !records)) throw std::invalid_argument("vp_metric_fetch_lanes: cap < 0, or null records with cap > 0");
+    std::vector<vp_metric_lanes_frame> host((size_t)g.lanes_frames());
+    g.fetch_lanes(reinterpret_cast<vp::LanesRecord*>(host.data()), g.lanes_frames());
+    const int n = std::min(cap, g.lanes_frames());
+    if (n) std::memcpy(records, host.data(), (size_t)n * sizeof(vp_metric_lanes_frame));
+    if (summary) lanes_summary(host, summary);
+  });
+}
+
+int vp_metric_add_rows(vp_metric* m, vp_engine* e, const float* target_xp, const float* target_h, const double* thr, int n_thr) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_rows(metric_engine(e, "vp_metric_add_rows"), target_xp, target_h, thr, n_thr); });
+}
+
+int vp_metric_add_rows_pair(vp_metric* m, vp_engine* e, vp_engine* ref, const double* thr, int n_thr) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_rows_pair(metric_engine(e, "vp_metric_add_rows_pair"), metric_engine(ref, "vp_metric_add_rows_pair"), thr, n_thr); });
+}
+
+int vp_metric_add_rows_raw(vp_metric* m, const float* xp, const float* h_vector, const float* target_xp, const float* target_h, int n_lines, int rows, const double* thr,
+                           int n_thr) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_rows_raw(xp, h_vector, target_xp, target_h, n_lines, rows, thr, n_thr); });
+}
+
+int vp_metric_rows_lines(const vp_metric* m) { return m && m->impl ? m->impl->rows_lines() : VP_ERR_ARG; }
+
+int vp_metric_fetch_rows(vp_metric* m, vp_metric_rows_line* records, int cap, vp_metric_rows_summary* summary) {
+  return metric_guarded(m, [&](vp::Metric& g) {
+    if (cap < 0 || (cap > 0 && !records)) throw std::invalid_argument("vp_metric_fetch_rows: cap < 0, or null records with cap > 0");
+    std::vector<vp_metric_rows_line> host((size_t)g.rows_lines());
+    g.fetch_rows(reinterpret_cast<vp::RowsRecord*>(host.data()), g.rows_lines());
+    const int n = std::min(cap, g.rows_lines());
+    if (n) std::memcpy(records, host.data(), (size_t)n * sizeof(vp_metric_rows_line));
+    if (summary) {
+      std::vector<uint32_t> tp(host.size());
+      std::vector<float> conf(host.size());
+      for (size_t i = 0; i < host.size(); ++i) {
+        tp[i] = host[i].tp;
+        conf[i] = host[i].conf;
+      }
+      rows_ap(tp.data(), conf.data(), (int)host.size(), g.rows_thr(), g.rows_n_thr(), summary);
+    }
+  });
+}
+
+int vp_metric_rows_ap(const uint32_t* tp, const float* conf, int n_lines, const double* thr, int n_thr, vp_metric_rows_summary* summary) {
+  if (!summary || n_lines < 0 || !thr || n_thr < 1 || n_thr > VP_ROWS_MAX_THR || (n_lines > 0 && (!tp || !conf))) return VP_ERR_ARG;
+  for (int k = 0; k < n_thr; ++k)
+    if (thr[k] != thr[k]) return VP_ERR_ARG;
+  try {
+    rows_ap(tp, conf, n_lines, thr, n_thr, summary);
     return VP_OK;
   } catch (const std::exception&) {
     return VP_ERR_STATE;

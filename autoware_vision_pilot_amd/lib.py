@@ -213,6 +213,17 @@ _SIGS = {
     "vp_metric_fetch_det": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P]),
     "vp_metric_det_ap": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "vp_op_detect_validate": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, C.c_char_p, C.c_size_t]),
+    "vp_metric_add_lanes": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
+    "vp_metric_add_lanes_pair": (C.c_int, [_P, _P, _P]),
+    "vp_metric_add_lanes_logits": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
+    "vp_metric_lanes_frames": (C.c_int, [_P]),
+    "vp_metric_fetch_lanes": (C.c_int, [_P, _P, C.c_int, _P]),
+    "vp_metric_add_rows": (C.c_int, [_P, _P, _P, _P, _P, C.c_int]),
+    "vp_metric_add_rows_pair": (C.c_int, [_P, _P, _P, _P, C.c_int]),
+    "vp_metric_add_rows_raw": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int]),
+    "vp_metric_rows_lines": (C.c_int, [_P]),
+    "vp_metric_fetch_rows": (C.c_int, [_P, _P, C.c_int, _P]),
+    "vp_metric_rows_ap": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P]),
 }
 # multi-camera exchange (csrc/vp_comm.cpp): part of libvp_hip.so, absent from the CPU-emulated test build
 _COMM_SIGS = {
@@ -315,6 +326,44 @@ class MetricDetSummary(C.Structure):
                 ("precision", C.c_double), ("recall", C.c_double), ("map50", C.c_double), ("map", C.c_double),
                 ("class_id", C.c_float * VP_DET_MAX_CLASSES), ("class_labels", C.c_uint32 * VP_DET_MAX_CLASSES), ("ap50", C.c_double * VP_DET_MAX_CLASSES),
                 ("ap", C.c_double * VP_DET_MAX_CLASSES), ("tp", C.c_double * VP_DET_MAX_CLASSES), ("fp", C.c_double * VP_DET_MAX_CLASSES)]
+
+
+VP_LANES_GT_PLANES, VP_LANES_GT_BITS, VP_LANES_GT_BITS_4X = 0, 1, 2
+LANES_GT_FORMS = {"planes": VP_LANES_GT_PLANES, "bits": VP_LANES_GT_BITS, "bits4x": VP_LANES_GT_BITS_4X}
+VP_ROWS_MAX_THR, VP_ROWS_MAX_LINES, VP_ROWS_MAX_ROWS = 8, 8, 1024
+ROWS_THR = (0.02, 0.05, 0.10)            # the trainer's thresholds (auto_steer_trainer.py:180)
+METRIC_LANES_FRAME_DTYPE = np.dtype([("bce", "<f4", (3,)), ("edge", "<f4", (3, 5)), ("loss", "<f4", (3,)), ("score", "<f4"), ("n", "<u4"), ("nonfinite", "<u4")])
+METRIC_ROWS_LINE_DTYPE = np.dtype([("dist", "<f4"), ("conf", "<f4"), ("tp", "<u4"), ("valid", "<u4"), ("target_valid", "<u4")])
+
+
+class MetricLanesFrame(C.Structure):
+    """vp_metric_lanes_frame (include/vp_hip.h)"""
+    _fields_ = [("bce", C.c_float * 3), ("edge", (C.c_float * 5) * 3), ("loss", C.c_float * 3), ("score", C.c_float), ("n", C.c_uint32), ("nonfinite", C.c_uint32)]
+
+
+class MetricLanesSummary(C.Structure):
+    """vp_metric_lanes_summary (include/vp_hip.h)"""
+    _fields_ = [("frames", C.c_int), ("nan_frames", C.c_int), ("score", C.c_double), ("loss", C.c_double * 3), ("bce", C.c_double * 3), ("edge", C.c_double * 3)]
+
+
+class MetricRowsLine(C.Structure):
+    """vp_metric_rows_line (include/vp_hip.h)"""
+    _fields_ = [("dist", C.c_float), ("conf", C.c_float), ("tp", C.c_uint32), ("valid", C.c_uint32), ("target_valid", C.c_uint32)]
+
+
+class MetricRowsSummary(C.Structure):
+    """vp_metric_rows_summary (include/vp_hip.h)"""
+    _fields_ = [("lines", C.c_int), ("n_thr", C.c_int), ("precision", C.c_double), ("recall", C.c_double), ("mean_ap", C.c_double), ("ap", C.c_double * VP_ROWS_MAX_THR),
+                ("map50", C.c_double)]
+
+
+def _rows_summary_dict(s):
+    return {"lines": s.lines, "n_thr": s.n_thr, "precision": s.precision, "recall": s.recall, "mean_ap": s.mean_ap, "ap": np.array(s.ap[:s.n_thr]), "map50": s.map50}
+
+
+def _rows_table(thr):
+    t = np.ascontiguousarray(ROWS_THR if thr is None else thr, dtype=np.float64).reshape(-1)
+    return t, _ptr(t), int(t.size)
 
 
 def _det_summary_dict(s):
@@ -1343,6 +1392,87 @@ class Metric:
         self._ck(self._lib.vp_metric_fetch_det(self._h, _ptr(fr) if n else None, n, _ptr(rows) if n else None, rows.size, C.byref(s)))
         return fr, rows[:s.rows].copy(), _det_summary_dict(s)
 
+    # ---- the lane part: EgoLanes frames and AutoSteer lines, counted apart
+    @staticmethod
+    def _lanes_gt(gt, gt_form, h, w, device):
+        """(pointer, on_device, keep-alive, form): "planes" float32 [3][h][w], "bits" uint8 [h][w], "bits4x" uint8 [4h][4w]"""
+        form = _named(LANES_GT_FORMS, gt_form)
+        if form not in (0, 1, 2):
+            raise ValueError("gt_form: 'planes', 'bits' or 'bits4x'")
+        if device:
+            return _P(int(gt)), 1, None, form
+        arr = np.ascontiguousarray(gt, dtype=np.float32 if form == 0 else np.uint8)
+        if arr.shape != ((3, h, w), (h, w), (4 * h, 4 * w))[form]:
+            raise ValueError("lanes ground truth: float32 [3][h][w], uint8 [h][w] or uint8 [4h][4w] for an output of h x w")
+        return _ptr(arr), 0, arr, form
+
+    def lanes_frames(self):
+        return self._ck(self._lib.vp_metric_lanes_frames(self._h))
+
+    def add_lanes(self, engine, gt, gt_form="bits", gt_device=False):
+        """the EgoLanes validation record of a VP_EGOLANES engine's last pass; gt: a numpy array in one of the three forms (or a device pointer with gt_device=True)"""
+        h, w = engine.output_dims()[-2:]
+        g, dev, keep, form = self._lanes_gt(gt, gt_form, h, w, gt_device)
+        self._ck(self._lib.vp_metric_add_lanes(self._h, engine._h, g, dev, form))
+
+    def add_lanes_pair(self, engine, ref):
+        """ref's own prediction (1 where its logit > 0) is the ground truth"""
+        self._ck(self._lib.vp_metric_add_lanes_pair(self._h, engine._h, ref._h))
+
+    def add_lanes_logits(self, logits, gt, gt_form="bits", device_hw=None):
+        """logits fp32 [3][h][w] and gt in one of the three forms: numpy arrays, or (with device_hw = (h, w)) device pointers (ints)"""
+        if device_hw is not None:
+            h, w = (int(v) for v in device_hw)
+            self._ck(self._lib.vp_metric_add_lanes_logits(self._h, _P(int(logits)), 1, h, w, _P(int(gt)), 1, _named(LANES_GT_FORMS, gt_form)))
+            return
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        if lg.ndim != 3 or lg.shape[0] != 3:
+            raise ValueError("add_lanes_logits: logits [3][h][w]")
+        g, dev, keep, form = self._lanes_gt(gt, gt_form, lg.shape[1], lg.shape[2], False)
+        self._ck(self._lib.vp_metric_add_lanes_logits(self._h, _ptr(lg), 0, lg.shape[1], lg.shape[2], g, dev, form))
+
+    def fetch_lanes(self):
+        """(records, summary): a numpy array of METRIC_LANES_FRAME_DTYPE and a dict of the means over the frames without NaN"""
+        n = self.lanes_frames()
+        rec = np.zeros(n, dtype=METRIC_LANES_FRAME_DTYPE)
+        s = MetricLanesSummary()
+        self._ck(self._lib.vp_metric_fetch_lanes(self._h, _ptr(rec) if n else None, n, C.byref(s)))
+        return rec, {"frames": s.frames, "nan_frames": s.nan_frames, "score": s.score, "loss": tuple(s.loss), "bce": tuple(s.bce), "edge": tuple(s.edge)}
+
+    def rows_lines(self):
+        return self._ck(self._lib.vp_metric_rows_lines(self._h))
+
+    def add_rows(self, engine, target_xp, target_h, thr=None):
+        """the line record of a VP_AUTOSTEER engine's last pass against host targets [rows]; thr: the run's threshold table (default: the trainer's)"""
+        rows = engine.output_dims()[-2]
+        tx = np.ascontiguousarray(target_xp, dtype=np.float32).reshape(-1)
+        th = np.ascontiguousarray(target_h, dtype=np.float32).reshape(-1)
+        if tx.size != rows or th.size != rows:
+            raise ValueError("add_rows: target_xp and target_h have one value per row of the engine's output")
+        t, tp, nt = _rows_table(thr)
+        self._ck(self._lib.vp_metric_add_rows(self._h, engine._h, _ptr(tx), _ptr(th), tp, nt))
+
+    def add_rows_pair(self, engine, ref, thr=None):
+        """ref's own rows are the targets"""
+        t, tp, nt = _rows_table(thr)
+        self._ck(self._lib.vp_metric_add_rows_pair(self._h, engine._h, ref._h, tp, nt))
+
+    def add_rows_raw(self, xp, h_vector, target_xp, target_h, thr=None):
+        """the operator entry: four float32 arrays [n_lines][rows] (or [rows] for one line)"""
+        a = [np.atleast_2d(np.ascontiguousarray(v, dtype=np.float32)) for v in (xp, h_vector, target_xp, target_h)]
+        if a[0].ndim != 2 or any(v.shape != a[0].shape for v in a):
+            raise ValueError("add_rows_raw: four arrays [n_lines][rows] of one shape")
+        t, tp, nt = _rows_table(thr)
+        self._ck(self._lib.vp_metric_add_rows_raw(self._h, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), a[0].shape[0], a[0].shape[1], tp, nt))
+
+    def fetch_rows(self):
+        """(records, summary): a numpy array of METRIC_ROWS_LINE_DTYPE and the dict of rows_ap over all lines"""
+        n = self.rows_lines()
+        rec = np.zeros(n, dtype=METRIC_ROWS_LINE_DTYPE)
+        s = MetricRowsSummary()
+        self._ck(self._lib.vp_metric_fetch_rows(self._h, _ptr(rec) if n else None, n, C.byref(s)))
+        return rec, _rows_summary_dict(s)
+
     def fetch(self):
         n = self.frames()
         rec = np.zeros(n, dtype=METRIC_FRAME_DTYPE)
@@ -1394,6 +1524,20 @@ def det_ap(tp, conf, det_cls, label_cls, n_iou=10):
     if rc != 0:
         raise (ValueError if rc == -1 else VpError)(f"vp_metric_det_ap failed ({rc})")
     return _det_summary_dict(s)
+
+
+def rows_ap(tp, conf, thr=None):
+    """vp_metric_rows_ap: compute_vector_ap on the host, no device -- tp words (bit t: dist < thr[t]) and conf per line, the threshold table"""
+    tpw = np.ascontiguousarray(tp, dtype=np.uint32).reshape(-1)
+    cf = np.ascontiguousarray(conf, dtype=np.float32).reshape(-1)
+    if tpw.size != cf.size:
+        raise ValueError("rows_ap: tp and conf have one entry per line")
+    t, tptr, nt = _rows_table(thr)
+    s = MetricRowsSummary()
+    rc = load().vp_metric_rows_ap(_ptr(tpw) if tpw.size else None, _ptr(cf) if cf.size else None, tpw.size, tptr, nt, C.byref(s))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_metric_rows_ap failed ({rc})")
+    return _rows_summary_dict(s)
 
 
 def decode_logits_host(logits_chw, decode_mode=VP_DECODE_SEG_MASK, gpu_id=0):

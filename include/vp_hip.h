@@ -818,6 +818,100 @@ int vp_metric_fetch_det(vp_metric* m, vp_metric_det_frame* frames_out, int frame
 int vp_metric_det_ap(const uint32_t* tp, const float* conf, const float* det_cls, int n_rows, const float* label_cls, int n_labels, int n_iou, vp_metric_det_summary* summary);
 int vp_op_detect_validate(int gpu_id, const float* raw, int nc, int nb, float conf, float iou, float* rows_out, int cap, uint32_t* counts_out, char* err, size_t err_len);
 
+/* ---- vp_metric: the lane networks' validation scores -----------------------------------------------------------------------------------
+ * EgoLanes validates with the mean of its training loss over the samples (Models/training/ego_lanes_trainer.py:127-140, 214-222, 280-356;
+ * train_ego_lanes.py:387-417); AutoSteer with a per-line distance, three thresholds and compute_vector_ap (auto_steer_trainer.py:176-248,
+ * auto_steer_util.py:353-399).  The same vp_metric handle accumulates both, each in records of its own, counted apart (vp_metric_lanes_frames,
+ * vp_metric_rows_lines): vp_metric_fetch / _frames / vp_metric_frame / vp_metric_summary and the detector entries know nothing of them, and
+ * vp_metric_add_seg keeps refusing a VP_EGOLANES engine.  VP_AUTODRIVE has no entry: its output is three scalars the host already holds.
+ * LANE MASKS (EgoLanes).  Logits x fp32 [3][h][w] and a ground truth g of three planes.  Per plane c, every floating operation in fp32 unless said:
+ *   bce_c  = mean of (1 - g) x + max(-x, 0) + log1p(exp(-|x|))    (BCEWithLogitsLoss; exp and log1p are the device library's, so this term is not
+ *            defined bit for bit; the per-pixel terms are summed in double)
+ *   R = x where x > 0, else 0 (relu);  T = R where R > 0, else 1.0 (torch.nn.Threshold(0, 1): NOT a step function -- a negative or zero logit gives 1.0)
+ *   e_0    = mean(|Gx(R - g)| + |Gy(R - g)|);   e_s, s = 1 .. 4: the same of P^s(T - g), P the 2x2 mean pool of stride 2 (0.25 ((a + b) + (c + d)); a
+ *            trailing odd row or column dropped), Gx / Gy the 3x3 filters of lines 127-140 with zero padding 1 in the expression of the depth
+ *            entries.  The filters and pools are applied to the difference, the same linear map as the trainer's difference of filtered planes.
+ *   edge_c = ((((e_0 + e_1) + e_2) + e_3) + e_4) / 5;   loss_c = edge_c + bce_c;   score = (2 loss_0 + 2 loss_1) + loss_2.
+ *   Every mean is one fp32 division of the sum (formed in double, partials folded in a fixed order, rounded to fp32) by the count.
+ *   Ground truth forms (gt_form), each in host memory (copied before the call returns) or, gt_on_device != 0, complete device memory on the metric's GPU:
+ *     VP_LANES_GT_PLANES   fp32 [3][h][w], any finite values;
+ *     VP_LANES_GT_BITS     u8 [h][w], bit c is plane c (VP_GT_BITS of the output size);
+ *     VP_LANES_GT_BITS_4X  u8 [4h][4w] (the dataset's 320 x 640 label for the 80 x 160 output): plane c of a pixel is bit c of the OR over its 4x4
+ *                          block -- the two MaxPool2d(2, 2) of lines 220-222 on binary planes.
+ *   DEPARTURE 3: a non-finite logit or fp32 ground-truth value makes every score of the frame NaN and is counted in `nonfinite`; the dataset means leave
+ *   such frames out and report them in nan_frames.  The trainer would propagate the NaN (or, for an infinite logit, answer inf).
+ *   DEPARTURE 4: the trainer's validation runs the model as its training does; this scores the engine's fp32 logits, whatever precision produced them.
+ *   vp_metric_add_lanes: e is a VP_EGOLANES engine with a pass behind it; its logits are read on the device under the ordering contract of
+ *     vp_metric_add_seg (the canvas's, unchanged).  The ground truth has the output's size (vp_output_dims), or four times it.
+ *   vp_metric_add_lanes_pair: the ground truth is ref's own prediction: planes of 1 where ref's logit > 0, else 0 (a NaN gives 0 and is not counted).
+ *   vp_metric_add_lanes_logits: the operator entry on a caller's logits [3][h][w], host or device; h, w >= 16 (scale 4 has a pixel) and h * w <= 1 << 22.
+ *     Planes of at most 12 800 pixels (the production 80 x 160) take two launches, larger ones seven; the scores are defined alike.
+ *   vp_metric_fetch_lanes: the one synchronisation.  Copies the first min(cap, frames) records and fills *summary (may be NULL) from ALL of them, in
+ *     double on the host: the means over the frames without NaN of score, loss_c, bce_c and edge_c = (e_0 + .. + e_4) / 5 (NaN where there is none).
+ * LANE ROWS (AutoSteer).  Per line, rows values each of xp, h_vector, target_xp, target_h (the 'n' network: one line of 64 rows per frame, logits
+ *   {1, 2, 64, 1} = xp, then h_vector):
+ *   m = h_vector > 0.5, mt = target_h > 0.5 (a NaN is not valid);  term_r = |xp_r * m_r - target_xp_r * mt_r| as fp32 operations;
+ *   dist = fp32(sum(term) / rows), conf = fp32(sum(h_vector) / rows).  SUMMATION ORDER: the sums are formed in double; element r is added to slot
+ *   r mod 256 in ascending r, then the 256 slots fold as slot i += slot i + o for o = 128, 64, .. 1; the quotient is a double division, rounded once.
+ *   Bit t of `tp` is (double)dist < thr[t]: the comparison in double against the fp32 value, as the trainer's .item() makes it.  `valid` and
+ *   `target_valid` count m and mt.  A NaN in xp or a target gives a NaN dist and no tp bit, as the trainer would.
+ *   Threshold table: the caller's, 1 .. 8 doubles, none NaN (the trainer's is {0.02, 0.05, 0.10}).  One table per run: an add with another table than the
+ *   lines so far is refused until vp_metric_reset.
+ *   DEPARTURE 5: the trainer's val() runs the model in half precision; this scores the engine's fp32 tensor with the arithmetic above.
+ *   vp_metric_add_rows: e is a VP_AUTOSTEER engine with a pass behind it; target_xp / target_h are host floats [rows], copied before the call returns.
+ *   vp_metric_add_rows_pair: the targets are ref's own rows (its xp and h_vector), read on the device.
+ *   vp_metric_add_rows_raw: the operator entry on host arrays [n_lines][rows], n_lines 1 .. 8, rows 1 .. 1024; one record per line, in order.
+ *   vp_metric_fetch_rows: the one synchronisation; the first min(cap, lines) records and *summary (may be NULL) from ALL lines with the run's table.
+ *   vp_metric_rows_ap: the summary's host code over caller arrays (tp words, conf [n_lines]); no device, no handle.  It is compute_vector_ap in
+ *     double: per table entry t the lines sorted by descending conf (TIE DEFINITION: equal conf keep line order -- the reference's argsort leaves it
+ *     open; a NaN conf goes last), tpc / fpc the running counts of set / clear tp bits, precision = tpc / (tpc + fpc + 1e-16), recall =
+ *     tpc / (lines + 1e-16), the precision envelope over {0, recall, 1} / {0, precision, 0}, numpy.interp at numpy.linspace(0, 1, 101) and the
+ *     trapezoid sum: ap[t].  precision / recall: the mean over the entries of the means over the lines; mean_ap: the mean of ap[t]; map50: the ap of the
+ *     entry equal to 0.05 as a double, NaN if the table has none.  Entries are taken in table order (the reference sorts its three ascending).
+ *     No lines: the four scores are 0, as val() answers.
+ * Capacity: max_frames lane-mask frames and max_frames lines.  vp_metric_reset empties both.  Records are bit-identical from run to run: no atomics, one
+ *   partial per workgroup, folded by the next launch in index order (bce_c up to the device library's exp / log1p, which are deterministic as well).
+ * ERRORS.  VP_ERR_ARG: another engine kind, an engine on another GPU, a pair of different sizes, h or w below 16, h * w above 1 << 22, an unknown gt_form,
+ *   a device pointer not aligned to 4 bytes (logits, fp32 planes, the 4x form), n_lines / rows / n_thr outside their ranges, a NaN threshold, another
+ *   table than the run's, a null pointer.  VP_ERR_STATE: an engine with no pass yet, a full accumulator.
+ * No add call waits for the device beyond the exceptions of vp_metric_add_seg (a scratch or staging buffer that has to grow, a pinned slot in use) and
+ *   the allocation of the record storage by the first add of either kind. */
+enum vp_lanes_gt_form { VP_LANES_GT_PLANES = 0, VP_LANES_GT_BITS = 1, VP_LANES_GT_BITS_4X = 2 };
+#define VP_ROWS_MAX_THR 8
+#define VP_ROWS_MAX_LINES 8
+#define VP_ROWS_MAX_ROWS 1024
+typedef struct vp_metric_lanes_frame {
+  float bce[3], edge[3][5], loss[3], score;
+  uint32_t n;                     /* h * w */
+  uint32_t nonfinite;             /* non-finite logits and fp32 ground-truth values */
+} vp_metric_lanes_frame;
+typedef struct vp_metric_lanes_summary {
+  int frames;
+  int nan_frames;                 /* left out of the means */
+  double score, loss[3], bce[3], edge[3];
+} vp_metric_lanes_summary;
+typedef struct vp_metric_rows_line {
+  float dist, conf;
+  uint32_t tp;                    /* bit t: dist < thr[t] */
+  uint32_t valid, target_valid;   /* rows with h_vector > 0.5 / target_h > 0.5 */
+} vp_metric_rows_line;
+typedef struct vp_metric_rows_summary {
+  int lines, n_thr;
+  double precision, recall, mean_ap, ap[VP_ROWS_MAX_THR], map50;
+} vp_metric_rows_summary;
+int vp_metric_add_lanes(vp_metric* m, vp_engine* e, const void* gt, int gt_on_device, int gt_form);
+int vp_metric_add_lanes_pair(vp_metric* m, vp_engine* e, vp_engine* ref);
+int vp_metric_add_lanes_logits(vp_metric* m, const float* logits_chw, int on_device, int h, int w, const void* gt, int gt_on_device, int gt_form);
+int vp_metric_lanes_frames(const vp_metric* m);
+int vp_metric_fetch_lanes(vp_metric* m, vp_metric_lanes_frame* records, int cap, vp_metric_lanes_summary* summary);
+int vp_metric_add_rows(vp_metric* m, vp_engine* e, const float* target_xp, const float* target_h, const double* thr, int n_thr);
+int vp_metric_add_rows_pair(vp_metric* m, vp_engine* e, vp_engine* ref, const double* thr, int n_thr);
+int vp_metric_add_rows_raw(vp_metric* m, const float* xp, const float* h_vector, const float* target_xp, const float* target_h, int n_lines, int rows, const double* thr,
+                           int n_thr);
+int vp_metric_rows_lines(const vp_metric* m);
+int vp_metric_fetch_rows(vp_metric* m, vp_metric_rows_line* records, int cap, vp_metric_rows_summary* summary);
+int vp_metric_rows_ap(const uint32_t* tp, const float* conf, int n_lines, const double* thr, int n_thr, vp_metric_rows_summary* summary);
+
 /* ---- multi-camera result exchange (BASELINE configs[3]) ---------------------------------------
  * One process (or thread) per GPU, camera r on rank r, weights replicated, no data-path collective in the networks.  For the
  * fused ego-path / BEV consumer every rank needs all cameras' results: ONE ncclAllGather (RCCL over xGMI) per frame of a

@@ -12,7 +12,10 @@ Nothing is fixed in advance: the file records what was measured.
   (d) --agreement: fp16 against fp16x3, and fp8 weight storage where the kind has it, over 32 synthetic frames: per-class IoU, flipped pixels, mAE, mEL.
   (e) the depth chain's distance from the fp64 restatement on the general cases of tests/metric_cases.py, beside torch fp32's own distance and the bar.
 
-python tools/bench_metric.py > profiles/metric.txt;  python tools/bench_metric.py --agreement >> profiles/metric.txt"""
+  --lanes: the same four measurements for the lane part (EgoLanes and AutoSteer records): see lanes().
+
+python tools/bench_metric.py > profiles/metric.txt;  python tools/bench_metric.py --agreement >> profiles/metric.txt
+python tools/bench_metric.py --lanes > profiles/metric_lanes.txt"""
 import json
 import os
 import sys
@@ -187,7 +190,92 @@ def agreement():
     print(json.dumps({"d_agreement": out}, indent=1))
 
 
+def lanes():
+    """--lanes: the lane part.  (a) device time per EgoLanes record (add_lanes on the resident logits with the ground truth resident, in each form, and the
+    pair form) and per AutoSteer record (add_rows_pair: nothing comes from the host), as in costs() (a); (b) the same scores on the host: vp_fetch_outputs +
+    the torch / numpy restatement of tests/metric_lanes_cases.py, per frame, wall clock, 16 threads; (c) EgoLanes fp16 frames/s, enqueue only, with and
+    without an add_lanes_pair behind every pass; (d) the general cases' distance from the reference's fp64 run."""
+    import metric_lanes_cases as lc
+
+    torch.set_num_threads(16)
+    ego, ego_ref = (lib.Engine("egolanes", vw.pack_state_dict(weights.make_state_dict("egolanes", 2)), precision="fp16") for _ in range(2))
+    blob = vw.pack_state_dict(synthetic.make_autosteer_state_dict(0))
+    st, st_ref = lib.Engine("autosteer", blob, precision="fp16"), lib.Engine("autosteer", blob, precision="fp16x3")
+    frame, sframe = synthetic.synthetic_frame(H, W, 21), synthetic.synthetic_frame(512, 1024, 22)
+    for e in (ego, ego_ref):
+        e.infer(frame)
+    for e in (st, st_ref):
+        e.infer(sframe)
+    oh, ow = ego.output_dims()[-2:]
+    bits = lc.general_inputs((oh, ow), seed=3)[1]
+    big, planes = lc.bits_4x(bits, 4), lc.planes_of_bits(bits)
+    d_bits, d_big, d_planes = (torch.from_numpy(v).cuda() for v in (bits, big, planes))
+    torch.cuda.synchronize()
+    m = lib.Metric(max_frames=WARM + FRAMES)
+    out = {"library": lib.version(), "weights": "SYNTHETIC (seeded state-dicts); frames: synthetic 1280 x 720 (EgoLanes, output %d x %d) and 1024 x 512 (AutoSteer)" % (oh, ow),
+           "frames_per_measurement": FRAMES, "warm_up": WARM}
+    a = {}
+    for name, eng, add in (("lanes_record_bits_us", ego, lambda: m.add_lanes(ego, d_bits.data_ptr(), "bits", gt_device=True)),
+                           ("lanes_record_bits4x_us", ego, lambda: m.add_lanes(ego, d_big.data_ptr(), "bits4x", gt_device=True)),
+                           ("lanes_record_planes_us", ego, lambda: m.add_lanes(ego, d_planes.data_ptr(), "planes", gt_device=True)),
+                           ("lanes_pair_record_us", ego, lambda: m.add_lanes_pair(ego, ego_ref)),
+                           ("rows_pair_record_us", st, lambda: m.add_rows_pair(st, st_ref))):
+        rounds = []
+        for _ in range(3):
+            m.reset()
+            rounds.append(round(timed_adds(eng, add), 2))
+            m.fetch_lanes()
+            m.fetch_rows()
+        a[name + "_rounds"] = rounds
+    out["a_device_time_per_record"] = a
+    b = {}
+    txp, th = np.random.default_rng(1).random(64).astype(np.float32), np.ones(64, np.float32)
+    for name, eng, fn in (("lanes_host_us", ego, lambda lg: lc.lanes_ref(lg, planes)), ("rows_host_us", st, lambda lg: lc.rows_ref(lg[0].reshape(-1), lg[1].reshape(-1), txp, th))):
+        d2h, total = [], []
+        for i in range(20 + 200):
+            eng.enqueue()
+            eng.sync()
+            t0 = time.perf_counter()
+            eng.fetch_outputs()
+            lg = eng.logits()
+            t1 = time.perf_counter()
+            fn(lg)
+            t2 = time.perf_counter()
+            if i >= 20:
+                d2h.append((t1 - t0) * 1e6)
+                total.append((t2 - t0) * 1e6)
+        b[name] = {"p50": round(float(np.percentile(total, 50)), 1), "p99": round(float(np.percentile(total, 99)), 1), "of_which_fetch_p50": round(float(np.percentile(d2h, 50)), 1)}
+    out["b_host_time_per_frame_200_frames_16_threads"] = b
+    c = {"without": [], "with_add_lanes_pair": []}
+    for _ in range(3):
+        for key in ("without", "with_add_lanes_pair"):
+            m.reset()
+            for _ in range(WARM):
+                ego.enqueue()
+            ego.sync()
+            t0 = time.perf_counter()
+            for _ in range(FRAMES):
+                ego.enqueue()
+                if key != "without":
+                    m.add_lanes_pair(ego, ego_ref)
+            ego.sync()
+            m.fetch_lanes()
+            c[key].append(round(FRAMES / (time.perf_counter() - t0), 1))
+    out["c_egolanes_fp16_frames_per_s_rounds"] = c
+    lines = []
+    for shape in lc.GENERAL_SHAPES:
+        lc.check_lanes_general(lib, shape, report=lines)
+    out["d_lanes_distance_from_fp64"] = lines
+    print(json.dumps(out, indent=1))
+    m.close()
+    for e in (ego, ego_ref, st, st_ref):
+        e.close()
+
+
 if __name__ == "__main__":
     if not torch.cuda.is_available():
         raise SystemExit("bench_metric.py needs a GPU")
-    agreement() if "--agreement" in sys.argv[1:] else costs()
+    if "--lanes" in sys.argv[1:]:
+        lanes()
+    else:
+        agreement() if "--agreement" in sys.argv[1:] else costs()
