@@ -605,6 +605,16 @@ class Metric {
   int rows_n_thr() const { return rows_n_thr_; }
   const double* rows_thr() const { return rows_thr_; }
   void fetch_rows(RowsRecord* out, int count);
+  // the label part (kernels.hpp LabelSegParams / LabelDepthParams): the ground truth is built on the device from a label file's decoded pixels, in host
+  // memory and copied before the call returns; then the seg / depth chain of add_seg / add_depth.  One MetricRecord AND one LabelRecord per call, the
+  // label records in storage of their own (allocated by the first such call).  crop: {l, t, r, b} or null (the whole image); colours: [n][4] r, g, b, class
+  void add_seg_label(Engine& e, const uint8_t* label, int channels, int h, int w, int stride, const int* crop, const uint8_t* colours, int n_colours);
+  void add_depth_label(Engine& e, const void* label, int dtype, int h, int w, int stride);
+  void add_seg_logits_label(const float* logits, bool on_device, int c, int oh, int ow, const uint8_t* label, int channels, int h, int w, int stride, const int* crop,
+                            const uint8_t* colours, int n_colours);
+  void add_depth_plane_label(const float* pred, bool pred_on_device, int oh, int ow, const void* label, int dtype, int h, int w, int stride);
+  int label_frames() const { return label_frames_; }
+  void fetch_labels(LabelRecord* out, int count);
 
  private:
   struct Stage {   // a caller's pageable array: copied into one of two pinned slots before the call returns, then one H2D into `d`
@@ -660,7 +670,27 @@ class Metric {
   RowsRecord* d_rows_records_ = nullptr;
   uint8_t* d_lanes_scratch_ = nullptr;   // the partials, then the general path's D0 and pooled levels: see lanes()
   size_t lanes_scratch_cap_ = 0;
+  // label part
+  struct LabelTab {   // a nearest table on the device, kept per (source, destination) size as Canvas::table keeps its tables
+    int src, dst;
+    int* idx;
+  };
+  const int* label_tab(int src, int dst);
+  LabelRecord* label_next(const char* who);
+  const uint8_t* label_seg(LabelSegParams q, const uint8_t* label, int oh, int ow, LabelRecord* rec);
+  const float* label_depth(const void* label, int dtype, int h, int w, int stride, int oh, int ow, LabelRecord* rec);
+  int label_frames_ = 0;
+  LabelRecord* d_label_records_ = nullptr;
+  uint8_t* d_label_scratch_ = nullptr;   // the ground truth at output size, then the partials
+  size_t label_scratch_cap_ = 0;
+  std::vector<LabelTab> label_tabs_;
 };
+
+// the arguments of a colour / mask label checked and laid into the kernel's parameters (std::invalid_argument names `who`); label, tables, outputs unset
+LabelSegParams label_seg_params(const char* who, const void* label, int channels, int h, int w, int stride, const int* crop, const uint8_t* colours, int n_colours);
+void label_check_depth(const char* who, const void* label, int dtype, int h, int w, int stride);
+// OpenCV's resizeNN index table (oracle/pre_post.py nearest_index): tab[d] for d in [0, dst)
+void label_nearest_tab(int src, int dst, int* tab);
 
 #define VP_HIP_CHECK(expr)                                                                                   \
   do {                                                                                                       \

@@ -1190,6 +1190,13 @@ void Metric::release() {
     *p = nullptr;
   }
   lanes_scratch_cap_ = 0;
+  for (void** p : {reinterpret_cast<void**>(&d_label_records_), reinterpret_cast<void**>(&d_label_scratch_)}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  label_scratch_cap_ = 0;
+  for (LabelTab& t : label_tabs_) (void)hipFree(t.idx);
+  label_tabs_.clear();
   if (stream_) (void)hipStreamDestroy(stream_);
   stream_ = nullptr;
 }
@@ -1202,7 +1209,7 @@ void Metric::reset() {
   if (d_det_small_) VP_HIP_CHECK(hipMemsetAsync(d_det_small_, 0, 2 * sizeof(unsigned), stream_));   // the running totals
   det_frames_ = det_n_iou_ = 0;
   det_labels_bound_ = 0;
-  lanes_frames_ = rows_lines_ = rows_n_thr_ = 0;   // their kernels store whole records
+  lanes_frames_ = rows_lines_ = rows_n_thr_ = label_frames_ = 0;   // their kernels store whole records
 }
 
 // a device buffer that has to grow is freed only once the metric's own work has run
@@ -1734,6 +1741,181 @@ void Metric::fetch_rows(RowsRecord* out, int count) {
   if (count < 0 || count > rows_lines_ || (count > 0 && !out)) throw std::invalid_argument("vp_metric_fetch_rows: more records than were added, or a null buffer");
   VP_HIP_CHECK(hipSetDevice(gpu_));
   if (count) VP_HIP_CHECK(hipMemcpyAsync(out, d_rows_records_, (size_t)count * sizeof(RowsRecord), hipMemcpyDeviceToHost, stream_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+// ---- the label part: ground truth from a label file's decoded pixels, records of their own
+void label_nearest_tab(int src, int dst, int* tab) { nearest_tab(src, dst, tab); }
+
+LabelSegParams label_seg_params(const char* who, const void* label, int channels, int h, int w, int stride, const int* crop, const uint8_t* colours, int n_colours) {
+  const std::string me(who);
+  if (!label) throw std::invalid_argument(me + ": null label");
+  if (channels != 1 && channels != 3) throw std::invalid_argument(me + ": channels " + std::to_string(channels) + " (1: a mask label, 3: a colour label)");
+  if (h < 1 || w < 1 || h > kLabelMaxSide || w > kLabelMaxSide) throw std::invalid_argument(me + ": a label of " + std::to_string(h) + " x " + std::to_string(w) + " (1 .. 16384 each)");
+  if ((long long)stride < (long long)w * channels) throw std::invalid_argument(me + ": stride " + std::to_string(stride) + " below the row's " + std::to_string(w * channels) + " bytes");
+  LabelSegParams q{};
+  q.channels = channels;
+  q.h = h;
+  q.w = w;
+  q.stride = stride;
+  q.cw = w;
+  q.ch = h;
+  if (crop) {
+    for (int k = 0; k < 4; ++k)
+      if (crop[k] < kLabelCropMin || crop[k] > kLabelCropMax) throw std::invalid_argument(me + ": a crop coordinate outside -16384 .. 32768");
+    q.l = crop[0];
+    q.t = crop[1];
+    q.cw = crop[2] - crop[0];
+    q.ch = crop[3] - crop[1];
+    if (q.cw < 1 || q.ch < 1) throw std::invalid_argument(me + ": a crop of " + std::to_string(q.ch) + " x " + std::to_string(q.cw) + " pixels");
+  }
+  if (channels == 3) {
+    if (!colours || n_colours < 1 || n_colours > kLabelMaxColours) throw std::invalid_argument(me + ": a null colour table, or n_colours outside 1 .. 16");
+    for (int k = 0; k < n_colours; ++k) {
+      if (colours[4 * k + 3] > 2) throw std::invalid_argument(me + ": class " + std::to_string(colours[4 * k + 3]) + " in the colour table (0 .. 2)");
+      q.rgb[k] = (unsigned)colours[4 * k] | (unsigned)colours[4 * k + 1] << 8 | (unsigned)colours[4 * k + 2] << 16;
+      q.cls[k] = colours[4 * k + 3];
+    }
+    q.n_colours = n_colours;
+  }
+  return q;
+}
+
+void label_check_depth(const char* who, const void* label, int dtype, int h, int w, int stride) {
+  const std::string me(who);
+  if (!label) throw std::invalid_argument(me + ": null label");
+  if (dtype != kLabelF32 && dtype != kLabelF64) throw std::invalid_argument(me + ": dtype " + std::to_string(dtype) + " (VP_LABEL_F32, VP_LABEL_F64)");
+  if (h < 1 || w < 1 || h > kLabelMaxSide || w > kLabelMaxSide) throw std::invalid_argument(me + ": a label of " + std::to_string(h) + " x " + std::to_string(w) + " (1 .. 16384 each)");
+  if (stride < w) throw std::invalid_argument(me + ": stride " + std::to_string(stride) + " below the row's " + std::to_string(w) + " elements");
+}
+
+// Canvas::table's scheme: the first use of a size uploads its table and waits; the one unused longest goes when there are 16
+const int* Metric::label_tab(int src, int dst) {
+  for (size_t i = 0; i < label_tabs_.size(); ++i)
+    if (label_tabs_[i].src == src && label_tabs_[i].dst == dst) {
+      std::rotate(label_tabs_.begin() + i, label_tabs_.begin() + i + 1, label_tabs_.end());
+      return label_tabs_.back().idx;
+    }
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  if (label_tabs_.size() >= 16) {
+    (void)hipFree(label_tabs_.front().idx);
+    label_tabs_.erase(label_tabs_.begin());
+  }
+  std::vector<int> idx((size_t)dst);
+  nearest_tab(src, dst, idx.data());
+  LabelTab t{src, dst, nullptr};
+  VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t.idx), idx.size() * sizeof(int)));
+  label_tabs_.push_back(t);   // owned from here on
+  VP_HIP_CHECK(hipMemcpyAsync(t.idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  return t.idx;
+}
+
+LabelRecord* Metric::label_next(const char* who) {
+  if (label_frames_ >= max_frames_)
+    throw std::runtime_error(std::string(who) + ": the label accumulator is full (" + std::to_string(max_frames_) + " frames; vp_metric_fetch_labels, then vp_metric_reset)");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (!d_label_records_) VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_label_records_), (size_t)max_frames_ * sizeof(LabelRecord)));
+  return d_label_records_ + label_frames_;
+}
+
+// scratch: the ground truth [oh][ow] (bytes, or fp32 for a depth label), then the partials.  Everything that may wait (tables, scratch) comes before the copy.
+const uint8_t* Metric::label_seg(LabelSegParams q, const uint8_t* label, int oh, int ow, LabelRecord* rec) {
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_part = up((size_t)oh * ow);
+  q.ty = label_tab(q.ch, oh);
+  q.tx = label_tab(q.cw, ow);
+  grow(d_label_scratch_, label_scratch_cap_, o_part + up(4 * kMetricBlocks * sizeof(unsigned)));
+  q.label = static_cast<const uint8_t*>(stage_host(stage_[1], label, (size_t)(q.h - 1) * q.stride + (size_t)q.w * q.channels));
+  q.oh = oh;
+  q.ow = ow;
+  q.gt = d_label_scratch_;
+  q.part = reinterpret_cast<unsigned*>(d_label_scratch_ + o_part);
+  q.rec = rec;
+  VP_HIP_CHECK(launch_label_seg(q, stream_));
+  return q.gt;
+}
+
+const float* Metric::label_depth(const void* label, int dtype, int h, int w, int stride, int oh, int ow, LabelRecord* rec) {
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_part = up(sizeof(float) * (size_t)oh * ow), es = dtype == kLabelF64 ? sizeof(double) : sizeof(float);
+  LabelDepthParams q{};
+  q.ty = label_tab(h, oh);
+  q.tx = label_tab(w, ow);
+  grow(d_label_scratch_, label_scratch_cap_, o_part + up(kMetricBlocks * sizeof(LabelExtPartial)));
+  q.label = stage_host(stage_[1], label, es * ((size_t)(h - 1) * stride + (size_t)w));
+  q.dtype = dtype;
+  q.h = h;
+  q.w = w;
+  q.stride = stride;
+  q.oh = oh;
+  q.ow = ow;
+  q.gt = reinterpret_cast<float*>(d_label_scratch_);
+  q.part = reinterpret_cast<LabelExtPartial*>(d_label_scratch_ + o_part);
+  q.rec = rec;
+  VP_HIP_CHECK(launch_label_depth(q, stream_));
+  return q.gt;
+}
+
+void Metric::add_seg_label(Engine& e, const uint8_t* label, int channels, int h, int w, int stride, const int* crop, const uint8_t* colours, int n_colours) {
+  source_of(e, "vp_metric_add_seg_label", false);
+  const LabelSegParams q = label_seg_params("vp_metric_add_seg_label", label, channels, h, w, stride, crop, colours, n_colours);
+  metric_check_seg_args("vp_metric_add_seg_label", e.d_logits_, e.out_c_, e.out_h_, e.out_w_, label, 0);
+  MetricRecord* rec = next_record("vp_metric_add_seg_label");
+  LabelRecord* lrec = label_next("vp_metric_add_seg_label");
+  const uint8_t* d_gt = label_seg(q, label, e.out_h_, e.out_w_, lrec);   // ahead of the wait: the label kernels overlap the engine's pass
+  wait_for(e, ev_src_[0]);
+  seg(e.d_logits_, nullptr, d_gt, e.out_c_, e.out_h_, e.out_w_, 0, rec);
+  release_to(e, ev_read_[0]);
+  ++frames_;
+  ++label_frames_;
+}
+
+void Metric::add_depth_label(Engine& e, const void* label, int dtype, int h, int w, int stride) {
+  source_of(e, "vp_metric_add_depth_label", true);
+  label_check_depth("vp_metric_add_depth_label", label, dtype, h, w, stride);
+  metric_check_depth_args("vp_metric_add_depth_label", e.d_logits_, label, e.out_h_, e.out_w_);
+  MetricRecord* rec = next_record("vp_metric_add_depth_label");
+  LabelRecord* lrec = label_next("vp_metric_add_depth_label");
+  const float* d_gt = label_depth(label, dtype, h, w, stride, e.out_h_, e.out_w_, lrec);
+  wait_for(e, ev_src_[0]);
+  depth(e.d_logits_, d_gt, e.out_h_, e.out_w_, rec);
+  release_to(e, ev_read_[0]);
+  ++frames_;
+  ++label_frames_;
+}
+
+void Metric::add_seg_logits_label(const float* logits, bool on_device, int c, int oh, int ow, const uint8_t* label, int channels, int h, int w, int stride, const int* crop,
+                                  const uint8_t* colours, int n_colours) {
+  const LabelSegParams q = label_seg_params("vp_metric_add_seg_logits_label", label, channels, h, w, stride, crop, colours, n_colours);
+  metric_check_seg_args("vp_metric_add_seg_logits_label", logits, c, oh, ow, label, 0);
+  if (on_device && (reinterpret_cast<uintptr_t>(logits) & 3)) throw std::invalid_argument("vp_metric_add_seg_logits_label: device logits not aligned to 4 bytes");
+  MetricRecord* rec = next_record("vp_metric_add_seg_logits_label");
+  LabelRecord* lrec = label_next("vp_metric_add_seg_logits_label");
+  const float* d_logits = on_device ? logits : static_cast<const float*>(stage_host(stage_[0], logits, sizeof(float) * (size_t)oh * ow * c));
+  const uint8_t* d_gt = label_seg(q, label, oh, ow, lrec);
+  seg(d_logits, nullptr, d_gt, c, oh, ow, 0, rec);
+  ++frames_;
+  ++label_frames_;
+}
+
+void Metric::add_depth_plane_label(const float* pred, bool pred_on_device, int oh, int ow, const void* label, int dtype, int h, int w, int stride) {
+  label_check_depth("vp_metric_add_depth_plane_label", label, dtype, h, w, stride);
+  metric_check_depth_args("vp_metric_add_depth_plane_label", pred, label, oh, ow);
+  if (pred_on_device && (reinterpret_cast<uintptr_t>(pred) & 3)) throw std::invalid_argument("vp_metric_add_depth_plane_label: device plane not aligned to 4 bytes");
+  MetricRecord* rec = next_record("vp_metric_add_depth_plane_label");
+  LabelRecord* lrec = label_next("vp_metric_add_depth_plane_label");
+  const float* d_pred = pred_on_device ? pred : static_cast<const float*>(stage_host(stage_[0], pred, sizeof(float) * (size_t)oh * ow));
+  const float* d_gt = label_depth(label, dtype, h, w, stride, oh, ow, lrec);
+  depth(d_pred, d_gt, oh, ow, rec);
+  ++frames_;
+  ++label_frames_;
+}
+
+void Metric::fetch_labels(LabelRecord* out, int count) {
+  if (count < 0 || count > label_frames_ || (count > 0 && !out)) throw std::invalid_argument("vp_metric_fetch_labels: more records than were added, or a null buffer");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (count) VP_HIP_CHECK(hipMemcpyAsync(out, d_label_records_, (size_t)count * sizeof(LabelRecord), hipMemcpyDeviceToHost, stream_));
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 

@@ -814,6 +814,52 @@ struct MetricRowsParams {
 };
 hipError_t launch_metric_rows(const MetricRowsParams& p, hipStream_t st);
 
+// ---- vp_metric, label part (include/vp_hip.h "vp_metric: ground truth from label files"; kernels_misc.hip label_*): a dataset's label file, as decoded,
+// becomes the ground truth of the network's output size on the device (load_data_scene_seg.py:55-166, load_data_scene_3d.py:59-66, the nearest resize
+// of augmentations.py:133-177).  Colour / mask labels: label_stats_kernel counts the full-resolution crop (the part of it inside the image; the launcher
+// knows the rest in closed form) into one integer partial per workgroup, label_gt_kernel samples through the two nearest tables, classifies and stores,
+// and its workgroup 0 folds the partials into the record.  Depth labels: label_minmax_kernel writes one partial per workgroup, every workgroup of
+// label_depth_gt_kernel folds them in index order before it normalises.  Integer folds and a fixed tree: records are bit-identical run to run.
+// LabelRecord is vp_label_frame's layout (vp_api.cpp checks it).
+struct LabelRecord {
+  int kind;   // 0 colour label, 2 mask label, 1 depth label: the engine kind the ground truth is for
+  unsigned n, freq[3], unmatched, outside, nonfinite;
+  double mn, mx;
+};
+constexpr int kLabelMaxColours = 16, kLabelMaxSide = 16384;
+constexpr int kLabelCropMin = -16384, kLabelCropMax = 32768;   // every box coordinate: cw * ch stays below 2^32
+enum { kLabelF32 = 0, kLabelF64 = 1 };
+struct LabelSegParams {
+  const uint8_t* label;   // [h][stride bytes], channels bytes per pixel (3: R, G, B)
+  int channels, h, w, stride;
+  int l, t, cw, ch;       // the crop box: pixel (y, x) of the crop is image pixel (t + y, l + x), (0, 0, 0) / 0 outside the image
+  int n_colours;          // channels 3: table rows, the first equal row gives the class
+  unsigned rgb[kLabelMaxColours];   // r | g << 8 | b << 16
+  unsigned char cls[kLabelMaxColours];
+  const int* ty;          // [oh] nearest table ch -> oh
+  const int* tx;          // [ow] nearest table cw -> ow
+  int oh, ow;
+  uint8_t* gt;            // [oh][ow]: the class or 255 (channels 3), the sampled byte (channels 1)
+  unsigned* part;         // [kMetricBlocks][4]: freq[3], unmatched
+  LabelRecord* rec;
+};
+hipError_t launch_label_seg(const LabelSegParams& p, hipStream_t st);
+struct LabelExtPartial {
+  double mn, mx;
+  unsigned bad, nan;   // non-finite values; NaNs among them
+};
+struct LabelDepthParams {
+  const void* label;      // [h][stride elements] fp32 or fp64
+  int dtype, h, w, stride;
+  const int* ty;          // [oh] nearest table h -> oh
+  const int* tx;          // [ow] nearest table w -> ow
+  int oh, ow;
+  float* gt;              // [oh][ow]
+  LabelExtPartial* part;  // [kMetricBlocks]
+  LabelRecord* rec;
+};
+hipError_t launch_label_depth(const LabelDepthParams& p, hipStream_t st);
+
 // ---- vp_metric, detector part (include/vp_hip.h "vp_metric: the detector"; kernels_detect.hip det_val_*): the validation post-process of the detector's
 // trainer (auto_speed_util.py non_max_suppression + compute_metric) on a raw tensor [4 + nc][nb].  The chain, one launch each, no workgroup talking to
 // another inside a launch:

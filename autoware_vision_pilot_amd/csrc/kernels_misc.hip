@@ -1914,4 +1914,213 @@ hipError_t launch_metric_rows(const MetricRowsParams& p, hipStream_t st) {
   VP_LAUNCH(metric_rows_kernel, dim3(p.n_lines), dim3(256), 0, st, p);
 }
 
+// ------------------------------------------------------------------------------------------ vp_metric, label part
+// load_data_scene_seg.py:55-166 (extractROI, createGroundTruth), load_data_scene_3d.py:59-66 and the nearest resize behind them, restated (kernels.hpp).
+// the class of a colour: the first table row it equals; 3: none
+__device__ __forceinline__ unsigned label_class(const LabelSegParams& p, unsigned rgb) {
+  unsigned c = 3u;
+  for (int k = p.n_colours - 1; k >= 0; --k) c = rgb == p.rgb[k] ? (unsigned)p.cls[k] : c;
+  return c;
+}
+// one pixel of the crop into cnt = freq[3], unmatched (colour) or cnt[0] = nonzero (mask)
+__device__ __forceinline__ void label_count(const LabelSegParams& p, unsigned v, unsigned* cnt) {
+  if (p.channels == 3) {
+    const unsigned c = label_class(p, v);
+    cnt[0] += c == 0u;
+    cnt[1] += c == 1u;
+    cnt[2] += c == 2u;
+    cnt[3] += c == 3u;
+  } else {
+    cnt[0] += v != 0u;
+  }
+}
+// The part [y0, y0 + ih) x [x0, x0 + iw) of the crop that lies inside the image, in runs of 16 pixels per row: a full run that starts on a 16-byte
+// boundary is read with 16-byte loads (every run of a row when the stride and the row's first byte are multiples of 16, as for a 1920-wide label),
+// any other run byte by byte.  Counters per work-item, a shuffle fold per wave, one partial per workgroup.
+__global__ __launch_bounds__(256) void label_stats_kernel(const LabelSegParams p, int x0, int y0, int iw, int ih) {
+  __shared__ unsigned wave_cnt[4][4];
+  unsigned cnt[4] = {0u, 0u, 0u, 0u};
+  const unsigned rpr = ((unsigned)iw + 15u) >> 4, total = rpr * (unsigned)ih;   // at most 1024 * 16384
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const unsigned row = i / rpr, run = i - row * rpr;
+    const int x = x0 + (int)(run << 4);
+    const int npx = min(16, x0 + iw - x);
+    const uint8_t* src = p.label + (size_t)(y0 + (int)row) * (size_t)p.stride + (size_t)x * (size_t)p.channels;
+    if (npx == 16 && !(reinterpret_cast<uintptr_t>(src) & 15)) {
+      if (p.channels == 3) {
+        unsigned w[12];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const int4 q = reinterpret_cast<const int4*>(src)[k];
+          w[4 * k] = (unsigned)q.x;
+          w[4 * k + 1] = (unsigned)q.y;
+          w[4 * k + 2] = (unsigned)q.z;
+          w[4 * k + 3] = (unsigned)q.w;
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const int word = (24 * j) >> 5, sh = (24 * j) & 31;
+          unsigned v = w[word] >> sh;
+          if (sh > 8) v |= w[word + 1] << (32 - sh);   // sh is 0, 8, 16 or 24: word + 1 <= 11 whenever sh > 8
+          label_count(p, v & 0xFFFFFFu, cnt);
+        }
+      } else {
+        const int4 q = *reinterpret_cast<const int4*>(src);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const unsigned w = (unsigned)((j >> 2) == 0 ? q.x : (j >> 2) == 1 ? q.y : (j >> 2) == 2 ? q.z : q.w);
+          label_count(p, (w >> (8 * (j & 3))) & 255u, cnt);
+        }
+      }
+    } else {
+      for (int j = 0; j < npx; ++j) {
+        const uint8_t* s = src + j * p.channels;
+        label_count(p, p.channels == 3 ? ((unsigned)s[0] | (unsigned)s[1] << 8 | (unsigned)s[2] << 16) : (unsigned)s[0], cnt);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt[k] += __shfl_xor(cnt[k], o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wave_cnt[threadIdx.x >> 6][k] = cnt[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) p.part[4 * blockIdx.x + threadIdx.x] = wave_cnt[0][threadIdx.x] + wave_cnt[1][threadIdx.x] + wave_cnt[2][threadIdx.x] + wave_cnt[3][threadIdx.x];
+}
+struct LabelAddJoin {
+  __device__ __forceinline__ unsigned operator()(unsigned a, unsigned b) const { return a + b; }
+};
+// one work-item per output pixel; workgroup 0 also folds the stats partials (nb <= 256) and stores the record.  outside: crop pixels outside the image,
+// black_cls: the class of (0, 0, 0) by the table (3: none) -- they are counted in it
+__global__ __launch_bounds__(256) void label_gt_kernel(const LabelSegParams p, unsigned nb, unsigned outside, unsigned black_cls) {
+  __shared__ unsigned lds[256];
+  const unsigned n_out = (unsigned)p.oh * (unsigned)p.ow, i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_out) {
+    const unsigned oy = i / (unsigned)p.ow, ox = i - oy * (unsigned)p.ow;
+    const int sy = p.t + p.ty[oy], sx = p.l + p.tx[ox];
+    unsigned v = 0u;
+    if (sy >= 0 && sy < p.h && sx >= 0 && sx < p.w) {
+      const uint8_t* s = p.label + (size_t)sy * (size_t)p.stride + (size_t)sx * (size_t)p.channels;
+      v = p.channels == 3 ? ((unsigned)s[0] | (unsigned)s[1] << 8 | (unsigned)s[2] << 16) : (unsigned)s[0];
+    }
+    if (p.channels == 3) {
+      const unsigned c = label_class(p, v);
+      v = c < 3u ? c : 255u;
+    }
+    p.gt[i] = (uint8_t)v;
+  }
+  if (blockIdx.x != 0) return;
+  unsigned tot[4];
+  for (int k = 0; k < 4; ++k) tot[k] = metric_block_reduce(threadIdx.x < nb ? p.part[4 * threadIdx.x + k] : 0u, lds, LabelAddJoin());
+  if (threadIdx.x != 0) return;
+  LabelRecord r;
+  r.kind = p.channels == 3 ? 0 : 2;
+  r.n = (unsigned)p.cw * (unsigned)p.ch;
+  for (int k = 0; k < 3; ++k) r.freq[k] = tot[k] + (p.channels == 3 && black_cls == (unsigned)k ? outside : 0u);
+  r.unmatched = p.channels == 3 ? tot[3] : 0u;
+  r.outside = outside;
+  r.nonfinite = 0u;
+  r.mn = r.mx = 0.0;
+  *p.rec = r;
+}
+hipError_t launch_label_seg(const LabelSegParams& p, hipStream_t st) {
+  if (!p.label || !p.ty || !p.tx || !p.gt || !p.part || !p.rec || (p.channels != 1 && p.channels != 3) || p.h < 1 || p.w < 1 || p.h > kLabelMaxSide || p.w > kLabelMaxSide ||
+      (long long)p.stride < (long long)p.w * p.channels || p.cw < 1 || p.ch < 1 || p.l < kLabelCropMin || p.t < kLabelCropMin || (long long)p.l + p.cw > kLabelCropMax ||
+      (long long)p.t + p.ch > kLabelCropMax || p.oh < 1 || p.ow < 1 || (long long)p.oh * p.ow > (long long)kMetricMaxN)
+    return hipErrorInvalidValue;
+  unsigned black_cls = 3u;
+  if (p.channels == 3) {
+    if (p.n_colours < 1 || p.n_colours > kLabelMaxColours) return hipErrorInvalidValue;
+    for (int k = p.n_colours - 1; k >= 0; --k) {
+      if (p.cls[k] > 2 || p.rgb[k] > 0xFFFFFFu) return hipErrorInvalidValue;
+      if (p.rgb[k] == 0u) black_cls = p.cls[k];
+    }
+  }
+  const int x0 = p.l > 0 ? p.l : 0, y0 = p.t > 0 ? p.t : 0;
+  const int x1 = p.l + p.cw < p.w ? p.l + p.cw : p.w, y1 = p.t + p.ch < p.h ? p.t + p.ch : p.h;
+  const int iw = x1 > x0 ? x1 - x0 : 0, ih = y1 > y0 ? y1 - y0 : 0;
+  const unsigned inside = (iw && ih) ? (unsigned)iw * (unsigned)ih : 0u, outside = (unsigned)p.cw * (unsigned)p.ch - inside;
+  const unsigned nb = metric_blocks(inside ? (size_t)((iw + 15) >> 4) * (size_t)ih : 0);
+  hipLaunchKernelGGL(label_stats_kernel, dim3(nb), dim3(256), 0, st, p, x0, y0, inside ? iw : 0, inside ? ih : 0);
+  VP_LAUNCH(label_gt_kernel, dim3(nblk((long long)p.oh * p.ow)), dim3(256), 0, st, p, nb, outside, black_cls);
+}
+
+// numpy's min and max of a plane: a NaN anywhere makes both NaN (the consumer applies that: `nan`).  Among equal values -0.0 is the smaller: numpy leaves
+// the sign of a zero extreme to its reduction order, this does not.
+struct LabelExtJoin {
+  __device__ __forceinline__ LabelExtPartial operator()(const LabelExtPartial& a, const LabelExtPartial& b) const {
+    LabelExtPartial r;
+    r.mn = (b.mn < a.mn || (b.mn == a.mn && __builtin_signbit(b.mn))) ? b.mn : a.mn;
+    r.mx = (b.mx > a.mx || (b.mx == a.mx && !__builtin_signbit(b.mx))) ? b.mx : a.mx;
+    r.bad = a.bad + b.bad;
+    r.nan = a.nan + b.nan;
+    return r;
+  }
+};
+__device__ __forceinline__ double label_depth_at(const LabelDepthParams& p, int y, int x) {
+  const size_t i = (size_t)y * (size_t)p.stride + (size_t)x;
+  return p.dtype == kLabelF64 ? static_cast<const double*>(p.label)[i] : (double)static_cast<const float*>(p.label)[i];   // fp32 -> fp64 is exact
+}
+// rows in turn over the workgroups, a row's elements over the work-items: one partial per workgroup
+__global__ __launch_bounds__(256) void label_minmax_kernel(const LabelDepthParams p) {
+  __shared__ LabelExtPartial lds[256];
+  LabelExtPartial s{INFINITY, -INFINITY, 0u, 0u};
+  for (int y = blockIdx.x; y < p.h; y += gridDim.x)
+    for (int x = threadIdx.x; x < p.w; x += 256) {
+      const double v = label_depth_at(p, y, x);
+      if (v != v) {
+        ++s.nan;
+        ++s.bad;
+      } else {
+        s = LabelExtJoin()(s, LabelExtPartial{v, v, fabs(v) == (double)INFINITY ? 1u : 0u, 0u});
+      }
+    }
+  s = metric_block_reduce(s, lds, LabelExtJoin());
+  if (threadIdx.x == 0) p.part[blockIdx.x] = s;
+}
+// every workgroup folds the nb <= 256 partials (partial b through work-item b, the fixed tree), then one work-item per output pixel:
+// g = (v - mn) / (mx - mn) in the label's type, one subtraction and one division, fp64 rounded to nearest into fp32
+__global__ __launch_bounds__(256) void label_depth_gt_kernel(const LabelDepthParams p, unsigned nb) {
+  __shared__ LabelExtPartial lds[256];
+  LabelExtPartial s{INFINITY, -INFINITY, 0u, 0u};
+  if (threadIdx.x < nb) s = p.part[threadIdx.x];
+  s = metric_block_reduce(s, lds, LabelExtJoin());
+  const double mn = s.nan ? (double)NAN : s.mn, mx = s.nan ? (double)NAN : s.mx;
+  const unsigned n_out = (unsigned)p.oh * (unsigned)p.ow, i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_out) {
+    const unsigned oy = i / (unsigned)p.ow, ox = i - oy * (unsigned)p.ow;
+    const size_t at = (size_t)p.ty[oy] * (size_t)p.stride + (size_t)p.tx[ox];
+    float g;
+    if (p.dtype == kLabelF64) {
+      g = (float)((static_cast<const double*>(p.label)[at] - mn) / (mx - mn));
+    } else {
+      const float fmn = (float)mn, fmx = (float)mx;   // exact: both are fp32 values of the plane
+      g = __fdiv_rn(__fsub_rn(static_cast<const float*>(p.label)[at], fmn), __fsub_rn(fmx, fmn));
+    }
+    p.gt[i] = g;
+  }
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  LabelRecord r;
+  r.kind = 1;
+  r.n = (unsigned)p.h * (unsigned)p.w;
+  r.freq[0] = r.freq[1] = r.freq[2] = r.unmatched = r.outside = 0u;
+  r.nonfinite = s.bad;
+  r.mn = mn;
+  r.mx = mx;
+  *p.rec = r;
+}
+hipError_t launch_label_depth(const LabelDepthParams& p, hipStream_t st) {
+  if (!p.label || !p.ty || !p.tx || !p.gt || !p.part || !p.rec || (p.dtype != kLabelF32 && p.dtype != kLabelF64) || p.h < 1 || p.w < 1 || p.h > kLabelMaxSide ||
+      p.w > kLabelMaxSide || p.stride < p.w || p.oh < 1 || p.ow < 1 || (long long)p.oh * p.ow > (long long)kMetricMaxN ||
+      (reinterpret_cast<uintptr_t>(p.label) & (p.dtype == kLabelF64 ? 7 : 3)))
+    return hipErrorInvalidValue;
+  const unsigned nb = p.h < kMetricBlocks ? (unsigned)p.h : (unsigned)kMetricBlocks;
+  hipLaunchKernelGGL(label_minmax_kernel, dim3(nb), dim3(256), 0, st, p);
+  VP_LAUNCH(label_depth_gt_kernel, dim3(nblk((long long)p.oh * p.ow)), dim3(256), 0, st, p, nb);
+}
+
 }  // namespace vp

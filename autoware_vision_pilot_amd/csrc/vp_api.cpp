@@ -2126,6 +2126,40 @@ int vp_metric_rows_ap(const uint32_t* tp, const float* conf, int n_lines, const 
   }
 }
 
+// ---- the label part
+static_assert(sizeof(vp_label_frame) == sizeof(vp::LabelRecord) && offsetof(vp_label_frame, freq) == offsetof(vp::LabelRecord, freq) &&
+                  offsetof(vp_label_frame, nonfinite) == offsetof(vp::LabelRecord, nonfinite) && offsetof(vp_label_frame, min) == offsetof(vp::LabelRecord, mn) &&
+                  offsetof(vp_label_frame, max) == offsetof(vp::LabelRecord, mx) && VP_LABEL_F32 == vp::kLabelF32 && VP_LABEL_F64 == vp::kLabelF64,
+              "vp_label_frame is the record the kernels write");
+
+int vp_metric_add_seg_label(vp_metric* m, vp_engine* e, const uint8_t* label, int channels, int h, int w, int stride_bytes, const int* crop_ltrb, const uint8_t* colours,
+                            int n_colours) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_seg_label(metric_engine(e, "vp_metric_add_seg_label"), label, channels, h, w, stride_bytes, crop_ltrb, colours, n_colours); });
+}
+
+int vp_metric_add_depth_label(vp_metric* m, vp_engine* e, const void* label, int dtype, int h, int w, int stride_elems) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_depth_label(metric_engine(e, "vp_metric_add_depth_label"), label, dtype, h, w, stride_elems); });
+}
+
+int vp_metric_add_seg_logits_label(vp_metric* m, const float* logits_chw, int on_device, int c, int oh, int ow, const uint8_t* label, int channels, int h, int w,
+                                   int stride_bytes, const int* crop_ltrb, const uint8_t* colours, int n_colours) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_seg_logits_label(logits_chw, on_device != 0, c, oh, ow, label, channels, h, w, stride_bytes, crop_ltrb, colours, n_colours); });
+}
+
+int vp_metric_add_depth_plane_label(vp_metric* m, const float* pred, int pred_on_device, int oh, int ow, const void* label, int dtype, int h, int w, int stride_elems) {
+  return metric_guarded(m, [&](vp::Metric& g) { g.add_depth_plane_label(pred, pred_on_device != 0, oh, ow, label, dtype, h, w, stride_elems); });
+}
+
+int vp_metric_label_frames(const vp_metric* m) { return m && m->impl ? m->impl->label_frames() : VP_ERR_ARG; }
+
+int vp_metric_fetch_labels(vp_metric* m, vp_label_frame* records, int cap) {
+  return metric_guarded(m, [&](vp::Metric& g) {
+    if (cap < 0 || (cap > 0 && !records)) throw std::invalid_argument("vp_metric_fetch_labels: cap < 0, or null records with cap > 0");
+    const int n = std::min(cap, g.label_frames());
+    g.fetch_labels(reinterpret_cast<vp::LabelRecord*>(records), n);
+  });
+}
+
 }  // extern "C"
 namespace {
 // (hi, lo) planes of an activation, NHWC with padded channels on the device -> fp16 bit patterns [Creal][H][W] on the host
@@ -2731,6 +2765,72 @@ int vp_op_detect_validate(int gpu_id, const float* raw, int nc, int nb, float co
       g.copy_d2h(rows.data(), d_rows, rows.size() * sizeof(float));
       for (size_t r = 0; r < n; ++r) std::memcpy(rows_out + r * 6, rows.data() + r * vp::kDetValRowWords, 6 * sizeof(float));
     }
+  });
+}
+
+// ---- vp_metric's label kernels alone: host label in, host ground truth and record out
+namespace {
+int* op_label_tab(vp::Engine& g, int src, int dst) {
+  std::vector<int> tab((size_t)dst);
+  vp::label_nearest_tab(src, dst, tab.data());
+  int* d = reinterpret_cast<int*>(g.alloc_f32((size_t)dst));
+  g.copy_h2d(d, tab.data(), tab.size() * sizeof(int));
+  return d;
+}
+void op_label_out_dims(const char* who, const void* gt_out, const void* frame_out, int oh, int ow) {
+  if (!gt_out || !frame_out) throw std::invalid_argument(std::string(who) + ": null output");
+  if (oh < 1 || ow < 1 || (long long)oh * ow > (long long)vp::kMetricMaxN) throw std::invalid_argument(std::string(who) + ": oh * ow outside 1 .. 2^24");
+}
+}  // namespace
+
+int vp_op_label_gt(int gpu_id, const uint8_t* label, int channels, int h, int w, int stride_bytes, const int* crop_ltrb, const uint8_t* colours, int n_colours, int oh, int ow,
+                   uint8_t* gt_out, vp_label_frame* frame_out, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    vp::LabelSegParams q = vp::label_seg_params("vp_op_label_gt", label, channels, h, w, stride_bytes, crop_ltrb, colours, n_colours);
+    op_label_out_dims("vp_op_label_gt", gt_out, frame_out, oh, ow);
+    vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
+    const size_t bytes = (size_t)(h - 1) * stride_bytes + (size_t)w * channels, n_out = (size_t)oh * ow;
+    uint8_t* d_label = reinterpret_cast<uint8_t*>(g.alloc_f32((bytes + 3) / 4));
+    g.copy_h2d(d_label, label, bytes);
+    q.label = d_label;
+    q.ty = op_label_tab(g, q.ch, oh);
+    q.tx = op_label_tab(g, q.cw, ow);
+    q.oh = oh;
+    q.ow = ow;
+    q.gt = reinterpret_cast<uint8_t*>(g.alloc_f32((n_out + 3) / 4));
+    q.part = reinterpret_cast<unsigned*>(g.alloc_f32(4 * (size_t)vp::kMetricBlocks));
+    q.rec = reinterpret_cast<vp::LabelRecord*>(g.alloc_f32(sizeof(vp::LabelRecord) / sizeof(float)));
+    VP_HIP_CHECK(vp::launch_label_seg(q, g.stream()));
+    g.copy_d2h(gt_out, q.gt, n_out);
+    g.copy_d2h(frame_out, q.rec, sizeof(vp::LabelRecord));
+  });
+}
+
+int vp_op_label_depth_gt(int gpu_id, const void* label, int dtype, int h, int w, int stride_elems, int oh, int ow, float* gt_out, vp_label_frame* frame_out, char* err,
+                         size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    vp::label_check_depth("vp_op_label_depth_gt", label, dtype, h, w, stride_elems);
+    op_label_out_dims("vp_op_label_depth_gt", gt_out, frame_out, oh, ow);
+    vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
+    const size_t es = dtype == VP_LABEL_F64 ? sizeof(double) : sizeof(float), bytes = es * ((size_t)(h - 1) * stride_elems + (size_t)w), n_out = (size_t)oh * ow;
+    void* d_label = g.alloc_f32(bytes / sizeof(float));
+    g.copy_h2d(d_label, label, bytes);
+    vp::LabelDepthParams q{};
+    q.label = d_label;
+    q.dtype = dtype;
+    q.h = h;
+    q.w = w;
+    q.stride = stride_elems;
+    q.ty = op_label_tab(g, h, oh);
+    q.tx = op_label_tab(g, w, ow);
+    q.oh = oh;
+    q.ow = ow;
+    q.gt = g.alloc_f32(n_out);
+    q.part = reinterpret_cast<vp::LabelExtPartial*>(g.alloc_f32((size_t)vp::kMetricBlocks * sizeof(vp::LabelExtPartial) / sizeof(float)));
+    q.rec = reinterpret_cast<vp::LabelRecord*>(g.alloc_f32(sizeof(vp::LabelRecord) / sizeof(float)));
+    VP_HIP_CHECK(vp::launch_label_depth(q, g.stream()));
+    g.copy_d2h(gt_out, q.gt, n_out * sizeof(float));
+    g.copy_d2h(frame_out, q.rec, sizeof(vp::LabelRecord));
   });
 }
 

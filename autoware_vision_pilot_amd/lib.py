@@ -224,6 +224,14 @@ _SIGS = {
     "vp_metric_rows_lines": (C.c_int, [_P]),
     "vp_metric_fetch_rows": (C.c_int, [_P, _P, C.c_int, _P]),
     "vp_metric_rows_ap": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P]),
+    "vp_metric_add_seg_label": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int]),
+    "vp_metric_add_depth_label": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vp_metric_add_seg_logits_label": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int]),
+    "vp_metric_add_depth_plane_label": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vp_metric_label_frames": (C.c_int, [_P]),
+    "vp_metric_fetch_labels": (C.c_int, [_P, _P, C.c_int]),
+    "vp_op_label_gt": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_char_p, C.c_size_t]),
+    "vp_op_label_depth_gt": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_char_p, C.c_size_t]),
 }
 # multi-camera exchange (csrc/vp_comm.cpp): part of libvp_hip.so, absent from the CPU-emulated test build
 _COMM_SIGS = {
@@ -355,6 +363,71 @@ class MetricRowsSummary(C.Structure):
     """vp_metric_rows_summary (include/vp_hip.h)"""
     _fields_ = [("lines", C.c_int), ("n_thr", C.c_int), ("precision", C.c_double), ("recall", C.c_double), ("mean_ap", C.c_double), ("ap", C.c_double * VP_ROWS_MAX_THR),
                 ("map50", C.c_double)]
+
+
+VP_LABEL_F32, VP_LABEL_F64 = 0, 1
+LABEL_FRAME_DTYPE = np.dtype([("kind", "<i4"), ("n", "<u4"), ("freq", "<u4", (3,)), ("unmatched", "<u4"), ("outside", "<u4"), ("nonfinite", "<u4"), ("min", "<f8"),
+                              ("max", "<f8")])
+# VP_SCENESEG_COLOURS_INIT (include/vp_hip.h): rows r, g, b, class -- class 0 sky, background objects, road-edge delimiter, unlabelled; class 1 vulnerable
+# living, small / large mobile vehicle, foreground objects; class 2 road
+SCENESEG_COLOURS = np.array([(61, 184, 255, 0), (61, 93, 255, 0), (216, 255, 61, 0), (0, 0, 0, 0), (255, 61, 61, 1), (255, 190, 61, 1), (255, 116, 61, 1), (255, 28, 145, 1),
+                             (0, 255, 220, 2)], dtype=np.uint8)
+SCENESEG_WEIGHT_OFFSET = 5120
+
+
+def sceneseg_roi(dataset, w, h):
+    """the PIL box (l, t, r, b) the SceneSeg loader crops image and label of `dataset` with, for a w x h image; None: no crop (MAPILLARY, anything else)"""
+    fixed = {"ACDC": (0, 0, 1919, 990), "BDD100K": (0, 0, 1000, 500), "IDDAW": (0, 476, 2047, 1500), "MUSES": (0, 0, 1919, 918)}
+    name = str(dataset).upper()
+    if name in fixed:
+        return fixed[name]
+    if name == "COMMA10K":
+        return (0, 0, int(w) - 1, int(int(h) * 0.7))
+    return None
+
+
+def class_weights(record):
+    """the loader's loss weights n / (freq[c] + 5120) of one colour-label record, in Python floats (double)"""
+    return [int(record["n"]) / (int(f) + SCENESEG_WEIGHT_OFFSET) for f in record["freq"]]
+
+
+def _label_u8(label):
+    """(array kept alive, channels, h, w, stride in bytes): uint8 [h][w][3] or [h][w]; rows may be further apart than their bytes"""
+    a = np.asarray(label)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3) or a.size == 0:
+        raise ValueError("label: a uint8 array [h][w][3] (colours) or [h][w] (a mask)")
+    ch = 3 if a.ndim == 3 else 1
+    if a.strides[-1] != 1 or (a.ndim == 3 and a.strides[1] != 3) or a.strides[0] < a.shape[1] * ch:
+        a = np.ascontiguousarray(a)
+    return a, ch, a.shape[0], a.shape[1], a.strides[0]
+
+
+def _label_depth(label):
+    """(array kept alive, dtype code, h, w, stride in elements): float32 or float64 [h][w]"""
+    a = np.asarray(label)
+    if a.dtype not in (np.float32, np.float64) or a.ndim != 2 or a.size == 0:
+        raise ValueError("label: a float32 or float64 array [h][w]")
+    if a.strides[1] != a.itemsize or a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize:
+        a = np.ascontiguousarray(a)
+    return a, (VP_LABEL_F64 if a.dtype == np.float64 else VP_LABEL_F32), a.shape[0], a.shape[1], a.strides[0] // a.itemsize
+
+
+def _label_crop(crop):
+    if crop is None:
+        return None, None
+    box = np.array([int(v) for v in crop], dtype=np.int32)
+    if box.shape != (4,):
+        raise ValueError("crop: (l, t, r, b)")
+    return _ptr(box), box
+
+
+def _label_colours(colours, channels):
+    if channels != 3:
+        return None, None, 0
+    t = np.ascontiguousarray(SCENESEG_COLOURS if colours is None else colours, dtype=np.uint8)
+    if t.ndim != 2 or t.shape[1] != 4:
+        raise ValueError("colours: rows r, g, b, class")
+    return _ptr(t), t, t.shape[0]
 
 
 def _rows_summary_dict(s):
@@ -1473,6 +1546,56 @@ class Metric:
         self._ck(self._lib.vp_metric_fetch_rows(self._h, _ptr(rec) if n else None, n, C.byref(s)))
         return rec, _rows_summary_dict(s)
 
+    def label_frames(self):
+        return self._ck(self._lib.vp_metric_label_frames(self._h))
+
+    def add_seg_label(self, engine, label, crop=None, colours=None):
+        """vp_metric_add_seg_label.  label: the label file's decoded pixels, uint8 [h][w][3] (R, G, B) or [h][w] (a mask), rows possibly strided; crop: a
+        PIL box (l, t, r, b) or None; colours: rows r, g, b, class (None: SCENESEG_COLOURS).  The label is copied before the call returns."""
+        a, ch, h, w, stride = _label_u8(label)
+        cp, keep_c = _label_crop(crop)
+        tp, keep_t, nt = _label_colours(colours, ch)
+        self._ck(self._lib.vp_metric_add_seg_label(self._h, engine._h, _P(a.ctypes.data), ch, h, w, stride, cp, tp, nt))
+
+    def add_depth_label(self, engine, label):
+        """vp_metric_add_depth_label.  label: the depth map as stored, float32 or float64 [h][w]"""
+        a, dt, h, w, stride = _label_depth(label)
+        self._ck(self._lib.vp_metric_add_depth_label(self._h, engine._h, _P(a.ctypes.data), dt, h, w, stride))
+
+    def add_seg_logits_label(self, logits, label, crop=None, colours=None, device_chw=None):
+        """vp_metric_add_seg_logits_label.  logits fp32 [c][oh][ow]: a numpy array, or (with device_chw = (c, oh, ow)) a device pointer (int)"""
+        a, ch, h, w, stride = _label_u8(label)
+        cp, keep_c = _label_crop(crop)
+        tp, keep_t, nt = _label_colours(colours, ch)
+        if device_chw is not None:
+            c, oh, ow = (int(v) for v in device_chw)
+            lp, dev, lg = _P(int(logits)), 1, None
+        else:
+            lg = np.ascontiguousarray(logits, dtype=np.float32)
+            if lg.ndim != 3:
+                raise ValueError("add_seg_logits_label: logits [c][oh][ow]")
+            (c, oh, ow), lp, dev = lg.shape, _ptr(lg), 0
+        self._ck(self._lib.vp_metric_add_seg_logits_label(self._h, lp, dev, c, oh, ow, _P(a.ctypes.data), ch, h, w, stride, cp, tp, nt))
+
+    def add_depth_plane_label(self, pred, label, device_hw=None):
+        """vp_metric_add_depth_plane_label.  pred fp32 [oh][ow]: a numpy array, or (with device_hw = (oh, ow)) a device pointer (int)"""
+        a, dt, h, w, stride = _label_depth(label)
+        if device_hw is not None:
+            (oh, ow), pp, dev, p = (int(v) for v in device_hw), _P(int(pred)), 1, None
+        else:
+            p = np.ascontiguousarray(pred, dtype=np.float32)
+            if p.ndim != 2:
+                raise ValueError("add_depth_plane_label: a plane [oh][ow]")
+            (oh, ow), pp, dev = p.shape, _ptr(p), 0
+        self._ck(self._lib.vp_metric_add_depth_plane_label(self._h, pp, dev, oh, ow, _P(a.ctypes.data), dt, h, w, stride))
+
+    def fetch_labels(self):
+        """the label records in call order: a numpy array of LABEL_FRAME_DTYPE (synchronous)"""
+        n = self.label_frames()
+        rec = np.zeros(n, dtype=LABEL_FRAME_DTYPE)
+        self._ck(self._lib.vp_metric_fetch_labels(self._h, _ptr(rec) if n else None, n))
+        return rec
+
     def fetch(self):
         n = self.frames()
         rec = np.zeros(n, dtype=METRIC_FRAME_DTYPE)
@@ -1493,6 +1616,34 @@ def select_f32(values, k, gpu_id=0):
     if rc != 0:
         raise (ValueError if rc == -1 else VpError)(f"vp_op_select_f32 failed ({rc}): {err.value.decode(errors='replace')}")
     return np.float32(out.value)
+
+
+def label_gt(label, out_hw, crop=None, colours=None, gpu_id=0):
+    """vp_op_label_gt: the label kernels alone -> (ground truth uint8 [oh][ow], record: a LABEL_FRAME_DTYPE scalar).  Arguments as Metric.add_seg_label"""
+    a, ch, h, w, stride = _label_u8(label)
+    cp, keep_c = _label_crop(crop)
+    tp, keep_t, nt = _label_colours(colours, ch)
+    oh, ow = (int(v) for v in out_hw)
+    gt = np.zeros((max(oh, 0), max(ow, 0)), dtype=np.uint8)
+    rec = np.zeros(1, dtype=LABEL_FRAME_DTYPE)
+    err = C.create_string_buffer(512)
+    rc = load().vp_op_label_gt(gpu_id, _P(a.ctypes.data), ch, h, w, stride, cp, tp, nt, oh, ow, _ptr(gt), _ptr(rec), err, len(err))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_op_label_gt failed ({rc}): {err.value.decode(errors='replace')}")
+    return gt, rec[0]
+
+
+def label_depth_gt(label, out_hw, gpu_id=0):
+    """vp_op_label_depth_gt: the depth label kernels alone -> (ground truth float32 [oh][ow], record).  label: float32 or float64 [h][w]"""
+    a, dt, h, w, stride = _label_depth(label)
+    oh, ow = (int(v) for v in out_hw)
+    gt = np.zeros((max(oh, 0), max(ow, 0)), dtype=np.float32)
+    rec = np.zeros(1, dtype=LABEL_FRAME_DTYPE)
+    err = C.create_string_buffer(512)
+    rc = load().vp_op_label_depth_gt(gpu_id, _P(a.ctypes.data), dt, h, w, stride, oh, ow, _ptr(gt), _ptr(rec), err, len(err))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_op_label_depth_gt failed ({rc}): {err.value.decode(errors='replace')}")
+    return gt, rec[0]
 
 
 def detect_validate(raw, conf=DET_CONF, iou=DET_IOU, gpu_id=0):

@@ -912,6 +912,75 @@ int vp_metric_rows_lines(const vp_metric* m);
 int vp_metric_fetch_rows(vp_metric* m, vp_metric_rows_line* records, int cap, vp_metric_rows_summary* summary);
 int vp_metric_rows_ap(const uint32_t* tp, const float* conf, int n_lines, const double* thr, int n_thr, vp_metric_rows_summary* summary);
 
+/* ---- vp_metric: ground truth from the datasets' label files, built on the device ------------------------------------------------------
+ * The entries above take ground truth that already has the network's output geometry.  The reference makes it on the host, per sample: extractROI
+ * crops the label with a PIL box, createGroundTruth walks the crop pixel by pixel in Python against nine colours and counts the class frequencies
+ * (Models/data_utils/load_data_scene_seg.py:55-166), A.Resize(640, 320) shrinks each plane with the nearest rule (augmentations.py:133-177); the depth
+ * loader min-max normalises a full-resolution .npy map, which is then resized (load_data_scene_3d.py:59-66); DomainSeg's label is an L image through
+ * the same resize (load_data_domain_seg.py:57-61).  These entries take the label file's decoded pixels as the dataset stores them and queue all of
+ * that on the metric's stream in front of the score: one vp_metric_frame per call as ever (vp_metric_fetch), and one vp_label_frame per call, in call
+ * order, in storage of its own (vp_metric_fetch_labels; vp_metric_fetch / vp_metric_frame / vp_metric_summary know nothing of it).
+ *     vp_infer(seg, ...);  vp_metric_add_seg_label(m, seg, rgb, 3, h, w, 3 * w, box, &table[0][0], 9);      no host wait
+ * ARITHMETIC.
+ *   Crop box {l, t, r, b} in PIL's sense: cw = r - l, ch = b - t, crop pixel (y, x) is image pixel (t + y, l + x); NULL: the whole image.  The box may
+ *     exceed the image: crop pixels outside it read as (0, 0, 0) / 0, as PIL.Image.crop pads (the reference's (0, 0, 1919, 990) drops the last column;
+ *     (0, 476, 2047, 1500) on a shorter image pads, and black, the "unlabelled" colour, is background).
+ *   Sampling: output pixel (oy, ox) of the oh x ow ground truth takes crop pixel (ty[oy], tx[ox]), t[d] = min(floor(d * (1 / (dst / src))), src - 1) in
+ *     double: OpenCV's resizeNN as vp_mask_resized reads it, from ch -> oh and cw -> ow.  oh x ow is the engine's output size (vp_output_dims).
+ *   Colour labels (channels 3; bytes R, G, B as the file has them): the table is n_colours (1 .. 16) rows {r, g, b, class}, class 0 .. 2; a pixel's
+ *     class is that of the FIRST row it equals exactly, no row: no class.  The ground truth byte is the class, or 255 (VP_GT_LABEL, as vp_metric_add_seg
+ *     reads it).  Classifying after sampling equals the reference's sampling of classified planes: both maps are per pixel.  VP_SCENESEG_COLOURS_INIT is the
+ *     reference's table: class 0 sky, background objects, road-edge delimiter, unlabelled; class 1 the four foreground colours; class 2 road.
+ *     Statistics over the FULL-RESOLUTION crop: freq[c] pixels of class c, unmatched (inside the image, no row), outside (crop pixels outside the image;
+ *     they are ALSO counted in the class of black, if it has one), n = cw * ch.  The reference's loss weights n / (freq[c] + 5120) are host arithmetic.
+ *   Mask labels (channels 1): the ground truth byte is the sampled byte (VP_GT_LABEL with one plane: nonzero is positive); freq[0] is the number of
+ *     nonzero pixels of the crop, freq[1] = freq[2] = unmatched = 0.
+ *   Depth labels (fp32 or fp64 [h][w], stride in ELEMENTS, no crop): mn and mx over the whole plane by numpy's rule -- any NaN makes both NaN;
+ *     g = (v - mn) / (mx - mn) in the label's own type, one subtraction and one division, fp64 then rounded to nearest into fp32; sampled by the same
+ *     tables (h -> oh, w -> ow).  What numpy answers, this answers: a constant plane gives 0 / 0 = NaN everywhere, a NaN anywhere an all-NaN plane,
+ *     infinities follow IEEE; the depth score then reports the frame (nonfinite, nan_frames).  A NaN's sign and payload are not part of the contract.
+ *     Among equal extremes -0.0 is the smaller (numpy leaves a zero extreme's sign to its reduction order).  min, max: as double; nonfinite: NaNs and
+ *     infinities of the input; n = h * w.
+ *   kind: VP_SCENESEG for a colour label, VP_DOMAINSEG for a mask label, VP_SCENE3D for a depth label.
+ *   Stated: the nearest rule is the project's reading of resizeNN, unpinned against albumentations / cv2; createGroundTruth, extractROI and the depth
+ *     normalisation are pinned (tools/pin_label.py).  The reference's apply_augmentations indexes getItemVal's list in a way that does not run as
+ *     written; this follows what it evidently intends: planes background, foreground, road.
+ * vp_metric_add_seg_label / vp_metric_add_depth_label: the engines of vp_metric_add_seg / vp_metric_add_depth under the same ordering contract.  The label
+ *   lies in host memory and is copied before the call returns.
+ * vp_metric_add_seg_logits_label / vp_metric_add_depth_plane_label: the operator forms on a caller's fp32 logits [c][oh][ow] / plane [oh][ow], host or
+ *   (on_device != 0) device, as vp_metric_add_seg_logits / vp_metric_add_depth_plane take them.
+ * vp_metric_label_frames: label records since the last reset (which empties them).  vp_metric_fetch_labels: waits for the metric's stream and copies the
+ *   first min(cap, frames) records.
+ * vp_op_label_gt / vp_op_label_depth_gt: the label kernels alone, host in, host out: gt_out [oh][ow] bytes / floats and *frame_out; no engine, no metric.
+ * Records are bit-identical from run to run: integer partials, one per workgroup, and the extremes folded in a fixed tree.
+ * ERRORS.  VP_ERR_ARG: channels outside {1, 3}; n_colours outside 1 .. 16 or a class above 2 (channels 3); a crop with cw or ch below 1, or a
+ *   coordinate outside -16384 .. 32768; h or w outside 1 .. 16384; a stride below the row; an unknown dtype; a null pointer; the refusals of
+ *   vp_metric_add_seg / _add_depth / _add_seg_logits / _add_depth_plane.  VP_ERR_STATE: as vp_metric_add_seg.  A refused call adds no record.
+ * No call waits for the device beyond the exceptions of vp_metric_add_seg, the first use of a (source, destination) size pair (its table is uploaded
+ *   once and kept; the sixteen most recent pairs stay) and the allocation of the label records by the first call. */
+enum vp_label_dtype { VP_LABEL_F32 = 0, VP_LABEL_F64 = 1 };
+typedef struct vp_label_frame {
+  int kind;
+  uint32_t n, freq[3], unmatched, outside, nonfinite;
+  double min, max;
+} vp_label_frame;
+/* const uint8_t table[9][4] = VP_SCENESEG_COLOURS_INIT; */
+#define VP_SCENESEG_COLOURS_INIT                                                                                                              \
+  {{61, 184, 255, 0}, {61, 93, 255, 0}, {216, 255, 61, 0}, {0, 0, 0, 0}, {255, 61, 61, 1}, {255, 190, 61, 1}, {255, 116, 61, 1}, {255, 28, 145, 1}, \
+   {0, 255, 220, 2}}
+int vp_metric_add_seg_label(vp_metric* m, vp_engine* e, const uint8_t* label, int channels, int h, int w, int stride_bytes, const int* crop_ltrb, const uint8_t* colours,
+                            int n_colours);
+int vp_metric_add_depth_label(vp_metric* m, vp_engine* e, const void* label, int dtype, int h, int w, int stride_elems);
+int vp_metric_add_seg_logits_label(vp_metric* m, const float* logits_chw, int on_device, int c, int oh, int ow, const uint8_t* label, int channels, int h, int w,
+                                   int stride_bytes, const int* crop_ltrb, const uint8_t* colours, int n_colours);
+int vp_metric_add_depth_plane_label(vp_metric* m, const float* pred, int pred_on_device, int oh, int ow, const void* label, int dtype, int h, int w, int stride_elems);
+int vp_metric_label_frames(const vp_metric* m);
+int vp_metric_fetch_labels(vp_metric* m, vp_label_frame* records, int cap);
+int vp_op_label_gt(int gpu_id, const uint8_t* label, int channels, int h, int w, int stride_bytes, const int* crop_ltrb, const uint8_t* colours, int n_colours, int oh, int ow,
+                   uint8_t* gt_out, vp_label_frame* frame_out, char* err, size_t err_len);
+int vp_op_label_depth_gt(int gpu_id, const void* label, int dtype, int h, int w, int stride_elems, int oh, int ow, float* gt_out, vp_label_frame* frame_out, char* err,
+                         size_t err_len);
+
 /* ---- multi-camera result exchange (BASELINE configs[3]) ---------------------------------------
  * One process (or thread) per GPU, camera r on rank r, weights replicated, no data-path collective in the networks.  For the
  * fused ego-path / BEV consumer every rank needs all cameras' results: ONE ncclAllGather (RCCL over xGMI) per frame of a
