@@ -71,6 +71,16 @@ public:
     return result;
   }
 
+  // The pass alone: the frame goes up, one pass is queued behind it, nothing comes back.  For consumers that read the logits on the device
+  // (LaneFilterHip, lane_filter_hip.hpp); false on failure.  getRawTensorData() / getTensorShape() keep answering for the last inference().
+  bool enqueue(const cv::Mat & input_image)
+  {
+    return !input_image.empty() && input_image.type() == CV_8UC3 &&
+           vp_upload_frame(engine_, input_image.data, input_image.rows, input_image.cols, static_cast<int>(input_image.step)) == VP_OK &&
+           vp_enqueue(engine_) == VP_OK;
+  }
+  vp_engine * handle() const { return engine_; }
+
   const float * getRawTensorData() const
   {
     const float * raw = nullptr;

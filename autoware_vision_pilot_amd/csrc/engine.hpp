@@ -391,6 +391,7 @@ class Engine {
   SourceRegion src_region_;
   friend class Canvas;   // reads the last mask / logits on the device and orders its stream against this engine's
   friend class Metric;   // reads the last logits on the device, ordered the same way
+  friend class Lanes;    // the same
   int* d_xtab_ = nullptr;
   int* d_ytab_ = nullptr;
   int tab_h_ = 0, tab_w_ = 0;
@@ -684,6 +685,63 @@ class Metric {
   uint8_t* d_label_scratch_ = nullptr;   // the ground truth at output size, then the partials
   size_t label_scratch_cap_ = 0;
   std::vector<LabelTab> label_tabs_;
+};
+
+// vp_lanes (include/vp_hip.h; handle: vp_handle.hpp; kernel: kernels_detect.hip lane_filter_kernel): the production app's LaneFilter::update behind an
+// EgoLanes pass.  add() queues one lane_filter launch on the filter's own stream, ordered against the engine by events alone (Metric's wait_for /
+// release_to), into the next of `capacity` device records (a ring); fetch() is the one synchronisation: it copies the oldest pending records and, in
+// the order they were added, solves each lane's normal equations from the integer moments (lanes_fit) and applies the temporal smoothing, whose state
+// (the previous fit of either lane) lives here on the host.  The collected points stay in a device side buffer until fetch_points asks for them.
+// Owns its stream and buffers.  One thread drives it.
+struct LanesFit {
+  int order;            // 0: no fit (no start point, fewer than 4 points, or singular), 1: a line, 2: a quadratic
+  int flags;            // kLanesSingular | kLanesSmoothed
+  int coeffs_valid;     // coeffs holds what LaneFilter::update leaves in left_coeffs / right_coeffs
+  double raw[6];        // this frame's own fit: 0, a, b, c, min_y, max_y of x = a y^2 + b y + c
+  double coeffs[6];     // the fit blended with the previous frame's
+};
+constexpr int kLanesSingular = 1, kLanesSmoothed = 2;
+// the least-squares polynomial of `order` (1 or 2) from the moments S_k = sum y^k, T_k = sum x y^k: out = {a, b, c} (a = 0 for a line).  Cramer's rule
+// with the determinants exact in 128-bit integers and each coefficient ONE correctly rounded quotient.  Returns false (out untouched) when the system is
+// singular.  Every |S_k|, |T_k| must be below 2^40 (std::invalid_argument): the production moments stay below 2^37.
+bool lanes_fit(const long long S[5], const long long T[3], int order, double out[3]);
+
+class Lanes {
+ public:
+  Lanes(int gpu, int capacity);
+  ~Lanes();
+  Lanes(const Lanes&) = delete;
+  Lanes& operator=(const Lanes&) = delete;
+  void set_smoothing(float s) { smoothing_ = s; }
+  void reset();                                        // forgets both previous fits; refused while records are pending
+  void add(Engine& e, float threshold);                // a VP_EGOLANES engine (a shared-prefix head included) with a pass behind it
+  void add_logits(const float* host, float threshold); // fp32 [3][80][160] in host memory, copied before the call returns
+  int pending() const { return count_; }
+  int capacity() const { return capacity_; }
+  int gpu() const { return gpu_; }
+  // the oldest `count` (<= pending) records, then their fits [count][2] in order; they stop being pending
+  void fetch(LaneFilterRecord* recs, LanesFit* fits, int count);
+  // the point list of one lane of pending record `index` (oldest first), the upward run's then the downward run's: xy [n][2] bytes; returns n
+  int fetch_points(int index, int lane, uint8_t* xy, int max_points);
+
+ private:
+  void release();
+  LaneFilterRecord* next_record(const char* who);
+  void launch(const float* d_logits, float threshold);
+  int gpu_, capacity_, head_ = 0, count_ = 0;
+  float smoothing_ = 0.5f;
+  hipStream_t stream_ = nullptr;
+  hipEvent_t ev_src_ = nullptr, ev_read_ = nullptr, stage_ev_[2] = {nullptr, nullptr};
+  LaneFilterRecord* d_records_ = nullptr;
+  LaneFilterRecord* h_records_ = nullptr;   // pinned [capacity]: where fetch lands the records
+  uint16_t* d_points_ = nullptr;     // [capacity][2 lanes][2 runs][kLaneRunPoints]
+  float* d_stage_ = nullptr;         // add_logits: the caller's planes on the device ...
+  float* h_stage_ = nullptr;         // ... staged through two pinned slots
+  int stage_slot_ = 0;
+  struct Prev {
+    bool valid = false;
+    double c[6] = {};
+  } prev_[2];
 };
 
 // the arguments of a colour / mask label checked and laid into the kernel's parameters (std::invalid_argument names `who`); label, tables, outputs unset

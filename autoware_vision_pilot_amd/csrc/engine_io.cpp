@@ -2207,4 +2207,220 @@ std::vector<Engine::RangeStats> Engine::range_survey() {
   return out;
 }
 
+// -------------------------------------------------------------------------------------------------- vp_lanes
+namespace {
+using i128 = __int128;
+using u128 = unsigned __int128;
+
+// num / den (den != 0) rounded once to the nearest double, ties to even: the quotient's bits are produced by long division until 64 are significant,
+// the rest is a sticky bit
+double quotient_rn(i128 num, i128 den) {
+  if (num == 0) return 0.0;
+  const bool neg = (num < 0) != (den < 0);
+  const u128 n = num < 0 ? (u128)0 - (u128)num : (u128)num, d = den < 0 ? (u128)0 - (u128)den : (u128)den;   // d < 2^127: the remainder may be doubled
+  u128 q = n / d, r = n % d;
+  int e = 0;
+  bool sticky = false;
+  const u128 top = (u128)1 << 63;
+  while (q < top) {
+    q <<= 1;
+    r <<= 1;
+    if (r >= d) r -= d, q |= 1;
+    --e;
+  }
+  while (q >= (top << 1)) {
+    sticky = sticky || (q & 1);
+    q >>= 1;
+    ++e;
+  }
+  sticky = sticky || r != 0;
+  const uint64_t q64 = (uint64_t)q, low = q64 & 0x7FFu;
+  uint64_t m = q64 >> 11;   // 53 bits
+  if (low > 0x400u || (low == 0x400u && (sticky || (m & 1)))) ++m;
+  const double v = std::ldexp((double)m, e + 11);
+  return neg ? -v : v;
+}
+}  // namespace
+
+bool lanes_fit(const long long S[5], const long long T[3], int order, double out[3]) {
+  if (!S || !T || !out) throw std::invalid_argument("vp_lanes_fit: null moments or null result");
+  if (order != 1 && order != 2) throw std::invalid_argument("vp_lanes_fit: order " + std::to_string(order) + " (1: a line, 2: a quadratic)");
+  const long long lim = 1ll << 40;
+  for (int k = 0; k < 5; ++k)
+    if (S[k] <= -lim || S[k] >= lim || (k < 3 && (T[k] <= -lim || T[k] >= lim))) throw std::invalid_argument("vp_lanes_fit: a moment of 2^40 or more");
+  const i128 s0 = S[0], s1 = S[1], s2 = S[2], s3 = S[3], s4 = S[4], t0 = T[0], t1 = T[1], t2 = T[2];
+  if (order == 1) {   // [s2 s1; s1 s0] (b, c) = (t1, t0)
+    const i128 det = s2 * s0 - s1 * s1;
+    if (det == 0) return false;
+    out[0] = 0.0;
+    out[1] = quotient_rn(t1 * s0 - t0 * s1, det);
+    out[2] = quotient_rn(s2 * t0 - s1 * t1, det);
+    return true;
+  }
+  // [s4 s3 s2; s3 s2 s1; s2 s1 s0] (a, b, c) = (t2, t1, t0): the cofactors of the symmetric matrix
+  const i128 c00 = s2 * s0 - s1 * s1, c01 = s2 * s1 - s3 * s0, c02 = s3 * s1 - s2 * s2, c11 = s4 * s0 - s2 * s2, c12 = s3 * s2 - s4 * s1, c22 = s4 * s2 - s3 * s3;
+  const i128 det = s4 * c00 + s3 * c01 + s2 * c02;
+  if (det == 0) return false;
+  out[0] = quotient_rn(c00 * t2 + c01 * t1 + c02 * t0, det);
+  out[1] = quotient_rn(c01 * t2 + c11 * t1 + c12 * t0, det);
+  out[2] = quotient_rn(c02 * t2 + c12 * t1 + c22 * t0, det);
+  return true;
+}
+
+Lanes::Lanes(int gpu, int capacity) : gpu_(gpu), capacity_(capacity) {
+  if (capacity < 1 || capacity > 4096) throw std::invalid_argument("vp_lanes_create: capacity " + std::to_string(capacity) + " (1 .. 4096)");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  try {
+    VP_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    for (hipEvent_t* ev : {&ev_src_, &ev_read_, &stage_ev_[0], &stage_ev_[1]}) VP_HIP_CHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_records_), (size_t)capacity * sizeof(LaneFilterRecord)));
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_points_), (size_t)capacity * 4 * kLaneRunPoints * sizeof(uint16_t)));
+    VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_records_), (size_t)capacity * sizeof(LaneFilterRecord), hipHostMallocDefault));
+  } catch (...) {
+    release();
+    throw;
+  }
+}
+
+Lanes::~Lanes() { release(); }
+
+void Lanes::release() {
+  (void)hipSetDevice(gpu_);
+  if (stream_) (void)hipStreamSynchronize(stream_);
+  for (hipEvent_t* ev : {&ev_src_, &ev_read_, &stage_ev_[0], &stage_ev_[1]}) {
+    if (*ev) (void)hipEventDestroy(*ev);
+    *ev = nullptr;
+  }
+  if (d_records_) (void)hipFree(d_records_);
+  if (d_points_) (void)hipFree(d_points_);
+  if (h_records_) (void)hipHostFree(h_records_);
+  h_records_ = nullptr;
+  if (d_stage_) (void)hipFree(d_stage_);
+  if (h_stage_) (void)hipHostFree(h_stage_);
+  d_records_ = nullptr;
+  d_points_ = nullptr;
+  d_stage_ = h_stage_ = nullptr;
+  if (stream_) (void)hipStreamDestroy(stream_);
+  stream_ = nullptr;
+}
+
+void Lanes::reset() {
+  if (count_) throw std::runtime_error("vp_lanes_reset: " + std::to_string(count_) + " records are pending (vp_lanes_fetch first: the smoothing is applied as they are fetched)");
+  prev_[0].valid = prev_[1].valid = false;
+}
+
+LaneFilterRecord* Lanes::next_record(const char* who) {
+  if (count_ >= capacity_) throw std::runtime_error(std::string(who) + ": " + std::to_string(capacity_) + " records are pending already (vp_lanes_fetch)");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  return d_records_ + (head_ + count_) % capacity_;
+}
+
+void Lanes::launch(const float* d_logits, float threshold) {
+  const int slot = (head_ + count_) % capacity_;
+  LaneFilterParams q{};
+  q.logits = d_logits;
+  q.threshold = threshold;
+  q.rec = d_records_ + slot;
+  q.points = d_points_ + (size_t)slot * 4 * kLaneRunPoints;
+  VP_HIP_CHECK(launch_lane_filter(q, stream_));
+}
+
+void Lanes::add(Engine& e, float threshold) {
+  const std::string me("vp_lanes_add");
+  if (e.gpu_ != gpu_) throw std::invalid_argument(me + ": the engine lives on GPU " + std::to_string(e.gpu_) + ", the lane filter on GPU " + std::to_string(gpu_));
+  if (e.kind_ != 3) throw std::invalid_argument(me + ": VP_EGOLANES engines only (the three lane planes of its logits)");
+  if (e.frames_ > 1) throw std::invalid_argument(me + ": a batched encoder has no outputs of its own (filter its per-camera heads)");
+  if (!e.have_outputs_) throw std::runtime_error("Inference has not been run yet");
+  if (!e.d_logits_ || e.out_c_ != 3 || e.out_h_ != kLaneH || e.out_w_ != kLaneW) throw std::invalid_argument(me + ": the engine has no logits of 3 x 80 x 160");
+  next_record("vp_lanes_add");
+  VP_HIP_CHECK(hipEventRecord(ev_src_, e.stream_));
+  VP_HIP_CHECK(hipStreamWaitEvent(stream_, ev_src_, 0));
+  launch(e.d_logits_, threshold);
+  VP_HIP_CHECK(hipEventRecord(ev_read_, stream_));
+  VP_HIP_CHECK(hipStreamWaitEvent(e.stream_, ev_read_, 0));
+  ++count_;
+}
+
+// Metric::stage_host's scheme: the copy into a pinned slot happens before the call returns, the H2D and the kernel follow on the stream
+void Lanes::add_logits(const float* host, float threshold) {
+  if (!host) throw std::invalid_argument("vp_lanes_add_logits: null logits");
+  next_record("vp_lanes_add_logits");
+  const size_t bytes = 3 * sizeof(float) * kLaneH * kLaneW;
+  if (!d_stage_) VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_stage_), bytes));
+  if (!h_stage_) VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_stage_), 2 * bytes, hipHostMallocDefault));
+  stage_slot_ ^= 1;
+  float* slot = h_stage_ + (size_t)stage_slot_ * 3 * kLaneH * kLaneW;
+  VP_HIP_CHECK(hipEventSynchronize(stage_ev_[stage_slot_]));   // the H2D that last read this slot, two calls ago
+  std::memcpy(slot, host, bytes);
+  VP_HIP_CHECK(hipMemcpyAsync(d_stage_, slot, bytes, hipMemcpyHostToDevice, stream_));
+  VP_HIP_CHECK(hipEventRecord(stage_ev_[stage_slot_], stream_));
+  launch(d_stage_, threshold);
+  ++count_;
+}
+
+void Lanes::fetch(LaneFilterRecord* recs, LanesFit* fits, int count) {
+  if (count < 0 || count > count_ || (count > 0 && (!recs || !fits))) throw std::invalid_argument("vp_lanes_fetch: more records than are pending, or a null buffer");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  const int first = std::min(count, capacity_ - head_);   // the ring wraps at most once
+  if (first > 0) VP_HIP_CHECK(hipMemcpyAsync(h_records_, d_records_ + head_, (size_t)first * sizeof(LaneFilterRecord), hipMemcpyDeviceToHost, stream_));
+  if (count > first) VP_HIP_CHECK(hipMemcpyAsync(h_records_ + first, d_records_, (size_t)(count - first) * sizeof(LaneFilterRecord), hipMemcpyDeviceToHost, stream_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  if (count) std::memcpy(recs, h_records_, (size_t)count * sizeof(LaneFilterRecord));
+  head_ = (head_ + count) % capacity_;
+  count_ -= count;
+  for (int i = 0; i < count; ++i) {
+    for (int l = 0; l < 2; ++l) {
+      const LaneFilterLane& r = recs[i].lane[l];
+      LanesFit& f = fits[2 * i + l];
+      f = LanesFit{};
+      if (r.start_x < 0) {   // no start point: the lane is lost and so is its history
+        prev_[l].valid = false;
+        continue;
+      }
+      const int n = r.n_points[0] + r.n_points[1];
+      if (n < 4) continue;   // a start point but no fit: the previous fit stays as it is
+      const int order = n < 30 ? 1 : 2;
+      double abc[3];
+      if (!lanes_fit(r.S, r.T, order, abc)) {
+        f.flags |= kLanesSingular;
+        continue;
+      }
+      f.order = order;
+      f.raw[0] = 0.0, f.raw[1] = abc[0], f.raw[2] = abc[1], f.raw[3] = abc[2], f.raw[4] = (double)r.min_y, f.raw[5] = (double)r.max_y;
+      for (int k = 0; k < 6; ++k) f.coeffs[k] = f.raw[k];
+      if (prev_[l].valid) {
+#pragma clang fp contract(off)
+        const double s = (double)smoothing_, t = (double)(1.0f - smoothing_);   // the reference's float factors, products and sum in double
+        for (int k = 0; k < 6; ++k) {
+          const double a = s * f.raw[k], b = t * prev_[l].c[k];
+          f.coeffs[k] = a + b;
+        }
+        f.flags |= kLanesSmoothed;
+      }
+      prev_[l].valid = true;
+      for (int k = 0; k < 6; ++k) prev_[l].c[k] = f.coeffs[k];
+      f.coeffs_valid = 1;
+    }
+  }
+}
+
+int Lanes::fetch_points(int index, int lane, uint8_t* xy, int max_points) {
+  if (count_ < 1) throw std::runtime_error("vp_lanes_fetch_points: no record is pending (the points of a record last until vp_lanes_fetch returns it)");
+  if (index < 0 || index >= count_ || (lane != 0 && lane != 1) || max_points < 0 || (max_points > 0 && !xy))
+    throw std::invalid_argument("vp_lanes_fetch_points: record_index outside the pending records, lane not 0 or 1, or a null buffer");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  const int slot = (head_ + index) % capacity_;
+  int np[2];
+  VP_HIP_CHECK(hipMemcpyAsync(np, reinterpret_cast<const uint8_t*>(d_records_ + slot) + offsetof(LaneFilterRecord, lane) + (size_t)lane * sizeof(LaneFilterLane) + offsetof(LaneFilterLane, n_points),
+                              sizeof(np), hipMemcpyDeviceToHost, stream_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  if (np[0] < 0 || np[0] > kLaneRunPoints || np[1] < 0 || np[1] > kLaneRunPoints) throw std::runtime_error("vp_lanes_fetch_points: a point count outside 0 .. 960 in the record");
+  const int total = np[0] + np[1], n = std::min(total, max_points), up = std::min(np[0], n);
+  const uint16_t* base = d_points_ + ((size_t)slot * 4 + (size_t)lane * 2) * kLaneRunPoints;   // x | y << 8, little endian: the byte pairs (x, y)
+  if (up > 0) VP_HIP_CHECK(hipMemcpyAsync(xy, base, (size_t)up * 2, hipMemcpyDeviceToHost, stream_));
+  if (n > up) VP_HIP_CHECK(hipMemcpyAsync(xy + (size_t)up * 2, base + kLaneRunPoints, (size_t)(n - up) * 2, hipMemcpyDeviceToHost, stream_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  return total;
+}
+
 }  // namespace vp

@@ -930,4 +930,27 @@ struct DetMatchParams {
 };
 hipError_t launch_det_val_match(const DetMatchParams& p, hipStream_t st);
 
+// ---- vp_lanes (include/vp_hip.h; kernels_detect.hip lane_filter_kernel): the production lane filter behind an EgoLanes pass -- start points, the four
+// sliding-window runs (lane x direction) and the integer moments of the collected points, one record per frame.  Geometry 80 x 160 only.
+constexpr int kLaneH = 80, kLaneW = 160, kLaneRowWords = kLaneW / 32, kLaneMaxSteps = 20, kLaneRunPoints = kLaneMaxSteps * 48;
+struct LaneFilterLane {
+  int start_x, start_y;        // (-1, -1): no start point, everything below is empty
+  int n_windows[2];            // [0] the upward run, [1] the downward run
+  int n_points[2];
+  int min_y, max_y;            // over the collected points; (kLaneH, -1) when there are none
+  long long S[5];              // sum y^k, k = 0 .. 4
+  long long T[3];              // sum x y^k, k = 0 .. 2
+  short win[2][kLaneMaxSteps][4];   // per run: x, y, w, h of every window, in order
+};
+struct LaneFilterRecord {
+  LaneFilterLane lane[2];      // ego left, ego right
+};
+struct LaneFilterParams {
+  const float* logits;         // fp32 [3][80][160]: ego left, ego right, other lanes; 16-byte aligned
+  float threshold;             // a pixel is set iff logit > threshold
+  LaneFilterRecord* rec;       // out [1]
+  uint16_t* points;            // out [2 lanes][2 runs][kLaneRunPoints]: x | y << 8, the first n_points[run] of each run in collection order
+};
+hipError_t launch_lane_filter(const LaneFilterParams& p, hipStream_t st);
+
 }  // namespace vp

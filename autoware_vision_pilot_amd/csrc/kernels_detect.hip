@@ -408,6 +408,190 @@ hipError_t launch_lane_rows_head(const LaneRowsHeadParams& p, hipStream_t st) {
   VP_LAUNCH(lane_rows_head_kernel, dim3(p.features.H), dim3(256), 0, st, p);
 }
 
+// ------------------------------------------------------------------------------------------------ production lane filter (vp_lanes)
+// LaneFilter::update's pixel work (VisionPilot/production_release/src/lane_filtering/lane_filter.cpp findStartingPoints :325-369,
+// slidingWindowSearch :375-594) on an EgoLanes engine's fp32 logits [3][80][160], one workgroup of four waves per frame:
+//   1. the three planes become bit rows in LDS (bit x of row y of plane c: logit > threshold, so a NaN is clear) by LDS atomicOr;
+//   2. start points: a thread per row of the lower half finds its row's candidate (left: the highest set x <= 79 of plane 0; right: the lowest set
+//      x >= 80 of plane 1), and the bottom-most row that has one wins;
+//   3. wave w runs the search of lane w >> 1 in direction w & 1 (0 up, 1 down).  The run's state is wave-uniform: every thread extracts the window's
+//      <= 4 rows of <= 12 bits from LDS and derives the counts, the coordinate sums, the float centroid / direction and the next position itself, so no
+//      value crosses lanes.  Only the append is spread out: thread p < w * h owns window pixel p (row-major) and stores it at the rank popcount of the
+//      set pixels before it gives -- the reference's collection order.
+//   4. the moments S_k = sum y^k, T_k = sum x y^k and min / max y are accumulated per run in 64-bit integers and added per lane through LDS.
+// The float steps are the host's: IEEE division and square root, dx * dx + dy * dy unfused, roundf for the centroid, truncation for the blind advance.
+// A run's y only moves away from its start (the centroid lies inside the window, the direction keeps its sign), so every window lies inside the plane;
+// the row range is clamped all the same before LDS is read.
+__device__ __forceinline__ unsigned lane_bits_field(const unsigned* row, const int x0, const int ww) {   // bits [x0, x0 + ww) of a bit row, 1 <= ww <= 12
+  const int w0 = x0 >> 5, sh = x0 & 31;
+  unsigned v = row[w0] >> sh;
+  if (sh + ww > 32) v |= row[w0 + 1] << (32 - sh);   // x0 + ww <= 160: word w0 + 1 exists
+  return v & ((1u << ww) - 1u);
+}
+__device__ __forceinline__ int lane_bits_possum(const unsigned v) {   // the sum of the positions of the set bits of a 12-bit field
+  return __builtin_popcount(v & 0xAAAu) + 2 * __builtin_popcount(v & 0xCCCu) + 4 * __builtin_popcount(v & 0x0F0u) + 8 * __builtin_popcount(v & 0xF00u);
+}
+
+__global__ __launch_bounds__(256) void lane_filter_kernel(const LaneFilterParams p) {
+  __shared__ unsigned bits[3 * kLaneH * kLaneRowWords];
+  __shared__ int cand[2][kLaneH / 2];
+  __shared__ long long s_mom[4][8];
+  __shared__ int s_cnt[4][4];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < 3 * kLaneH * kLaneRowWords; i += 256) bits[i] = 0u;
+  __syncthreads();
+  // 1. threshold: pixel i of the [3][80][160] tensor is bit i & 31 of word i >> 5 (160 = 5 * 32).  Eight 16-byte loads a thread are in flight at a time
+  constexpr int kVec = 3 * kLaneH * kLaneW / 4;
+  const float t = p.threshold;
+  for (int q0 = tid; q0 < kVec; q0 += 256 * 8) {
+    int4 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (q0 + 256 * j < kVec) v[j] = reinterpret_cast<const int4*>(p.logits)[q0 + 256 * j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int q = q0 + 256 * j;
+      if (q < kVec) {
+        const unsigned m = (__uint_as_float((unsigned)v[j].x) > t ? 1u : 0u) | (__uint_as_float((unsigned)v[j].y) > t ? 2u : 0u) |
+                           (__uint_as_float((unsigned)v[j].z) > t ? 4u : 0u) | (__uint_as_float((unsigned)v[j].w) > t ? 8u : 0u);
+        if (m) atomicOr(&bits[q >> 3], m << ((q & 7) * 4));
+      }
+    }
+  }
+  __syncthreads();
+  // 2. start candidates: thread t of wave 0 / wave 1 takes row 79 - t of the left / right lane
+  if ((tid & 63) < kLaneH / 2 && tid < 128) {
+    const int side = tid >> 6, y = kLaneH - 1 - (tid & 63);
+    const unsigned* row = bits + (side * kLaneH + y) * kLaneRowWords;
+    int x = -1;
+    if (side == 0) {
+      const unsigned w2 = row[2] & 0xFFFFu;   // x 64 .. 79
+      if (w2) x = 64 + 31 - __builtin_clz(w2);
+      else if (row[1]) x = 32 + 31 - __builtin_clz(row[1]);
+      else if (row[0]) x = 31 - __builtin_clz(row[0]);
+    } else {
+      const unsigned w2 = row[2] & 0xFFFF0000u;   // x 80 .. 95
+      if (w2) x = 64 + __builtin_ctz(w2);
+      else if (row[3]) x = 96 + __builtin_ctz(row[3]);
+      else if (row[4]) x = 128 + __builtin_ctz(row[4]);
+    }
+    cand[side][tid & 63] = x;
+  }
+  __syncthreads();
+  // 3. the run of this wave
+  const int wave = tid >> 6, ln = tid & 63, side = wave >> 1, down = wave & 1;
+  int sx = -1, sy = -1;
+  for (int r = 0; r < kLaneH / 2; ++r) {
+    if (cand[side][r] >= 0) {
+      sx = cand[side][r];
+      sy = kLaneH - 1 - r;
+      break;
+    }
+  }
+  sx = __builtin_amdgcn_readfirstlane(sx);   // wave-uniform by construction: say so, and the run's integer state lives in scalar registers
+  sy = __builtin_amdgcn_readfirstlane(sy);
+  LaneFilterLane* out = &p.rec->lane[side];
+  uint16_t* pts = p.points + (size_t)(side * 2 + down) * kLaneRunPoints;
+  const unsigned* ego = bits + side * kLaneH * kLaneRowWords;
+  const unsigned* other = bits + 2 * kLaneH * kLaneRowWords;
+  int nwin = 0, npts = 0, miny = kLaneH, maxy = -1;
+  long long S0 = 0, S1 = 0, S2 = 0, S3 = 0, S4 = 0, T0 = 0, T1 = 0, T2 = 0;
+  if (sx >= 0) {
+    int x = sx, y = sy + (down ? 4 : 0), empty = 0;
+    float dirx = 0.0f, diry = down ? 1.0f : -1.0f;
+    for (int step = 0; step < kLaneMaxSteps; ++step) {
+      if (x < 0 || x >= kLaneW) break;
+      if (down ? y >= kLaneH : y < 0) break;
+      const int hw = y < 40 ? 1 : 6;
+      const int ylo = down ? y : max(0, y - 4), yhi = down ? min(kLaneH, y + 4) : y;
+      const int xlo = max(0, x - hw), xhi = min(kLaneW, x + hw), ww = xhi - xlo;
+      if (ln == 0) {
+        short* w = out->win[down][nwin];
+        w[0] = (short)xlo, w[1] = (short)ylo, w[2] = (short)ww, w[3] = (short)(yhi - ylo);
+      }
+      ++nwin;
+      const bool strict = y < 40;   // above the lower half the other-lane plane is not looked at
+      const int r0 = max(ylo, 0), r1 = min(yhi, kLaneH);
+      unsigned re[4] = {0u, 0u, 0u, 0u}, ro[4] = {0u, 0u, 0u, 0u};
+      int ce = 0, co = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (r0 + r < r1) {
+          re[r] = __builtin_amdgcn_readfirstlane(lane_bits_field(ego + (r0 + r) * kLaneRowWords, xlo, ww));
+          if (!strict) ro[r] = __builtin_amdgcn_readfirstlane(lane_bits_field(other + (r0 + r) * kLaneRowWords, xlo, ww));
+          ce += __builtin_popcount(re[r]);
+          co += __builtin_popcount(ro[r]);
+        }
+      }
+      const bool take_ego = ce >= 3, found = take_ego || co >= 3;
+      if (found) {
+        const int cnt = take_ego ? ce : co;
+        unsigned long long m = 0ull;
+        unsigned a0 = 0u, a1 = 0u, a2 = 0u, a3 = 0u, a4 = 0u, b0 = 0u, b1 = 0u, b2 = 0u;   // this window's share of the moments: 48 * 79^4 < 2^32
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const unsigned f = take_ego ? re[r] : ro[r];
+          const unsigned c = (unsigned)__builtin_popcount(f), yy = (unsigned)(r0 + r), y2 = yy * yy;
+          const unsigned xs = c * (unsigned)xlo + (unsigned)lane_bits_possum(f);
+          m |= (unsigned long long)f << (r * ww);
+          a0 += c, a1 += c * yy, a2 += c * y2, a3 += c * y2 * yy, a4 += c * y2 * y2;
+          b0 += xs, b1 += xs * yy, b2 += xs * y2;
+          if (c) miny = min(miny, (int)yy), maxy = max(maxy, (int)yy);
+        }
+        const int sumx = (int)b0, sumy = (int)a1;
+        S0 += a0, S1 += a1, S2 += a2, S3 += a3, S4 += a4, T0 += b0, T1 += b1, T2 += b2;
+        if (ln < 4 * ww && ((m >> ln) & 1ull)) {
+          const int row = (ln >= ww) + (ln >= 2 * ww) + (ln >= 3 * ww), col = ln - row * ww;   // pixel ln of the window, row-major
+          const int rank = __builtin_popcountll(m & ((1ull << ln) - 1ull)), at = npts + rank;
+          if (at < kLaneRunPoints) pts[at] = (uint16_t)((xlo + col) | ((r0 + row) << 8));
+        }
+        npts += cnt;
+        empty = 0;
+        const float cx = __fdiv_rn((float)sumx, (float)cnt), cy = __fdiv_rn((float)sumy, (float)cnt);
+        const float dx = __fsub_rn(cx, (float)x), dy = __fsub_rn(cy, (float)y);
+        const float len = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+        if (len > 0.1f) {
+          dirx = __fdiv_rn(dx, len);
+          diry = __fdiv_rn(dy, len);
+        }
+        x = __builtin_amdgcn_readfirstlane((int)roundf(cx));
+        y = __builtin_amdgcn_readfirstlane((int)roundf(cy));
+      } else {
+        if (!down && y < kLaneH / 4) break;   // the horizon
+        if (++empty >= 12) break;
+        x += __builtin_amdgcn_readfirstlane((int)__fmul_rn(dirx, 4.0f));      // the blind advance truncates
+        y += __builtin_amdgcn_readfirstlane((int)__fmul_rn(diry, 4.0f));
+      }
+      if (!down && y >= yhi - 1) y -= 4;      // the two forced moves: every step leaves its window
+      if (down && y <= ylo + 1) y += 4;
+    }
+  }
+  // 4. per lane: both runs' counts and moments
+  if (ln == 0) {
+    s_mom[wave][0] = S0, s_mom[wave][1] = S1, s_mom[wave][2] = S2, s_mom[wave][3] = S3, s_mom[wave][4] = S4;
+    s_mom[wave][5] = T0, s_mom[wave][6] = T1, s_mom[wave][7] = T2;
+    s_cnt[wave][0] = nwin, s_cnt[wave][1] = npts, s_cnt[wave][2] = miny, s_cnt[wave][3] = maxy;
+  }
+  __syncthreads();
+  if (down == 0 && ln < 8) {
+    const long long v = s_mom[wave][ln] + s_mom[wave + 1][ln];
+    if (ln < 5) out->S[ln] = v;
+    else out->T[ln - 5] = v;
+    if (ln == 0) {
+      out->start_x = sx, out->start_y = sy;
+      out->n_windows[0] = s_cnt[wave][0], out->n_windows[1] = s_cnt[wave + 1][0];
+      out->n_points[0] = s_cnt[wave][1], out->n_points[1] = s_cnt[wave + 1][1];
+      out->min_y = min(s_cnt[wave][2], s_cnt[wave + 1][2]);
+      out->max_y = max(s_cnt[wave][3], s_cnt[wave + 1][3]);
+    }
+  }
+}
+
+hipError_t launch_lane_filter(const LaneFilterParams& p, hipStream_t st) {
+  if (!p.logits || !p.rec || !p.points || (reinterpret_cast<uintptr_t>(p.logits) & 15)) return hipErrorInvalidValue;
+  VP_LAUNCH(lane_filter_kernel, dim3(1), dim3(256), 0, st, p);
+}
+
 // ------------------------------------------------------------------------------------------------ validation NMS + matching (vp_metric_add_det*)
 // The trainer's validation post-process (Models/training/auto_speed_util.py non_max_suppression :123-169, compute_metric :99-120), as include/vp_hip.h
 // defines it; the chain and its buffers: kernels.hpp DetValParams.  Every fp32 operation is one __f*_rn in the order of the definition.

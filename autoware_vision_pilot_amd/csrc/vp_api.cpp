@@ -2161,6 +2161,130 @@ int vp_metric_fetch_labels(vp_metric* m, vp_label_frame* records, int cap) {
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------- vp_lanes
+namespace {
+
+static_assert(VP_LANES_MAX_WINDOWS == 2 * vp::kLaneMaxSteps && VP_LANES_MAX_POINTS == 2 * vp::kLaneRunPoints && VP_LANES_SINGULAR == vp::kLanesSingular &&
+                  VP_LANES_SMOOTHED == vp::kLanesSmoothed && sizeof(long long) == sizeof(int64_t),
+              "vp_lanes_result holds what the kernel's record and the host fit hold");
+
+template <class F>
+int lanes_guarded(vp_lanes* l, F&& fn) {
+  if (!l || !l->impl) return VP_ERR_ARG;
+  try {
+    fn(*l->impl);
+    return VP_OK;
+  } catch (const std::invalid_argument& ex) {
+    l->err = ex.what();
+    return VP_ERR_ARG;
+  } catch (const std::exception& ex) {
+    l->err = ex.what();
+    return std::strncmp(ex.what(), "HIP error", 9) == 0 ? VP_ERR_HIP : VP_ERR_STATE;
+  }
+}
+
+void lanes_result_lane(const vp::LaneFilterLane& r, const vp::LanesFit& f, vp_lanes_lane* o) {
+  std::memset(o, 0, sizeof(*o));
+  o->start_x = r.start_x, o->start_y = r.start_y;
+  o->n_windows_up = r.n_windows[0], o->n_windows_down = r.n_windows[1];
+  o->n_points_up = r.n_points[0], o->n_points_down = r.n_points[1];
+  o->min_y = r.min_y, o->max_y = r.max_y;
+  for (int k = 0; k < 5; ++k) o->S[k] = r.S[k];
+  for (int k = 0; k < 3; ++k) o->T[k] = r.T[k];
+  int at = 0;
+  for (int run = 0; run < 2; ++run)
+    for (int i = 0; i < r.n_windows[run] && i < vp::kLaneMaxSteps; ++i, ++at)
+      for (int k = 0; k < 4; ++k) o->windows[at][k] = r.win[run][i][k];
+  o->order = f.order, o->flags = f.flags, o->coeffs_valid = f.coeffs_valid;
+  for (int k = 0; k < 6; ++k) o->raw_coeffs[k] = f.raw[k], o->coeffs[k] = f.coeffs[k];
+}
+
+}  // namespace
+
+extern "C" {
+
+int vp_lanes_create(vp_lanes** out, int gpu_id, int capacity, char* err, size_t err_len) {
+  if (!out) return VP_ERR_ARG;
+  *out = nullptr;
+  try {
+    if (capacity < 1 || capacity > 4096) throw std::invalid_argument("vp_lanes_create: capacity " + std::to_string(capacity) + " (1 .. 4096)");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) throw std::runtime_error("HIP error: no HIP device visible: a vp_lanes lives on the device");
+    if (gpu_id < 0 || gpu_id >= n) throw std::invalid_argument("gpu_id out of range");
+    auto l = std::make_unique<vp_lanes>();
+    l->impl = std::make_unique<vp::Lanes>(gpu_id, capacity);
+    *out = l.release();
+    return VP_OK;
+  } catch (const std::invalid_argument& ex) {
+    set_err(err, err_len, ex.what());
+    return VP_ERR_ARG;
+  } catch (const std::exception& ex) {
+    set_err(err, err_len, ex.what());
+    return VP_ERR_HIP;
+  }
+}
+
+void vp_lanes_destroy(vp_lanes* l) { delete l; }
+
+const char* vp_lanes_last_error(const vp_lanes* l) { return l ? l->err.c_str() : "null lane filter"; }
+
+int vp_lanes_set_smoothing(vp_lanes* l, float smoothing) {
+  return lanes_guarded(l, [&](vp::Lanes& g) {
+    if (!(smoothing >= 0.0f && smoothing <= 1.0f)) throw std::invalid_argument("vp_lanes_set_smoothing: a factor outside 0 .. 1");
+    g.set_smoothing(smoothing);
+  });
+}
+
+int vp_lanes_reset(vp_lanes* l) {
+  return lanes_guarded(l, [&](vp::Lanes& g) { g.reset(); });
+}
+
+int vp_lanes_add(vp_lanes* l, vp_engine* e, float threshold) {
+  return lanes_guarded(l, [&](vp::Lanes& g) { g.add(metric_engine(e, "vp_lanes_add"), threshold); });
+}
+
+int vp_lanes_add_logits(vp_lanes* l, const float* logits_3x80x160, float threshold) {
+  return lanes_guarded(l, [&](vp::Lanes& g) { g.add_logits(logits_3x80x160, threshold); });
+}
+
+int vp_lanes_pending(const vp_lanes* l) { return l && l->impl ? l->impl->pending() : VP_ERR_ARG; }
+
+int vp_lanes_fetch(vp_lanes* l, vp_lanes_result* out, int max, int* n) {
+  return lanes_guarded(l, [&](vp::Lanes& g) {
+    if (!n || max < 0 || (max > 0 && !out)) throw std::invalid_argument("vp_lanes_fetch: null n, max < 0, or null out with max > 0");
+    const int count = std::min(max, g.pending());
+    l->recs.resize((size_t)count);
+    l->fits.resize(2 * (size_t)count);
+    g.fetch(l->recs.data(), l->fits.data(), count);
+    for (int i = 0; i < count; ++i)
+      for (int k = 0; k < 2; ++k) lanes_result_lane(l->recs[i].lane[k], l->fits[2 * i + k], &out[i].lane[k]);
+    *n = count;
+  });
+}
+
+int vp_lanes_fetch_points(vp_lanes* l, int record_index, int lane, uint8_t* xy, int max_points, int* n) {
+  return lanes_guarded(l, [&](vp::Lanes& g) {
+    if (!n) throw std::invalid_argument("vp_lanes_fetch_points: null n");
+    *n = g.fetch_points(record_index, lane, xy, max_points);
+  });
+}
+
+int vp_lanes_fit(const int64_t S[5], const int64_t T[3], int order, double out[3], int* singular) {
+  try {
+    if (!S || !T || !out) return VP_ERR_ARG;
+    long long s[5], t[3];
+    for (int k = 0; k < 5; ++k) s[k] = S[k];
+    for (int k = 0; k < 3; ++k) t[k] = T[k];
+    const bool ok = vp::lanes_fit(s, t, order, out);
+    if (singular) *singular = ok ? 0 : 1;
+    return VP_OK;
+  } catch (const std::exception&) {
+    return VP_ERR_ARG;
+  }
+}
+
+}  // extern "C"
 namespace {
 // (hi, lo) planes of an activation, NHWC with padded channels on the device -> fp16 bit patterns [Creal][H][W] on the host
 void read_planes_chw(vp::Engine& g, const vp::Act* a, uint16_t* out_hi, uint16_t* out_lo) {

@@ -84,3 +84,12 @@ struct vp_metric {
   std::vector<float> det_label_cls;
   std::string err;
 };
+
+// vp_lanes: the production lane filter behind an EgoLanes pass (vp::Lanes, engine.hpp / engine_io.cpp; C ABI: vp_api.cpp).  `recs` / `fits`: the
+// scratch of a fetch.  One thread drives it.
+struct vp_lanes {
+  std::unique_ptr<vp::Lanes> impl;
+  std::vector<vp::LaneFilterRecord> recs;
+  std::vector<vp::LanesFit> fits;
+  std::string err;
+};

@@ -232,6 +232,17 @@ _SIGS = {
     "vp_metric_fetch_labels": (C.c_int, [_P, _P, C.c_int]),
     "vp_op_label_gt": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_char_p, C.c_size_t]),
     "vp_op_label_depth_gt": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_char_p, C.c_size_t]),
+    "vp_lanes_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "vp_lanes_destroy": (None, [_P]),
+    "vp_lanes_last_error": (C.c_char_p, [_P]),
+    "vp_lanes_set_smoothing": (C.c_int, [_P, C.c_float]),
+    "vp_lanes_reset": (C.c_int, [_P]),
+    "vp_lanes_add": (C.c_int, [_P, _P, C.c_float]),
+    "vp_lanes_add_logits": (C.c_int, [_P, _P, C.c_float]),
+    "vp_lanes_pending": (C.c_int, [_P]),
+    "vp_lanes_fetch": (C.c_int, [_P, _P, C.c_int, _P]),
+    "vp_lanes_fetch_points": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "vp_lanes_fit": (C.c_int, [_P, _P, C.c_int, _P, _P]),
 }
 # multi-camera exchange (csrc/vp_comm.cpp): part of libvp_hip.so, absent from the CPU-emulated test build
 _COMM_SIGS = {
@@ -365,6 +376,13 @@ class MetricRowsSummary(C.Structure):
                 ("map50", C.c_double)]
 
 
+VP_LANES_MAX_WINDOWS, VP_LANES_MAX_POINTS = 40, 1920
+VP_LANES_SINGULAR, VP_LANES_SMOOTHED = 1, 2
+# vp_lanes_lane / vp_lanes_result (include/vp_hip.h)
+LANES_LANE_DTYPE = np.dtype([("start_x", "<i4"), ("start_y", "<i4"), ("n_windows_up", "<i4"), ("n_windows_down", "<i4"), ("n_points_up", "<i4"), ("n_points_down", "<i4"),
+                             ("min_y", "<i4"), ("max_y", "<i4"), ("S", "<i8", (5,)), ("T", "<i8", (3,)), ("windows", "<i2", (VP_LANES_MAX_WINDOWS, 4)), ("order", "<i4"),
+                             ("flags", "<i4"), ("coeffs_valid", "<i4"), ("reserved", "<i4"), ("raw_coeffs", "<f8", (6,)), ("coeffs", "<f8", (6,))])
+LANES_RESULT_DTYPE = np.dtype([("lane", LANES_LANE_DTYPE, (2,))])
 VP_LABEL_F32, VP_LABEL_F64 = 0, 1
 LABEL_FRAME_DTYPE = np.dtype([("kind", "<i4"), ("n", "<u4"), ("freq", "<u4", (3,)), ("unmatched", "<u4"), ("outside", "<u4"), ("nonfinite", "<u4"), ("min", "<f8"),
                               ("max", "<f8")])
@@ -1605,6 +1623,85 @@ class Metric:
                    "nan_frames": s.nan_frames, "sceneseg_iou": tuple(s.sceneseg_iou), "sceneseg_iou_full": s.sceneseg_iou_full, "domainseg_iou": s.domainseg_iou,
                    "mae": s.mae, "mel": s.mel}
         return rec, summary
+
+
+class Lanes:
+    """vp_lanes: the production app's LaneFilter::update on the device.  add() reads an EgoLanes Engine's device-resident logits behind its pass and
+    returns without waiting; fetch() is the one synchronisation: a numpy array of LANES_RESULT_DTYPE, one record per add, oldest first -- start points,
+    windows, point counts, moments, this frame's fit and the smoothed coefficients.  One thread drives a filter (include/vp_hip.h)."""
+
+    def __init__(self, gpu_id=0, capacity=64):
+        self._lib = load()
+        self._h = _P()
+        err = C.create_string_buffer(512)
+        rc = self._lib.vp_lanes_create(C.byref(self._h), gpu_id, int(capacity), err, len(err))
+        if rc != 0:
+            self._h = None
+            raise (ValueError if rc == -1 else VpError)(f"vp_lanes_create failed ({rc}): {err.value.decode(errors='replace')}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vp_lanes_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _ck(self, rc):
+        if rc < 0:
+            msg = self._lib.vp_lanes_last_error(self._h).decode(errors="replace")
+            raise (ValueError if rc == -1 else VpError)(f"libvp_hip lanes error {rc}: {msg}")
+        return rc
+
+    def set_smoothing(self, s):
+        self._ck(self._lib.vp_lanes_set_smoothing(self._h, float(s)))
+
+    def reset(self):
+        self._ck(self._lib.vp_lanes_reset(self._h))
+
+    def pending(self):
+        return self._ck(self._lib.vp_lanes_pending(self._h))
+
+    def add(self, engine, threshold=0.0):
+        self._ck(self._lib.vp_lanes_add(self._h, engine._h if engine is not None else None, float(threshold)))
+
+    def add_logits(self, logits, threshold=0.0):
+        """logits: float32 [3][80][160] on the host (ego left, ego right, other lanes), copied before the call returns"""
+        if logits is None:
+            return self._ck(self._lib.vp_lanes_add_logits(self._h, None, float(threshold)))
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        if lg.shape != (3, 80, 160):
+            raise ValueError("add_logits: logits of shape (3, 80, 160)")
+        self._ck(self._lib.vp_lanes_add_logits(self._h, _ptr(lg), float(threshold)))
+
+    def fetch(self, max_records=None):
+        n = self.pending() if max_records is None else int(max_records)
+        rec = np.zeros(max(n, 0), dtype=LANES_RESULT_DTYPE)
+        got = C.c_int(0)
+        self._ck(self._lib.vp_lanes_fetch(self._h, _ptr(rec) if n > 0 else None, n, C.byref(got)))
+        return rec[:got.value]
+
+    def fetch_points(self, record_index, lane):
+        """the (x, y) points of one lane of a pending record, in collection order: uint8 [n][2]"""
+        xy = np.zeros((VP_LANES_MAX_POINTS, 2), dtype=np.uint8)
+        n = C.c_int(0)
+        self._ck(self._lib.vp_lanes_fetch_points(self._h, int(record_index), int(lane), _ptr(xy), VP_LANES_MAX_POINTS, C.byref(n)))
+        return xy[:n.value].copy()
+
+
+def lanes_fit(S, T, order):
+    """vp_lanes_fit: the exact least-squares line (order 1) or quadratic (order 2) from the integer moments -> ((a, b, c), singular); host only"""
+    s = np.ascontiguousarray(S, dtype=np.int64).reshape(5)
+    t = np.ascontiguousarray(T, dtype=np.int64).reshape(3)
+    out = np.zeros(3, dtype=np.float64)
+    sing = C.c_int(0)
+    rc = load().vp_lanes_fit(_ptr(s), _ptr(t), int(order), _ptr(out), C.byref(sing))
+    if rc != 0:
+        raise ValueError(f"vp_lanes_fit failed ({rc}): order 1 or 2, moments below 2^40")
+    return (tuple(float(v) for v in out), bool(sing.value))
 
 
 def select_f32(values, k, gpu_id=0):

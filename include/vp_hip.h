@@ -981,6 +981,78 @@ int vp_op_label_gt(int gpu_id, const uint8_t* label, int channels, int h, int w,
 int vp_op_label_depth_gt(int gpu_id, const void* label, int dtype, int h, int w, int stride_elems, int oh, int ow, float* gt_out, vp_label_frame* frame_out, char* err,
                          size_t err_len);
 
+/* ---- vp_lanes: the production lane filter on the device, logits in, fits out -----------------------------------------------------------
+ * What LaneFilter::update (VisionPilot/production_release/src/lane_filtering/lane_filter.cpp) computes between the EgoLanes pass and
+ * LaneTracker: two lane polynomials with their start points and search windows.  A vp_lanes handle owns a stream, a ring of `capacity` device
+ * records and the smoothing state.  vp_lanes_add reads an engine's device-resident logits behind its pass, ordered by events alone (the contract
+ * of vp_metric_add_seg), queues one kernel and returns; vp_lanes_fetch is the one synchronisation and moves about 1 KB per frame.
+ * Geometry: three fp32 planes [3][80][160] -- ego left, ego right, other lanes.  A pixel is SET iff logit > threshold (a NaN is never set).
+ *   START POINTS.  Left: rows 79 down to 40, in each row x from 79 down to 0 on the ego-left plane, the first set pixel.  Right: the same rows, x
+ *     from 80 up to 159 on the ego-right plane.  No hit: start = (-1, -1), the lane has no windows, points or fit, and its previous fit is forgotten.
+ *   SEARCH.  Per lane an upward run from the start point, then a downward run from 4 rows below it; each at most 20 steps.  A step at (x, y): it
+ *     ends the run when x is outside 0 .. 159, or y < 0 (up) / y >= 80 (down).  Half-width w = 1 when y < 40, else 6.  The window is columns
+ *     [x - w, x + w) and rows [y - 4, y) (up) or [y, y + 4) (down), clipped to the plane; it is recorded as x, y, width, height.  The set pixels of
+ *     the lane's own plane in the window, in row-major order, are the ego set; those of the other-lane plane the other set, empty when y < 40.
+ *     The ego set is taken when it has 3 pixels or more, else the other set when it has 3 or more.  A taken set is appended to the lane's points
+ *     (pixels of overlapping windows appear again); with its float centroid (cx, cy) = (sum x / n, sum y / n), d = (cx - x, cy - y) and
+ *     |d| = sqrt(dx dx + dy dy) (fp32, no fused multiply-add), the direction becomes d / |d| when |d| > 0.1f, and (x, y) = (roundf(cx), roundf(cy)).
+ *     Nothing taken: an upward run ends when y < 20; either run ends at the 12th empty window in a row; else (x, y) += (int)(direction * 4),
+ *     truncated.  The direction starts as (0, -1) / (0, 1).  Last, an upward run at y >= window bottom - 1 moves 4 rows up, a downward run at
+ *     y <= window top + 1 moves 4 rows down.
+ *   MOMENTS.  Over the lane's points, exact in 64-bit integers: S[k] = sum y^k (k = 0 .. 4), T[k] = sum x y^k (k = 0 .. 2), min_y, max_y.
+ *   FIT (vp_lanes_fetch, on the host).  n = S[0] < 4: none.  n < 30: the least-squares line x = b y + c; else the quadratic x = a y^2 + b y + c.
+ *     The normal equations are solved by Cramer's rule, every determinant exact in 128-bit integers, each coefficient ONE correctly rounded
+ *     quotient.  raw_coeffs = {0, a, b, c, min_y, max_y} (a = 0 for a line), `order` 1 or 2.
+ *     DEPARTURE 1: the reference's RANSAC loop (:137-177) is not run.  Its best inlier set starts as all points and is replaced only by a strictly
+ *     larger set, and every inlier set is a subset of the points: the final refit is always on all points, the loop only consumes random numbers.
+ *     DEPARTURE 2: a singular system (all points on one row; a quadratic's on two rows) gives order 0, VP_LANES_SINGULAR and no coefficients; the
+ *     reference's SVD solve would answer the minimum-norm solution.  The previous fit is left as it is, as for n < 4.
+ *     NOT PINNED: the reference solves the same least-squares problem with cv::solve(DECOMP_SVD) in double; how far its rounding lies from the
+ *     exact solution was not measured (no OpenCV where this was built).  tests/test_lane_filter_host.py measures numpy.linalg.lstsq instead.
+ *   SMOOTHING (vp_lanes_fetch, in the order of the adds).  A lane with a fit: when the previous fit is valid all six numbers become
+ *     s * raw + (1.0f - s) * previous (s a float, default 0.5f; products and sum in double, VP_LANES_SMOOTHED); the result is `coeffs`,
+ *     coeffs_valid = 1, and it is the new previous fit.  A start point but no fit: coeffs_valid = 0, the previous fit untouched.  No start point:
+ *     the previous fit is forgotten.  vp_lanes_reset forgets both; it is refused while records are pending.
+ * vp_lanes_add: e is a VP_EGOLANES engine (a shared-prefix head included) of output 3 x 80 x 160 with a pass behind it.
+ * vp_lanes_add_logits: the operator entry on host floats [3][80][160], copied before the call returns.
+ * vp_lanes_fetch: the oldest min(max, pending) records into out, *n their number; they stop being pending.
+ * vp_lanes_fetch_points: the point list of lane `lane` (0 left, 1 right) of pending record `record_index` (0 = the oldest, the first the next
+ *   vp_lanes_fetch returns): byte pairs (x, y), the upward run's points then the downward run's, at most 1920.  *n = the lane's point count;
+ *   min(*n, max_points) pairs are written.  Refused (VP_ERR_STATE) when nothing is pending: a fetch ends a record's window.
+ * vp_lanes_fit: the host solve alone, no device, no handle.  out = {a, b, c}; *singular (may be NULL) = 1 and out untouched for a singular
+ *   system (still VP_OK).  VP_ERR_ARG: a null pointer, order not 1 or 2, a moment of magnitude 2^40 or more.
+ * ERRORS.  VP_ERR_ARG: a null pointer, another engine kind or output size, an engine on another GPU, capacity outside 1 .. 4096, an index or lane
+ *   out of range.  VP_ERR_STATE: an engine with no pass yet, `capacity` records pending already, a reset with records pending.  A refused call
+ *   changes nothing.  One thread drives a handle. */
+#define VP_LANES_MAX_WINDOWS 40
+#define VP_LANES_MAX_POINTS 1920
+enum vp_lanes_flags { VP_LANES_SINGULAR = 1, VP_LANES_SMOOTHED = 2 };
+typedef struct vp_lanes vp_lanes;
+typedef struct vp_lanes_lane {
+  int32_t start_x, start_y;                      /* (-1, -1): no start point */
+  int32_t n_windows_up, n_windows_down;
+  int32_t n_points_up, n_points_down;
+  int32_t min_y, max_y;                          /* (80, -1) without points */
+  int64_t S[5], T[3];
+  int16_t windows[VP_LANES_MAX_WINDOWS][4];      /* x, y, width, height; the upward run's first */
+  int32_t order, flags, coeffs_valid, reserved;
+  double raw_coeffs[6], coeffs[6];
+} vp_lanes_lane;
+typedef struct vp_lanes_result {
+  vp_lanes_lane lane[2];                         /* ego left, ego right */
+} vp_lanes_result;
+int vp_lanes_create(vp_lanes** out, int gpu_id, int capacity, char* err, size_t err_len);
+void vp_lanes_destroy(vp_lanes* l);
+const char* vp_lanes_last_error(const vp_lanes* l);
+int vp_lanes_set_smoothing(vp_lanes* l, float smoothing);
+int vp_lanes_reset(vp_lanes* l);
+int vp_lanes_add(vp_lanes* l, vp_engine* e, float threshold);
+int vp_lanes_add_logits(vp_lanes* l, const float* logits_3x80x160, float threshold);
+int vp_lanes_pending(const vp_lanes* l);
+int vp_lanes_fetch(vp_lanes* l, vp_lanes_result* out, int max, int* n);
+int vp_lanes_fetch_points(vp_lanes* l, int record_index, int lane, uint8_t* xy, int max_points, int* n);
+int vp_lanes_fit(const int64_t S[5], const int64_t T[3], int order, double out[3], int* singular);
+
 /* ---- multi-camera result exchange (BASELINE configs[3]) ---------------------------------------
  * One process (or thread) per GPU, camera r on rank r, weights replicated, no data-path collective in the networks.  For the
  * fused ego-path / BEV consumer every rank needs all cameras' results: ONE ncclAllGather (RCCL over xGMI) per frame of a
