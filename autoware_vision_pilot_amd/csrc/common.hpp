@@ -87,6 +87,9 @@ struct ConvGemmParams {
   // v * out_mul (2^-s_out) behind activation, residual and post-activation.  scaled == 0: the three floats are not read (zero-initialised blocks stay valid).
   int scaled;
   float in_mul, res_mul, out_mul;
+  // VP_MFMA_FP8 (conv3x3_f8_kernel only; w8 holds the codes in the F8_K64 layout, wscale the row scales S_n): the layer's activation exponent qexp
+  // as the two powers of two the kernel multiplies with -- f8_qmul = 2^-qexp in front of the quantiser, f8_smul = 2^qexp on the row scale
+  float f8_qmul, f8_smul;
 };
 
 // nn.GELU() (exact erf form, scene_neck.py:8).  ~300 M activations per frame: libm's erff (~45 VALU ops, branchy)
@@ -113,6 +116,25 @@ __host__ __device__ __forceinline__ float e4m3_to_float(unsigned b) {
   v.u = ((e + 120u) << 23) | (m << 20);
   const float mag = e ? v.f : (float)m * 0.001953125f;
   return (b & 0x80u) ? -mag : mag;
+}
+// VP_MFMA_FP8, the activation quantiser (include/vp_hip.h "FP8 MFMA ENGINES"): the e4m3 code of x * mul, x an fp16 value carried exactly in fp32 and
+// mul = 2^-qexp (|qexp| <= 24: the product is exact and a normal fp32 number).  Round to nearest even onto the e4m3 grid -- multiples of 2^-9 below
+// 2^-6, three mantissa bits above -- everything beyond +-448, the infinities included, becomes +-448 (clamping first is the same: 448 is on the grid
+// and rounding is monotone), NaN becomes the NaN code 0x7f with the sign, zeros keep their sign.  One body for the kernel, the array kernel and the host entry.
+__host__ __device__ __forceinline__ unsigned e4m3_quantize(float x, float mul) {
+  union { float f; unsigned u; } v;
+  v.f = x * mul;
+  const unsigned sign = (v.u >> 24) & 0x80u;
+  unsigned a = v.u & 0x7fffffffu;
+  if (a > 0x7f800000u) return sign | 0x7fu;
+  if (a > 0x43e00000u) a = 0x43e00000u;   // 448
+  if (a < 0x3c800000u) {                  // below 2^-6: adding 2^14 (one ulp = 2^-9) rounds to the subnormal grid, ties to even
+    v.u = a;
+    v.f += 16384.0f;
+    return sign | (v.u - 0x46800000u);
+  }
+  a += 0x7ffffu + ((a >> 20) & 1u);       // ties to even on the 20 dropped mantissa bits; a carry moves into the exponent
+  return sign | ((a >> 20) - 960u);       // (fp32 exponent - 120) << 3 | three mantissa bits
 }
 // 8 e4m3 codes (two dwords, element i in byte i) -> 8 fp16 values packed as a 16-byte piece (what the fp16 weight layout holds there).  Two codes per
 // step: sign to bit 15, (exponent, mantissa) to bits 13..7 of each half -- as fp16 bits that is value / 256, an fp16 SUBNORMAL for the seven subnormal

@@ -161,6 +161,13 @@ RowScale row_prescale(const float* w, size_t rows, size_t per, size_t rows_alloc
 // ==================================================================================================== Engine
 Engine::Engine(int kind, const WeightBlob* blob, int precision, int gpu_id, Engine* base, int frames, int frame_index)
     : kind_(kind), precision_(precision), gpu_(gpu_id), frames_(frames), frame_index_(frame_index), base_(base) {
+  if ((precision & 128) != 0) {
+    if ((precision & 15) != 0) throw std::invalid_argument("VP_MFMA_FP8 needs VP_FP16 (VP_FP16X3 is the parity mode: fp8 activations cannot meet its contract)");
+    if ((precision & 16) != 0) throw std::invalid_argument("VP_MFMA_FP8 cannot be combined with VP_WEIGHTS_FP8 (the e4m3 MFMA layers quantise their own weights)");
+    if ((precision & 64) != 0) throw std::invalid_argument("VP_MFMA_FP8 cannot be combined with VP_ACT_SCALE");
+    if (kind >= 4) throw std::invalid_argument("VP_MFMA_FP8: VP_SCENESEG, VP_SCENE3D, VP_DOMAINSEG and VP_EGOLANES engines only (not VP_AUTODRIVE, VP_AUTOSPEED, VP_AUTOSTEER)");
+    if (base || frames != 1) throw std::invalid_argument("VP_MFMA_FP8: shared-prefix and batched creation are not supported (the engine must own its whole network)");
+  }
   if ((precision & 64) != 0) {
     if (kind >= 0 && kind != 4 && kind != 5 && kind != 6)
       throw std::invalid_argument("VP_ACT_SCALE: the per-tensor activation scale is built for VP_AUTODRIVE, VP_AUTOSPEED and VP_AUTOSTEER engines (not for the scene networks)");
@@ -177,7 +184,7 @@ Engine::Engine(int kind, const WeightBlob* blob, int precision, int gpu_id, Engi
   if (kind == 6 && ((precision & 16) != 0 || base || frames > 1))
     throw std::invalid_argument("VP_AUTOSTEER: VP_WEIGHTS_FP8, shared-prefix and batched creation are not supported for the lane-perception network (VP_FP16 / VP_FP16X3, optionally | VP_PLAN_LATENCY)");
   if (base && base->kind_ == 6) throw std::invalid_argument("VP_AUTOSTEER engines cannot be the base of a shared-prefix engine");
-  if ((precision & 15) > 1 || (precision & ~(1 | 16 | 32 | 64)) != 0) throw std::invalid_argument("precision must be VP_FP16 or VP_FP16X3 (optionally | VP_WEIGHTS_FP8 | VP_PLAN_LATENCY | VP_ACT_SCALE)");
+  if ((precision & 15) > 1 || (precision & ~(1 | 16 | 32 | 64 | 128)) != 0) throw std::invalid_argument("precision must be VP_FP16 or VP_FP16X3 (optionally | VP_WEIGHTS_FP8 | VP_PLAN_LATENCY | VP_ACT_SCALE | VP_MFMA_FP8)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     throw std::runtime_error("libvp_hip: no HIP device visible (this library has no CPU fallback)");

@@ -268,6 +268,19 @@ class Engine {
   void reset_range();
   std::vector<int> act_scales() const;                  // one per acts() entry
   void set_act_scales(const int* exps, int n);
+  // VP_MFMA_FP8 (creation flag, VP_FP16 scene networks that own their whole network, and the operator entry): the plain big 3x3 layers run on the e4m3
+  // MFMA kernel; every such layer quantises its input as e4m3(x * 2^-qexp) with a per-layer exponent (include/vp_hip.h "FP8 MFMA ENGINES")
+  bool mfma_fp8() const { return (precision_ & 128) != 0; }
+  struct Fp8Layer {
+    size_t op = 0;     // launch index (ops())
+    int tensor = -1;   // the input tensor's index in acts()
+    int qexp = 0;
+    bool seen = false; // measured or installed since the last reset: a later calibration only raises it
+  };
+  const std::vector<Fp8Layer>& fp8_layers() const { return f8_layers_; }
+  void calibrate_fp8(int target_log2);
+  void reset_fp8();
+  void set_fp8_exps(const int* exps, int n);
   void stash_previous_frame();                          // AutoDrive: keeps the frame vp_infer_pair primes with, so that a calibration can run the pair again
   // kernel plan target of THIS engine (round 6: a creation flag, VP_PLAN_LATENCY; the process-wide developer option VP_PLAN_TARGET still selects it for
   // every engine created while it is set): the round-4 choices for the CU-time rules of engine_dispatch.cpp
@@ -363,6 +376,7 @@ class Engine {
   Act* neck_out_ = nullptr;
   std::vector<int> act_exp_;        // VP_ACT_SCALE: exponent per tie group (Act::tie)
   std::vector<char> act_exp_seen_;  // ... measured since the last reset: a later measurement only raises it
+  std::vector<Fp8Layer> f8_layers_; // VP_MFMA_FP8: one per conv3x3_f8 launch, in launch order (the launches read qexp when they run)
   unsigned* d_absmax_ = nullptr;
   unsigned long long* d_survey_ = nullptr;   // range_survey: per tensor {abs-max bits | non-finite count << 32 as two words, VP_HIST_WORDS counters}
   // The eager launch-by-launch walk calibrate_range and range_survey share (engine_io.cpp): visit(i, a, begin, prime) runs behind launch i for every

@@ -295,6 +295,19 @@ int late_c64_tile(const ConvQuery& q, int ncols, int M, int halo, ConvChoice* c)
   return halo;
 }
 
+// step 5b, VP_MFMA_FP8: what the e4m3 MFMA kernel (halo tile 13, kernels_conv3x3.hip conv3x3_f8_kernel) can run ...
+bool f8_shape_ok(const ConvQuery& q, int ncols) {
+  return q.ks == 3 && std::max(1, q.stride) == 1 && !q.split && !q.fp8_storage && !q.in2 && !q.logits_out && plain_epilogue(q) && q.cin_pad >= 64 &&
+         q.cin_pad % 64 == 0 && round_up(ncols, 64) == ncols;
+}
+// ... and which of those layers a flagged engine hands to it: maps of 80 x 160 pixels and larger (below, the fp16 engines' layers are split-K or
+// map-kernel layers the kernel has no form for) with at least 512 input channels -- decode_layer_5 of the scene decoders (512 -> 256 on 80 x 160).
+// The channel floor is MEASURED (profiles/f8_mfma.txt, us, fp16 kernel -> conv3x3_f8): decode_layer_5 55.4 -> 51.8, but decode_layer_7 (256 -> 128 on
+// 160 x 320) 38.2 -> 56.3 and decode_layer_9 (128 -> 64 on 320 x 640) 50.1 -> 60.4: the kernel runs at 500 - 580 TFLOP/s on all three (it quantises its
+// halo in VALU instructions, per output-channel tile), the fp16 kernels at 545 / 790 / 600.  VP_PLAN_OVERRIDE "<layer>=13" still puts any layer that
+// f8_shape_ok accepts on the kernel (tools/bench_f8.py measures the two excluded layers that way).
+bool f8_rule(const ConvQuery& q, int ncols) { return f8_shape_ok(q, ncols) && q.H * q.W >= 12800 && q.cin_pad >= 512; }
+
 }  // namespace
 
 ConvChoice choose_conv(const std::string& name, const ConvQuery& q) {
@@ -315,8 +328,21 @@ ConvChoice choose_conv(const std::string& name, const ConvQuery& q) {
     if (halo == 11 && (q.fp8_storage || (!q.split && q.cin_pad % 32 != 0) || !conv3x3_map_shape_ok(q.H, q.W, q.cin_pad, round_up(ncols, 32))))
       throw std::invalid_argument("halo tile 11 (map kernel): maps that tile into 20x40 or 10x20 regions, >= 32 input channels (a multiple of 32 in the fp16 engines): " + name);
     if (halo >= 6 && halo <= 9 && !q.split && q.cin_pad % 64 != 0) throw std::invalid_argument("halo tiles 6 - 9 in the fp16 engines: input channels a multiple of 64: " + name);
+    // step 5b, VP_MFMA_FP8 (only with the flag): the plain big layers move to the e4m3 MFMA kernel, whatever fp16 kernel the steps above gave them
+    if (q.mfma_fp8 && q.tile < 0 && q.nsplit <= 0 && f8_rule(q, ncols)) halo = 13;
+    if (halo == 13 && !(q.mfma_fp8 && f8_shape_ok(q, ncols)))
+      throw std::invalid_argument("halo tile 13 (e4m3 MFMA kernel): VP_FP16 | VP_MFMA_FP8, 3x3 stride 1, conv + bias + {GELU, none}, input channels a multiple of 64, output channels that pad to a multiple of 64 without waste: " + name);
   }
   ConvChoice c;
+  if (halo == 13) {   // one tile shape, no split-K
+    c.tile = 113;
+    c.bk = 64;
+    c.CoutW = round_up(ncols, 64);
+    c.nsplit = 1;
+    c.layout = F8_K64;
+    c.w8 = true;
+    return c;
+  }
   if (halo >= 0) {
     // The fp16 rule of step 2 picks four K slices WITH halo tile 7, and a later step may still replace the tile: the factor then reaches the new tile's
     // kernel as if the caller had forced it (SceneNeck.decode_layer_0 of the three-op fp16 plan runs the map kernel on 4 slices instead of its own ~10:
@@ -378,6 +404,7 @@ size_t pack_index(WeightLayout layout, int co, int ci, int tap, int cin_pad, int
     case MAP_K32: return conv3x3_map_pack_index_k32(co, ci, tap, cin_pad);
     case MAP2: return conv3x3_map2_pack_index(co, ci, tap, cin_pad);
     case GEMM_DMA: return gemm_dma_pack_index(co, ci, cin_pad);
+    case F8_K64: return (((size_t)(ci >> 6) * 9 + tap) * CoutW + co) * 64 + ((((ci & 63) >> 4) ^ ((co >> 2) & 3)) << 4 | (ci & 15));
   }
   return 0;
 }
@@ -611,11 +638,30 @@ void Engine::push_conv_op(const std::string& name, const Act* in, const PackedCo
     op.bytes += esz * ((double)M * 4.0 * o.in2->Creal + (double)cout_real * o.in2->Creal);
   }
   int ht = tile - 100;
-  if (tile >= 100 && o.tile < 100 && dev_option_is("VP_AUTOTUNE", '1') && kind_ >= 0) ht = autotune_halo_tile(p, ht, sp, stream_);
+  if (tile >= 100 && ht != 13 && o.tile < 100 && dev_option_is("VP_AUTOTUNE", '1') && kind_ >= 0) ht = autotune_halo_tile(p, ht, sp, stream_);
   // the heads' logits convolution: weights stationary in registers, 16x16x32 MFMA, LDS-DMA halo (kernels_head.hip); same weight
   // packing as halo tile 4.  VP_HEAD_CONV=0 keeps the halo kernel.
   const bool head = tile >= 100 && ht == 4 && o.tile < 0 && head_conv_supported(p) && !(dev_option_is("VP_HEAD_CONV", '0'));
-  if (tile >= 100 && ht == 11) {
+  if (tile >= 100 && ht == 13) {
+    // VP_MFMA_FP8: the launch reads its layer's qexp when it RUNS (vp_calibrate_fp8 / vp_set_fp8_exps change it and invalidate the graph)
+    p.f8_qmul = p.f8_smul = 1.0f;
+    if (!mfma_fp8() || !conv3x3_f8_supported(p))
+      throw std::invalid_argument("halo tile 13 (e4m3 MFMA kernel): VP_FP16 | VP_MFMA_FP8, conv + bias + {GELU, none}, NHWC, input and output channels multiples of 64: " + name);
+    Fp8Layer fl;
+    fl.op = ops_.size();
+    for (size_t t = 0; t < acts_.size(); ++t)
+      if (acts_[t].get() == in) fl.tensor = (int)t;
+    const size_t slot = f8_layers_.size();
+    f8_layers_.push_back(fl);
+    op.kernel = "conv3x3_f8";
+    op.run = [this, p, slot](hipStream_t st) {
+      ConvGemmParams q = p;
+      const int e = f8_layers_[slot].qexp;
+      q.f8_qmul = std::ldexp(1.0f, -e);
+      q.f8_smul = std::ldexp(1.0f, e);
+      return launch_conv3x3_f8(q, st);
+    };
+  } else if (tile >= 100 && ht == 11) {
     if (!conv3x3_map_supported(p)) throw std::invalid_argument("halo tile 11 (map kernel): 3x3 stride 1, 20x40 or 10x20 regions: " + name);
     op.kernel = conv_kernel_tag(K_MAP, p, ht, bk, sp, fuse_decode);
     op.run = [p](hipStream_t st) { return launch_conv3x3_map(p, st); };
@@ -683,6 +729,7 @@ Act* Engine::add_conv(const std::string& name, const Act* in, const std::vector<
   q.logits_out = o.logits_out != nullptr, q.in2 = o.in2 != nullptr;
   q.tile = o.tile, q.bk = o.bk, q.nsplit = o.nsplit;
   q.split = split(), q.fp8_storage = fp8_storage(), q.plan_latency = plan_latency();
+  q.mfma_fp8 = mfma_fp8();
   const ConvChoice c = choose_conv(name, q);
   PackedConv pc(c);
   const HostWeights hw = pack_weight_rows(

@@ -30,7 +30,8 @@ enum WeightLayout {
   MAP,           // map kernel (halo tile 11), parity mode
   MAP_K32,       // map kernel in the fp16 engines: 32-channel steps, the step's halves in the two plane arrays
   MAP2,          // map kernel, 64-channel slabs (halo tile 12)
-  GEMM_DMA       // LDS-DMA GEMM kernel (tile 6)
+  GEMM_DMA,      // LDS-DMA GEMM kernel (tile 6)
+  F8_K64         // VP_MFMA_FP8 (halo tile 13): e4m3 codes [K / 64][tap][CoutW][64], the 16-byte chunks of a row XOR-swizzled (the kernel's LDS image)
 };
 struct ConvQuery {
   int H = 0, W = 0, stride = 1;          // INPUT map, convolution stride
@@ -39,6 +40,7 @@ struct ConvQuery {
   bool logits_out = false, in2 = false;
   int tile = -1, bk = -1, nsplit = -1;   // caller-forced (ConvOpts, VP_PLAN_OVERRIDE); < 0 / <= 0 = the rule's
   bool split = false, fp8_storage = false, plan_latency = false;
+  bool mfma_fp8 = false;                 // VP_MFMA_FP8: the engine's plain big 3x3 layers take the e4m3 MFMA kernel (halo tile 13)
 };
 struct ConvChoice {
   int tile = 0;                          // 0 - 6: generic GEMM / LDS-DMA GEMM tile, 100 + halo tile: the 3x3 kernels

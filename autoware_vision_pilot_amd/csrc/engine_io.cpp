@@ -2151,6 +2151,74 @@ void Engine::calibrate_range(int target_log2) {
   if (!done) throw RangeError("vp_calibrate_range: the exponents did not settle");
 }
 
+// ------------------------------------------------------------------------------------------------ VP_MFMA_FP8
+// Per-layer activation exponents of the e4m3 MFMA layers (include/vp_hip.h "FP8 MFMA ENGINES").  The launches read f8_layers_[..].qexp when they run, so a
+// changed exponent only invalidates the captured graph -- the mechanism of VP_ACT_SCALE, per layer instead of per tensor.
+void Engine::set_fp8_exps(const int* exps, int n) {
+  if (!mfma_fp8()) throw std::invalid_argument("vp_set_fp8_exps: the engine was not created with VP_MFMA_FP8");
+  if (!exps || n != (int)f8_layers_.size()) throw std::invalid_argument("vp_set_fp8_exps: the table needs one exponent per fp8 layer (" + std::to_string(f8_layers_.size()) + ")");
+  for (int i = 0; i < n; ++i)
+    if (exps[i] < -24 || exps[i] > 24) throw std::invalid_argument("vp_set_fp8_exps: exponent out of range (-24 .. 24): " + ops_[f8_layers_[i].op].name);
+  for (int i = 0; i < n; ++i) {
+    f8_layers_[i].qexp = exps[i];
+    f8_layers_[i].seen = true;   // an installed exponent counts as measured: a later calibration only raises it
+  }
+  exps_changed();
+}
+
+void Engine::reset_fp8() {
+  if (!mfma_fp8()) throw std::invalid_argument("vp_reset_fp8: the engine was not created with VP_MFMA_FP8");
+  for (Fp8Layer& l : f8_layers_) {
+    l.qexp = 0;
+    l.seen = false;
+  }
+  exps_changed();
+}
+
+// One eager pass over the resident frame (walk_stored).  Behind the launch that stores the input tensor of an fp8 layer the tensor's abs-max is measured
+// (act_absmax_kernel) and the layer's qexp set so that absmax * 2^-qexp lies in [2^(target - 1), 2^target) -- before that layer runs, so every layer
+// downstream sees what the calibrated layers ahead of it produce.  An all-zero (or all non-finite) tensor leaves qexp as it is; later calls only raise.
+void Engine::calibrate_fp8(int target_log2) {
+  if (!mfma_fp8()) throw std::invalid_argument("vp_calibrate_fp8: the engine was not created with VP_MFMA_FP8");
+  if (target_log2 == 0) target_log2 = 8;
+  if (target_log2 < 1 || target_log2 > 8) throw std::invalid_argument("vp_calibrate_fp8: target_log2 is 1 .. 8 (0 = the default, 8: 1.75x headroom below 448)");
+  if (!input_is_tensor_ && !d_frame_) throw std::runtime_error("no frame resident: call vp_upload_frame / vp_infer first");
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  if (!d_absmax_) d_absmax_ = static_cast<unsigned*>(dalloc(2 * sizeof(unsigned)));
+  auto settle = [&](size_t i, const Act* a, size_t, bool) -> bool {
+    for (Fp8Layer& l : f8_layers_) {
+      if (l.tensor < 0 || acts_[l.tensor].get() != a || l.op <= i) continue;
+      bool last = true;   // the finished tensor: no launch between this one and the layer stores it again
+      for (size_t j = i + 1; j < l.op && last; ++j)
+        for (const Act* w : ops_[j].writes) last = last && w != a;
+      if (!last) continue;
+      unsigned r[2] = {0u, 0u};
+      fill_zero(d_absmax_, sizeof(r));
+      VP_HIP_CHECK(launch_act_absmax(a->hi, a->lo, a->Creal, a->H, a->W, a->C, d_absmax_, stream_));
+      copy_d2h(r, d_absmax_, sizeof(r));
+      float amax;
+      std::memcpy(&amax, &r[0], sizeof(float));
+      if (!(amax > 0.0f)) continue;
+      int e2 = 0;
+      std::frexp(amax, &e2);   // abs-max in [2^(e2 - 1), 2^e2)
+      const int want = std::max(-24, std::min(24, e2 - target_log2));
+      l.qexp = l.seen ? std::max(l.qexp, want) : want;
+      l.seen = true;
+    }
+    return true;
+  };
+  try {
+    walk_stored(settle);
+  } catch (...) {
+    hipStreamSynchronize(stream_);
+    exps_changed();
+    throw;
+  }
+  VP_HIP_CHECK(hipStreamSynchronize(stream_));
+  exps_changed();
+}
+
 // vp_range_survey: the same walk with a visitor that only measures.  Behind the LAST launch that stores a tensor (alias slices of a concatenation, in-place
 // copies: one measurement of the finished tensor) it queues act_absmax_kernel and act_exp_hist_kernel on the stored planes; nothing is read back until the
 // pass has ended, so the survey costs one synchronisation.  No exponent, launch or graph changes: the engine is left as a plain pass over the same input

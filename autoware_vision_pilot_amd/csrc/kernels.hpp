@@ -465,6 +465,12 @@ hipError_t launch_conv3x3_x3(const ConvGemmParams& p, int shape, hipStream_t st)
 int halo_tile_co(int tile);
 int halo_tile_px(int tile);
 int halo_tile_th(int tile);
+// halo tile 13, VP_MFMA_FP8 (kernels_conv3x3.hip conv3x3_f8_kernel): e4m3 codes in p.w8 (F8_K64 layout), row scales in p.wscale, p.f8_qmul / p.f8_smul =
+// 2^-qexp / 2^qexp; conv + bias + {GELU, none}, one fp16 plane in and out, NHWC, Cin and CoutW multiples of 64, no split-K
+bool conv3x3_f8_supported(const ConvGemmParams& p);
+hipError_t launch_conv3x3_f8(const ConvGemmParams& p, hipStream_t st);
+// out[i] = e4m3_quantize(in[i], mul) (common.hpp): the kernel's quantiser over an array
+hipError_t launch_fp8_quantize(const half_t* in, size_t n, float mul, uint8_t* out, hipStream_t st);
 
 // small-map 3x3 of the parity mode (kernels_conv3x3_map.hip; halo tile id 11): a workgroup = 32 output channels x a K slice x all 800 pixels of a
 // 20x40 region; weights packed by conv3x3_map_pack_index; always finishes through splitk_finish_kernel (p.partial required, nsplit >= 1)

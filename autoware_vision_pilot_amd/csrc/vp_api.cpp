@@ -1562,6 +1562,34 @@ int vp_set_act_scales(vp_engine* e, const int* exps, int n) {
   return guarded(e, [&](vp::Engine& g) { g.set_act_scales(exps, n); });
 }
 
+// ---- VP_MFMA_FP8: per-layer activation exponents of the e4m3 MFMA layers (engine_io.cpp)
+int vp_calibrate_fp8(vp_engine* e, int target_log2) {
+  return guarded(e, [&](vp::Engine& g) { g.calibrate_fp8(target_log2); });
+}
+int vp_reset_fp8(vp_engine* e) {
+  return guarded(e, [&](vp::Engine& g) { g.reset_fp8(); });
+}
+int vp_fp8_layers(const vp_engine* e, vp_fp8_layer* out, int cap) {
+  if (!e || !e->impl || cap < 0 || (cap > 0 && !out) || !e->impl->mfma_fp8()) return VP_ERR_ARG;
+  const std::vector<vp::Engine::Fp8Layer>& v = e->impl->fp8_layers();
+  for (int i = 0; i < cap && i < (int)v.size(); ++i) out[i] = vp_fp8_layer{(int)v[i].op, v[i].tensor, v[i].qexp};
+  return (int)v.size();
+}
+int vp_set_fp8_exps(vp_engine* e, const int* exps, int n) {
+  return guarded(e, [&](vp::Engine& g) { g.set_fp8_exps(exps, n); });
+}
+// host only: the quantiser of the e4m3 MFMA layers (common.hpp e4m3_quantize) over fp16 bit patterns
+int vp_fp8_quantize_act(const uint16_t* f16, size_t n, int qexp, uint8_t* codes) {
+  if ((n > 0 && (!f16 || !codes)) || qexp < -24 || qexp > 24) return VP_ERR_ARG;
+  const float mul = std::ldexp(1.0f, -qexp);
+  for (size_t i = 0; i < n; ++i) {
+    vp::half_t h;
+    std::memcpy(&h, f16 + i, 2);
+    codes[i] = (uint8_t)vp::e4m3_quantize((float)h, mul);
+  }
+  return VP_OK;
+}
+
 // ---- range survey (engine_io.cpp Engine::range_survey)
 static_assert(VP_RANGE_BINS == vp::VP_HIST_BINS && VP_RANGE_EXP_MIN == vp::VP_HIST_EXP_MIN, "vp_hip.h and kernels.hpp describe one histogram");
 int vp_range_survey(vp_engine* e, vp_range_stats* out, int cap) {
@@ -2569,6 +2597,39 @@ int vp_op_dwconv3x3(int gpu_id, int precision, const float* in, int c, int h, in
     }
     VP_HIP_CHECK(vp::launch_dwconv_plain(dp, g.stream()));
     read_planes_chw(g, to, out_hi, out_lo);
+  });
+}
+
+// ---- the e4m3 MFMA layer (VP_MFMA_FP8): the engine's packer and launch on any map size (the dispatch rule's size floor is the engine's, not the kernel's)
+int vp_op_conv3x3_f8(int gpu_id, const float* in, int cin, int h, int w, const float* weight, const float* bias, int cout, int act, int qexp,
+                     uint16_t* out_f16, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!in || !weight || !bias || !out_f16 || cin < 1 || cout < 1 || h < 1 || w < 1 || (long long)h * w > (1 << 22)) throw std::invalid_argument("bad argument");
+    if (act != 0 && act != 1) throw std::invalid_argument("vp_op_conv3x3_f8: act 0 (none) or 1 (GELU)");
+    if (h < 8 || w < 16) throw std::invalid_argument("vp_op_conv3x3_f8: maps of at least 8 x 16 pixels");
+    vp::Engine g(-1, nullptr, VP_FP16 | VP_MFMA_FP8, gpu_id);
+    vp::Act* a = g.new_act("in", cin, h, w);
+    g.upload_act(a, in);   // one fp16 plane: the values rounded to fp16
+    vp::ConvOpts o;
+    o.act = act;
+    o.tile = 113;
+    const size_t wn = (size_t)cin * cout * 9;
+    vp::Act* y = g.add_conv("op", a, std::vector<float>(weight, weight + wn), std::vector<float>(bias, bias + cout), cout, 3, o);
+    g.set_fp8_exps(&qexp, 1);
+    g.run_eager();
+    g.sync();
+    read_planes_chw(g, y, out_f16, nullptr);
+  });
+}
+
+int vp_op_fp8_quantize(int gpu_id, const uint16_t* f16, size_t n, int qexp, uint8_t* codes, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!f16 || !codes || n < 1 || n > (1u << 28) || qexp < -24 || qexp > 24) throw std::invalid_argument("bad argument (qexp: -24 .. 24)");
+    vp::Engine g(-1, nullptr, VP_FP16, gpu_id);
+    const DevPlanes d = upload_planes(g, f16, nullptr, n);
+    uint8_t* dc = reinterpret_cast<uint8_t*>(g.alloc_f32((n + 3) / 4));
+    VP_HIP_CHECK(vp::launch_fp8_quantize(d.hi, n, std::ldexp(1.0f, -qexp), dc, g.stream()));
+    g.copy_d2h(codes, dc, n);
   });
 }
 

@@ -19,6 +19,7 @@ VP_SCENESEG, VP_SCENE3D, VP_DOMAINSEG, VP_EGOLANES, VP_AUTODRIVE, VP_AUTOSPEED, 
 VP_WEIGHTS_FP8 = 16
 VP_PLAN_LATENCY = 32  # creation flag: this engine's kernel plan targets one network on one camera, one frame at a time (vp_hip.h)
 VP_ACT_SCALE = 64  # creation flag: per-tensor power-of-two activation scale (AutoDrive, AutoSpeed, AutoSteer; parity mode; vp_hip.h)
+VP_MFMA_FP8 = 128  # creation flag: the big plain 3x3 layers of a VP_FP16 scene network on the e4m3 MFMA kernel (vp_hip.h "FP8 MFMA ENGINES")
 VP_FP16, VP_FP16X3 = 0, 1
 VP_BGR8, VP_RGB8 = 0, 1
 VP_PLANES_BGR, VP_PLANES_RGB = 0, 1
@@ -100,6 +101,13 @@ _SIGS = {
     "vp_act_scales": (C.c_int, [_P, _P, C.c_int]),
     "vp_set_act_scales": (C.c_int, [_P, _P, C.c_int]),
     "vp_range_survey": (C.c_int, [_P, _P, C.c_int]),
+    "vp_calibrate_fp8": (C.c_int, [_P, C.c_int]),
+    "vp_reset_fp8": (C.c_int, [_P]),
+    "vp_fp8_layers": (C.c_int, [_P, _P, C.c_int]),
+    "vp_set_fp8_exps": (C.c_int, [_P, _P, C.c_int]),
+    "vp_fp8_quantize_act": (C.c_int, [_P, C.c_size_t, C.c_int, _P]),
+    "vp_op_conv3x3_f8": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_char_p, C.c_size_t]),
+    "vp_op_fp8_quantize": (C.c_int, [C.c_int, _P, C.c_size_t, C.c_int, _P, C.c_char_p, C.c_size_t]),
     "vp_op_exp_hist": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_char_p, C.c_size_t]),
     "vp_op_absmax": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint), C.c_char_p, C.c_size_t]),
     "vp_op_conv2d_scaled": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P,
@@ -295,6 +303,11 @@ GT_FORMS = {"label": VP_GT_LABEL, "bits": VP_GT_BITS}
 
 def _named(table, v):
     return table[v.lower()] if isinstance(v, str) else int(v)
+
+
+class Fp8Layer(C.Structure):
+    """vp_fp8_layer (include/vp_hip.h): one conv3x3_f8 launch -- its launch index, its input tensor's index, its activation exponent"""
+    _fields_ = [("launch", C.c_int), ("tensor", C.c_int), ("qexp", C.c_int)]
 
 
 class RangeStats(C.Structure):
@@ -594,6 +607,44 @@ def fp8_encode_rows(w):
     return codes, scale
 
 
+def fp8_quantize_act(f16, qexp=0):
+    """vp_fp8_quantize_act (host only): float16 array -> uint8 e4m3 codes of x * 2^-qexp under the rule of the e4m3 MFMA layers."""
+    a = np.ascontiguousarray(f16, dtype=np.float16)
+    codes = np.empty(a.shape, np.uint8)
+    if load().vp_fp8_quantize_act(_ptr(a), a.size, int(qexp), _ptr(codes)) != 0:
+        raise ValueError("vp_fp8_quantize_act failed (qexp: -24 .. 24)")
+    return codes
+
+
+def fp8_quantize(f16, qexp=0, gpu_id=0):
+    """vp_op_fp8_quantize: the same codes from the kernel's device function."""
+    a = np.ascontiguousarray(f16, dtype=np.float16)
+    codes = np.empty(a.shape, np.uint8)
+    err = C.create_string_buffer(512)
+    rc = load().vp_op_fp8_quantize(gpu_id, _ptr(a), a.size, int(qexp), _ptr(codes), err, len(err))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_op_fp8_quantize failed ({rc}): {err.value.decode(errors='replace')}")
+    return codes
+
+
+def conv3x3_f8(x, weight, bias, act=0, qexp=0, gpu_id=0):
+    """vp_op_conv3x3_f8: Conv2d 3x3 + bias + act (0 none, 1 GELU) on the e4m3 MFMA kernel under the activation exponent qexp.
+    x [cin][h][w], weight [cout][cin][3][3], bias [cout] -> the stored float16 [cout][h][w]."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    weight = np.ascontiguousarray(weight, dtype=np.float32)
+    bias = np.ascontiguousarray(bias, dtype=np.float32)
+    cin, h, w = x.shape
+    cout = weight.shape[0]
+    if weight.shape != (cout, cin, 3, 3) or bias.shape != (cout,):
+        raise ValueError("weight [cout][cin][3][3], bias [cout]")
+    out = np.empty((cout, h, w), np.float16)
+    err = C.create_string_buffer(512)
+    rc = load().vp_op_conv3x3_f8(gpu_id, _ptr(x), cin, h, w, _ptr(weight), _ptr(bias), cout, int(act), int(qexp), _ptr(out), err, len(err))
+    if rc != 0:
+        raise (ValueError if rc == -1 else VpError)(f"vp_op_conv3x3_f8 failed ({rc}): {err.value.decode(errors='replace')}")
+    return out
+
+
 def split_weight_rows(w):
     """vp_split_weight_rows (host only): fp32 [rows][per_row] -> (hi fp16, lo fp16, post_scale fp32 [rows])."""
     w = np.ascontiguousarray(w, dtype=np.float32)
@@ -620,7 +671,7 @@ def convert_onnx(onnx_path, vpw_path):
 class Engine:
     """Thin RAII wrapper over a vp_engine handle."""
 
-    def __init__(self, kind, weights, precision="fp16", gpu_id=0, base=None, weights_fp8=False, frames=1, frame_index=None, plan_latency=False, act_scale=False):
+    def __init__(self, kind, weights, precision="fp16", gpu_id=0, base=None, weights_fp8=False, frames=1, frame_index=None, plan_latency=False, act_scale=False, mfma_fp8=False):
         """base: another Engine -> shared-prefix engine (vp_create_shared): reuses the base engine's backbone (and
         context + neck when their parameters are identical) on the frame the base last processed.
         frames > 1: batched encoder (vp_create_batched) -- preprocess + backbone of `frames` cameras per pass, no head;
@@ -637,6 +688,8 @@ class Engine:
             pr |= VP_PLAN_LATENCY
         if act_scale:
             pr |= VP_ACT_SCALE
+        if mfma_fp8:
+            pr |= VP_MFMA_FP8
         self._base = base  # keeps the base engine alive as long as this one
         path = None if isinstance(weights, (bytes, bytearray, memoryview, np.ndarray)) else (os.fsencode(weights) if weights else b"")
         if frames != 1 or frame_index is not None:
@@ -765,6 +818,27 @@ class Engine:
     def set_act_scales(self, exps):
         e = np.ascontiguousarray(exps, dtype=np.int32)
         self._ck(self._lib.vp_set_act_scales(self._h, _ptr(e), int(e.size)))
+
+    # ---- e4m3 MFMA layers (engines created with mfma_fp8=True)
+    def calibrate_fp8(self, target_log2=0):
+        """vp_calibrate_fp8 over the resident frame: every fp8 layer's qexp so that absmax(input) * 2^-qexp lies in [2^(t-1), 2^t); 0 = 8."""
+        self._ck(self._lib.vp_calibrate_fp8(self._h, int(target_log2)))
+
+    def reset_fp8(self):
+        self._ck(self._lib.vp_reset_fp8(self._h))
+
+    def fp8_layers(self):
+        """[(launch index, input tensor index, qexp)] of the conv3x3_f8 launches, in plan order."""
+        n = self._lib.vp_fp8_layers(self._h, None, 0)
+        if n < 0:
+            raise ValueError("vp_fp8_layers: the engine was not created with VP_MFMA_FP8")
+        buf = (Fp8Layer * max(n, 1))()
+        self._lib.vp_fp8_layers(self._h, buf, n)
+        return [(buf[i].launch, buf[i].tensor, buf[i].qexp) for i in range(n)]
+
+    def set_fp8_exps(self, exps):
+        e = np.ascontiguousarray(exps, dtype=np.int32)
+        self._ck(self._lib.vp_set_fp8_exps(self._h, _ptr(e), int(e.size)))
 
     def infer_shared(self):
         """Run this shared-prefix engine's own layers on the frame its base engine processed last."""

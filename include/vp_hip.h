@@ -99,7 +99,12 @@ enum vp_precision { VP_FP16 = 0, VP_FP16X3 = 1,
                      * network kinds, VP_FP16, vp_create_shared* and vp_create_batched* return VP_ERR_ARG.  Every activation tensor t is stored as
                      * x * 2^-s_t; all s_t start at 0, and with all of them 0 the engine's launches and bits are the unflagged engine's.
                      * vp_calibrate_range chooses them, vp_set_act_scales installs a shipped table. */
-                    VP_ACT_SCALE = 64 };
+                    VP_ACT_SCALE = 64,
+                    /* OR-able flag: the e4m3 MFMA form of the big plain 3x3 layers (see FP8 MFMA ENGINES below).  With VP_FP16 only, alone or with
+                     * VP_PLAN_LATENCY, for VP_SCENESEG, VP_SCENE3D, VP_DOMAINSEG and VP_EGOLANES engines that own their whole network; VP_FP16X3,
+                     * VP_WEIGHTS_FP8, VP_ACT_SCALE, the other three kinds, vp_create_shared* and vp_create_batched* return VP_ERR_ARG and say which.
+                     * An engine without the flag is untouched: same plan, same bits. */
+                    VP_MFMA_FP8 = 128 };
 
 enum vp_pixel_format { VP_BGR8 = 0, VP_RGB8 = 1 };
 /* Plane order of the network input: BGR planes = middleware "common" backends (onnx_runtime_backend.cpp:47-57),
@@ -238,6 +243,40 @@ int vp_calibrate_range(vp_engine* e, int target_log2);
 int vp_reset_range(vp_engine* e);
 int vp_act_scales(const vp_engine* e, int* exps, int cap);   /* returns the tensor count */
 int vp_set_act_scales(vp_engine* e, const int* exps, int n);
+/* FP8 MFMA ENGINES (engines created with VP_FP16 | VP_MFMA_FP8).  The VP_FP16 engines are the non-parity configuration (judged by a 3e-2 regression
+ * bound and by the task scores of vp_metric, not by 1e-3); the flag moves their big plain 3x3 layers -- 3x3, stride 1, conv + bias + {GELU, none}, one
+ * input tensor, input channels a multiple of 64, output channels that pad to a multiple of 64 without waste, maps of H * W >= 12800 pixels (80 x 160 and
+ * larger) and, as measured, at least 512 input channels: decode_layer_5 of the scene decoders; decode_layer_7 / 9 fit the kernel but run faster on their
+ * fp16 kernels (profiles/f8_mfma.txt) and stay there -- onto v_mfma_scale_f32_32x32x64_f8f6f4 with e4m3 operands, the one fp8 MFMA that runs at twice
+ * the fp16 rate.  vp_layer_kernel reports "conv3x3_f8" for those launches; every other launch is the unflagged plan's.
+ * THE QUANTISATION RULE of such a layer (restated in numpy in tests/f8_cases.py):
+ *   activations: the stored fp16 value x of the input tensor becomes q = e4m3(x * 2^-qexp), qexp a per-layer integer in [-24, 24] (the scaling is
+ *     exact).  e4m3 is OCP e4m3fn (bias 7, maximum 448, subnormals down to 2^-9; not the fnuz encoding); rounding is to nearest, ties to even; every
+ *     finite or infinite value that would round above 448 gives +-448; NaN gives the NaN code (0x7f with the sign); zeros keep their sign.
+ *   weights: per output channel n the e4m3 codes of w / S_n and the fp32 row scale S_n = amax_n / 448 (1 for an all-zero row): what
+ *     vp_fp8_encode_rows returns (the packer of VP_WEIGHTS_FP8).
+ *   result: y_n = fl32(acc_n * fl32(S_n * 2^qexp)) + bias_n, acc_n the fp32 MFMA accumulator over the e4m3 products; then the layer's activation
+ *     and the engine's fp16 store.
+ * vp_calibrate_fp8: one eager pass over the RESIDENT frame (the walk of vp_range_survey); for every fp8 layer, in plan order and before the layer runs,
+ *   qexp is set so that absmax(input) * 2^-qexp lies in [2^(target_log2 - 1), 2^target_log2) -- target_log2 1 .. 8, 0 = 8 (1.75x headroom below 448),
+ *   clamped to [-24, 24].  An all-zero input keeps its qexp.  Later calls only RAISE (calibrate over several frames); vp_reset_fp8 puts every qexp back
+ *   to 0.  All qexp start at 0.  VP_ERR_STATE when nothing is resident.
+ * vp_fp8_layers: out[i], i < min(cap, count), for the i-th conv3x3_f8 launch in plan order; returns the count.
+ * vp_set_fp8_exps: installs a shipped table, one exponent per entry of vp_fp8_layers (VP_ERR_ARG if n differs or an exponent is outside [-24, 24]);
+ *   an installed exponent counts as measured.  Engines with equal tables give equal bits; vp_plan_hash does not change (exponents are data, not plan);
+ *   a changed exponent re-captures the graph on the next pass.
+ * All four return VP_ERR_ARG on an engine created without the flag. */
+typedef struct vp_fp8_layer {
+  int launch;   /* index of the launch (vp_layer_name / vp_layer_kernel) */
+  int tensor;   /* index of its input tensor (vp_tensor_info, vp_tensor_read, vp_range_survey) */
+  int qexp;
+} vp_fp8_layer;
+int vp_calibrate_fp8(vp_engine* e, int target_log2);
+int vp_reset_fp8(vp_engine* e);
+int vp_fp8_layers(const vp_engine* e, vp_fp8_layer* out, int cap);
+int vp_set_fp8_exps(vp_engine* e, const int* exps, int n);
+/* host only: codes[i] = the e4m3 code the rule above gives the fp16 bit pattern f16[i] under exponent qexp (|qexp| <= 24, else VP_ERR_ARG) */
+int vp_fp8_quantize_act(const uint16_t* f16, size_t n, int qexp, uint8_t* codes);
 /* RANGE SURVEY (any engine that owns its whole network: all seven kinds, VP_FP16 and VP_FP16X3, with or without VP_WEIGHTS_FP8 / VP_PLAN_LATENCY /
  * VP_ACT_SCALE).  vp_range_survey runs the plan eagerly, launch by launch, over the RESIDENT input -- the frame of the last vp_upload_frame / vp_infer,
  * the tensor of the last vp_infer_tensor / vp_detect_infer; AutoDrive: the pair vp_calibrate_range would run (an engine without VP_ACT_SCALE keeps no
@@ -1219,6 +1258,16 @@ int vp_op_rowpair_conv_scaled(int gpu_id, int precision, const float* in, int ci
 int vp_op_lane_rows_head_scaled(int gpu_id, int precision, const float* features, int cin, int h, int w, const float* c1_w, float c1_b, const float* c2_w,
                                 float c2_b, const float* h1_w, float h1_b, const float* h2_w, float h2_b, int in_exp, float* out_2xh, char* err,
                                 size_t err_len);
+
+/* ---- the e4m3 MFMA layer of VP_MFMA_FP8 engines (unit tests; not used by callers) ------------
+ * vp_op_conv3x3_f8: Conv2d 3x3 (stride 1, pad 1) + bias + act (0 none, 1 GELU) on conv3x3_f8_kernel under the activation exponent qexp (FP8 MFMA
+ *   ENGINES above) -- the engine's own packer and launch, whatever the map size.  in [cin][h][w] fp32 (rounded to fp16 first, as an engine stores it),
+ *   weight [cout][cin][3][3], bias [cout]; out_f16: the stored fp16 bit patterns [cout][h][w].  VP_ERR_ARG unless cin and cout, each rounded up to 32 as an engine
+ *   pads them, are multiples of 64 and the map is at least 8 x 16 pixels.
+ * vp_op_fp8_quantize: the kernel's quantiser (a device function) over an array of n fp16 bit patterns; equals vp_fp8_quantize_act bit for bit. */
+int vp_op_conv3x3_f8(int gpu_id, const float* in, int cin, int h, int w, const float* weight, const float* bias, int cout, int act, int qexp,
+                     uint16_t* out_f16, char* err, size_t err_len);
+int vp_op_fp8_quantize(int gpu_id, const uint16_t* f16, size_t n, int qexp, uint8_t* codes, char* err, size_t err_len);
 
 /* ---- the convolution forms the networks launch beyond vp_op_conv2d's (unit tests; not used by callers) ------------
  * vp_op_conv2d_forms: Conv2d ks x ks (pad ks / 2, stride 1 or 2: stride 2 needs ks == 3 and even h, w) + bias + act, then the residual (res_mode
