@@ -482,6 +482,38 @@ class Engine {
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
 };
 
+// The baseline JPEG of a device BGR8 picture (include/vp_hip.h "the picture as a baseline JPEG"; kernels: kernels_misc.hip jpeg_*).  The host half --
+// tables, header, bound -- needs no device.  JpegEncoder owns the device buffers of one user (a canvas, or one call of the operator entry) and grows
+// them once per geometry: coefficients, interval lengths / offsets, the scan data at its bound, the Huffman entries, one pinned word for the total.
+constexpr int kJpegDefaultRestart = 4;       // what restart_mcus = 0 selects (profiles/canvas_jpeg.txt)
+constexpr size_t kJpegHeaderBytes = 629;     // SOI 2, APP0 18, DQT 2 x 69, SOF0 19, DHT 33 + 183 + 33 + 183, DRI 6, SOS 14: every segment has a fixed length
+inline int jpeg_restart(int restart_mcus) { return restart_mcus == 0 ? kJpegDefaultRestart : restart_mcus; }
+void jpeg_quant_tables(int quality, uint8_t q[2][64]);                 // luminance, chrominance; row-major
+size_t jpeg_scan_bound(int h, int w, int restart_mcus);                // scan data alone, markers included
+inline size_t jpeg_bound(int h, int w, int restart_mcus) { return kJpegHeaderBytes + jpeg_scan_bound(h, w, restart_mcus) + 2; }
+void jpeg_write_header(int h, int w, int quality, int restart_mcus, uint8_t dst[kJpegHeaderBytes]);
+class JpegEncoder {
+ public:
+  JpegEncoder() = default;
+  ~JpegEncoder() { release(); }
+  JpegEncoder(const JpegEncoder&) = delete;
+  JpegEncoder& operator=(const JpegEncoder&) = delete;
+  // d_bgr: h x w (both even, 2 .. 16384), rows pitch >= frame_bgr_pitch(w) apart, complete in `st`'s order.  Queues the four launches on st, waits for
+  // the total, refuses a cap below the stream's size (std::invalid_argument naming it; *n = that size; dst beyond the header untouched), else copies the
+  // scan data behind the header and waits again.  The device must be current.
+  void encode(const uint8_t* d_bgr, int pitch, int h, int w, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n, const char* who, hipStream_t st);
+  void release();
+
+ private:
+  void grow(void** p, size_t* cap, size_t bytes, hipStream_t st);
+  int16_t* d_coef_ = nullptr;
+  uint32_t* d_len_ = nullptr;
+  uint8_t* d_out_ = nullptr;
+  uint32_t* d_huff_ = nullptr;
+  uint32_t* h_total_ = nullptr;
+  size_t coef_cap_ = 0, len_cap_ = 0, out_cap_ = 0;
+};
+
 // vp_canvas (include/vp_hip.h; handle: vp_handle.hpp; kernels: kernels_misc.hip canvas_*): one BGR8 picture per camera frame on the device.  begin()
 // copies a vp_frame's image; every engine, heads included, blends its mask or pastes its depth map into the region its input came from; the detector's
 // boxes are drawn on top; fetch() hands the picture out once, in any vp_frame format.  The blend and the depth pipeline are those of
@@ -513,6 +545,8 @@ class Canvas {
   void fetch(int format, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows, int n_planes);
   // the same for the picture resized to out_h x out_w (the integer bilinear of the preprocess path); the canvas's own picture is left as it is
   void fetch_resized(int format, int out_h, int out_w, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows, int n_planes);
+  // the picture (out_h = 0), or the resized picture of fetch_resized, as a baseline JPEG; arguments checked by the caller.  Two host waits (JpegEncoder).
+  void fetch_jpeg(int out_h, int out_w, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n);
   // vp_canvas_set_color (values checked by the caller): the standard and chroma rule of later fetches into the YUV formats and GRAY8
   void set_color(int matrix, int range, int chroma_mode) { matrix_ = matrix, range_ = range, chroma_mode_ = chroma_mode; }
   void get_color(int* matrix, int* range, int* chroma_mode) const { *matrix = matrix_, *range = range_, *chroma_mode = chroma_mode_; }
@@ -544,6 +578,7 @@ class Canvas {
   const uint8_t* stage_host(const void* src, size_t bytes);   // a caller's pageable array: copied before the call returns, then one H2D into d_umask_
   void fetch_picture(const uint8_t* d_bgr, int pitch, int h, int w, int format, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows,
                      int n_planes);
+  int resize_to_small(int out_h, int out_w);   // queues the resize into d_small_; the row pitch of the result
   template <class T>
   void grow(T*& p, size_t& cap, size_t bytes);
   int gpu_;
@@ -569,6 +604,7 @@ class Canvas {
   size_t h_umask_cap_ = 0;
   int umask_slot_ = 0;
   hipEvent_t umask_ev_[2] = {nullptr, nullptr};
+  JpegEncoder jpeg_;               // fetch_jpeg: buffers of its own, never touched by the other fetches
 };
 
 // vp_metric (include/vp_hip.h; handle: vp_handle.hpp; kernels: kernels_misc.hip metric_*): the validation scores of the segmentation and depth trainers,

@@ -766,6 +766,7 @@ void Canvas::release() {
   for (void* p : {(void*)d_bgr_, (void*)d_lut_, (void*)d_minmax_, (void*)d_depth_, (void*)d_out_, (void*)d_small_, (void*)d_umask_})
     if (p) (void)hipFree(p);
   if (h_umask_) (void)hipHostFree(h_umask_);
+  jpeg_.release();
   if (stream_) (void)hipStreamDestroy(stream_);
   stream_ = nullptr;
   ev_src_ = ev_read_ = umask_ev_[0] = umask_ev_[1] = nullptr;
@@ -1088,6 +1089,11 @@ void Canvas::fetch(int format, uint8_t* const* planes, const int* strides, const
 void Canvas::fetch_resized(int format, int out_h, int out_w, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows, int n_planes) {
   need_begun("vp_canvas_fetch_resized");
   VP_HIP_CHECK(hipSetDevice(gpu_));
+  const int pitch = resize_to_small(out_h, out_w);
+  fetch_picture(d_small_, pitch, out_h, out_w, format, planes, strides, row_bytes, rows, n_planes);
+}
+
+int Canvas::resize_to_small(int out_h, int out_w) {
   CanvasResizeParams q{};
   q.dst_pitch = frame_bgr_pitch(out_w);
   grow(d_small_, small_cap_, (size_t)out_h * q.dst_pitch);
@@ -1101,7 +1107,7 @@ void Canvas::fetch_resized(int format, int out_h, int out_w, uint8_t* const* pla
   q.out_h = out_h;
   q.out_w = out_w;
   VP_HIP_CHECK(launch_canvas_resize(q, stream_));
-  fetch_picture(d_small_, q.dst_pitch, out_h, out_w, format, planes, strides, row_bytes, rows, n_planes);
+  return q.dst_pitch;
 }
 
 void Canvas::fetch_picture(const uint8_t* d_bgr, int pitch, int h, int w, int format, uint8_t* const* planes, const int* strides, const size_t* row_bytes, const int* rows,
@@ -1133,6 +1139,196 @@ void Canvas::fetch_picture(const uint8_t* d_bgr, int pitch, int h, int w, int fo
       VP_HIP_CHECK(hipMemcpy2DAsync(planes[i], strides[i], dev[i], i ? ppc : pp, row_bytes[i], rows[i], hipMemcpyDeviceToHost, stream_));
   }
   VP_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+void Canvas::fetch_jpeg(int out_h, int out_w, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n) {
+  const char* who = out_h ? "vp_canvas_fetch_jpeg_resized" : "vp_canvas_fetch_jpeg";
+  need_begun(who);
+  VP_HIP_CHECK(hipSetDevice(gpu_));
+  if (out_h) {
+    const int pitch = resize_to_small(out_h, out_w);
+    jpeg_.encode(d_small_, pitch, out_h, out_w, quality, restart_mcus, dst, cap, n, who, stream_);
+  } else {
+    jpeg_.encode(d_bgr_, pitch_, h_, w_, quality, restart_mcus, dst, cap, n, who, stream_);
+  }
+}
+
+// -------------------------------------------------------------------------------------------------- baseline JPEG: the host half and the schedule
+namespace {
+// T.81 Annex K.1 / K.2, row-major
+constexpr uint8_t kJpegBaseQ[2][64] = {
+    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+constexpr uint8_t kJpegZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+// T.81 Annex K.3.3: BITS[1 .. 16] and HUFFVAL of tables K.3 (DC luminance), K.5 (AC luminance), K.4 (DC chrominance), K.6 (AC chrominance) -- the DHT order
+struct JpegHuffSpec {
+  uint8_t bits[16];
+  int n;
+  uint8_t vals[162];
+};
+const JpegHuffSpec kJpegHuff[4] = {
+    {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}},
+    {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D},
+     162,
+     {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xA1, 0x08, 0x23, 0x42, 0xB1,
+      0xC1, 0x15, 0x52, 0xD1, 0xF0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0A, 0x16, 0x17, 0x18, 0x19, 0x1A, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x34, 0x35, 0x36, 0x37,
+      0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A,
+      0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3,
+      0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3,
+      0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE1, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF1, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA}},
+    {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}},
+    {{0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77},
+     162,
+     {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xA1, 0xB1, 0xC1,
+      0x09, 0x23, 0x33, 0x52, 0xF0, 0x15, 0x62, 0x72, 0xD1, 0x0A, 0x16, 0x24, 0x34, 0xE1, 0x25, 0xF1, 0x17, 0x18, 0x19, 0x1A, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x35, 0x36,
+      0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
+      0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A,
+      0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA,
+      0xD2, 0xD3, 0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA}}};
+
+// the kernel's entries (code | length << 16, by symbol): [2][16] DC, then [2][256] AC; codes by T.81 Annex C
+const uint32_t* jpeg_huff_words() {
+  static const std::vector<uint32_t> words = [] {
+    std::vector<uint32_t> w(kJpegHuffWords, 0u);
+    for (int t = 0; t < 4; ++t) {
+      uint32_t* dst = w.data() + ((t & 1) ? 32 + 256 * (t >> 1) : 16 * (t >> 1));
+      unsigned code = 0;
+      int k = 0;
+      for (int len = 1; len <= 16; ++len) {
+        for (int i = 0; i < kJpegHuff[t].bits[len - 1]; ++i) dst[kJpegHuff[t].vals[k++]] = code++ | ((unsigned)len << 16);
+        code <<= 1;
+      }
+    }
+    return w;
+  }();
+  return words.data();
+}
+
+uint8_t* jpeg_put_segment(uint8_t* p, int marker, int payload) {   // the marker and the length; the payload follows
+  *p++ = 0xFF;
+  *p++ = (uint8_t)marker;
+  *p++ = (uint8_t)((payload + 2) >> 8);
+  *p++ = (uint8_t)((payload + 2) & 255);
+  return p;
+}
+}  // namespace
+
+void jpeg_quant_tables(int quality, uint8_t q[2][64]) {
+  const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  for (int t = 0; t < 2; ++t)
+    for (int i = 0; i < 64; ++i) q[t][i] = (uint8_t)std::min(std::max((kJpegBaseQ[t][i] * s + 50) / 100, 1), 255);
+}
+
+// Per MCU six blocks of at most 22 + 63 * 26 bits: the longest DC code (11 bits) + 11, and per AC position at most the longest code (16 bits) + 10 -- a ZRL
+// or an EOB is shorter than the coefficients it stands for.  That is 1245 whole bytes, so an interval's padding stays inside them; every byte may be
+// stuffed; + 2 per interval for its marker.
+size_t jpeg_scan_bound(int h, int w, int restart_mcus) {
+  const size_t n = (size_t)((h + 15) / 16) * ((w + 15) / 16), ri = (size_t)jpeg_restart(restart_mcus);
+  return n * 2 * (6 * (22 + 63 * 26) / 8) + 2 * ((n + ri - 1) / ri);
+}
+
+void jpeg_write_header(int h, int w, int quality, int restart_mcus, uint8_t dst[kJpegHeaderBytes]) {
+  uint8_t q[2][64];
+  jpeg_quant_tables(quality, q);
+  uint8_t* p = dst;
+  *p++ = 0xFF;
+  *p++ = 0xD8;
+  p = jpeg_put_segment(p, 0xE0, 14);
+  for (uint8_t b : {0x4A, 0x46, 0x49, 0x46, 0x00, 1, 1, 0, 0, 1, 0, 1, 0, 0}) *p++ = b;   // "JFIF\0", 1.01, no units, 1:1, no thumbnail
+  for (int t = 0; t < 2; ++t) {
+    p = jpeg_put_segment(p, 0xDB, 65);
+    *p++ = (uint8_t)t;
+    for (int i = 0; i < 64; ++i) *p++ = q[t][kJpegZigzag[i]];
+  }
+  p = jpeg_put_segment(p, 0xC0, 15);
+  for (int b : {8, h >> 8, h & 255, w >> 8, w & 255, 3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1}) *p++ = (uint8_t)b;
+  for (int t = 0; t < 4; ++t) {
+    p = jpeg_put_segment(p, 0xC4, 17 + kJpegHuff[t].n);
+    *p++ = (uint8_t)(((t & 1) << 4) | (t >> 1));
+    for (int i = 0; i < 16; ++i) *p++ = kJpegHuff[t].bits[i];
+    for (int i = 0; i < kJpegHuff[t].n; ++i) *p++ = kJpegHuff[t].vals[i];
+  }
+  const int ri = jpeg_restart(restart_mcus);
+  p = jpeg_put_segment(p, 0xDD, 2);
+  *p++ = (uint8_t)(ri >> 8);
+  *p++ = (uint8_t)(ri & 255);
+  p = jpeg_put_segment(p, 0xDA, 10);
+  for (uint8_t b : {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0}) *p++ = b;
+  if ((size_t)(p - dst) != kJpegHeaderBytes) throw std::logic_error("jpeg_write_header: the header's length");
+}
+
+void JpegEncoder::release() {
+  for (void* p : {(void*)d_coef_, (void*)d_len_, (void*)d_out_, (void*)d_huff_})
+    if (p) (void)hipFree(p);
+  if (h_total_) (void)hipHostFree(h_total_);
+  d_coef_ = nullptr;
+  d_len_ = nullptr;
+  d_out_ = nullptr;
+  d_huff_ = nullptr;
+  h_total_ = nullptr;
+  coef_cap_ = len_cap_ = out_cap_ = 0;
+}
+
+// as Canvas::grow: a buffer that has to grow is freed only once the stream's work has run
+void JpegEncoder::grow(void** p, size_t* cap, size_t bytes, hipStream_t st) {
+  if (bytes <= *cap) return;
+  VP_HIP_CHECK(hipStreamSynchronize(st));
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t n = (bytes + 255) & ~(size_t)255;
+  VP_HIP_CHECK(hipMalloc(p, n));
+  *cap = n;
+}
+
+void JpegEncoder::encode(const uint8_t* d_bgr, int pitch, int h, int w, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n, const char* who,
+                         hipStream_t st) {
+  const int ri = jpeg_restart(restart_mcus), mcus_x = (w + 15) / 16, n_mcus = mcus_x * ((h + 15) / 16), n_int = (n_mcus + ri - 1) / ri;
+  grow(reinterpret_cast<void**>(&d_coef_), &coef_cap_, (size_t)n_mcus * 6 * 64 * sizeof(int16_t), st);
+  grow(reinterpret_cast<void**>(&d_len_), &len_cap_, (size_t)n_mcus * sizeof(uint32_t), st);
+  grow(reinterpret_cast<void**>(&d_out_), &out_cap_, jpeg_scan_bound(h, w, 1), st);   // restart_mcus = 1 has the largest bound: one size per geometry
+  if (!d_huff_) {
+    VP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_huff_), kJpegHuffWords * sizeof(uint32_t)));
+    VP_HIP_CHECK(hipMemcpyAsync(d_huff_, jpeg_huff_words(), kJpegHuffWords * sizeof(uint32_t), hipMemcpyHostToDevice, st));   // the source is static
+  }
+  if (!h_total_) VP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_total_), 64, hipHostMallocDefault));
+  if (cap >= kJpegHeaderBytes) jpeg_write_header(h, w, quality, restart_mcus, dst);
+  JpegBlocksParams b{};
+  b.src = d_bgr;
+  b.src_pitch = pitch;
+  b.h = h;
+  b.w = w;
+  b.mcus_x = mcus_x;
+  b.n_mcus = n_mcus;
+  b.k = color_standard(VP_COLOR_BT601, VP_COLOR_RANGE_FULL).fwd;   // JFIF's standard, whatever vp_canvas_set_color says
+  jpeg_quant_tables(quality, b.q);
+  b.coef = d_coef_;
+  JpegEntropyParams e{};
+  e.coef = d_coef_;
+  e.huff = d_huff_;
+  e.n_mcus = n_mcus;
+  e.restart_mcus = ri;
+  e.n_intervals = n_int;
+  e.len = d_len_;
+  e.out = d_out_;
+  VP_HIP_CHECK(launch_jpeg_blocks(b, st));
+  VP_HIP_CHECK(launch_jpeg_entropy(e, false, st));
+  VP_HIP_CHECK(launch_jpeg_scan(d_len_, n_int, h_total_, st));
+  VP_HIP_CHECK(launch_jpeg_entropy(e, true, st));
+  VP_HIP_CHECK(hipStreamSynchronize(st));   // wait 1: the total
+  const size_t total = *h_total_, need = kJpegHeaderBytes + total + 2;
+  if (cap < need) {
+    *n = need;
+    throw std::invalid_argument(std::string(who) + ": the stream has " + std::to_string(need) + " bytes, cap is " + std::to_string(cap));
+  }
+  VP_HIP_CHECK(hipMemcpyAsync(dst + kJpegHeaderBytes, d_out_, total, hipMemcpyDeviceToHost, st));
+  VP_HIP_CHECK(hipStreamSynchronize(st));   // wait 2: the stream
+  dst[kJpegHeaderBytes + total] = 0xFF;
+  dst[kJpegHeaderBytes + total + 1] = 0xD9;
+  *n = need;
 }
 
 // -------------------------------------------------------------------------------------------------- vp_metric

@@ -242,6 +242,39 @@ struct CanvasResizeParams {
   int dst_pitch, out_h, out_w;
 };
 hipError_t launch_canvas_resize(const CanvasResizeParams& p, hipStream_t st);
+// The baseline JPEG of a BGR8 picture (include/vp_hip.h "the picture as a baseline JPEG" states the stream as the DEFINITION).  Three kernels:
+//   jpeg_blocks_kernel: a workgroup of 256 takes kJpegMcusPerGroup MCUs of 16 x 16 pixels in raster order.  Load: work-item (MCU, row pair, four-pixel
+//     block) reads its two rows through load_bgr4 and forms 8 luma samples and 2 mean chroma pairs by canvas_to_format_kernel's own device functions
+//     (luma_of / chroma_of / chroma_mean4 with k = color_standard(BT.601, full).fwd); sources beyond the picture are clamped per plane (Y: row h - 1 /
+//     column w - 1; chroma: row h / 2 - 1 / column w / 2 - 1).  The level-shifted samples go to LDS as int16 [block][8][8], blocks kJpegBlockPitch apart.
+//     Row pass: one work-item per (block, row), in place.  Column pass behind a barrier: one work-item per (block, column) forms F, quantises by
+//     q[table][row-major index] and puts the value at its zigzag position of a second LDS image; behind another barrier the image is copied out as
+//     16-byte words.  coef: int16 [MCU][6][64], MCUs in raster order, so the blocks of one restart interval are contiguous.
+//   jpeg_entropy_kernel<WRITE>: one restart interval per work-item, coded serially (a 64-bit bit accumulator; coefficients read as 16-byte words, the next
+//     block's eight loaded ahead, a word of eight zeros skipped as a run; the entries copied into LDS by each workgroup of 64).  WRITE false: len[i] = the interval's stuffed byte count + 2 for the RST marker behind it (none behind the last).
+//     WRITE true: the bytes at out + off[i], then the marker.  huff: [2][16] DC then [2][256] AC entries, code | length << 16.
+//   jpeg_scan_kernel: ONE workgroup of 256 turns len[0, n) into its exclusive prefix sum in place and stores the total in *total (a pinned word).
+constexpr int kJpegMcusPerGroup = 8;
+constexpr int kJpegBlockPitch = 72;    // int16 elements between the LDS images of two blocks: 64 + 8, still 16-byte aligned
+constexpr int kJpegHuffWords = 2 * 16 + 2 * 256;
+struct JpegBlocksParams {
+  const uint8_t* src;     // BGR8, rows src_pitch apart, every row readable up to 12 * ceil(w / 4) bytes
+  int src_pitch, h, w;    // h, w even
+  int mcus_x, n_mcus;
+  BgrToYuv k;             // color_standard(VP_COLOR_BT601, VP_COLOR_RANGE_FULL).fwd, whatever the canvas's own setting
+  uint8_t q[2][64];       // luminance, chrominance; row-major
+  int16_t* coef;          // [n_mcus][6][64], zigzag order
+};
+hipError_t launch_jpeg_blocks(const JpegBlocksParams& p, hipStream_t st);
+struct JpegEntropyParams {
+  const int16_t* coef;
+  const uint32_t* huff;   // kJpegHuffWords entries on the device
+  int n_mcus, restart_mcus, n_intervals;
+  uint32_t* len;          // [n_intervals]: written by the counting launch, scanned in place, read by the writing launch as offsets
+  uint8_t* out;           // the scan data (writing launch)
+};
+hipError_t launch_jpeg_entropy(const JpegEntropyParams& p, bool write, hipStream_t st);
+hipError_t launch_jpeg_scan(uint32_t* len, int n, uint32_t* total, hipStream_t st);
 // frame_remap_kernel: one BGR8 picture resampled through a per-pixel map (vp_frame's rectification: undistort, warp to the standard pose; include/vp_hip.h
 // states the sample as the DEFINITION).  A map entry is (X, Y), the source coordinates of a destination pixel in units of 1/32 pixel, both inside
 // [-2^20, 2^20 - 1]: ix = X >> 5, fx = X & 31 (likewise y); taps (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1) with the weights (32 - fx)(32 - fy),

@@ -939,6 +939,242 @@ __global__ __launch_bounds__(256) void canvas_to_format_kernel(const CanvasToFor
   }
 }
 
+// ------------------------------------------------------------------------------------------ vp_canvas: the picture as a baseline JPEG
+// kernels.hpp JpegBlocksParams / JpegEntropyParams; include/vp_hip.h states the stream.  One 8-point pass of the integer DCT:
+// out[k] = (sum_n M[k][n] x[n] + round) >> shift with M[k][n] = rne(2^13 s_k cos((2n + 1) k pi / 16)); fully unrolled, M becomes immediates.
+__device__ __forceinline__ void jpeg_dct8(const int x[8], int out[8], int round, int shift) {
+  constexpr int M[8][8] = {{2896, 2896, 2896, 2896, 2896, 2896, 2896, 2896},      {4017, 3406, 2276, 799, -799, -2276, -3406, -4017},
+                           {3784, 1567, -1567, -3784, -3784, -1567, 1567, 3784},  {3406, -799, -4017, -2276, 2276, 4017, 799, -3406},
+                           {2896, -2896, -2896, 2896, 2896, -2896, -2896, 2896},  {2276, -4017, 799, 3406, -3406, -799, 4017, -2276},
+                           {1567, -3784, 3784, -1567, -1567, 3784, -3784, 1567},  {799, -2276, 3406, -4017, 4017, -3406, 2276, -799}};
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    int s = round;
+#pragma unroll
+    for (int n = 0; n < 8; ++n) s += M[k][n] * x[n];
+    out[k] = s >> shift;
+  }
+}
+// luma_of in a register of its own, for the reason chroma_of pins V: four of them are packed into one word below.  Unpinned, the backend merges a pair of
+// shift-and-clamp steps into one v_ashr_pk_u8_i32 and ORs the other two samples into bits 16 .. 31 of its result, which it takes for zero; on the MI355X
+// they are not.
+__device__ __forceinline__ unsigned luma_pinned(const BgrToYuv& k, unsigned px) {
+  unsigned v = luma_of(k, px);
+  asm volatile("" : "+v"(v));
+  return v;
+}
+__global__ __launch_bounds__(256) void jpeg_blocks_kernel(const JpegBlocksParams p) {
+  constexpr int G = kJpegMcusPerGroup, BP = kJpegBlockPitch, NB = 6 * G;
+  __shared__ int4 lds_a[NB * BP / 8];   // samples, then the row pass in place
+  __shared__ int4 lds_b[NB * BP / 8];   // quantised coefficients in zigzag order
+  __shared__ int lds_q[128];
+  int16_t* sa = reinterpret_cast<int16_t*>(lds_a);
+  int16_t* sb = reinterpret_cast<int16_t*>(lds_b);
+  const int tid = threadIdx.x, mcu0 = (int)blockIdx.x * G;
+  if (tid < 128) lds_q[tid] = p.q[tid >> 6][tid & 63];
+  {   // load: MCU m, row pair r, four-pixel block j
+    const int m = tid >> 5, r = (tid >> 2) & 7, j = tid & 3, mcu = mcu0 + m;
+    if (mcu < p.n_mcus) {
+      const int my = mcu / p.mcus_x, mx = mcu - my * p.mcus_x;
+      const int gp = 8 * my + r, hp = p.h >> 1, gpc = min(gp, hp - 1);
+      const int jb = 4 * mx + j, jbc = min(jb, (p.w - 1) >> 2);
+      unsigned px[4], px1[4];
+      load_bgr4(p.src + (size_t)(2 * gpc) * p.src_pitch, jbc, px);
+      load_bgr4(p.src + (size_t)(2 * gpc + 1) * p.src_pitch, jbc, px1);
+      unsigned ya = 0u, yb = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        ya |= luma_pinned(p.k, px[k]) << (8 * k);
+        yb |= luma_pinned(p.k, px1[k]) << (8 * k);
+      }
+      if (gp >= hp) ya = yb;   // both rows lie below the picture: row h - 1 again
+      const unsigned c0 = chroma_mean4(chroma_of(p.k, px[0]), chroma_of(p.k, px[1]), chroma_of(p.k, px1[0]), chroma_of(p.k, px1[1]));
+      const unsigned c1 = chroma_mean4(chroma_of(p.k, px[2]), chroma_of(p.k, px[3]), chroma_of(p.k, px1[2]), chroma_of(p.k, px1[3]));
+      int16_t* yblk = sa + (6 * m + (r >= 4 ? 2 : 0) + (j >> 1)) * BP + ((2 * r) & 7) * 8 + (j & 1) * 4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int sx = min(4 * jb + k, p.w - 1) - 4 * jbc;   // 0 .. 3: the pixel of the loaded block this sample repeats
+        yblk[k] = (int16_t)((int)((ya >> (8 * sx)) & 255u) - 128);
+        yblk[8 + k] = (int16_t)((int)((yb >> (8 * sx)) & 255u) - 128);
+        if (!(k & 1)) {
+          const unsigned c = (sx >> 1) ? c1 : c0;
+          sa[(6 * m + 4) * BP + r * 8 + 2 * j + (k >> 1)] = (int16_t)((int)(c & 255u) - 128);
+          sa[(6 * m + 5) * BP + r * 8 + 2 * j + (k >> 1)] = (int16_t)((int)(c >> 8) - 128);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int u = tid; u < 8 * NB; u += 256) {   // rows: T[y][k] = (sum_n M[k][n] x[y][n] + 2^9) >> 10, in place
+    const int b = u >> 3, y = u & 7;
+    if (mcu0 + b / 6 >= p.n_mcus) continue;
+    int4* row = lds_a + (b * BP + y * 8) / 8;
+    const int4 v = *row;
+    const int x[8] = {(int16_t)v.x, v.x >> 16, (int16_t)v.y, v.y >> 16, (int16_t)v.z, v.z >> 16, (int16_t)v.w, v.w >> 16};
+    int t[8];
+    jpeg_dct8(x, t, 1 << 9, 10);
+    int4 o;
+    o.x = (t[0] & 0xFFFF) | (int)((unsigned)t[1] << 16);
+    o.y = (t[2] & 0xFFFF) | (int)((unsigned)t[3] << 16);
+    o.z = (t[4] & 0xFFFF) | (int)((unsigned)t[5] << 16);
+    o.w = (t[6] & 0xFFFF) | (int)((unsigned)t[7] << 16);
+    *row = o;
+  }
+  __syncthreads();
+  for (int u = tid; u < 8 * NB; u += 256) {   // columns: F[l][k] = (sum_m M[l][m] T[m][k] + 2^15) >> 16, quantised into its zigzag place
+    constexpr uint8_t kPlace[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
+                                    10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+    const int b = u >> 3, k = u & 7;
+    if (mcu0 + b / 6 >= p.n_mcus) continue;
+    const int* q = lds_q + (b % 6 >= 4 ? 64 : 0);
+    int x[8], f[8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) x[m] = sa[b * BP + m * 8 + k];
+    jpeg_dct8(x, f, 1 << 15, 16);
+#pragma unroll
+    for (int l = 0; l < 8; ++l) {
+      const int Q = q[l * 8 + k], a = (abs(f[l]) + (Q >> 1)) / Q;
+      int c = f[l] < 0 ? -a : a;
+      if (l | k) c = min(max(c, -1023), 1023);
+      sb[b * BP + kPlace[l * 8 + k]] = (int16_t)c;
+    }
+  }
+  __syncthreads();
+  int4* dst = reinterpret_cast<int4*>(p.coef) + (size_t)mcu0 * 48;
+  for (int u = tid; u < 8 * NB; u += 256)
+    if (mcu0 + (u >> 3) / 6 < p.n_mcus) dst[u] = lds_b[(u >> 3) * (BP / 8) + (u & 7)];
+}
+// One restart interval, coded serially (T.81 F.1.2).  The sink counts, or stores at dst: every byte that leaves the accumulator, a 0x00 behind each 0xFF.
+template <bool WRITE>
+struct JpegSink {
+  uint8_t* dst;
+  unsigned n;
+  unsigned long long acc;
+  int nb;
+  __device__ __forceinline__ void put(unsigned bits, int len) {   // len <= 26 on top of fewer than 8 pending bits
+    acc = (acc << len) | bits;
+    nb += len;
+    while (nb >= 8) {
+      const unsigned b = (unsigned)(acc >> (nb - 8)) & 255u;
+      nb -= 8;
+      if (WRITE) dst[n] = (uint8_t)b;
+      ++n;
+      if (b == 255u) {
+        if (WRITE) dst[n] = 0;
+        ++n;
+      }
+    }
+  }
+  __device__ __forceinline__ void symbol(unsigned entry, int v, int size) {   // a Huffman entry (code | length << 16), then the low `size` bits of v (v - 1 when negative)
+    const unsigned extra = (unsigned)(v < 0 ? v - 1 : v) & ((1u << size) - 1u);
+    put(((entry & 0xFFFFu) << size) | extra, (int)(entry >> 16) + size);
+  }
+};
+__device__ __forceinline__ int jpeg_size_of(int v) {
+  const unsigned a = (unsigned)abs(v);
+  return a ? 32 - __builtin_clz(a) : 0;
+}
+// `huff` is the workgroup's LDS copy of the entries.  The eight 16-byte words of the NEXT block are loaded before the current block is coded, so that a
+// work-item waits for memory once per block at the most, not once per word.
+template <bool WRITE>
+__device__ unsigned jpeg_code_interval(const int4* coef, int n_mcus, const uint32_t* huff, uint8_t* dst) {
+  JpegSink<WRITE> s{dst, 0u, 0ull, 0};
+  int pred_y = 0, pred_cb = 0, pred_cr = 0;
+  const int n_blocks = 6 * n_mcus;
+  int4 nxt[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) nxt[i] = coef[i];
+  for (int t = 0, b = 0; t < n_blocks; ++t, b = b == 5 ? 0 : b + 1) {
+    int4 w[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = nxt[i];
+    const int4* ahead = coef + (size_t)min(t + 1, n_blocks - 1) * 8;   // the last block once more: never past the interval
+#pragma unroll
+    for (int i = 0; i < 8; ++i) nxt[i] = ahead[i];
+    const int comp = b < 4 ? 0 : b - 3;
+    const uint32_t* dc = huff + (comp ? 16 : 0);
+    const uint32_t* ac = huff + 32 + (comp ? 256 : 0);
+    int run = 0;
+#pragma unroll
+    for (int wi = 0; wi < 8; ++wi) {
+      const int4 v = w[wi];
+      const int c[8] = {(int16_t)v.x, v.x >> 16, (int16_t)v.y, v.y >> 16, (int16_t)v.z, v.z >> 16, (int16_t)v.w, v.w >> 16};
+      if (wi == 0) {
+        const int d = c[0] - (comp == 0 ? pred_y : (comp == 1 ? pred_cb : pred_cr)), size = jpeg_size_of(d);
+        if (comp == 0) pred_y = c[0];
+        if (comp == 1) pred_cb = c[0];
+        if (comp == 2) pred_cr = c[0];
+        s.symbol(dc[size], d, size);
+      }
+      if (((wi == 0 ? v.x & (int)0xFFFF0000u : v.x) | v.y | v.z | v.w) == 0) {
+        run += wi == 0 ? 7 : 8;
+        continue;
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (wi == 0 && e == 0) continue;
+        if (c[e] == 0) {
+          ++run;
+          continue;
+        }
+        while (run > 15) {
+          s.put(ac[0xF0] & 0xFFFFu, (int)(ac[0xF0] >> 16));
+          run -= 16;
+        }
+        const int size = jpeg_size_of(c[e]);
+        s.symbol(ac[(run << 4) | size], c[e], size);
+        run = 0;
+      }
+    }
+    if (run > 0) s.put(ac[0] & 0xFFFFu, (int)(ac[0] >> 16));
+  }
+  if (s.nb > 0) s.put((1u << (8 - s.nb)) - 1u, 8 - s.nb);
+  return s.n;
+}
+template <bool WRITE>
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(const JpegEntropyParams p) {
+  __shared__ uint32_t lds_huff[kJpegHuffWords];
+  for (int k = threadIdx.x; k < kJpegHuffWords; k += 64) lds_huff[k] = p.huff[k];
+  __syncthreads();
+  const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  if (i >= p.n_intervals) return;
+  const int first = i * p.restart_mcus, n = min(p.restart_mcus, p.n_mcus - first);
+  const int4* coef = reinterpret_cast<const int4*>(p.coef) + (size_t)first * 48;
+  const bool marker = i + 1 < p.n_intervals;
+  if (WRITE) {
+    uint8_t* dst = p.out + p.len[i];
+    const unsigned bytes = jpeg_code_interval<true>(coef, n, lds_huff, dst);
+    if (marker) {
+      dst[bytes] = 0xFF;
+      dst[bytes + 1] = (uint8_t)(0xD0 + (i & 7));
+    }
+  } else {
+    p.len[i] = jpeg_code_interval<false>(coef, n, lds_huff, nullptr) + (marker ? 2u : 0u);
+  }
+}
+// len[0, n) -> its exclusive prefix sum, in place; *total = the sum.  One workgroup: a chunk per work-item, the 256 chunk sums scanned through LDS.
+__global__ __launch_bounds__(256) void jpeg_scan_kernel(uint32_t* len, int n, uint32_t* total) {
+  __shared__ unsigned part[2][256];
+  const int tid = threadIdx.x, chunk = (n + 255) / 256, lo = min(n, tid * chunk), hi = min(n, lo + chunk);
+  unsigned sum = 0u;
+  for (int i = lo; i < hi; ++i) sum += len[i];
+  part[0][tid] = sum;
+  __syncthreads();
+  int cur = 0;
+  for (int d = 1; d < 256; d <<= 1) {
+    part[cur ^ 1][tid] = part[cur][tid] + (tid >= d ? part[cur][tid - d] : 0u);
+    cur ^= 1;
+    __syncthreads();
+  }
+  unsigned at = part[cur][tid] - sum;
+  for (int i = lo; i < hi; ++i) {
+    const unsigned l = len[i];
+    len[i] = at;
+    at += l;
+  }
+  if (tid == 255) *total = part[cur][255];
+}
+
 // ----------------------------------------------------------------------------------- layout conversions
 // fp32 NCHW (host-visible test/debug format) <-> NHWC activation.
 __global__ __launch_bounds__(256) void nchw_to_act_kernel(const float* src, int Creal, ActView a) {
@@ -1225,6 +1461,26 @@ hipError_t launch_canvas_to_format(const CanvasToFormatParams& q, hipStream_t st
   }
   const long long n = (long long)(f420 ? p.h / 2 : p.h) * ((p.w + 3) / 4);
   VP_LAUNCH(canvas_to_format_kernel, dim3(nblk(n)), dim3(256), 0, st, p);
+}
+hipError_t launch_jpeg_blocks(const JpegBlocksParams& p, hipStream_t st) {
+  if (!p.src || !p.coef || p.h < 2 || p.w < 2 || p.h > 16384 || p.w > 16384 || ((p.h | p.w) & 1) || p.src_pitch < frame_bgr_pitch(p.w) || (p.src_pitch & 3) ||
+      p.mcus_x != (p.w + 15) / 16 || p.n_mcus != p.mcus_x * ((p.h + 15) / 16) || ((reinterpret_cast<uintptr_t>(p.src) & 3) | (reinterpret_cast<uintptr_t>(p.coef) & 15)))
+    return hipErrorInvalidValue;
+  for (int i = 0; i < 128; ++i)
+    if (p.q[i >> 6][i & 63] == 0) return hipErrorInvalidValue;
+  VP_LAUNCH(jpeg_blocks_kernel, dim3((unsigned)((p.n_mcus + kJpegMcusPerGroup - 1) / kJpegMcusPerGroup)), dim3(256), 0, st, p);
+}
+hipError_t launch_jpeg_entropy(const JpegEntropyParams& p, bool write, hipStream_t st) {
+  if (!p.coef || !p.huff || !p.len || (write && !p.out) || p.n_mcus < 1 || p.restart_mcus < 1 || p.restart_mcus > 65535 ||
+      p.n_intervals != (p.n_mcus + p.restart_mcus - 1) / p.restart_mcus || (reinterpret_cast<uintptr_t>(p.coef) & 15))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((p.n_intervals + 63) / 64));
+  if (write) VP_LAUNCH(jpeg_entropy_kernel<true>, grid, dim3(64), 0, st, p);
+  VP_LAUNCH(jpeg_entropy_kernel<false>, grid, dim3(64), 0, st, p);
+}
+hipError_t launch_jpeg_scan(uint32_t* len, int n, uint32_t* total, hipStream_t st) {
+  if (!len || !total || n < 1) return hipErrorInvalidValue;
+  VP_LAUNCH(jpeg_scan_kernel, dim3(1), dim3(256), 0, st, len, n, total);
 }
 hipError_t launch_nchw_to_act(const float* src, int Creal, const ActView& a, hipStream_t st) {
   VP_LAUNCH(nchw_to_act_kernel, dim3(nblk((long long)a.H * a.W * a.C)), dim3(256), 0, st, src, Creal, a);

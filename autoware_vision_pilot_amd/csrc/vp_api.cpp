@@ -1402,6 +1402,33 @@ int vp_canvas_fetch_resized(vp_canvas* c, int format, int out_h, int out_w, uint
   });
 }
 
+// the refusals every JPEG entry shares: the geometry's are the I420 fetch's own, with its texts
+static void check_jpeg_args(const char* who, int h, int w, int quality, int restart_mcus) {
+  const std::string me(who);
+  if (quality < 1 || quality > 100) throw std::invalid_argument(me + ": quality " + std::to_string(quality) + " (1 .. 100)");
+  if (restart_mcus < 0 || restart_mcus > 65535)
+    throw std::invalid_argument(me + ": restart_mcus " + std::to_string(restart_mcus) + " (1 .. 65535, or 0 for the default " + std::to_string(vp::kJpegDefaultRestart) + ")");
+  (void)frame_layout(me, VP_FRAME_I420, h, w);
+}
+
+int vp_canvas_fetch_jpeg(vp_canvas* c, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (!dst || !n) throw std::invalid_argument("vp_canvas_fetch_jpeg: null dst / n");
+    if (!g.begun()) throw std::runtime_error("vp_canvas_fetch_jpeg: the canvas holds no picture (vp_canvas_begin first)");
+    check_jpeg_args("vp_canvas_fetch_jpeg", g.h(), g.w(), quality, restart_mcus);
+    g.fetch_jpeg(0, 0, quality, restart_mcus, dst, cap, n);
+  });
+}
+
+int vp_canvas_fetch_jpeg_resized(vp_canvas* c, int out_h, int out_w, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n) {
+  return canvas_guarded(c, [&](vp::Canvas& g) {
+    if (!dst || !n) throw std::invalid_argument("vp_canvas_fetch_jpeg_resized: null dst / n");
+    if (!g.begun()) throw std::runtime_error("vp_canvas_fetch_jpeg_resized: the canvas holds no picture (vp_canvas_begin first)");
+    check_jpeg_args("vp_canvas_fetch_jpeg_resized", out_h, out_w, quality, restart_mcus);
+    g.fetch_jpeg(out_h, out_w, quality, restart_mcus, dst, cap, n);
+  });
+}
+
 int vp_sync(vp_engine* e) {
   return guarded(e, [&](vp::Engine& g) { g.sync(); });
 }
@@ -2869,6 +2896,45 @@ int vp_op_remap_bgr8(int gpu_id, const uint8_t* src, int src_h, int src_w, int s
     g.copy_d2h(back.data(), d_dst, dst_bytes);
     const size_t row = (size_t)(dst_stride >= pitch ? pitch : 3 * out_w);
     for (int y = 0; y < out_h; ++y) std::memcpy(dst + (size_t)y * dst_stride, back.data() + (size_t)y * pitch, row);
+  });
+}
+
+// ---- the canvas's JPEG encoder on a host picture, and its host half (no device)
+int vp_op_jpeg_encode_bgr8(int gpu_id, const uint8_t* bgr, int h, int w, int stride, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n, char* err,
+                           size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!bgr || !dst || !n) throw std::invalid_argument("vp_op_jpeg_encode_bgr8: null bgr / dst / n");
+    check_jpeg_args("vp_op_jpeg_encode_bgr8", h, w, quality, restart_mcus);
+    if (stride < 3 * w) throw std::invalid_argument("vp_op_jpeg_encode_bgr8: stride " + std::to_string(stride) + " is below the row's " + std::to_string(3 * w) + " bytes");
+    vp::Engine g(-1, nullptr, VP_FP16X3, gpu_id);
+    const int pitch = vp::frame_bgr_pitch(w);
+    uint8_t* d_src = reinterpret_cast<uint8_t*>(g.alloc_f32((size_t)h * pitch / 4));
+    std::vector<uint8_t> rows((size_t)h * pitch, 0);   // the canvas's own layout: bytes behind a row's end are 0
+    for (int y = 0; y < h; ++y) std::memcpy(rows.data() + (size_t)y * pitch, bgr + (size_t)y * stride, (size_t)3 * w);
+    g.copy_h2d(d_src, rows.data(), rows.size());
+    vp::JpegEncoder enc;
+    enc.encode(d_src, pitch, h, w, quality, restart_mcus, dst, cap, n, "vp_op_jpeg_encode_bgr8", g.stream());
+  });
+}
+
+int vp_jpeg_bound(int h, int w, int restart_mcus, size_t* bytes, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!bytes) throw std::invalid_argument("vp_jpeg_bound: null bytes");
+    check_jpeg_args("vp_jpeg_bound", h, w, 100, restart_mcus);
+    *bytes = vp::jpeg_bound(h, w, restart_mcus);
+  });
+}
+
+int vp_jpeg_header(int h, int w, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n, char* err, size_t err_len) {
+  return op_guarded(err, err_len, [&] {
+    if (!dst || !n) throw std::invalid_argument("vp_jpeg_header: null dst / n");
+    check_jpeg_args("vp_jpeg_header", h, w, quality, restart_mcus);
+    if (cap < vp::kJpegHeaderBytes) {
+      *n = vp::kJpegHeaderBytes;
+      throw std::invalid_argument("vp_jpeg_header: the header has " + std::to_string(vp::kJpegHeaderBytes) + " bytes, cap is " + std::to_string(cap));
+    }
+    vp::jpeg_write_header(h, w, quality, restart_mcus, dst);
+    *n = vp::kJpegHeaderBytes;
   });
 }
 

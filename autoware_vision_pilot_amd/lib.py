@@ -201,6 +201,11 @@ _SIGS = {
     "vp_canvas_draw_points": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "vp_canvas_draw_lane_rows": (C.c_int, [_P, _P]),
     "vp_canvas_fetch_resized": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(C.c_int), C.c_int]),
+    "vp_canvas_fetch_jpeg": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vp_canvas_fetch_jpeg_resized": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vp_jpeg_bound": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
+    "vp_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
+    "vp_op_jpeg_encode_bgr8": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
     "vp_metric_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "vp_metric_destroy": (None, [_P]),
     "vp_metric_last_error": (C.c_char_p, [_P]),
@@ -1288,6 +1293,44 @@ def canvas_layout3(fmt, h, w):
     return [(rb[i], rows[i]) for i in range(n.value)]
 
 
+def _op_raise(entry, rc, err):
+    raise (ValueError if rc == -1 else VpError)(f"{entry} failed ({rc}): {err.value.decode(errors='replace')}")
+
+
+def jpeg_bound(h, w, restart_mcus=0):
+    """vp_jpeg_bound (host only): a buffer size that holds the JPEG of any h x w picture at `restart_mcus`"""
+    n, err = C.c_size_t(), C.create_string_buffer(512)
+    rc = load().vp_jpeg_bound(int(h), int(w), int(restart_mcus), C.byref(n), err, len(err))
+    if rc != 0:
+        _op_raise("vp_jpeg_bound", rc, err)
+    return n.value
+
+
+def jpeg_header(h, w, quality=90, restart_mcus=0):
+    """vp_jpeg_header (host only): the stream's first 629 bytes, SOI through SOS"""
+    buf, n, err = np.empty(1024, np.uint8), C.c_size_t(), C.create_string_buffer(512)
+    rc = load().vp_jpeg_header(int(h), int(w), int(quality), int(restart_mcus), _ptr(buf), buf.size, C.byref(n), err, len(err))
+    if rc != 0:
+        _op_raise("vp_jpeg_header", rc, err)
+    return buf[:n.value].tobytes()
+
+
+def jpeg_encode(bgr, quality=90, restart_mcus=0, cap=None, gpu_id=0):
+    """vp_op_jpeg_encode_bgr8: the baseline JPEG (bytes) of bgr (uint8 [h][w][3]; a view with its own row stride is passed as it is), encoded on the
+    device.  cap: the size of the buffer offered (default: jpeg_bound)."""
+    bgr = np.asarray(bgr)
+    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3 or bgr.strides[2] != 1 or bgr.strides[1] != 3 or bgr.strides[0] < 0:
+        bgr = np.ascontiguousarray(bgr, dtype=np.uint8)
+    h, w = bgr.shape[:2]
+    n, err = C.c_size_t(), C.create_string_buffer(512)
+    buf = np.empty(max(1, jpeg_bound(h, w, restart_mcus) if cap is None else int(cap)), np.uint8)
+    rc = load().vp_op_jpeg_encode_bgr8(gpu_id, C.c_void_p(bgr.ctypes.data), h, w, int(bgr.strides[0]), int(quality), int(restart_mcus), _ptr(buf), buf.size,
+                                       C.byref(n), err, len(err))
+    if rc != 0:
+        _op_raise("vp_op_jpeg_encode_bgr8", rc, err)
+    return buf[:n.value].tobytes()
+
+
 class Canvas:
     """vp_canvas: one picture per camera frame, composed on the device.  begin(frame) copies the Frame's BGR8 picture; every Engine (heads included)
     blends its mask or pastes its depth map into the region its input came from; detections are drawn as boxes; overlay_lanes draws an EgoLanes
@@ -1433,6 +1476,22 @@ class Canvas:
         if f <= VP_FRAME_RGBA8:
             planes[0] = planes[0].reshape(h, w, _FRAME_PX_BYTES[f])
         return planes[0] if len(planes) == 1 else tuple(planes)
+
+    def fetch_jpeg(self, quality=90, restart_mcus=0, size=None):
+        """vp_canvas_fetch_jpeg (synchronous): the picture as a baseline JPEG (bytes; JFIF, 4:2:0), encoded on the device -- what
+        cv2.VideoWriter(.., "MJPG").write(frame) makes on the host.  `size` = (out_h, out_w): vp_canvas_fetch_jpeg_resized, the picture resized on the
+        device first.  Fetched into jpeg_bound bytes of fresh address space, of which only the stream's bytes are touched."""
+        try:
+            h, w = self.hw() if size is None else (int(size[0]), int(size[1]))
+            cap = jpeg_bound(h, w, restart_mcus)
+        except (ValueError, VpError):
+            h, w, cap = 0, 0, 1024   # no picture or no such geometry: the library words the refusal
+        buf, n = np.empty(cap, np.uint8), C.c_size_t()
+        if size is None:
+            self._ck(self._lib.vp_canvas_fetch_jpeg(self._h, int(quality), int(restart_mcus), _ptr(buf), buf.size, C.byref(n)))
+        else:
+            self._ck(self._lib.vp_canvas_fetch_jpeg_resized(self._h, int(size[0]), int(size[1]), int(quality), int(restart_mcus), _ptr(buf), buf.size, C.byref(n)))
+        return buf[:n.value].tobytes()
 
 
 class Metric:

@@ -667,6 +667,41 @@ int vp_rectify_homography(const vp_camera_pose* inference, const vp_camera_pose*
  *   beyond the fetch itself: the once-per-geometry ones of the ORDERING CONTRACT (the second picture growing, the first use of a tap table).
  * vp_canvas_device / vp_canvas_sync: the device picture (BGR8, rows *pitch_bytes apart) for a device consumer such as an encoder; complete after
  *   vp_canvas_sync, valid until the next vp_canvas_begin or vp_canvas_destroy.
+ * THE PICTURE AS A BASELINE JPEG, encoded on the device (vp_canvas_fetch_jpeg*, vp_op_jpeg_encode_bgr8): what a visualisation script's
+ *   cv2.VideoWriter(.., fourcc "MJPG").write(frame) makes on a host thread, so that a fetch moves the compressed stream instead of the picture.  The
+ *   rules below ARE the definition: for a given (picture, quality, Ri) the bytes are a pure function of the input, the same on every call, and
+ *   tests/jpeg_ref.py restates them in numpy.  Baseline sequential DCT (ITU-T T.81, SOF0), 8 bits, three components, 4:2:0, JFIF 1.01.
+ *   SAMPLES.  The Y, Cb, Cr planes are exactly the bytes vp_canvas_fetch(VP_FRAME_I420) gives under (VP_COLOR_BT601, VP_COLOR_RANGE_FULL, VP_CHROMA_MEAN)
+ *   -- JFIF's YCbCr -- whatever vp_canvas_set_color says (the same device functions form them).  w and h are even, 2 .. 16384: the I420 fetch's
+ *   refusals, with its texts.  The MCU is 16 x 16 pixels, the grid ceil(w / 16) x ceil(h / 16) MCUs in raster order; samples beyond the picture repeat
+ *   the last column / row of their plane (Y and chroma each on their own); an MCU holds six 8 x 8 blocks in the order Y00 Y01 Y10 Y11 Cb Cr;
+ *   x = sample - 128.
+ *   FORWARD DCT, integer.  M[k][n] = rne(2^13 s_k cos((2n + 1) k pi / 16)) with s_0 = 1 / (2 sqrt 2), s_k = 1 / 2 otherwise, formed in double (2896 for
+ *   k = 0, M[1][0] = 4017, |M| <= 4017).  Rows: T[y][k] = (sum_n M[k][n] x[y][n] + 2^9) >> 10; columns: F[l][k] = (sum_m M[l][m] T[m][k] + 2^15) >> 16;
+ *   arithmetic shifts, int32 sums (|T| <= 2896, column sums below 2^26; |F - the exact orthonormal DCT| <= 0.65 on the random and extreme blocks of
+ *   tests/test_jpeg_host.py, whose bound is 1).
+ *   QUANTISATION.  T.81 Annex K.1 (luminance) and K.2 (chrominance), scaled by quality q in 1 .. 100 as libjpeg does: s = q < 50 ? 5000 / q : 200 - 2 q
+ *   (integer division), Q = clamp((base * s + 50) / 100, 1, 255); c = sign(F) * ((|F| + (Q >> 1)) / Q).  AC values are clamped to +-1023 (never reached:
+ *   tests/test_jpeg_host.py shows it from M's row sums).  Coefficients are taken in zigzag order.
+ *   ENTROPY CODING (T.81 F.1.2) with the four typical Huffman tables of Annex K.3.3 (K.3 .. K.6): luminance DC 0 / AC 0, both chroma components DC 1 /
+ *   AC 1.  DC: the difference to the previous block of the same component, predictor 0 at the start of every restart interval; the category's code, then
+ *   SSSS low bits (a negative value sends v - 1).  AC: (run, size) symbols, ZRL = 0xF0, EOB = 0x00 only when the block ends in zeros.  Bits MSB first, a
+ *   0x00 stuffed behind every 0xFF data byte, each interval padded to a byte boundary with 1-bits.
+ *   RESTART INTERVALS.  restart_mcus (Ri) 1 .. 65535 MCUs in raster order; between interval i and i + 1 the marker RST(i mod 8), none behind the last.
+ *   restart_mcus = 0 selects the default, 4 (profiles/canvas_jpeg.txt: the fastest of 1, 2, 4, 8 whose size stays within 5 % of Ri = 8).  An interval is
+ *   what one work-item of the entropy kernel codes, so Ri trades parallelism against marker bytes.
+ *   LAYOUT.  SOI; APP0 "JFIF\0" (1.01, units 0, density 1:1, no thumbnail); DQT table 0, DQT table 1 (8-bit, zigzag); SOF0 (precision 8, h, w,
+ *   {1: 2x2 Tq 0, 2: 1x1 Tq 1, 3: 1x1 Tq 1}); four DHT (DC 0, AC 0, DC 1, AC 1); DRI (always); SOS (Ss 0, Se 63, Ah / Al 0); scan data; EOI.  The
+ *   header, SOI through SOS, has 629 bytes whatever the arguments.
+ *   vp_canvas_fetch_jpeg: synchronous; the stream into dst [cap], its length in *n.  The canvas is unchanged: later draws and fetches see the same
+ *   picture.  The header is written on the host straight into dst; the scan is coded on the device behind the canvas's stream order.  Host waits: two,
+ *   one for the scan's length and one for its bytes (beyond them the once-per-geometry ones of the ORDERING CONTRACT: the encoder's buffers growing).
+ *   VP_ERR_ARG with text: null dst / n, quality outside 1 .. 100, restart_mcus outside 0 .. 65535, the geometry refusals above, and a cap below the
+ *   stream's length -- decided before any byte of dst beyond the header is written; the text names the length and *n receives it (the one thing a
+ *   refused call stores).  vp_jpeg_bound answers a cap that always suffices.  VP_ERR_STATE before the first vp_canvas_begin.
+ *   vp_canvas_fetch_jpeg_resized: the JPEG of the second picture vp_canvas_fetch_resized forms (out_h, out_w even, 2 .. 16384): the production display's
+ *   1280 x 720.  vp_op_jpeg_encode_bgr8 (declared with the operator entries below) is the same encoder on a host picture, without frame or canvas.
+ *   Not built: 4:4:4 / 4:2:2 / grey, per-picture Huffman tables, progressive mode, a decoder; an MJPG / AVI container is a few host bytes per frame.
  * ORDERING CONTRACT (vp_frame's, in the other direction).  Nothing waits on the host before vp_canvas_fetch / vp_canvas_sync.  A draw call makes the
  *   canvas's stream wait for the work queued on the engine's stream so far, and the engine's stream wait for the canvas's read of the mask / logits
  *   before anything queued on it afterwards: `infer A; blend; infer B; fetch` shows A's mask.  The exceptions are once per geometry: a buffer that
@@ -697,6 +732,12 @@ int vp_canvas_overlay_lanes(vp_canvas* c, vp_engine* egolanes, float threshold);
 int vp_canvas_draw_points(vp_canvas* c, const int* xy, int n, int radius, const uint8_t* bgr);
 int vp_canvas_draw_lane_rows(vp_canvas* c, vp_engine* autosteer);
 int vp_canvas_fetch_resized(vp_canvas* c, int format, int out_h, int out_w, uint8_t* const* planes, const int* strides, int n_planes);
+int vp_canvas_fetch_jpeg(vp_canvas* c, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n);
+int vp_canvas_fetch_jpeg_resized(vp_canvas* c, int out_h, int out_w, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n);
+/* host only, no device: an upper bound of the stream's length for (h, w, restart_mcus) -- 629 + 2 + 2490 bytes per MCU (six blocks of at most
+ * 22 + 63 * 26 bits, every byte stuffed) + 2 per interval -- and the header, SOI through SOS (629 bytes into dst [cap], *n = 629).  Refusals as above. */
+int vp_jpeg_bound(int h, int w, int restart_mcus, size_t* bytes, char* err, size_t err_len);
+int vp_jpeg_header(int h, int w, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n, char* err, size_t err_len);
 
 /* ---- vp_metric: the reference's validation scores, computed on the device, one small record per frame -----------------------------
  * The reference qualifies its runtimes by task score: the IoU of SceneSegTrainer.calc_IoU_val / IoU (Models/training/scene_seg_trainer.py:206-244,
@@ -1334,6 +1375,11 @@ int vp_op_upconv(int gpu_id, const float* in, int cin, int h, int w, const float
  * writes behind each row's end (zeros).  The device destination is filled with 0xFF before the launch.  Sizes 1 .. 16384 each way. */
 int vp_op_remap_bgr8(int gpu_id, const uint8_t* src, int src_h, int src_w, int src_stride, const int16_t* xy, const uint16_t* frac, int out_h, int out_w,
                      int border, uint8_t* dst, int dst_stride, char* err, size_t err_len);
+/* vp_op_jpeg_encode_bgr8: the encoder of vp_canvas_fetch_jpeg (vp_canvas, "THE PICTURE AS A BASELINE JPEG") on a host BGR8 picture bgr [h][w][3], rows
+ * stride >= 3 * w bytes apart; needs no frame and no canvas.  The stream into dst [cap], its length in *n; refusals and the cap rule as there, the text in
+ * err. */
+int vp_op_jpeg_encode_bgr8(int gpu_id, const uint8_t* bgr, int h, int w, int stride, int quality, int restart_mcus, uint8_t* dst, size_t cap, size_t* n,
+                           char* err, size_t err_len);
 
 /* ---- developer options ------------------------------------------------------------------------------------
  * The library NEVER reads the environment.  The dispatch rules' developer knobs (A/B timing of a kernel against the one it replaced,
